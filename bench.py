@@ -18,6 +18,13 @@ all_gather_into_tensor + index_copy_ instead.
 The timed region starts with scene, seeds and framebuffer resident in HBM and is bracketed by
 barrier + torch.cuda.synchronize(); the time is the max over ranks.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times --steps steps and prints the line (with "roofline" and "roofline_valu", which
+take no run of their own).  --full adds every side run and check after the timed region: "frame_matches_n1",
+"exchange_ms" (N > 1), "other_variant", "configs" and "cpu_baseline".  --dump-outputs DIR writes the frame of the
+timed region's last step (DIR/frame.npy, float32, width*height x 4, as read_frame returns it) and, at N = 1, the
+LCG states (DIR/rnds.npy, int32 values as float64); above 64 MB in all, a fixed seeded sample of pixels of both,
+with DIR/pixel_index.npy.  The inputs (scene, seeds) are the same in every run with the same arguments.
+
 Extra objects:
   "roofline"       SURVEY 8(d)'s algorithmic HBM bytes of the kernel that runs / HIP-event kernel time vs
                    the 8 TB/s peak.  Megakernel (default): 40 B/sample (colors 16 B R + 16 B W, rnds 4 B R +
@@ -82,7 +89,26 @@ def parse():
     ap.add_argument("--no-band-check", action="store_true", help="skip the one-rank band render that proves the frame equals an N = 1 render")
     ap.add_argument("--no-configs", action="store_true", help="skip the side runs of BASELINE configs 1, 3, 4 (N = 1) and 5")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the band check, the exchange alone, the other variant, the other configs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed region's frame (and LCG states at N = 1) to DIR/*.npy")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6 - 4096   # 64 MB in all, less room for the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """Per-pixel arrays (rows = pixels, same row count) -> path/<name>.npy.  Past the budget, the same fixed seeded
+    sample of rows from every array, and the sampled pixel ids as pixel_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    if n * row_bytes > DUMP_BUDGET_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BUDGET_BYTES // (row_bytes + 8), replace=False))
+        arrays = dict({k: a[idx] for k, a in arrays.items()}, pixel_index=idx.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def cpu_baseline(width, height, bounces, target_s):
@@ -106,6 +132,8 @@ def cpu_baseline(width, height, bounces, target_s):
     osc = O.load_scene(spec)
     cam = O.make_camera(spec.fov, spec.yaw, spec.pitch, spec.shift, width, height)
     cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():      # where set, the job's share of a host shared with others
+        cores = max(1, min(cores, int(os.environ["OMP_NUM_THREADS"])))
     # calibrate on a 1/16-area strip: rows [0, height/16) via a short frame of the same width
     fr = O.OracleFrame(width, height)
     t0 = time.time()
@@ -368,9 +396,19 @@ def main():
     dt = time.perf_counter() - t0
     timed_stats = (sc.stat("segments"), sc.stat("samples"), sc.stat("kernel_ms"), sc.stat("kernel_launches"))
 
+    # ---- the frame of the timed region's last step, read before the side runs render more samples into this context
+    frame_np = None
+    if rank == 0:
+        frame_np = sc.read_frame() if (use_cabi or world == 1) else out.detach().cpu().numpy()
+        if args.dump_outputs:
+            arrays = {"frame": frame_np}
+            if world == 1:          # at N > 1 every rank holds the LCG states of its own pixels only
+                arrays["rnds"] = sc.read_rnds().astype(np.float64)
+            dump_outputs(args.dump_outputs, arrays)
+
     # ---- the exchange alone (untimed repeat of the final step of the timed region: same buffers, same result)
     exchange_ms = None
-    if world > 1:
+    if args.full and world > 1:
         sync_all()
         t1 = time.perf_counter()
         out = exchange()
@@ -381,9 +419,8 @@ def main():
     # pixel ids are those of the global frame) -- so prove it: rank 0 renders a 24-row band as a ONE-rank context, same
     # seeds, same spp, and compares it bit for bit with those rows of the assembled frame
     frame_matches_n1, band = None, None
-    if rank == 0 and not args.no_band_check:
+    if args.full and rank == 0 and not args.no_band_check:
         band = band_context(H, 24)
-        frame_np = sc.read_frame() if (use_cabi or world == 1) else out.detach().cpu().numpy()
         bsc = api.Scene(W, H, device=gpu_index, **band).load(spec)
         bsc.iterations = B
         if args.lds_scene >= 0:
@@ -398,7 +435,7 @@ def main():
 
     # ---- side measurement (untimed, not part of `value`): the other formulation, same workload
     other = None
-    if world == 1 and not args.no_variants:
+    if args.full and world == 1 and not args.no_variants:
         ov = 1 - args.variant
         sc.set_option("variant", ov)
         sc.render(args.spp_per_step)
@@ -428,12 +465,9 @@ def main():
     segs, samples, kms_sum, launches = [float(x) for x in stats.tolist()]
     total_spp = args.steps * args.spp_per_step
     assert samples == float(W) * H * total_spp, (samples, W * H * total_spp)
-    if use_cabi or world == 1:
-        checksum = float(sc.read_frame()[:, :3].astype(np.float64).sum())
-    else:
-        checksum = float(out[:, :3].double().sum().item())
 
     if rank == 0:
+        checksum = float(frame_np[:, :3].astype(np.float64).sum())
         dbar = segs / samples
         value = samples / dt / 1e6
         # dominant kernel: k_render (or wf_intersect).  Algorithmic bytes per launch / mean launch time.
@@ -468,7 +502,7 @@ def main():
                                                       "context": "pt_create_tiled(rank=%d, world=%d, rows_per_block=%d)" % (band["rank"], band["world"], band["rows_per_block"])},
             "exchange_path": "none (one rank: the colors buffer is the frame)" if world == 1 else ("pt_gather_frame" if use_cabi else ("gloo all_gather (rehearsal)" if args.rehearse_on_one_gpu else "torch all_gather_into_tensor")),
             "kernel_ms_per_rank": {"min": float(kmin.item()), "max": float(kmax.item())},
-            "exchange_ms": (float(xmax.item()) if world > 1 else 0.0),
+            "exchange_ms": (0.0 if world == 1 else (float(xmax.item()) if args.full else None)),
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "kernel": "k_render" if args.variant == 0 else "wf_intersect", "mean_launch_ms": mean_launch_ms,
@@ -497,10 +531,10 @@ def main():
                                  "traffic": otraffic, "algorithmic_bytes_per_step": obytes, "model": omodel,
                                  "time": "wall clock of the untimed side run (all launches of a step)"}
             line["other_variant"] = other
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             sc.close()
             line["configs"] = all_configs(gpu_index)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(W, H, B, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:

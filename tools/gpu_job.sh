@@ -2,7 +2,7 @@
 # usage: tools/gpu_job.sh <tag> [tests] [ab "<names>"] [rates]   -- the round's standing measurement job, pieces by keyword:
 #   tests  the GPU test suite (-m gpu), log under gpurun_out/<tag>/tests.log
 #   abtests <lib> <-k expr>   GPU tests matching the expression against an A/B library
-#   bench  bench.py, then bench.py --steps 5 under rocprofv3 --kernel-trace --stats
+#   bench  bench.py --full, then bench.py --steps 5 under rocprofv3 --kernel-trace --stats
 #   pmc    the rocprofv3 --pmc passes of the six tracked launch shapes -> gpurun_out/counters.json (copy it to profiles/)
 #   sweep  tools/sweep.py --count on every BASELINE config
 #   ab     mesh / Cornell rates with the default library and with every A/B library named (make ab AB=...)
@@ -25,7 +25,7 @@ while [ $# -gt 0 ]; do
             timeout -k 10 300 python tools/prof_render.py $sc >> $out/ab.txt 2>&1 || exit 1
           done
         done; done; unset PTAMD_LIB; cat $out/ab.txt;;
-    bench) timeout -k 10 600 python bench.py > $out/bench.json 2> $out/bench.err; rc=$?; tail -2 $out/bench.err; cut -c1-300 $out/bench.json; [ $rc -ne 0 ] && { echo "bench failed rc=$rc"; exit 1; }
+    bench) timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.err; rc=$?; tail -2 $out/bench.err; cut -c1-300 $out/bench.json; [ $rc -ne 0 ] && { echo "bench failed rc=$rc"; exit 1; }
         rocprofv3 --kernel-trace --stats -d $out/bench_rocprof -o b --output-format csv -- python3 bench.py --steps 5 --no-cpu-baseline --no-variants --no-configs > $out/bench_rocprof.json 2> $out/bench_rocprof.err
         cut -c1-200 $out/bench_rocprof.json; head -4 $out/bench_rocprof/b_kernel_stats.csv;;
     pmc) # the PMC passes behind profiles/counters.json (one counter set per pass; never with the runtime traces)
