@@ -119,6 +119,28 @@ int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
  * sample counter, main.cpp:28) do generate_rays + trace_rays; the counter advances by
  * nsamples.  Fused on the device: one launch, path state in registers. */
 int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples);
+/* Adaptive frame: renders min_spp samples to every tile, then keeps doubling the sample count of the 8x8 tiles whose
+ * noise estimate is still >= threshold, up to max_spp.  Starts a frame: current_sample must be 0.
+ * Rounds: boundaries b0 = min_spp/2, b1 = min_spp, b(k+1) = min(2 b(k), max_spp) (pt_adaptive_rounds); round k renders
+ * samples [b(k-1), b(k)) of the tiles still active.  After every b(k) with k >= 1 and b(k) < max_spp each pixel's mean M is
+ * compared with its mean A at b(k-1) = b(k)/2 in float32, in this order: e = ((|M.r-A.r| + |M.g-A.g|) + |M.b-A.b|) /
+ * (1e-4 + sqrt((M.r + M.g) + M.b)); a tile's estimate is the max over its pixels (+inf if any e is not finite) and the tile
+ * retires iff it is < threshold, keeping its colours and LCG states.  A retired tile has the samples of the boundary it
+ * retired at, the others max_spp; the call returns early when no tile is active, and current_sample is the largest count.
+ * min_spp even and >= 2, max_spp >= min_spp, threshold >= 0 (0 retires nothing, +inf every tile with a finite estimate);
+ * contexts of one rank (world 1) and variant 0 only, else PT_EINVAL.  Synchronises the stream once per round (the number of
+ * active tiles comes back to the host).  Until pt_set_current_sample(ctx, 0) starts a new frame, pt_render, pt_trace_rays
+ * and another pt_render_adaptive return PT_EINVAL. */
+int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations,
+                       int32_t min_spp, int32_t max_spp, float threshold);
+/* per local pixel: the number of samples its colour is the mean of (0 for none yet) */
+int pt_read_sample_counts(pt_context* ctx, int32_t* out, int64_t npix);
+/* per 8x8 tile of the local frame (raster order): samples rendered, and the last noise estimate computed for it (+inf: none);
+ * either pointer may be NULL */
+int pt_read_tile_state(pt_context* ctx, int32_t* spp, float* err, int64_t n_tiles);
+/* host only, no device: the sample-count boundaries pt_render_adaptive uses (min_spp/2, min_spp, 2*min_spp, ..., max_spp);
+ * *count = their number, the first min(cap, *count) are written to out */
+int pt_adaptive_rounds(int32_t min_spp, int32_t max_spp, int32_t* out, int32_t cap, int32_t* count);
 int pt_set_current_sample(pt_context* ctx, int32_t current_sample);  /* main.cpp:1046 etc.: key events reset it to 0 */
 int pt_get_current_sample(const pt_context* ctx, int32_t* out);
 int pt_sync(pt_context* ctx);                                        /* queue.finish(), main.cpp:675 */
@@ -255,6 +277,9 @@ int pt_debug_scene_sizes(const pt_context* ctx, int64_t* ntris, int64_t* nmats, 
 int pt_debug_scene_copy(const pt_context* ctx, pt_triangle* tris, pt_material* mats, int32_t* obj_begin);
 /* the reference's traversal encounter rank of each triangle, in add order */
 int pt_debug_encounter_rank(const pt_context* ctx, int32_t* out, int64_t n);
+/* the list of active tiles the last decision of the held adaptive frame left (ascending local-frame tile indices): *n = its length
+ * (0 without an adaptive frame, or before its first decision), the first min(cap, *n) entries go to out */
+int pt_debug_adaptive_list(pt_context* ctx, int32_t* out, int64_t cap, int64_t* n);
 /* after a counting launch (option count_work = 1, pt_render; schedules 0 and 1 -- under schedule 2 a wave works on two tiles at
  * once and leaves this zero): per 8x8 tile of the local frame, shader-clock cycles / 64 spent on it */
 int pt_debug_tile_cost(pt_context* ctx, uint32_t* out, int64_t n_tiles);

@@ -104,6 +104,11 @@ public:
         camera = Camera(globals);
         ck(pt_render(ctx, &camera, globals.iterations, nsamples));
     }
+    // one adaptive frame (pt_render_adaptive): min_spp to every tile, then doubling where the noise estimate is >= threshold
+    void render_adaptive(int min_spp, int max_spp, float threshold) {
+        camera = Camera(globals);
+        ck(pt_render_adaptive(ctx, &camera, globals.iterations, min_spp, max_spp, threshold));
+    }
     int current_sample() { int32_t s = 0; ck(pt_get_current_sample(ctx, &s)); return s; }
     void reset_samples() { ck(pt_set_current_sample(ctx, 0)); }                                // main.cpp:1046
     void finish() { ck(pt_sync(ctx)); }                                                        // queue.finish(), main.cpp:675

@@ -43,10 +43,11 @@ EXPORTS = [
     "pt_material_init", "pt_triangle_init", "pt_triangles_init", "pt_camera_init", "pt_camera_move", "pt_create", "pt_create_tiled", "pt_destroy",
     "pt_last_error", "pt_device_info", "pt_add_material", "pt_add_triangle", "pt_add_triangles", "pt_end_obj",
     "pt_add_obj", "pt_upload_triangles", "pt_upload_materials", "pt_seed_default", "pt_upload_seeds",
-    "pt_generate_rays", "pt_trace_rays", "pt_render", "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
+    "pt_generate_rays", "pt_trace_rays", "pt_render", "pt_render_adaptive", "pt_read_sample_counts", "pt_read_tile_state", "pt_adaptive_rounds",
+    "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
-    "pt_set_option", "pt_get_stat", "pt_debug_bvh_sizes", "pt_debug_bvh_copy", "pt_debug_wide_nodes", "pt_debug_encounter_rank", "pt_debug_tile_cost", "pt_debug_launch_plan",
+    "pt_set_option", "pt_get_stat", "pt_debug_bvh_sizes", "pt_debug_bvh_copy", "pt_debug_wide_nodes", "pt_debug_encounter_rank", "pt_debug_tile_cost", "pt_debug_adaptive_list", "pt_debug_launch_plan",
     "pt_debug_scene_sizes", "pt_debug_scene_copy", "pt_debug_closest_hit",
     "pt_slab_pixel_count", "pt_frame_size", "pt_comm_available", "pt_comm_unique_id", "pt_comm_init", "pt_gather_frame", "pt_device_frame", "pt_read_frame",
     "pt_write_pfm", "pt_write_ppm", "pt_image_write_pfm", "pt_image_write_ppm", "pt_debug_gather_index", "pt_debug_deinterleave",
@@ -94,6 +95,10 @@ def _load():
     sig("pt_generate_rays", C.c_int, vp, vp)
     sig("pt_trace_rays", C.c_int, vp, vp, i32, i32)
     sig("pt_render", C.c_int, vp, vp, i32, i32)
+    sig("pt_render_adaptive", C.c_int, vp, vp, i32, i32, i32, f32)
+    sig("pt_read_sample_counts", C.c_int, vp, vp, i64)
+    sig("pt_read_tile_state", C.c_int, vp, vp, vp, i64)
+    sig("pt_adaptive_rounds", C.c_int, i32, i32, vp, i32, C.POINTER(i32))
     sig("pt_set_current_sample", C.c_int, vp, i32)
     sig("pt_get_current_sample", C.c_int, vp, C.POINTER(i32))
     sig("pt_sync", C.c_int, vp)
@@ -114,6 +119,7 @@ def _load():
     sig("pt_debug_wide_nodes", C.c_int, vp, vp, i64, C.POINTER(i64))
     sig("pt_debug_encounter_rank", C.c_int, vp, vp, i64)
     sig("pt_debug_tile_cost", C.c_int, vp, vp, i64)
+    sig("pt_debug_adaptive_list", C.c_int, vp, vp, i64, C.POINTER(i64))
     sig("pt_debug_launch_plan", C.c_int, vp, i32, i32, vp)
     sig("pt_debug_scene_sizes", C.c_int, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64))
     sig("pt_debug_scene_copy", C.c_int, vp, vp, vp, vp)
@@ -181,6 +187,19 @@ def triangles_from_vertices(verts, mati):
     out = np.zeros(verts.shape[0], dtype=TRIANGLE)
     LIB.pt_triangles_init(_ptr(out), _ptr(verts), _ptr(mati), verts.shape[0])
     return out
+
+
+def adaptive_rounds(min_spp, max_spp):
+    """The sample-count boundaries of Scene.render_adaptive(min_spp, max_spp, ...): min_spp/2, min_spp, 2*min_spp, ..., max_spp."""
+    n = C.c_int32()
+    rc = LIB.pt_adaptive_rounds(int(min_spp), int(max_spp), None, 0, C.byref(n))
+    if rc != PT_OK:
+        raise PtError(rc, (LIB.pt_last_error(None) or b"").decode())
+    out = np.zeros(n.value, dtype=np.int32)
+    rc = LIB.pt_adaptive_rounds(int(min_spp), int(max_spp), _ptr(out), n.value, C.byref(n))
+    if rc != PT_OK:
+        raise PtError(rc, (LIB.pt_last_error(None) or b"").decode())
+    return [int(v) for v in out]
 
 
 def comm_available():
@@ -339,6 +358,31 @@ class Scene:
                 self.trace_rays()
                 self.current_sample = self.current_sample + 1                                        # main.cpp:686
 
+    def render_adaptive(self, min_spp, max_spp, threshold):
+        """One adaptive frame (pt_render_adaptive; current_sample must be 0).  Returns {"rounds": the boundaries whose round ran,
+        "active_tiles": tiles rendered in each of those rounds, "samples": samples spent on the frame}."""
+        self._ck(LIB.pt_render_adaptive(self._h, _ptr(self.camera), self.iterations, int(min_spp), int(max_spp), float(threshold)))
+        spp, _ = self.tile_state()
+        bounds = adaptive_rounds(min_spp, max_spp)
+        active = [int((spp >= b).sum()) for b in bounds]
+        ran = [k for k in range(len(bounds)) if active[k] > 0]
+        return {"rounds": [bounds[k] for k in ran], "active_tiles": [active[k] for k in ran],
+                "samples": int(self.sample_counts().sum(dtype=np.int64))}
+
+    def sample_counts(self):
+        """Per local pixel (local_rows x width, int32): the number of samples its colour is the mean of."""
+        out = np.empty(self.local_pixels, dtype=np.int32)
+        self._ck(LIB.pt_read_sample_counts(self._h, _ptr(out), out.size))
+        return out.reshape(-1, self.width)
+
+    def tile_state(self):
+        """Per 8x8 tile of the local frame, raster order: (samples rendered int32, last noise estimate float32, +inf: none)."""
+        n = ((self.width + 7) // 8) * ((self.local_pixels // self.width + 7) // 8)
+        spp = np.empty(n, dtype=np.int32)
+        err = np.empty(n, dtype=np.float32)
+        self._ck(LIB.pt_read_tile_state(self._h, _ptr(spp), _ptr(err), n))
+        return spp, err
+
     def sync(self):
         self._ck(LIB.pt_sync(self._h))
 
@@ -485,6 +529,15 @@ class Scene:
         self._ck(LIB.pt_debug_launch_plan(self._h, int(nsamples), int(cu_count), _ptr(out)))
         keys = ("block", "waves_per_simd", "schedule", "chunk_spp", "resident_waves", "tiles", "node_mode", "lds_bytes")
         return dict(zip(keys, (int(v) for v in out)))
+
+    def debug_adaptive_list(self):
+        """The active tiles the last decision of the held adaptive frame left, in the order the next round would render them."""
+        n = C.c_int64()
+        self._ck(LIB.pt_debug_adaptive_list(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            self._ck(LIB.pt_debug_adaptive_list(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
 
     def debug_tile_cost(self):
         """After set_option("count_work", 1) + render(n): per 8x8 tile of the local frame, the shader-clock cycles / 64 its wave spent on it."""

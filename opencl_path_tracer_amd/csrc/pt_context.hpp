@@ -119,6 +119,15 @@ struct pt_context {
     uint32_t* d_tile_counter = nullptr;
     uint32_t* d_tile_done = nullptr;
     uint32_t* d_tile_cost = nullptr;   // count_work: per tile, cycles / 64 its waves spent on it in the last launch (pt_debug_tile_cost)
+    // adaptive frames (pt_render_adaptive; allocated on first use): per local pixel the colour at half the tile's samples; per tile of
+    // the local frame the samples rendered, the last noise estimate and the active flag; the active tiles in ascending order + their count
+    float4* d_adapt_snap = nullptr;
+    int32_t* d_adapt_spp = nullptr;
+    float* d_adapt_err = nullptr;
+    uint8_t* d_adapt_active = nullptr;
+    int32_t* d_adapt_list = nullptr;   // n_tiles entries, then the count word
+    int32_t* h_adapt_count = nullptr;  // pinned
+    bool adaptive_frame = false;       // an adaptive frame is held: pt_render / pt_trace_rays / pt_render_adaptive refuse until pt_set_current_sample(0)
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -294,6 +303,7 @@ int time_begin(pt_context* ctx, EventPair** ep);
 int time_end(pt_context* ctx, EventPair* ep);
 int time_collect(pt_context* ctx);
 int sync_and_check(pt_context* ctx);
+inline int32_t local_tiles(const pt_context* c) { return ((c->W + 7) / 8) * ((c->local_rows + 7) / 8); }
 template <class T>
 int upload_vec(pt_context* ctx, T** dptr, const void* src, size_t bytes) {
     if (*dptr) { PT_HIP(ctx, hipFree(*dptr)); *dptr = nullptr; }

@@ -228,6 +228,15 @@ PT_DEV PixelId pixel_of_wave(const RenderParams& p, int wave) {
     return r;
 }
 
+// Tile t of a launch -> tile of the local frame: t itself, or the t-th entry of an adaptive frame's list of active tiles
+// (p.tile_list, pt_render_adaptive).  t is wave-uniform and so is the answer (scalar registers); a t past the list -- the last
+// workgroup of a non-persistent grid -- becomes the first tile below the frame, which has no pixels.
+PT_DEV int frame_tile(const RenderParams& p, int t) {
+    if (!p.tile_list) return t;
+    if (t >= p.n_tiles) return ((p.width + 7) >> 3) * ((p.local_rows + 7) >> 3);
+    return __builtin_amdgcn_readfirstlane(p.tile_list[t]);
+}
+
 PT_DEV PixelId pixel_of_thread(const RenderParams& p) {
     return pixel_of_wave(p, (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
 }

@@ -225,6 +225,12 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->d_tile_counter) (void)hipFree(ctx->d_tile_counter);
         if (ctx->d_tile_done) (void)hipFree(ctx->d_tile_done);
         if (ctx->d_tile_cost) (void)hipFree(ctx->d_tile_cost);
+        if (ctx->d_adapt_snap) (void)hipFree(ctx->d_adapt_snap);
+        if (ctx->d_adapt_spp) (void)hipFree(ctx->d_adapt_spp);
+        if (ctx->d_adapt_err) (void)hipFree(ctx->d_adapt_err);
+        if (ctx->d_adapt_active) (void)hipFree(ctx->d_adapt_active);
+        if (ctx->d_adapt_list) (void)hipFree(ctx->d_adapt_list);
+        if (ctx->h_adapt_count) (void)hipHostFree(ctx->h_adapt_count);
         if (ctx->d_wf_state) (void)hipFree(ctx->d_wf_state);
         if (ctx->d_wf_queues) (void)hipFree(ctx->d_wf_queues);
         if (ctx->d_wf_counters) (void)hipFree(ctx->d_wf_counters);
@@ -418,6 +424,37 @@ int pt_read_rnds(pt_context* ctx, int32_t* out, int64_t npix) {
     PT_NEED_DEVICE(ctx);
     if (!out || npix != ctx->npix) return fail(ctx, PT_EINVAL, "npix must equal the local pixel count");
     return read_back(ctx, out, ctx->d_rnds, sizeof(int32_t) * (size_t)npix);
+}
+// the samples behind each pixel's colour: its tile's count in an adaptive frame, current_sample otherwise
+int pt_read_sample_counts(pt_context* ctx, int32_t* out, int64_t npix) {
+    PT_NEED_DEVICE(ctx);
+    if (!out || npix != ctx->npix) return fail(ctx, PT_EINVAL, "npix must equal the local pixel count");
+    if (!ctx->adaptive_frame) {
+        std::fill(out, out + npix, ctx->current_sample);
+        return PT_OK;
+    }
+    std::vector<int32_t> spp((size_t)local_tiles(ctx));
+    const int rc = read_back(ctx, spp.data(), ctx->d_adapt_spp, sizeof(int32_t) * spp.size());
+    if (rc != PT_OK) return rc;
+    const int32_t tiles_x = (ctx->W + 7) / 8;
+    for (int64_t i = 0; i < npix; ++i) {
+        const int32_t y = (int32_t)(i / ctx->W), x = (int32_t)(i % ctx->W);
+        out[i] = spp[(size_t)(y / 8) * tiles_x + x / 8];
+    }
+    return PT_OK;
+}
+int pt_read_tile_state(pt_context* ctx, int32_t* spp, float* err, int64_t n_tiles) {
+    PT_NEED_DEVICE(ctx);
+    if (n_tiles != local_tiles(ctx)) return fail(ctx, PT_EINVAL, "pt_read_tile_state: n_tiles must be the number of 8x8 tiles of the local frame");
+    if (!ctx->adaptive_frame) {
+        if (spp) std::fill(spp, spp + n_tiles, ctx->current_sample);
+        if (err) std::fill(err, err + n_tiles, std::numeric_limits<float>::infinity());
+        return PT_OK;
+    }
+    int rc = PT_OK;
+    if (spp && (rc = read_back(ctx, spp, ctx->d_adapt_spp, sizeof(int32_t) * (size_t)n_tiles)) != PT_OK) return rc;
+    if (err && (rc = read_back(ctx, err, ctx->d_adapt_err, sizeof(float) * (size_t)n_tiles)) != PT_OK) return rc;
+    return PT_OK;
 }
 int pt_read_rays(pt_context* ctx, pt_ray* out, int64_t npix) {
     PT_NEED_DEVICE(ctx);

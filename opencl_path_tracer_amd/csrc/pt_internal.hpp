@@ -136,7 +136,7 @@ struct RenderParams {
     uint32_t poll_ticks;         // chained passes: how long a wave waits for a tile's previous pass, in 10-ns ticks of s_memrealtime, before it
                                  // reports the tile in word 4 and the launch winds down (pt_sync then returns PT_EHIP)
     int32_t debug_stall_tile;    // tests: pass 0 of this tile is rendered but never published (-1: none)
-    int32_t n_tiles;
+    int32_t n_tiles;             // tiles of the launch: those of the local frame, or the n_tiles entries of tile_list
     // passes of DIFFERENT lengths (option chunk_taper): n_taper > 0 -> pass k of a tile is samples [taper_end[k-1], taper_end[k]) of the
     // launch (taper_end[-1] = 0), n_taper passes in all; the last passes are short, so that the launch does not end on whole long items
     int32_t n_taper;
@@ -149,6 +149,8 @@ struct RenderParams {
     int32_t leaf_min_lanes;      // ... and the leaf phase when at most this many lanes still hold leaves and another has a node (0: never)
     int32_t migrate_lanes;       // kSchedMigrate: lanes that are done with the wave's current work item move to the next one when this many have gathered
     uint32_t* tile_cost;         // counting instances only, or null: [n_tiles] += shader-clock cycles / 64 the wave spent on each work item of the tile (pt_debug_tile_cost)
+    const int32_t* tile_list;    // != 0 (adaptive frames, pt_render_adaptive): tile t of the launch is frame tile tile_list[t]; work items,
+                                 // tile_done[] and debug_stall_tile count list positions, tile_cost frame tiles
 };
 
 // ---- wavefront (stream-compacted) formulation
@@ -302,6 +304,12 @@ hipError_t launch_filt_im(const float4* colors, float4* out, int32_t width, int3
 hipError_t launch_wf_generate(const WfParams& p, hipStream_t stream);
 hipError_t launch_wf_intersect(const WfParams& p, int bounce, int cu_count, hipStream_t stream);
 hipError_t launch_wf_shade(const WfParams& p, int bounce, hipStream_t stream);
+// adaptive frames (pt_adaptive.hip): per tile of `list` (null: every tile of the frame, n_list of them) -- mode 0 tile_spp = spp; 1 also
+// snap = colors; 2 also the noise estimate against snap -> tile_err, active (0: retired), and snap = colors where the tile stays active
+hipError_t launch_adaptive_tiles(const float4* colors, float4* snap, const int32_t* list, int32_t n_list, int32_t width, int32_t rows, int mode,
+                                 float threshold, int32_t spp, float* tile_err, int32_t* tile_spp, uint8_t* active, hipStream_t stream);
+// the frame tiles whose flag is set, ascending, into list[0, *count) (one workgroup)
+hipError_t launch_compact_tiles(const uint8_t* active, int32_t n, int32_t* list, int32_t* count, hipStream_t stream);
 hipError_t launch_debug_closest_hit(const RenderParams& p, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri, int cu_count, hipStream_t stream);
 
 }  // namespace ptamd

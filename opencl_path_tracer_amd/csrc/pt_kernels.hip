@@ -335,7 +335,7 @@ PT_DEV void render_items_migrating(const RenderParams& p, const SceneView& sv, c
     const int tiles_x = (p.width + 7) >> 3;
     const bool rows_aligned = (p.rows_per_block & 7) == 0;
     auto take_pixel = [&](int item) {
-        const int tile = tile_of(item);
+        const int tile = frame_tile(p, tile_of(item));
         const int ty = tile / tiles_x, tx = tile - ty * tiles_x;            // (wave-uniform: scalar unit)
         const int x = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
         if (x >= p.width || lrow >= p.local_rows) return;                   // (stays parked: the tile has no pixel for this lane)
@@ -542,7 +542,8 @@ __global__ void __launch_bounds__(BLOCK, WPS) k_render(RenderParams p) {
         const bool tabled = chained && p.n_taper > 0;           // (passes of different lengths: RenderParams::taper_end)
         const int s_begin = p.first_sample + (tabled ? (pass > 0 ? (int)p.taper_end[pass - 1] : 0) : chained ? pass * p.chunk_spp : 0);
         const int s_end = tabled ? p.first_sample + (int)p.taper_end[pass] : chained ? min(s_begin + p.chunk_spp, p.first_sample + p.nsamples) : p.first_sample + p.nsamples;
-        const PixelId px = pixel_of_wave(p, tile);
+        const int ftile = frame_tile(p, tile);                 // (tile_done[] and the work counter count launch tiles)
+        const PixelId px = pixel_of_wave(p, ftile);
         unsigned item_segs = 0;
         const unsigned long long item_t0 = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
         if (px.li >= 0) {
@@ -562,7 +563,7 @@ __global__ void __launch_bounds__(BLOCK, WPS) k_render(RenderParams p) {
             item_lane_steps += (unsigned long long)mxs * 64ull;
             // what the tile cost THIS wave, in shader-clock cycles / 64 (the wave shares its SIMD with the others resident there:
             // that is the latency a launch with one tile per wave ends on)
-            if (p.tile_cost && lane0) atomicAdd(&p.tile_cost[tile], (unsigned)((__builtin_amdgcn_s_memtime() - item_t0) >> 6));
+            if (p.tile_cost && lane0) atomicAdd(&p.tile_cost[ftile], (unsigned)((__builtin_amdgcn_s_memtime() - item_t0) >> 6));
         }
         if (chained) {                                           // ---- release this pass of the tile
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -691,7 +692,7 @@ hipError_t launch_gen_ray(const RenderParams& p, hipStream_t stream) {
 
 template <bool SPLIT, int MODE, int BLOCK, bool COUNT, int SCHED, int WPS>
 static hipError_t launch_one(const RenderParams& p, const LaunchConfig& lc, hipStream_t stream) {
-    const int waves = n_waves(p);
+    const int waves = p.tile_list ? p.n_tiles : n_waves(p);
     if (waves == 0) return hipSuccess;
     constexpr int wpb = BLOCK / 64;
     int blocks = (waves + wpb - 1) / wpb;

@@ -3,7 +3,7 @@
 //   * kernel parameters (RenderParams), event timing
 //   * the launch policy: kernel instance, schedule, samples per work item, by tiles per resident wave (DESIGN.md sections 5, 6)
 //   * the wavefront variant's chains; the work counter's recovery after a launch that did not run to its end
-//   * pt_generate_rays, pt_trace_rays, pt_render, pt_sync, pt_debug_launch_plan
+//   * pt_generate_rays, pt_trace_rays, pt_render, pt_render_adaptive, pt_sync, pt_debug_launch_plan
 #include "pt_context.hpp"
 
 namespace ptamd {
@@ -353,6 +353,7 @@ int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
     if (iterations < 0 || current_sample < 0) return fail(ctx, PT_EINVAL, "iterations/current_sample must be >= 0");
+    if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     fill_params(ctx, cam, &p);
@@ -468,24 +469,17 @@ static int render_wavefront(pt_context* ctx, const RenderParams& rp, int32_t nsa
     return PT_OK;
 }
 
-int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples) {
-    PT_NEED_DEVICE(ctx);
-    int rc = check_ready(ctx, cam);
-    if (rc != PT_OK) return rc;
-    if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "iterations/nsamples must be >= 0");
-    if (nsamples == 0) return PT_OK;
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    fill_params(ctx, cam, &p);
-    p.iterations = iterations;
-    p.first_sample = ctx->current_sample;
-    p.nsamples = nsamples;
-    ctx->render_epoch++;
-    if (ctx->variant == 1) {
-        if ((rc = render_wavefront(ctx, p, nsamples)) != PT_OK) return rc;
-        ctx->current_sample += nsamples;
-        return PT_OK;
+// One megakernel launch of samples [p.first_sample, p.first_sample + p.nsamples) over the tiles of the local frame (tile_list null) or over the
+// n_active frame tiles of tile_list (an adaptive frame's round: launch_cfg and the pass length see n_active as the launch's tiles).
+// Everything pt_render launches goes through here.
+static int launch_megakernel(pt_context* ctx, RenderParams& p, const int32_t* tile_list, int32_t n_active) {
+    int rc = PT_OK;
+    const int32_t nsamples = p.nsamples;
+    if (tile_list) {
+        p.tile_list = tile_list;
+        p.n_tiles = n_active;
     }
+    const size_t frame_tiles = (size_t)local_tiles(ctx);
     LaunchConfig lc;
     launch_cfg(ctx, p, &lc);
     if (ctx->persistent) {
@@ -527,15 +521,17 @@ int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t
         if (items + (int64_t)resident_waves + 64 >= ((int64_t)1 << 31))
             return fail(ctx, PT_EINVAL, "nsamples / chunk_spp x tiles does not fit the 31-bit work-item counter of one launch: render in several calls");
         if (chunk > 0 && nsamples > chunk && p.n_tiles > 0) {
-            if (!ctx->d_tile_done) PT_HIP(ctx, hipMalloc((void**)&ctx->d_tile_done, sizeof(uint32_t) * (size_t)p.n_tiles));
+            if (!ctx->d_tile_done) PT_HIP(ctx, hipMalloc((void**)&ctx->d_tile_done, sizeof(uint32_t) * frame_tiles));
             PT_HIP(ctx, hipMemsetAsync(ctx->d_tile_done, 0, sizeof(uint32_t) * (size_t)p.n_tiles, ctx->stream));
             p.tile_done = ctx->d_tile_done;
             p.chunk_spp = chunk;
         }
     }
     if (lc.count_work && p.n_tiles > 0) {      // per-tile cost of this launch (pt_debug_tile_cost)
-        if (!ctx->d_tile_cost) PT_HIP(ctx, hipMalloc((void**)&ctx->d_tile_cost, sizeof(uint32_t) * (size_t)p.n_tiles));
-        PT_HIP(ctx, hipMemsetAsync(ctx->d_tile_cost, 0, sizeof(uint32_t) * (size_t)p.n_tiles, ctx->stream));
+        // (+ 16: in a non-persistent grid the waves past the last tile of the last workgroup (at most 15) still add their time -- the
+        // atomicAdd in k_render is not conditional on the wave having pixels -- at indices up to 15 past the frame's tiles)
+        if (!ctx->d_tile_cost) PT_HIP(ctx, hipMalloc((void**)&ctx->d_tile_cost, sizeof(uint32_t) * (frame_tiles + 16)));
+        PT_HIP(ctx, hipMemsetAsync(ctx->d_tile_cost, 0, sizeof(uint32_t) * frame_tiles, ctx->stream));      // (indexed by frame tile)
         p.tile_cost = ctx->d_tile_cost;
     }
     EventPair* ep;
@@ -545,13 +541,143 @@ int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t
         if (le != hipSuccess) { ctx->counters_suspect = true; return fail(ctx, PT_EHIP, std::string("launch_render_mega: ") + hipGetErrorString(le)); }
     }
     if ((rc = time_end(ctx, ep)) != PT_OK) { ctx->counters_suspect = true; return rc; }
+    return PT_OK;
+}
+
+int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples) {
+    PT_NEED_DEVICE(ctx);
+    int rc = check_ready(ctx, cam);
+    if (rc != PT_OK) return rc;
+    if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "iterations/nsamples must be >= 0");
+    if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
+    if (nsamples == 0) return PT_OK;
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    fill_params(ctx, cam, &p);
+    p.iterations = iterations;
+    p.first_sample = ctx->current_sample;
+    p.nsamples = nsamples;
+    ctx->render_epoch++;
+    if (ctx->variant == 1) {
+        if ((rc = render_wavefront(ctx, p, nsamples)) != PT_OK) return rc;
+        ctx->current_sample += nsamples;
+        return PT_OK;
+    }
+    if ((rc = launch_megakernel(ctx, p, nullptr, p.n_tiles)) != PT_OK) return rc;
     ctx->current_sample += nsamples;  // main.cpp:686
+    return PT_OK;
+}
+
+// Adaptive frames: the sample-count boundaries b0 = min_spp / 2, b1 = min_spp, b(k+1) = min(2 b(k), max_spp); "" or what is wrong
+static std::string adaptive_bounds(int32_t min_spp, int32_t max_spp, std::vector<int32_t>* out) {
+    if (min_spp < 2 || (min_spp & 1)) return "min_spp must be even and >= 2";
+    if (max_spp < min_spp) return "max_spp must be >= min_spp";
+    out->clear();
+    out->push_back(min_spp / 2);
+    for (int64_t b = min_spp;; b = std::min<int64_t>(2 * b, max_spp)) {
+        out->push_back((int32_t)b);
+        if (b == max_spp) break;
+    }
+    return "";
+}
+
+// Round k renders samples [b(k-1), b(k)) of the active tiles -- an ordinary megakernel launch over the list of them -- and, where
+// b(0) < b(k) < max_spp, k_adaptive_tiles compares every pixel's mean with its snapshot at b(k-1) = b(k) / 2 and retires the tiles whose
+// largest estimate is below the threshold; k_compact_tiles lists the others for the next round, and their count comes back to the host
+// (one synchronisation per round).  Round 0 (b(0) samples, every tile) only takes the snapshot.
+int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t min_spp, int32_t max_spp, float threshold) {
+    if (!ctx) return PT_EINVAL;
+    std::vector<int32_t> bounds;
+    std::string why = adaptive_bounds(min_spp, max_spp, &bounds);
+    if (why.empty() && !(threshold >= 0.0f)) why = "threshold must be >= 0 (and not NaN)";
+    if (why.empty() && iterations < 0) why = "iterations must be >= 0";
+    if (why.empty()) {      // the longest round must fit one launch's 31-bit work-item counter at one sample per item, with room for the grid
+        int64_t longest = bounds[0];
+        for (size_t k = 1; k < bounds.size(); ++k) longest = std::max<int64_t>(longest, (int64_t)bounds[k] - bounds[k - 1]);
+        if (longest * (int64_t)local_tiles(ctx) + ((int64_t)1 << 20) >= ((int64_t)1 << 31))
+            why = "max_spp too large: a round of " + std::to_string(longest) + " samples over " + std::to_string(local_tiles(ctx)) +
+                  " tiles does not fit the 31-bit work-item counter of one launch";
+    }
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_render_adaptive: " + why);
+    PT_NEED_DEVICE(ctx);
+    int rc = check_ready(ctx, cam);
+    if (rc != PT_OK) return rc;
+    if (ctx->variant != 0) return fail(ctx, PT_EINVAL, "pt_render_adaptive: the megakernel (variant 0) only");
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_render_adaptive: contexts of one rank (world == 1) only");
+    if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
+    if (ctx->current_sample != 0) return fail(ctx, PT_EINVAL, "pt_render_adaptive starts a frame: current_sample must be 0");
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    const int32_t n_frame = local_tiles(ctx);
+    if (!ctx->d_adapt_snap) {
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_snap, sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_spp, sizeof(int32_t) * (size_t)n_frame));
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_err, sizeof(float) * (size_t)n_frame));
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_active, (size_t)n_frame));
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_list, sizeof(int32_t) * ((size_t)n_frame + 1)));
+        PT_HIP(ctx, hipHostMalloc((void**)&ctx->h_adapt_count, sizeof(int32_t), hipHostMallocDefault));
+    }
+    int32_t* d_count = ctx->d_adapt_list + n_frame;
+    PT_HIP(ctx, hipMemsetAsync(ctx->d_adapt_active, 1, (size_t)n_frame, ctx->stream));
+    PT_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(int32_t), ctx->stream));          // (no list before the first decision)
+    PT_HIP(ctx, hipMemsetAsync(ctx->d_adapt_spp, 0, sizeof(int32_t) * (size_t)n_frame, ctx->stream));
+    PT_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->d_adapt_err, 0x7f800000, (size_t)n_frame, ctx->stream));      // +inf: no estimate yet
+    ctx->adaptive_frame = true;
+    ctx->render_epoch++;
+    RenderParams p;
+    fill_params(ctx, cam, &p);
+    p.iterations = iterations;
+    const int32_t* list = nullptr;          // round 0 and 1: every tile
+    int32_t n_active = n_frame;
+    for (size_t k = 0; k < bounds.size(); ++k) {
+        const int32_t b = bounds[k], prev = k == 0 ? 0 : bounds[k - 1];
+        RenderParams pr = p;
+        pr.first_sample = prev;
+        pr.nsamples = b - prev;
+        if ((rc = launch_megakernel(ctx, pr, list, n_active)) != PT_OK) return rc;
+        ctx->current_sample = b;
+        const int mode = k == 0 ? 1 : b < max_spp ? 2 : 0;
+        PT_HIP(ctx, launch_adaptive_tiles(ctx->d_colors, ctx->d_adapt_snap, list, n_active, ctx->W, ctx->local_rows, mode, threshold, b,
+                                          ctx->d_adapt_err, ctx->d_adapt_spp, ctx->d_adapt_active, ctx->stream));
+        if (mode != 2) continue;
+        PT_HIP(ctx, launch_compact_tiles(ctx->d_adapt_active, n_frame, ctx->d_adapt_list, d_count, ctx->stream));
+        PT_HIP(ctx, hipMemcpyAsync(ctx->h_adapt_count, d_count, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = sync_and_check(ctx)) != PT_OK) return rc;
+        n_active = *ctx->h_adapt_count;
+        list = ctx->d_adapt_list;
+        if (n_active == 0) break;
+    }
+    return PT_OK;
+}
+
+int pt_debug_adaptive_list(pt_context* ctx, int32_t* out, int64_t cap, int64_t* n) {
+    PT_NEED_DEVICE(ctx);
+    if (!n || cap < 0 || (cap > 0 && !out)) return fail(ctx, PT_EINVAL, "pt_debug_adaptive_list: n non-null, cap >= 0, out non-null when cap > 0");
+    *n = 0;
+    if (!ctx->adaptive_frame || !ctx->d_adapt_list) return PT_OK;
+    int rc = sync_and_check(ctx);
+    if (rc != PT_OK) return rc;
+    const int32_t n_frame = local_tiles(ctx);
+    int32_t count = 0;
+    PT_HIP(ctx, hipMemcpy(&count, ctx->d_adapt_list + n_frame, sizeof count, hipMemcpyDeviceToHost));
+    *n = count;
+    if (cap > 0 && count > 0) PT_HIP(ctx, hipMemcpy(out, ctx->d_adapt_list, sizeof(int32_t) * (size_t)std::min<int64_t>(cap, count), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_adaptive_rounds(int32_t min_spp, int32_t max_spp, int32_t* out, int32_t cap, int32_t* count) {
+    std::vector<int32_t> bounds;
+    std::string why = adaptive_bounds(min_spp, max_spp, &bounds);
+    if (why.empty() && (!count || cap < 0 || (cap > 0 && !out))) why = "count must be non-null, cap >= 0, out non-null when cap > 0";
+    if (!why.empty()) return fail(nullptr, PT_EINVAL, "pt_adaptive_rounds: " + why);
+    *count = (int32_t)bounds.size();
+    for (int32_t k = 0; k < std::min<int32_t>(cap, *count); ++k) out[k] = bounds[(size_t)k];
     return PT_OK;
 }
 
 int pt_set_current_sample(pt_context* ctx, int32_t s) {
     if (!ctx || s < 0) return PT_EINVAL;
     ctx->current_sample = s;
+    if (s == 0) ctx->adaptive_frame = false;
     return PT_OK;
 }
 int pt_get_current_sample(const pt_context* ctx, int32_t* out) {
