@@ -156,6 +156,48 @@ int pt_read_rays(pt_context* ctx, pt_ray* out, int64_t npix);        /* buffer_r
  * prog.cl:380); which = 0 Reinhard, 1 = filt_im (3x3 median + filmic, prog.cl:391-427). */
 int pt_resolve_ldr(pt_context* ctx, int32_t which, float* out_rgba, int64_t npix);
 
+/* ---- guide buffers and an edge-avoiding a-trous denoiser (new: the reference has no denoiser) ------------------------
+ * Guide buffers ("AOVs") of the frame seen through cam.  Per local pixel, subpixels x subpixels (1..8) camera rays with the
+ * sub-pixel offsets rnd1 = ((float)i + 0.5f) / (float)n, rnd2 = ((float)j + 0.5f) / (float)n fed to camera_get_ray
+ * (prog.cl:82-92); no LCG draw.  Each ray follows at most specular_depth (0..16) mirror (type 1) / dielectric (type 2) hits
+ * with the next ray shade_hit would build (flipped N, mirror direction, normalisation, +-0.001 offset); a dielectric refracts
+ * iff disc > 0 and reflects otherwise, toggling `inside` as prog.cl:228-245 does; a mirror multiplies the running tint
+ * (1,1,1 at first) by its F0, a dielectric leaves it.  The terminal hit (the first of any other type, or the one where the
+ * depth runs out) gives albedo = tint x (kd + emission) (prog.cl:323-325; F0 at a terminal mirror, 1 at a terminal
+ * dielectric) and its N flipped against the incoming ray; a miss anywhere on the chain gives albedo 0 and normal 0.
+ * Per pixel, sub-pixels in raster order (j outer, i inner): albedo = sum / (float)(n*n); normal = sum s times
+ * 1.0f / sqrtf((s.x*s.x + s.y*s.y) + s.z*s.z) (0 when s is 0); depth = the sum of the primary rays' t over the sub-pixels
+ * that hit, / (float)hits, -1 when none hit.  Touches neither colors, rnds, rays nor current_sample, and is allowed while an
+ * adaptive frame is held.  Any context (tiled ranks: their local pixels, at global pixel ids).  Arguments are checked
+ * before the device: out-of-range ones give PT_EINVAL, a host-only context PT_ENODEVICE. */
+int pt_render_aovs(pt_context* ctx, const pt_camera* cam, int32_t subpixels, int32_t specular_depth);
+/* albedo_rgbm: {r, g, b, material index of the first sub-pixel's terminal hit or -1}; normal_depth: {nx, ny, nz, depth};
+ * 16 B each per local pixel, either pointer may be NULL */
+int pt_read_aovs(pt_context* ctx, float* albedo_rgbm, float* normal_depth, int64_t npix);
+/* The filter (Dammertz et al. 2010, the spatial part of SVGF), L = iterations:
+ *   x0 = c / max(a, 1e-3) per channel with demodulate (a: the guides' albedo), else c;
+ *   iteration i = 0..L-1, step s = 2^i, taps q = p + s (dx, dy), dx, dy in -2..2; taps outside the frame are skipped:
+ *     x(i+1)(p) = sum h wc wn wz x(i)(q) / sum h wc wn wz,  h = k[dx] k[dy], k = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *     wc = exp(-|x(i)(p) - x(i)(q)|^2 4^i / sigma_color^2)
+ *     wn = max(0, n_p . n_q)^sigma_normal, 1 if either normal is 0
+ *     wz = 1 if both primary rays miss, 0 if exactly one does, else exp(-|z_p - z_q| / (sigma_depth s max(|dx|,|dy|) z_p))
+ *   the centre tap q = p weighs 9/64 (every term 1), so the denominator never vanishes; sigma = +inf turns its term off
+ *   (weight 1), and so does sigma_normal = 0;
+ *   output x(L) max(a, 1e-3) with demodulate, else x(L); .w = 1.
+ * Float32 on the device (expf / powf), deterministic (no atomics): two runs give the same bits. */
+typedef struct { int32_t iterations; float sigma_color, sigma_normal, sigma_depth; int32_t demodulate; } pt_denoise_params;
+/* iterations 3, sigma_color 0.125, sigma_normal 8, sigma_depth 0.05, demodulate 1: the best value of every axis of the 16-spp
+ * sweep of tools/denoise_bench.py at 1920x1080, 8 bounces -- the same on the Cornell box and on MESH-100k.  The RMSE gain is
+ * small (3-4 %: caustic fireflies dominate the error), see profiles/denoise/README.md */
+void pt_denoise_defaults(pt_denoise_params* p);
+/* Filters the context's colors (the bound framebuffer, if any) with the last pt_render_aovs guides into a buffer of its
+ * own; colors is never written.  World-1 contexts only.  PT_EINVAL without guides, after pt_upload_triangles /
+ * pt_upload_materials made them stale, for iterations outside 1..10 or negative / NaN sigmas.  Two launches' worth of
+ * buffers (32 B/px) are allocated on first use. */
+int pt_denoise(pt_context* ctx, const pt_denoise_params* p);
+int pt_read_denoised(pt_context* ctx, float* out_rgba, int64_t npix);   /* float3 @ 16 B, colors' layout (row 0 = bottom) */
+void* pt_device_denoised(pt_context* ctx);                               /* NULL until pt_denoise ran */
+
 /* ---- multi-GPU frame assembly (SURVEY 8b "RCCL communicator per context", 8e) ----------
  * The reference is single-device (main.cpp:466-476); a host that tiles the frame over N contexts with
  * pt_create_tiled assembles it with these.  One process (or thread) per GPU:

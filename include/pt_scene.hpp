@@ -109,6 +109,16 @@ public:
         camera = Camera(globals);
         ck(pt_render_adaptive(ctx, &camera, globals.iterations, min_spp, max_spp, threshold));
     }
+    // guide buffers of the current view (pt_render_aovs) and the a-trous filter over them (pt_denoise; p = NULL: the defaults)
+    // (the view of the last render: a new Camera(globals) would move a moving camera once more)
+    void render_aovs(int subpixels = 1, int specular_depth = 4) {
+        ck(pt_render_aovs(ctx, &camera, subpixels, specular_depth));
+    }
+    void denoise(const pt_denoise_params* p = nullptr) {
+        pt_denoise_params d;
+        pt_denoise_defaults(&d);
+        ck(pt_denoise(ctx, p ? p : &d));
+    }
     int current_sample() { int32_t s = 0; ck(pt_get_current_sample(ctx, &s)); return s; }
     void reset_samples() { ck(pt_set_current_sample(ctx, 0)); }                                // main.cpp:1046
     void finish() { ck(pt_sync(ctx)); }                                                        // queue.finish(), main.cpp:675

@@ -45,6 +45,7 @@ EXPORTS = [
     "pt_add_obj", "pt_upload_triangles", "pt_upload_materials", "pt_seed_default", "pt_upload_seeds",
     "pt_generate_rays", "pt_trace_rays", "pt_render", "pt_render_adaptive", "pt_read_sample_counts", "pt_read_tile_state", "pt_adaptive_rounds",
     "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
+    "pt_render_aovs", "pt_read_aovs", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
     "pt_set_option", "pt_get_stat", "pt_debug_bvh_sizes", "pt_debug_bvh_copy", "pt_debug_wide_nodes", "pt_debug_encounter_rank", "pt_debug_tile_cost", "pt_debug_adaptive_list", "pt_debug_launch_plan",
@@ -99,6 +100,12 @@ def _load():
     sig("pt_read_sample_counts", C.c_int, vp, vp, i64)
     sig("pt_read_tile_state", C.c_int, vp, vp, vp, i64)
     sig("pt_adaptive_rounds", C.c_int, i32, i32, vp, i32, C.POINTER(i32))
+    sig("pt_render_aovs", C.c_int, vp, vp, i32, i32)
+    sig("pt_read_aovs", C.c_int, vp, vp, vp, i64)
+    sig("pt_denoise_defaults", None, vp)
+    sig("pt_denoise", C.c_int, vp, vp)
+    sig("pt_read_denoised", C.c_int, vp, vp, i64)
+    sig("pt_device_denoised", vp, vp)
     sig("pt_set_current_sample", C.c_int, vp, i32)
     sig("pt_get_current_sample", C.c_int, vp, C.POINTER(i32))
     sig("pt_sync", C.c_int, vp)
@@ -200,6 +207,22 @@ def adaptive_rounds(min_spp, max_spp):
     if rc != PT_OK:
         raise PtError(rc, (LIB.pt_last_error(None) or b"").decode())
     return [int(v) for v in out]
+
+
+class DenoiseParams(C.Structure):
+    """pt_denoise_params (include/pt_api.h)."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def denoise_defaults():
+    """pt_denoise_defaults as a dict: iterations, sigma_color, sigma_normal, sigma_depth, demodulate."""
+    p = DenoiseParams()
+    LIB.pt_denoise_defaults(C.byref(p))
+    return p.as_dict()
 
 
 def comm_available():
@@ -382,6 +405,37 @@ class Scene:
         err = np.empty(n, dtype=np.float32)
         self._ck(LIB.pt_read_tile_state(self._h, _ptr(spp), _ptr(err), n))
         return spp, err
+
+    # -- guide buffers + a-trous denoiser (include/pt_api.h pins both)
+    def render_aovs(self, subpixels=1, specular_depth=4):
+        """Guide buffers of the current view (pt_render_aovs): albedo, normal, depth per local pixel; touches no render state."""
+        self._ck(LIB.pt_render_aovs(self._h, _ptr(self.camera), int(subpixels), int(specular_depth)))
+
+    def read_aovs(self):
+        """(albedo_rgbm, normal_depth), each (local_pixels, 4) float32: {r, g, b, material or -1}, {nx, ny, nz, depth or -1}."""
+        alb = np.empty((self.local_pixels, 4), dtype=np.float32)
+        nd = np.empty((self.local_pixels, 4), dtype=np.float32)
+        self._ck(LIB.pt_read_aovs(self._h, _ptr(alb), _ptr(nd), alb.shape[0]))
+        return alb, nd
+
+    def denoise(self, **params):
+        """pt_denoise with pt_denoise_defaults overridden by params; returns the denoised frame like read_colors()."""
+        p = DenoiseParams(**denoise_defaults())
+        for k, v in params.items():
+            if k not in p.as_dict():
+                raise TypeError("unknown denoise parameter %r" % k)
+            setattr(p, k, v)
+        self._ck(LIB.pt_denoise(self._h, C.byref(p)))
+        return self.read_denoised()
+
+    def read_denoised(self):
+        out = np.empty((self.local_pixels, 4), dtype=np.float32)
+        self._ck(LIB.pt_read_denoised(self._h, _ptr(out), out.shape[0]))
+        return out
+
+    def device_denoised(self):
+        """Device pointer of the last pt_denoise result (None before the first)."""
+        return LIB.pt_device_denoised(self._h)
 
     def sync(self):
         self._ck(LIB.pt_sync(self._h))

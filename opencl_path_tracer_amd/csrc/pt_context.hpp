@@ -128,6 +128,12 @@ struct pt_context {
     int32_t* d_adapt_list = nullptr;   // n_tiles entries, then the count word
     int32_t* h_adapt_count = nullptr;  // pinned
     bool adaptive_frame = false;       // an adaptive frame is held: pt_render / pt_trace_rays / pt_render_adaptive refuse until pt_set_current_sample(0)
+    // guide buffers (pt_render_aovs) and the a-trous filter (pt_denoise), allocated on first use: per local pixel albedo_rgbm then
+    // normal_depth (2 x npix float4); two ping-pong frames (2 x npix float4); d_denoised points at the one the last pt_denoise left
+    float4* d_aov = nullptr;
+    float4* d_dn = nullptr;
+    float4* d_denoised = nullptr;
+    bool aov_valid = false;            // pt_render_aovs ran and no pt_upload_triangles / pt_upload_materials has made its guides stale
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)

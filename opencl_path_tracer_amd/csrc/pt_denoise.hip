@@ -1,0 +1,198 @@
+// pt_denoise.hip -- guide buffers (pt_render_aovs) and the edge-avoiding a-trous filter over them (pt_denoise).
+//   k_aovs      one lane per local pixel, persistent blocks: n x n fixed sub-pixel camera rays through the render kernels'
+//               traversal (pt_device.hpp), a short deterministic specular chain, then albedo / normal / depth (include/pt_api.h)
+//   k_atrous    one launch per iteration, 32x8 blocks, 5x5 taps at step 2^i; demodulation fused into the first launch and
+//               remodulation into the last
+// The specular step below restates what shade_hit does for types 1 and 2 without the random draw; shade_hit itself is not
+// touched (every k_render instance inlines it).
+#include "pt_device.hpp"
+
+#include <algorithm>
+
+namespace ptamd {
+
+// ---------------------------------------------------------------------------- AOV pass
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spec_depth, long long npix, float4* albedo_rgbm, float4* normal_depth) {
+    LaneStack<typename StackOf<MODE>::type> stk;
+    SceneView sv;
+    setup_traversal<MODE, BLOCK>(p, &sv, &stk);
+    WorkCount wc;
+    const float fn = (float)sub;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < npix; i += (long long)gridDim.x * BLOCK) {
+        const int lrow = (int)(i / p.width), x = (int)(i % p.width);
+        const int grow = ((lrow / p.rows_per_block) * p.world + p.rank) * p.rows_per_block + lrow % p.rows_per_block;
+        const int gid = grow * p.width + x;
+        f3 sa = mk(0.f, 0.f, 0.f), sn = sa;
+        float st = 0.0f;
+        int hits = 0;
+        float mat0 = -1.0f;
+        for (int j = 0; j < sub; ++j) {
+            for (int k = 0; k < sub; ++k) {
+                f3 P, D;
+                camera_get_ray(gid, p.cam, ((float)k + 0.5f) / fn, ((float)j + 0.5f) / fn, &P, &D);
+                float t;
+                int ti = closest_hit<MODE, false>(sv, P, D, stk, &t, &wc);
+                f3 alb = mk(0.f, 0.f, 0.f), nrm = alb;
+                float mat = -1.0f;
+                if (ti >= 0) {
+                    st += t;
+                    ++hits;
+                    f3 tint = mk(1.f, 1.f, 1.f);
+                    bool inside = false;
+                    for (int d = 0;; ++d) {
+                        const float4 c = p.tris[ti * 3 + 2];
+                        f3 N = mk(c.y, c.z, c.w);
+                        const int mi = p.meta[ti].mati;
+                        const pt_material* __restrict__ m = &p.mats[mi];
+                        const int type = m->type;
+                        if (dot3(D, N) > 0.0f) N = -N;
+                        if ((type == 1 || type == 2) && d < spec_depth) {
+                            const f3 hp = madd(D, t, P);
+                            f3 dnew = D - (N * dot3(N, D)) * 2.0f;
+                            float side = 0.001f;
+                            if (type == 1) {
+                                tint = tint * ldf3(m->F0);
+                            } else {
+                                float n = m->n;
+                                if (inside) n = 1.0f / n;
+                                const float cosa = dot3(-D, N);
+                                const float disc = 1.0f - (fmaf_(-cosa, cosa, 1.0f) / n) / n;
+                                if (disc > 0.0f) {
+                                    const f3 dn = mk(D.x / n, D.y / n, D.z / n);
+                                    dnew = madd(N, cosa / n - __builtin_sqrtf(disc), dn);
+                                    inside = !inside;
+                                    side = -0.001f;
+                                }
+                            }
+                            D = normalize3(dnew);
+                            P = madd(N, side, hp);
+                            ti = closest_hit<MODE, false>(sv, P, D, stk, &t, &wc);
+                            if (ti < 0) break;          // escaped: albedo 0, normal 0
+                            continue;
+                        }
+                        const f3 a = type == 1 ? ldf3(m->F0) : type == 2 ? mk(1.f, 1.f, 1.f) : ldf3(m->kd) + ldf3(m->emission);
+                        alb = tint * a;
+                        nrm = N;
+                        mat = (float)mi;
+                        break;
+                    }
+                }
+                if (j == 0 && k == 0) mat0 = mat;
+                sa = sa + alb;
+                sn = sn + nrm;
+            }
+        }
+        const float n2 = (float)(sub * sub);
+        albedo_rgbm[i] = make_float4(sa.x / n2, sa.y / n2, sa.z / n2, mat0);
+        f3 nout = mk(0.f, 0.f, 0.f);
+        if (sn.x != 0.0f || sn.y != 0.0f || sn.z != 0.0f) {
+            const float s = 1.0f / __builtin_sqrtf((sn.x * sn.x + sn.y * sn.y) + sn.z * sn.z);
+            nout = sn * s;
+        }
+        normal_depth[i] = make_float4(nout.x, nout.y, nout.z, hits ? st / (float)hits : -1.0f);
+    }
+}
+
+template <int MODE, int BLOCK>
+static hipError_t launch_aovs_t(const RenderParams& p, int sub, int spec_depth, int64_t npix, float4* albedo, float4* nd, int cu_count, hipStream_t stream) {
+    const size_t lds = traversal_lds_bytes(p, BLOCK);
+    auto kern = k_aovs<MODE, BLOCK>;
+    static LdsMark mark;
+    const hipError_t e = ensure_dynamic_lds((const void*)kern, mark, lds);
+    if (e != hipSuccess) return e;
+    const long long need = (npix + BLOCK - 1) / BLOCK;
+    const int blocks = (int)std::min<long long>(need, (long long)cu_count * (2048 / BLOCK));
+    if (p.stack_ovf && (long long)blocks * BLOCK > (long long)p.stack_ovf_lanes) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK), lds, stream, p, sub, spec_depth, (long long)npix, albedo, nd);
+    return hipGetLastError();
+}
+
+hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
+                       int cu_count, hipStream_t stream) {
+    if (npix == 0) return hipSuccess;
+    switch (p.node_mode) {
+    case kNodesLds: return launch_aovs_t<kNodesLds, 512>(p, subpixels, specular_depth, npix, albedo_rgbm, normal_depth, cu_count, stream);
+    case kNodesGlobal: return launch_aovs_t<kNodesGlobal, 256>(p, subpixels, specular_depth, npix, albedo_rgbm, normal_depth, cu_count, stream);
+    case kNodesWide: return launch_aovs_t<kNodesWide, 256>(p, subpixels, specular_depth, npix, albedo_rgbm, normal_depth, cu_count, stream);
+    case kNodesTreelet: return launch_aovs_t<kNodesTreelet, 1024>(p, subpixels, specular_depth, npix, albedo_rgbm, normal_depth, cu_count, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------------------- a-trous iteration
+PT_DEV f3 demod(float4 c, float4 a) {
+    return mk(c.x / fmaxf(a.x, 1e-3f), c.y / fmaxf(a.y, 1e-3f), c.z / fmaxf(a.z, 1e-3f));
+}
+
+// FIRST: `in` is the context's colors, demodulated tap by tap when DEMOD; LAST: the result is remodulated when DEMOD
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) k_atrous(const float4* __restrict__ in, float4* __restrict__ out, const float4* __restrict__ albedo,
+                                                const float4* __restrict__ nd, int W, int H, AtrousStep s) {
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31);
+    const int y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= W || y >= H) return;
+    const float kern[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    const size_t ip = (size_t)y * W + x;
+    const float4 gp = nd[ip];
+    const bool miss_p = gp.w < 0.0f, zero_np = gp.x == 0.0f && gp.y == 0.0f && gp.z == 0.0f;
+    const float4 cp4 = in[ip];
+    const f3 cp = (FIRST && s.demodulate) ? demod(cp4, albedo[ip]) : mk(cp4.x, cp4.y, cp4.z);
+    f3 acc = mk(0.f, 0.f, 0.f);
+    float wsum = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + dy * s.step;
+        if (qy < 0 || qy >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * s.step;
+            if (qx < 0 || qx >= W) continue;
+            const size_t iq = (size_t)qy * W + qx;
+            const float4 gq = nd[iq];
+            const bool miss_q = gq.w < 0.0f;
+            if (miss_p != miss_q) continue;                     // w_z = 0 across a hit / miss boundary
+            const float4 cq4 = in[iq];
+            const f3 cq = (FIRST && s.demodulate) ? demod(cq4, albedo[iq]) : mk(cq4.x, cq4.y, cq4.z);
+            float w = kern[dx + 2] * kern[dy + 2];
+            if (dx == 0 && dy == 0) {                           // the centre tap: 9/64, every term 1
+                wsum += w;
+                continue;
+            }
+            if (s.color_on) {
+                const f3 dc = cp - cq;
+                const float d2 = (dc.x * dc.x + dc.y * dc.y) + dc.z * dc.z;
+                if (d2 != 0.0f) w *= expf(-(d2 * s.color_scale) / s.sigma_color2);
+            }
+            if (s.normal_on && !zero_np && !(gq.x == 0.0f && gq.y == 0.0f && gq.z == 0.0f)) {
+                const float dn = (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z;
+                w *= powf(fmaxf(dn, 0.0f), s.sigma_normal);
+            }
+            if (s.depth_on && !miss_p) {
+                const float dz = fabsf(gp.w - gq.w);
+                if (dz != 0.0f) w *= expf(-dz / (((s.sigma_depth * (float)s.step) * (float)max(abs(dx), abs(dy))) * gp.w));
+            }
+            acc = madd(cq - cp, w, acc);
+            wsum += w;
+        }
+    }
+    // x(p) + sum w (x(q) - x(p)) / sum w: the same weighted mean, and a flat neighbourhood comes out with the centre's bits
+    f3 r = mk(cp.x + acc.x / wsum, cp.y + acc.y / wsum, cp.z + acc.z / wsum);
+    if (LAST && s.demodulate) {
+        const float4 a = albedo[ip];
+        r = mk(r.x * fmaxf(a.x, 1e-3f), r.y * fmaxf(a.y, 1e-3f), r.z * fmaxf(a.z, 1e-3f));
+    }
+    out[ip] = make_float4(r.x, r.y, r.z, 1.0f);
+}
+
+hipError_t launch_atrous(const float4* in, float4* out, const float4* albedo, const float4* nd, int32_t W, int32_t H, const AtrousStep& s,
+                         bool first, bool last, hipStream_t stream) {
+    const dim3 grid((W + 31) / 32, (H + 7) / 8), block(256);
+    if (first && last) hipLaunchKernelGGL((k_atrous<true, true>), grid, block, 0, stream, in, out, albedo, nd, W, H, s);
+    else if (first) hipLaunchKernelGGL((k_atrous<true, false>), grid, block, 0, stream, in, out, albedo, nd, W, H, s);
+    else if (last) hipLaunchKernelGGL((k_atrous<false, true>), grid, block, 0, stream, in, out, albedo, nd, W, H, s);
+    else hipLaunchKernelGGL((k_atrous<false, false>), grid, block, 0, stream, in, out, albedo, nd, W, H, s);
+    return hipGetLastError();
+}
+
+}  // namespace ptamd

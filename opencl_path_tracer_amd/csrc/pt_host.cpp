@@ -231,6 +231,8 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->d_adapt_active) (void)hipFree(ctx->d_adapt_active);
         if (ctx->d_adapt_list) (void)hipFree(ctx->d_adapt_list);
         if (ctx->h_adapt_count) (void)hipHostFree(ctx->h_adapt_count);
+        if (ctx->d_aov) (void)hipFree(ctx->d_aov);
+        if (ctx->d_dn) (void)hipFree(ctx->d_dn);
         if (ctx->d_wf_state) (void)hipFree(ctx->d_wf_state);
         if (ctx->d_wf_queues) (void)hipFree(ctx->d_wf_queues);
         if (ctx->d_wf_counters) (void)hipFree(ctx->d_wf_counters);
@@ -276,6 +278,7 @@ int pt_add_triangles(pt_context* ctx, const pt_triangle* t, int64_t n) {
 
 int pt_upload_materials(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
+    ctx->aov_valid = false;
     for (const pt_triangle& t : ctx->tris)
         if (t.mati >= ctx->mats.size()) return fail(ctx, PT_EINVAL, "a triangle references a material index that was never added");
     if (ctx->has_device) {
@@ -456,6 +459,78 @@ int pt_read_tile_state(pt_context* ctx, int32_t* spp, float* err, int64_t n_tile
     if (err && (rc = read_back(ctx, err, ctx->d_adapt_err, sizeof(float) * (size_t)n_tiles)) != PT_OK) return rc;
     return PT_OK;
 }
+// ---- guide buffers + a-trous denoiser (kernels: pt_denoise.hip; the filter is pinned in include/pt_api.h)
+int pt_render_aovs(pt_context* ctx, const pt_camera* cam, int32_t subpixels, int32_t specular_depth) {
+    if (!ctx) return PT_EINVAL;
+    if (subpixels < 1 || subpixels > 8) return fail(ctx, PT_EINVAL, "pt_render_aovs: subpixels must be 1..8");
+    if (specular_depth < 0 || specular_depth > 16) return fail(ctx, PT_EINVAL, "pt_render_aovs: specular_depth must be 0..16");
+    PT_NEED_DEVICE(ctx);
+    int rc = check_ready(ctx, cam);
+    if (rc != PT_OK) return rc;
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_aov) PT_HIP(ctx, hipMalloc((void**)&ctx->d_aov, 2 * sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
+    RenderParams p;
+    fill_params(ctx, cam, &p);         // the render kernels' node placement
+    PT_HIP(ctx, launch_aovs(p, subpixels, specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, ctx->cu_count, ctx->stream));
+    ctx->aov_valid = true;
+    return PT_OK;
+}
+int pt_read_aovs(pt_context* ctx, float* albedo_rgbm, float* normal_depth, int64_t npix) {
+    PT_NEED_DEVICE(ctx);
+    if (npix != ctx->npix) return fail(ctx, PT_EINVAL, "npix must equal the local pixel count");
+    if (!ctx->d_aov) return fail(ctx, PT_EINVAL, "pt_read_aovs: pt_render_aovs has not run");
+    int rc = PT_OK;
+    if (albedo_rgbm && (rc = read_back(ctx, albedo_rgbm, ctx->d_aov, sizeof(float4) * (size_t)npix)) != PT_OK) return rc;
+    if (normal_depth && (rc = read_back(ctx, normal_depth, ctx->d_aov + npix, sizeof(float4) * (size_t)npix)) != PT_OK) return rc;
+    return PT_OK;
+}
+void pt_denoise_defaults(pt_denoise_params* p) {
+    if (!p) return;
+    p->iterations = 3;
+    p->sigma_color = 0.125f;
+    p->sigma_normal = 8.0f;
+    p->sigma_depth = 0.05f;
+    p->demodulate = 1;
+}
+int pt_denoise(pt_context* ctx, const pt_denoise_params* dp) {
+    if (!ctx) return PT_EINVAL;
+    if (!dp) return fail(ctx, PT_EINVAL, "pt_denoise: params is NULL");
+    if (dp->iterations < 1 || dp->iterations > 10) return fail(ctx, PT_EINVAL, "pt_denoise: iterations must be 1..10");
+    if (!(dp->sigma_color >= 0.0f) || !(dp->sigma_normal >= 0.0f) || !(dp->sigma_depth >= 0.0f))
+        return fail(ctx, PT_EINVAL, "pt_denoise: sigmas must be >= 0 (and not NaN)");
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_denoise: contexts of one rank (world == 1) only");
+    if (!ctx->aov_valid)
+        return fail(ctx, PT_EINVAL, "pt_denoise: no guides (pt_render_aovs has not run since the scene was last uploaded)");
+    PT_NEED_DEVICE(ctx);
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->npix;
+    if (!ctx->d_dn) PT_HIP(ctx, hipMalloc((void**)&ctx->d_dn, 2 * sizeof(float4) * std::max<size_t>(npix, 1)));
+    for (int i = 0; i < dp->iterations; ++i) {
+        AtrousStep s;
+        s.step = 1 << i;
+        s.demodulate = dp->demodulate ? 1 : 0;
+        s.color_on = std::isfinite(dp->sigma_color) ? 1 : 0;
+        s.normal_on = std::isfinite(dp->sigma_normal) && dp->sigma_normal > 0.0f ? 1 : 0;
+        s.depth_on = std::isfinite(dp->sigma_depth) ? 1 : 0;
+        s.color_scale = (float)(1 << (2 * i));
+        s.sigma_color2 = dp->sigma_color * dp->sigma_color;
+        s.sigma_normal = dp->sigma_normal;
+        s.sigma_depth = dp->sigma_depth;
+        const float4* in = i == 0 ? ctx->d_colors : ctx->d_dn + ((i - 1) & 1) * npix;
+        float4* out = ctx->d_dn + (i & 1) * npix;
+        PT_HIP(ctx, launch_atrous(in, out, ctx->d_aov, ctx->d_aov + npix, ctx->W, ctx->local_rows, s, i == 0, i == dp->iterations - 1, ctx->stream));
+    }
+    ctx->d_denoised = ctx->d_dn + ((dp->iterations - 1) & 1) * npix;
+    return PT_OK;
+}
+int pt_read_denoised(pt_context* ctx, float* out, int64_t npix) {
+    PT_NEED_DEVICE(ctx);
+    if (!out || npix != ctx->npix) return fail(ctx, PT_EINVAL, "npix must equal the local pixel count");
+    if (!ctx->d_denoised) return fail(ctx, PT_EINVAL, "pt_read_denoised: pt_denoise has not run");
+    return read_back(ctx, out, ctx->d_denoised, sizeof(float4) * (size_t)npix);
+}
+void* pt_device_denoised(pt_context* ctx) { return ctx ? (void*)ctx->d_denoised : nullptr; }
+
 int pt_read_rays(pt_context* ctx, pt_ray* out, int64_t npix) {
     PT_NEED_DEVICE(ctx);
     if (!out || npix != ctx->npix) return fail(ctx, PT_EINVAL, "npix must equal the local pixel count");

@@ -311,5 +311,18 @@ hipError_t launch_adaptive_tiles(const float4* colors, float4* snap, const int32
 // the frame tiles whose flag is set, ascending, into list[0, *count) (one workgroup)
 hipError_t launch_compact_tiles(const uint8_t* active, int32_t n, int32_t* list, int32_t* count, hipStream_t stream);
 hipError_t launch_debug_closest_hit(const RenderParams& p, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri, int cu_count, hipStream_t stream);
+// guide buffers and the a-trous filter (pt_denoise.hip; the filter is pinned in include/pt_api.h next to pt_denoise)
+hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
+                       int cu_count, hipStream_t stream);
+struct AtrousStep {
+    int32_t step;            // 2^i
+    int32_t demodulate;
+    int32_t color_on, normal_on, depth_on;   // 0: that weight is 1 (sigma +inf; sigma_normal 0)
+    float color_scale;       // 4^i
+    float sigma_color2, sigma_normal, sigma_depth;
+};
+// one iteration: first reads colors (demodulated when s.demodulate), last remodulates; out must not alias in
+hipError_t launch_atrous(const float4* in, float4* out, const float4* albedo, const float4* nd, int32_t W, int32_t H, const AtrousStep& s,
+                         bool first, bool last, hipStream_t stream);
 
 }  // namespace ptamd
