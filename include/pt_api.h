@@ -156,6 +156,45 @@ int pt_read_rays(pt_context* ctx, pt_ray* out, int64_t npix);        /* buffer_r
  * prog.cl:380); which = 0 Reinhard, 1 = filt_im (3x3 median + filmic, prog.cl:391-427). */
 int pt_resolve_ldr(pt_context* ctx, int32_t which, float* out_rgba, int64_t npix);
 
+/* ---- next-event estimation with multiple importance sampling (new: opt-in; pt_render is unchanged) -------------------
+ * The estimator of pt_render (prog.cl:292-389), per sample: a lobe vertex (type 0 diffuse, type 3 emitter) draws w with
+ * pdf p_b(w) = max(0, N.w) / pi (two LCG values); type 0 then does fL *= kd max(0, N.w), fB *= ks pow(max(0, N.h), shininess)
+ * with h = normalize(normalize(eye - x) + w) (the CAMERA eye), type 3 leaves the factors; an emitter hit at y adds
+ * E (fL + fB) fS fR |cos_y|; types 1 / 2 change fS / fR only; iterations segments; iterations == 1 is the flat preview.
+ * pt_render_nee keeps that LCG stream draw for draw -- rnds and rays after a frame are pt_render's in every strategy -- and
+ * adds, at a lobe vertex x of segment k with k + 1 < iterations, a light sample:
+ *   u0, u1, u2 = pt_nee_rand(S, k, 0 / 1 / 2) >> 8 times 2^-24, S = the pixel's LCG state at the start of the sample;
+ *   light j = the first index with cdf[j] > u0 (pt_debug_light_table), su = sqrt(u1),
+ *   y = r1 + (r2 - r1) (u2 su) + (r3 - r1) (su (1 - u2)) on that triangle;
+ *   o = x + 0.001 N (the origin the BSDF ray uses), d = y - o, r = |d|, w = d / r;
+ *   y is visible iff the closest hit of (o, w) with the search cut at 1.0001 r is that triangle;
+ *   p_b = max(0, N.w) / pi, p_l = (P_sel / area)(tri) r^2 / |cos_y|, both > 0 or no contribution;
+ *   contribution = E_y (fL' + fB') fS fR |cos_y| times W_l, fL' / fB' = the factors x's own update with w would give;
+ * and every emitter hit on segment k + 1 after a lobe vertex x on segment k (BSDF-sampled, p_b from x's normal and the
+ * ray, p_l with r = the hit distance from x's offset origin and P_sel / area of the hit triangle, 0 for a non-light) has
+ * its addition times W_b.  A hit seen from the camera or through mirror / glass vertices only keeps W_b = 1.
+ *   PT_NEE_BSDF   W_b = 1, no light sample: exactly pt_render's estimator (same bits)
+ *   PT_NEE_LIGHT  W_b = 0 if p_l > 0 else 1,          W_l = p_b / p_l
+ *   PT_NEE_MIS    W_b = p_b^2 / (p_b^2 + p_l^2),      W_l = p_b p_l / (p_b^2 + p_l^2)   (power heuristic; W_l includes p_b / p_l)
+ * All three have pt_render's expectation.  Light table (built on the host at the first pt_render_nee after an upload): the
+ * packed triangles of type-3 material with E.r + E.g + E.b > 0 and non-zero area (in packed order), cdf in float (last entry 1)
+ * proportional to the running sum of area (E.r + E.g + E.b); P_sel in p_l and in the weights is the probability the 24-bit u0
+ * actually picks the light with: (ceil(cdf[j] 2^24) - ceil(cdf[j-1] 2^24)) / 2^24 (0: never picked, p_l = 0 for its hits).
+ * No lights: every strategy is PT_NEE_BSDF.
+ * Same rules as pt_render: argument checks (iterations >= 0, nsamples >= 0, strategy 0..2, else PT_EINVAL), advances
+ * current_sample by nsamples, running mean into colors (or the bound framebuffer), refused while an adaptive frame is held,
+ * any rank of a tiled frame, any variant (one launch of k_nee, pt_nee.hip). */
+#define PT_NEE_BSDF 0
+#define PT_NEE_LIGHT 1
+#define PT_NEE_MIS 2
+int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples, int32_t strategy);
+/* lowbias32(x) = x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16;
+ * pt_nee_rand(state, segment, dim) = lowbias32(lowbias32(state) + 0x9e3779b9 * (3 segment + dim + 1)) (uint32 arithmetic) */
+uint32_t pt_nee_rand(uint32_t state, int32_t segment, int32_t dim);
+/* the light table (host only, any context with triangles and materials uploaded): *n = lights; the first min(cap, *n) of
+ * orig_tri (add-order triangle index) and cdf are written (either may be NULL) */
+int pt_debug_light_table(pt_context* ctx, int32_t* orig_tri, float* cdf, int64_t cap, int64_t* n);
+
 /* ---- guide buffers and an edge-avoiding a-trous denoiser (new: the reference has no denoiser) ------------------------
  * Guide buffers ("AOVs") of the frame seen through cam.  Per local pixel, subpixels x subpixels (1..8) camera rays with the
  * sub-pixel offsets rnd1 = ((float)i + 0.5f) / (float)n, rnd2 = ((float)j + 0.5f) / (float)n fed to camera_get_ray

@@ -109,6 +109,11 @@ public:
         camera = Camera(globals);
         ck(pt_render_adaptive(ctx, &camera, globals.iterations, min_spp, max_spp, threshold));
     }
+    // nsamples of render(n)'s estimator with next-event estimation (pt_render_nee; strategy PT_NEE_BSDF / _LIGHT / _MIS)
+    void render_nee(int nsamples, int strategy = PT_NEE_MIS) {
+        camera = Camera(globals);
+        ck(pt_render_nee(ctx, &camera, globals.iterations, nsamples, strategy));
+    }
     // guide buffers of the current view (pt_render_aovs) and the a-trous filter over them (pt_denoise; p = NULL: the defaults)
     // (the view of the last render: a new Camera(globals) would move a moving camera once more)
     void render_aovs(int subpixels = 1, int specular_depth = 4) {

@@ -45,6 +45,7 @@ EXPORTS = [
     "pt_add_obj", "pt_upload_triangles", "pt_upload_materials", "pt_seed_default", "pt_upload_seeds",
     "pt_generate_rays", "pt_trace_rays", "pt_render", "pt_render_adaptive", "pt_read_sample_counts", "pt_read_tile_state", "pt_adaptive_rounds",
     "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
+    "pt_render_nee", "pt_nee_rand", "pt_debug_light_table",
     "pt_render_aovs", "pt_read_aovs", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
@@ -100,6 +101,9 @@ def _load():
     sig("pt_read_sample_counts", C.c_int, vp, vp, i64)
     sig("pt_read_tile_state", C.c_int, vp, vp, vp, i64)
     sig("pt_adaptive_rounds", C.c_int, i32, i32, vp, i32, C.POINTER(i32))
+    sig("pt_render_nee", C.c_int, vp, vp, i32, i32, i32)
+    sig("pt_nee_rand", C.c_uint32, C.c_uint32, i32, i32)
+    sig("pt_debug_light_table", C.c_int, vp, vp, vp, i64, C.POINTER(i64))
     sig("pt_render_aovs", C.c_int, vp, vp, i32, i32)
     sig("pt_read_aovs", C.c_int, vp, vp, vp, i64)
     sig("pt_denoise_defaults", None, vp)
@@ -207,6 +211,15 @@ def adaptive_rounds(min_spp, max_spp):
     if rc != PT_OK:
         raise PtError(rc, (LIB.pt_last_error(None) or b"").decode())
     return [int(v) for v in out]
+
+
+PT_NEE_BSDF, PT_NEE_LIGHT, PT_NEE_MIS = 0, 1, 2
+NEE_STRATEGIES = {"bsdf": PT_NEE_BSDF, "light": PT_NEE_LIGHT, "mis": PT_NEE_MIS}
+
+
+def nee_rand(state, segment, dim):
+    """pt_nee_rand: the counter-based hash the light samples of Scene.render_nee draw from (include/pt_api.h pins it)."""
+    return int(LIB.pt_nee_rand(int(state) & 0xffffffff, int(segment), int(dim)))
 
 
 class DenoiseParams(C.Structure):
@@ -405,6 +418,22 @@ class Scene:
         err = np.empty(n, dtype=np.float32)
         self._ck(LIB.pt_read_tile_state(self._h, _ptr(spp), _ptr(err), n))
         return spp, err
+
+    # -- next-event estimation with MIS (include/pt_api.h pins the estimator)
+    def render_nee(self, nsamples=1, strategy="mis"):
+        """nsamples samples of pt_render's estimator with explicit light sampling (pt_render_nee), into the same running mean.
+        strategy: "bsdf" (exactly render()), "light" or "mis" (or PT_NEE_*).  rnds and rays end as render() leaves them."""
+        code = NEE_STRATEGIES[strategy] if isinstance(strategy, str) else int(strategy)
+        self._ck(LIB.pt_render_nee(self._h, _ptr(self.camera), self.iterations, int(nsamples), code))
+
+    def debug_light_table(self):
+        """(orig_tri int32, cdf float32): the lights pt_render_nee samples, in packed order, with their add-order triangle index."""
+        n = C.c_int64()
+        self._ck(LIB.pt_debug_light_table(self._h, None, None, 0, C.byref(n)))
+        tri = np.zeros(n.value, dtype=np.int32)
+        cdf = np.zeros(n.value, dtype=np.float32)
+        self._ck(LIB.pt_debug_light_table(self._h, _ptr(tri), _ptr(cdf), n.value, C.byref(n)))
+        return tri, cdf
 
     # -- guide buffers + a-trous denoiser (include/pt_api.h pins both)
     def render_aovs(self, subpixels=1, specular_depth=4):

@@ -1145,6 +1145,7 @@ static void compute_cost_boxes(pt_context* ctx) { compute_cost_boxes_impl(ctx); 
 int pt_upload_triangles(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
     ctx->aov_valid = false;          // the guides of pt_render_aovs describe the old scene
+    ctx->nee_valid = false;          // and the light table its packed order
     if (ctx->tri_shift != (int32_t)ctx->tris.size())
         return fail(ctx, PT_EINVAL, "triangles were added after the last end_Obj; close the object first (main.cpp:536)");
     const auto t0 = std::chrono::steady_clock::now();

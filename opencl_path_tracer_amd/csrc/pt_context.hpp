@@ -134,6 +134,16 @@ struct pt_context {
     float4* d_dn = nullptr;
     float4* d_denoised = nullptr;
     bool aov_valid = false;            // pt_render_aovs ran and no pt_upload_triangles / pt_upload_materials has made its guides stale
+    // next-event estimation (pt_render_nee): the light table, built on the host at first use after an upload (nee_valid).  Packed
+    // triangle index and cdf per light; P_sel / area per packed triangle (0 for non-lights).  Device copies allocated with it.
+    std::vector<int32_t> nee_tri;
+    std::vector<float> nee_cdf;
+    std::vector<float> nee_pdf_area;
+    bool nee_valid = false;
+    int32_t* d_nee_tri = nullptr;
+    float* d_nee_cdf = nullptr;
+    float* d_nee_pdf_area = nullptr;
+    bool nee_uploaded = false;         // the device copies hold the current table
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)

@@ -233,6 +233,9 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->h_adapt_count) (void)hipHostFree(ctx->h_adapt_count);
         if (ctx->d_aov) (void)hipFree(ctx->d_aov);
         if (ctx->d_dn) (void)hipFree(ctx->d_dn);
+        if (ctx->d_nee_tri) (void)hipFree(ctx->d_nee_tri);
+        if (ctx->d_nee_cdf) (void)hipFree(ctx->d_nee_cdf);
+        if (ctx->d_nee_pdf_area) (void)hipFree(ctx->d_nee_pdf_area);
         if (ctx->d_wf_state) (void)hipFree(ctx->d_wf_state);
         if (ctx->d_wf_queues) (void)hipFree(ctx->d_wf_queues);
         if (ctx->d_wf_counters) (void)hipFree(ctx->d_wf_counters);
@@ -279,6 +282,7 @@ int pt_add_triangles(pt_context* ctx, const pt_triangle* t, int64_t n) {
 int pt_upload_materials(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
     ctx->aov_valid = false;
+    ctx->nee_valid = false;          // the light table reads emission and type
     for (const pt_triangle& t : ctx->tris)
         if (t.mati >= ctx->mats.size()) return fail(ctx, PT_EINVAL, "a triangle references a material index that was never added");
     if (ctx->has_device) {
@@ -530,6 +534,126 @@ int pt_read_denoised(pt_context* ctx, float* out, int64_t npix) {
     return read_back(ctx, out, ctx->d_denoised, sizeof(float4) * (size_t)npix);
 }
 void* pt_device_denoised(pt_context* ctx) { return ctx ? (void*)ctx->d_denoised : nullptr; }
+
+// ---- next-event estimation (kernel: pt_nee.hip; the estimator is pinned in include/pt_api.h)
+uint32_t pt_nee_rand(uint32_t state, int32_t segment, int32_t dim) {
+    auto lowbias32 = [](uint32_t x) {
+        x ^= x >> 16;
+        x *= 0x7feb352du;
+        x ^= x >> 15;
+        x *= 0x846ca68bu;
+        x ^= x >> 16;
+        return x;
+    };
+    return lowbias32(lowbias32(state) + 0x9e3779b9u * (uint32_t)(3 * segment + dim + 1));
+}
+// The light table of the uploaded scene, in packed order: type-3 triangles with E.r + E.g + E.b > 0 and non-zero area, P_sel
+// proportional to area x (E.r + E.g + E.b) (summed and normalised in double, then rounded; the last cdf entry is 1)
+static int nee_table(pt_context* ctx) {
+    if (!ctx->tris_uploaded) return fail(ctx, PT_EINVAL, "pt_upload_triangles has not been called");
+    if (!ctx->mats_uploaded) return fail(ctx, PT_EINVAL, "pt_upload_materials has not been called");
+    if (ctx->nee_valid) return PT_OK;
+    const size_t m = ctx->orig.size();
+    std::vector<double> wgt, area;
+    ctx->nee_tri.clear();
+    ctx->nee_cdf.clear();
+    ctx->nee_pdf_area.assign(std::max<size_t>(m, 1), 0.0f);
+    for (size_t k = 0; k < m; ++k) {
+        const pt_triangle& t = ctx->tris[(size_t)ctx->orig[k]];
+        const pt_material& mt = ctx->mats[t.mati];
+        if (mt.type != 3) continue;
+        const double esum = ((double)mt.emission.s[0] + (double)mt.emission.s[1]) + (double)mt.emission.s[2];
+        const double e1[3] = {(double)t.r2.s[0] - t.r1.s[0], (double)t.r2.s[1] - t.r1.s[1], (double)t.r2.s[2] - t.r1.s[2]};
+        const double e2[3] = {(double)t.r3.s[0] - t.r1.s[0], (double)t.r3.s[1] - t.r1.s[1], (double)t.r3.s[2] - t.r1.s[2]};
+        const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+        const double a = 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz);
+        if (!(esum > 0.0) || !(a > 0.0) || !std::isfinite(a * esum)) continue;
+        ctx->nee_tri.push_back((int32_t)k);
+        wgt.push_back(a * esum);
+        area.push_back(a);
+    }
+    double total = 0.0;
+    for (double w : wgt) total += w;
+    double run = 0.0;
+    for (size_t j = 0; j < wgt.size(); ++j) {
+        run += wgt[j];
+        ctx->nee_cdf.push_back(j + 1 == wgt.size() ? 1.0f : (float)(run / total));
+    }
+    // P_sel as the kernel samples it, not as the weights ask for it: u0 = m 2^-24 (m < 2^24) picks light j iff
+    // cdf[j-1] <= u0 < cdf[j], i.e. for ceil(cdf[j] 2^24) - ceil(cdf[j-1] 2^24) values of m.  (A light whose share rounds to no
+    // value of m is never picked: its P_sel / area is 0, and the BSDF strategy keeps its hits at weight 1.)
+    double below = 0.0;
+    for (size_t j = 0; j < wgt.size(); ++j) {
+        const double upto = std::ceil((double)ctx->nee_cdf[j] * 16777216.0);
+        ctx->nee_pdf_area[(size_t)ctx->nee_tri[j]] = (float)((upto - below) / 16777216.0 / area[j]);
+        below = upto;
+    }
+    ctx->nee_valid = true;
+    ctx->nee_uploaded = false;
+    return PT_OK;
+}
+int pt_debug_light_table(pt_context* ctx, int32_t* orig_tri, float* cdf, int64_t cap, int64_t* n) {
+    if (!ctx) return PT_EINVAL;
+    if (!n || cap < 0) return fail(ctx, PT_EINVAL, "pt_debug_light_table: n is NULL or cap < 0");
+    int rc = nee_table(ctx);
+    if (rc != PT_OK) return rc;
+    *n = (int64_t)ctx->nee_tri.size();
+    const size_t k = (size_t)std::min<int64_t>(cap, *n);
+    for (size_t j = 0; j < k; ++j) {
+        if (orig_tri) orig_tri[j] = ctx->orig[(size_t)ctx->nee_tri[j]];
+        if (cdf) cdf[j] = ctx->nee_cdf[j];
+    }
+    return PT_OK;
+}
+int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples, int32_t strategy) {
+    if (!ctx) return PT_EINVAL;
+    if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "pt_render_nee: iterations/nsamples must be >= 0");
+    if (strategy < PT_NEE_BSDF || strategy > PT_NEE_MIS) return fail(ctx, PT_EINVAL, "pt_render_nee: strategy must be PT_NEE_BSDF, PT_NEE_LIGHT or PT_NEE_MIS");
+    PT_NEED_DEVICE(ctx);
+    int rc = check_ready(ctx, cam);
+    if (rc != PT_OK) return rc;
+    if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "pt_render_nee: an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
+    if ((int64_t)ctx->current_sample + nsamples > INT32_MAX) return fail(ctx, PT_EINVAL, "pt_render_nee: current_sample + nsamples overflows");
+    if (nsamples == 0) return PT_OK;
+    if ((rc = nee_table(ctx)) != PT_OK) return rc;
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->nee_uploaded) {
+        if (ctx->d_nee_tri) PT_HIP(ctx, hipFree(ctx->d_nee_tri));
+        if (ctx->d_nee_cdf) PT_HIP(ctx, hipFree(ctx->d_nee_cdf));
+        if (ctx->d_nee_pdf_area) PT_HIP(ctx, hipFree(ctx->d_nee_pdf_area));
+        ctx->d_nee_tri = nullptr;
+        ctx->d_nee_cdf = nullptr;
+        ctx->d_nee_pdf_area = nullptr;
+        const size_t nl = std::max<size_t>(ctx->nee_tri.size(), 1);
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_nee_tri, sizeof(int32_t) * nl));
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_nee_cdf, sizeof(float) * nl));
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_nee_pdf_area, sizeof(float) * ctx->nee_pdf_area.size()));
+        if (!ctx->nee_tri.empty()) {
+            PT_HIP(ctx, hipMemcpy(ctx->d_nee_tri, ctx->nee_tri.data(), sizeof(int32_t) * ctx->nee_tri.size(), hipMemcpyHostToDevice));
+            PT_HIP(ctx, hipMemcpy(ctx->d_nee_cdf, ctx->nee_cdf.data(), sizeof(float) * ctx->nee_cdf.size(), hipMemcpyHostToDevice));
+        }
+        PT_HIP(ctx, hipMemcpy(ctx->d_nee_pdf_area, ctx->nee_pdf_area.data(), sizeof(float) * ctx->nee_pdf_area.size(), hipMemcpyHostToDevice));
+        ctx->nee_uploaded = true;
+    }
+    RenderParams p;
+    fill_params(ctx, cam, &p);         // the render kernels' node placement
+    p.iterations = iterations;
+    p.first_sample = ctx->current_sample;
+    p.nsamples = nsamples;
+    NeeTable lt;
+    lt.tri = ctx->d_nee_tri;
+    lt.cdf = ctx->d_nee_cdf;
+    lt.pdf_area = ctx->d_nee_pdf_area;
+    lt.n = (int32_t)ctx->nee_tri.size();
+    lt.strategy = strategy;
+    ctx->render_epoch++;
+    EventPair* ep;
+    if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
+    PT_HIP(ctx, launch_nee(p, lt, ctx->npix, ctx->cu_count, ctx->stream));
+    if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
+    ctx->current_sample += nsamples;
+    return PT_OK;
+}
 
 int pt_read_rays(pt_context* ctx, pt_ray* out, int64_t npix) {
     PT_NEED_DEVICE(ctx);

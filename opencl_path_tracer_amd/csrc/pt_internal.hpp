@@ -322,6 +322,15 @@ struct AtrousStep {
     float sigma_color2, sigma_normal, sigma_depth;
 };
 // one iteration: first reads colors (demodulated when s.demodulate), last remodulates; out must not alias in
+// next-event estimation (pt_nee.hip; the estimator is pinned in include/pt_api.h next to pt_render_nee)
+struct NeeTable {
+    const int32_t* tri;          // [n] packed triangle of each light
+    const float* cdf;            // [n]
+    const float* pdf_area;       // [packed triangles] P_sel / area, 0 for non-lights
+    int32_t n;                   // 0: no lights (every strategy is PT_NEE_BSDF)
+    int32_t strategy;
+};
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, int64_t npix, int cu_count, hipStream_t stream);
 hipError_t launch_atrous(const float4* in, float4* out, const float4* albedo, const float4* nd, int32_t W, int32_t H, const AtrousStep& s,
                          bool first, bool last, hipStream_t stream);
 
