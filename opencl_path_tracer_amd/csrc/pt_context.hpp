@@ -304,9 +304,6 @@ int reindex_treelet(std::vector<Node64>& nodes, int interior_depth, int want);
 
 // ---- pt_launch.cpp
 int32_t count_local_rows(int32_t H, int32_t rank, int32_t world, int32_t rb);
-inline int32_t global_row(const pt_context* c, int32_t lrow) {
-    return ((lrow / c->rows_per_block) * c->world + c->rank) * c->rows_per_block + (lrow % c->rows_per_block);
-}
 int wide_stack_entries(int pending);
 int stack_entries_for(int interior_depth);
 bool whole_tree_fits_lds(size_t n_nodes, size_t n_tris, int interior_depth, int n_flat);

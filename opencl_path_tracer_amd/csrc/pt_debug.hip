@@ -2,8 +2,6 @@
 // same traversal code (pt_device.hpp) and the same node placement the render kernels use.
 #include "pt_device.hpp"
 
-#include <algorithm>
-
 namespace ptamd {
 
 // persistent blocks, grid-stride over the rays; one ray per lane at a time
@@ -23,29 +21,8 @@ __global__ void __launch_bounds__(BLOCK) k_debug_closest_hit(RenderParams p, con
     }
 }
 
-template <int MODE, int BLOCK>
-static hipError_t launch_debug_t(const RenderParams& p, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri, int cu_count, hipStream_t stream) {
-    const size_t lds = traversal_lds_bytes(p, BLOCK);
-    auto kern = k_debug_closest_hit<MODE, BLOCK>;
-    static LdsMark mark;
-    const hipError_t e = ensure_dynamic_lds((const void*)kern, mark, lds);
-    if (e != hipSuccess) return e;
-    const long long need = (n + BLOCK - 1) / BLOCK;
-    const int blocks = (int)std::min<long long>(need, (long long)cu_count * (2048 / BLOCK));
-    if (p.stack_ovf && (long long)blocks * BLOCK > (long long)p.stack_ovf_lanes) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK), lds, stream, p, rays, (long long)n, out_t, out_tri);
-    return hipGetLastError();
-}
-
 hipError_t launch_debug_closest_hit(const RenderParams& p, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri, int cu_count, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    switch (p.node_mode) {
-    case kNodesLds: return launch_debug_t<kNodesLds, 512>(p, rays, n, out_t, out_tri, cu_count, stream);
-    case kNodesGlobal: return launch_debug_t<kNodesGlobal, 256>(p, rays, n, out_t, out_tri, cu_count, stream);
-    case kNodesWide: return launch_debug_t<kNodesWide, 256>(p, rays, n, out_t, out_tri, cu_count, stream);
-    case kNodesTreelet: return launch_debug_t<kNodesTreelet, 1024>(p, rays, n, out_t, out_tri, cu_count, stream);
-    }
-    return hipErrorInvalidValue;
+    return launch_lanes([](auto s) { return k_debug_closest_hit<s.mode, s.block>; }, p, n, cu_count, stream, rays, (long long)n, out_t, out_tri);
 }
 
 }  // namespace ptamd

@@ -3,11 +3,8 @@
 //               traversal (pt_device.hpp), a short deterministic specular chain, then albedo / normal / depth (include/pt_api.h)
 //   k_atrous    one launch per iteration, 32x8 blocks, 5x5 taps at step 2^i; demodulation fused into the first launch and
 //               remodulation into the last
-// The specular step below restates what shade_hit does for types 1 and 2 without the random draw; shade_hit itself is not
-// touched (every k_render instance inlines it).
+// The specular step below restates what shade_hit does for types 1 and 2 without the random draw.
 #include "pt_device.hpp"
-
-#include <algorithm>
 
 namespace ptamd {
 
@@ -21,7 +18,7 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
     const float fn = (float)sub;
     for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < npix; i += (long long)gridDim.x * BLOCK) {
         const int lrow = (int)(i / p.width), x = (int)(i % p.width);
-        const int grow = ((lrow / p.rows_per_block) * p.world + p.rank) * p.rows_per_block + lrow % p.rows_per_block;
+        const int grow = global_row(p, lrow);
         const int gid = grow * p.width + x;
         f3 sa = mk(0.f, 0.f, 0.f), sn = sa;
         float st = 0.0f;
@@ -94,30 +91,10 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
     }
 }
 
-template <int MODE, int BLOCK>
-static hipError_t launch_aovs_t(const RenderParams& p, int sub, int spec_depth, int64_t npix, float4* albedo, float4* nd, int cu_count, hipStream_t stream) {
-    const size_t lds = traversal_lds_bytes(p, BLOCK);
-    auto kern = k_aovs<MODE, BLOCK>;
-    static LdsMark mark;
-    const hipError_t e = ensure_dynamic_lds((const void*)kern, mark, lds);
-    if (e != hipSuccess) return e;
-    const long long need = (npix + BLOCK - 1) / BLOCK;
-    const int blocks = (int)std::min<long long>(need, (long long)cu_count * (2048 / BLOCK));
-    if (p.stack_ovf && (long long)blocks * BLOCK > (long long)p.stack_ovf_lanes) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK), lds, stream, p, sub, spec_depth, (long long)npix, albedo, nd);
-    return hipGetLastError();
-}
-
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
                        int cu_count, hipStream_t stream) {
-    if (npix == 0) return hipSuccess;
-    switch (p.node_mode) {
-    case kNodesLds: return launch_aovs_t<kNodesLds, 512>(p, subpixels, specular_depth, npix, albedo_rgbm, normal_depth, cu_count, stream);
-    case kNodesGlobal: return launch_aovs_t<kNodesGlobal, 256>(p, subpixels, specular_depth, npix, albedo_rgbm, normal_depth, cu_count, stream);
-    case kNodesWide: return launch_aovs_t<kNodesWide, 256>(p, subpixels, specular_depth, npix, albedo_rgbm, normal_depth, cu_count, stream);
-    case kNodesTreelet: return launch_aovs_t<kNodesTreelet, 1024>(p, subpixels, specular_depth, npix, albedo_rgbm, normal_depth, cu_count, stream);
-    }
-    return hipErrorInvalidValue;
+    return launch_lanes([](auto s) { return k_aovs<s.mode, s.block>; }, p, npix, cu_count, stream, subpixels, specular_depth, (long long)npix,
+                        albedo_rgbm, normal_depth);
 }
 
 // ---------------------------------------------------------------------------- a-trous iteration

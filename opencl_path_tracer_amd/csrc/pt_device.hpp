@@ -1,6 +1,7 @@
 // pt_device.hpp -- gfx950 device code shared by the kernel translation units of libptamd.so
 // (pt_kernels.hip: megakernel; pt_wavefront.hip: stream-compacted variant; pt_debug.hip: test entry
-// points).  Everything here is __device__ __forceinline__.
+// points).  Everything here is __device__ __forceinline__, except the host launcher of the per-lane
+// traversal kernels (launch_lanes).
 //
 // Arithmetic: compiled with -ffp-contract=off; the only fused operations are the explicit fma calls,
 // placed as DESIGN.md section 3 prescribes, so that results can be compared bit for bit with the CPU
@@ -11,6 +12,8 @@
 #pragma once
 
 #include "pt_internal.hpp"
+
+#include <algorithm>
 
 // A/B switch of the slab test for nodes read from global memory (1: one fma per plane, planes picked
 // by the sign of the direction; 0: round 1's (plane - P) * inv with min/max)
@@ -222,7 +225,7 @@ PT_DEV PixelId pixel_of_wave(const RenderParams& p, int wave) {
         r.gid = 0;
         return r;
     }
-    const int grow = ((lrow / p.rows_per_block) * p.world + p.rank) * p.rows_per_block + (lrow % p.rows_per_block);
+    const int grow = global_row(p, lrow);
     r.li = lrow * p.width + x;
     r.gid = grow * p.width + x;
     return r;
@@ -970,10 +973,18 @@ struct PathRegs {
     PT_DEV void setC(f3 v) { color = v; }
 };
 
+// The light hook of shade_hit: three points in the segment body where k_nee (pt_nee.hip) adds next-event estimation.  Every
+// statement that touches the hook sits under `if constexpr (HOOK::active)`, so the default instantiation (k_render, wf_shade)
+// compiles exactly as without it -- plain empty inline methods change k_render's register allocation.
+struct NoShadeHook {
+    static constexpr bool active = false;
+};
+
 // one iteration body of prog.cl:317-366 for a ray that hit packed triangle `ti` at `t`
 // (SK: double-precision constants pinned to scalar registers, see KC)
-template <bool SK, class ST>
-PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const RenderParams& p, const float4* tris, const TriMeta* meta, int ti, float t) {
+template <bool SK, class ST, class HOOK = NoShadeHook>
+PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const RenderParams& p, const float4* tris, const TriMeta* meta, int ti, float t,
+                      HOOK* hook = nullptr) {
     const float4 c = tris[ti * 3 + 2];
     f3 N = mk(c.y, c.z, c.w);
     const f3 hp = madd(rD, t, rP);
@@ -988,10 +999,15 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     f3 dnew = rD;
     float side = 0.001f;
     float inten = 0.0f;
+    float wb = 1.0f;                                                        // the hook's weight of this hit's emission
     if (lobe) {
         // diffuse (prog.cl:329-340) and emitter (prog.cl:358-366) both continue with a cosine-
         // sampled ray drawn from two LCG values; the emitter's cosine uses the OLD direction.
         inten = max0(dot3(-rD, N));
+        if constexpr (HOOK::active) {
+            if (type == 3) wb = hook->emitter_weight(ti, t, inten, rD);
+            hook->light_sample(st, p, m, type, N, hp);                      // before the LCG draws and this hit's emission
+        }
         const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
         dnew = diffuse_direction<SK>(N, rnd1, rnd2);
     } else if (spec) {
@@ -1044,9 +1060,11 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         st.setB(st.B() * (ldf3(m->ks) * pw));
     } else if (type == 3) {
         const f3 e = ((ldf3(m->emission) * (st.L() + st.B())) * st.S()) * st.R();
-        st.setC(madd(e, inten, st.C()));
+        if constexpr (HOOK::active) st.setC(madd(e * wb, inten, st.C()));
+        else st.setC(madd(e, inten, st.C()));
     }
     // any other type: the ray is left unchanged and the loop hits the same surface again
+    if constexpr (HOOK::active) hook->end_vertex(lobe, N);
 }
 
 PT_DEV f3 running_mean(f3 acc, f3 color, int s) {   // prog.cl:379
@@ -1148,6 +1166,39 @@ PT_DEV void setup_traversal(const RenderParams& p, SceneView* sv, LaneStack<type
         sv->lds_nodes = lds_nodes;
     }
     __syncthreads();
+}
+
+// ---------------------------------------------------------------------------- per-lane traversal kernels (host side)
+// k_debug_closest_hit, k_aovs and k_nee: one lane per item, persistent blocks of the node mode's per-lane size, at most
+// 2048 / BLOCK blocks per CU.  pick(LaneShape<MODE, BLOCK>{}) names the kernel instance; it is launched with (p, args...).
+template <int MODE, int BLOCK>
+struct LaneShape {
+    static constexpr int mode = MODE, block = BLOCK;
+};
+// `mark` is keyed on (PICK, MODE, BLOCK) -- PICK is the caller's own lambda -- so there is one per kernel instance
+template <int MODE, int BLOCK, class PICK, class... A>
+hipError_t launch_lanes_t(PICK pick, const RenderParams& p, int64_t n, int cu_count, hipStream_t stream, A... args) {
+    const auto kern = pick(LaneShape<MODE, BLOCK>{});
+    const size_t lds = traversal_lds_bytes(p, BLOCK);
+    static LdsMark mark;
+    const hipError_t e = ensure_dynamic_lds((const void*)kern, mark, lds);
+    if (e != hipSuccess) return e;
+    const long long need = (n + BLOCK - 1) / BLOCK;
+    const int blocks = (int)std::min<long long>(need, (long long)cu_count * (2048 / BLOCK));
+    if (p.stack_ovf && (long long)blocks * BLOCK > (long long)p.stack_ovf_lanes) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK), lds, stream, p, args...);
+    return hipGetLastError();
+}
+template <class PICK, class... A>
+hipError_t launch_lanes(PICK pick, const RenderParams& p, int64_t n, int cu_count, hipStream_t stream, A... args) {
+    if (n == 0) return hipSuccess;
+    switch (p.node_mode) {
+    case kNodesLds: return launch_lanes_t<kNodesLds, 512>(pick, p, n, cu_count, stream, args...);
+    case kNodesGlobal: return launch_lanes_t<kNodesGlobal, 256>(pick, p, n, cu_count, stream, args...);
+    case kNodesWide: return launch_lanes_t<kNodesWide, 256>(pick, p, n, cu_count, stream, args...);
+    case kNodesTreelet: return launch_lanes_t<kNodesTreelet, 1024>(pick, p, n, cu_count, stream, args...);
+    }
+    return hipErrorInvalidValue;
 }
 
 // statistics live in kStatRows rows of 8 counters; a block adds to the row picked by its index, so

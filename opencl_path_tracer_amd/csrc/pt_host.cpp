@@ -409,7 +409,7 @@ int pt_debug_gather_index(int32_t width, int32_t height, int32_t world, int32_t 
 int pt_local_pixel_ids(const pt_context* ctx, int32_t* out, int64_t n) {
     if (!ctx || !out || n != ctx->npix) return PT_EINVAL;
     for (int32_t lr = 0; lr < ctx->local_rows; ++lr) {
-        const int32_t gr = global_row(ctx, lr);
+        const int32_t gr = global_row(*ctx, lr);
         for (int32_t x = 0; x < ctx->W; ++x) out[(size_t)lr * ctx->W + x] = gr * ctx->W + x;
     }
     return PT_OK;
@@ -536,17 +536,7 @@ int pt_read_denoised(pt_context* ctx, float* out, int64_t npix) {
 void* pt_device_denoised(pt_context* ctx) { return ctx ? (void*)ctx->d_denoised : nullptr; }
 
 // ---- next-event estimation (kernel: pt_nee.hip; the estimator is pinned in include/pt_api.h)
-uint32_t pt_nee_rand(uint32_t state, int32_t segment, int32_t dim) {
-    auto lowbias32 = [](uint32_t x) {
-        x ^= x >> 16;
-        x *= 0x7feb352du;
-        x ^= x >> 15;
-        x *= 0x846ca68bu;
-        x ^= x >> 16;
-        return x;
-    };
-    return lowbias32(lowbias32(state) + 0x9e3779b9u * (uint32_t)(3 * segment + dim + 1));
-}
+uint32_t pt_nee_rand(uint32_t state, int32_t segment, int32_t dim) { return nee_rand(state, segment, dim); }
 // The light table of the uploaded scene, in packed order: type-3 triangles with E.r + E.g + E.b > 0 and non-zero area, P_sel
 // proportional to area x (E.r + E.g + E.b) (summed and normalised in double, then rounded; the last cdf entry is 1)
 static int nee_table(pt_context* ctx) {

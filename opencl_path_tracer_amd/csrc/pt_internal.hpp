@@ -153,6 +153,13 @@ struct RenderParams {
                                  // tile_done[] and debug_stall_tile count list positions, tile_cost frame tiles
 };
 
+// local row -> row of the frame: the frame's rows are dealt out to the `world` ranks in blocks of rows_per_block
+// (P: RenderParams on the device, pt_context on the host)
+template <class P>
+__host__ __device__ __forceinline__ int global_row(const P& p, int lrow) {
+    return ((lrow / p.rows_per_block) * p.world + p.rank) * p.rows_per_block + lrow % p.rows_per_block;
+}
+
 // ---- wavefront (stream-compacted) formulation
 // Ray streams, one per (bounce parity, cost class), addressed by POSITION (compact, written and read coalesced), 48 B per
 // ray:   rsA = {P.xyz, D.x}   rsB = {D.y, D.z, bits(li), bits(flags)}   rsC = {factor_L.xyz, bits(LCG state)}
@@ -322,6 +329,8 @@ struct AtrousStep {
     float sigma_color2, sigma_normal, sigma_depth;
 };
 // one iteration: first reads colors (demodulated when s.demodulate), last remodulates; out must not alias in
+hipError_t launch_atrous(const float4* in, float4* out, const float4* albedo, const float4* nd, int32_t W, int32_t H, const AtrousStep& s,
+                         bool first, bool last, hipStream_t stream);
 // next-event estimation (pt_nee.hip; the estimator is pinned in include/pt_api.h next to pt_render_nee)
 struct NeeTable {
     const int32_t* tri;          // [n] packed triangle of each light
@@ -331,7 +340,17 @@ struct NeeTable {
     int32_t strategy;
 };
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, int64_t npix, int cu_count, hipStream_t stream);
-hipError_t launch_atrous(const float4* in, float4* out, const float4* albedo, const float4* nd, int32_t W, int32_t H, const AtrousStep& s,
-                         bool first, bool last, hipStream_t stream);
+// the light samples' counter-based hash of (LCG state at the start of the sample, segment, dimension): k_nee and pt_nee_rand
+__host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+__host__ __device__ __forceinline__ uint32_t nee_rand(uint32_t state, int segment, int dim) {
+    return lowbias32(lowbias32(state) + 0x9e3779b9u * (uint32_t)(3 * segment + dim + 1));
+}
 
 }  // namespace ptamd

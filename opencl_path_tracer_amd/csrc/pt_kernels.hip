@@ -342,7 +342,7 @@ PT_DEV void render_items_migrating(const RenderParams& p, const SceneView& sv, c
         int grow;
         if (p.world == 1) grow = lrow;
         else if (rows_aligned) { const int r0 = ty * 8; grow = ((r0 / p.rows_per_block) * p.world + p.rank) * p.rows_per_block + (r0 % p.rows_per_block) + (lane >> 3); }
-        else grow = ((lrow / p.rows_per_block) * p.world + p.rank) * p.rows_per_block + (lrow % p.rows_per_block);
+        else grow = global_row(p, lrow);
         li = lrow * p.width + x;
         int gx = x, gy = grow;                                               // prog.cl:84-85: id % X, id / X with id = grow * width + x
         if (camX != p.width) { const int gid = grow * p.width + x; gx = gid % camX; gy = gid / camX; }

@@ -112,7 +112,7 @@ int alloc_stack_overflow(pt_context* ctx) {
 int seed_upload(pt_context* ctx, const int32_t* global_seeds) {
     std::vector<int32_t> local((size_t)ctx->npix);
     for (int32_t lr = 0; lr < ctx->local_rows; ++lr) {
-        const int32_t gr = global_row(ctx, lr);
+        const int32_t gr = global_row(*ctx, lr);
         std::memcpy(&local[(size_t)lr * ctx->W], &global_seeds[(size_t)gr * ctx->W], sizeof(int32_t) * (size_t)ctx->W);
     }
     if (ctx->npix) PT_HIP(ctx, hipMemcpyAsync(ctx->d_rnds, local.data(), sizeof(int32_t) * local.size(), hipMemcpyHostToDevice, ctx->stream));

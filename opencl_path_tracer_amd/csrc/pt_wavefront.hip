@@ -198,7 +198,7 @@ __global__ void __launch_bounds__(kWfGenBlock) wf_generate(WfParams w) {
         if (idx < w.npix) {
             ++live;
             const int lrow = li / p.width, x = li - lrow * p.width;
-            const int grow = ((lrow / p.rows_per_block) * p.world + p.rank) * p.rows_per_block + (lrow % p.rows_per_block);
+            const int grow = global_row(p, lrow);
             const int gid = grow * p.width + x;
             int seed = p.rnds[li];
             const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
