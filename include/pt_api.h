@@ -352,6 +352,15 @@ int pt_debug_wide_nodes(const pt_context* ctx, void* out, int64_t capacity, int6
 /* Closest hit of n caller-supplied rays through the device traversal (kd_intersect, prog.cl:144-184):
  * out_t[i] = t (-1 on a miss), out_tri[i] = add-order index of the triangle hit (-1 on a miss). */
 int pt_debug_closest_hit(pt_context* ctx, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri);
+/* The IEEE divide / sqrt fast paths of the render kernels against the compiler's expansions, on the device of ctx:
+ * inputs first .. first + n - 1 of enumeration fn (PT_MATH_SQRT, PT_MATH_RSQRT: x = the input's low 32 bits as a float;
+ * PT_MATH_DIV_GRID: a / b over every exponent pair, 8 mantissas each (0, 1, 2, half, max - 1, max, 2 hashed) and 4 sign pairs,
+ * input k = ea | eb << 8 | ia << 16 | ib << 19 | signs << 22, 2^24 in all; PT_MATH_DIV_RANDOM: hashed bit patterns;
+ * PT_MATH_DIV_NORMAL: hashed normal pairs with exponents -63 .. 63).  out[0] = inputs whose result differs in any bit
+ * (or whose window admits a zero, denormal, inf or NaN), out[1] = inputs inside the fast path's window, out[2] = out[0];
+ * bad[2 j], bad[2 j + 1] = the bit patterns (x or a, b) of up to bad_cap of the mismatching inputs. */
+enum { PT_MATH_SQRT = 0, PT_MATH_RSQRT = 1, PT_MATH_DIV_GRID = 2, PT_MATH_DIV_RANDOM = 3, PT_MATH_DIV_NORMAL = 4 };
+int pt_debug_math(pt_context* ctx, int32_t fn, int64_t first, int64_t n, int64_t out[3], uint32_t* bad, int64_t bad_cap);
 /* The authored scene (what the reference keeps in Scene::tris / Scene::mats, main.cpp:366-371):
  * triangles in add order, materials, and the first triangle of every object. */
 int pt_debug_scene_sizes(const pt_context* ctx, int64_t* ntris, int64_t* nmats, int64_t* nobjs);

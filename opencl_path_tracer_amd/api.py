@@ -50,7 +50,7 @@ EXPORTS = [
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
     "pt_set_option", "pt_get_stat", "pt_debug_bvh_sizes", "pt_debug_bvh_copy", "pt_debug_wide_nodes", "pt_debug_encounter_rank", "pt_debug_tile_cost", "pt_debug_adaptive_list", "pt_debug_launch_plan",
-    "pt_debug_scene_sizes", "pt_debug_scene_copy", "pt_debug_closest_hit",
+    "pt_debug_scene_sizes", "pt_debug_scene_copy", "pt_debug_closest_hit", "pt_debug_math",
     "pt_slab_pixel_count", "pt_frame_size", "pt_comm_available", "pt_comm_unique_id", "pt_comm_init", "pt_gather_frame", "pt_device_frame", "pt_read_frame",
     "pt_write_pfm", "pt_write_ppm", "pt_image_write_pfm", "pt_image_write_ppm", "pt_debug_gather_index", "pt_debug_deinterleave",
 ]
@@ -148,6 +148,7 @@ def _load():
     sig("pt_image_write_pfm", C.c_int, C.c_char_p, vp, i32, i32)
     sig("pt_image_write_ppm", C.c_int, C.c_char_p, vp, i32, i32)
     sig("pt_debug_gather_index", C.c_int, i32, i32, i32, i32, i64, vp)
+    sig("pt_debug_math", C.c_int, vp, i32, i64, i64, vp, vp, i64)
     sig("pt_debug_deinterleave", C.c_int, vp, vp, i64, vp)
     return L
 
@@ -214,6 +215,7 @@ def adaptive_rounds(min_spp, max_spp):
 
 
 PT_NEE_BSDF, PT_NEE_LIGHT, PT_NEE_MIS = 0, 1, 2
+PT_MATH_SQRT, PT_MATH_RSQRT, PT_MATH_DIV_GRID, PT_MATH_DIV_RANDOM, PT_MATH_DIV_NORMAL = 0, 1, 2, 3, 4   # pt_debug_math enumerations
 NEE_STRATEGIES = {"bsdf": PT_NEE_BSDF, "light": PT_NEE_LIGHT, "mis": PT_NEE_MIS}
 
 
@@ -600,6 +602,13 @@ class Scene:
         tri = np.empty(rays.shape[0], dtype=np.int32)
         self._ck(LIB.pt_debug_closest_hit(self._h, _ptr(rays), rays.shape[0], _ptr(t), _ptr(tri)))
         return t, tri
+
+    def debug_math(self, fn, first, n, bad_cap=8):
+        """pt_debug_math: (mismatches, inputs inside the fast path's window, uint32 [k, 2] bit patterns of the first mismatches)."""
+        out = np.zeros(3, dtype=np.int64)
+        bad = np.zeros((max(int(bad_cap), 1), 2), dtype=np.uint32)
+        self._ck(LIB.pt_debug_math(self._h, int(fn), int(first), int(n), _ptr(out), _ptr(bad), int(bad_cap)))
+        return int(out[0]), int(out[1]), bad[:min(int(out[2]), int(bad_cap))]
 
     def debug_encounter_rank(self, n):
         out = np.empty(n, dtype=np.int32)

@@ -1,5 +1,6 @@
-// pt_debug.hip -- test entry point of libptamd.so: closest hit of caller-supplied rays through the
-// same traversal code (pt_device.hpp) and the same node placement the render kernels use.
+// pt_debug.hip -- test entry points of libptamd.so: closest hit of caller-supplied rays through the
+// same traversal code (pt_device.hpp) and the same node placement the render kernels use; the IEEE
+// divide / sqrt cores of pt_device.hpp against the compiler's expansions on enumerated inputs.
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -23,6 +24,79 @@ __global__ void __launch_bounds__(BLOCK) k_debug_closest_hit(RenderParams p, con
 
 hipError_t launch_debug_closest_hit(const RenderParams& p, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri, int cu_count, hipStream_t stream) {
     return launch_lanes([](auto s) { return k_debug_closest_hit<s.mode, s.block>; }, p, n, cu_count, stream, rays, (long long)n, out_t, out_tri);
+}
+
+// input k of enumeration `fn` (PT_MATH_* in pt_api.h) as one or two bit patterns
+__device__ __forceinline__ uint32_t math_hash(unsigned long long k, uint32_t salt) {
+    return lowbias32(lowbias32((uint32_t)k ^ salt) + 0x9e3779b9u * ((uint32_t)(k >> 32) + 1u));
+}
+__device__ __forceinline__ void math_input(int fn, unsigned long long k, uint32_t* a, uint32_t* b) {
+    *b = 0x3f800000u;
+    if (fn == PT_MATH_SQRT || fn == PT_MATH_RSQRT) {
+        *a = (uint32_t)k;
+    } else if (fn == PT_MATH_DIV_GRID) {          // every exponent pair x 8 x 8 mantissas x 4 signs
+        const uint32_t ea = (uint32_t)(k & 255), eb = (uint32_t)((k >> 8) & 255), ia = (uint32_t)((k >> 16) & 7),
+                       ib = (uint32_t)((k >> 19) & 7), sg = (uint32_t)((k >> 22) & 3);
+        const uint32_t h = math_hash(k, 0x51ed270bu);
+        const uint32_t mant[8] = {0u, 1u, 2u, 0x400000u, 0x7ffffeu, 0x7fffffu, h & 0x7fffffu, (h >> 9) & 0x7fffffu};
+        *a = ((sg & 1u) << 31) | (ea << 23) | mant[ia];
+        *b = ((sg >> 1) << 31) | (eb << 23) | mant[ib];
+    } else if (fn == PT_MATH_DIV_RANDOM) {        // any bit patterns
+        *a = math_hash(k, 0x2545f491u);
+        *b = math_hash(k, 0x9e3779b9u);
+    } else {                                      // PT_MATH_DIV_NORMAL: normal pairs, exponents 2^-63 .. 2^63
+        const uint32_t h1 = math_hash(k, 0x68e31da4u), h2 = math_hash(k, 0xb5297a4du);
+        *a = (h1 & 0x807fffffu) | ((64u + ((h1 >> 23) & 127u)) << 23);
+        *b = (h2 & 0x807fffffu) | ((64u + ((h2 >> 23) & 127u)) << 23);
+    }
+}
+__device__ __forceinline__ bool math_special(float x) { return !(__builtin_fabsf(x) >= 0x1p-126f) || __builtin_isinf(x); }
+
+// out[0] mismatches, out[1] inputs inside the core's window; bad[2 j], bad[2 j + 1]: the first inputs that mismatched.
+// A mismatch is a core result (inside the window) or a wave-level result (div_rn / sqrt_rn / rsqrt_rn, whichever path its
+// wave took) that differs in any bit from the compiler's expansion, or a window that admits a zero, denormal, inf or NaN.
+__global__ void __launch_bounds__(256) k_debug_math(int fn, unsigned long long first, unsigned long long n, unsigned long long* out, uint32_t* bad,
+                                                    long long bad_cap) {
+    unsigned long long miss = 0, inside = 0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        uint32_t ua, ub;
+        math_input(fn, first + i, &ua, &ub);
+        const float a = __uint_as_float(ua), b = __uint_as_float(ub);
+        bool win, bad_lane;
+        if (fn == PT_MATH_SQRT) {
+            const float ref = __builtin_sqrtf(a);
+            win = a >= kSqrtWindowLo;
+            bad_lane = (win && __float_as_uint(sqrt_core(a)) != __float_as_uint(ref)) || __float_as_uint(sqrt_rn(a)) != __float_as_uint(ref);
+        } else if (fn == PT_MATH_RSQRT) {
+            const float ref = 1.0f / __builtin_sqrtf(a);
+            win = rsqrt_window(a);
+            bad_lane = (win && __float_as_uint(rsqrt_core(a)) != __float_as_uint(ref)) || __float_as_uint(rsqrt_rn(a)) != __float_as_uint(ref);
+        } else {
+            const float ref = a / b, r0 = __builtin_amdgcn_rcpf(b);
+            win = div_window(b, r0, a * r0);
+            bad_lane = (win && (math_special(a) || math_special(b) || __float_as_uint(div_core(a, b, r0)) != __float_as_uint(ref))) ||
+                       __float_as_uint(div_rn(a, b)) != __float_as_uint(ref);
+        }
+        inside += win;
+        if (bad_lane) {
+            ++miss;
+            const long long j = (long long)atomicAdd(&out[2], 1ull);
+            if (j < bad_cap) {
+                bad[2 * j] = ua;
+                bad[2 * j + 1] = ub;
+            }
+        }
+    }
+    atomicAdd(&out[0], miss);
+    atomicAdd(&out[1], inside);
+}
+
+hipError_t launch_debug_math(int fn, unsigned long long first, unsigned long long n, unsigned long long* out, uint32_t* bad, long long bad_cap, int cu_count,
+                             hipStream_t stream) {
+    const unsigned long long blocks = std::min<unsigned long long>((n + 255) / 256, (unsigned long long)cu_count * 32);
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_debug_math, dim3((unsigned)blocks), dim3(256), 0, stream, fn, first, n, out, bad, bad_cap);
+    return hipGetLastError();
 }
 
 }  // namespace ptamd

@@ -58,8 +58,72 @@ PT_DEV float dot3(f3 a, f3 b) { return fmaf_(a.z, b.z, fmaf_(a.y, b.y, a.x * b.x
 PT_DEV f3 cross3(f3 a, f3 b) {
     return mk(fmaf_(a.y, b.z, -(a.z * b.y)), fmaf_(a.z, b.x, -(a.x * b.z)), fmaf_(a.x, b.y, -(a.y * b.x)));
 }
+// ---- IEEE divide and sqrt without the range handling their operands here almost never need
+// hipcc expands a correctly rounded f32 a / b (denormals kept) into
+//   d = v_div_scale(b, b, a)   n = v_div_scale(a, b, a) -> VCC   r = v_rcp(d)   e = fma(-d, r, 1)   r = fma(e, r, r)
+//   q = n * r   e = fma(-d, q, n)   q = fma(e, r, q)   e = fma(-d, q, n)   q = v_div_fmas(e, r, q) [VCC]   v_div_fixup(q, b, a)
+// By the ISA definitions, v_div_scale returns its first operand unchanged and clears VCC unless a or b is zero, inf, NaN
+// or denormal, exp(a) - exp(b) >= 96, 1/b or a/b is denormal, or a's biased exponent is <= 23; with VCC clear v_div_fmas
+// is v_fma; v_div_fixup returns |q| with the sign of a * b unless an operand is zero, inf or NaN, a is not finite or the
+// quotient underflows past 2^-150.  div_window() below admits only pairs where none of that applies (|b| and |1/b| at
+// most 2^40, so b is normal; the quotient between 2^-40 and 2^40, so a is normal, within 2^81 of b, and neither zero
+// nor inf) -- and there the core sequence, which is what is left, gives the same bits as '/'.  The sqrt expansion is
+//   s = v_sqrt(x') on x' = x < 2^-96 ? x * 2^32 : x, then s -/+ 1 ulp when fma(-(s -/+ 1 ulp), s, x') is <= 0 / > 0,
+//   then * 2^-16 if x was scaled, then x' itself if x' is +-0 or +inf;
+// for x >= 2^-96 neither scale applies and +inf comes out of the core as inf, so the core alone is exact.
+// Callers take the core when every active lane of the wave is in the window (one uniform branch) and the compiler's
+// expansion otherwise: both give the same bits, so lanes never see which one ran.  tests/test_gpu_fast_math.py checks
+// each core against the expansion on every input of its window edges (pt_debug_math).
+constexpr float kDivWindow = 0x1p40f, kDivWindowLo = 0x1p-40f, kSqrtWindowLo = 0x1p-96f;
+// A/B switch: 0 picks core or expansion once per wave (a ballot, one uniform branch); 1 per lane (a wave with lanes on both
+// sides runs both under exec masks).  profiles/fastmath/README.md compares them.
+#ifndef PT_FASTMATH_PER_LANE
+#define PT_FASTMATH_PER_LANE 0
+#endif
+PT_DEV bool wave_all(bool c) { return PT_FASTMATH_PER_LANE ? c : __builtin_amdgcn_ballot_w64(!c) == 0; }
+// r0 = v_rcp(b), q0 = a * r0 (both as the caller may already hold them)
+PT_DEV bool div_window(float b, float r0, float q0) {
+    return __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(b), __builtin_fabsf(r0)), __builtin_fabsf(q0)) <= kDivWindow &&
+           __builtin_fabsf(q0) >= kDivWindowLo;
+}
+PT_DEV float div_core(float a, float b, float r0) {
+    const float r = fmaf_(fmaf_(-b, r0, 1.0f), r0, r0);
+    float q = a * r;
+    q = fmaf_(fmaf_(-b, q, a), r, q);
+    return fmaf_(fmaf_(-b, q, a), r, q);
+}
+PT_DEV float sqrt_core(float x) {
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float sm = __int_as_float(__float_as_int(s) - 1), sp = __int_as_float(__float_as_int(s) + 1);
+    const float t = fmaf_(-sm, s, x) <= 0.0f ? sm : s;
+    return fmaf_(-sp, s, x) > 0.0f ? sp : t;
+}
+// a / b, bit for bit
+PT_DEV float div_rn(float a, float b) {
+    const float r0 = __builtin_amdgcn_rcpf(b);
+    if (wave_all(div_window(b, r0, a * r0))) return div_core(a, b, r0);
+    return a / b;
+}
+// sqrtf(x), bit for bit
+PT_DEV float sqrt_rn(float x) {
+    if (wave_all(x >= kSqrtWindowLo)) return sqrt_core(x);
+    return __builtin_sqrtf(x);
+}
+// 1.0f / sqrtf(x), two roundings, bit for bit: for finite x >= 2^-96 the root b lies in [2^-48, 2^64].  With numerator 1
+// none of the scaling conditions above applies there (exp(1) - exp(b) <= 48 < 96; 1/b >= 2^-64 is normal, so is 1/b as the
+// quotient; exp(1) = 127 > 23) and v_div_fixup has no special case to take, so the divide core is exact on the whole
+// range -- a wider range than div_window's, which has to bound a general numerator.  One compare pair covers both cores.
+PT_DEV bool rsqrt_window(float x) { return x >= kSqrtWindowLo && x < __builtin_inff(); }
+PT_DEV float rsqrt_core(float x) {
+    const float s = sqrt_core(x);
+    return div_core(1.0f, s, __builtin_amdgcn_rcpf(s));
+}
+PT_DEV float rsqrt_rn(float x) {
+    if (wave_all(rsqrt_window(x))) return rsqrt_core(x);
+    return 1.0f / __builtin_sqrtf(x);
+}
 PT_DEV f3 normalize3(f3 a) {
-    const float s = 1.0f / __builtin_sqrtf(dot3(a, a));
+    const float s = rsqrt_rn(dot3(a, a));
     return a * s;
 }
 PT_DEV float max0(float c) { return c > 0.0f ? c : 0.0f; }
@@ -345,7 +409,10 @@ PT_DEV float tri_test(const float4 a, const float4 b, const float4 c, f3 P, f3 V
     }
     if (cand) {
         if (wc) { count_low(wc, 2); if (first_active_lane()) wc->low[5]++; }
-        const float t = num / den;
+        // num / den (div_rn).  Under QUOT the rcp and the quotient estimate here are the early-out's, merged by the compiler
+        // (same operands, and the early-out's dominate); under !QUOT the early-out's rcp ran inside the `&&` and is evaluated again
+        const float r0 = __builtin_amdgcn_rcpf(den);
+        const float t = wave_all(div_window(den, r0, num * r0)) ? div_core(num, den, r0) : num / den;
         const f3 pt = madd(Vd, t, P);
         const float c1 = dot3(cross3(r2 - r1, pt - r1), N);
         const float c2 = dot3(cross3(r3 - r2, pt - r2), N);
@@ -926,14 +993,26 @@ PT_DEV f3 diffuse_direction(f3 N, float rnd1, float rnd2) {       // prog.cl:205
     const float E = 0.001f;
     const bool yaxis = __builtin_fabsf(N.x) <= E && __builtin_fabsf(N.z) <= E;
     const float other = yaxis ? N.y : N.x;
-    const float rl = 1.0f / __builtin_sqrtf(fmaf_(N.z, N.z, other * other));
+    const float l2 = fmaf_(N.z, N.z, other * other);
+    // the three roots and the divide below are IEEE; one uniform branch picks the cores for all of them or the compiler's
+    // expansions.  sqrt_core needs rnd1 >= 2^-96 and 1 - rnd1 >= 2^-96; the latter holds for every float rnd1 < 1 (1 - rnd1
+    // is then at least 2^-24)
+    float rl, r, z;
+    if (wave_all(rsqrt_window(l2) && rnd1 >= kSqrtWindowLo && rnd1 < 1.0f)) {
+        rl = rsqrt_core(l2);
+        r = sqrt_core(rnd1);
+        z = sqrt_core(1.0f - rnd1);
+    } else {
+        rl = 1.0f / __builtin_sqrtf(l2);
+        r = __builtin_sqrtf(rnd1);
+        z = __builtin_sqrtf(1.0f - rnd1);
+    }
     const f3 Z = yaxis ? mk(0.0f, -N.z * rl, N.y * rl) : mk(-N.z * rl, 0.0f, N.x * rl);
     const f3 X = cross3(N, Z);
-    const float r = __builtin_sqrtf(rnd1);
     const float theta = (float)(6.283185307179586 * (double)rnd2);
     float sn, cs;
     spec_sincos<SK>(theta, &sn, &cs);
-    const float x = r * cs, y = r * sn, z = __builtin_sqrtf(1.0f - rnd1);
+    const float x = r * cs, y = r * sn;
     f3 d = X * x;
     d = madd(N, z, d);
     d = madd(Z, y, d);
@@ -1027,7 +1106,7 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
             const bool refr = disc > 0.0f && rnd > prob;
             if (refr) {
                 const f3 dn = mk(oldD.x / n, oldD.y / n, oldD.z / n);
-                dnew = madd(N, cosa / n - __builtin_sqrtf(disc), dn);
+                dnew = madd(N, cosa / n - sqrt_rn(disc), dn);
                 const float k = 1.0f / (1.0f - prob);
                 st.setR((st.R() * mk(1.0f - F.x, 1.0f - F.y, 1.0f - F.z)) * k);
                 inside = !inside;

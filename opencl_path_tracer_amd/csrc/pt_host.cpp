@@ -908,6 +908,26 @@ struct EventOwner {
 };
 }  // namespace
 
+int pt_debug_math(pt_context* ctx, int32_t fn, int64_t first, int64_t n, int64_t out[3], uint32_t* bad, int64_t bad_cap) {
+    PT_NEED_DEVICE(ctx);
+    if (fn < PT_MATH_SQRT || fn > PT_MATH_DIV_NORMAL || first < 0 || n < 0 || !out || bad_cap < 0 || (bad_cap > 0 && !bad))
+        return fail(ctx, PT_EINVAL, "pt_debug_math: bad arguments");
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceBuf d_out, d_bad;
+    PT_HIP(ctx, d_out.alloc(3 * sizeof(unsigned long long)));
+    PT_HIP(ctx, d_bad.alloc(2 * sizeof(uint32_t) * (size_t)std::max<int64_t>(bad_cap, 1)));
+    PT_HIP(ctx, hipMemsetAsync(d_out.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    PT_HIP(ctx, launch_debug_math(fn, (unsigned long long)first, (unsigned long long)n, (unsigned long long*)d_out.p, (uint32_t*)d_bad.p, (long long)bad_cap,
+                                  ctx->cu_count, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned long long h[3];
+    PT_HIP(ctx, hipMemcpy(h, d_out.p, sizeof h, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) out[i] = (int64_t)h[i];
+    const int64_t k = std::min<int64_t>(out[2], bad_cap);
+    if (k > 0) PT_HIP(ctx, hipMemcpy(bad, d_bad.p, 2 * sizeof(uint32_t) * (size_t)k, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 int pt_debug_closest_hit(pt_context* ctx, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri) {
     PT_NEED_DEVICE(ctx);
     if (!rays || !out_t || !out_tri || n < 0) return fail(ctx, PT_EINVAL, "bad arguments");

@@ -318,6 +318,8 @@ hipError_t launch_adaptive_tiles(const float4* colors, float4* snap, const int32
 // the frame tiles whose flag is set, ascending, into list[0, *count) (one workgroup)
 hipError_t launch_compact_tiles(const uint8_t* active, int32_t n, int32_t* list, int32_t* count, hipStream_t stream);
 hipError_t launch_debug_closest_hit(const RenderParams& p, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri, int cu_count, hipStream_t stream);
+hipError_t launch_debug_math(int fn, unsigned long long first, unsigned long long n, unsigned long long* out, uint32_t* bad, long long bad_cap, int cu_count,
+                             hipStream_t stream);
 // guide buffers and the a-trous filter (pt_denoise.hip; the filter is pinned in include/pt_api.h next to pt_denoise)
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
                        int cu_count, hipStream_t stream);
