@@ -195,6 +195,23 @@ uint32_t pt_nee_rand(uint32_t state, int32_t segment, int32_t dim);
  * orig_tri (add-order triangle index) and cdf are written (either may be NULL) */
 int pt_debug_light_table(pt_context* ctx, int32_t* orig_tri, float* cdf, int64_t cap, int64_t* n);
 
+/* ---- per-pixel variance of the mean luminance (new: opt-in with option "moments"; the reference keeps the mean only) -------
+ * With option "moments" = 1 every render path (pt_render in every variant, schedule and node mode, pt_trace_rays,
+ * pt_render_adaptive, pt_render_nee, tiled ranks) also folds each sample's squared luminance into colors[].w, float32 in this order:
+ *   l(c) = fmaf(0.0722f, c.b, fmaf(0.7152f, c.g, 0.2126f * c.r))
+ *   q = l(x_s) * l(x_s), x_s = the colour of sample s (the value the running mean folds in)
+ *   m2 = fmaf(m2, (float)s, q) / (float)(s + 1)      (the running mean of prog.cl:379; sample 0 starts from 0)
+ * .xyz, rnds and rays are the same bits either way; with "moments" = 0 (default) .w = 0 exactly as before.
+ * A frame starts at a launch whose first sample is 0 (pt_render / pt_render_nee at current_sample 0, pt_render_adaptive,
+ * pt_trace_rays with current_sample 0); it is valid while every launch of it had "moments" = 1 (switching it on mid-frame makes
+ * the frame invalid until the next one starts).  Per local pixel, with n = what pt_read_sample_counts reports (a caller driving
+ * pt_trace_rays keeps that counter with pt_set_current_sample) and mu = l(colors.xyz):
+ *   v = fmaxf(fmaf(-mu, mu, m2), 0.0f) / (float)(n - 1), +inf when n < 2
+ * computed on the device (k_variance) into a 4 B/px buffer allocated on first use.  PT_EINVAL when the current frame is not
+ * valid or has no samples (current_sample 0); any context, tiled ranks included (their local pixels). */
+int pt_read_variance(pt_context* ctx, float* out, int64_t npix);
+void* pt_device_variance(pt_context* ctx);                           /* the same, left on the device; NULL on failure (pt_last_error) */
+
 /* ---- guide buffers and an edge-avoiding a-trous denoiser (new: the reference has no denoiser) ------------------------
  * Guide buffers ("AOVs") of the frame seen through cam.  Per local pixel, subpixels x subpixels (1..8) camera rays with the
  * sub-pixel offsets rnd1 = ((float)i + 0.5f) / (float)n, rnd2 = ((float)j + 0.5f) / (float)n fed to camera_get_ray
@@ -235,6 +252,26 @@ void pt_denoise_defaults(pt_denoise_params* p);
  * buffers (32 B/px) are allocated on first use. */
 int pt_denoise(pt_context* ctx, const pt_denoise_params* p);
 int pt_read_denoised(pt_context* ctx, float* out_rgba, int64_t npix);   /* float3 @ 16 B, colors' layout (row 0 = bottom) */
+/* The variance-guided filter (the spatial part of SVGF, Schied et al. 2017) on the same guides, L = iterations:
+ *   x0 = the colour, demodulated per channel as pt_denoise does when demodulate is set; v0 = pt_read_variance's v,
+ *   / max(l(a), 1e-3)^2 with demodulate (l as pinned for the moments);
+ *   taps, h, wn, wz, the hit / miss rule, the centre tap (every term 1) and the skipped out-of-frame taps are pt_denoise's; the
+ *   luminance term replaces the colour term:
+ *     g(p) = the 3x3 blur of v(i) with weights (1/4, 1/2, 1/4)^2, one pixel apart at every iteration, normalised over the in-frame taps
+ *     wl = exp(-|l(x(i)(p)) - l(x(i)(q))| / (sigma_luminance sqrt(g(p)) + 1e-6)), 1 when the difference is 0, g(p) = +inf or
+ *     sigma_luminance = +inf;
+ *   x(i+1)(p) = sum w x(i)(q) / sum w,  v(i+1)(p) = sum w^2 v(i)(q) / (sum w)^2  (w = h wl wn wz; a tap of weight 0 adds nothing);
+ *   output x(L), remodulated with demodulate; .w = v(L), times max(l(a), 1e-3)^2 with demodulate.
+ * Float32 on the device, deterministic.  World-1 contexts only.  PT_EINVAL without guides or with stale ones, when the frame's moments
+ * are not valid or it has no samples (pt_read_variance), for iterations outside 1..10 or negative / NaN sigmas.  The result is
+ * read like pt_denoise's (pt_read_denoised / pt_device_denoised, the same two buffers); the variance read-out is refreshed. */
+typedef struct { int32_t iterations; float sigma_luminance, sigma_normal, sigma_depth; int32_t demodulate; } pt_denoise_variance_params;
+/* iterations 2, sigma_luminance 4, sigma_normal 8, sigma_depth 0.05, demodulate 0: normal and depth as pt_denoise; the rest from the
+ * 16-spp sweep of tools/denoise_variance_bench.py at 1920x1080 on the Cornell box and MESH-100k, the best sum of the two RMSE ratios
+ * to raw (0.35 and 0.74).  Demodulation loses on both: a dark albedo (clamped at 1e-3) scales the pixel and its variance up, and the
+ * luminance term then lets it spread (profiles/denoise/README.md) */
+void pt_denoise_variance_defaults(pt_denoise_variance_params* p);
+int pt_denoise_variance(pt_context* ctx, const pt_denoise_variance_params* p);
 void* pt_device_denoised(pt_context* ctx);                               /* NULL until pt_denoise ran */
 
 /* ---- multi-GPU frame assembly (SURVEY 8b "RCCL communicator per context", 8e) ----------
@@ -325,6 +362,7 @@ int pt_set_stream(pt_context* ctx, void* hip_stream);                /* hipStrea
  *   "sah_visit_cost"  SAH price of one node visit in tenths of a triangle test (default 10; set before
  *                  the triangles are uploaded.  Measured: 5 / 10 / 15 / 20 -> 1006 / 1448 / 1393 / 1266 Msamples/s)
  *   "cost_binning" 0/1 wavefront: separate ray streams for rays touching a complex object's box
+ *   "moments"      0 (default) / 1 fold each sample's squared luminance into colors[].w (pt_read_variance)
  *   "timing"       0/1 record HIP events around the dominant kernel ("kernel_ms" statistic)
  *   "count_work"   0/1 also count node visits / triangle tests (slower kernel instance)
  *   "reset_stats"  1 zero all statistics

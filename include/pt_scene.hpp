@@ -124,6 +124,25 @@ public:
         pt_denoise_defaults(&d);
         ck(pt_denoise(ctx, p ? p : &d));
     }
+    // per local pixel, the variance of its mean luminance (pt_read_variance: the frame was rendered with option "moments" = 1)
+    std::vector<float> read_variance() {
+        int64_t n = 0;
+        ck(pt_local_pixel_count(ctx, &n));
+        std::vector<float> out((size_t)n);
+        ck(pt_read_variance(ctx, out.data(), n));
+        return out;
+    }
+    void* device_variance() {                  // throws with pt_last_error's text (host-only context, or moments not valid)
+        void* d = pt_device_variance(ctx);
+        if (!d) ck(PT_EINVAL);
+        return d;
+    }
+    // the variance-guided filter (pt_denoise_variance; p = NULL: the defaults); result: pt_read_denoised like denoise()
+    void denoise_variance(const pt_denoise_variance_params* p = nullptr) {
+        pt_denoise_variance_params d;
+        pt_denoise_variance_defaults(&d);
+        ck(pt_denoise_variance(ctx, p ? p : &d));
+    }
     int current_sample() { int32_t s = 0; ck(pt_get_current_sample(ctx, &s)); return s; }
     void reset_samples() { ck(pt_set_current_sample(ctx, 0)); }                                // main.cpp:1046
     void finish() { ck(pt_sync(ctx)); }                                                        // queue.finish(), main.cpp:675

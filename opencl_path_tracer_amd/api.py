@@ -46,6 +46,7 @@ EXPORTS = [
     "pt_generate_rays", "pt_trace_rays", "pt_render", "pt_render_adaptive", "pt_read_sample_counts", "pt_read_tile_state", "pt_adaptive_rounds",
     "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
     "pt_render_nee", "pt_nee_rand", "pt_debug_light_table",
+    "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_render_aovs", "pt_read_aovs", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
@@ -104,6 +105,10 @@ def _load():
     sig("pt_render_nee", C.c_int, vp, vp, i32, i32, i32)
     sig("pt_nee_rand", C.c_uint32, C.c_uint32, i32, i32)
     sig("pt_debug_light_table", C.c_int, vp, vp, vp, i64, C.POINTER(i64))
+    sig("pt_read_variance", C.c_int, vp, vp, i64)
+    sig("pt_device_variance", vp, vp)
+    sig("pt_denoise_variance_defaults", None, vp)
+    sig("pt_denoise_variance", C.c_int, vp, vp)
     sig("pt_render_aovs", C.c_int, vp, vp, i32, i32)
     sig("pt_read_aovs", C.c_int, vp, vp, vp, i64)
     sig("pt_denoise_defaults", None, vp)
@@ -233,6 +238,22 @@ class DenoiseParams(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DenoiseVarianceParams(C.Structure):
+    """pt_denoise_variance_params (include/pt_api.h)."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def denoise_variance_defaults():
+    """pt_denoise_variance_defaults as a dict: iterations, sigma_luminance, sigma_normal, sigma_depth, demodulate."""
+    p = DenoiseVarianceParams()
+    LIB.pt_denoise_variance_defaults(C.byref(p))
+    return p.as_dict()
+
+
 def denoise_defaults():
     """pt_denoise_defaults as a dict: iterations, sigma_color, sigma_normal, sigma_depth, demodulate."""
     p = DenoiseParams()
@@ -292,6 +313,7 @@ class Scene:
         self.fov, self.yaw, self.pitch, self.shift = 60.0, 0.0, 0.0, (0.0, 0.0, 0.0)
         self._h = C.c_void_p()
         dev = -1 if device is None else int(device)
+        self._host_only = device is None
         rc = LIB.pt_create_tiled(dev, self.width, self.height, rank, world, rows_per_block, C.byref(self._h))
         if rc != PT_OK:
             raise PtError(rc, (LIB.pt_last_error(None) or b"").decode())
@@ -437,6 +459,22 @@ class Scene:
         self._ck(LIB.pt_debug_light_table(self._h, _ptr(tri), _ptr(cdf), n.value, C.byref(n)))
         return tri, cdf
 
+    # -- per-pixel variance of the mean luminance (option "moments"; include/pt_api.h pins both the fold and the read-out)
+    def read_variance(self):
+        """Per local pixel (local_rows x width, float32): the variance of its mean luminance, +inf below two samples.
+        The frame must have been rendered with set_option("moments", 1) from its first sample."""
+        out = np.empty(self.local_pixels, dtype=np.float32)
+        self._ck(LIB.pt_read_variance(self._h, _ptr(out), out.size))
+        return out.reshape(-1, self.width)
+
+    def device_variance(self):
+        """Device pointer of the same read-out (4 B per local pixel), computed on the context's stream; raises like read_variance
+        (PT_ENODEVICE on a host-only context, PT_EINVAL when the frame's moments are not valid)."""
+        ptr = LIB.pt_device_variance(self._h)
+        if not ptr:
+            raise PtError(PT_ENODEVICE if self._host_only else PT_EINVAL, (LIB.pt_last_error(self._h) or b"").decode())
+        return ptr
+
     # -- guide buffers + a-trous denoiser (include/pt_api.h pins both)
     def render_aovs(self, subpixels=1, specular_depth=4):
         """Guide buffers of the current view (pt_render_aovs): albedo, normal, depth per local pixel; touches no render state."""
@@ -457,6 +495,17 @@ class Scene:
                 raise TypeError("unknown denoise parameter %r" % k)
             setattr(p, k, v)
         self._ck(LIB.pt_denoise(self._h, C.byref(p)))
+        return self.read_denoised()
+
+    def denoise_variance(self, **params):
+        """pt_denoise_variance with pt_denoise_variance_defaults overridden by params; returns the filtered frame like read_colors(),
+        with the filtered variance in column 3.  Needs guides (render_aovs) and a frame rendered with set_option("moments", 1)."""
+        p = DenoiseVarianceParams(**denoise_variance_defaults())
+        for k, v in params.items():
+            if k not in p.as_dict():
+                raise TypeError("unknown denoise_variance parameter %r" % k)
+            setattr(p, k, v)
+        self._ck(LIB.pt_denoise_variance(self._h, C.byref(p)))
         return self.read_denoised()
 
     def read_denoised(self):

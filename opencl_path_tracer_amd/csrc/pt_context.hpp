@@ -134,6 +134,11 @@ struct pt_context {
     float4* d_dn = nullptr;
     float4* d_denoised = nullptr;
     bool aov_valid = false;            // pt_render_aovs ran and no pt_upload_triangles / pt_upload_materials has made its guides stale
+    // option "moments": render launches fold the second moment into colors[].w; moments_valid = every launch of the current frame did
+    // (note_moments); the variance read-out (pt_read_variance, pt_denoise_variance) lives in d_variance, allocated on first use
+    int moments = 0;
+    bool moments_valid = false;
+    float* d_variance = nullptr;
     // next-event estimation (pt_render_nee): the light table, built on the host at first use after an upload (nee_valid).  Packed
     // triangle index and cdf per light; P_sel / area per packed triangle (0 for non-lights).  Device copies allocated with it.
     std::vector<int32_t> nee_tri;
@@ -195,6 +200,10 @@ int host_threads(const pt_context* ctx);                          // threads of 
         if (e_ != hipSuccess)                                                               \
             return fail(ctx, PT_EHIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
     } while (0)
+
+// a render launch of samples [first_sample, ...) was enqueued: a frame starts at sample 0, and stays valid for pt_read_variance while every
+// launch of it has folded the second moment (option "moments")
+inline void note_moments(pt_context* ctx, int32_t first_sample) { ctx->moments_valid = (first_sample == 0 || ctx->moments_valid) && ctx->moments != 0; }
 
 #define PT_NEED_DEVICE(ctx)                                                                 \
     do {                                                                                    \

@@ -162,6 +162,147 @@ __global__ void __launch_bounds__(256) k_atrous(const float4* __restrict__ in, f
     out[ip] = make_float4(r.x, r.y, r.z, 1.0f);
 }
 
+// ---------------------------------------------------------------------------- variance of the mean luminance (pt_read_variance)
+// n = tile_spp[tile of the pixel] (adaptive frames) or n_all; v = max(m2 - mu^2, 0) / (n - 1), +inf below two samples (pinned in pt_api.h)
+__global__ void __launch_bounds__(256) k_variance(const float4* __restrict__ colors, const int32_t* __restrict__ tile_spp, int32_t n_all, int W,
+                                                  long long npix, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix) return;
+    int n = n_all;
+    if (tile_spp) {
+        const int y = (int)(i / W), x = (int)(i - (long long)y * W);
+        n = tile_spp[(y >> 3) * ((W + 7) >> 3) + (x >> 3)];
+    }
+    const float4 c = colors[i];
+    const float mu = luminance(mk(c.x, c.y, c.z));
+    out[i] = n < 2 ? __builtin_inff() : fmaxf(fmaf_(-mu, mu, c.w), 0.0f) / (float)(n - 1);
+}
+
+hipError_t launch_variance(const float4* colors, const int32_t* tile_spp, int32_t n_all, int32_t W, int64_t npix, float* out, hipStream_t stream) {
+    if (npix <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_variance, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, colors, tile_spp, n_all, W, (long long)npix, out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------- variance-guided a-trous iteration (pt_denoise_variance)
+// x(p) and v(p) of an iteration's input: FIRST reads the context's colors and the variance read-out, demodulated when s.demodulate
+// (x / max(a, 1e-3) per channel, v / max(l(a), 1e-3)^2); later iterations read the previous one's {x, v} float4
+template <bool FIRST>
+PT_DEV void load_xv(const float4* __restrict__ in, const float* __restrict__ var, const float4* __restrict__ albedo, size_t i, int demodulate,
+                    f3* x, float* v) {
+    const float4 c = in[i];
+    if (FIRST) {
+        float vv = var[i];
+        if (demodulate) {
+            const float4 a = albedo[i];
+            *x = demod(c, a);
+            const float la = fmaxf(luminance(mk(a.x, a.y, a.z)), 1e-3f);
+            vv = vv / (la * la);
+        } else {
+            *x = mk(c.x, c.y, c.z);
+        }
+        *v = vv;
+    } else {
+        *x = mk(c.x, c.y, c.z);
+        *v = c.w;
+    }
+}
+
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) k_atrous_var(const float4* __restrict__ in, const float* __restrict__ var, float4* __restrict__ out,
+                                                    const float4* __restrict__ albedo, const float4* __restrict__ nd, int W, int H, AtrousVarStep s) {
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31);
+    const int y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= W || y >= H) return;
+    const float kern[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    const float gk[3] = {0.25f, 0.5f, 0.25f};
+    const size_t ip = (size_t)y * W + x;
+    const float4 gp = nd[ip];
+    const bool miss_p = gp.w < 0.0f, zero_np = gp.x == 0.0f && gp.y == 0.0f && gp.z == 0.0f;
+    f3 cp;
+    float vp;
+    load_xv<FIRST>(in, var, albedo, ip, s.demodulate, &cp, &vp);
+    const float lp = luminance(cp);
+    // g(p): the 3x3 blur of v, one pixel apart, normalised over the taps inside the frame
+    float lum_scale = 0.0f;          // sigma_luminance sqrt(g(p)) + 1e-6; 0: the luminance term is off (weight 1)
+    if (s.lum_on) {
+        float gs = 0.0f, gw = 0.0f;
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int qy = y + dy;
+            if (qy < 0 || qy >= H) continue;
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int qx = x + dx;
+                if (qx < 0 || qx >= W) continue;
+                f3 xq;
+                float vq;
+                load_xv<FIRST>(in, var, albedo, (size_t)qy * W + qx, s.demodulate, &xq, &vq);
+                const float k = gk[dx + 1] * gk[dy + 1];
+                gs = fmaf_(k, vq, gs);
+                gw += k;
+            }
+        }
+        const float g = gs / gw;
+        if (g < __builtin_inff()) lum_scale = s.sigma_luminance * sqrtf(g) + 1e-6f;
+    }
+    f3 acc = mk(0.f, 0.f, 0.f);
+    float wsum = 0.0f, vacc = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + dy * s.step;
+        if (qy < 0 || qy >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * s.step;
+            if (qx < 0 || qx >= W) continue;
+            const size_t iq = (size_t)qy * W + qx;
+            const float4 gq = nd[iq];
+            const bool miss_q = gq.w < 0.0f;
+            if (miss_p != miss_q) continue;                     // w_z = 0 across a hit / miss boundary
+            f3 cq;
+            float vq;
+            load_xv<FIRST>(in, var, albedo, iq, s.demodulate, &cq, &vq);
+            float w = kern[dx + 2] * kern[dy + 2];
+            if (!(dx == 0 && dy == 0)) {                        // the centre tap: 9/64, every term 1
+                if (lum_scale > 0.0f) {
+                    const float dl = fabsf(lp - luminance(cq));
+                    if (dl != 0.0f) w *= expf(-dl / lum_scale);
+                }
+                if (s.normal_on && !zero_np && !(gq.x == 0.0f && gq.y == 0.0f && gq.z == 0.0f)) {
+                    const float dn = (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z;
+                    w *= powf(fmaxf(dn, 0.0f), s.sigma_normal);
+                }
+                if (s.depth_on && !miss_p) {
+                    const float dz = fabsf(gp.w - gq.w);
+                    if (dz != 0.0f) w *= expf(-dz / (((s.sigma_depth * (float)s.step) * (float)max(abs(dx), abs(dy))) * gp.w));
+                }
+                if (w == 0.0f) continue;                        // a tap of weight 0 adds nothing (not even 0 x inf to the variance)
+            }
+            acc = madd(cq, w, acc);
+            vacc = fmaf_(w * w, vq, vacc);
+            wsum += w;
+        }
+    }
+    f3 r = mk(acc.x / wsum, acc.y / wsum, acc.z / wsum);
+    float rv = vacc / (wsum * wsum);
+    if (LAST && s.demodulate) {
+        const float4 a = albedo[ip];
+        r = mk(r.x * fmaxf(a.x, 1e-3f), r.y * fmaxf(a.y, 1e-3f), r.z * fmaxf(a.z, 1e-3f));
+        const float la = fmaxf(luminance(mk(a.x, a.y, a.z)), 1e-3f);
+        rv = rv * (la * la);
+    }
+    out[ip] = make_float4(r.x, r.y, r.z, rv);
+}
+
+hipError_t launch_atrous_var(const float4* in, const float* var, float4* out, const float4* albedo, const float4* nd, int32_t W, int32_t H,
+                             const AtrousVarStep& s, bool first, bool last, hipStream_t stream) {
+    const dim3 grid((W + 31) / 32, (H + 7) / 8), block(256);
+    if (first && last) hipLaunchKernelGGL((k_atrous_var<true, true>), grid, block, 0, stream, in, var, out, albedo, nd, W, H, s);
+    else if (first) hipLaunchKernelGGL((k_atrous_var<true, false>), grid, block, 0, stream, in, var, out, albedo, nd, W, H, s);
+    else if (last) hipLaunchKernelGGL((k_atrous_var<false, true>), grid, block, 0, stream, in, var, out, albedo, nd, W, H, s);
+    else hipLaunchKernelGGL((k_atrous_var<false, false>), grid, block, 0, stream, in, var, out, albedo, nd, W, H, s);
+    return hipGetLastError();
+}
+
 hipError_t launch_atrous(const float4* in, float4* out, const float4* albedo, const float4* nd, int32_t W, int32_t H, const AtrousStep& s,
                          bool first, bool last, hipStream_t stream) {
     const dim3 grid((W + 31) / 32, (H + 7) / 8), block(256);

@@ -1151,6 +1151,13 @@ PT_DEV f3 running_mean(f3 acc, f3 color, int s) {   // prog.cl:379
     return mk(fmaf_(acc.x, cs, color.x) / cs1, fmaf_(acc.y, cs, color.y) / cs1, fmaf_(acc.z, cs, color.z) / cs1);
 }
 
+// option "moments" (pt_api.h): the running mean of prog.cl:379 over the squared luminance of the samples, kept in colors[].w
+PT_DEV float luminance(f3 c) { return fmaf_(0.0722f, c.z, fmaf_(0.7152f, c.y, 0.2126f * c.x)); }
+PT_DEV float running_moment(float m2, f3 color, int s) {
+    const float l = luminance(color);
+    return fmaf_(m2, (float)s, l * l) / (float)(s + 1);
+}
+
 // ---------------------------------------------------------------------------- LDS staging
 
 // Nodes staged in LDS are re-laid out on the way in: the three box quads {L.lo, L.hi, R.lo, R.hi}

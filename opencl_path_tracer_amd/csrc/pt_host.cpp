@@ -233,6 +233,7 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->h_adapt_count) (void)hipHostFree(ctx->h_adapt_count);
         if (ctx->d_aov) (void)hipFree(ctx->d_aov);
         if (ctx->d_dn) (void)hipFree(ctx->d_dn);
+        if (ctx->d_variance) (void)hipFree(ctx->d_variance);
         if (ctx->d_nee_tri) (void)hipFree(ctx->d_nee_tri);
         if (ctx->d_nee_cdf) (void)hipFree(ctx->d_nee_cdf);
         if (ctx->d_nee_pdf_area) (void)hipFree(ctx->d_nee_pdf_area);
@@ -535,6 +536,73 @@ int pt_read_denoised(pt_context* ctx, float* out, int64_t npix) {
 }
 void* pt_device_denoised(pt_context* ctx) { return ctx ? (void*)ctx->d_denoised : nullptr; }
 
+// ---- variance of each pixel's mean luminance (kernel k_variance, pt_denoise.hip; pinned in include/pt_api.h)
+static int compute_variance(pt_context* ctx, const char* who) {
+    if (!ctx->moments_valid) return fail(ctx, PT_EINVAL, std::string(who) + ": the frame was not rendered with option moments = 1 from its first sample");
+    if (ctx->current_sample <= 0) return fail(ctx, PT_EINVAL, std::string(who) + ": the frame has no samples");
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_variance) PT_HIP(ctx, hipMalloc((void**)&ctx->d_variance, sizeof(float) * (size_t)std::max<int64_t>(ctx->npix, 1)));
+    PT_HIP(ctx, launch_variance(ctx->d_colors, ctx->adaptive_frame ? ctx->d_adapt_spp : nullptr, ctx->current_sample, ctx->W, ctx->npix,
+                                ctx->d_variance, ctx->stream));
+    return PT_OK;
+}
+int pt_read_variance(pt_context* ctx, float* out, int64_t npix) {
+    PT_NEED_DEVICE(ctx);
+    if (!out || npix != ctx->npix) return fail(ctx, PT_EINVAL, "npix must equal the local pixel count");
+    const int rc = compute_variance(ctx, "pt_read_variance");
+    if (rc != PT_OK) return rc;
+    return read_back(ctx, out, ctx->d_variance, sizeof(float) * (size_t)npix);
+}
+void* pt_device_variance(pt_context* ctx) {
+    if (!ctx || !ctx->has_device) {
+        if (ctx) (void)fail(ctx, PT_ENODEVICE, "context was created without a HIP device (host-only); no CPU render path exists");
+        return nullptr;
+    }
+    return compute_variance(ctx, "pt_device_variance") == PT_OK ? (void*)ctx->d_variance : nullptr;
+}
+
+// ---- variance-guided a-trous filter (kernel k_atrous_var, pt_denoise.hip; pinned in include/pt_api.h)
+void pt_denoise_variance_defaults(pt_denoise_variance_params* p) {
+    if (!p) return;
+    p->iterations = 2;
+    p->sigma_luminance = 4.0f;
+    p->sigma_normal = 8.0f;
+    p->sigma_depth = 0.05f;
+    p->demodulate = 0;
+}
+int pt_denoise_variance(pt_context* ctx, const pt_denoise_variance_params* dp) {
+    if (!ctx) return PT_EINVAL;
+    if (!dp) return fail(ctx, PT_EINVAL, "pt_denoise_variance: params is NULL");
+    if (dp->iterations < 1 || dp->iterations > 10) return fail(ctx, PT_EINVAL, "pt_denoise_variance: iterations must be 1..10");
+    if (!(dp->sigma_luminance >= 0.0f) || !(dp->sigma_normal >= 0.0f) || !(dp->sigma_depth >= 0.0f))
+        return fail(ctx, PT_EINVAL, "pt_denoise_variance: sigmas must be >= 0 (and not NaN)");
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_denoise_variance: contexts of one rank (world == 1) only");
+    if (!ctx->aov_valid)
+        return fail(ctx, PT_EINVAL, "pt_denoise_variance: no guides (pt_render_aovs has not run since the scene was last uploaded)");
+    PT_NEED_DEVICE(ctx);
+    int rc = compute_variance(ctx, "pt_denoise_variance");       // (checks the moments)
+    if (rc != PT_OK) return rc;
+    const size_t npix = (size_t)ctx->npix;
+    if (!ctx->d_dn) PT_HIP(ctx, hipMalloc((void**)&ctx->d_dn, 2 * sizeof(float4) * std::max<size_t>(npix, 1)));
+    for (int i = 0; i < dp->iterations; ++i) {
+        AtrousVarStep s;
+        s.step = 1 << i;
+        s.demodulate = dp->demodulate ? 1 : 0;
+        s.lum_on = std::isfinite(dp->sigma_luminance) ? 1 : 0;
+        s.normal_on = std::isfinite(dp->sigma_normal) && dp->sigma_normal > 0.0f ? 1 : 0;
+        s.depth_on = std::isfinite(dp->sigma_depth) ? 1 : 0;
+        s.sigma_luminance = dp->sigma_luminance;
+        s.sigma_normal = dp->sigma_normal;
+        s.sigma_depth = dp->sigma_depth;
+        const float4* in = i == 0 ? ctx->d_colors : ctx->d_dn + ((i - 1) & 1) * npix;
+        float4* out = ctx->d_dn + (i & 1) * npix;
+        PT_HIP(ctx, launch_atrous_var(in, ctx->d_variance, out, ctx->d_aov, ctx->d_aov + npix, ctx->W, ctx->local_rows, s, i == 0,
+                                      i == dp->iterations - 1, ctx->stream));
+    }
+    ctx->d_denoised = ctx->d_dn + ((dp->iterations - 1) & 1) * npix;
+    return PT_OK;
+}
+
 // ---- next-event estimation (kernel: pt_nee.hip; the estimator is pinned in include/pt_api.h)
 uint32_t pt_nee_rand(uint32_t state, int32_t segment, int32_t dim) { return nee_rand(state, segment, dim); }
 // The light table of the uploaded scene, in packed order: type-3 triangles with E.r + E.g + E.b > 0 and non-zero area, P_sel
@@ -637,6 +705,7 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     lt.n = (int32_t)ctx->nee_tri.size();
     lt.strategy = strategy;
     ctx->render_epoch++;
+    note_moments(ctx, p.first_sample);
     EventPair* ep;
     if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
     PT_HIP(ctx, launch_nee(p, lt, ctx->npix, ctx->cu_count, ctx->stream));
@@ -725,6 +794,9 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value) {
         if (value < 4 || value > kWideLdsEntries || (value & 1)) return fail(ctx, PT_EINVAL, "wide_lds_entries: even, 4..20");
         ctx->wide_lds_entries = (int)value;
         ctx->tris_uploaded = false;                  // the global part of the stacks is sized at upload
+    } else if (k == "moments") {
+        if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "moments must be 0 (off) or 1 (second moment of the luminance in colors[].w)");
+        ctx->moments = (int)value;
     } else if (k == "timing") {
         ctx->timing = value ? 1 : 0;
     } else if (k == "count_work") {

@@ -151,6 +151,7 @@ struct RenderParams {
     uint32_t* tile_cost;         // counting instances only, or null: [n_tiles] += shader-clock cycles / 64 the wave spent on each work item of the tile (pt_debug_tile_cost)
     const int32_t* tile_list;    // != 0 (adaptive frames, pt_render_adaptive): tile t of the launch is frame tile tile_list[t]; work items,
                                  // tile_done[] and debug_stall_tile count list positions, tile_cost frame tiles
+    int32_t moments;             // option "moments": 1 folds every sample's squared luminance into colors[].w (running_moment), 0 writes .w = 0
 };
 
 // local row -> row of the frame: the frame's rows are dealt out to the `world` ranks in blocks of rows_per_block
@@ -333,6 +334,19 @@ struct AtrousStep {
 // one iteration: first reads colors (demodulated when s.demodulate), last remodulates; out must not alias in
 hipError_t launch_atrous(const float4* in, float4* out, const float4* albedo, const float4* nd, int32_t W, int32_t H, const AtrousStep& s,
                          bool first, bool last, hipStream_t stream);
+// one iteration of the variance-guided filter (pt_denoise_variance): {x, v} float4 in / out; FIRST reads colors + the variance read-out
+// (demodulated when s.demodulate), LAST remodulates both; out must not alias in
+struct AtrousVarStep {
+    int32_t step;            // 2^i
+    int32_t demodulate;
+    int32_t lum_on, normal_on, depth_on;   // 0: that weight is 1 (sigma +inf; sigma_normal 0)
+    float sigma_luminance, sigma_normal, sigma_depth;
+};
+hipError_t launch_atrous_var(const float4* in, const float* var, float4* out, const float4* albedo, const float4* nd, int32_t W, int32_t H,
+                             const AtrousVarStep& s, bool first, bool last, hipStream_t stream);
+// per local pixel, the variance of its mean luminance from colors[].xyz / .w (option "moments"); n from tile_spp (adaptive frames, per 8x8
+// tile of the local frame) or n_all (tile_spp null): pt_read_variance, pinned in include/pt_api.h
+hipError_t launch_variance(const float4* colors, const int32_t* tile_spp, int32_t n_all, int32_t W, int64_t npix, float* out, hipStream_t stream);
 // next-event estimation (pt_nee.hip; the estimator is pinned in include/pt_api.h next to pt_render_nee)
 struct NeeTable {
     const int32_t* tri;          // [n] packed triangle of each light

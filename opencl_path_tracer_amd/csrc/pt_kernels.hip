@@ -80,14 +80,18 @@ enum : int { kSchedLockstep = 0, kSchedSuspend = 1, kSchedMigrate = 2 };
 // coordinates are rebuilt from its id at every sample start.  (The allocator spilled seven dwords around every
 // traversal of the 72-VGPR instance: 16 GB written and ~38 GB re-read per 42-ms launch, profiles/r03/a_*.)
 // prog.cl:379 on the frame buffer itself (LEAN): sample 0 starts from black (prog.cl:312-314)
+// (and, with option "moments", the running second moment in .w, from the same 16-B load)
 PT_DEV void fold_sample(const RenderParams& p, int li, f3 color, int s) {
     f3 acc = mk(0.0f, 0.0f, 0.0f);
+    float m2 = 0.0f;
     if (s != 0) {
         const float4 c = p.colors[li];
         acc = mk(c.x, c.y, c.z);
+        m2 = c.w;
     }
     acc = running_mean(acc, color, s);
-    p.colors[li] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+    m2 = p.moments ? running_moment(m2, color, s) : 0.0f;
+    p.colors[li] = make_float4(acc.x, acc.y, acc.z, m2);
 }
 
 template <bool SPLIT, int MODE, bool COUNT, bool LEAN, bool SK>
@@ -95,9 +99,11 @@ PT_DEV void render_pixel_lockstep(const RenderParams& p, const SceneView& sv, co
                                   int s_begin, int s_end, unsigned* segs, WorkCount* wc) {
     int seed = p.rnds[px.li];
     f3 acc = mk(0.0f, 0.0f, 0.0f);
+    float m2 = 0.0f;                           // option "moments": the running second moment (colors[].w)
     if (!LEAN && s_begin != 0) {               // prog.cl:312-314: sample 0 starts from black
         const float4 c = p.colors[px.li];
         acc = mk(c.x, c.y, c.z);
+        if (p.moments) m2 = c.w;
     }
     const int camX = (int)p.cam.XM;
     const int gx = px.gid % camX, gy = px.gid / camX;                                // prog.cl:84-85
@@ -129,9 +135,12 @@ PT_DEV void render_pixel_lockstep(const RenderParams& p, const SceneView& sv, co
             shade_hit<SK>(rP, rD, st, seed, inside, p, sv.tris, sv.meta, ti, t);
         }
         if (LEAN) fold_sample(p, px.li, st.C(), s);
-        else acc = running_mean(acc, st.C(), s);
+        else {
+            acc = running_mean(acc, st.C(), s);
+            if (p.moments) m2 = running_moment(m2, st.C(), s);
+        }
     }
-    if (!LEAN) p.colors[px.li] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+    if (!LEAN) p.colors[px.li] = make_float4(acc.x, acc.y, acc.z, m2);
     p.rnds[px.li] = seed;
     if (SPLIT) {
         float4* r = reinterpret_cast<float4*>(&p.rays[px.li]);
@@ -149,9 +158,11 @@ PT_DEV void render_pixel_suspend(const RenderParams& p, const SceneView& sv, con
     bool inside = false;
     int seed = p.rnds[px.li];
     f3 acc = mk(0.0f, 0.0f, 0.0f);
+    float m2 = 0.0f;                           // option "moments": the running second moment (colors[].w)
     if (!LEAN && s_begin != 0) {               // prog.cl:312-314: sample 0 starts from black
         const float4 c = p.colors[px.li];
         acc = mk(c.x, c.y, c.z);
+        if (p.moments) m2 = c.w;
     }
     int s = s_begin;
     int bounce = 0;
@@ -213,12 +224,15 @@ PT_DEV void render_pixel_suspend(const RenderParams& p, const SceneView& sv, con
         }
         if (finished) {
             if (LEAN) fold_sample(p, px.li, st.C(), s);
-            else acc = running_mean(acc, st.C(), s);
+            else {
+                acc = running_mean(acc, st.C(), s);
+                if (p.moments) m2 = running_moment(m2, st.C(), s);
+            }
             ++s;
                 fresh = true;
         }
     }
-    if (!LEAN) p.colors[px.li] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+    if (!LEAN) p.colors[px.li] = make_float4(acc.x, acc.y, acc.z, m2);
     p.rnds[px.li] = seed;
     if (SPLIT) {
         float4* r = reinterpret_cast<float4*>(&p.rays[px.li]);
@@ -286,6 +300,7 @@ PT_DEV void render_items_migrating(const RenderParams& p, const SceneView& sv, c
     bool inside = false;
     int seed = 0;
     f3 acc = mk(0.0f, 0.0f, 0.0f);
+    float m2 = 0.0f;                       // option "moments": the running second moment (colors[].w)
     int s = 0, bounce = 0;
     bool fresh = true, traversing = false;
     bool parked = true, on_next = false;
@@ -351,9 +366,11 @@ PT_DEV void render_items_migrating(const RenderParams& p, const SceneView& sv, c
         s = begin_of(item);
         if (!LEAN) {
             acc = mk(0.0f, 0.0f, 0.0f);
+            m2 = 0.0f;
             if (s != 0) {                          // prog.cl:312-314: sample 0 starts from black
                 const float4 c = p.colors[li];
                 acc = mk(c.x, c.y, c.z);
+                if (p.moments) m2 = c.w;
             }
         }
         fresh = true;
@@ -366,7 +383,7 @@ PT_DEV void render_items_migrating(const RenderParams& p, const SceneView& sv, c
         if (COUNT && first_active_lane()) wc->wtrips++;
         // ---- a pixel that has had its samples of the item is written out
         if (!parked && fresh && !traversing && s == (on_next ? nxt_end : cur_end)) {
-            if (!LEAN) p.colors[li] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+            if (!LEAN) p.colors[li] = make_float4(acc.x, acc.y, acc.z, m2);
             p.rnds[li] = seed;
             parked = true;
         }
@@ -457,7 +474,10 @@ PT_DEV void render_items_migrating(const RenderParams& p, const SceneView& sv, c
         samples += (unsigned long long)__popcll(__ballot(finished));
         if (finished) {
             if (LEAN) fold_sample(p, li, st.C(), s);
-            else acc = running_mean(acc, st.C(), s);
+            else {
+                acc = running_mean(acc, st.C(), s);
+                if (p.moments) m2 = running_moment(m2, st.C(), s);
+            }
             ++s;
             fresh = true;
         }

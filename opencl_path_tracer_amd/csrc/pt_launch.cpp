@@ -130,6 +130,7 @@ void fill_params(const pt_context* ctx, const pt_camera* cam, RenderParams* p) {
     p->colors = ctx->d_colors;
     p->rays = ctx->d_rays;
     p->stats = ctx->d_stats;
+    p->moments = ctx->moments;
     p->cam = *cam;
     p->width = ctx->W;
     p->height = ctx->H;
@@ -373,6 +374,7 @@ int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
         if (le != hipSuccess) { ctx->counters_suspect = true; return fail(ctx, PT_EHIP, std::string("launch_trace_ray: ") + hipGetErrorString(le)); }
     }
     ctx->render_epoch++;
+    note_moments(ctx, current_sample);
     rc = time_end(ctx, ep);
     if (rc != PT_OK) ctx->counters_suspect = true;
     return rc;
@@ -558,6 +560,7 @@ int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t
     p.first_sample = ctx->current_sample;
     p.nsamples = nsamples;
     ctx->render_epoch++;
+    note_moments(ctx, p.first_sample);
     if (ctx->variant == 1) {
         if ((rc = render_wavefront(ctx, p, nsamples)) != PT_OK) return rc;
         ctx->current_sample += nsamples;
@@ -623,6 +626,7 @@ int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations
     PT_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->d_adapt_err, 0x7f800000, (size_t)n_frame, ctx->stream));      // +inf: no estimate yet
     ctx->adaptive_frame = true;
     ctx->render_epoch++;
+    note_moments(ctx, 0);
     RenderParams p;
     fill_params(ctx, cam, &p);
     p.iterations = iterations;

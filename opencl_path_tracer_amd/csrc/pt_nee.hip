@@ -114,9 +114,11 @@ __global__ void __launch_bounds__(BLOCK) k_nee(RenderParams p, NeeTable lt, long
         const float pix_x = (float)(gid % camX), pix_y = (float)(gid / camX);      // prog.cl:84-85
         int seed = p.rnds[i];
         f3 acc = mk(0.f, 0.f, 0.f);
+        float m2 = 0.0f;                           // option "moments": the running second moment (colors[].w)
         if (p.first_sample != 0) {                 // prog.cl:312-314: sample 0 starts from black
             const float4 c = p.colors[i];
             acc = mk(c.x, c.y, c.z);
+            if (p.moments) m2 = c.w;
         }
         f3 rP = mk(0.f, 0.f, 0.f), rD = mk(0.f, 0.f, 1.f);
         for (int s = p.first_sample; s < p.first_sample + p.nsamples; ++s) {
@@ -137,8 +139,9 @@ __global__ void __launch_bounds__(BLOCK) k_nee(RenderParams p, NeeTable lt, long
                 shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, t, &hook);
             }
             acc = running_mean(acc, st.C(), s);
+            if (p.moments) m2 = running_moment(m2, st.C(), s);
         }
-        p.colors[i] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+        p.colors[i] = make_float4(acc.x, acc.y, acc.z, m2);
         p.rnds[i] = seed;
         float4* rr = reinterpret_cast<float4*>(&p.rays[i]);        // the last segment's ray, as trace_ray leaves it
         rr[0] = make_float4(rP.x, rP.y, rP.z, 0.0f);

@@ -80,12 +80,15 @@ PT_DEV int ray_cost_class(const WfParams& w, f3 P, f3 D) {
 
 PT_DEV void wf_finalize(const WfParams& w, int li, f3 color) {
     f3 acc = mk(0.0f, 0.0f, 0.0f);
+    float m2 = 0.0f;
     if (w.sample != 0) {
         const float4 c = w.rp.colors[li];
         acc = mk(c.x, c.y, c.z);
+        m2 = c.w;
     }
     acc = running_mean(acc, color, w.sample);
-    w.rp.colors[li] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+    m2 = w.rp.moments ? running_moment(m2, color, w.sample) : 0.0f;      // option "moments" (pt_api.h)
+    w.rp.colors[li] = make_float4(acc.x, acc.y, acc.z, m2);
 }
 
 // The four path factors and the colour of pixel li in HBM, sP[field][li] x 12 B, behind the accessors shade_hit uses
