@@ -274,6 +274,49 @@ void pt_denoise_variance_defaults(pt_denoise_variance_params* p);
 int pt_denoise_variance(pt_context* ctx, const pt_denoise_variance_params* p);
 void* pt_device_denoised(pt_context* ctx);                               /* NULL until pt_denoise ran */
 
+/* ---- temporal accumulation with reprojection (new: the temporal part of SVGF; the reference restarts at every camera move) -----
+ * pt_temporal_accumulate blends the current frame into a history kept by the context, reprojected from the view the history was made
+ * in.  Per local pixel p of the frame seen through cam (the camera its launches and its guides used), with the guides of the last
+ * pt_render_aovs, float32 on the device (one lane per pixel, k_temporal), in this order:
+ *   1. depth < 0 (the primary ray missed): no history.
+ *   2. X = fmaf(depth, D, eye), D = the direction camera_get_ray(p, cam, 0.5f, 0.5f) gives (normalize3: d times 1.0f / sqrtf(d.d)).
+ *   3. v = X - eye_prev, ahead = lookat_prev - eye_prev; by Cramer's rule with triple products (dot / cross with fmaf as the kernels'
+ *      dot3 / cross3): det = ahead.(right x up), a = v.(right x up) / det, b = ahead.(v x up) / det, c = ahead.(right x v) / det
+ *      (right, up: prev's).  a <= 0 (X behind prev) or not finite: no history.  u = b / a, w = c / a,
+ *      x' = ((u + 1) XM) 0.5 - 0.5, y' = ((w + 1) YM) 0.5 - 0.5: continuous coordinates relative to pixel centres, row 0 at the bottom.
+ *   4. x0 = floorf(x'), fx = x' - x0 (same for y); fx < 2^-10 -> fx = 0; fx > 1 - 2^-10 -> fx = 0 and x0 + 1.  Taps q in the order
+ *      (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), weights (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy; a tap of
+ *      weight 0 is neither read nor tested (a camera at rest reads exactly one tap: the pixel itself).
+ *   5. q is valid iff it is in the frame, depth_q > 0, material_q == material_p, the normals agree (both 0: yes; exactly one 0: no;
+ *      else dot(n_p, n_q) >= normal_cos) and |sqrtf(v.v) - depth_q| <= depth_tolerance depth_q (q's values: the previous set's guides).
+ *   6. W = sum of the valid taps' weights (in tap order); W < 0.01: no history; else colour_h, m2_h, n_h = sum fmaf(value_q, w_q, .) / W.
+ *   Blend, counted in samples: k = the frame's samples at p (pt_read_sample_counts), n_h' = min(n_h, max_history); n_h' = 0 (no
+ *   history, or max_history = 0: how a caller restarts) -> the frame's own .xyz and .w bit for bit and n = k; else n = n_h' + k,
+ *   c = fmaf(n_h', c_h, k c_frame) / n per channel, the same for m2.  v = fmaxf(fmaf(-l(c), l(c), m2), 0) / (n - 1), +inf when n < 2
+ *   (pt_read_variance's read-out with a fractional n).  The result (c, m2, n and the guides it was made with: 40 B/px) becomes the
+ *   history, cam its camera.  Two history sets (80 B/px) and the variance (4 B/px) are allocated on first use; nothing is copied.
+ * World-1 contexts only.  Checked in this order: arguments (max_history >= 0, normal_cos in [-1, 1], depth_tolerance >= 0, none NaN)
+ * and world, PT_EINVAL; the device, PT_ENODEVICE; then PT_EINVAL without guides or with stale ones, when the frame's moments are not
+ * valid or it has no samples (pt_read_variance's rule), when a launch of the frame used a camera that differs in any byte from the one
+ * it started with, when the guides' camera differs from the frame's, and when this frame was already accumulated.
+ * pt_upload_triangles / pt_upload_materials drop the history: the next accumulate gives n = k everywhere. */
+typedef struct { int32_t max_history; float normal_cos, depth_tolerance; } pt_temporal_params;
+/* max_history 64, normal_cos 0.9, depth_tolerance 0.02: from the sweep of tools/temporal_bench.py at 1920x1080, 8 bounces, 16 frames of
+ * 4 spp on the Cornell box and MESH-100k.  64 has the best sum of the two RMSE ratios to raw (0.235 + 0.501); normal_cos and
+ * depth_tolerance move them by less than 0.3 % over 0.8-0.95 and 0.01-0.05, so the stricter trial values stay
+ * (profiles/temporal/README.md) */
+void pt_temporal_defaults(pt_temporal_params* p);
+int pt_temporal_accumulate(pt_context* ctx, const pt_temporal_params* p);
+/* the last accumulate's result: rgbv {r, g, b, v} 16 B per local pixel, n the samples behind it (float: bilinear histories are
+ * fractional); either pointer may be NULL */
+int pt_read_temporal(pt_context* ctx, float* rgbv, float* n, int64_t npix);
+void* pt_device_temporal(pt_context* ctx);      /* that colour on the device: {r, g, b, m2} 16 B per local pixel; NULL before an accumulate */
+/* pt_denoise_variance's filter (same parameters, same guides, same output: pt_read_denoised / pt_device_denoised) run on the last
+ * accumulate's colour and variance instead of colors and pt_read_variance's.  PT_EINVAL unless an accumulate ran on the current guides. */
+int pt_denoise_temporal(pt_context* ctx, const pt_denoise_variance_params* p);
+/* host only: steps 2-3 for pixel (x, y) of cur at depth into prev: out = {x', y', sqrtf(v.v)}; PT_EINVAL when a <= 0 */
+int pt_debug_reproject(const pt_camera* cur, const pt_camera* prev, int32_t x, int32_t y, float depth, float out[3]);
+
 /* ---- multi-GPU frame assembly (SURVEY 8b "RCCL communicator per context", 8e) ----------
  * The reference is single-device (main.cpp:466-476); a host that tiles the frame over N contexts with
  * pt_create_tiled assembles it with these.  One process (or thread) per GPU:

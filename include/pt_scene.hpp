@@ -143,6 +143,29 @@ public:
         pt_denoise_variance_defaults(&d);
         ck(pt_denoise_variance(ctx, p ? p : &d));
     }
+    void set_option(const char* key, int64_t value) { ck(pt_set_option(ctx, key, value)); }   // pt_set_option, e.g. ("moments", 1)
+    // temporal accumulation with reprojection (pt_temporal_accumulate; p = NULL: the defaults): after a frame rendered with option
+    // "moments" = 1 and render_aovs() of its camera
+    void temporal_accumulate(const pt_temporal_params* p = nullptr) {
+        pt_temporal_params d;
+        pt_temporal_defaults(&d);
+        ck(pt_temporal_accumulate(ctx, p ? p : &d));
+    }
+    // the last accumulate's {r, g, b, variance of the mean} per local pixel (rgbv: 4 floats each) and the samples behind it
+    void read_temporal(std::vector<float>& rgbv, std::vector<float>& n) {
+        int64_t np = 0;
+        ck(pt_local_pixel_count(ctx, &np));
+        rgbv.resize((size_t)np * 4);
+        n.resize((size_t)np);
+        ck(pt_read_temporal(ctx, rgbv.data(), n.data(), np));
+    }
+    void* device_temporal() { return pt_device_temporal(ctx); }   // {r, g, b, m2} per local pixel; NULL before an accumulate
+    // the variance-guided filter on the accumulated colour and variance (pt_denoise_temporal); result: pt_read_denoised like denoise()
+    void denoise_temporal(const pt_denoise_variance_params* p = nullptr) {
+        pt_denoise_variance_params d;
+        pt_denoise_variance_defaults(&d);
+        ck(pt_denoise_temporal(ctx, p ? p : &d));
+    }
     int current_sample() { int32_t s = 0; ck(pt_get_current_sample(ctx, &s)); return s; }
     void reset_samples() { ck(pt_set_current_sample(ctx, 0)); }                                // main.cpp:1046
     void finish() { ck(pt_sync(ctx)); }                                                        // queue.finish(), main.cpp:675

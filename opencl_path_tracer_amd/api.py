@@ -47,6 +47,7 @@ EXPORTS = [
     "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
     "pt_render_nee", "pt_nee_rand", "pt_debug_light_table",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
+    "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
     "pt_render_aovs", "pt_read_aovs", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
@@ -109,6 +110,12 @@ def _load():
     sig("pt_device_variance", vp, vp)
     sig("pt_denoise_variance_defaults", None, vp)
     sig("pt_denoise_variance", C.c_int, vp, vp)
+    sig("pt_temporal_defaults", None, vp)
+    sig("pt_temporal_accumulate", C.c_int, vp, vp)
+    sig("pt_read_temporal", C.c_int, vp, vp, vp, i64)
+    sig("pt_device_temporal", vp, vp)
+    sig("pt_denoise_temporal", C.c_int, vp, vp)
+    sig("pt_debug_reproject", C.c_int, vp, vp, i32, i32, f32, fp)
     sig("pt_render_aovs", C.c_int, vp, vp, i32, i32)
     sig("pt_read_aovs", C.c_int, vp, vp, vp, i64)
     sig("pt_denoise_defaults", None, vp)
@@ -259,6 +266,31 @@ def denoise_defaults():
     p = DenoiseParams()
     LIB.pt_denoise_defaults(C.byref(p))
     return p.as_dict()
+
+
+class TemporalParams(C.Structure):
+    """pt_temporal_params (include/pt_api.h)."""
+    _fields_ = [("max_history", C.c_int32), ("normal_cos", C.c_float), ("depth_tolerance", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def temporal_defaults():
+    """pt_temporal_defaults as a dict: max_history, normal_cos, depth_tolerance."""
+    p = TemporalParams()
+    LIB.pt_temporal_defaults(C.byref(p))
+    return p.as_dict()
+
+
+def debug_reproject(cur, prev, x, y, depth):
+    """pt_debug_reproject: pixel (x, y) of CAMERA record cur at `depth`, in CAMERA record prev's view -> (x', y', distance to prev's
+    eye); raises PtError(PT_EINVAL) when the point is not in front of prev."""
+    out = (C.c_float * 3)()
+    rc = LIB.pt_debug_reproject(_ptr(cur), _ptr(prev), int(x), int(y), float(depth), out)
+    if rc != PT_OK:
+        raise PtError(rc, (LIB.pt_last_error(None) or b"").decode())
+    return (out[0], out[1], out[2])
 
 
 def comm_available():
@@ -506,6 +538,40 @@ class Scene:
                 raise TypeError("unknown denoise_variance parameter %r" % k)
             setattr(p, k, v)
         self._ck(LIB.pt_denoise_variance(self._h, C.byref(p)))
+        return self.read_denoised()
+
+    # -- temporal accumulation with reprojection (include/pt_api.h pins it)
+    def temporal_accumulate(self, **params):
+        """pt_temporal_accumulate with pt_temporal_defaults overridden by params: blends this frame (rendered with set_option("moments", 1),
+        guides from render_aovs with the frame's camera) into the reprojected history.  Returns rgbv like read_temporal()."""
+        p = TemporalParams(**temporal_defaults())
+        for k, v in params.items():
+            if k not in p.as_dict():
+                raise TypeError("unknown temporal parameter %r" % k)
+            setattr(p, k, v)
+        self._ck(LIB.pt_temporal_accumulate(self._h, C.byref(p)))
+        return self.read_temporal()[0]
+
+    def read_temporal(self):
+        """(rgbv (local_pixels, 4) float32 {r, g, b, variance of the mean}, n (local_pixels,) float32 samples behind it) of the last
+        temporal_accumulate."""
+        rgbv = np.empty((self.local_pixels, 4), dtype=np.float32)
+        n = np.empty(self.local_pixels, dtype=np.float32)
+        self._ck(LIB.pt_read_temporal(self._h, _ptr(rgbv), _ptr(n), n.size))
+        return rgbv, n
+
+    def device_temporal(self):
+        """Device pointer of the last temporal_accumulate's colour, {r, g, b, m2} per local pixel (None before the first)."""
+        return LIB.pt_device_temporal(self._h)
+
+    def denoise_temporal(self, **params):
+        """denoise_variance's filter (same params) on the last temporal_accumulate's colour and variance; returns like denoise_variance."""
+        p = DenoiseVarianceParams(**denoise_variance_defaults())
+        for k, v in params.items():
+            if k not in p.as_dict():
+                raise TypeError("unknown denoise_temporal parameter %r" % k)
+            setattr(p, k, v)
+        self._ck(LIB.pt_denoise_temporal(self._h, C.byref(p)))
         return self.read_denoised()
 
     def read_denoised(self):

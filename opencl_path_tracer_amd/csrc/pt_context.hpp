@@ -139,6 +139,23 @@ struct pt_context {
     int moments = 0;
     bool moments_valid = false;
     float* d_variance = nullptr;
+    // temporal accumulation (pt_temporal_accumulate).  Every frame start bumps frame_serial and records the frame's camera (note_frame;
+    // frame_cam_same while every launch of the frame used it byte for byte); pt_render_aovs records its camera and bumps aov_serial.
+    // Two history sets in d_temporal, allocated on first use: per set and local pixel {r, g, b, m2}, {nx, ny, nz, depth} of the guides
+    // it was made with, {n, material} (40 B; the float4 arrays of both sets, then the float2 ones), and the variance of the mean of the
+    // last result in d_temporal_var.  temporal_out: the set the last accumulate wrote (-1: none yet)
+    uint64_t frame_serial = 0;
+    pt_camera frame_cam = {};
+    bool frame_cam_same = false;
+    uint64_t aov_serial = 0;
+    pt_camera aov_cam = {};
+    float4* d_temporal = nullptr;
+    float* d_temporal_var = nullptr;
+    int temporal_out = -1;
+    bool temporal_history = false;      // set temporal_out is the history of the next accumulate (dropped when the scene is uploaded)
+    pt_camera temporal_cam = {};        // the camera of that history
+    uint64_t temporal_frame = ~0ull;    // frame_serial of the last accumulate
+    uint64_t temporal_aov = ~0ull;      // aov_serial of the guides it used
     // next-event estimation (pt_render_nee): the light table, built on the host at first use after an upload (nee_valid).  Packed
     // triangle index and cdf per light; P_sel / area per packed triangle (0 for non-lights).  Device copies allocated with it.
     std::vector<int32_t> nee_tri;
@@ -201,9 +218,19 @@ int host_threads(const pt_context* ctx);                          // threads of 
             return fail(ctx, PT_EHIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
-// a render launch of samples [first_sample, ...) was enqueued: a frame starts at sample 0, and stays valid for pt_read_variance while every
-// launch of it has folded the second moment (option "moments")
-inline void note_moments(pt_context* ctx, int32_t first_sample) { ctx->moments_valid = (first_sample == 0 || ctx->moments_valid) && ctx->moments != 0; }
+// a render launch of samples [first_sample, ...) through cam was enqueued: a frame starts at sample 0, and stays valid for pt_read_variance
+// while every launch of it has folded the second moment (option "moments"), and for pt_temporal_accumulate while every launch of it used
+// the camera it started with
+inline void note_frame(pt_context* ctx, int32_t first_sample, const pt_camera* cam) {
+    ctx->moments_valid = (first_sample == 0 || ctx->moments_valid) && ctx->moments != 0;
+    if (first_sample == 0) {
+        ++ctx->frame_serial;
+        ctx->frame_cam = *cam;
+        ctx->frame_cam_same = true;
+    } else if (std::memcmp(cam, &ctx->frame_cam, sizeof(pt_camera)) != 0) {
+        ctx->frame_cam_same = false;
+    }
+}
 
 #define PT_NEED_DEVICE(ctx)                                                                 \
     do {                                                                                    \

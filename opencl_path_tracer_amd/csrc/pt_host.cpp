@@ -234,6 +234,8 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->d_aov) (void)hipFree(ctx->d_aov);
         if (ctx->d_dn) (void)hipFree(ctx->d_dn);
         if (ctx->d_variance) (void)hipFree(ctx->d_variance);
+        if (ctx->d_temporal) (void)hipFree(ctx->d_temporal);
+        if (ctx->d_temporal_var) (void)hipFree(ctx->d_temporal_var);
         if (ctx->d_nee_tri) (void)hipFree(ctx->d_nee_tri);
         if (ctx->d_nee_cdf) (void)hipFree(ctx->d_nee_cdf);
         if (ctx->d_nee_pdf_area) (void)hipFree(ctx->d_nee_pdf_area);
@@ -477,7 +479,12 @@ int pt_render_aovs(pt_context* ctx, const pt_camera* cam, int32_t subpixels, int
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
     PT_HIP(ctx, launch_aovs(p, subpixels, specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, ctx->cu_count, ctx->stream));
+    // the first guides after pt_upload_triangles / pt_upload_materials (which made the old ones stale): the temporal history describes
+    // the old scene, and every accumulate needs guides, so this is where it is dropped
+    if (!ctx->aov_valid) ctx->temporal_history = false;
     ctx->aov_valid = true;
+    ctx->aov_cam = *cam;
+    ++ctx->aov_serial;
     return PT_OK;
 }
 int pt_read_aovs(pt_context* ctx, float* albedo_rgbm, float* normal_depth, int64_t npix) {
@@ -570,18 +577,15 @@ void pt_denoise_variance_defaults(pt_denoise_variance_params* p) {
     p->sigma_depth = 0.05f;
     p->demodulate = 0;
 }
-int pt_denoise_variance(pt_context* ctx, const pt_denoise_variance_params* dp) {
-    if (!ctx) return PT_EINVAL;
-    if (!dp) return fail(ctx, PT_EINVAL, "pt_denoise_variance: params is NULL");
-    if (dp->iterations < 1 || dp->iterations > 10) return fail(ctx, PT_EINVAL, "pt_denoise_variance: iterations must be 1..10");
-    if (!(dp->sigma_luminance >= 0.0f) || !(dp->sigma_normal >= 0.0f) || !(dp->sigma_depth >= 0.0f))
-        return fail(ctx, PT_EINVAL, "pt_denoise_variance: sigmas must be >= 0 (and not NaN)");
-    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_denoise_variance: contexts of one rank (world == 1) only");
-    if (!ctx->aov_valid)
-        return fail(ctx, PT_EINVAL, "pt_denoise_variance: no guides (pt_render_aovs has not run since the scene was last uploaded)");
-    PT_NEED_DEVICE(ctx);
-    int rc = compute_variance(ctx, "pt_denoise_variance");       // (checks the moments)
-    if (rc != PT_OK) return rc;
+// the arguments of the variance-guided filter: "" or what is wrong (pt_denoise_variance, pt_denoise_temporal)
+static std::string variance_params_error(const pt_denoise_variance_params* dp) {
+    if (!dp) return "params is NULL";
+    if (dp->iterations < 1 || dp->iterations > 10) return "iterations must be 1..10";
+    if (!(dp->sigma_luminance >= 0.0f) || !(dp->sigma_normal >= 0.0f) || !(dp->sigma_depth >= 0.0f)) return "sigmas must be >= 0 (and not NaN)";
+    return "";
+}
+// the iterations of k_atrous_var over colour in0 (.xyz) and variance var with the current guides, into the two d_dn buffers
+static int atrous_var_iterations(pt_context* ctx, const pt_denoise_variance_params* dp, const float4* in0, const float* var) {
     const size_t npix = (size_t)ctx->npix;
     if (!ctx->d_dn) PT_HIP(ctx, hipMalloc((void**)&ctx->d_dn, 2 * sizeof(float4) * std::max<size_t>(npix, 1)));
     for (int i = 0; i < dp->iterations; ++i) {
@@ -594,12 +598,130 @@ int pt_denoise_variance(pt_context* ctx, const pt_denoise_variance_params* dp) {
         s.sigma_luminance = dp->sigma_luminance;
         s.sigma_normal = dp->sigma_normal;
         s.sigma_depth = dp->sigma_depth;
-        const float4* in = i == 0 ? ctx->d_colors : ctx->d_dn + ((i - 1) & 1) * npix;
+        const float4* in = i == 0 ? in0 : ctx->d_dn + ((i - 1) & 1) * npix;
         float4* out = ctx->d_dn + (i & 1) * npix;
-        PT_HIP(ctx, launch_atrous_var(in, ctx->d_variance, out, ctx->d_aov, ctx->d_aov + npix, ctx->W, ctx->local_rows, s, i == 0,
+        PT_HIP(ctx, launch_atrous_var(in, var, out, ctx->d_aov, ctx->d_aov + npix, ctx->W, ctx->local_rows, s, i == 0,
                                       i == dp->iterations - 1, ctx->stream));
     }
     ctx->d_denoised = ctx->d_dn + ((dp->iterations - 1) & 1) * npix;
+    return PT_OK;
+}
+int pt_denoise_variance(pt_context* ctx, const pt_denoise_variance_params* dp) {
+    if (!ctx) return PT_EINVAL;
+    const std::string why = variance_params_error(dp);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_denoise_variance: " + why);
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_denoise_variance: contexts of one rank (world == 1) only");
+    if (!ctx->aov_valid)
+        return fail(ctx, PT_EINVAL, "pt_denoise_variance: no guides (pt_render_aovs has not run since the scene was last uploaded)");
+    PT_NEED_DEVICE(ctx);
+    const int rc = compute_variance(ctx, "pt_denoise_variance");       // (checks the moments)
+    if (rc != PT_OK) return rc;
+    return atrous_var_iterations(ctx, dp, ctx->d_colors, ctx->d_variance);
+}
+
+// ---- temporal accumulation with reprojection (kernel k_temporal, pt_temporal.hip; pinned in include/pt_api.h)
+void pt_temporal_defaults(pt_temporal_params* p) {
+    if (!p) return;
+    p->max_history = 64;
+    p->normal_cos = 0.9f;
+    p->depth_tolerance = 0.02f;
+}
+// set s of the two history sets: {r, g, b, m2}, {nx, ny, nz, depth}, {n, material} per local pixel
+static float4* temporal_colour(const pt_context* ctx, int s) { return ctx->d_temporal + (size_t)s * (size_t)std::max<int64_t>(ctx->npix, 1); }
+static float4* temporal_guides(const pt_context* ctx, int s) { return ctx->d_temporal + (size_t)(2 + s) * (size_t)std::max<int64_t>(ctx->npix, 1); }
+static float2* temporal_nm(const pt_context* ctx, int s) {
+    const size_t np = (size_t)std::max<int64_t>(ctx->npix, 1);
+    return reinterpret_cast<float2*>(ctx->d_temporal + 4 * np) + (size_t)s * np;
+}
+int pt_temporal_accumulate(pt_context* ctx, const pt_temporal_params* tp) {
+    if (!ctx) return PT_EINVAL;
+    if (!tp) return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: params is NULL");
+    if (tp->max_history < 0) return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: max_history must be >= 0");
+    if (!(tp->normal_cos >= -1.0f && tp->normal_cos <= 1.0f)) return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: normal_cos must be in [-1, 1]");
+    if (!(tp->depth_tolerance >= 0.0f)) return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: depth_tolerance must be >= 0 (and not NaN)");
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: contexts of one rank (world == 1) only");
+    PT_NEED_DEVICE(ctx);
+    if (!ctx->aov_valid)
+        return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: no guides (pt_render_aovs has not run since the scene was last uploaded)");
+    if (!ctx->moments_valid)
+        return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: the frame was not rendered with option moments = 1 from its first sample");
+    if (ctx->current_sample <= 0) return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: the frame has no samples");
+    if (!ctx->frame_cam_same) return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: the launches of the frame used different cameras");
+    if (std::memcmp(&ctx->aov_cam, &ctx->frame_cam, sizeof(pt_camera)) != 0)
+        return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: the guides were rendered with a different camera from the frame");
+    if (ctx->temporal_frame == ctx->frame_serial) return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: this frame was already accumulated");
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t np = (size_t)std::max<int64_t>(ctx->npix, 1);
+    if (!ctx->d_temporal) {
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_temporal, (4 * sizeof(float4) + 2 * sizeof(float2)) * np));
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_temporal_var, sizeof(float) * np));
+    }
+    const int out = ctx->temporal_out == 0 ? 1 : 0, prev = 1 - out;
+    TemporalArgs a;
+    a.cur = ctx->frame_cam;
+    a.prev = ctx->temporal_cam;
+    a.colors = ctx->d_colors;
+    a.tile_spp = ctx->adaptive_frame ? ctx->d_adapt_spp : nullptr;
+    a.n_all = ctx->current_sample;
+    a.albedo = ctx->d_aov;
+    a.nd = ctx->d_aov + ctx->npix;
+    a.prev_c = temporal_colour(ctx, prev);
+    a.prev_g = temporal_guides(ctx, prev);
+    a.prev_nm = temporal_nm(ctx, prev);
+    a.out_c = temporal_colour(ctx, out);
+    a.out_g = temporal_guides(ctx, out);
+    a.out_nm = temporal_nm(ctx, out);
+    a.out_v = ctx->d_temporal_var;
+    a.W = ctx->W;
+    a.H = ctx->local_rows;
+    a.has_prev = ctx->temporal_history ? 1 : 0;
+    a.max_history = (float)tp->max_history;
+    a.normal_cos = tp->normal_cos;
+    a.depth_tolerance = tp->depth_tolerance;
+    PT_HIP(ctx, launch_temporal(a, ctx->stream));
+    ctx->temporal_out = out;
+    ctx->temporal_history = true;
+    ctx->temporal_cam = ctx->frame_cam;
+    ctx->temporal_frame = ctx->frame_serial;
+    ctx->temporal_aov = ctx->aov_serial;
+    return PT_OK;
+}
+int pt_read_temporal(pt_context* ctx, float* rgbv, float* n, int64_t npix) {
+    PT_NEED_DEVICE(ctx);
+    if (npix != ctx->npix) return fail(ctx, PT_EINVAL, "npix must equal the local pixel count");
+    if (ctx->temporal_out < 0) return fail(ctx, PT_EINVAL, "pt_read_temporal: pt_temporal_accumulate has not run");
+    int rc = PT_OK;
+    if (rgbv) {
+        std::vector<float> v((size_t)npix);
+        if ((rc = read_back(ctx, rgbv, temporal_colour(ctx, ctx->temporal_out), sizeof(float4) * (size_t)npix)) != PT_OK) return rc;
+        if ((rc = read_back(ctx, v.data(), ctx->d_temporal_var, sizeof(float) * (size_t)npix)) != PT_OK) return rc;
+        for (int64_t i = 0; i < npix; ++i) rgbv[4 * i + 3] = v[(size_t)i];
+    }
+    if (n) {
+        std::vector<float2> nm((size_t)npix);
+        if ((rc = read_back(ctx, nm.data(), temporal_nm(ctx, ctx->temporal_out), sizeof(float2) * (size_t)npix)) != PT_OK) return rc;
+        for (int64_t i = 0; i < npix; ++i) n[i] = nm[(size_t)i].x;
+    }
+    return PT_OK;
+}
+void* pt_device_temporal(pt_context* ctx) { return ctx && ctx->temporal_out >= 0 ? (void*)temporal_colour(ctx, ctx->temporal_out) : nullptr; }
+int pt_denoise_temporal(pt_context* ctx, const pt_denoise_variance_params* dp) {
+    if (!ctx) return PT_EINVAL;
+    const std::string why = variance_params_error(dp);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_denoise_temporal: " + why);
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_denoise_temporal: contexts of one rank (world == 1) only");
+    PT_NEED_DEVICE(ctx);
+    if (!ctx->aov_valid || ctx->temporal_out < 0 || ctx->temporal_aov != ctx->aov_serial)
+        return fail(ctx, PT_EINVAL, "pt_denoise_temporal: pt_temporal_accumulate has not run on the current guides");
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    return atrous_var_iterations(ctx, dp, temporal_colour(ctx, ctx->temporal_out), ctx->d_temporal_var);
+}
+int pt_debug_reproject(const pt_camera* cur, const pt_camera* prev, int32_t x, int32_t y, float depth, float out[3]) {
+    if (!cur || !prev || !out) return fail(nullptr, PT_EINVAL, "pt_debug_reproject: NULL argument");
+    if (!(cur->XM >= 1.0f && cur->XM <= 65535.0f && cur->YM >= 1.0f && cur->YM <= 65535.0f) || x < 0 || y < 0 || x >= (int32_t)cur->XM || y >= (int32_t)cur->YM)
+        return fail(nullptr, PT_EINVAL, "pt_debug_reproject: (x, y) must lie in cur's frame");
+    if (!reproject(*cur, *prev, y * (int32_t)cur->XM + x, depth, out))
+        return fail(nullptr, PT_EINVAL, "pt_debug_reproject: the point is not in front of prev (a <= 0)");
     return PT_OK;
 }
 
@@ -705,7 +827,7 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     lt.n = (int32_t)ctx->nee_tri.size();
     lt.strategy = strategy;
     ctx->render_epoch++;
-    note_moments(ctx, p.first_sample);
+    note_frame(ctx, p.first_sample, cam);
     EventPair* ep;
     if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
     PT_HIP(ctx, launch_nee(p, lt, ctx->npix, ctx->cu_count, ctx->stream));

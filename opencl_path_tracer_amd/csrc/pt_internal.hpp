@@ -369,4 +369,61 @@ __host__ __device__ __forceinline__ uint32_t nee_rand(uint32_t state, int segmen
     return lowbias32(lowbias32(state) + 0x9e3779b9u * (uint32_t)(3 * segment + dim + 1));
 }
 
+// temporal accumulation (pt_temporal.hip; pinned in include/pt_api.h next to pt_temporal_accumulate)
+struct TemporalArgs {
+    pt_camera cur, prev;           // the frame's view, the history's view
+    const float4* colors;          // the frame: .xyz the mean, .w the second moment
+    const int32_t* tile_spp;       // samples per 8x8 tile of an adaptive frame, or null: n_all for every pixel
+    int32_t n_all;
+    const float4* albedo;          // the current guides: albedo_rgbm (.w the material index), normal_depth
+    const float4* nd;
+    const float4* prev_c;          // the previous set (read only when has_prev): {r, g, b, m2}, {nx, ny, nz, depth}, {n, material}
+    const float4* prev_g;
+    const float2* prev_nm;
+    float4* out_c;                 // the new set, same layout, and the variance of the mean
+    float4* out_g;
+    float2* out_nm;
+    float* out_v;
+    int32_t W, H;                  // the frame (one rank: local pixel = global pixel id)
+    int32_t has_prev;
+    float max_history, normal_cos, depth_tolerance;
+};
+hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
+// float32 dot / cross with the fma placement of pt_device.hpp's dot3 / cross3
+__host__ __device__ __forceinline__ float rp_dot(const float* a, const float* b) { return __builtin_fmaf(a[2], b[2], __builtin_fmaf(a[1], b[1], a[0] * b[0])); }
+__host__ __device__ __forceinline__ void rp_cross(const float* a, const float* b, float* r) {
+    r[0] = __builtin_fmaf(a[1], b[2], -(a[2] * b[1]));
+    r[1] = __builtin_fmaf(a[2], b[0], -(a[0] * b[2]));
+    r[2] = __builtin_fmaf(a[0], b[1], -(a[1] * b[0]));
+}
+// The reprojection of k_temporal and pt_debug_reproject: global pixel gid's centre ray under cur -- camera_get_ray(gid, cur, 0.5f, 0.5f)
+// bit for bit (1 / sqrt rounds as normalize3's rsqrt_rn does) -- followed to depth, in prev's view: out = {x', y', |X - eye_prev|}.
+// false when X is not in front of prev (a <= 0, or a is not finite).
+__host__ __device__ inline bool reproject(const pt_camera& cur, const pt_camera& prev, int gid, float depth, float out[3]) {
+    const int X = (int)cur.XM, Y = (int)cur.YM;
+    const float sx = (2.0f * ((float)(gid % X) + 0.5f)) / (float)X - 1.0f;
+    const float sy = (2.0f * ((float)(gid / X) + 0.5f)) / (float)Y - 1.0f;
+    float d[3], v[3], ahead[3];
+    for (int i = 0; i < 3; ++i) d[i] = ((cur.lookat.s[i] + cur.right.s[i] * sx) + cur.up.s[i] * sy) - cur.eye.s[i];
+    const float inv = 1.0f / __builtin_sqrtf(rp_dot(d, d));
+    for (int i = 0; i < 3; ++i) {
+        v[i] = __builtin_fmaf(depth, d[i] * inv, cur.eye.s[i]) - prev.eye.s[i];
+        ahead[i] = prev.lookat.s[i] - prev.eye.s[i];
+    }
+    // v = a ahead + b right + c up by Cramer's rule: det = ahead . (right x up), a = v . (right x up) / det,
+    // b = ahead . (v x up) / det, c = ahead . (right x v) / det
+    float ru[3], vu[3], rv[3];
+    rp_cross(prev.right.s, prev.up.s, ru);
+    rp_cross(v, prev.up.s, vu);
+    rp_cross(prev.right.s, v, rv);
+    const float det = rp_dot(ahead, ru);
+    const float a = rp_dot(v, ru) / det;
+    if (!(a > 0.0f && a < __builtin_inff())) return false;
+    const float u = (rp_dot(ahead, vu) / det) / a, w = (rp_dot(ahead, rv) / det) / a;
+    out[0] = ((u + 1.0f) * prev.XM) * 0.5f - 0.5f;
+    out[1] = ((w + 1.0f) * prev.YM) * 0.5f - 0.5f;
+    out[2] = __builtin_sqrtf(rp_dot(v, v));
+    return true;
+}
+
 }  // namespace ptamd

@@ -374,7 +374,7 @@ int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
         if (le != hipSuccess) { ctx->counters_suspect = true; return fail(ctx, PT_EHIP, std::string("launch_trace_ray: ") + hipGetErrorString(le)); }
     }
     ctx->render_epoch++;
-    note_moments(ctx, current_sample);
+    note_frame(ctx, current_sample, cam);
     rc = time_end(ctx, ep);
     if (rc != PT_OK) ctx->counters_suspect = true;
     return rc;
@@ -560,7 +560,7 @@ int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t
     p.first_sample = ctx->current_sample;
     p.nsamples = nsamples;
     ctx->render_epoch++;
-    note_moments(ctx, p.first_sample);
+    note_frame(ctx, p.first_sample, cam);
     if (ctx->variant == 1) {
         if ((rc = render_wavefront(ctx, p, nsamples)) != PT_OK) return rc;
         ctx->current_sample += nsamples;
@@ -626,7 +626,7 @@ int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations
     PT_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->d_adapt_err, 0x7f800000, (size_t)n_frame, ctx->stream));      // +inf: no estimate yet
     ctx->adaptive_frame = true;
     ctx->render_epoch++;
-    note_moments(ctx, 0);
+    note_frame(ctx, 0, cam);
     RenderParams p;
     fill_params(ctx, cam, &p);
     p.iterations = iterations;
