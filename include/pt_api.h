@@ -195,6 +195,52 @@ uint32_t pt_nee_rand(uint32_t state, int32_t segment, int32_t dim);
  * orig_tri (add-order triangle index) and cdf are written (either may be NULL) */
 int pt_debug_light_table(pt_context* ctx, int32_t* orig_tri, float* cdf, int64_t cap, int64_t* n);
 
+/* ---- environment lighting for pt_render_nee (new: the reference's sky terms, prog.cl:367-376, are commented out) -----------
+ * A lat-long map lights the scene from infinity.  Only pt_render_nee draws it; without one (or with an all-zero one) pt_render_nee
+ * computes exactly what it computed before.
+ * Map and lookup: w x h texels of float RGB, row 0 touches the +y pole (y is up).  For a unit direction d, in float32:
+ *   theta = acosf(clamp(d.y, -1, 1)), phi = atan2f(d.z, d.x) - yaw (yaw = yaw_degrees pi / 180, rounded to float);
+ *   row = min(h - 1, floor(theta / pi * h)); col = min(w - 1, floor(frac(phi / (2 pi)) * w)), frac(x) = x - floor(x);
+ *   nearest texel (the map is piecewise constant); E(d) = scale * texel.  A 1 x 1 map is a constant sky.
+ * A miss on segment k along D ends the path as before and adds
+ *   k = 0: E(D) (prog.cl:369: no factor of two for a sky seen directly; iterations == 1, the flat preview, shows E(D));
+ *   k > 0: W_b E(D) (fL + fB) fS fR (prog.cl:371-373), W_b = 1 unless the previous vertex was a lobe vertex (below).
+ * Distribution: piecewise constant over texels with weight lum(texel) Omega(row), lum = the luminance of option "moments",
+ *   Omega(row) = (2 pi / w)(cos theta_row - cos theta_row+1), theta_row = pi row / h.  The host builds the row marginal cdf [h] and
+ *   the per-row column cdfs [h][w] in double and stores them as float (last entries 1; a row of weight 0 gets a uniform column cdf and
+ *   is never picked).  u1 picks the first row with row_cdf > u1, t1 = (u1 - below) / (row_cdf[row] - below) is the position inside
+ *   it: cos theta = cos theta_row - t1 (cos theta_row - cos theta_row+1); u2 picks the column the same way, phi = 2 pi (col + t2) / w
+ *   + yaw; w = (sin theta cos phi, cos theta, sin theta sin phi): uniform in solid angle inside the texel.
+ *   p_env(d) = P(texel) / Omega(row), P(texel) = the product of the two stored float cdfs' own steps (computed in double, stored as
+ *   float next to the texel).  A map whose weights are all 0 has no distribution.
+ * At a lobe vertex x of segment k with k + 1 < iterations, strategies LIGHT and MIS:
+ *   u_sel = pt_nee_rand(~S, k, 0) >> 8 times 2^-24 (the complemented key: dimension 3 of S would be the next segment's dimension 0);
+ *   u_sel < P_env: the sky, direction from u1, u2 as above (u0 is not used); else the light table with u0, u1, u2 as before.
+ *   P_env = ceil(select 2^24) / 2^24; 1 when the light table is empty; 0 when the map has no distribution.
+ *   Triangle pdfs become (1 - P_env) (P_sel / area) r^2 / |cos_y| (in the weights of emitter hits too); p_l(sky) = P_env p_env(w).
+ *   Sky sample: o = x + 0.001 N; rejected unless N.w > 0 and p_l > 0; visible iff no triangle is hit from o along w at any distance;
+ *   adds E (fL' + fB') fS fR W_l, E the sampled texel's value (no second lookup), p_b = max(0, N.w) / pi, W_l from the strategy table.
+ *   A miss after a lobe vertex: W_b from the strategy table with p_l = P_env p_env(D), p_b from that vertex's normal.
+ * PT_NEE_BSDF: W_b = 1, no light samples.  All three strategies have the same expectation; rnds and rays are pt_render's.
+ * While an environment is set (an all-zero one too) pt_render, pt_generate_rays, pt_trace_rays and pt_render_adaptive return
+ * PT_EINVAL naming pt_render_nee; after pt_clear_environment they render what they rendered before.  pt_upload_triangles /
+ * pt_upload_materials keep the map.  Every rank of a tiled frame sets its own copy. */
+typedef struct { float scale, yaw_degrees, select; } pt_environment_params;
+#define PT_ENV_MAX_WIDTH 4096
+#define PT_ENV_MAX_HEIGHT 2048
+void pt_environment_defaults(pt_environment_params* p);              /* scale 1, yaw_degrees 0, select 0.5 */
+/* rgb: w x h x 3 floats, row 0 at the +y pole; p = NULL: the defaults.  Copies the map, builds the tables on the host (works on a
+ * host-only context) and uploads them on a device context.  PT_EINVAL: a NaN, infinite or negative texel, w or h < 1 or above
+ * PT_ENV_MAX_*, select outside [0, 1], a non-finite or negative scale, a non-finite yaw_degrees */
+int pt_set_environment(pt_context* ctx, const float* rgb, int32_t w, int32_t h, const pt_environment_params* p);
+int pt_clear_environment(pt_context* ctx);
+/* host only: the texel of unit direction dir[3] (the mapping above, the code the kernel runs) */
+int pt_env_lookup(int32_t w, int32_t h, float yaw_degrees, const float dir[3], int32_t* row, int32_t* col);
+/* the tables the kernel samples (host data): *w, *h the map's size; row_cdf: min(cap, h) entries; col_cdf and pdf (p_env per texel):
+ * min(cap, w h) entries, row-major; *P_env the effective value (the light table is built if the scene is uploaded, else taken as empty).
+ * Any pointer may be NULL.  PT_EINVAL when no environment is set */
+int pt_debug_environment(pt_context* ctx, int32_t* w, int32_t* h, float* row_cdf, float* col_cdf, float* pdf, int64_t cap, float* P_env);
+
 /* ---- per-pixel variance of the mean luminance (new: opt-in with option "moments"; the reference keeps the mean only) -------
  * With option "moments" = 1 every render path (pt_render in every variant, schedule and node mode, pt_trace_rays,
  * pt_render_adaptive, pt_render_nee, tiled ranks) also folds each sample's squared luminance into colors[].w, float32 in this order:
@@ -348,6 +394,10 @@ int pt_write_pfm(pt_context* ctx, const char* path);
 int pt_write_ppm(pt_context* ctx, const char* path, int32_t which);
 int pt_image_write_pfm(const char* path, const float* rgba, int32_t width, int32_t height);
 int pt_image_write_ppm(const char* path, const float* rgba, int32_t width, int32_t height);
+/* Reads what pt_image_write_pfm writes ("PF" colour or "Pf" grey, either byte order): *width, *height from the header; with rgba_out
+ * != NULL the pixels in the file's row order (the writer's: row 0 = bottom; flip the rows for a map whose row 0 is the +y pole),
+ * float3 @ 16 B with .w = 0; cap = the pixels rgba_out holds (PT_EINVAL when too small).  PT_EIO: unreadable, mis-headed or truncated */
+int pt_image_read_pfm(const char* path, float* rgba_out, int64_t cap, int32_t* width, int32_t* height);
 
 /* ---- plumbing: device memory, streams, options, statistics --------------------------- */
 /* Use caller-owned device buffers (e.g. torch tensors) for colors (16 B/px) and rnds (4 B/px)

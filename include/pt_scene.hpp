@@ -114,6 +114,9 @@ public:
         camera = Camera(globals);
         ck(pt_render_nee(ctx, &camera, globals.iterations, nsamples, strategy));
     }
+    // a lat-long map lighting render_nee (pt_set_environment; rgb: w x h x 3 floats, row 0 at the +y pole; p = NULL: the defaults)
+    void set_environment(const float* rgb, int w, int h, const pt_environment_params* p = nullptr) { ck(pt_set_environment(ctx, rgb, w, h, p)); }
+    void clear_environment() { ck(pt_clear_environment(ctx)); }
     // guide buffers of the current view (pt_render_aovs) and the a-trous filter over them (pt_denoise; p = NULL: the defaults)
     // (the view of the last render: a new Camera(globals) would move a moving camera once more)
     void render_aovs(int subpixels = 1, int specular_depth = 4) {

@@ -46,6 +46,7 @@ EXPORTS = [
     "pt_generate_rays", "pt_trace_rays", "pt_render", "pt_render_adaptive", "pt_read_sample_counts", "pt_read_tile_state", "pt_adaptive_rounds",
     "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
     "pt_render_nee", "pt_nee_rand", "pt_debug_light_table",
+    "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
     "pt_render_aovs", "pt_read_aovs", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
@@ -106,6 +107,12 @@ def _load():
     sig("pt_render_nee", C.c_int, vp, vp, i32, i32, i32)
     sig("pt_nee_rand", C.c_uint32, C.c_uint32, i32, i32)
     sig("pt_debug_light_table", C.c_int, vp, vp, vp, i64, C.POINTER(i64))
+    sig("pt_environment_defaults", None, vp)
+    sig("pt_set_environment", C.c_int, vp, vp, i32, i32, vp)
+    sig("pt_clear_environment", C.c_int, vp)
+    sig("pt_env_lookup", C.c_int, i32, i32, f32, fp, C.POINTER(i32), C.POINTER(i32))
+    sig("pt_debug_environment", C.c_int, vp, C.POINTER(i32), C.POINTER(i32), vp, vp, vp, i64, fp)
+    sig("pt_image_read_pfm", C.c_int, C.c_char_p, vp, i64, C.POINTER(i32), C.POINTER(i32))
     sig("pt_read_variance", C.c_int, vp, vp, i64)
     sig("pt_device_variance", vp, vp)
     sig("pt_denoise_variance_defaults", None, vp)
@@ -236,6 +243,30 @@ def nee_rand(state, segment, dim):
     return int(LIB.pt_nee_rand(int(state) & 0xffffffff, int(segment), int(dim)))
 
 
+class EnvironmentParams(C.Structure):
+    """pt_environment_params (include/pt_api.h)."""
+    _fields_ = [("scale", C.c_float), ("yaw_degrees", C.c_float), ("select", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def environment_defaults():
+    """pt_environment_defaults as a dict: scale, yaw_degrees, select."""
+    p = EnvironmentParams()
+    LIB.pt_environment_defaults(C.byref(p))
+    return p.as_dict()
+
+
+def env_lookup(w, h, yaw_degrees, direction):
+    """pt_env_lookup: (row, col) of the texel a unit direction reads in a w x h lat-long map (include/pt_api.h pins the mapping)."""
+    row, col = C.c_int32(), C.c_int32()
+    rc = LIB.pt_env_lookup(int(w), int(h), float(yaw_degrees), _f3(direction), C.byref(row), C.byref(col))
+    if rc != PT_OK:
+        raise PtError(rc, (LIB.pt_last_error(None) or b"").decode())
+    return row.value, col.value
+
+
 class DenoiseParams(C.Structure):
     """pt_denoise_params (include/pt_api.h)."""
     _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
@@ -321,6 +352,20 @@ def write_pfm(path, rgba, width, height):
     rc = LIB.pt_image_write_pfm(os.fsencode(path), _ptr(rgba), width, height)
     if rc != PT_OK:
         raise PtError(rc, "cannot write %s" % path)
+
+
+def read_pfm(path):
+    """pt_image_read_pfm: (height, width, 4) float32 in the file's row order -- row 0 is the bottom of an image write_pfm wrote; a
+    lat-long map for Scene.set_environment wants its top row first: read_pfm(path)[::-1, :, :3]."""
+    w, h = C.c_int32(), C.c_int32()
+    rc = LIB.pt_image_read_pfm(os.fsencode(path), None, 0, C.byref(w), C.byref(h))
+    if rc != PT_OK:
+        raise PtError(rc, "cannot read %s" % path)
+    out = np.empty((h.value, w.value, 4), dtype=np.float32)
+    rc = LIB.pt_image_read_pfm(os.fsencode(path), _ptr(out), w.value * h.value, C.byref(w), C.byref(h))
+    if rc != PT_OK:
+        raise PtError(rc, "cannot read %s" % path)
+    return out
 
 
 def write_ppm(path, rgba, width, height):
@@ -490,6 +535,34 @@ class Scene:
         cdf = np.zeros(n.value, dtype=np.float32)
         self._ck(LIB.pt_debug_light_table(self._h, _ptr(tri), _ptr(cdf), n.value, C.byref(n)))
         return tri, cdf
+
+    # -- environment lighting for render_nee (include/pt_api.h pins the map, its distribution and the estimator)
+    def set_environment(self, rgb, **params):
+        """pt_set_environment: rgb (h, w, 3) float, row 0 at the +y pole; params override pt_environment_defaults (scale, yaw_degrees,
+        select).  While it is set only render_nee renders."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("rgb must have shape (h, w, 3)")
+        p = EnvironmentParams(**environment_defaults())
+        for k, v in params.items():
+            if k not in p.as_dict():
+                raise TypeError("unknown environment parameter %r" % k)
+            setattr(p, k, v)
+        self._ck(LIB.pt_set_environment(self._h, _ptr(rgb), rgb.shape[1], rgb.shape[0], C.byref(p)))
+
+    def clear_environment(self):
+        self._ck(LIB.pt_clear_environment(self._h))
+
+    def debug_environment(self):
+        """The tables render_nee samples: {"row_cdf" (h,), "col_cdf" (h, w), "pdf" (h, w): p_env per texel, "P_env": the effective
+        probability of choosing the sky at a lobe vertex}."""
+        w, h, pe = C.c_int32(), C.c_int32(), C.c_float()
+        self._ck(LIB.pt_debug_environment(self._h, C.byref(w), C.byref(h), None, None, None, 0, None))
+        row = np.zeros(h.value, dtype=np.float32)
+        col = np.zeros((h.value, w.value), dtype=np.float32)
+        pdf = np.zeros((h.value, w.value), dtype=np.float32)
+        self._ck(LIB.pt_debug_environment(self._h, C.byref(w), C.byref(h), _ptr(row), _ptr(col), _ptr(pdf), col.size, C.byref(pe)))
+        return {"row_cdf": row, "col_cdf": col, "pdf": pdf, "P_env": float(pe.value)}
 
     # -- per-pixel variance of the mean luminance (option "moments"; include/pt_api.h pins both the fold and the read-out)
     def read_variance(self):

@@ -166,6 +166,16 @@ struct pt_context {
     float* d_nee_cdf = nullptr;
     float* d_nee_pdf_area = nullptr;
     bool nee_uploaded = false;         // the device copies hold the current table
+    // the environment of pt_render_nee (pt_set_environment, pt_env.cpp): the map with p_env = P(texel) / Omega(row) in .w, the row
+    // marginal cdf [h] and the per-row column cdfs [h][w]; env_dist: some weight is non-zero.  Device copies made by pt_set_environment.
+    bool env_set = false, env_dist = false;
+    int32_t env_w = 0, env_h = 0;
+    float env_scale = 1.0f, env_yaw = 0.0f, env_select = 0.5f;   // yaw in radians
+    std::vector<float4> env_texels;
+    std::vector<float> env_row_cdf, env_col_cdf;
+    float4* d_env_texels = nullptr;
+    float* d_env_row_cdf = nullptr;
+    float* d_env_col_cdf = nullptr;
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -209,6 +219,8 @@ constexpr size_t kLdsPerCu = 160 * 1024;
 constexpr size_t kLdsSlack = 32 * 100 + 4096 + 1024 + 256;
 
 int fail(pt_context* ctx, int code, const std::string& msg);      // pt_host.cpp: records the text behind pt_last_error
+int light_table_ready(pt_context* ctx);                            // pt_host.cpp: builds the light table of the uploaded scene if it is stale
+float env_select(const pt_context* ctx, bool no_lights);           // pt_env.cpp: the effective P_env
 int host_threads(const pt_context* ctx);                          // threads of the host-side scene path (option build_threads)
 
 #define PT_HIP(ctx, call)                                                                   \

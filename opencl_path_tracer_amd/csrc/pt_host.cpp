@@ -239,6 +239,9 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->d_nee_tri) (void)hipFree(ctx->d_nee_tri);
         if (ctx->d_nee_cdf) (void)hipFree(ctx->d_nee_cdf);
         if (ctx->d_nee_pdf_area) (void)hipFree(ctx->d_nee_pdf_area);
+        if (ctx->d_env_texels) (void)hipFree(ctx->d_env_texels);
+        if (ctx->d_env_row_cdf) (void)hipFree(ctx->d_env_row_cdf);
+        if (ctx->d_env_col_cdf) (void)hipFree(ctx->d_env_col_cdf);
         if (ctx->d_wf_state) (void)hipFree(ctx->d_wf_state);
         if (ctx->d_wf_queues) (void)hipFree(ctx->d_wf_queues);
         if (ctx->d_wf_counters) (void)hipFree(ctx->d_wf_counters);
@@ -772,6 +775,11 @@ static int nee_table(pt_context* ctx) {
     ctx->nee_uploaded = false;
     return PT_OK;
 }
+}  // extern "C"
+namespace ptamd {
+int light_table_ready(pt_context* ctx) { return nee_table(ctx); }     // for pt_env.cpp
+}  // namespace ptamd
+extern "C" {
 int pt_debug_light_table(pt_context* ctx, int32_t* orig_tri, float* cdf, int64_t cap, int64_t* n) {
     if (!ctx) return PT_EINVAL;
     if (!n || cap < 0) return fail(ctx, PT_EINVAL, "pt_debug_light_table: n is NULL or cap < 0");
@@ -826,11 +834,24 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     lt.pdf_area = ctx->d_nee_pdf_area;
     lt.n = (int32_t)ctx->nee_tri.size();
     lt.strategy = strategy;
+    // an environment without a distribution is all zero: the instances without one compute the same frame
+    EnvView env;
+    const bool sky = ctx->env_set && ctx->env_dist;
+    if (sky) {
+        env.texels = ctx->d_env_texels;
+        env.row_cdf = ctx->d_env_row_cdf;
+        env.col_cdf = ctx->d_env_col_cdf;
+        env.w = ctx->env_w;
+        env.h = ctx->env_h;
+        env.scale = ctx->env_scale;
+        env.yaw = ctx->env_yaw;
+        env.p_env = env_select(ctx, lt.n == 0);
+    }
     ctx->render_epoch++;
     note_frame(ctx, p.first_sample, cam);
     EventPair* ep;
     if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-    PT_HIP(ctx, launch_nee(p, lt, ctx->npix, ctx->cu_count, ctx->stream));
+    PT_HIP(ctx, launch_nee(p, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream));
     if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
     ctx->current_sample += nsamples;
     return PT_OK;

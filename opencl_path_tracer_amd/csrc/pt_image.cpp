@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pt_internal.hpp"
@@ -34,6 +35,58 @@ int pt_image_write_pfm(const char* path, const float* rgba, int32_t width, int32
         ok = std::fwrite(row.data(), sizeof(float), row.size(), f) == row.size();
     }
     ok = (std::fclose(f) == 0) && ok;
+    return ok ? PT_OK : PT_EIO;
+}
+
+int pt_image_read_pfm(const char* path, float* rgba_out, int64_t cap, int32_t* width, int32_t* height) {
+    if (!path || !width || !height || cap < 0) return PT_EINVAL;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return PT_EIO;
+    // header: "PF" | "Pf", width height, scale (negative: little-endian), each followed by white space; one byte of it (or "\r\n")
+    // before the data
+    char magic[3] = {0, 0, 0};
+    int w = 0, h = 0;
+    double scale = 0.0;
+    const bool head = std::fscanf(f, "%2s %d %d %lf", magic, &w, &h, &scale) == 4 && magic[0] == 'P' && (magic[1] == 'F' || magic[1] == 'f') &&
+                      w >= 1 && h >= 1 && w <= 65535 && h <= 65535 && scale != 0.0 && std::isfinite(scale);
+    int sep = head ? std::fgetc(f) : EOF;
+    if (sep == '\r') {                                                  // a CRLF header: the separator is the pair
+        const int lf = std::fgetc(f);
+        if (lf == '\n') sep = lf;
+        else if (lf != EOF) std::ungetc(lf, f);
+    }
+    if (!head || !(sep == '\n' || sep == ' ' || sep == '\r' || sep == '\t')) {
+        std::fclose(f);
+        return PT_EIO;
+    }
+    *width = w;
+    *height = h;
+    if (!rgba_out) {
+        std::fclose(f);
+        return PT_OK;
+    }
+    if (cap < (int64_t)w * h) {
+        std::fclose(f);
+        return PT_EINVAL;
+    }
+    const int ch = magic[1] == 'F' ? 3 : 1;
+    std::vector<float> row((size_t)w * ch);
+    bool ok = true;
+    for (int32_t y = 0; y < h && ok; ++y) {
+        ok = std::fread(row.data(), sizeof(float), row.size(), f) == row.size();
+        if (ok && scale > 0.0) {                                       // big-endian file
+            unsigned char* b = reinterpret_cast<unsigned char*>(row.data());
+            for (size_t i = 0; i < row.size(); ++i) { std::swap(b[4 * i], b[4 * i + 3]); std::swap(b[4 * i + 1], b[4 * i + 2]); }
+        }
+        float* dst = rgba_out + (size_t)y * w * 4;
+        for (int32_t x = 0; x < w && ok; ++x) {
+            dst[4 * x] = row[(size_t)ch * x];
+            dst[4 * x + 1] = row[(size_t)ch * x + (ch == 3 ? 1 : 0)];
+            dst[4 * x + 2] = row[(size_t)ch * x + (ch == 3 ? 2 : 0)];
+            dst[4 * x + 3] = 0.0f;
+        }
+    }
+    std::fclose(f);
     return ok ? PT_OK : PT_EIO;
 }
 

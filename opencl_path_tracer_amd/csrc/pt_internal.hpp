@@ -355,7 +355,27 @@ struct NeeTable {
     int32_t n;                   // 0: no lights (every strategy is PT_NEE_BSDF)
     int32_t strategy;
 };
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, int64_t npix, int cu_count, hipStream_t stream);
+// the environment of pt_render_nee (pt_set_environment; pinned in include/pt_api.h)
+struct EnvView {
+    const float4* texels;        // [h][w] {r, g, b, p_env = P(texel) / Omega(row)}
+    const float* row_cdf;        // [h]
+    const float* col_cdf;        // [h][w]
+    int32_t w, h;
+    float scale, yaw;            // yaw in radians
+    float p_env;                 // the effective P_env (a multiple of 2^-24)
+};
+// env == nullptr: the instances without an environment
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream);
+// the texel of unit direction (x, y, z): k_nee and pt_env_lookup
+__host__ __device__ __forceinline__ void env_texel(int32_t w, int32_t h, float yaw, float x, float y, float z, int32_t* row, int32_t* col) {
+    const float theta = acosf(fminf(fmaxf(y, -1.0f), 1.0f));
+    const float phi = atan2f(z, x) - yaw;
+    const int r = (int)floorf(theta / 3.14159265358979323846f * (float)h);
+    const float turn = phi / 6.28318530717958647692f;
+    const int c = (int)floorf((turn - floorf(turn)) * (float)w);
+    *row = r < h - 1 ? (r < 0 ? 0 : r) : h - 1;
+    *col = c < w - 1 ? (c < 0 ? 0 : c) : w - 1;
+}
 // the light samples' counter-based hash of (LCG state at the start of the sample, segment, dimension): k_nee and pt_nee_rand
 __host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
     x ^= x >> 16;

@@ -342,6 +342,7 @@ int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
     PT_NEED_DEVICE(ctx);
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
+    if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_generate_rays: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     fill_params(ctx, cam, &p);
@@ -354,6 +355,7 @@ int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
     if (iterations < 0 || current_sample < 0) return fail(ctx, PT_EINVAL, "iterations/current_sample must be >= 0");
+    if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_trace_rays: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
@@ -551,6 +553,7 @@ int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
     if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "iterations/nsamples must be >= 0");
+    if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_render: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
     if (nsamples == 0) return PT_OK;
     PT_HIP(ctx, hipSetDevice(ctx->device));
@@ -605,6 +608,7 @@ int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations
     PT_NEED_DEVICE(ctx);
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
+    if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_render_adaptive: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
     if (ctx->variant != 0) return fail(ctx, PT_EINVAL, "pt_render_adaptive: the megakernel (variant 0) only");
     if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_render_adaptive: contexts of one rank (world == 1) only");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");

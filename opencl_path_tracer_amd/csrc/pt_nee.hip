@@ -5,6 +5,9 @@
 //           point.  The light sample's three numbers come from a counter-based hash (nee_rand, pt_internal.hpp) of (LCG state at
 //           the start of the sample, segment, dimension), never from the LCG, so the BSDF path draws exactly what pt_render draws
 //           and rnds / rays come out the same in every strategy.
+//   k_nee_env  the same frame under an environment map (pt_set_environment): a miss adds the sky, and a lobe vertex samples either
+//           the sky or a triangle light, chosen by one more hash value.  One body, nee_frame<MODE, BLOCK, ENV>; every statement that
+//           touches the environment sits under `if constexpr (ENV)`, so k_nee is the code it was.
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -25,8 +28,16 @@ PT_DEV int shadow_hit(const SceneView& sv, f3 o, f3 w, float limit, const LaneSt
     return tr.best;
 }
 
+// the environment a hook carries: nothing without one
+template <bool ENV>
+struct EnvSlot {};
+template <>
+struct EnvSlot<true> {
+    EnvView v;
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
-template <int MODE>
+template <int MODE, bool ENV = false>
 struct NeeHook {
     static constexpr bool active = true;
     NeeTable lt;
@@ -39,11 +50,13 @@ struct NeeHook {
     int k = 0;                     // the segment
     bool after_lobe = false;       // the previous vertex was a lobe vertex (its flipped normal: Nprev)
     f3 Nprev = mk(0.f, 0.f, 0.f);
+    EnvSlot<ENV> env;
 
     // the weight of an emitter hit's emission (at distance t, cosine inten, along rD)
     PT_DEV float emitter_weight(int ti, float t, float inten, f3 rD) const {
         if (!nee || !after_lobe) return 1.0f;
-        const float pa = lt.pdf_area[ti];
+        float pa = lt.pdf_area[ti];
+        if constexpr (ENV) pa *= 1.0f - env.v.p_env;                 // the light table is chosen with probability 1 - P_env
         if (!(pa > 0.0f && inten > 0.0f)) return 1.0f;
         if (!mis) return 0.0f;
         const float pb = max0(dot3(Nprev, rD)) * kInvPi;
@@ -53,8 +66,14 @@ struct NeeHook {
     }
 
     // a point y on a light, the bracket an emitter hit at y on segment k + 1 would add, for the lobe vertex hp (normal N)
+    // (TWIN: the triangle branch and the tail of light_sample_env below restate this body, so that k_nee's code stays what it was;
+    // a change to one belongs in the other)
     PT_DEV void light_sample(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp) {
         if (!nee || k + 1 >= p.iterations) return;
+        if constexpr (ENV) {
+            light_sample_env(st, p, m, type, N, hp);
+            return;
+        }
         const float u0 = nee_unit(nee_rand(key, k, 0)), u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
         int lo = 0, hi = lt.n - 1;        // first light with cdf > u0
         while (lo < hi) {
@@ -94,19 +113,135 @@ struct NeeHook {
         if (wl < __builtin_inff()) st.setC(madd(e, cosy * wl, st.C()));
     }
 
+    // ENV: the sky with probability P_env (u_sel, keyed with ~key), else a light of the table with its pdf times 1 - P_env.  Both
+    // branches only produce the shadow ray and what it would add; the traversal and the weighting are shared, so a wave that holds
+    // both kinds of sample runs one traversal.  (TWIN: the triangle branch and the tail restate light_sample above.)
+    PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp) {
+        const EnvView& ev = env.v;
+        const float u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
+        const f3 o = madd(N, 0.001f, hp);
+        f3 w, e;
+        float limit, pl, g;            // the search's cut, p_l, the emitter's cosine (1 for the sky)
+        int want;                      // what the shadow ray must return
+        if (nee_unit(nee_rand(~key, k, 0)) < ev.p_env) {
+            int lo = 0, hi = ev.h - 1;        // first row with cdf > u1, then first column of that row with cdf > u2
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (ev.row_cdf[mid] > u1) hi = mid;
+                else lo = mid + 1;
+            }
+            const int row = lo;
+            const float rb = row ? ev.row_cdf[row - 1] : 0.0f;
+            const float t1 = (u1 - rb) / (ev.row_cdf[row] - rb);
+            const float* __restrict__ cc = ev.col_cdf + (size_t)row * ev.w;
+            lo = 0;
+            hi = ev.w - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (cc[mid] > u2) hi = mid;
+                else lo = mid + 1;
+            }
+            const int col = lo;
+            const float cb = col ? cc[col - 1] : 0.0f;
+            const float t2 = (u2 - cb) / (cc[col] - cb);
+            const float4 tx = ev.texels[(size_t)row * ev.w + col];
+            const float c0 = cosf(3.14159265358979323846f * (float)row / (float)ev.h), c1 = cosf(3.14159265358979323846f * (float)(row + 1) / (float)ev.h);
+            const float ct = c0 - t1 * (c0 - c1);
+            const float sn = __builtin_sqrtf(max0(fmaf_(-ct, ct, 1.0f)));
+            const float phi = fmaf_(6.28318530717958647692f, ((float)col + t2) / (float)ev.w, ev.yaw);
+            w = mk(sn * cosf(phi), ct, sn * sinf(phi));
+            e = mk(tx.x, tx.y, tx.z) * ev.scale;
+            pl = ev.p_env * tx.w;
+            g = 1.0f;
+            limit = __builtin_inff();
+            want = -1;
+        } else {
+            if (lt.n <= 0) return;            // (P_env is 1 then: not reached)
+            const float u0 = nee_unit(nee_rand(key, k, 0));
+            int lo = 0, hi = lt.n - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (lt.cdf[mid] > u0) hi = mid;
+                else lo = mid + 1;
+            }
+            const int li = lt.tri[lo];
+            const float4 a = p.tris[li * 3], b = p.tris[li * 3 + 1], cc = p.tris[li * 3 + 2];
+            const f3 v1 = mk(a.x, a.y, a.z), v2 = mk(a.w, b.x, b.y), v3 = mk(b.z, b.w, cc.x), Ny = mk(cc.y, cc.z, cc.w);
+            const float su = __builtin_sqrtf(u1);
+            const f3 y = madd(v3 - v1, su * (1.0f - u2), madd(v2 - v1, u2 * su, v1));
+            const f3 d = y - o;
+            const float r2 = dot3(d, d);
+            const float r = __builtin_sqrtf(r2);
+            w = mk(d.x / r, d.y / r, d.z / r);
+            g = __builtin_fabsf(dot3(w, Ny));
+            pl = (lt.pdf_area[li] * (1.0f - ev.p_env)) * r2 / g;       // g = 0: inf or NaN, rejected below
+            e = ldf3(p.mats[p.meta[li].mati].emission);
+            limit = r * 1.0001f;
+            want = li;
+        }
+        const float cosx = dot3(N, w);
+        if (!(cosx > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
+        if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
+        const float pb = cosx * kInvPi;
+        const float q = pb / pl;
+        const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
+        f3 fl = st.L(), fb = st.B();
+        if (type == 0) {           // as in light_sample
+            fl = fl * (ldf3(m->kd) * cosx);
+            float pw = 1.0f;
+            if (!m->_pad) {
+                const f3 view = normalize3(eye - hp);
+                const f3 halfway = normalize3(view + w);
+                pw = spec_pow<false>(max0(dot3(N, halfway)), m->shininess);
+            }
+            fb = fb * (ldf3(m->ks) * pw);
+        }
+        e = ((e * (fl + fb)) * st.S()) * st.R();
+        if (wl < __builtin_inff()) st.setC(madd(e, g * wl, st.C()));
+    }
+
+    // ENV: a miss on segment kk along rD (the path ends there)
+    PT_DEV void miss(PathRegs& st, f3 rD, int kk) const {
+        const EnvView& ev = env.v;
+        int row, col;
+        env_texel(ev.w, ev.h, ev.yaw, rD.x, rD.y, rD.z, &row, &col);
+        const float4 tx = ev.texels[(size_t)row * ev.w + col];
+        const f3 e = mk(tx.x, tx.y, tx.z) * ev.scale;
+        if (kk == 0) {             // prog.cl:369: the sky itself
+            st.setC(st.C() + e);
+            return;
+        }
+        float wb = 1.0f;
+        const float pl = ev.p_env * tx.w;
+        if (nee && after_lobe && pl > 0.0f) {
+            if (mis) {
+                const float pb = max0(dot3(Nprev, rD)) * kInvPi;
+                const float rr = pl / pb;      // pb = 0: rr = inf, weight 0
+                wb = 1.0f / fmaf_(rr, rr, 1.0f);
+            } else {
+                wb = 0.0f;
+            }
+        }
+        st.setC(madd(((e * (st.L() + st.B())) * st.S()) * st.R(), wb, st.C()));      // prog.cl:371-373
+    }
+
     PT_DEV void end_vertex(bool lobe, f3 N) {
         after_lobe = lobe;
         Nprev = N;
     }
 };
 
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee(RenderParams p, NeeTable lt, long long npix) {
+template <int MODE, int BLOCK, bool ENV>
+PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    if constexpr (ENV) {
+        hook.env = env;
+        hook.nee = lt.strategy != 0;       // the sky is a light (the host launches this instance only for a map with a distribution)
+    }
     const int camX = (int)p.cam.XM;
     for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < npix; i += (long long)gridDim.x * BLOCK) {
         const int lrow = (int)(i / p.width), x = (int)(i % p.width);
@@ -134,7 +269,10 @@ __global__ void __launch_bounds__(BLOCK) k_nee(RenderParams p, NeeTable lt, long
             for (int k = 0; k < p.iterations; ++k) {
                 float t;
                 const int ti = closest_hit<MODE, false>(sv, rP, rD, stk, &t, &wc);
-                if (ti < 0) break;                 // black environment, prog.cl:367-376
+                if (ti < 0) {                      // prog.cl:367-376: black without an environment
+                    if constexpr (ENV) hook.miss(st, rD, k);
+                    break;
+                }
                 hook.k = k;
                 shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, t, &hook);
             }
@@ -149,7 +287,17 @@ __global__ void __launch_bounds__(BLOCK) k_nee(RenderParams p, NeeTable lt, long
     }
 }
 
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, int64_t npix, int cu_count, hipStream_t stream) {
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee(RenderParams p, NeeTable lt, long long npix) {
+    nee_frame<MODE, BLOCK, false>(p, lt, EnvSlot<false>{}, npix);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env(RenderParams p, NeeTable lt, EnvView env, long long npix) {
+    nee_frame<MODE, BLOCK, true>(p, lt, EnvSlot<true>{env}, npix);
+}
+
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream) {
+    if (env) return launch_lanes([](auto s) { return k_nee_env<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, (long long)npix);
     return launch_lanes([](auto s) { return k_nee<s.mode, s.block>; }, p, npix, cu_count, stream, lt, (long long)npix);
 }
 

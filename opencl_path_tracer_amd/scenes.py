@@ -109,6 +109,24 @@ def cornell_box(segments=32, rings=16):
     return spec
 
 
+def sun_and_sky(width=64, height=32, sun_dir=(0.3, 0.8, 0.5), sun_radius_deg=5.0, sun_radiance=(400.0, 360.0, 300.0),
+                zenith=(0.25, 0.45, 0.9), horizon=(0.8, 0.85, 0.9), ground=(0.1, 0.09, 0.08)):
+    """A procedural lat-long map (height, width, 3) float32 for Scene.set_environment, row 0 at the +y pole: a sky that fades from
+    `zenith` to `horizon`, a dim `ground` below it, and a sun disc of angular radius sun_radius_deg and radiance sun_radiance around
+    sun_dir (texel centres inside the disc; at least the one nearest to sun_dir)."""
+    th = (np.arange(height) + 0.5) * np.pi / height
+    ph = (np.arange(width) + 0.5) * 2.0 * np.pi / width
+    d = np.stack([np.outer(np.sin(th), np.cos(ph)), np.outer(np.cos(th), np.ones(width)), np.outer(np.sin(th), np.sin(ph))], axis=-1)
+    up = np.clip(d[..., 1], 0.0, 1.0)[..., None]
+    img = np.where(d[..., 1:2] >= 0.0, np.asarray(horizon) * (1.0 - up) + np.asarray(zenith) * up, np.asarray(ground))
+    s = np.asarray(sun_dir, dtype=np.float64)
+    cosang = d @ (s / np.linalg.norm(s))
+    disc = cosang >= np.cos(np.radians(sun_radius_deg))
+    disc.flat[int(np.argmax(cosang))] = True
+    img[disc] = np.asarray(sun_radiance)
+    return img.astype(np.float32)
+
+
 def _lcg_floats(n, seed=1):
     """minstd (48271) stream mapped to [0,1): deterministic displacement noise."""
     out = np.empty(n, dtype=np.float64)
