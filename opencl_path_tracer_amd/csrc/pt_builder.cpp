@@ -1121,6 +1121,7 @@ static int build_on_device(pt_context* ctx, bool* done) {
     clk.lap("node placement + 4-wide nodes");
     if (rc != PT_OK) { drop(); return rc; }
     if (retopped) ctx->bvh_depth = ctx->interior_depth + 1;
+    ctx->shaderec_dirty = true;
     if (ctx->d_tris) (void)hipFree(ctx->d_tris);
     if (ctx->d_meta) (void)hipFree(ctx->d_meta);
     ctx->d_tris = r.d_tris;
@@ -1177,6 +1178,7 @@ int pt_upload_triangles(pt_context* ctx) {
         if ((rc = upload_vec(ctx, &ctx->d_nodes, ctx->nodes.data(), sizeof(Node64) * ctx->nodes.size())) != PT_OK) return rc;
         if ((rc = upload_vec(ctx, &ctx->d_nodes4, ctx->nodes4.data(), sizeof(Node4q) * ctx->nodes4.size())) != PT_OK) return rc;
         if ((rc = alloc_stack_overflow(ctx)) != PT_OK) return rc;
+        ctx->shaderec_dirty = true;
         if ((rc = upload_vec(ctx, &ctx->d_tris, ctx->packets.data(), sizeof(TriPacket) * ctx->packets.size())) != PT_OK) return rc;
         if ((rc = upload_vec(ctx, &ctx->d_meta, ctx->meta.data(), sizeof(TriMeta) * ctx->meta.size())) != PT_OK) return rc;
         clk.lap("device allocations + copies");

@@ -81,6 +81,12 @@ struct pt_context {
     float4* d_tris = nullptr;
     TriMeta* d_meta = nullptr;
     pt_material* d_mats = nullptr;
+    // per-triangle shading records (ShadeRec): built from d_tris, d_meta and d_mats at the next render launch that reads them after
+    // any of the three was written (every writer sets shaderec_dirty; ensure_shade_records, pt_launch.cpp)
+    ShadeRec* d_shaderec = nullptr;
+    size_t shaderec_cap = 0;           // records d_shaderec has room for
+    bool shaderec_dirty = true;
+    int32_t mats_on_device = 0;        // materials d_mats holds (ctx->mats can run ahead of it until the next pt_upload_materials)
     int32_t* d_rnds = nullptr;
     float4* d_colors = nullptr;
     pt_ray* d_rays = nullptr;
@@ -359,6 +365,7 @@ int plan_node_placement(pt_context* ctx, const float4* d_bvh2 = nullptr, bool* w
 int alloc_stack_overflow(pt_context* ctx);
 int seed_upload(pt_context* ctx, const int32_t* global_seeds);
 void fill_params(const pt_context* ctx, const pt_camera* cam, RenderParams* p);
+int ensure_shade_records(pt_context* ctx, RenderParams* p);
 int check_ready(pt_context* ctx, const pt_camera* cam);
 int time_begin(pt_context* ctx, EventPair** ep);
 int time_end(pt_context* ctx, EventPair* ep);

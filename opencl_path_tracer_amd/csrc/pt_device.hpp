@@ -988,12 +988,39 @@ PT_DEV int closest_hit(const SceneView& sv, f3 P, f3 D, const LaneStack<typename
 
 // ---------------------------------------------------------------------------- BSDF sampling
 // prog.cl:186-218
+// The tangent frame of the cosine lobe around N (prog.cl:205-212): Z, X.  A pure function of N, in two steps so that the inline
+// path of diffuse_direction can take ONE wave-uniform branch for this root and its own two; tangent_frame() is the whole of it.
+PT_DEV float frame_l2(f3 N, bool* yaxis) {
+    const float E = 0.001f;
+    *yaxis = __builtin_fabsf(N.x) <= E && __builtin_fabsf(N.z) <= E;
+    const float other = *yaxis ? N.y : N.x;
+    return fmaf_(N.z, N.z, other * other);
+}
+PT_DEV void frame_from_rl(f3 N, bool yaxis, float rl, f3* Z, f3* X) {      // rl = 1 / sqrt(frame_l2(N)), IEEE
+    *Z = yaxis ? mk(0.0f, -N.z * rl, N.y * rl) : mk(-N.z * rl, 0.0f, N.x * rl);
+    *X = cross3(N, *Z);
+}
+PT_DEV void tangent_frame(f3 N, f3* Z, f3* X) {
+    bool yaxis;
+    const float l2 = frame_l2(N, &yaxis);
+    frame_from_rl(N, yaxis, rsqrt_rn(l2), Z, X);
+}
+// prog.cl:213-218 up to the normalisation (shade_hit does it): the direction in the frame (Z, X) of N
+template <bool SK>
+PT_DEV f3 lobe_direction(f3 N, f3 Z, f3 X, float r, float z, float rnd2) {      // r = sqrt(rnd1), z = sqrt(1 - rnd1), IEEE
+    const float theta = (float)(6.283185307179586 * (double)rnd2);
+    float sn, cs;
+    spec_sincos<SK>(theta, &sn, &cs);
+    const float x = r * cs, y = r * sn;
+    f3 d = X * x;
+    d = madd(N, z, d);
+    d = madd(Z, y, d);
+    return d;
+}
 template <bool SK>
 PT_DEV f3 diffuse_direction(f3 N, float rnd1, float rnd2) {       // prog.cl:205-218 up to the normalisation (shade_hit does it)
-    const float E = 0.001f;
-    const bool yaxis = __builtin_fabsf(N.x) <= E && __builtin_fabsf(N.z) <= E;
-    const float other = yaxis ? N.y : N.x;
-    const float l2 = fmaf_(N.z, N.z, other * other);
+    bool yaxis;
+    const float l2 = frame_l2(N, &yaxis);
     // the three roots and the divide below are IEEE; one uniform branch picks the cores for all of them or the compiler's
     // expansions.  sqrt_core needs rnd1 >= 2^-96 and 1 - rnd1 >= 2^-96; the latter holds for every float rnd1 < 1 (1 - rnd1
     // is then at least 2^-24)
@@ -1007,16 +1034,24 @@ PT_DEV f3 diffuse_direction(f3 N, float rnd1, float rnd2) {       // prog.cl:205
         r = __builtin_sqrtf(rnd1);
         z = __builtin_sqrtf(1.0f - rnd1);
     }
-    const f3 Z = yaxis ? mk(0.0f, -N.z * rl, N.y * rl) : mk(-N.z * rl, 0.0f, N.x * rl);
-    const f3 X = cross3(N, Z);
-    const float theta = (float)(6.283185307179586 * (double)rnd2);
-    float sn, cs;
-    spec_sincos<SK>(theta, &sn, &cs);
-    const float x = r * cs, y = r * sn;
-    f3 d = X * x;
-    d = madd(N, z, d);
-    d = madd(Z, y, d);
-    return d;
+    f3 Z, X;
+    frame_from_rl(N, yaxis, rl, &Z, &X);
+    return lobe_direction<SK>(N, Z, X, r, z, rnd2);
+}
+// the same with the frame of N read from the triangle's shading record (ShadeRec::frame of the orientation the flip chose):
+// what is left of the wave-level window are the rnd1 conditions
+template <bool SK>
+PT_DEV f3 diffuse_direction_rec(f3 N, const float4* frame, float rnd1, float rnd2) {
+    const float4 fa = frame[0], fb = frame[1];
+    float r, z;
+    if (wave_all(rnd1 >= kSqrtWindowLo && rnd1 < 1.0f)) {
+        r = sqrt_core(rnd1);
+        z = sqrt_core(1.0f - rnd1);
+    } else {
+        r = __builtin_sqrtf(rnd1);
+        z = __builtin_sqrtf(1.0f - rnd1);
+    }
+    return lobe_direction<SK>(N, mk(fa.x, fa.y, fa.z), mk(fa.w, fb.x, fb.y), r, z, rnd2);
 }
 
 // prog.cl:219-222
@@ -1061,16 +1096,39 @@ struct NoShadeHook {
 
 // one iteration body of prog.cl:317-366 for a ray that hit packed triangle `ti` at `t`
 // (SK: double-precision constants pinned to scalar registers, see KC)
-template <bool SK, class ST, class HOOK = NoShadeHook>
+// REC: what is constant per triangle comes from its shading record p.shaderec[ti] (ShadeRec, pt_internal.hpp) instead of being
+// gathered and recomputed at every hit.  First round trip: normal, type, mati, kd -- without the record the type waits for
+// meta[ti] and then the material.  Second, once the flip is known: a lobe hit reads the frame of its orientation, every other
+// case the material fields it needs through mati; a diffuse hit on a material without a specular lobe never touches the material.
+template <bool SK, bool REC = false, class ST, class HOOK = NoShadeHook>
 PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const RenderParams& p, const float4* tris, const TriMeta* meta, int ti, float t,
                       HOOK* hook = nullptr) {
-    const float4 c = tris[ti * 3 + 2];
-    f3 N = mk(c.y, c.z, c.w);
+    f3 N, kd;
+    int type;
+    bool plain;                                                             // type 0: ks is +0 and the pow is skipped
+    const pt_material* __restrict__ m;
+    const float4* rec = nullptr;
+    if constexpr (REC) {
+        rec = p.shaderec + (size_t)ti * (sizeof(ShadeRec) / sizeof(float4));
+        const float4 a = rec[0], b = rec[1];
+        N = mk(a.x, a.y, a.z);
+        type = __float_as_int(a.w);
+        kd = mk(b.x, b.y, b.z);
+        const unsigned mi = (unsigned)__float_as_int(b.w);
+        plain = (mi & kShadeRecPlain) != 0;
+        m = &p.mats[mi & ~kShadeRecPlain];
+    } else {
+        const float4 c = tris[ti * 3 + 2];
+        N = mk(c.y, c.z, c.w);
+        m = &p.mats[meta[ti].mati];
+        type = m->type;
+        kd = mk(0.0f, 0.0f, 0.0f);      // (read from the material where it is needed)
+        plain = false;
+    }
     const f3 hp = madd(rD, t, rP);
-    const pt_material* __restrict__ m = &p.mats[meta[ti].mati];
-    const int type = m->type;
-    if (p.iterations == 1) st.setC(ldf3(m->kd) + ldf3(m->emission));        // prog.cl:323-325
-    if (dot3(rD, N) > 0.0f) N = -N;                                         // prog.cl:326-328
+    if (p.iterations == 1) st.setC((REC ? kd : ldf3(m->kd)) + ldf3(m->emission));        // prog.cl:323-325
+    const bool flip = dot3(rD, N) > 0.0f;
+    if (flip) N = -N;                                                       // prog.cl:326-328
     // Every material that continues the path ends the same way: normalise the new direction, step off the surface
     // along +-N.  The two sampling branches below only produce the direction BEFORE normalisation and the side; the
     // tail is shared, so a wave that holds both kinds of hit runs one normalisation (IEEE sqrt + divide), not two.
@@ -1088,7 +1146,8 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
             hook->light_sample(st, p, m, type, N, hp);                      // before the LCG draws and this hit's emission
         }
         const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
-        dnew = diffuse_direction<SK>(N, rnd1, rnd2);
+        if constexpr (REC) dnew = diffuse_direction_rec<SK>(N, rec + (flip ? 4 : 2), rnd1, rnd2);
+        else dnew = diffuse_direction<SK>(N, rnd1, rnd2);
     } else if (spec) {
         // mirror (prog.cl:341-345) and dielectric (prog.cl:346-357, 228-245) share the Fresnel
         // term and the mirror direction; the dielectric may pick the refracted direction instead.
@@ -1125,18 +1184,23 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     }
     if (type == 0) {
         const float idiff = max0(dot3(rD, N));
-        st.setL(st.L() * (ldf3(m->kd) * idiff));
+        st.setL(st.L() * ((REC ? kd : ldf3(m->kd)) * idiff));
         // m->_pad = 1: ks is exactly 0 and shininess is finite >= 0, so ks * pow(...) is +-0 whatever the
         // (finite) power is -- skip the halfway vector (two normalisations) and the double-precision pow
         // (set by pt_upload_materials)
-        float pw = 1.0f;
-        if (!m->_pad) {
-            const f3 view = normalize3(ldf3(p.cam.eye) - hp);
-            const f3 halfway = normalize3(view + rD);
-            const float ispec = max0(dot3(N, halfway));
-            pw = spec_pow<SK>(ispec, m->shininess);
+        // (REC and `plain`: ks is +0 in every component, and ks * 1.0f is ks)
+        if (REC && plain) {
+            st.setB(st.B() * mk(0.0f, 0.0f, 0.0f));
+        } else {
+            float pw = 1.0f;
+            if (!m->_pad) {
+                const f3 view = normalize3(ldf3(p.cam.eye) - hp);
+                const f3 halfway = normalize3(view + rD);
+                const float ispec = max0(dot3(N, halfway));
+                pw = spec_pow<SK>(ispec, m->shininess);
+            }
+            st.setB(st.B() * (ldf3(m->ks) * pw));
         }
-        st.setB(st.B() * (ldf3(m->ks) * pw));
     } else if (type == 3) {
         const f3 e = ((ldf3(m->emission) * (st.L() + st.B())) * st.S()) * st.R();
         if constexpr (HOOK::active) st.setC(madd(e * wb, inten, st.C()));

@@ -219,6 +219,7 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->d_tris) (void)hipFree(ctx->d_tris);
         if (ctx->d_meta) (void)hipFree(ctx->d_meta);
         if (ctx->d_mats) (void)hipFree(ctx->d_mats);
+        if (ctx->d_shaderec) (void)hipFree(ctx->d_shaderec);
         if (ctx->d_rays) (void)hipFree(ctx->d_rays);
         if (ctx->d_ldr) (void)hipFree(ctx->d_ldr);
         if (ctx->d_stats) (void)hipFree(ctx->d_stats);
@@ -298,8 +299,10 @@ int pt_upload_materials(pt_context* ctx) {
         std::vector<pt_material> dm(ctx->mats);
         for (pt_material& m : dm)
             m._pad = (m.ks.s[0] == 0.0f && m.ks.s[1] == 0.0f && m.ks.s[2] == 0.0f && std::isfinite(m.shininess) && m.shininess >= 0.0f) ? 1 : 0;
+        ctx->shaderec_dirty = true;
         int rc = upload_vec(ctx, &ctx->d_mats, dm.data(), sizeof(pt_material) * dm.size());
         if (rc != PT_OK) return rc;
+        ctx->mats_on_device = (int32_t)dm.size();
     }
     ctx->mats_uploaded = true;
     return PT_OK;

@@ -42,6 +42,28 @@ struct TriMeta {
     int32_t mati;
 };
 
+// per packed triangle: what shade_hit needs of the triangle and of its material, 96 B = 6 x float4 (pt_shaderec.hip builds it on the
+// device after every upload of triangles or materials; shade_hit<SK, REC = true> reads it).  All of it is constant between uploads:
+//   { N.xyz, bits(type) }          the geometric normal as packed (packet floats 9..11), the material's type
+//   { kd.xyz, bits(mati | plain) } the material's kd; its index, with kShadeRecPlain set when a diffuse hit needs nothing else of
+//                                  the material: _pad is set (pt_upload_materials) and ks is +0 in all three components
+//   frame[o] = { Z.xyz, X.x | X.yz, 0, 0 }    tangent_frame() of N (o = 0) and of -N (o = 1): both are computed, never one derived
+//                                  from the other -- Z has a literal +0 component, so the signs of zeros in X do not simply flip
+struct ShadeRec {
+    float N[3];
+    int32_t type;
+    float kd[3];
+    uint32_t mati;
+    float frame[2][8];
+};
+static_assert(sizeof(ShadeRec) == 96, "ShadeRec must be 96 B");
+constexpr uint32_t kShadeRecPlain = 0x80000000u;
+constexpr int32_t kShadeRecNoMaterial = 0x7fffffff;   // type of a record whose mati is outside the uploaded materials (never a lobe or a specular type)
+// Which k_render instances read the record: the fused ones (SPLIT = false) with the tree in LDS, the VALU-bound launches.  The
+// launches that read nodes from global memory wait for memory, not for the VALU, and a mesh's records would be 96 B per triangle
+// next to packets that already miss L2: no record is built for them.
+constexpr bool shade_records_for(int node_mode) { return node_mode == 0 /* kNodesLds */; }
+
 // 4-wide node, 64 B = 4 x float4 (pt_wide.cpp builds it from the BVH2; Trav<kNodesWide>::wide_step reads it):
 //   { origin.xyz, exp_x | exp_y << 8 | exp_z << 16 | nchild << 24 }      grid of the node: plane = origin + q * 2^(exp - 127)
 //   { qlo_x, qhi_x, qlo_y, qhi_y }   { qlo_z, qhi_z, -, - }              byte k of each word = child k's plane on that grid
@@ -151,6 +173,7 @@ struct RenderParams {
     uint32_t* tile_cost;         // counting instances only, or null: [n_tiles] += shader-clock cycles / 64 the wave spent on each work item of the tile (pt_debug_tile_cost)
     const int32_t* tile_list;    // != 0 (adaptive frames, pt_render_adaptive): tile t of the launch is frame tile tile_list[t]; work items,
                                  // tile_done[] and debug_stall_tile count list positions, tile_cost frame tiles
+    const float4* shaderec;      // [n_tris] ShadeRec, or null where the launch's instance does not read it (shade_records_for)
     int32_t moments;             // option "moments": 1 folds every sample's squared luminance into colors[].w (running_moment), 0 writes .w = 0
 };
 
@@ -309,6 +332,8 @@ hipError_t launch_trace_ray(const RenderParams& p, const LaunchConfig& lc, hipSt
 hipError_t launch_render_mega(const RenderParams& p, const LaunchConfig& lc, hipStream_t stream);
 hipError_t launch_resolve_reinhard(const float4* colors, float4* out, int64_t n, hipStream_t stream);
 hipError_t launch_filt_im(const float4* colors, float4* out, int32_t width, int32_t height, hipStream_t stream);
+// the per-triangle shading records of n packed triangles (pt_shaderec.hip)
+hipError_t launch_shade_records(const float4* tris, const TriMeta* meta, const pt_material* mats, int32_t n_mats, int32_t n, ShadeRec* out, hipStream_t stream);
 hipError_t launch_wf_generate(const WfParams& p, hipStream_t stream);
 hipError_t launch_wf_intersect(const WfParams& p, int bounce, int cu_count, hipStream_t stream);
 hipError_t launch_wf_shade(const WfParams& p, int bounce, hipStream_t stream);

@@ -73,6 +73,12 @@ __global__ void __launch_bounds__(256) k_gen_ray(RenderParams p) {
 //                  the others finish: a wave has up to two items in hand, and only the end of the launch is a tail.  (render_items_migrating)
 enum : int { kSchedLockstep = 0, kSchedSuspend = 1, kSchedMigrate = 2 };
 
+// Which instances shade from the per-triangle records (shade_hit<SK, REC>): the schedule-2 item loop (render_items_migrating) of the
+// launches whose node mode has records (shade_records_for, pt_internal.hpp; the host builds them for exactly those launches).  That
+// is the instance the record was measured on.  The lockstep and suspend loops keep the inline path: the 768-thread suspend instance
+// needs 16 bytes more scratch with the record (36 -> 52) and neither loop has been measured with it.  So does the split API's trace_ray.
+template <int MODE>
+constexpr bool kShadeRec = shade_records_for(MODE);
 
 // LEAN (the instances for 6 / 7 waves per SIMD: 80 / 72 VGPRs hold the traversal and little else): nothing that can be
 // recomputed or fetched is carried across a traversal -- the running mean is folded into colors[] at the end of every
@@ -424,7 +430,7 @@ PT_DEV void render_items_migrating(const RenderParams& p, const SceneView& sv, c
                 nxt_item = fetch();
                 no_more = __builtin_amdgcn_readfirstlane((int)(nxt_item < 0));
                 nxt_ready = 0;
-                nxt_end = __builtin_amdgcn_readfirstlane(end_of(nxt_item));
+                if (nxt_item >= 0) nxt_end = __builtin_amdgcn_readfirstlane(end_of(nxt_item));      // (-1: no pass to look up)
             }
             if (nxt_item >= 0 && !nxt_ready && released(nxt_item)) {
                 if (pass_of(nxt_item) > 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -465,7 +471,7 @@ PT_DEV void render_items_migrating(const RenderParams& p, const SceneView& sv, c
                 ++my_segs;
                 if (tr.best >= 0) {
                     if (COUNT) { if (first_active_lane()) wc->wshade++; count_low(wc, 3); }
-                    shade_hit<SK>(rP, rD, st, seed, inside, p, sv.tris, sv.meta, tr.best, tr.best_t);
+                    shade_hit<SK, kShadeRec<MODE>>(rP, rD, st, seed, inside, p, sv.tris, sv.meta, tr.best, tr.best_t);
                     ++bounce;
                     finished = (bounce >= p.iterations);
                 }

@@ -187,6 +187,29 @@ void fill_params(const pt_context* ctx, const pt_camera* cam, RenderParams* p) {
     p->migrate_lanes = ctx->migrate_lanes > 0 ? ctx->migrate_lanes : 1;      // (1 / 9 / 20: MESH-100k 1,192 / 1,112 / 1,113 -- waiting for company costs more than moving alone)
 }
 
+// The shading records of a launch whose k_render instance reads them (shade_records_for): built here, on the context's stream in
+// front of the launch, when triangles or materials were uploaded since the last build -- once per upload, not per render.  Sets
+// p->shaderec; launches of the other instances carry null and the records are not built for them.
+int ensure_shade_records(pt_context* ctx, RenderParams* p) {
+    p->shaderec = nullptr;
+    if (!shade_records_for(p->node_mode)) return PT_OK;
+    if (ctx->shaderec_dirty) {
+        const size_t n = ctx->orig.size();
+        if (!ctx->d_shaderec || ctx->shaderec_cap < std::max<size_t>(n, 1)) {
+            if (ctx->d_shaderec) { PT_HIP(ctx, hipFree(ctx->d_shaderec)); ctx->d_shaderec = nullptr; }
+            ctx->shaderec_cap = 0;
+            PT_HIP(ctx, hipMalloc((void**)&ctx->d_shaderec, sizeof(ShadeRec) * std::max<size_t>(n, 1)));
+            ctx->shaderec_cap = std::max<size_t>(n, 1);
+        }
+        // (an empty scene keeps one all-zero record next to its one all-zero packet, which can never be hit)
+        if (n == 0) PT_HIP(ctx, hipMemsetAsync(ctx->d_shaderec, 0, sizeof(ShadeRec), ctx->stream));
+        PT_HIP(ctx, launch_shade_records(ctx->d_tris, ctx->d_meta, ctx->d_mats, ctx->mats_on_device, (int32_t)n, ctx->d_shaderec, ctx->stream));
+        ctx->shaderec_dirty = false;
+    }
+    p->shaderec = reinterpret_cast<const float4*>(ctx->d_shaderec);
+    return PT_OK;
+}
+
 int check_ready(pt_context* ctx, const pt_camera* cam) {
     if (!cam) return fail(ctx, PT_EINVAL, "camera is NULL");
     if (!ctx->tris_uploaded) return fail(ctx, PT_EINVAL, "pt_upload_triangles has not been called");
@@ -486,6 +509,8 @@ static int launch_megakernel(pt_context* ctx, RenderParams& p, const int32_t* ti
     const size_t frame_tiles = (size_t)local_tiles(ctx);
     LaunchConfig lc;
     launch_cfg(ctx, p, &lc);
+    // (the schedule-2 item loop is the one that reads shading records: launch_render_mega takes it for persistent launches only)
+    if (lc.schedule == 2 && ctx->persistent && (rc = ensure_shade_records(ctx, &p)) != PT_OK) return rc;
     if (ctx->persistent) {
         if (int rc2 = prepare_work_counter(ctx)) return rc2;
         p.tile_counter = ctx->d_tile_counter;      // (zero: the previous launch's last wave reset it)
