@@ -133,6 +133,35 @@ int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t
  * and another pt_render_adaptive return PT_EINVAL. */
 int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations,
                        int32_t min_spp, int32_t max_spp, float threshold);
+/* The same frame with a choice of error measure and render path (new; pt_render_adaptive is {PT_ADAPT_HALF, PT_ADAPT_PATH_RENDER} and
+ * is unchanged).  Rounds, boundaries, decisions after every b(k) with k >= 1 and b(k) < max_spp, one synchronisation per round, the
+ * held frame, world 1, pt_read_sample_counts / pt_read_tile_state / pt_debug_adaptive_list, the "samples" statistic and the argument
+ * checks are pt_render_adaptive's; params NULL, an unknown metric or path, or (path NEE) an unknown strategy give PT_EINVAL, all before
+ * PT_ENODEVICE.
+ * metric PT_ADAPT_HALF: the estimate above, max over the tile.
+ * metric PT_ADAPT_VARIANCE: option "moments" must be 1 (else PT_EINVAL); no snapshot is kept.  At boundary b, float32, in this order:
+ *   per pixel inside the frame  mu = l(colors.xyz), v = fmaxf(fmaf(-mu, mu, colors.w), 0) / (float)(b - 1)   (pt_read_variance at n = b)
+ *   tonemapped != 0:            d = 1.0f + mu, v = v / ((d*d)*(d*d))      (the derivative of Reinhard's L / (1 + L), pt_resolve_ldr(0))
+ *   lane (y&7)*8 + (x&7) of the tile's 64 holds v (0 outside the frame); for off = 32, 16, 8, 4, 2, 1: s[lane] = s[lane] + s[lane ^ off]
+ *   e = sqrtf(s / (float)pixels inside), +inf if not finite; the tile retires iff e < threshold.
+ *   The threshold is the tile's predicted root-mean-square error of the mean luminance (display-referred with tonemapped).
+ * path PT_ADAPT_PATH_RENDER: rounds are pt_render's megakernel over the active tiles; PT_EINVAL while an environment is set and for
+ *   variant != 0; strategy is ignored.
+ * path PT_ADAPT_PATH_NEE: rounds render with pt_render_nee's estimator at `strategy` (PT_NEE_*), the environment included when one is
+ *   set; a pixel that stopped after k samples holds what pt_render_nee(k) from sample 0 leaves in colors (.w too), rnds and rays.  Any
+ *   variant; the 31-bit work-item check of the megakernel path does not apply. */
+enum { PT_ADAPT_HALF = 0, PT_ADAPT_VARIANCE = 1 };          /* metric */
+enum { PT_ADAPT_PATH_RENDER = 0, PT_ADAPT_PATH_NEE = 1 };   /* path   */
+typedef struct { int32_t min_spp, max_spp; float threshold;
+                 int32_t metric, path, strategy, tonemapped; } pt_adaptive_params;
+/* min_spp 16, max_spp 1024, threshold 0.03, metric VARIANCE, path RENDER, strategy PT_NEE_MIS, tonemapped 1.  The threshold comes from
+ * the {VARIANCE, RENDER, tonemapped 1} sweep of tools/adaptive_sweep.py at 1920x1080, 8 bounces (profiles/adaptive/README.md): the
+ * largest value of the sweep whose display-referred RMSE stays near the one of max_spp -- Cornell box 0.0260 against 0.0215 with 0.73 of
+ * the samples, MESH-100k (16..256) 0.0445 against 0.0433 with 0.86.  It saves neither samples nor wall time against uniform sampling at
+ * equal error there; the one measured saving (25-30 % of the samples at equal RMSE, wall time about level) is tonemapped 0 with a
+ * threshold on the linear scale, 0.05 to 0.15 in that sweep (same file). */
+void pt_adaptive_defaults(pt_adaptive_params* p);
+int pt_render_adaptive_ex(pt_context* ctx, const pt_camera* cam, int32_t iterations, const pt_adaptive_params* params);
 /* per local pixel: the number of samples its colour is the mean of (0 for none yet) */
 int pt_read_sample_counts(pt_context* ctx, int32_t* out, int64_t npix);
 /* per 8x8 tile of the local frame (raster order): samples rendered, and the last noise estimate computed for it (+inf: none);

@@ -109,6 +109,11 @@ public:
         camera = Camera(globals);
         ck(pt_render_adaptive(ctx, &camera, globals.iterations, min_spp, max_spp, threshold));
     }
+    // the same with a choice of error measure and render path (pt_render_adaptive_ex; start from pt_adaptive_defaults)
+    void render_adaptive(const pt_adaptive_params& params) {
+        camera = Camera(globals);
+        ck(pt_render_adaptive_ex(ctx, &camera, globals.iterations, &params));
+    }
     // nsamples of render(n)'s estimator with next-event estimation (pt_render_nee; strategy PT_NEE_BSDF / _LIGHT / _MIS)
     void render_nee(int nsamples, int strategy = PT_NEE_MIS) {
         camera = Camera(globals);

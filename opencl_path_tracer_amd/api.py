@@ -43,7 +43,7 @@ EXPORTS = [
     "pt_material_init", "pt_triangle_init", "pt_triangles_init", "pt_camera_init", "pt_camera_move", "pt_create", "pt_create_tiled", "pt_destroy",
     "pt_last_error", "pt_device_info", "pt_add_material", "pt_add_triangle", "pt_add_triangles", "pt_end_obj",
     "pt_add_obj", "pt_upload_triangles", "pt_upload_materials", "pt_seed_default", "pt_upload_seeds",
-    "pt_generate_rays", "pt_trace_rays", "pt_render", "pt_render_adaptive", "pt_read_sample_counts", "pt_read_tile_state", "pt_adaptive_rounds",
+    "pt_generate_rays", "pt_trace_rays", "pt_render", "pt_render_adaptive", "pt_adaptive_defaults", "pt_render_adaptive_ex", "pt_read_sample_counts", "pt_read_tile_state", "pt_adaptive_rounds",
     "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
     "pt_render_nee", "pt_nee_rand", "pt_debug_light_table",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
@@ -101,6 +101,8 @@ def _load():
     sig("pt_trace_rays", C.c_int, vp, vp, i32, i32)
     sig("pt_render", C.c_int, vp, vp, i32, i32)
     sig("pt_render_adaptive", C.c_int, vp, vp, i32, i32, i32, f32)
+    sig("pt_adaptive_defaults", None, vp)
+    sig("pt_render_adaptive_ex", C.c_int, vp, vp, i32, vp)
     sig("pt_read_sample_counts", C.c_int, vp, vp, i64)
     sig("pt_read_tile_state", C.c_int, vp, vp, vp, i64)
     sig("pt_adaptive_rounds", C.c_int, i32, i32, vp, i32, C.POINTER(i32))
@@ -236,6 +238,28 @@ def adaptive_rounds(min_spp, max_spp):
 PT_NEE_BSDF, PT_NEE_LIGHT, PT_NEE_MIS = 0, 1, 2
 PT_MATH_SQRT, PT_MATH_RSQRT, PT_MATH_DIV_GRID, PT_MATH_DIV_RANDOM, PT_MATH_DIV_NORMAL = 0, 1, 2, 3, 4   # pt_debug_math enumerations
 NEE_STRATEGIES = {"bsdf": PT_NEE_BSDF, "light": PT_NEE_LIGHT, "mis": PT_NEE_MIS}
+
+
+PT_ADAPT_HALF, PT_ADAPT_VARIANCE = 0, 1
+PT_ADAPT_PATH_RENDER, PT_ADAPT_PATH_NEE = 0, 1
+ADAPT_METRICS = {"half": PT_ADAPT_HALF, "variance": PT_ADAPT_VARIANCE}
+ADAPT_PATHS = {"render": PT_ADAPT_PATH_RENDER, "nee": PT_ADAPT_PATH_NEE}
+
+
+class AdaptiveParams(C.Structure):
+    """pt_adaptive_params (include/pt_api.h)."""
+    _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float), ("metric", C.c_int32), ("path", C.c_int32),
+                ("strategy", C.c_int32), ("tonemapped", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def adaptive_defaults():
+    """pt_adaptive_defaults as a dict: min_spp, max_spp, threshold, metric, path, strategy, tonemapped."""
+    p = AdaptiveParams()
+    LIB.pt_adaptive_defaults(C.byref(p))
+    return p.as_dict()
 
 
 def nee_rand(state, segment, dim):
@@ -495,10 +519,28 @@ class Scene:
                 self.trace_rays()
                 self.current_sample = self.current_sample + 1                                        # main.cpp:686
 
-    def render_adaptive(self, min_spp, max_spp, threshold):
-        """One adaptive frame (pt_render_adaptive; current_sample must be 0).  Returns {"rounds": the boundaries whose round ran,
-        "active_tiles": tiles rendered in each of those rounds, "samples": samples spent on the frame}."""
-        self._ck(LIB.pt_render_adaptive(self._h, _ptr(self.camera), self.iterations, int(min_spp), int(max_spp), float(threshold)))
+    def render_adaptive(self, min_spp, max_spp, threshold, **params):
+        """One adaptive frame (current_sample must be 0): pt_render_adaptive, or pt_render_adaptive_ex when any of metric= ("half" /
+        "variance"), path= ("render" / "nee"), strategy= ("bsdf" / "light" / "mis") or tonemapped= is given (or the PT_* codes); what
+        is not given is pt_adaptive_defaults'.  Returns {"rounds": the boundaries whose round ran, "active_tiles": tiles rendered in
+        each of those rounds, "samples": samples spent on the frame}."""
+        if params:
+            p = AdaptiveParams(**adaptive_defaults())
+            p.min_spp, p.max_spp, p.threshold = int(min_spp), int(max_spp), float(threshold)
+            names = {"metric": ADAPT_METRICS, "path": ADAPT_PATHS, "strategy": NEE_STRATEGIES, "tonemapped": None}
+            for k, v in params.items():
+                if k not in names:
+                    raise TypeError("unknown adaptive parameter %r" % k)
+                if isinstance(v, str):
+                    if names[k] is None:
+                        raise TypeError("%s must be a number, not %r" % (k, v))
+                    if v not in names[k]:
+                        raise KeyError("%s must be one of %s (or the PT_* code), not %r" % (k, ", ".join(sorted(names[k])), v))
+                    v = names[k][v]
+                setattr(p, k, int(v))
+            self._ck(LIB.pt_render_adaptive_ex(self._h, _ptr(self.camera), self.iterations, C.byref(p)))
+        else:
+            self._ck(LIB.pt_render_adaptive(self._h, _ptr(self.camera), self.iterations, int(min_spp), int(max_spp), float(threshold)))
         spp, _ = self.tile_state()
         bounds = adaptive_rounds(min_spp, max_spp)
         active = [int((spp >= b).sum()) for b in bounds]

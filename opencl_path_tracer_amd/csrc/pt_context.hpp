@@ -227,6 +227,8 @@ constexpr size_t kLdsSlack = 32 * 100 + 4096 + 1024 + 256;
 int fail(pt_context* ctx, int code, const std::string& msg);      // pt_host.cpp: records the text behind pt_last_error
 int light_table_ready(pt_context* ctx);                            // pt_host.cpp: builds the light table of the uploaded scene if it is stale
 float env_select(const pt_context* ctx, bool no_lights);           // pt_env.cpp: the effective P_env
+// pt_host.cpp: the light table on the device and the environment's view (*sky: a map with a distribution is set) for a launch_nee
+int nee_prepare(pt_context* ctx, int32_t strategy, NeeTable* lt, EnvView* env, bool* sky);
 int host_threads(const pt_context* ctx);                          // threads of the host-side scene path (option build_threads)
 
 #define PT_HIP(ctx, call)                                                                   \

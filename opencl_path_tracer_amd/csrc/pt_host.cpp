@@ -796,16 +796,12 @@ int pt_debug_light_table(pt_context* ctx, int32_t* orig_tri, float* cdf, int64_t
     }
     return PT_OK;
 }
-int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples, int32_t strategy) {
-    if (!ctx) return PT_EINVAL;
-    if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "pt_render_nee: iterations/nsamples must be >= 0");
-    if (strategy < PT_NEE_BSDF || strategy > PT_NEE_MIS) return fail(ctx, PT_EINVAL, "pt_render_nee: strategy must be PT_NEE_BSDF, PT_NEE_LIGHT or PT_NEE_MIS");
-    PT_NEED_DEVICE(ctx);
-    int rc = check_ready(ctx, cam);
-    if (rc != PT_OK) return rc;
-    if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "pt_render_nee: an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
-    if ((int64_t)ctx->current_sample + nsamples > INT32_MAX) return fail(ctx, PT_EINVAL, "pt_render_nee: current_sample + nsamples overflows");
-    if (nsamples == 0) return PT_OK;
+}  // extern "C"
+namespace ptamd {
+// What a launch of the NEE kernels needs besides RenderParams (pt_render_nee, the NEE rounds of pt_render_adaptive_ex): the light table
+// of the uploaded scene on the device, and the environment's view when a map with a distribution is set (*sky)
+int nee_prepare(pt_context* ctx, int32_t strategy, NeeTable* ltp, EnvView* envp, bool* skyp) {
+    int rc = PT_OK;
     if ((rc = nee_table(ctx)) != PT_OK) return rc;
     PT_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->nee_uploaded) {
@@ -826,19 +822,14 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
         PT_HIP(ctx, hipMemcpy(ctx->d_nee_pdf_area, ctx->nee_pdf_area.data(), sizeof(float) * ctx->nee_pdf_area.size(), hipMemcpyHostToDevice));
         ctx->nee_uploaded = true;
     }
-    RenderParams p;
-    fill_params(ctx, cam, &p);         // the render kernels' node placement
-    p.iterations = iterations;
-    p.first_sample = ctx->current_sample;
-    p.nsamples = nsamples;
-    NeeTable lt;
+    NeeTable& lt = *ltp;
     lt.tri = ctx->d_nee_tri;
     lt.cdf = ctx->d_nee_cdf;
     lt.pdf_area = ctx->d_nee_pdf_area;
     lt.n = (int32_t)ctx->nee_tri.size();
     lt.strategy = strategy;
     // an environment without a distribution is all zero: the instances without one compute the same frame
-    EnvView env;
+    EnvView& env = *envp;
     const bool sky = ctx->env_set && ctx->env_dist;
     if (sky) {
         env.texels = ctx->d_env_texels;
@@ -850,6 +841,30 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
         env.yaw = ctx->env_yaw;
         env.p_env = env_select(ctx, lt.n == 0);
     }
+    *skyp = sky;
+    return PT_OK;
+}
+}  // namespace ptamd
+extern "C" {
+int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples, int32_t strategy) {
+    if (!ctx) return PT_EINVAL;
+    if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "pt_render_nee: iterations/nsamples must be >= 0");
+    if (strategy < PT_NEE_BSDF || strategy > PT_NEE_MIS) return fail(ctx, PT_EINVAL, "pt_render_nee: strategy must be PT_NEE_BSDF, PT_NEE_LIGHT or PT_NEE_MIS");
+    PT_NEED_DEVICE(ctx);
+    int rc = check_ready(ctx, cam);
+    if (rc != PT_OK) return rc;
+    if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "pt_render_nee: an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
+    if ((int64_t)ctx->current_sample + nsamples > INT32_MAX) return fail(ctx, PT_EINVAL, "pt_render_nee: current_sample + nsamples overflows");
+    if (nsamples == 0) return PT_OK;
+    NeeTable lt;
+    EnvView env;
+    bool sky = false;
+    if ((rc = nee_prepare(ctx, strategy, &lt, &env, &sky)) != PT_OK) return rc;
+    RenderParams p;
+    fill_params(ctx, cam, &p);         // the render kernels' node placement
+    p.iterations = iterations;
+    p.first_sample = ctx->current_sample;
+    p.nsamples = nsamples;
     ctx->render_epoch++;
     note_frame(ctx, p.first_sample, cam);
     EventPair* ep;

@@ -341,6 +341,10 @@ hipError_t launch_wf_shade(const WfParams& p, int bounce, hipStream_t stream);
 // snap = colors; 2 also the noise estimate against snap -> tile_err, active (0: retired), and snap = colors where the tile stays active
 hipError_t launch_adaptive_tiles(const float4* colors, float4* snap, const int32_t* list, int32_t n_list, int32_t width, int32_t rows, int mode,
                                  float threshold, int32_t spp, float* tile_err, int32_t* tile_spp, uint8_t* active, hipStream_t stream);
+// metric PT_ADAPT_VARIANCE (pinned in include/pt_api.h): per tile of `list` the root mean square of the pixels' variance of the mean
+// luminance at spp samples (colors[].w: option "moments") -> tile_err, active (0: retired), tile_spp = spp; reads and writes no snapshot
+hipError_t launch_adaptive_variance(const float4* colors, const int32_t* list, int32_t n_list, int32_t width, int32_t rows, float threshold,
+                                    int tonemapped, int32_t spp, float* tile_err, int32_t* tile_spp, uint8_t* active, hipStream_t stream);
 // the frame tiles whose flag is set, ascending, into list[0, *count) (one workgroup)
 hipError_t launch_compact_tiles(const uint8_t* active, int32_t n, int32_t* list, int32_t* count, hipStream_t stream);
 hipError_t launch_debug_closest_hit(const RenderParams& p, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri, int cu_count, hipStream_t stream);
@@ -389,8 +393,9 @@ struct EnvView {
     float scale, yaw;            // yaw in radians
     float p_env;                 // the effective P_env (a multiple of 2^-24)
 };
-// env == nullptr: the instances without an environment
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream);
+// env == nullptr: the instances without an environment.  tiled (the rounds of pt_render_adaptive_ex): k_nee_tiles / k_nee_env_tiles over
+// the p.n_tiles 8x8 frame tiles of p.tile_list (null: the frame's tiles in order), one lane per pixel of a tile; npix is then not read
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled = false);
 // the texel of unit direction (x, y, z): k_nee and pt_env_lookup
 __host__ __device__ __forceinline__ void env_texel(int32_t w, int32_t h, float yaw, float x, float y, float z, int32_t* row, int32_t* col) {
     const float theta = acosf(fminf(fmaxf(y, -1.0f), 1.0f));

@@ -612,42 +612,58 @@ static std::string adaptive_bounds(int32_t min_spp, int32_t max_spp, std::vector
     return "";
 }
 
-// Round k renders samples [b(k-1), b(k)) of the active tiles -- an ordinary megakernel launch over the list of them -- and, where
-// b(0) < b(k) < max_spp, k_adaptive_tiles compares every pixel's mean with its snapshot at b(k-1) = b(k) / 2 and retires the tiles whose
-// largest estimate is below the threshold; k_compact_tiles lists the others for the next round, and their count comes back to the host
-// (one synchronisation per round).  Round 0 (b(0) samples, every tile) only takes the snapshot.
-int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t min_spp, int32_t max_spp, float threshold) {
+// Round k renders samples [b(k-1), b(k)) of the active tiles -- an ordinary megakernel launch over the list of them, or (path NEE) the
+// tiled k_nee instance -- and, where b(0) < b(k) < max_spp, the decision kernel retires tiles: k_adaptive_tiles (metric HALF) compares
+// every pixel's mean with its snapshot at b(k-1) = b(k) / 2 and retires the tiles whose largest estimate is below the threshold,
+// k_adaptive_variance (metric VARIANCE) those whose root-mean-square variance of the mean is; k_compact_tiles lists the others for the next
+// round, and their count comes back to the host (one synchronisation per round).  Round 0 (b(0) samples, every tile) only takes the
+// snapshot (HALF).  Both entry points run this; `who` names the caller in the messages.
+static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterations, const pt_adaptive_params* ap, const std::string& who) {
     if (!ctx) return PT_EINVAL;
+    if (!ap) return fail(ctx, PT_EINVAL, who + ": params is NULL");
+    const int32_t min_spp = ap->min_spp, max_spp = ap->max_spp;
+    const float threshold = ap->threshold;
+    const bool variance = ap->metric == PT_ADAPT_VARIANCE, nee = ap->path == PT_ADAPT_PATH_NEE;
     std::vector<int32_t> bounds;
     std::string why = adaptive_bounds(min_spp, max_spp, &bounds);
     if (why.empty() && !(threshold >= 0.0f)) why = "threshold must be >= 0 (and not NaN)";
     if (why.empty() && iterations < 0) why = "iterations must be >= 0";
-    if (why.empty()) {      // the longest round must fit one launch's 31-bit work-item counter at one sample per item, with room for the grid
+    if (why.empty() && ap->metric != PT_ADAPT_HALF && ap->metric != PT_ADAPT_VARIANCE) why = "metric must be PT_ADAPT_HALF or PT_ADAPT_VARIANCE";
+    if (why.empty() && ap->path != PT_ADAPT_PATH_RENDER && ap->path != PT_ADAPT_PATH_NEE) why = "path must be PT_ADAPT_PATH_RENDER or PT_ADAPT_PATH_NEE";
+    if (why.empty() && nee && (ap->strategy < PT_NEE_BSDF || ap->strategy > PT_NEE_MIS)) why = "strategy must be PT_NEE_BSDF, PT_NEE_LIGHT or PT_NEE_MIS";
+    if (why.empty() && !nee) {      // the longest round must fit one launch's 31-bit work-item counter at one sample per item, with room for the grid
         int64_t longest = bounds[0];
         for (size_t k = 1; k < bounds.size(); ++k) longest = std::max<int64_t>(longest, (int64_t)bounds[k] - bounds[k - 1]);
         if (longest * (int64_t)local_tiles(ctx) + ((int64_t)1 << 20) >= ((int64_t)1 << 31))
             why = "max_spp too large: a round of " + std::to_string(longest) + " samples over " + std::to_string(local_tiles(ctx)) +
                   " tiles does not fit the 31-bit work-item counter of one launch";
     }
-    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_render_adaptive: " + why);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, who + ": " + why);
     PT_NEED_DEVICE(ctx);
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
-    if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_render_adaptive: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
-    if (ctx->variant != 0) return fail(ctx, PT_EINVAL, "pt_render_adaptive: the megakernel (variant 0) only");
-    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_render_adaptive: contexts of one rank (world == 1) only");
+    if (!nee && ctx->env_set) return fail(ctx, PT_EINVAL, who + ": an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
+    if (!nee && ctx->variant != 0) return fail(ctx, PT_EINVAL, who + ": the megakernel (variant 0) only");
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, who + ": contexts of one rank (world == 1) only");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
-    if (ctx->current_sample != 0) return fail(ctx, PT_EINVAL, "pt_render_adaptive starts a frame: current_sample must be 0");
+    if (ctx->current_sample != 0) return fail(ctx, PT_EINVAL, who + " starts a frame: current_sample must be 0");
+    if (variance && !ctx->moments)
+        return fail(ctx, PT_EINVAL, who + ": metric PT_ADAPT_VARIANCE: the frame was not rendered with option moments = 1 from its first sample");
     PT_HIP(ctx, hipSetDevice(ctx->device));
+    NeeTable lt;
+    EnvView env;
+    bool sky = false;
+    if (nee && (rc = nee_prepare(ctx, ap->strategy, &lt, &env, &sky)) != PT_OK) return rc;
     const int32_t n_frame = local_tiles(ctx);
-    if (!ctx->d_adapt_snap) {
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_snap, sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
+    if (!ctx->d_adapt_spp) {
         PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_spp, sizeof(int32_t) * (size_t)n_frame));
         PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_err, sizeof(float) * (size_t)n_frame));
         PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_active, (size_t)n_frame));
         PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_list, sizeof(int32_t) * ((size_t)n_frame + 1)));
         PT_HIP(ctx, hipHostMalloc((void**)&ctx->h_adapt_count, sizeof(int32_t), hipHostMallocDefault));
     }
+    if (!variance && !ctx->d_adapt_snap)      // (the variance metric keeps no snapshot)
+        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_snap, sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
     int32_t* d_count = ctx->d_adapt_list + n_frame;
     PT_HIP(ctx, hipMemsetAsync(ctx->d_adapt_active, 1, (size_t)n_frame, ctx->stream));
     PT_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(int32_t), ctx->stream));          // (no list before the first decision)
@@ -666,11 +682,27 @@ int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations
         RenderParams pr = p;
         pr.first_sample = prev;
         pr.nsamples = b - prev;
-        if ((rc = launch_megakernel(ctx, pr, list, n_active)) != PT_OK) return rc;
+        if (nee) {
+            pr.tile_list = list;
+            pr.n_tiles = n_active;
+            EventPair* ep;
+            if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
+            PT_HIP(ctx, launch_nee(pr, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, true));
+            if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
+        } else if ((rc = launch_megakernel(ctx, pr, list, n_active)) != PT_OK) {
+            return rc;
+        }
         ctx->current_sample = b;
         const int mode = k == 0 ? 1 : b < max_spp ? 2 : 0;
-        PT_HIP(ctx, launch_adaptive_tiles(ctx->d_colors, ctx->d_adapt_snap, list, n_active, ctx->W, ctx->local_rows, mode, threshold, b,
-                                          ctx->d_adapt_err, ctx->d_adapt_spp, ctx->d_adapt_active, ctx->stream));
+        if (!variance)
+            PT_HIP(ctx, launch_adaptive_tiles(ctx->d_colors, ctx->d_adapt_snap, list, n_active, ctx->W, ctx->local_rows, mode, threshold, b,
+                                              ctx->d_adapt_err, ctx->d_adapt_spp, ctx->d_adapt_active, ctx->stream));
+        else if (mode != 2)      // (mode 0 of k_adaptive_tiles: tile_spp only, no snapshot touched)
+            PT_HIP(ctx, launch_adaptive_tiles(ctx->d_colors, nullptr, list, n_active, ctx->W, ctx->local_rows, 0, threshold, b, ctx->d_adapt_err,
+                                              ctx->d_adapt_spp, ctx->d_adapt_active, ctx->stream));
+        else
+            PT_HIP(ctx, launch_adaptive_variance(ctx->d_colors, list, n_active, ctx->W, ctx->local_rows, threshold, ap->tonemapped ? 1 : 0, b,
+                                                 ctx->d_adapt_err, ctx->d_adapt_spp, ctx->d_adapt_active, ctx->stream));
         if (mode != 2) continue;
         PT_HIP(ctx, launch_compact_tiles(ctx->d_adapt_active, n_frame, ctx->d_adapt_list, d_count, ctx->stream));
         PT_HIP(ctx, hipMemcpyAsync(ctx->h_adapt_count, d_count, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -680,6 +712,26 @@ int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations
         if (n_active == 0) break;
     }
     return PT_OK;
+}
+
+int pt_render_adaptive(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t min_spp, int32_t max_spp, float threshold) {
+    const pt_adaptive_params ap = {min_spp, max_spp, threshold, PT_ADAPT_HALF, PT_ADAPT_PATH_RENDER, PT_NEE_MIS, 0};
+    return adaptive_frame(ctx, cam, iterations, &ap, "pt_render_adaptive");
+}
+
+void pt_adaptive_defaults(pt_adaptive_params* p) {
+    if (!p) return;
+    p->min_spp = 16;
+    p->max_spp = 1024;
+    p->threshold = 0.03f;      // (the tonemapped sweep of profiles/adaptive/README.md)
+    p->metric = PT_ADAPT_VARIANCE;
+    p->path = PT_ADAPT_PATH_RENDER;
+    p->strategy = PT_NEE_MIS;
+    p->tonemapped = 1;
+}
+
+int pt_render_adaptive_ex(pt_context* ctx, const pt_camera* cam, int32_t iterations, const pt_adaptive_params* params) {
+    return adaptive_frame(ctx, cam, iterations, params, "pt_render_adaptive_ex");
 }
 
 int pt_debug_adaptive_list(pt_context* ctx, int32_t* out, int64_t cap, int64_t* n) {

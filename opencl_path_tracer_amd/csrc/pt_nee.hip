@@ -8,6 +8,11 @@
 //   k_nee_env  the same frame under an environment map (pt_set_environment): a miss adds the sky, and a lobe vertex samples either
 //           the sky or a triangle light, chosen by one more hash value.  One body, nee_frame<MODE, BLOCK, ENV>; every statement that
 //           touches the environment sits under `if constexpr (ENV)`, so k_nee is the code it was.
+//   k_nee_tiles, k_nee_env_tiles  the same body over a list of 8x8 frame tiles (the rounds of pt_render_adaptive_ex): work item j is
+//           pixel j & 63 of tile frame_tile(p, j >> 6), so a wave is a tile as in k_render.  nee_frame<..., TILED>; the work it adds
+//           sits under `if constexpr (TILED)`.  Three declarations do not, because both branches use them after the branch (the loop
+//           counter j with the pixel i = j, lrow / x, and the pixel counter `rendered`, which is dead in the untiled instances): the
+//           untiled kernels compile to the code they were (the same kernel-resource lines).
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -231,7 +236,7 @@ struct NeeHook {
     }
 };
 
-template <int MODE, int BLOCK, bool ENV>
+template <int MODE, int BLOCK, bool ENV, bool TILED = false>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
@@ -243,8 +248,24 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
         hook.nee = lt.strategy != 0;       // the sky is a light (the host launches this instance only for a map with a distribution)
     }
     const int camX = (int)p.cam.XM;
-    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < npix; i += (long long)gridDim.x * BLOCK) {
-        const int lrow = (int)(i / p.width), x = (int)(i % p.width);
+    unsigned rendered = 0;                     // TILED: pixels this lane rendered (statistic "samples", as k_render counts them)
+    if constexpr (TILED) npix = (long long)p.n_tiles * 64;      // work items: 64 per listed tile
+    for (long long j = (long long)blockIdx.x * BLOCK + threadIdx.x; j < npix; j += (long long)gridDim.x * BLOCK) {
+        long long i = j;                       // the local pixel
+        int lrow, x;
+        if constexpr (TILED) {                 // BLOCK is whole waves and so is the stride: a wave is one tile, j >> 6 wave-uniform
+            const int tile = frame_tile(p, (int)(j >> 6));
+            const int tiles_x = (p.width + 7) >> 3;
+            const int ty = tile / tiles_x, lane = (int)(j & 63);
+            x = (tile - ty * tiles_x) * 8 + (lane & 7);
+            lrow = ty * 8 + (lane >> 3);
+            if (x >= p.width || lrow >= p.local_rows) continue;       // (a ragged tile's lanes outside the frame)
+            i = (long long)lrow * p.width + x;
+            ++rendered;
+        } else {
+            lrow = (int)(i / p.width);
+            x = (int)(i % p.width);
+        }
         const int gid = global_row(p, lrow) * p.width + x;
         const float pix_x = (float)(gid % camX), pix_y = (float)(gid / camX);      // prog.cl:84-85
         int seed = p.rnds[i];
@@ -285,6 +306,12 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
         rr[0] = make_float4(rP.x, rP.y, rP.z, 0.0f);
         rr[1] = make_float4(rD.x, rD.y, rD.z, 0.0f);
     }
+    if constexpr (TILED) {
+        if (p.stats) {
+            const unsigned long long n = wave_sum((unsigned long long)rendered) * (unsigned long long)p.nsamples;
+            if ((threadIdx.x & 63) == 0 && n) stat_add(p, 1, n);
+        }
+    }
 }
 
 template <int MODE, int BLOCK>
@@ -296,7 +323,21 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env(RenderParams p, NeeTable lt, 
     nee_frame<MODE, BLOCK, true>(p, lt, EnvSlot<true>{env}, npix);
 }
 
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream) {
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles(RenderParams p, NeeTable lt) {
+    nee_frame<MODE, BLOCK, false, true>(p, lt, EnvSlot<false>{}, 0);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles(RenderParams p, NeeTable lt, EnvView env) {
+    nee_frame<MODE, BLOCK, true, true>(p, lt, EnvSlot<true>{env}, 0);
+}
+
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled) {
+    if (tiled) {
+        const int64_t items = (int64_t)p.n_tiles * 64;
+        if (env) return launch_lanes([](auto s) { return k_nee_env_tiles<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env);
+        return launch_lanes([](auto s) { return k_nee_tiles<s.mode, s.block>; }, p, items, cu_count, stream, lt);
+    }
     if (env) return launch_lanes([](auto s) { return k_nee_env<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, (long long)npix);
     return launch_lanes([](auto s) { return k_nee<s.mode, s.block>; }, p, npix, cu_count, stream, lt, (long long)npix);
 }
