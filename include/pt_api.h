@@ -270,6 +270,61 @@ int pt_env_lookup(int32_t w, int32_t h, float yaw_degrees, const float dir[3], i
  * Any pointer may be NULL.  PT_EINVAL when no environment is set */
 int pt_debug_environment(pt_context* ctx, int32_t* w, int32_t* h, float* row_cdf, float* col_cdf, float* pdf, int64_t cap, float* P_env);
 
+/* ---- smooth shading from vertex normals for pt_render_nee (new: opt-in with option "smooth_normals"; the reference shades with the
+ * triangle's geometric normal only) -----------
+ * Authoring (host data; all of it works on a host-only context, none of it rebuilds the BVH).  Triangles are counted in add order over
+ * the whole scene, the order of pt_debug_scene_copy.  A triangle HAS vertex normals iff all nine values recorded for it are finite and
+ * none of its three vectors is zero; every other triangle (never set, cleared, added later) has none.  Normals need not be unit length.
+ * The recorded normals survive pt_upload_triangles / pt_upload_materials.  They are repacked LAZILY: the first pt_render_nee /
+ * pt_render_adaptive_ex (path NEE) / pt_debug_shading_normal that runs with the option on after the normals or the uploaded triangles
+ * changed copies them to the device and runs k_pack_vertex_normals (pt_smooth.hip) on the context's stream: per PACKED triangle (the
+ * permutation `orig` of pt_debug_bvh_copy) three float4 {n.xyz, flag}, n = the corner's normal divided by its length in float64 and
+ * rounded once to float32, flag != 0 iff the triangle has vertex normals.
+ *   pt_set_vertex_normals      normals = count x 9 floats, n1 n2 n3 per triangle, for triangles [first_triangle, first_triangle + count);
+ *                              PT_EINVAL when the range is not inside the triangles added so far
+ *   pt_clear_vertex_normals    no triangle has vertex normals
+ *   pt_compute_vertex_normals  object = index of an object (pt_end_obj order) or -1 for all (each object on its own).  Per corner: the sum,
+ *                              in float64 and add order, of angle x face normal (the record's N divided by its float64 length; angle = the
+ *                              triangle's interior angle at that corner, acos of the clamped float64 cosine) over the triangles of the same
+ *                              object that have a corner at the same position bit for bit (+0 == -0) and whose face normal is within
+ *                              crease_degrees of this triangle's (float64 dot >= cos(crease_degrees) - 1e-12; the triangle itself always counts),
+ *                              normalised, rounded to float.  crease_degrees = 0: the face normal on every corner.  A triangle whose N is zero or
+ *                              not finite gets none.  PT_EINVAL: crease_degrees not in [0, 180], object out of range
+ *   pt_add_obj                 a face whose corners all carry a vn index (i//k, i/j/k) that exists records, for its fan triangles, those
+ *                              normals transformed by the inverse transpose of the positions' linear map -- x negated, rotate_x(pitch),
+ *                              rotate_y(yaw), DIVIDED by scale -- in float64, normalised, rounded to float.  The triangles are unchanged.
+ *   pt_debug_vertex_normals    normals: 9 floats per added triangle as recorded (0 where none), has: 1 / 0 per triangle; either may be NULL
+ * Option "smooth_normals" = 1 (default 0: every path computes what it computed before, bit for bit): pt_render_nee (every strategy, with
+ * and without an environment) and pt_render_adaptive_ex with path PT_ADAPT_PATH_NEE shade with the interpolated normal; pt_render,
+ * pt_generate_rays, pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex with PT_ADAPT_PATH_RENDER (every variant) return
+ * PT_EINVAL naming the option.  pt_render_aovs, the denoisers and pt_temporal_accumulate keep the geometric normal.
+ * The estimator is pt_render_nee's with these changes at a hit of segment k (float32, fma where dot3 / cross3 / madd have it:
+ * dot3(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x b.x)), cross3(a, b).x = fma(a.y, b.z, -(a.z b.y)) and cyclic, madd(u, s, w) = fma(u, s, w)):
+ *   N = the record's normal, Ng = N flipped against the ray (as before), hp = madd(D, t, P), vertices r1 r2 r3, packed normals n1 n2 n3;
+ *   a1 = max0(dot3(cross3(r3 - r2, hp - r2), N)), a2 = max0(dot3(cross3(r1 - r3, hp - r3), N)), a3 = max0(dot3(cross3(r2 - r1, hp - r1), N))
+ *        (max0(c) = c > 0 ? c : 0: the three terms of the exact triangle test, each the weight of the opposite vertex);
+ *   s = madd(n3, a3, madd(n2, a2, n1 * a1)), l2 = dot3(s, s), Ns = s * (1.0f / sqrtf(l2)) (both IEEE); Ns = -Ns if dot3(Ns, Ng) < 0;
+ *   Ns = Ng, the same bits, when the triangle has no vertex normals, when not 0 < l2 < inf, or when not dot3(-D, Ns) > 0.
+ * Ns replaces the flipped normal in: the emitter cosine, the cosine-sampled frame and direction, factor_L's cosine, the halfway term,
+ * Fresnel, the mirror direction and the refraction, the light sample's cosine and p_b (and fL' / fB'), and the p_b of W_b at the next
+ * hit or miss.  Offsets use the geometric normal: the new origin is hp +- 0.001 Ng and the light sample's origin o = hp + 0.001 Ng.
+ * Geometric side -- specular vertices (types 1, 2): the vertex is evaluated with Ns; if the new direction w BEFORE normalisation has
+ * dot3(w, Ng) <= 0 (reflection) or >= 0 (refraction), the whole vertex -- Fresnel, the choice between reflection and refraction, the
+ * direction, the factors -- is evaluated again with Ng in place of Ns and the same LCG value, and that evaluation stands (one LCG draw,
+ * factors applied once).  Lobe vertices (types 0, 3): a light sample counts only if dot3(w, Ng) > 0 as well as dot3(w, Ns) > 0; after the
+ * vertex's light sample, its two LCG draws and its own update (type 0: the factors; type 3: its emission), the path ends -- no further
+ * segment, draw or light sample in this sample -- if the sampled direction before normalisation has dot3(w, Ng) <= 0; rays[] then holds
+ * that direction and origin.
+ * With the option on and no triangle carrying vertex normals the frame (colors, rnds, rays) is the option-off frame bit for bit.  With
+ * normals present the paths differ from pt_render's, so rnds and rays no longer equal pt_render's. */
+int pt_set_vertex_normals(pt_context* ctx, int64_t first_triangle, int64_t count, const float* normals);
+int pt_clear_vertex_normals(pt_context* ctx);
+int pt_compute_vertex_normals(pt_context* ctx, int32_t object, float crease_degrees);
+int pt_debug_vertex_normals(const pt_context* ctx, float* normals, int32_t* has);
+/* the shading normal of the closest hit of each ray, by the device function the smooth k_nee instances call (any setting of the option):
+ * out_tri[i] = add-order triangle or -1, out_ns[4 i ..] = {Ns.xyz, t} ({0, 0, 0, -1} for a miss) */
+int pt_debug_shading_normal(pt_context* ctx, const pt_ray* rays, int64_t n, int32_t* out_tri, float* out_ns);
+
 /* ---- per-pixel variance of the mean luminance (new: opt-in with option "moments"; the reference keeps the mean only) -------
  * With option "moments" = 1 every render path (pt_render in every variant, schedule and node mode, pt_trace_rays,
  * pt_render_adaptive, pt_render_nee, tiled ranks) also folds each sample's squared luminance into colors[].w, float32 in this order:

@@ -122,6 +122,11 @@ public:
     // a lat-long map lighting render_nee (pt_set_environment; rgb: w x h x 3 floats, row 0 at the +y pole; p = NULL: the defaults)
     void set_environment(const float* rgb, int w, int h, const pt_environment_params* p = nullptr) { ck(pt_set_environment(ctx, rgb, w, h, p)); }
     void clear_environment() { ck(pt_clear_environment(ctx)); }
+    // vertex normals for smooth shading (set_option("smooth_normals", 1); render_nee only): normals = count x 9 floats, n1 n2 n3 per
+    // triangle in add order starting at first_triangle; compute_vertex_normals derives them per object (obj = -1: every object)
+    void set_vertex_normals(const float* normals, int64_t count, int64_t first_triangle = 0) { ck(pt_set_vertex_normals(ctx, first_triangle, count, normals)); }
+    void clear_vertex_normals() { ck(pt_clear_vertex_normals(ctx)); }
+    void compute_vertex_normals(float crease_degrees, int32_t obj = -1) { ck(pt_compute_vertex_normals(ctx, obj, crease_degrees)); }
     // guide buffers of the current view (pt_render_aovs) and the a-trous filter over them (pt_denoise; p = NULL: the defaults)
     // (the view of the last render: a new Camera(globals) would move a moving camera once more)
     void render_aovs(int subpixels = 1, int specular_depth = 4) {

@@ -46,6 +46,7 @@ EXPORTS = [
     "pt_generate_rays", "pt_trace_rays", "pt_render", "pt_render_adaptive", "pt_adaptive_defaults", "pt_render_adaptive_ex", "pt_read_sample_counts", "pt_read_tile_state", "pt_adaptive_rounds",
     "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
     "pt_render_nee", "pt_nee_rand", "pt_debug_light_table",
+    "pt_set_vertex_normals", "pt_clear_vertex_normals", "pt_compute_vertex_normals", "pt_debug_vertex_normals", "pt_debug_shading_normal",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
@@ -109,6 +110,11 @@ def _load():
     sig("pt_render_nee", C.c_int, vp, vp, i32, i32, i32)
     sig("pt_nee_rand", C.c_uint32, C.c_uint32, i32, i32)
     sig("pt_debug_light_table", C.c_int, vp, vp, vp, i64, C.POINTER(i64))
+    sig("pt_set_vertex_normals", C.c_int, vp, i64, i64, vp)
+    sig("pt_clear_vertex_normals", C.c_int, vp)
+    sig("pt_compute_vertex_normals", C.c_int, vp, i32, f32)
+    sig("pt_debug_vertex_normals", C.c_int, vp, vp, vp)
+    sig("pt_debug_shading_normal", C.c_int, vp, vp, i64, vp, vp)
     sig("pt_environment_defaults", None, vp)
     sig("pt_set_environment", C.c_int, vp, vp, i32, i32, vp)
     sig("pt_clear_environment", C.c_int, vp)
@@ -467,6 +473,37 @@ class Scene:
     def add_Obj(self, file, pos, scale, pitch, yaw):
         self._ck(LIB.pt_add_obj(self._h, os.fsencode(file), _f3(pos), _f3(scale), float(pitch), float(yaw)))
 
+    # -- vertex normals (option "smooth_normals"; authoring calls: host data, no BVH rebuild, packed for the device at the next
+    #    render_nee / render_adaptive(path="nee") / debug_shading_normals)
+    def set_vertex_normals(self, normals, first=0):
+        """normals (n, 3, 3): n1 n2 n3 of triangles [first, first + n) in add order; a triangle with a zero or non-finite normal has none."""
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 9)
+        self._ck(LIB.pt_set_vertex_normals(self._h, int(first), nrm.shape[0], _ptr(nrm)))
+
+    def clear_vertex_normals(self):
+        self._ck(LIB.pt_clear_vertex_normals(self._h))
+
+    def compute_vertex_normals(self, crease_degrees, obj=-1):
+        """Angle-weighted normals per corner over the triangles of the same object that share the position and lie within crease_degrees."""
+        self._ck(LIB.pt_compute_vertex_normals(self._h, int(obj), float(crease_degrees)))
+
+    def debug_vertex_normals(self):
+        """(normals (n, 3, 3) as recorded, has (n,) bool) per added triangle."""
+        nt = C.c_int64()
+        self._ck(LIB.pt_debug_scene_sizes(self._h, C.byref(nt), None, None))
+        nrm = np.zeros((nt.value, 3, 3), dtype=np.float32)
+        has = np.zeros(nt.value, dtype=np.int32)
+        self._ck(LIB.pt_debug_vertex_normals(self._h, _ptr(nrm), _ptr(has)))
+        return nrm, has.astype(bool)
+
+    def debug_shading_normals(self, rays):
+        """pt_debug_shading_normal: (add-order triangle or -1, (n, 4) float32 {Ns.xyz, t}) of each ray's closest hit."""
+        rays = np.ascontiguousarray(rays, dtype=RAY)
+        tri = np.empty(rays.shape[0], dtype=np.int32)
+        ns = np.empty((rays.shape[0], 4), dtype=np.float32)
+        self._ck(LIB.pt_debug_shading_normal(self._h, _ptr(rays), rays.shape[0], _ptr(tri), _ptr(ns)))
+        return tri, ns
+
     def upload_Triangles(self):
         self._ck(LIB.pt_upload_triangles(self._h))
 
@@ -477,9 +514,14 @@ class Scene:
         """Author a scenes.SceneSpec: materials, then one object per entry, then upload."""
         for m in spec.materials:
             self.add_Material(*m)
-        for verts, mati in spec.objects:
+        first = 0
+        normals = getattr(spec, "normals", None) or []
+        for k, (verts, mati) in enumerate(spec.objects):
             self.add_Triangles(triangles_from_vertices(verts, mati))
             self.end_Obj()
+            if k < len(normals) and normals[k] is not None:      # the object's vertex normals (n, 3, 3)
+                self.set_vertex_normals(normals[k], first=first)
+            first += int(np.asarray(verts).shape[0])
         self.upload_Triangles()
         self.upload_Materials()
         self.set_view(spec.fov, spec.yaw, spec.pitch, spec.shift)

@@ -842,6 +842,7 @@ int pt_end_obj(pt_context* ctx) {
     if (ro.degenerate) {
         ctx->tris.resize((size_t)ctx->tri_shift);
         ctx->enc_rank.resize((size_t)ctx->tri_shift);
+        if (ctx->vnormals.size() > (size_t)ctx->tri_shift * 9) ctx->vnormals.resize((size_t)ctx->tri_shift * 9);
         return fail(ctx, PT_ESCENE, "object has more than 6 triangles sharing one centroid: the reference's NodeOnHost::build (main.cpp:246-257) never terminates on it");
     }
     ctx->obj_begin.push_back(ctx->tri_shift);
@@ -1147,6 +1148,7 @@ int pt_upload_triangles(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
     ctx->aov_valid = false;          // the guides of pt_render_aovs describe the old scene
     ctx->nee_valid = false;          // and the light table its packed order
+    ctx->vnormals_dirty = true;      // and the packed vertex normals
     if (ctx->tri_shift != (int32_t)ctx->tris.size())
         return fail(ctx, PT_EINVAL, "triangles were added after the last end_Obj; close the object first (main.cpp:536)");
     const auto t0 = std::chrono::steady_clock::now();

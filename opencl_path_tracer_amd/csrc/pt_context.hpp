@@ -182,6 +182,14 @@ struct pt_context {
     float4* d_env_texels = nullptr;
     float* d_env_row_cdf = nullptr;
     float* d_env_col_cdf = nullptr;
+    // smooth shading (option smooth_normals, pt_set_vertex_normals; pinned in include/pt_api.h): 9 floats per add-order triangle as
+    // recorded, all zero where a triangle has none (shorter than tris: the rest has none).  d_vnormals: 3 float4 per packed triangle,
+    // packed by k_pack_vertex_normals (pt_smooth.hip) at the first smooth launch after the normals or the uploaded triangles changed
+    int smooth_normals = 0;
+    std::vector<float> vnormals;
+    bool vnormals_dirty = true;
+    float4* d_vnormals = nullptr;
+    size_t vnormals_cap = 0;           // packed triangles d_vnormals has room for
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -229,6 +237,8 @@ int light_table_ready(pt_context* ctx);                            // pt_host.cp
 float env_select(const pt_context* ctx, bool no_lights);           // pt_env.cpp: the effective P_env
 // pt_host.cpp: the light table on the device and the environment's view (*sky: a map with a distribution is set) for a launch_nee
 int nee_prepare(pt_context* ctx, int32_t strategy, NeeTable* lt, EnvView* env, bool* sky);
+// pt_host.cpp: the packed vertex normals on the device for a smooth launch (repacked if stale); *vn = null when the option is off, unless force
+int smooth_prepare(pt_context* ctx, const float4** vn, bool force = false);
 int host_threads(const pt_context* ctx);                          // threads of the host-side scene path (option build_threads)
 
 #define PT_HIP(ctx, call)                                                                   \

@@ -1090,9 +1090,33 @@ struct PathRegs {
 // The light hook of shade_hit: three points in the segment body where k_nee (pt_nee.hip) adds next-event estimation.  Every
 // statement that touches the hook sits under `if constexpr (HOOK::active)`, so the default instantiation (k_render, wf_shade)
 // compiles exactly as without it -- plain empty inline methods change k_render's register allocation.
+// A hook with `smooth` set also supplies the shading normal (option smooth_normals, pinned in include/pt_api.h): shading_normal()
+// below, the specular vertex with its fall-back to the geometric normal (spec_vertex), and the geometric normal for the offsets.
+// Every statement that does so sits under `if constexpr (HOOK::smooth)`.
 struct NoShadeHook {
     static constexpr bool active = false;
+    static constexpr bool smooth = false;
 };
+
+// The interpolated shading normal of a hit at hp = madd(D, t, P) on packed triangle ti (include/pt_api.h pins every operation): vn =
+// the packed vertex normals (k_pack_vertex_normals), N the record's normal, Ng = N flipped against the ray.  Ng itself -- the same
+// bits -- when the triangle has none, when the weighted sum cannot be normalised or when the result faces away from the ray.
+PT_DEV f3 shading_normal(const float4* __restrict__ vn, const float4* __restrict__ tris, int ti, f3 D, f3 hp, f3 N, f3 Ng) {
+    const float4 q1 = vn[(size_t)ti * 3], q2 = vn[(size_t)ti * 3 + 1], q3 = vn[(size_t)ti * 3 + 2];
+    if (q1.w == 0.0f) return Ng;
+    const float4 a = tris[ti * 3], b = tris[ti * 3 + 1], c = tris[ti * 3 + 2];
+    const f3 r1 = mk(a.x, a.y, a.z), r2 = mk(a.w, b.x, b.y), r3 = mk(b.z, b.w, c.x);
+    const float a1 = max0(dot3(cross3(r3 - r2, hp - r2), N));
+    const float a2 = max0(dot3(cross3(r1 - r3, hp - r3), N));
+    const float a3 = max0(dot3(cross3(r2 - r1, hp - r1), N));
+    const f3 s = madd(mk(q3.x, q3.y, q3.z), a3, madd(mk(q2.x, q2.y, q2.z), a2, mk(q1.x, q1.y, q1.z) * a1));
+    const float l2 = dot3(s, s);
+    if (!(l2 > 0.0f && l2 < __builtin_inff())) return Ng;
+    f3 Ns = s * (1.0f / __builtin_sqrtf(l2));
+    if (dot3(Ns, Ng) < 0.0f) Ns = -Ns;
+    if (!(dot3(-D, Ns) > 0.0f)) return Ng;
+    return Ns;
+}
 
 // one iteration body of prog.cl:317-366 for a ray that hit packed triangle `ti` at `t`
 // (SK: double-precision constants pinned to scalar registers, see KC)
@@ -1129,6 +1153,9 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     if (p.iterations == 1) st.setC((REC ? kd : ldf3(m->kd)) + ldf3(m->emission));        // prog.cl:323-325
     const bool flip = dot3(rD, N) > 0.0f;
     if (flip) N = -N;                                                       // prog.cl:326-328
+    // smooth shading: from here on N is the shading normal Ns; the hook keeps the geometric one (hook->Ng) for the offsets and the
+    // geometric-side rules
+    if constexpr (HOOK::smooth) N = hook->shading_normal_at(tris, ti, rD, hp, flip ? -N : N, N);
     // Every material that continues the path ends the same way: normalise the new direction, step off the surface
     // along +-N.  The two sampling branches below only produce the direction BEFORE normalisation and the side; the
     // tail is shared, so a wave that holds both kinds of hit runs one normalisation (IEEE sqrt + divide), not two.
@@ -1149,38 +1176,46 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         if constexpr (REC) dnew = diffuse_direction_rec<SK>(N, rec + (flip ? 4 : 2), rnd1, rnd2);
         else dnew = diffuse_direction<SK>(N, rnd1, rnd2);
     } else if (spec) {
-        // mirror (prog.cl:341-345) and dielectric (prog.cl:346-357, 228-245) share the Fresnel
-        // term and the mirror direction; the dielectric may pick the refracted direction instead.
-        const f3 oldD = rD;
-        const f3 F0 = ldf3(m->F0);
-        const f3 F = fresnel(F0, N, oldD);
-        dnew = oldD - (N * dot3(N, oldD)) * 2.0f;
-        if (type == 2) {
-            float n = m->n;
-            if (inside) n = 1.0f / n;
-            const float rnd = lcg_rand(seed);
-            const float cosa = dot3(-oldD, N);
-            const float disc = 1.0f - (fmaf_(-cosa, cosa, 1.0f) / n) / n;
-            const float prob = ((F.x + F.y) + F.z) / 3.0f;
-            const bool refr = disc > 0.0f && rnd > prob;
-            if (refr) {
-                const f3 dn = mk(oldD.x / n, oldD.y / n, oldD.z / n);
-                dnew = madd(N, cosa / n - sqrt_rn(disc), dn);
-                const float k = 1.0f / (1.0f - prob);
-                st.setR((st.R() * mk(1.0f - F.x, 1.0f - F.y, 1.0f - F.z)) * k);
-                inside = !inside;
-                side = -0.001f;
-            } else {
-                const float k = 1.0f / prob;
-                st.setR((st.R() * F) * k);
-            }
+        // smooth shading: the vertex as a function of the normal, which may have to run twice (TWIN: NeeHook::spec_vertex restates the
+        // branch below; a change to one belongs in the other)
+        if constexpr (HOOK::smooth) {
+            hook->spec_vertex(rD, st, seed, inside, m, type, N, &dnew, &side);
         } else {
-            st.setS(st.S() * F);
+            // mirror (prog.cl:341-345) and dielectric (prog.cl:346-357, 228-245) share the Fresnel
+            // term and the mirror direction; the dielectric may pick the refracted direction instead.
+            const f3 oldD = rD;
+            const f3 F0 = ldf3(m->F0);
+            const f3 F = fresnel(F0, N, oldD);
+            dnew = oldD - (N * dot3(N, oldD)) * 2.0f;
+            if (type == 2) {
+                float n = m->n;
+                if (inside) n = 1.0f / n;
+                const float rnd = lcg_rand(seed);
+                const float cosa = dot3(-oldD, N);
+                const float disc = 1.0f - (fmaf_(-cosa, cosa, 1.0f) / n) / n;
+                const float prob = ((F.x + F.y) + F.z) / 3.0f;
+                const bool refr = disc > 0.0f && rnd > prob;
+                if (refr) {
+                    const f3 dn = mk(oldD.x / n, oldD.y / n, oldD.z / n);
+                    dnew = madd(N, cosa / n - sqrt_rn(disc), dn);
+                    const float k = 1.0f / (1.0f - prob);
+                    st.setR((st.R() * mk(1.0f - F.x, 1.0f - F.y, 1.0f - F.z)) * k);
+                    inside = !inside;
+                    side = -0.001f;
+                } else {
+                    const float k = 1.0f / prob;
+                    st.setR((st.R() * F) * k);
+                }
+            } else {
+                st.setS(st.S() * F);
+            }
         }
     }
     if (lobe || spec) {
+        if constexpr (HOOK::smooth) hook->leaves_surface(lobe, dnew);           // a lobe direction below the geometric surface ends the path
         rD = normalize3(dnew);
-        rP = madd(N, side, hp);
+        if constexpr (HOOK::smooth) rP = madd(hook->geo(N), side, hp);
+        else rP = madd(N, side, hp);
     }
     if (type == 0) {
         const float idiff = max0(dot3(rD, N));

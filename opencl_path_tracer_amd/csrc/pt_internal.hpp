@@ -395,7 +395,13 @@ struct EnvView {
 };
 // env == nullptr: the instances without an environment.  tiled (the rounds of pt_render_adaptive_ex): k_nee_tiles / k_nee_env_tiles over
 // the p.n_tiles 8x8 frame tiles of p.tile_list (null: the frame's tiles in order), one lane per pixel of a tile; npix is then not read
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled = false);
+// vn != nullptr (option smooth_normals): the smooth instances, which shade with the interpolated normal of the packed vertex normals vn
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled = false,
+                      const float4* vn = nullptr);
+// smooth shading (pt_smooth.hip): add-order normals (9 floats per triangle, n_src triangles; the rest has none) -> 3 float4 per packed triangle
+hipError_t launch_pack_vertex_normals(const float* src, int64_t n_src, const int32_t* orig, int32_t n, float4* out, hipStream_t stream);
+hipError_t launch_debug_shading_normal(const RenderParams& p, const float4* vn, const pt_ray* rays, int64_t n, int32_t* out_tri, float4* out_ns, int cu_count,
+                                       hipStream_t stream);
 // the texel of unit direction (x, y, z): k_nee and pt_env_lookup
 __host__ __device__ __forceinline__ void env_texel(int32_t w, int32_t h, float yaw, float x, float y, float z, int32_t* row, int32_t* col) {
     const float theta = acosf(fminf(fmaxf(y, -1.0f), 1.0f));

@@ -366,6 +366,7 @@ int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
     if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_generate_rays: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
+    if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, "pt_generate_rays: option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     fill_params(ctx, cam, &p);
@@ -379,6 +380,7 @@ int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     if (rc != PT_OK) return rc;
     if (iterations < 0 || current_sample < 0) return fail(ctx, PT_EINVAL, "iterations/current_sample must be >= 0");
     if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_trace_rays: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
+    if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, "pt_trace_rays: option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
@@ -579,6 +581,7 @@ int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t
     if (rc != PT_OK) return rc;
     if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "iterations/nsamples must be >= 0");
     if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_render: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
+    if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, "pt_render: option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
     if (nsamples == 0) return PT_OK;
     PT_HIP(ctx, hipSetDevice(ctx->device));
@@ -643,6 +646,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
     if (!nee && ctx->env_set) return fail(ctx, PT_EINVAL, who + ": an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
+    if (!nee && ctx->smooth_normals) return fail(ctx, PT_EINVAL, who + ": option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
     if (!nee && ctx->variant != 0) return fail(ctx, PT_EINVAL, who + ": the megakernel (variant 0) only");
     if (ctx->world != 1) return fail(ctx, PT_EINVAL, who + ": contexts of one rank (world == 1) only");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
@@ -654,6 +658,8 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
     EnvView env;
     bool sky = false;
     if (nee && (rc = nee_prepare(ctx, ap->strategy, &lt, &env, &sky)) != PT_OK) return rc;
+    const float4* vn = nullptr;             // option smooth_normals: the packed vertex normals
+    if (nee && (rc = smooth_prepare(ctx, &vn)) != PT_OK) return rc;
     const int32_t n_frame = local_tiles(ctx);
     if (!ctx->d_adapt_spp) {
         PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_spp, sizeof(int32_t) * (size_t)n_frame));
@@ -687,7 +693,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
             pr.n_tiles = n_active;
             EventPair* ep;
             if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-            PT_HIP(ctx, launch_nee(pr, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, true));
+            PT_HIP(ctx, launch_nee(pr, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, true, vn));
             if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
         } else if ((rc = launch_megakernel(ctx, pr, list, n_active)) != PT_OK) {
             return rc;

@@ -41,10 +41,22 @@ struct EnvSlot<true> {
     EnvView v;
 };
 
+// what a hook carries for smooth shading (option smooth_normals): nothing without it
+template <bool SMOOTH>
+struct SmoothSlot {};
+template <>
+struct SmoothSlot<true> {
+    const float4* vn = nullptr;    // packed vertex normals (k_pack_vertex_normals, pt_smooth.hip)
+    int ti = 0;                    // the current vertex's packed triangle and whether its normal was flipped against the ray: the geometric
+    bool flip = false;             // normal Ng is read back from the packet where it is needed, not carried across the light sample's traversal
+    bool dead = false;             // a lobe vertex sampled a direction below the geometric surface: the path ends
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
-template <int MODE, bool ENV = false>
+template <int MODE, bool ENV = false, bool SMOOTH = false>
 struct NeeHook {
     static constexpr bool active = true;
+    static constexpr bool smooth = SMOOTH;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -56,6 +68,77 @@ struct NeeHook {
     bool after_lobe = false;       // the previous vertex was a lobe vertex (its flipped normal: Nprev)
     f3 Nprev = mk(0.f, 0.f, 0.f);
     EnvSlot<ENV> env;
+    SmoothSlot<SMOOTH> sm;
+
+    // the normal the offsets use: N itself, or under smooth shading (where N is the shading normal) the geometric one
+    PT_DEV f3 geo(f3 N) const {
+        if constexpr (SMOOTH) {
+            const float4 c = sv.tris[sm.ti * 3 + 2];
+            const f3 Ng = mk(c.y, c.z, c.w);
+            return sm.flip ? -Ng : Ng;
+        } else {
+            return N;
+        }
+    }
+    // SMOOTH: the shading normal of the hit (N the record's normal, Ng flipped against the ray); keeps Ng for the rest of the vertex
+    PT_DEV f3 shading_normal_at(const float4* __restrict__ tris, int ti, f3 rD, f3 hp, f3 N, f3 Ng) {
+        sm.ti = ti;
+        sm.flip = dot3(rD, N) > 0.0f;      // shade_hit's flip
+        return shading_normal(sm.vn, tris, ti, rD, hp, N, Ng);
+    }
+    // SMOOTH: a lobe vertex whose sampled direction (before normalisation) is not above the geometric surface ends the path
+    PT_DEV void leaves_surface(bool lobe, f3 dnew) {
+        if (lobe && dot3(dnew, geo(dnew)) <= 0.0f) sm.dead = true;
+    }
+    // SMOOTH: the mirror / dielectric vertex of shade_hit evaluated with Ns; if the direction it picks is on the wrong geometric side
+    // (a reflection not above, a refraction not below the surface), once more with Ng and the same LCG value, and that stands
+    // (TWIN of the specular branch of shade_hit: the same expressions in the same order)
+    template <class ST>
+    PT_DEV void spec_vertex(f3 oldD, ST& st, int& seed, bool& inside, const pt_material* __restrict__ m, int type, f3 Ns, f3* dnew, float* side) {
+        const f3 F0 = ldf3(m->F0);
+        float n = 1.0f, rnd = 0.0f;
+        if (type == 2) {
+            n = m->n;
+            if (inside) n = 1.0f / n;
+            rnd = lcg_rand(seed);
+        }
+        const f3 Ng = geo(Ns);
+        f3 F, d;
+        float prob = 0.0f;
+        bool refr = false;
+        auto eval = [&](f3 N) {
+            F = fresnel(F0, N, oldD);
+            d = oldD - (N * dot3(N, oldD)) * 2.0f;
+            refr = false;
+            if (type == 2) {
+                const float cosa = dot3(-oldD, N);
+                const float disc = 1.0f - (fmaf_(-cosa, cosa, 1.0f) / n) / n;
+                prob = ((F.x + F.y) + F.z) / 3.0f;
+                refr = disc > 0.0f && rnd > prob;
+                if (refr) {
+                    const f3 dn = mk(oldD.x / n, oldD.y / n, oldD.z / n);
+                    d = madd(N, cosa / n - sqrt_rn(disc), dn);
+                }
+            }
+        };
+        eval(Ns);
+        const float g = dot3(d, Ng);
+        if (refr ? g >= 0.0f : g <= 0.0f) eval(Ng);
+        *dnew = d;
+        if (type == 2) {
+            if (refr) {
+                const float k = 1.0f / (1.0f - prob);
+                st.setR((st.R() * mk(1.0f - F.x, 1.0f - F.y, 1.0f - F.z)) * k);
+                inside = !inside;
+                *side = -0.001f;
+            } else {
+                const float k = 1.0f / prob;
+                st.setR((st.R() * F) * k);
+            }
+        } else {
+            st.setS(st.S() * F);
+        }
+    }
 
     // the weight of an emitter hit's emission (at distance t, cosine inten, along rD)
     PT_DEV float emitter_weight(int ti, float t, float inten, f3 rD) const {
@@ -91,7 +174,7 @@ struct NeeHook {
         const f3 v1 = mk(a.x, a.y, a.z), v2 = mk(a.w, b.x, b.y), v3 = mk(b.z, b.w, cc.x), Ny = mk(cc.y, cc.z, cc.w);
         const float su = __builtin_sqrtf(u1);
         const f3 y = madd(v3 - v1, su * (1.0f - u2), madd(v2 - v1, u2 * su, v1));
-        const f3 o = madd(N, 0.001f, hp);
+        const f3 o = madd(geo(N), 0.001f, hp);
         const f3 d = y - o;
         const float r2 = dot3(d, d);
         const float r = __builtin_sqrtf(r2);
@@ -99,6 +182,7 @@ struct NeeHook {
         const float cosx = dot3(N, w), cosy = __builtin_fabsf(dot3(w, Ny));
         const float pl = lt.pdf_area[li] * r2 / cosy;
         if (!(cosx > 0.0f && cosy > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
+        if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // the sample must be above the geometric surface too
         if (shadow_hit<MODE>(sv, o, w, r * 1.0001f, stk, wc) != li) return;
         const float pb = cosx * kInvPi;
         const float q = pb / pl;
@@ -124,7 +208,7 @@ struct NeeHook {
     PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp) {
         const EnvView& ev = env.v;
         const float u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
-        const f3 o = madd(N, 0.001f, hp);
+        const f3 o = madd(geo(N), 0.001f, hp);
         f3 w, e;
         float limit, pl, g;            // the search's cut, p_l, the emitter's cosine (1 for the sky)
         int want;                      // what the shadow ray must return
@@ -186,6 +270,7 @@ struct NeeHook {
         }
         const float cosx = dot3(N, w);
         if (!(cosx > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
+        if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // as in light_sample
         if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
         const float pb = cosx * kInvPi;
         const float q = pb / pl;
@@ -236,13 +321,16 @@ struct NeeHook {
     }
 };
 
-template <int MODE, int BLOCK, bool ENV, bool TILED = false>
-PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix) {
+// SMOOTH (option smooth_normals; k_nee*_smooth below): the hook supplies the shading normal from the packed vertex normals vn; what it
+// adds here sits under `if constexpr (SMOOTH)`
+template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false>
+PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (ENV) {
         hook.env = env;
         hook.nee = lt.strategy != 0;       // the sky is a light (the host launches this instance only for a map with a distribution)
@@ -280,6 +368,7 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
         for (int s = p.first_sample; s < p.first_sample + p.nsamples; ++s) {
             hook.key = (unsigned)seed;
             hook.after_lobe = false;
+            if constexpr (SMOOTH) hook.sm.dead = false;
             PathRegs st;
             st.reset();
             bool inside = false;
@@ -296,6 +385,7 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
                 }
                 hook.k = k;
                 shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, t, &hook);
+                if constexpr (SMOOTH) if (hook.sm.dead) break;
             }
             acc = running_mean(acc, st.C(), s);
             if (p.moments) m2 = running_moment(m2, st.C(), s);
@@ -332,7 +422,49 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles(RenderParams p, NeeTabl
     nee_frame<MODE, BLOCK, true, true>(p, lt, EnvSlot<true>{env}, 0);
 }
 
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled) {
+// the smooth instances (option smooth_normals): the same four kernels with the packed vertex normals as one more argument
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_smooth(RenderParams p, NeeTable lt, const float4* vn, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true>(p, lt, EnvSlot<false>{}, npix, vn);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_smooth(RenderParams p, NeeTable lt, EnvView env, const float4* vn, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true>(p, lt, EnvSlot<true>{env}, npix, vn);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_smooth(RenderParams p, NeeTable lt, const float4* vn) {
+    nee_frame<MODE, BLOCK, false, true, true>(p, lt, EnvSlot<false>{}, 0, vn);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_smooth(RenderParams p, NeeTable lt, EnvView env, const float4* vn) {
+    nee_frame<MODE, BLOCK, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn);
+}
+
+// launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
+// of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
+// the staged treelet are sized for the workgroup at launch, as for every shape)
+template <class PICK, class... A>
+static hipError_t launch_lanes_env_tiles_smooth(PICK pick, const RenderParams& p, int64_t n, int cu_count, hipStream_t stream, A... args) {
+    if (n == 0) return hipSuccess;
+    switch (p.node_mode) {
+    case kNodesLds: return launch_lanes_t<kNodesLds, 512>(pick, p, n, cu_count, stream, args...);
+    case kNodesGlobal: return launch_lanes_t<kNodesGlobal, 256>(pick, p, n, cu_count, stream, args...);
+    case kNodesWide: return launch_lanes_t<kNodesWide, 256>(pick, p, n, cu_count, stream, args...);
+    case kNodesTreelet: return launch_lanes_t<kNodesTreelet, 512>(pick, p, n, cu_count, stream, args...);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled, const float4* vn) {
+    if (vn) {
+        if (tiled) {
+            const int64_t items = (int64_t)p.n_tiles * 64;
+            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_smooth<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn);
+            return launch_lanes([](auto s) { return k_nee_tiles_smooth<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn);
+        }
+        if (env) return launch_lanes([](auto s) { return k_nee_env_smooth<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, (long long)npix);
+        return launch_lanes([](auto s) { return k_nee_smooth<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, (long long)npix);
+    }
     if (tiled) {
         const int64_t items = (int64_t)p.n_tiles * 64;
         if (env) return launch_lanes([](auto s) { return k_nee_env_tiles<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env);

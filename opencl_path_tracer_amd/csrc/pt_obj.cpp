@@ -10,6 +10,9 @@
 //   * add_Obj itself: custom keys Kn / Kk (three floats, split on single blanks, atof) and
 //     Tp (atoi) are REQUIRED (main.cpp:568-571 uses .at()); x is negated, then rotate_x(pitch),
 //     rotate_y(yaw), scale, translate (main.cpp:598-606); one end_Obj per shape (main.cpp:615).
+// New (the reference throws vn away): a face whose corners all carry a vn index records those normals for its fan triangles
+// (pt_set_vertex_normals; include/pt_api.h), transformed by the inverse transpose of the positions' linear map.  The triangles
+// themselves are what they were.
 // Deviations, all turning undefined behaviour of the reference into errors: a missing
 // Kn/Kk/Tp, a face without usemtl (material id -1) and an empty shape return PT_EIO.
 #include "pt_internal.hpp"
@@ -189,7 +192,18 @@ void rot_y(float v[3], float beta) {    // main.cpp:55-62
     v[0] = r0; v[2] = r2;
 }
 
-struct Face3 { int v[3]; int mat; };
+constexpr int kNoVn = INT32_MIN;      // a face corner without a vn index
+// the vn of v//vn or v/vt/vn in the token at t (kNoVn: none)
+inline int parse_vn(const char* t) {
+    const char* e = t + std::strcspn(t, " \t");
+    const char* s1 = (const char*)std::memchr(t, '/', (size_t)(e - t));
+    if (!s1) return kNoVn;
+    const char* s2 = (const char*)std::memchr(s1 + 1, '/', (size_t)(e - (s1 + 1)));
+    if (!s2 || s2 + 1 >= e) return kNoVn;
+    return parse_int(s2 + 1);
+}
+
+struct Face3 { int v[3]; int mat; int vn[3]; };      // vn: resolved index, or -1
 struct Shape { std::vector<Face3> faces; };
 
 // run fn(begin, end) over [0, n) on up to 16 threads (element-wise work: any split gives the same result)
@@ -231,13 +245,13 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
     // triangulate = true) when the material changes, at g / o and at the end of the file; g / o keeps the shape only if
     // the group it closes is not empty (tiny_obj_loader.h:1509-1567) -- faces exported by an earlier usemtl are lost
     // with it, which B reproduces.  A face of fewer than three vertices opens the group and exports nothing.
-    struct RawTri { int idx[3]; int nv_local; };
+    struct RawTri { int idx[3]; int nv_local; int vn[3]; int nvn_local; };
     enum { kEvUsemtl = 0, kEvMtllib = 1, kEvShape = 2, kEvShortFace = 3 };
     struct Event { int kind; size_t tri_pos; std::string name; };
     struct Piece {
         char* begin = nullptr;
         char* end = nullptr;
-        std::vector<float> v;
+        std::vector<float> v, vn;
         std::vector<RawTri> tris;
         std::vector<Event> ev;
     };
@@ -279,16 +293,25 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
                 pc.v.push_back(p[0]); pc.v.push_back(p[1]); pc.v.push_back(p[2]);
                 continue;
             }
+            if (t[0] == 'v' && t[1] == 'n' && is_space(t[2])) {
+                t += 3;
+                float p[3];
+                parse_float3(p, &t);
+                pc.vn.push_back(p[0]); pc.vn.push_back(p[1]); pc.vn.push_back(p[2]);
+                continue;
+            }
             if (t[0] == 'f' && is_space(t[1])) {
                 t += 2;
                 t += std::strspn(t, " \t");
-                const int nv_local = (int)(pc.v.size() / 3);
-                int first = 0, prev = 0, count = 0;
+                const int nv_local = (int)(pc.v.size() / 3), nvn_local = (int)(pc.vn.size() / 3);
+                int first = 0, prev = 0, count = 0, nfirst = kNoVn, nprev = kNoVn;
                 while (*t != '\0') {
                     const int idx = parse_int(t);                         // the v of v, v/vt, v//vn, v/vt/vn
-                    if (count == 0) first = idx;
-                    else if (count >= 2) pc.tris.push_back(RawTri{{first, prev, idx}, nv_local});   // fan: (first, previous, this)
+                    const int nidx = parse_vn(t);
+                    if (count == 0) { first = idx; nfirst = nidx; }
+                    else if (count >= 2) pc.tris.push_back(RawTri{{first, prev, idx}, nv_local, {nfirst, nprev, nidx}, nvn_local});   // fan: (first, previous, this)
                     prev = idx;
+                    nprev = nidx;
                     ++count;
                     t += std::strcspn(t, " \t");
                     t += std::strspn(t, " \t");
@@ -304,7 +327,7 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
                 continue;
             }
             if ((t[0] == 'g' || t[0] == 'o') && is_space(t[1])) pc.ev.push_back(Event{kEvShape, pc.tris.size(), std::string()});
-            // vn, vt, s, t ...: nothing add_Obj reads
+            // vt, s, t ...: nothing add_Obj reads
         }
     };
     {
@@ -335,10 +358,11 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
     shape_kept.push_back(0);
     bool group_open = false;
     int material = -1;
-    std::vector<size_t> vbase(n_pieces + 1, 0);
+    std::vector<size_t> vbase(n_pieces + 1, 0), vnbase(n_pieces + 1, 0);
     for (size_t k = 0; k < n_pieces; ++k) {
         const Piece& pc = pieces[k];
         vbase[k + 1] = vbase[k] + pc.v.size() / 3;
+        vnbase[k + 1] = vnbase[k] + pc.vn.size() / 3;
         size_t at = 0;
         auto close_run = [&](size_t upto) {
             if (upto > at) {
@@ -371,7 +395,7 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
     shape_kept.back() = (group_open || shape_tris.back() != 0) ? 1 : 0;     // end of file: tiny_obj_loader.h flushes the pending group
 
     // C: vertices in file order, triangles into their shapes
-    std::vector<float> v(vbase[n_pieces] * 3);
+    std::vector<float> v(vbase[n_pieces] * 3), vn(vnbase[n_pieces] * 3);
     std::vector<Shape> shapes;
     std::vector<size_t> shape_slot(shape_tris.size(), (size_t)-1);
     for (size_t sidx = 0; sidx < shape_tris.size(); ++sidx)
@@ -383,6 +407,8 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
     parallel_ranges(n_pieces, 1, [&](size_t b, size_t e) {
         for (size_t k = b; k < e; ++k)
             if (!pieces[k].v.empty()) std::memcpy(&v[vbase[k] * 3], pieces[k].v.data(), sizeof(float) * pieces[k].v.size());
+        for (size_t k = b; k < e; ++k)
+            if (!pieces[k].vn.empty()) std::memcpy(&vn[vnbase[k] * 3], pieces[k].vn.data(), sizeof(float) * pieces[k].vn.size());
     });
     parallel_ranges(runs.size(), 1, [&](size_t b, size_t e) {
         for (size_t r = b; r < e; ++r) {
@@ -394,6 +420,7 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
             for (size_t i = run.tri_begin; i < run.tri_end; ++i, ++out) {
                 const RawTri& rt = pc.tris[i];
                 for (int c = 0; c < 3; ++c) out->v[c] = fix_index(rt.idx[c], vb + rt.nv_local);
+                for (int c = 0; c < 3; ++c) out->vn[c] = rt.vn[c] == kNoVn || rt.vn[c] == 0 ? -1 : fix_index(rt.vn[c], (int)vnbase[run.piece] + rt.nvn_local);
                 out->mat = run.material;
             }
         }
@@ -432,6 +459,20 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
         }
     });
 
+    // ---- normals: the inverse transpose of that linear map -- negate x, rotate_x(pitch), rotate_y(yaw), divide by scale -- in double
+    const size_t nnorm = vn.size() / 3;
+    std::vector<float> wn(vn.size());
+    {
+        const double gx = (double)(pitch / 180.0f * 3.141593f), gy = (double)(yaw / 180.0f * 3.141593f);      // the angles rot_x / rot_y use
+        const double cx = std::cos(gx), sx = std::sin(gx), cy = std::cos(gy), sy = std::sin(gy);
+        for (size_t i = 0; i < nnorm; ++i) {
+            const double x0 = -(double)vn[3 * i], y0 = vn[3 * i + 1], z0 = vn[3 * i + 2];
+            const double y1 = y0 * cx - z0 * sx, z1 = y0 * sx + z0 * cx;
+            const double q[3] = {(x0 * cy + z1 * sy) / (double)scale[0], y1 / (double)scale[1], (-x0 * sy + z1 * cy) / (double)scale[2]};
+            const double l = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+            for (int a = 0; a < 3; ++a) wn[3 * i + a] = l > 0.0 && std::isfinite(l) ? (float)(q[a] / l) : 0.0f;
+        }
+    }
     clk.lap("transform vertices");
     // ---- shapes, main.cpp:587-616: one add_Triangle per face, one end_Obj per shape
     for (const Shape& sh : shapes) {
@@ -456,6 +497,22 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
             }
         });
         clk.lap("triangle records (add_Triangle)");
+        bool any_vn = false;
+        for (size_t i = 0; i < nf && !any_vn; ++i) any_vn = sh.faces[i].vn[0] >= 0;
+        if (any_vn) {
+            int64_t ntris = 0;
+            pt_debug_scene_sizes(ctx, &ntris, nullptr, nullptr);
+            std::vector<float> fn(nf * 9, 0.0f);
+            for (size_t i = 0; i < nf; ++i) {
+                const Face3& f = sh.faces[i];
+                bool all = true;
+                for (int k = 0; k < 3; ++k) all = all && f.vn[k] >= 0 && (size_t)f.vn[k] < nnorm;
+                if (!all) continue;
+                for (int k = 0; k < 3; ++k) std::memcpy(&fn[i * 9 + 3 * (size_t)k], &wn[3 * (size_t)f.vn[k]], sizeof(float) * 3);
+            }
+            rc = pt_set_vertex_normals(ctx, ntris - (int64_t)nf, (int64_t)nf, fn.data());
+            if (rc != PT_OK) return rc;
+        }
         rc = pt_end_obj(ctx);
         if (rc != PT_OK) return rc;
         clk.lap("pt_end_obj");

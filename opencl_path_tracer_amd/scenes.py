@@ -34,6 +34,7 @@ class SceneSpec:
     pitch: float = 0.0
     shift: tuple = (0.0, 0.0, 0.0)
     name: str = ""
+    normals: list = field(default_factory=list)      # optional, per object: vertex normals (n,3,3) f32 or None (Scene.load applies them)
 
     @property
     def ntris(self):
@@ -97,15 +98,25 @@ def uv_sphere(center, radius, segments=32, rings=16):
     return np.asarray(tris, dtype=np.float64).astype(np.float32)
 
 
-def cornell_box(segments=32, rings=16):
+def uv_sphere_normals(center, radius, segments=32, rings=16):
+    """The analytic normals (v - c) / r of uv_sphere's corners, (n, 3, 3) float32, for Scene.set_vertex_normals."""
+    v = uv_sphere(center, radius, segments, rings).astype(np.float64)
+    return ((v - np.asarray(center, dtype=np.float64)) / float(radius)).astype(np.float32)
+
+
+def cornell_box(segments=32, rings=16, smooth=False):
     """Scene CB of SURVEY 8(d): 12 wall/lamp triangles + two tessellated spheres
-    (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects."""
+    (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects.
+    smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals)."""
     spec = SceneSpec(materials=list(BUILTIN_MATERIALS), name="cornell_box")
     spec.objects.append(cornell_walls())
     s1 = uv_sphere((250.0, 200.0, 300.0), 200.0, segments, rings)
     spec.objects.append((s1, np.full(s1.shape[0], CHROMIUM, dtype=np.uint16)))
     s2 = uv_sphere((750.0, 200.0, -200.0), 200.0, segments, rings)
     spec.objects.append((s2, np.full(s2.shape[0], GLASS, dtype=np.uint16)))
+    if smooth:
+        spec.normals = [None, uv_sphere_normals((250.0, 200.0, 300.0), 200.0, segments, rings),
+                        uv_sphere_normals((750.0, 200.0, -200.0), 200.0, segments, rings)]
     return spec
 
 

@@ -1,6 +1,9 @@
 """Next-event estimation (render_nee): rate, kernel time per path segment, and what each strategy buys in RMSE.
 
-usage: python tools/nee_bench.py [scene=cornell|walls|mesh100k|all] [W=1920 H=1080] [bounces=8] [ref=4096] [spp=64] [out=DIR]
+usage: python tools/nee_bench.py [--smooth] [scene=cornell|walls|mesh100k|all] [W=1920 H=1080] [bounces=8] [ref=4096] [spp=64] [quality=1] [out=DIR]
+
+--smooth: the Cornell box carries its spheres' analytic vertex normals and render_nee runs with option smooth_normals = 1 (render(),
+which refuses under the option, runs with it off); quality=0 skips the reference frame and the RMSE curve (rates only).
 
 One JSON line per scene on stdout; with out=DIR also DIR/<scene>_<W>x<H>.json.
 
@@ -26,9 +29,9 @@ from opencl_path_tracer_amd import api, scenes  # noqa: E402
 STRATEGIES = ("bsdf", "light", "mis")
 
 
-def scene_spec(name):
+def scene_spec(name, smooth=False):
     if name == "cornell":
-        return scenes.cornell_box()
+        return scenes.cornell_box(smooth=smooth)
     if name == "walls":
         spec = scenes.SceneSpec(materials=list(scenes.BUILTIN_MATERIALS), name="cornell_walls")
         spec.objects.append(scenes.cornell_walls())
@@ -65,10 +68,15 @@ def timed(sc, fn, setup, reps=3):
     return float(np.median(ev)), float(np.median(kern))
 
 
-def run_scene(name, W, H, bounces, ref_spp, spp):
-    spec = scene_spec(name)
+def run_scene(name, W, H, bounces, ref_spp, spp, smooth=False, quality=True):
+    spec = scene_spec(name, smooth)
     npix = W * H
-    res = {"scene": name, "W": W, "H": H, "bounces": bounces, "ref_spp": ref_spp, "rate_spp": spp}
+    res = {"scene": name, "W": W, "H": H, "bounces": bounces, "ref_spp": ref_spp, "rate_spp": spp, "smooth": bool(smooth)}
+
+    def nee(sc, n, s):
+        sc.set_option("smooth_normals", 1 if smooth else 0)
+        sc.render_nee(n, s)
+        sc.set_option("smooth_normals", 0)
 
     def ctx(seed=None):
         sc = api.Scene(W, H, device=0).load(spec)
@@ -77,10 +85,15 @@ def run_scene(name, W, H, bounces, ref_spp, spp):
             sc.upload_seeds(np.random.default_rng(seed).integers(1, 2 ** 31 - 2, npix).astype(np.int32))
         return sc
 
-    sc = ctx(seed=12345)
-    sc.render(ref_spp)
-    gt = sc.read_colors()
-    sc.close()
+    gt = None
+    if quality:
+        sc = ctx(seed=12345)
+        if smooth:
+            nee(sc, ref_spp, "mis")            # the reference of a smooth frame is a smooth frame
+        else:
+            sc.render(ref_spp)
+        gt = sc.read_colors()
+        sc.close()
     sc = ctx()
     res["lights"] = int(len(sc.debug_light_table()[0]))
 
@@ -101,9 +114,11 @@ def run_scene(name, W, H, bounces, ref_spp, spp):
         rates[key] = {"ms": ms, "kernel_ms": kms, "msamples_s": npix * spp / (ms * 1e-3) / 1e6, "ns_per_segment": ms * 1e6 / segs}
     rate("render", lambda: sc.render(spp))
     for s in STRATEGIES:
-        rate("nee_" + s, lambda s=s: sc.render_nee(spp, s))
+        rate("nee_" + s, lambda s=s: nee(sc, spp, s))
     res["rates"] = rates
     sc.close()
+    if not quality:
+        return res
 
     # ---- quality
     curve = {}
@@ -114,7 +129,7 @@ def run_scene(name, W, H, bounces, ref_spp, spp):
             if s == "render":
                 sc.render(n)
             else:
-                sc.render_nee(n, s)
+                nee(sc, n, s)
             e = rmse(sc.read_colors(), gt)
             t = rates["render" if s == "render" else "nee_" + s]["ms"] * n / spp
             row[s] = {"rmse": e, "ms": t, "efficiency": 1.0 / (e * e * t * 1e-3)}
@@ -129,7 +144,8 @@ def run_scene(name, W, H, bounces, ref_spp, spp):
 
 
 def main():
-    a = dict(kv.split("=", 1) for kv in sys.argv[1:])
+    smooth = "--smooth" in sys.argv[1:]
+    a = dict(kv.split("=", 1) for kv in sys.argv[1:] if kv != "--smooth")
     names = ["cornell", "walls", "mesh100k"] if a.get("scene", "all") == "all" else [a["scene"]]
     W, H, B = int(a.get("W", 1920)), int(a.get("H", 1080)), int(a.get("bounces", 8))
     ref, spp = int(a.get("ref", 4096)), int(a.get("spp", 64))
@@ -137,10 +153,10 @@ def main():
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     for name in names:
-        r = run_scene(name, W, H, B, ref, spp)
+        r = run_scene(name, W, H, B, ref, spp, smooth, int(a.get("quality", 1)) != 0)
         print(json.dumps(r), flush=True)
         if out_dir:
-            with open(os.path.join(out_dir, "%s_%dx%d.json" % (name, W, H)), "w") as f:
+            with open(os.path.join(out_dir, "%s%s_%dx%d.json" % (name, "_smooth" if smooth else "", W, H)), "w") as f:
                 json.dump(r, f, indent=1)
 
 
