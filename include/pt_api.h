@@ -325,6 +325,69 @@ int pt_debug_vertex_normals(const pt_context* ctx, float* normals, int32_t* has)
  * out_tri[i] = add-order triangle or -1, out_ns[4 i ..] = {Ns.xyz, t} ({0, 0, 0, -1} for a miss) */
 int pt_debug_shading_normal(pt_context* ctx, const pt_ray* rays, int64_t n, int32_t* out_tri, float* out_ns);
 
+/* ---- albedo textures with UV coordinates for pt_render_nee (new: opt-in with option "textures"; the reference has one kd per
+ * material and throws vt / map_Kd away) -----------
+ * Authoring (host data; all of it works on a host-only context, none of it rebuilds the BVH).
+ * Textures.  pt_add_texture returns the new texture's index (0, 1, ...) or a negative code.  rgb = w x h x 3 floats, ROW 0 IS THE TOP of
+ * the image (where v is just below 1); p = NULL: pt_texture_defaults = {filter 1, srgb 0}.  filter 0 = nearest, 1 = bilinear; srgb = 1
+ * applies the sRGB EOTF on the host first: c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4), in double, rounded to float.
+ * PT_EINVAL: w or h below 1 or above PT_TEX_MAX_SIZE, already PT_TEX_MAX_COUNT textures, a texel that is not finite, negative or above
+ * 65504 (with srgb = 1 also after the EOTF), filter or srgb outside {0, 1}, more than 2^31 - 1 texels over all textures.  Stored form (host and device): a texel is 8 bytes, three
+ * IEEE half values r g b (each the float rounded to nearest-even) and 16 zero bits; all textures live in one device buffer, each with a
+ * descriptor {first texel, w, h, filter}.  Textures and bindings survive pt_upload_triangles / pt_upload_materials.
+ *   pt_clear_textures          drops all textures and all bindings
+ *   pt_set_material_texture    binds texture (an index, or -1: none) to a material added so far; PT_EINVAL when either index is out of
+ *                              range.  A binding on a material whose type is not 0 is accepted and ignored
+ *   pt_debug_texture           the stored halves widened to float: *w, *h, *filter (any may be NULL); with rgb != NULL w x h x 3 floats,
+ *                              cap = the texels rgb holds (PT_EINVAL when too small)
+ * UV coordinates.  Triangles are counted in add order over the whole scene, as for pt_set_vertex_normals; the range rules are the same.
+ * A triangle HAS uvs iff all six values recorded for it are finite and at most 65536 in magnitude; every other triangle has none.
+ *   pt_set_vertex_uvs          uvs = count x 6 floats, u1 v1 u2 v2 u3 v3 per triangle, for triangles [first_triangle, first_triangle + count)
+ *   pt_clear_vertex_uvs        no triangle has uvs
+ *   pt_debug_vertex_uvs        uvs: 6 floats per added triangle as recorded where it has uvs, 0 where it has none; has: 1 / 0; either may be NULL
+ *   pt_add_obj                 parses vt u v [w]; a face whose corners all carry a vt index that exists (i/j, i/j/k; the index rules of v)
+ *                              records those uvs for its fan triangles.  map_Kd <file> in the MTL: the last blank-separated token is
+ *                              the file name, resolved against the MTL's directory; a line with a -option token is skipped; .ppm (binary
+ *                              P6, srgb = 1) and .pfm (srgb = 0, rows flipped to top-first) load with filter 1, extensions compared
+ *                              without case, each file once per call, and the texture is bound to the material pt_add_obj creates.  Any
+ *                              other extension or a read failure leaves the material untextured and pt_add_obj succeeds (statistics
+ *                              "obj_textures_loaded" / "obj_textures_skipped" count the map_Kd lines of the last pt_add_obj either way).
+ *                              Triangles and material records are what they were.
+ * Bindings, textures and uvs take effect LAZILY: the first textured launch after any of them, the uploaded triangles or the uploaded
+ * materials changed copies them to the device on the context's stream and runs k_pack_vertex_uvs (pt_texture.hip): per PACKED
+ * triangle two float4 {u1, v1, u2, v2}, {u3, v3, flag, 0}, flag != 0 iff the triangle has uvs.
+ * Option "textures" = 1 (default 0: every path computes what it computed before, bit for bit): pt_render_nee (every strategy, with and
+ * without an environment, with and without smooth_normals) and pt_render_adaptive_ex with path PT_ADAPT_PATH_NEE use the textured
+ * albedo; pt_render, pt_generate_rays, pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex with PT_ADAPT_PATH_RENDER return
+ * PT_EINVAL naming the option.  pt_render_aovs, the denoisers and pt_temporal_accumulate keep the material's kd.
+ * The textured albedo kd' of a hit at hp = madd(D, t, P) on packed triangle ti whose material has type 0 and texture T bound and which
+ * has uvs (float32; fma as dot3 / cross3 / madd have it, see the smooth-normals block above):
+ *   a1, a2, a3 = the three weights of the shading normal above (max0 included), A = (a1 + a2) + a3; not 0 < A < inf: kd' = kd;
+ *   inv = 1.0f / A (IEEE); u = fmaf(u3, a3, fmaf(u2, a2, u1 * a1)) * inv, v likewise; fu = u - floorf(u), fv = v - floorf(v) (repeat);
+ *   nearest:  x = min(w - 1, (int)floorf(fu * w)), y = min(h - 1, (int)floorf((1.0f - fv) * h)), tex = texel(x, y);
+ *   bilinear: px = fmaf(fu, w, -0.5f), x0 = floorf(px), tx = px - x0, columns ((int)x0 mod w + w) mod w and the next one mod w; rows the
+ *             same with py = fmaf(1.0f - fv, h, -0.5f); per channel top = fmaf(tx, c10 - c00, c00), bot = fmaf(tx, c11 - c01, c01),
+ *             tex = fmaf(ty, bot - top, top)  (cXY: column X, row Y of the 2 x 2 taps);
+ *   kd' = kd * tex, component-wise; kd is the value the untextured vertex uses.
+ * Every other case -- option off, no texture bound, no uvs, a type other than 0 -- yields kd, the same bits.  kd' replaces kd in the
+ * preview colour of iterations == 1 (kd' + emission), in the factor_L update of the type-0 vertex and in fL' of that vertex's light
+ * sample (triangle light and sky), and nowhere else: ks, emission and the light table are untouched, and no LCG draw and no pt_nee_rand
+ * value depends on kd', so a textured frame leaves rnds and rays as the untextured frame does. */
+typedef struct { int32_t filter, srgb; } pt_texture_params;
+#define PT_TEX_MAX_SIZE 8192
+#define PT_TEX_MAX_COUNT 1024
+void pt_texture_defaults(pt_texture_params* p);
+int pt_add_texture(pt_context* ctx, const float* rgb, int32_t w, int32_t h, const pt_texture_params* p);
+int pt_clear_textures(pt_context* ctx);
+int pt_set_material_texture(pt_context* ctx, int32_t material, int32_t texture);
+int pt_debug_texture(const pt_context* ctx, int32_t texture, float* rgb, int64_t cap, int32_t* w, int32_t* h, int32_t* filter);
+int pt_set_vertex_uvs(pt_context* ctx, int64_t first_triangle, int64_t count, const float* uvs);
+int pt_clear_vertex_uvs(pt_context* ctx);
+int pt_debug_vertex_uvs(const pt_context* ctx, float* uvs, int32_t* has);
+/* the albedo of the closest hit of each ray, by the device function the textured k_nee instances call (any setting of the option):
+ * out_tri[i] = add-order triangle or -1, out_rgbt[4 i ..] = {kd'.rgb, t} ({0, 0, 0, -1} for a miss) */
+int pt_debug_albedo(pt_context* ctx, const pt_ray* rays, int64_t n, int32_t* out_tri, float* out_rgbt);
+
 /* ---- per-pixel variance of the mean luminance (new: opt-in with option "moments"; the reference keeps the mean only) -------
  * With option "moments" = 1 every render path (pt_render in every variant, schedule and node mode, pt_trace_rays,
  * pt_render_adaptive, pt_render_nee, tiled ranks) also folds each sample's squared luminance into colors[].w, float32 in this order:
@@ -482,6 +545,10 @@ int pt_image_write_ppm(const char* path, const float* rgba, int32_t width, int32
  * != NULL the pixels in the file's row order (the writer's: row 0 = bottom; flip the rows for a map whose row 0 is the +y pole),
  * float3 @ 16 B with .w = 0; cap = the pixels rgba_out holds (PT_EINVAL when too small).  PT_EIO: unreadable, mis-headed or truncated */
 int pt_image_read_pfm(const char* path, float* rgba_out, int64_t cap, int32_t* width, int32_t* height);
+/* Reads a binary PPM (P6; `#` comments in the header; maxval 1..65535, two-byte samples big-endian above 255): *width, *height from the
+ * header; with rgb_out != NULL the pixels top row first as 3 floats each, sample / maxval (a float division), no colour transform; cap =
+ * the pixels rgb_out holds (PT_EINVAL when too small).  PT_EIO: unreadable, mis-headed or truncated */
+int pt_image_read_ppm(const char* path, float* rgb_out, int64_t cap, int32_t* width, int32_t* height);
 
 /* ---- plumbing: device memory, streams, options, statistics --------------------------- */
 /* Use caller-owned device buffers (e.g. torch tensors) for colors (16 B/px) and rnds (4 B/px)

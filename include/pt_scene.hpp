@@ -127,6 +127,16 @@ public:
     void set_vertex_normals(const float* normals, int64_t count, int64_t first_triangle = 0) { ck(pt_set_vertex_normals(ctx, first_triangle, count, normals)); }
     void clear_vertex_normals() { ck(pt_clear_vertex_normals(ctx)); }
     void compute_vertex_normals(float crease_degrees, int32_t obj = -1) { ck(pt_compute_vertex_normals(ctx, obj, crease_degrees)); }
+    // albedo textures (set_option("textures", 1); render_nee only): rgb = w x h x 3 floats, row 0 at the top (p = NULL: bilinear, linear);
+    // a texture is bound to a type-0 material (texture = -1: none); uvs = count x 6 floats, u1 v1 u2 v2 u3 v3 per triangle in add order
+    int add_texture(const float* rgb, int w, int h, const pt_texture_params* p = nullptr) { return ck(pt_add_texture(ctx, rgb, w, h, p)); }
+    void clear_textures() { ck(pt_clear_textures(ctx)); }
+    void set_material_texture(int32_t material, int32_t texture) { ck(pt_set_material_texture(ctx, material, texture)); }
+    void set_vertex_uvs(const float* uvs, int64_t count, int64_t first_triangle = 0) { ck(pt_set_vertex_uvs(ctx, first_triangle, count, uvs)); }
+    void clear_vertex_uvs() { ck(pt_clear_vertex_uvs(ctx)); }
+    void debug_vertex_uvs(float* uvs, int32_t* has) { ck(pt_debug_vertex_uvs(ctx, uvs, has)); }
+    void debug_texture(int32_t texture, float* rgb, int64_t cap, int32_t* w, int32_t* h, int32_t* filter) { ck(pt_debug_texture(ctx, texture, rgb, cap, w, h, filter)); }
+    void debug_albedo(const pt_ray* rays, int64_t n, int32_t* out_tri, float* out_rgbt) { ck(pt_debug_albedo(ctx, rays, n, out_tri, out_rgbt)); }
     // guide buffers of the current view (pt_render_aovs) and the a-trous filter over them (pt_denoise; p = NULL: the defaults)
     // (the view of the last render: a new Camera(globals) would move a moving camera once more)
     void render_aovs(int subpixels = 1, int specular_depth = 4) {

@@ -47,6 +47,8 @@ EXPORTS = [
     "pt_set_current_sample", "pt_get_current_sample", "pt_sync",
     "pt_render_nee", "pt_nee_rand", "pt_debug_light_table",
     "pt_set_vertex_normals", "pt_clear_vertex_normals", "pt_compute_vertex_normals", "pt_debug_vertex_normals", "pt_debug_shading_normal",
+    "pt_texture_defaults", "pt_add_texture", "pt_clear_textures", "pt_set_material_texture", "pt_debug_texture",
+    "pt_set_vertex_uvs", "pt_clear_vertex_uvs", "pt_debug_vertex_uvs", "pt_debug_albedo", "pt_image_read_ppm",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
@@ -115,6 +117,16 @@ def _load():
     sig("pt_compute_vertex_normals", C.c_int, vp, i32, f32)
     sig("pt_debug_vertex_normals", C.c_int, vp, vp, vp)
     sig("pt_debug_shading_normal", C.c_int, vp, vp, i64, vp, vp)
+    sig("pt_texture_defaults", None, vp)
+    sig("pt_add_texture", C.c_int, vp, vp, i32, i32, vp)
+    sig("pt_clear_textures", C.c_int, vp)
+    sig("pt_set_material_texture", C.c_int, vp, i32, i32)
+    sig("pt_debug_texture", C.c_int, vp, i32, vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32))
+    sig("pt_set_vertex_uvs", C.c_int, vp, i64, i64, vp)
+    sig("pt_clear_vertex_uvs", C.c_int, vp)
+    sig("pt_debug_vertex_uvs", C.c_int, vp, vp, vp)
+    sig("pt_debug_albedo", C.c_int, vp, vp, i64, vp, vp)
+    sig("pt_image_read_ppm", C.c_int, C.c_char_p, vp, i64, C.POINTER(i32), C.POINTER(i32))
     sig("pt_environment_defaults", None, vp)
     sig("pt_set_environment", C.c_int, vp, vp, i32, i32, vp)
     sig("pt_clear_environment", C.c_int, vp)
@@ -288,6 +300,21 @@ def environment_defaults():
     return p.as_dict()
 
 
+class TextureParams(C.Structure):
+    """pt_texture_params (include/pt_api.h): filter 0 nearest / 1 bilinear, srgb 1 = the texels are sRGB-encoded."""
+    _fields_ = [("filter", C.c_int32), ("srgb", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def texture_defaults():
+    """pt_texture_defaults as a dict: filter, srgb."""
+    p = TextureParams()
+    LIB.pt_texture_defaults(C.byref(p))
+    return p.as_dict()
+
+
 def env_lookup(w, h, yaw_degrees, direction):
     """pt_env_lookup: (row, col) of the texel a unit direction reads in a w x h lat-long map (include/pt_api.h pins the mapping)."""
     row, col = C.c_int32(), C.c_int32()
@@ -393,6 +420,20 @@ def read_pfm(path):
         raise PtError(rc, "cannot read %s" % path)
     out = np.empty((h.value, w.value, 4), dtype=np.float32)
     rc = LIB.pt_image_read_pfm(os.fsencode(path), _ptr(out), w.value * h.value, C.byref(w), C.byref(h))
+    if rc != PT_OK:
+        raise PtError(rc, "cannot read %s" % path)
+    return out
+
+
+def read_ppm(path):
+    """pt_image_read_ppm: (height, width, 3) float32, sample / maxval, top row first (what Scene.add_texture takes; srgb=1 for an
+    8-bit picture)."""
+    w, h = C.c_int32(), C.c_int32()
+    rc = LIB.pt_image_read_ppm(os.fsencode(path), None, 0, C.byref(w), C.byref(h))
+    if rc != PT_OK:
+        raise PtError(rc, "cannot read %s" % path)
+    out = np.empty((h.value, w.value, 3), dtype=np.float32)
+    rc = LIB.pt_image_read_ppm(os.fsencode(path), _ptr(out), w.value * h.value, C.byref(w), C.byref(h))
     if rc != PT_OK:
         raise PtError(rc, "cannot read %s" % path)
     return out
@@ -504,6 +545,61 @@ class Scene:
         self._ck(LIB.pt_debug_shading_normal(self._h, _ptr(rays), rays.shape[0], _ptr(tri), _ptr(ns)))
         return tri, ns
 
+    # -- albedo textures and uvs (option "textures"; authoring calls: host data, no BVH rebuild, copied to the device at the next
+    #    render_nee / render_adaptive(path="nee") / debug_albedo)
+    def add_texture(self, rgb, **params):
+        """pt_add_texture: rgb (h, w, 3) float, row 0 at the top; params override pt_texture_defaults (filter, srgb).  Returns the index."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("rgb must have shape (h, w, 3)")
+        p = TextureParams(**texture_defaults())
+        for k, v in params.items():
+            if k not in ("filter", "srgb"):
+                raise TypeError("unknown texture parameter %r" % k)
+            setattr(p, k, int(v))
+        return self._ck(LIB.pt_add_texture(self._h, _ptr(rgb), rgb.shape[1], rgb.shape[0], C.byref(p)))
+
+    def clear_textures(self):
+        self._ck(LIB.pt_clear_textures(self._h))
+
+    def set_material_texture(self, material, texture):
+        """Bind texture (an index of add_texture, or -1 / None: none) to a material; only a type-0 material reads it."""
+        self._ck(LIB.pt_set_material_texture(self._h, int(material), -1 if texture is None else int(texture)))
+
+    def debug_texture(self, texture):
+        """pt_debug_texture: ((h, w, 3) float32 of the stored halves, filter)."""
+        w, h, f = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(LIB.pt_debug_texture(self._h, int(texture), None, 0, C.byref(w), C.byref(h), C.byref(f)))
+        out = np.empty((h.value, w.value, 3), dtype=np.float32)
+        self._ck(LIB.pt_debug_texture(self._h, int(texture), _ptr(out), w.value * h.value, None, None, None))
+        return out, f.value
+
+    def set_vertex_uvs(self, uvs, first=0):
+        """uvs (n, 3, 2): (u, v) of the corners of triangles [first, first + n) in add order; a triangle with a non-finite value or one
+        above 65536 in magnitude has none."""
+        uv = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 6)
+        self._ck(LIB.pt_set_vertex_uvs(self._h, int(first), uv.shape[0], _ptr(uv)))
+
+    def clear_vertex_uvs(self):
+        self._ck(LIB.pt_clear_vertex_uvs(self._h))
+
+    def debug_vertex_uvs(self):
+        """(uvs (n, 3, 2) as recorded, 0 where a triangle has none, has (n,) bool) per added triangle."""
+        nt = C.c_int64()
+        self._ck(LIB.pt_debug_scene_sizes(self._h, C.byref(nt), None, None))
+        uv = np.zeros((nt.value, 3, 2), dtype=np.float32)
+        has = np.zeros(nt.value, dtype=np.int32)
+        self._ck(LIB.pt_debug_vertex_uvs(self._h, _ptr(uv), _ptr(has)))
+        return uv, has.astype(bool)
+
+    def debug_albedo(self, rays):
+        """pt_debug_albedo: (add-order triangle or -1, (n, 4) float32 {kd'.rgb, t}) of each ray's closest hit."""
+        rays = np.ascontiguousarray(rays, dtype=RAY)
+        tri = np.empty(rays.shape[0], dtype=np.int32)
+        out = np.empty((rays.shape[0], 4), dtype=np.float32)
+        self._ck(LIB.pt_debug_albedo(self._h, _ptr(rays), rays.shape[0], _ptr(tri), _ptr(out)))
+        return tri, out
+
     def upload_Triangles(self):
         self._ck(LIB.pt_upload_triangles(self._h))
 
@@ -512,15 +608,28 @@ class Scene:
 
     def load(self, spec):
         """Author a scenes.SceneSpec: materials, then one object per entry, then upload."""
+        nm = C.c_int64()
+        self._ck(LIB.pt_debug_scene_sizes(self._h, None, C.byref(nm), None))
         for m in spec.materials:
             self.add_Material(*m)
+        # optional: textures (rgb, or (rgb, dict(filter=, srgb=))), material_textures {index into spec.materials: index into
+        # spec.textures}, uvs per object ((n, 3, 2) or None)
+        tex = []
+        for t in getattr(spec, "textures", None) or []:
+            rgb, params = t if isinstance(t, tuple) else (t, {})
+            tex.append(self.add_texture(rgb, **params))
+        for mi, ti in (getattr(spec, "material_textures", None) or {}).items():
+            self.set_material_texture(nm.value + int(mi), tex[int(ti)])
         first = 0
         normals = getattr(spec, "normals", None) or []
+        uvs = getattr(spec, "uvs", None) or []
         for k, (verts, mati) in enumerate(spec.objects):
             self.add_Triangles(triangles_from_vertices(verts, mati))
             self.end_Obj()
             if k < len(normals) and normals[k] is not None:      # the object's vertex normals (n, 3, 3)
                 self.set_vertex_normals(normals[k], first=first)
+            if k < len(uvs) and uvs[k] is not None:              # the object's uvs (n, 3, 2)
+                self.set_vertex_uvs(uvs[k], first=first)
             first += int(np.asarray(verts).shape[0])
         self.upload_Triangles()
         self.upload_Materials()

@@ -843,6 +843,7 @@ int pt_end_obj(pt_context* ctx) {
         ctx->tris.resize((size_t)ctx->tri_shift);
         ctx->enc_rank.resize((size_t)ctx->tri_shift);
         if (ctx->vnormals.size() > (size_t)ctx->tri_shift * 9) ctx->vnormals.resize((size_t)ctx->tri_shift * 9);
+        if (ctx->vuvs.size() > (size_t)ctx->tri_shift * 6) ctx->vuvs.resize((size_t)ctx->tri_shift * 6);
         return fail(ctx, PT_ESCENE, "object has more than 6 triangles sharing one centroid: the reference's NodeOnHost::build (main.cpp:246-257) never terminates on it");
     }
     ctx->obj_begin.push_back(ctx->tri_shift);
@@ -1149,6 +1150,7 @@ int pt_upload_triangles(pt_context* ctx) {
     ctx->aov_valid = false;          // the guides of pt_render_aovs describe the old scene
     ctx->nee_valid = false;          // and the light table its packed order
     ctx->vnormals_dirty = true;      // and the packed vertex normals
+    ctx->vuvs_dirty = true;          // and uvs
     if (ctx->tri_shift != (int32_t)ctx->tris.size())
         return fail(ctx, PT_EINVAL, "triangles were added after the last end_Obj; close the object first (main.cpp:536)");
     const auto t0 = std::chrono::steady_clock::now();

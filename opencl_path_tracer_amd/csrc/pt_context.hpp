@@ -190,6 +190,24 @@ struct pt_context {
     bool vnormals_dirty = true;
     float4* d_vnormals = nullptr;
     size_t vnormals_cap = 0;           // packed triangles d_vnormals has room for
+    // albedo textures (option textures, pt_add_texture / pt_set_vertex_uvs / pt_set_material_texture; pinned in include/pt_api.h).
+    // Host: every texture's texels back to back (8 B each: three halves r g b and 16 zero bits) with one descriptor per texture, the
+    // binding per material (-1: none; shorter than mats: the rest has none) and 6 floats per add-order triangle (NaN where a triangle
+    // has no uvs; shorter than tris: the rest has none).  The device copies are made by texture_prepare (pt_host.cpp) at the first
+    // textured launch after any of them, the uploaded triangles or the uploaded materials changed; d_vuvs: 2 float4 per packed
+    // triangle (k_pack_vertex_uvs, pt_texture.hip); d_mat_tex: per material on the device the binding, -1 where its type is not 0
+    int textures = 0;
+    std::vector<uint64_t> tex_texels;
+    std::vector<TexDesc> tex_desc;
+    std::vector<int32_t> mat_tex;
+    std::vector<float> vuvs;
+    bool tex_dirty = true, vuvs_dirty = true;      // textures / bindings / materials; uvs / triangles
+    uint2* d_tex_texels = nullptr;
+    TexDesc* d_tex_desc = nullptr;
+    int32_t* d_mat_tex = nullptr;
+    float4* d_vuvs = nullptr;
+    size_t vuvs_cap = 0;               // packed triangles d_vuvs has room for
+    int obj_textures_loaded = 0, obj_textures_skipped = 0;      // map_Kd lines of the last pt_add_obj
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -239,7 +257,10 @@ float env_select(const pt_context* ctx, bool no_lights);           // pt_env.cpp
 int nee_prepare(pt_context* ctx, int32_t strategy, NeeTable* lt, EnvView* env, bool* sky);
 // pt_host.cpp: the packed vertex normals on the device for a smooth launch (repacked if stale); *vn = null when the option is off, unless force
 int smooth_prepare(pt_context* ctx, const float4** vn, bool force = false);
-int host_threads(const pt_context* ctx);                          // threads of the host-side scene path (option build_threads)
+// pt_host.cpp: the textures, bindings and packed uvs on the device for a textured launch (refreshed if stale); tv->uv = null when the
+// option is off, unless force
+int texture_prepare(pt_context* ctx, TexView* tv, bool force = false);
+int host_threads(const pt_context* ctx);                        // threads of the host-side scene path (option build_threads)
 
 #define PT_HIP(ctx, call)                                                                   \
     do {                                                                                    \

@@ -1093,9 +1093,13 @@ struct PathRegs {
 // A hook with `smooth` set also supplies the shading normal (option smooth_normals, pinned in include/pt_api.h): shading_normal()
 // below, the specular vertex with its fall-back to the geometric normal (spec_vertex), and the geometric normal for the offsets.
 // Every statement that does so sits under `if constexpr (HOOK::smooth)`.
+// A hook with `textured` set (it has `smooth` too) also supplies the albedo of a type-0 vertex (option textures, pinned in
+// include/pt_api.h): shading_normal_albedo() below, one evaluation of the barycentric weights for the normal and the uv; every
+// statement that does so sits under `if constexpr (HOOK::textured)`.
 struct NoShadeHook {
     static constexpr bool active = false;
     static constexpr bool smooth = false;
+    static constexpr bool textured = false;
 };
 
 // The interpolated shading normal of a hit at hp = madd(D, t, P) on packed triangle ti (include/pt_api.h pins every operation): vn =
@@ -1109,6 +1113,81 @@ PT_DEV f3 shading_normal(const float4* __restrict__ vn, const float4* __restrict
     const float a1 = max0(dot3(cross3(r3 - r2, hp - r2), N));
     const float a2 = max0(dot3(cross3(r1 - r3, hp - r3), N));
     const float a3 = max0(dot3(cross3(r2 - r1, hp - r1), N));
+    const f3 s = madd(mk(q3.x, q3.y, q3.z), a3, madd(mk(q2.x, q2.y, q2.z), a2, mk(q1.x, q1.y, q1.z) * a1));
+    const float l2 = dot3(s, s);
+    if (!(l2 > 0.0f && l2 < __builtin_inff())) return Ng;
+    f3 Ns = s * (1.0f / __builtin_sqrtf(l2));
+    if (dot3(Ns, Ng) < 0.0f) Ns = -Ns;
+    if (!(dot3(-D, Ns) > 0.0f)) return Ng;
+    return Ns;
+}
+
+// ---- albedo textures (option textures; include/pt_api.h pins every operation)
+// a stored half widened by the hardware convert (v_cvt_f32_f16)
+PT_DEV float half_to_float(unsigned bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
+// texel (x, y) of the texture that starts at `first`: one 8-byte load; 0 <= x < w, 0 <= y < h
+PT_DEV f3 texel_rgb(const uint2* __restrict__ texels, unsigned first, int w, int x, int y) {
+    const uint2 q = texels[first + (unsigned)y * (unsigned)w + (unsigned)x];
+    return mk(half_to_float(q.x & 0xffffu), half_to_float(q.x >> 16), half_to_float(q.y & 0xffffu));
+}
+// (i mod n + n) mod n for the i a lookup can produce, -1 <= i <= n, without a division; any other i (a uv that overflowed) lands in range too
+PT_DEV int tex_wrap(int i, int n) {
+    if (i < 0) i += n;
+    if (i >= n) i -= n;
+    return i < 0 ? 0 : i > n - 1 ? n - 1 : i;
+}
+// texture T at (u, v): repeat wrap, row 0 at the top, nearest or bilinear
+PT_DEV f3 texture_lookup(const TexView& tv, int T, float u, float v) {
+    const TexDesc d = tv.desc[T];
+    const float fu = u - __builtin_floorf(u), fv = v - __builtin_floorf(v);
+    const float w = (float)d.w, h = (float)d.h;
+    if (d.filter == 0) {
+        const int x = (int)__builtin_floorf(fu * w), y = (int)__builtin_floorf((1.0f - fv) * h);
+        return texel_rgb(tv.texels, d.first, d.w, x < d.w - 1 ? (x < 0 ? 0 : x) : d.w - 1, y < d.h - 1 ? (y < 0 ? 0 : y) : d.h - 1);
+    }
+    const float px = fmaf_(fu, w, -0.5f), py = fmaf_(1.0f - fv, h, -0.5f);
+    const float x0 = __builtin_floorf(px), y0 = __builtin_floorf(py);
+    const float tx = px - x0, ty = py - y0;
+    const int xa = tex_wrap((int)x0, d.w), ya = tex_wrap((int)y0, d.h);
+    const int xb = xa + 1 < d.w ? xa + 1 : 0, yb = ya + 1 < d.h ? ya + 1 : 0;
+    const f3 c00 = texel_rgb(tv.texels, d.first, d.w, xa, ya), c10 = texel_rgb(tv.texels, d.first, d.w, xb, ya);
+    const f3 c01 = texel_rgb(tv.texels, d.first, d.w, xa, yb), c11 = texel_rgb(tv.texels, d.first, d.w, xb, yb);
+    const f3 top = mk(fmaf_(tx, c10.x - c00.x, c00.x), fmaf_(tx, c10.y - c00.y, c00.y), fmaf_(tx, c10.z - c00.z, c00.z));
+    const f3 bot = mk(fmaf_(tx, c11.x - c01.x, c01.x), fmaf_(tx, c11.y - c01.y, c01.y), fmaf_(tx, c11.z - c01.z, c01.z));
+    return mk(fmaf_(ty, bot.x - top.x, top.x), fmaf_(ty, bot.y - top.y, top.y), fmaf_(ty, bot.z - top.z, top.z));
+}
+
+// shading_normal() and the textured albedo of the same hit with ONE evaluation of the weights a1, a2, a3: returns Ns as
+// shading_normal does (vn == nullptr: no triangle has vertex normals) and multiplies *kd by the texel when the material mati has
+// type 0 and a texture bound and the triangle has uvs; every other case leaves *kd alone.  Only lanes at such a hit run the lookup.
+PT_DEV f3 shading_normal_albedo(const float4* __restrict__ vn, const TexView& tv, const float4* __restrict__ tris, int ti, f3 D, f3 hp, f3 N, f3 Ng, int type,
+                                int mati, f3* kd) {
+    float4 q1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (vn) q1 = vn[(size_t)ti * 3];
+    const bool sn = q1.w != 0.0f;
+    int T = -1;
+    if (type == 0) T = tv.mat_tex[mati];
+    float4 ub = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (T >= 0) ub = tv.uv[(size_t)ti * 2 + 1];
+    const bool tx = ub.z != 0.0f;
+    if (!sn && !tx) return Ng;
+    const float4 a = tris[ti * 3], b = tris[ti * 3 + 1], c = tris[ti * 3 + 2];
+    const f3 r1 = mk(a.x, a.y, a.z), r2 = mk(a.w, b.x, b.y), r3 = mk(b.z, b.w, c.x);
+    const float a1 = max0(dot3(cross3(r3 - r2, hp - r2), N));
+    const float a2 = max0(dot3(cross3(r1 - r3, hp - r3), N));
+    const float a3 = max0(dot3(cross3(r2 - r1, hp - r1), N));
+    if (tx) {
+        const float A = (a1 + a2) + a3;
+        if (A > 0.0f && A < __builtin_inff()) {
+            const float4 ua = tv.uv[(size_t)ti * 2];
+            const float inv = 1.0f / A;
+            const float u = fmaf_(ub.x, a3, fmaf_(ua.z, a2, ua.x * a1)) * inv;
+            const float v = fmaf_(ub.y, a3, fmaf_(ua.w, a2, ua.y * a1)) * inv;
+            *kd = *kd * texture_lookup(tv, T, u, v);
+        }
+    }
+    if (!sn) return Ng;
+    const float4 q2 = vn[(size_t)ti * 3 + 1], q3 = vn[(size_t)ti * 3 + 2];
     const f3 s = madd(mk(q3.x, q3.y, q3.z), a3, madd(mk(q2.x, q2.y, q2.z), a2, mk(q1.x, q1.y, q1.z) * a1));
     const float l2 = dot3(s, s);
     if (!(l2 > 0.0f && l2 < __builtin_inff())) return Ng;
@@ -1150,12 +1229,19 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         plain = false;
     }
     const f3 hp = madd(rD, t, rP);
-    if (p.iterations == 1) st.setC((REC ? kd : ldf3(m->kd)) + ldf3(m->emission));        // prog.cl:323-325
+    if constexpr (!HOOK::textured)
+        if (p.iterations == 1) st.setC((REC ? kd : ldf3(m->kd)) + ldf3(m->emission));        // prog.cl:323-325
     const bool flip = dot3(rD, N) > 0.0f;
     if (flip) N = -N;                                                       // prog.cl:326-328
     // smooth shading: from here on N is the shading normal Ns; the hook keeps the geometric one (hook->Ng) for the offsets and the
     // geometric-side rules
-    if constexpr (HOOK::smooth) N = hook->shading_normal_at(tris, ti, rD, hp, flip ? -N : N, N);
+    // textures: the same call also leaves the vertex's albedo kd' in the hook (hook->albedo), which the preview colour, the factor_L
+    // update below and the light sample read instead of the material's kd
+    if constexpr (HOOK::textured) {
+        static_assert(HOOK::smooth && !REC, "the textured instances are built on the smooth ones");
+        N = hook->shading_attributes_at(p, tris, ti, rD, hp, flip ? -N : N, N, type, m);
+        if (p.iterations == 1) st.setC(hook->albedo(m) + ldf3(m->emission));
+    } else if constexpr (HOOK::smooth) N = hook->shading_normal_at(tris, ti, rD, hp, flip ? -N : N, N);
     // Every material that continues the path ends the same way: normalise the new direction, step off the surface
     // along +-N.  The two sampling branches below only produce the direction BEFORE normalisation and the side; the
     // tail is shared, so a wave that holds both kinds of hit runs one normalisation (IEEE sqrt + divide), not two.
@@ -1219,7 +1305,8 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     }
     if (type == 0) {
         const float idiff = max0(dot3(rD, N));
-        st.setL(st.L() * ((REC ? kd : ldf3(m->kd)) * idiff));
+        if constexpr (HOOK::textured) st.setL(st.L() * (hook->albedo(m) * idiff));
+        else st.setL(st.L() * ((REC ? kd : ldf3(m->kd)) * idiff));
         // m->_pad = 1: ks is exactly 0 and shininess is finite >= 0, so ks * pow(...) is +-0 whatever the
         // (finite) power is -- skip the halfway vector (two normalisations) and the double-precision pow
         // (set by pt_upload_materials)

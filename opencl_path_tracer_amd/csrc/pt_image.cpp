@@ -90,6 +90,61 @@ int pt_image_read_pfm(const char* path, float* rgba_out, int64_t cap, int32_t* w
     return ok ? PT_OK : PT_EIO;
 }
 
+// one unsigned decimal of a PPM header: white space and `#` comments (to the end of the line) may precede it; -1 if none follows
+static long ppm_header_int(FILE* f) {
+    int c = std::fgetc(f);
+    for (;;) {
+        while (c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f') c = std::fgetc(f);
+        if (c != '#') break;
+        while (c != '\n' && c != '\r' && c != EOF) c = std::fgetc(f);
+    }
+    if (c < '0' || c > '9') return -1;
+    long v = 0;
+    while (c >= '0' && c <= '9') {
+        v = v * 10 + (c - '0');
+        if (v > 1000000) return -1;
+        c = std::fgetc(f);
+    }
+    if (c != EOF) std::ungetc(c, f);
+    return v;
+}
+
+int pt_image_read_ppm(const char* path, float* rgb_out, int64_t cap, int32_t* width, int32_t* height) {
+    if (!path || !width || !height || cap < 0) return PT_EINVAL;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return PT_EIO;
+    const bool magic = std::fgetc(f) == 'P' && std::fgetc(f) == '6';
+    const long w = magic ? ppm_header_int(f) : -1, h = w >= 1 ? ppm_header_int(f) : -1, maxval = h >= 1 ? ppm_header_int(f) : -1;
+    const int sep = maxval >= 1 ? std::fgetc(f) : EOF;            // exactly one white-space byte in front of the samples
+    if (w < 1 || h < 1 || w > 65535 || h > 65535 || maxval < 1 || maxval > 65535 || !(sep == '\n' || sep == ' ' || sep == '\r' || sep == '\t')) {
+        std::fclose(f);
+        return PT_EIO;
+    }
+    *width = (int32_t)w;
+    *height = (int32_t)h;
+    if (!rgb_out) {
+        std::fclose(f);
+        return PT_OK;
+    }
+    if (cap < (int64_t)w * h) {
+        std::fclose(f);
+        return PT_EINVAL;
+    }
+    const size_t bps = maxval > 255 ? 2 : 1;
+    std::vector<unsigned char> row((size_t)w * 3 * bps);
+    bool ok = true;
+    for (long y = 0; y < h && ok; ++y) {
+        ok = std::fread(row.data(), 1, row.size(), f) == row.size();
+        float* dst = rgb_out + (size_t)y * (size_t)w * 3;
+        for (size_t i = 0; i < (size_t)w * 3 && ok; ++i) {
+            const unsigned s = bps == 2 ? ((unsigned)row[2 * i] << 8) | row[2 * i + 1] : row[i];
+            dst[i] = (float)s / (float)maxval;
+        }
+    }
+    std::fclose(f);
+    return ok ? PT_OK : PT_EIO;
+}
+
 int pt_image_write_ppm(const char* path, const float* rgba, int32_t width, int32_t height) {
     if (!path || !rgba || width <= 0 || height <= 0) return PT_EINVAL;
     FILE* f = std::fopen(path, "wb");

@@ -393,11 +393,28 @@ struct EnvView {
     float scale, yaw;            // yaw in radians
     float p_env;                 // the effective P_env (a multiple of 2^-24)
 };
+// albedo textures of pt_render_nee (option textures; pinned in include/pt_api.h)
+struct TexDesc {
+    uint32_t first;              // the texture's first texel in the shared buffer
+    int32_t w, h, filter;        // filter 0 nearest, 1 bilinear
+};
+struct TexView {
+    const float4* uv;            // [packed triangles][2] {u1, v1, u2, v2}, {u3, v3, flag, 0} (k_pack_vertex_uvs, pt_texture.hip)
+    const uint2* texels;         // 8 B each: halves r | g << 16, b
+    const TexDesc* desc;         // [textures]
+    const int32_t* mat_tex;      // [materials on the device] texture of a type-0 material, else -1
+};
 // env == nullptr: the instances without an environment.  tiled (the rounds of pt_render_adaptive_ex): k_nee_tiles / k_nee_env_tiles over
 // the p.n_tiles 8x8 frame tiles of p.tile_list (null: the frame's tiles in order), one lane per pixel of a tile; npix is then not read
 // vn != nullptr (option smooth_normals): the smooth instances, which shade with the interpolated normal of the packed vertex normals vn
+// tv != nullptr (option textures): the textured instances, built on the smooth code; with smooth_normals off they are handed vn = null,
+// which they read as "no triangle has vertex normals" (the pinned rule "no vertex normals: Ns = Ng, the same bits" makes that exact)
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled = false,
-                      const float4* vn = nullptr);
+                      const float4* vn = nullptr, const TexView* tv = nullptr);
+// albedo textures (pt_texture.hip): add-order uvs (6 floats per triangle, n_src triangles; the rest has none) -> 2 float4 per packed triangle
+hipError_t launch_pack_vertex_uvs(const float* src, int64_t n_src, const int32_t* orig, int32_t n, float4* out, hipStream_t stream);
+hipError_t launch_debug_albedo(const RenderParams& p, const float4* vn, const TexView& tv, const pt_ray* rays, int64_t n, int32_t* out_tri, float4* out_rgbt,
+                               int cu_count, hipStream_t stream);
 // smooth shading (pt_smooth.hip): add-order normals (9 floats per triangle, n_src triangles; the rest has none) -> 3 float4 per packed triangle
 hipError_t launch_pack_vertex_normals(const float* src, int64_t n_src, const int32_t* orig, int32_t n, float4* out, hipStream_t stream);
 hipError_t launch_debug_shading_normal(const RenderParams& p, const float4* vn, const pt_ray* rays, int64_t n, int32_t* out_tri, float4* out_ns, int cu_count,

@@ -367,6 +367,7 @@ int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
     if (rc != PT_OK) return rc;
     if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_generate_rays: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
     if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, "pt_generate_rays: option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
+    if (ctx->textures) return fail(ctx, PT_EINVAL, "pt_generate_rays: option textures is on and only pt_render_nee reads albedo textures (pt_set_option(ctx, \"textures\", 0) turns it off)");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     fill_params(ctx, cam, &p);
@@ -381,6 +382,7 @@ int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     if (iterations < 0 || current_sample < 0) return fail(ctx, PT_EINVAL, "iterations/current_sample must be >= 0");
     if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_trace_rays: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
     if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, "pt_trace_rays: option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
+    if (ctx->textures) return fail(ctx, PT_EINVAL, "pt_trace_rays: option textures is on and only pt_render_nee reads albedo textures (pt_set_option(ctx, \"textures\", 0) turns it off)");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
@@ -582,6 +584,7 @@ int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t
     if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "iterations/nsamples must be >= 0");
     if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_render: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
     if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, "pt_render: option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
+    if (ctx->textures) return fail(ctx, PT_EINVAL, "pt_render: option textures is on and only pt_render_nee reads albedo textures (pt_set_option(ctx, \"textures\", 0) turns it off)");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
     if (nsamples == 0) return PT_OK;
     PT_HIP(ctx, hipSetDevice(ctx->device));
@@ -647,6 +650,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
     if (rc != PT_OK) return rc;
     if (!nee && ctx->env_set) return fail(ctx, PT_EINVAL, who + ": an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
     if (!nee && ctx->smooth_normals) return fail(ctx, PT_EINVAL, who + ": option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
+    if (!nee && ctx->textures) return fail(ctx, PT_EINVAL, who + ": option textures is on and only pt_render_nee reads albedo textures (pt_set_option(ctx, \"textures\", 0) turns it off)");
     if (!nee && ctx->variant != 0) return fail(ctx, PT_EINVAL, who + ": the megakernel (variant 0) only");
     if (ctx->world != 1) return fail(ctx, PT_EINVAL, who + ": contexts of one rank (world == 1) only");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
@@ -660,6 +664,8 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
     if (nee && (rc = nee_prepare(ctx, ap->strategy, &lt, &env, &sky)) != PT_OK) return rc;
     const float4* vn = nullptr;             // option smooth_normals: the packed vertex normals
     if (nee && (rc = smooth_prepare(ctx, &vn)) != PT_OK) return rc;
+    TexView tv{nullptr, nullptr, nullptr, nullptr};      // option textures: uvs, texels, descriptors, bindings
+    if (nee && (rc = texture_prepare(ctx, &tv)) != PT_OK) return rc;
     const int32_t n_frame = local_tiles(ctx);
     if (!ctx->d_adapt_spp) {
         PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_spp, sizeof(int32_t) * (size_t)n_frame));
@@ -693,7 +699,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
             pr.n_tiles = n_active;
             EventPair* ep;
             if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-            PT_HIP(ctx, launch_nee(pr, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, true, vn));
+            PT_HIP(ctx, launch_nee(pr, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, true, vn, tv.uv ? &tv : nullptr));
             if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
         } else if ((rc = launch_megakernel(ctx, pr, list, n_active)) != PT_OK) {
             return rc;

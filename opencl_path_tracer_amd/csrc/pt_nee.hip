@@ -13,6 +13,9 @@
 //           sits under `if constexpr (TILED)`.  Three declarations do not, because both branches use them after the branch (the loop
 //           counter j with the pixel i = j, lrow / x, and the pixel counter `rendered`, which is dead in the untiled instances): the
 //           untiled kernels compile to the code they were (the same kernel-resource lines).
+//   k_nee*_smooth, k_nee*_tex  the same four kernels with smooth shading from vertex normals (option smooth_normals, DESIGN.md section
+//           5.9) and, built on that code, with albedo textures (option textures, section 5.10): NeeHook<.., SMOOTH, TEX>; what they add
+//           sits under `if constexpr (SMOOTH)` / `if constexpr (TEX)` here and under HOOK::smooth / HOOK::textured in shade_hit.
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -52,11 +55,22 @@ struct SmoothSlot<true> {
     bool dead = false;             // a lobe vertex sampled a direction below the geometric surface: the path ends
 };
 
+// what a hook carries for albedo textures (option textures): nothing without it
+template <bool TEX>
+struct TexSlot {};
+template <>
+struct TexSlot<true> {
+    TexView v;                     // packed uvs, texels, descriptors, bindings (texture_prepare, pt_host.cpp)
+    f3 kd = mk(0.f, 0.f, 0.f);     // the current vertex's albedo kd' (its material's kd where nothing is bound)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
-template <int MODE, bool ENV = false, bool SMOOTH = false>
+template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false>
 struct NeeHook {
+    static_assert(SMOOTH || !TEX, "the textured instances are built on the smooth code");
     static constexpr bool active = true;
     static constexpr bool smooth = SMOOTH;
+    static constexpr bool textured = TEX;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -69,7 +83,25 @@ struct NeeHook {
     f3 Nprev = mk(0.f, 0.f, 0.f);
     EnvSlot<ENV> env;
     SmoothSlot<SMOOTH> sm;
+    TexSlot<TEX> tx;
 
+    // the albedo of the current type-0 vertex: the material's kd, or under TEX what shading_attributes_at left
+    PT_DEV f3 albedo(const pt_material* __restrict__ m) const {
+        if constexpr (TEX) return tx.kd;
+        else return ldf3(m->kd);
+    }
+    // TEX: shading_normal_at and the vertex's albedo from one evaluation of the weights (sm.vn == nullptr: smooth_normals is off).  kd is
+    // read where something uses it: a type-0 vertex and the preview of iterations == 1
+    PT_DEV f3 shading_attributes_at(const RenderParams& p, const float4* __restrict__ tris, int ti, f3 rD, f3 hp, f3 N, f3 Ng, int type,
+                                    const pt_material* __restrict__ m) {
+        sm.ti = ti;
+        sm.flip = dot3(rD, N) > 0.0f;      // shade_hit's flip
+        f3 kd = mk(0.f, 0.f, 0.f);
+        if (type == 0 || p.iterations == 1) kd = ldf3(m->kd);
+        const f3 Ns = shading_normal_albedo(sm.vn, tx.v, tris, ti, rD, hp, N, Ng, type, (int)(m - p.mats), &kd);
+        tx.kd = kd;
+        return Ns;
+    }
     // the normal the offsets use: N itself, or under smooth shading (where N is the shading normal) the geometric one
     PT_DEV f3 geo(f3 N) const {
         if constexpr (SMOOTH) {
@@ -189,7 +221,7 @@ struct NeeHook {
         const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
         f3 fl = st.L(), fb = st.B();
         if (type == 0) {           // the factors the vertex's own update with w would give (shade_hit)
-            fl = fl * (ldf3(m->kd) * cosx);
+            fl = fl * (albedo(m) * cosx);
             float pw = 1.0f;
             if (!m->_pad) {
                 const f3 view = normalize3(eye - hp);
@@ -277,7 +309,7 @@ struct NeeHook {
         const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
         f3 fl = st.L(), fb = st.B();
         if (type == 0) {           // as in light_sample
-            fl = fl * (ldf3(m->kd) * cosx);
+            fl = fl * (albedo(m) * cosx);
             float pw = 1.0f;
             if (!m->_pad) {
                 const f3 view = normalize3(eye - hp);
@@ -323,14 +355,16 @@ struct NeeHook {
 
 // SMOOTH (option smooth_normals; k_nee*_smooth below): the hook supplies the shading normal from the packed vertex normals vn; what it
 // adds here sits under `if constexpr (SMOOTH)`
-template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false>
-PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr) {
+// TEX (option textures; k_nee*_tex below; on the SMOOTH code only): the hook also supplies the albedo of a type-0 vertex from the view tv
+template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false>
+PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
+    if constexpr (TEX) hook.tx.v = *tv;
     if constexpr (ENV) {
         hook.env = env;
         hook.nee = lt.strategy != 0;       // the sky is a light (the host launches this instance only for a map with a distribution)
@@ -440,6 +474,24 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_smooth(RenderParams p, 
     nee_frame<MODE, BLOCK, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn);
 }
 
+// the textured instances (option textures): the smooth kernels with the texture view as one more argument (vn = null: smooth_normals off)
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tex(RenderParams p, NeeTable lt, const float4* vn, TexView tv, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tex(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_tex(RenderParams p, NeeTable lt, const float4* vn, TexView tv) {
+    nee_frame<MODE, BLOCK, false, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_tex(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv) {
+    nee_frame<MODE, BLOCK, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -455,7 +507,19 @@ static hipError_t launch_lanes_env_tiles_smooth(PICK pick, const RenderParams& p
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled, const float4* vn) {
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled, const float4* vn,
+                      const TexView* tv) {
+    if (tv) {
+        if (tiled) {
+            const int64_t items = (int64_t)p.n_tiles * 64;
+            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_tex<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv);
+            return launch_lanes([](auto s) { return k_nee_tiles_tex<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv);
+        }
+        // (k_nee_env_tex needs 3 VGPRs more than k_nee_env_smooth, which sits at the 128-VGPR cap of a 1,024-thread workgroup: the
+        // 512-thread treelet shape of k_nee_env_tiles_smooth keeps it out of scratch)
+        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tex<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, (long long)npix);
+        return launch_lanes([](auto s) { return k_nee_tex<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, (long long)npix);
+    }
     if (vn) {
         if (tiled) {
             const int64_t items = (int64_t)p.n_tiles * 64;

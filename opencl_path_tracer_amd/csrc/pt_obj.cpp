@@ -13,8 +13,12 @@
 // New (the reference throws vn away): a face whose corners all carry a vn index records those normals for its fan triangles
 // (pt_set_vertex_normals; include/pt_api.h), transformed by the inverse transpose of the positions' linear map.  The triangles
 // themselves are what they were.
+// New as well (the reference throws vt and map_Kd away): a face whose corners all carry a vt index records those uvs for its fan
+// triangles (pt_set_vertex_uvs), and a material's map_Kd -- a .ppm or .pfm next to the MTL -- becomes a texture bound to the material
+// pt_add_obj creates (pt_add_texture / pt_set_material_texture; include/pt_api.h).  A map that cannot be used leaves the material as it was.
 // Deviations, all turning undefined behaviour of the reference into errors: a missing
 // Kn/Kk/Tp, a face without usemtl (material id -1) and an empty shape return PT_EIO.
+#include "pt_context.hpp"
 #include "pt_internal.hpp"
 
 #include <algorithm>
@@ -24,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <sstream>
 #include <string>
@@ -42,6 +47,8 @@ struct MtlRec {
     float diffuse[3] = {0, 0, 0}, specular[3] = {0, 0, 0}, emission[3] = {0, 0, 0};
     float shininess = 1.0f;                         // tiny_obj_loader.h:858
     std::map<std::string, std::string> unknown;
+    std::string map_kd;                             // the file of the last usable map_Kd line
+    int map_kd_skipped = 0;                         // map_Kd lines with a -option token
 };
 
 inline bool is_space(char c) { return c == ' ' || c == '\t'; }
@@ -141,6 +148,22 @@ bool load_mtl(const std::string& path, std::vector<MtlRec>* mats, std::map<std::
         if (t[0] == 'K' && t[1] == 's' && is_space(t[2])) { t += 2; parse_float3(cur.specular, &t); continue; }
         if (t[0] == 'K' && t[1] == 'e' && is_space(t[2])) { t += 2; parse_float3(cur.emission, &t); continue; }
         if (t[0] == 'N' && t[1] == 's' && is_space(t[2])) { t += 2; cur.shininess = parse_float(&t); continue; }
+        if (0 == std::strncmp(t, "map_Kd", 6) && is_space(t[6])) {      // the last blank-separated token; a line with an option is skipped
+            const char* q = t + 6;
+            std::string last;
+            bool option = false;
+            for (;;) {
+                q += std::strspn(q, " \t");
+                if (*q == '\0') break;
+                const size_t n = std::strcspn(q, " \t");
+                if (*q == '-') option = true;
+                last.assign(q, n);
+                q += n;
+            }
+            if (option) ++cur.map_kd_skipped;
+            else if (!last.empty()) cur.map_kd = last;
+            continue;
+        }
         // keys tinyobj knows but add_Obj never reads
         static const char* known[] = {"Ka", "Kt", "Tf", "Ni", "illum", "d", "Tr", "Pr", "Pm", "Ps", "Pc", "Pcr", "aniso", "anisor",
                                       "map_Ka", "map_Kd", "map_Ks", "map_Ns", "map_bump", "bump", "map_d", "disp", "refl",
@@ -203,7 +226,48 @@ inline int parse_vn(const char* t) {
     return parse_int(s2 + 1);
 }
 
-struct Face3 { int v[3]; int mat; int vn[3]; };      // vn: resolved index, or -1
+// the vt of v/vt or v/vt/vn in the token at t (kNoVn: none)
+inline int parse_vt(const char* t) {
+    const char* e = t + std::strcspn(t, " \t");
+    const char* s1 = (const char*)std::memchr(t, '/', (size_t)(e - t));
+    if (!s1 || s1 + 1 >= e || s1[1] == '/') return kNoVn;
+    return parse_int(s1 + 1);
+}
+
+bool ends_with_nocase(const std::string& s, const char* ext) {
+    const size_t n = std::strlen(ext);
+    if (s.size() < n) return false;
+    for (size_t i = 0; i < n; ++i)
+        if (std::tolower((unsigned char)s[s.size() - n + i]) != ext[i]) return false;
+    return true;
+}
+
+// a map_Kd file as a texture of ctx: its index, or -1 when it cannot be used (another format, unreadable, refused by pt_add_texture)
+int load_albedo_map(pt_context* ctx, const std::string& path) {
+    const bool ppm = ends_with_nocase(path, ".ppm"), pfm = ends_with_nocase(path, ".pfm");
+    if (!ppm && !pfm) return -1;
+    int32_t w = 0, h = 0;
+    if ((ppm ? pt_image_read_ppm(path.c_str(), nullptr, 0, &w, &h) : pt_image_read_pfm(path.c_str(), nullptr, 0, &w, &h)) != PT_OK) return -1;
+    if (w < 1 || h < 1 || w > PT_TEX_MAX_SIZE || h > PT_TEX_MAX_SIZE) return -1;
+    const size_t n = (size_t)w * (size_t)h;
+    std::vector<float> rgb(n * 3);
+    if (ppm) {
+        if (pt_image_read_ppm(path.c_str(), rgb.data(), (int64_t)n, &w, &h) != PT_OK) return -1;
+    } else {
+        std::vector<float> rgba(n * 4);
+        if (pt_image_read_pfm(path.c_str(), rgba.data(), (int64_t)n, &w, &h) != PT_OK) return -1;
+        for (int32_t y = 0; y < h; ++y)                      // the file's rows run bottom to top
+            for (int32_t x = 0; x < w; ++x)
+                for (int c = 0; c < 3; ++c) rgb[((size_t)y * w + x) * 3 + c] = rgba[((size_t)(h - 1 - y) * w + x) * 4 + c];
+    }
+    const pt_texture_params tp = {1, ppm ? 1 : 0};
+    const std::string keep = pt_last_error(ctx);            // (a refused map is no error of pt_add_obj)
+    const int t = pt_add_texture(ctx, rgb.data(), w, h, &tp);
+    if (t < 0) ctx->err = keep;
+    return t < 0 ? -1 : t;
+}
+
+struct Face3 { int v[3]; int mat; int vn[3]; int vt[3]; };      // vn, vt: resolved index, or -1
 struct Shape { std::vector<Face3> faces; };
 
 // run fn(begin, end) over [0, n) on up to 16 threads (element-wise work: any split gives the same result)
@@ -245,13 +309,13 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
     // triangulate = true) when the material changes, at g / o and at the end of the file; g / o keeps the shape only if
     // the group it closes is not empty (tiny_obj_loader.h:1509-1567) -- faces exported by an earlier usemtl are lost
     // with it, which B reproduces.  A face of fewer than three vertices opens the group and exports nothing.
-    struct RawTri { int idx[3]; int nv_local; int vn[3]; int nvn_local; };
+    struct RawTri { int idx[3]; int nv_local; int vn[3]; int nvn_local; int vt[3]; int nvt_local; };
     enum { kEvUsemtl = 0, kEvMtllib = 1, kEvShape = 2, kEvShortFace = 3 };
     struct Event { int kind; size_t tri_pos; std::string name; };
     struct Piece {
         char* begin = nullptr;
         char* end = nullptr;
-        std::vector<float> v, vn;
+        std::vector<float> v, vn, vt;
         std::vector<RawTri> tris;
         std::vector<Event> ev;
     };
@@ -300,18 +364,25 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
                 pc.vn.push_back(p[0]); pc.vn.push_back(p[1]); pc.vn.push_back(p[2]);
                 continue;
             }
+            if (t[0] == 'v' && t[1] == 't' && is_space(t[2])) {
+                t += 3;
+                const float u = parse_float(&t), vv = parse_float(&t);      // (an optional w is not read)
+                pc.vt.push_back(u); pc.vt.push_back(vv);
+                continue;
+            }
             if (t[0] == 'f' && is_space(t[1])) {
                 t += 2;
                 t += std::strspn(t, " \t");
-                const int nv_local = (int)(pc.v.size() / 3), nvn_local = (int)(pc.vn.size() / 3);
-                int first = 0, prev = 0, count = 0, nfirst = kNoVn, nprev = kNoVn;
+                const int nv_local = (int)(pc.v.size() / 3), nvn_local = (int)(pc.vn.size() / 3), nvt_local = (int)(pc.vt.size() / 2);
+                int first = 0, prev = 0, count = 0, nfirst = kNoVn, nprev = kNoVn, tfirst = kNoVn, tprev = kNoVn;
                 while (*t != '\0') {
                     const int idx = parse_int(t);                         // the v of v, v/vt, v//vn, v/vt/vn
-                    const int nidx = parse_vn(t);
-                    if (count == 0) { first = idx; nfirst = nidx; }
-                    else if (count >= 2) pc.tris.push_back(RawTri{{first, prev, idx}, nv_local, {nfirst, nprev, nidx}, nvn_local});   // fan: (first, previous, this)
+                    const int nidx = parse_vn(t), tidx = parse_vt(t);
+                    if (count == 0) { first = idx; nfirst = nidx; tfirst = tidx; }
+                    else if (count >= 2) pc.tris.push_back(RawTri{{first, prev, idx}, nv_local, {nfirst, nprev, nidx}, nvn_local, {tfirst, tprev, tidx}, nvt_local});   // fan: (first, previous, this)
                     prev = idx;
                     nprev = nidx;
+                    tprev = tidx;
                     ++count;
                     t += std::strcspn(t, " \t");
                     t += std::strspn(t, " \t");
@@ -327,7 +398,7 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
                 continue;
             }
             if ((t[0] == 'g' || t[0] == 'o') && is_space(t[1])) pc.ev.push_back(Event{kEvShape, pc.tris.size(), std::string()});
-            // vt, s, t ...: nothing add_Obj reads
+            // s, t ...: nothing add_Obj reads
         }
     };
     {
@@ -358,11 +429,12 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
     shape_kept.push_back(0);
     bool group_open = false;
     int material = -1;
-    std::vector<size_t> vbase(n_pieces + 1, 0), vnbase(n_pieces + 1, 0);
+    std::vector<size_t> vbase(n_pieces + 1, 0), vnbase(n_pieces + 1, 0), vtbase(n_pieces + 1, 0);
     for (size_t k = 0; k < n_pieces; ++k) {
         const Piece& pc = pieces[k];
         vbase[k + 1] = vbase[k] + pc.v.size() / 3;
         vnbase[k + 1] = vnbase[k] + pc.vn.size() / 3;
+        vtbase[k + 1] = vtbase[k] + pc.vt.size() / 2;
         size_t at = 0;
         auto close_run = [&](size_t upto) {
             if (upto > at) {
@@ -395,7 +467,7 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
     shape_kept.back() = (group_open || shape_tris.back() != 0) ? 1 : 0;     // end of file: tiny_obj_loader.h flushes the pending group
 
     // C: vertices in file order, triangles into their shapes
-    std::vector<float> v(vbase[n_pieces] * 3), vn(vnbase[n_pieces] * 3);
+    std::vector<float> v(vbase[n_pieces] * 3), vn(vnbase[n_pieces] * 3), vt(vtbase[n_pieces] * 2);
     std::vector<Shape> shapes;
     std::vector<size_t> shape_slot(shape_tris.size(), (size_t)-1);
     for (size_t sidx = 0; sidx < shape_tris.size(); ++sidx)
@@ -409,6 +481,8 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
             if (!pieces[k].v.empty()) std::memcpy(&v[vbase[k] * 3], pieces[k].v.data(), sizeof(float) * pieces[k].v.size());
         for (size_t k = b; k < e; ++k)
             if (!pieces[k].vn.empty()) std::memcpy(&vn[vnbase[k] * 3], pieces[k].vn.data(), sizeof(float) * pieces[k].vn.size());
+        for (size_t k = b; k < e; ++k)
+            if (!pieces[k].vt.empty()) std::memcpy(&vt[vtbase[k] * 2], pieces[k].vt.data(), sizeof(float) * pieces[k].vt.size());
     });
     parallel_ranges(runs.size(), 1, [&](size_t b, size_t e) {
         for (size_t r = b; r < e; ++r) {
@@ -421,6 +495,7 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
                 const RawTri& rt = pc.tris[i];
                 for (int c = 0; c < 3; ++c) out->v[c] = fix_index(rt.idx[c], vb + rt.nv_local);
                 for (int c = 0; c < 3; ++c) out->vn[c] = rt.vn[c] == kNoVn || rt.vn[c] == 0 ? -1 : fix_index(rt.vn[c], (int)vnbase[run.piece] + rt.nvn_local);
+                for (int c = 0; c < 3; ++c) out->vt[c] = rt.vt[c] == kNoVn || rt.vt[c] == 0 ? -1 : fix_index(rt.vt[c], (int)vtbase[run.piece] + rt.nvt_local);
                 out->mat = run.material;
             }
         }
@@ -430,6 +505,8 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
 
     // ---- materials, main.cpp:562-581
     int base = -1;                                   // mat_offset, main.cpp:562
+    std::map<std::string, int> maps;                 // map_Kd files of this call: texture index, or -1 for one that cannot be used
+    ctx->obj_textures_loaded = ctx->obj_textures_skipped = 0;
     for (size_t i = 0; i < mtls.size(); ++i) {
         const MtlRec& m = mtls[i];
         auto kn = m.unknown.find("Kn"), kk = m.unknown.find("Kk"), tp = m.unknown.find("Tp");
@@ -443,6 +520,13 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
         int idx = pt_add_material(ctx, &pm);
         if (idx < 0) return idx;
         if (base < 0) base = idx;
+        ctx->obj_textures_skipped += m.map_kd_skipped;
+        if (!m.map_kd.empty()) {
+            auto it = maps.find(m.map_kd);
+            if (it == maps.end()) it = maps.insert(std::make_pair(m.map_kd, load_albedo_map(ctx, matpath + m.map_kd))).first;
+            if (it->second >= 0 && pt_set_material_texture(ctx, idx, it->second) == PT_OK) ++ctx->obj_textures_loaded;
+            else ++ctx->obj_textures_skipped;
+        }
     }
     if (base < 0) base = 0;
 
@@ -511,6 +595,23 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
                 for (int k = 0; k < 3; ++k) std::memcpy(&fn[i * 9 + 3 * (size_t)k], &wn[3 * (size_t)f.vn[k]], sizeof(float) * 3);
             }
             rc = pt_set_vertex_normals(ctx, ntris - (int64_t)nf, (int64_t)nf, fn.data());
+            if (rc != PT_OK) return rc;
+        }
+        bool any_vt = false;
+        for (size_t i = 0; i < nf && !any_vt; ++i) any_vt = sh.faces[i].vt[0] >= 0;
+        if (any_vt) {
+            int64_t ntris = 0;
+            pt_debug_scene_sizes(ctx, &ntris, nullptr, nullptr);
+            const size_t nuv = vt.size() / 2;
+            std::vector<float> fu(nf * 6, std::numeric_limits<float>::quiet_NaN());      // (NaN: the triangle has no uvs)
+            for (size_t i = 0; i < nf; ++i) {
+                const Face3& f = sh.faces[i];
+                bool all = true;
+                for (int k = 0; k < 3; ++k) all = all && f.vt[k] >= 0 && (size_t)f.vt[k] < nuv;
+                if (!all) continue;
+                for (int k = 0; k < 3; ++k) std::memcpy(&fu[i * 6 + 2 * (size_t)k], &vt[2 * (size_t)f.vt[k]], sizeof(float) * 2);
+            }
+            rc = pt_set_vertex_uvs(ctx, ntris - (int64_t)nf, (int64_t)nf, fu.data());
             if (rc != PT_OK) return rc;
         }
         rc = pt_end_obj(ctx);

@@ -35,6 +35,9 @@ class SceneSpec:
     shift: tuple = (0.0, 0.0, 0.0)
     name: str = ""
     normals: list = field(default_factory=list)      # optional, per object: vertex normals (n,3,3) f32 or None (Scene.load applies them)
+    uvs: list = field(default_factory=list)          # optional, per object: corner uvs (n,3,2) f32 (NaN: none) or None
+    textures: list = field(default_factory=list)     # optional: (h,w,3) f32 images, or (image, dict(filter=, srgb=)) (Scene.add_texture)
+    material_textures: dict = field(default_factory=dict)   # optional: {index into materials: index into textures}
 
     @property
     def ntris(self):
@@ -104,10 +107,39 @@ def uv_sphere_normals(center, radius, segments=32, rings=16):
     return ((v - np.asarray(center, dtype=np.float64)) / float(radius)).astype(np.float32)
 
 
-def cornell_box(segments=32, rings=16, smooth=False):
+def uv_sphere_uvs(rings=16, segments=32):
+    """The lat-long uvs of uv_sphere's corners in its triangle order, (n, 3, 2) float32, for Scene.set_vertex_uvs: u = j / segments
+    around the axis (1 at the seam's far side, the middle of its segment at a pole), v = 1 - i / rings (1 at the +y pole)."""
+    tris = []
+
+    def q(i, j):
+        return (j / segments, 1.0 - i / rings)
+
+    for j in range(segments):
+        tris.append((((j + 0.5) / segments, 1.0), q(1, j + 1), q(1, j)))
+    for i in range(1, rings - 1):
+        for j in range(segments):
+            a, b, c, d = q(i, j), q(i, j + 1), q(i + 1, j), q(i + 1, j + 1)
+            tris.append((a, b, d))
+            tris.append((a, d, c))
+    for j in range(segments):
+        tris.append((((j + 0.5) / segments, 0.0), q(rings - 1, j), q(rings - 1, j + 1)))
+    return np.asarray(tris, dtype=np.float64).astype(np.float32)
+
+
+def checker_texture(n, a, b):
+    """An n x n checkerboard (n, n, 3) float32 for Scene.add_texture: colour a where row + column is even, b elsewhere."""
+    i, j = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    even = ((i + j) % 2 == 0)[:, :, None]
+    return np.where(even, np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)).astype(np.float32)
+
+
+def cornell_box(segments=32, rings=16, smooth=False, textured=False):
     """Scene CB of SURVEY 8(d): 12 wall/lamp triangles + two tessellated spheres
     (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects.
-    smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals)."""
+    smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals).
+    textured: the floor carries uvs (one repeat per 1,600 units) and WHITE_DIFFUSE an 8 x 8 checker with nearest filtering, so under
+    option textures the floor shows checks of 200 units; the other white walls have no uvs and keep their kd."""
     spec = SceneSpec(materials=list(BUILTIN_MATERIALS), name="cornell_box")
     spec.objects.append(cornell_walls())
     s1 = uv_sphere((250.0, 200.0, 300.0), 200.0, segments, rings)
@@ -117,6 +149,13 @@ def cornell_box(segments=32, rings=16, smooth=False):
     if smooth:
         spec.normals = [None, uv_sphere_normals((250.0, 200.0, 300.0), 200.0, segments, rings),
                         uv_sphere_normals((750.0, 200.0, -200.0), 200.0, segments, rings)]
+    if textured:
+        walls = spec.objects[0][0]
+        uv = np.full((walls.shape[0], 3, 2), np.nan, dtype=np.float32)
+        uv[10:12] = walls[10:12][:, :, [0, 2]] / np.float32(1600.0)        # the floor: (x, z)
+        spec.uvs = [uv, None, None]
+        spec.textures = [(checker_texture(8, (1.0, 1.0, 1.0), (0.25, 0.25, 0.25)), dict(filter=0, srgb=0))]
+        spec.material_textures = {WHITE_DIFFUSE: 0}
     return spec
 
 

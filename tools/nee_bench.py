@@ -1,9 +1,12 @@
 """Next-event estimation (render_nee): rate, kernel time per path segment, and what each strategy buys in RMSE.
 
-usage: python tools/nee_bench.py [--smooth] [scene=cornell|walls|mesh100k|all] [W=1920 H=1080] [bounces=8] [ref=4096] [spp=64] [quality=1] [out=DIR]
+usage: python tools/nee_bench.py [--smooth] [--textured | --textures-on] [scene=cornell|walls|mesh100k|all] [W=1920 H=1080] [bounces=8] [ref=4096] [spp=64] [quality=1] [out=DIR]
 
 --smooth: the Cornell box carries its spheres' analytic vertex normals and render_nee runs with option smooth_normals = 1 (render(),
 which refuses under the option, runs with it off); quality=0 skips the reference frame and the RMSE curve (rates only).
+--textured: the Cornell box carries its checker floor (scenes.cornell_box(textured=True)) and render_nee runs with option textures = 1;
+--textures-on: option textures = 1 on the untextured scene (what the textured kernel instances cost by themselves); rates only make sense
+with quality=0 here (the reference frame of the quality part is render()'s, which has no textures).
 
 One JSON line per scene on stdout; with out=DIR also DIR/<scene>_<W>x<H>.json.
 
@@ -29,9 +32,9 @@ from opencl_path_tracer_amd import api, scenes  # noqa: E402
 STRATEGIES = ("bsdf", "light", "mis")
 
 
-def scene_spec(name, smooth=False):
+def scene_spec(name, smooth=False, textured=False):
     if name == "cornell":
-        return scenes.cornell_box(smooth=smooth)
+        return scenes.cornell_box(smooth=smooth, textured=textured)
     if name == "walls":
         spec = scenes.SceneSpec(materials=list(scenes.BUILTIN_MATERIALS), name="cornell_walls")
         spec.objects.append(scenes.cornell_walls())
@@ -68,15 +71,17 @@ def timed(sc, fn, setup, reps=3):
     return float(np.median(ev)), float(np.median(kern))
 
 
-def run_scene(name, W, H, bounces, ref_spp, spp, smooth=False, quality=True):
-    spec = scene_spec(name, smooth)
+def run_scene(name, W, H, bounces, ref_spp, spp, smooth=False, quality=True, textures=0):
+    spec = scene_spec(name, smooth, textures == 2)
     npix = W * H
-    res = {"scene": name, "W": W, "H": H, "bounces": bounces, "ref_spp": ref_spp, "rate_spp": spp, "smooth": bool(smooth)}
+    res = {"scene": name, "W": W, "H": H, "bounces": bounces, "ref_spp": ref_spp, "rate_spp": spp, "smooth": bool(smooth), "textures": ("off", "on", "on, textured scene")[textures]}
 
     def nee(sc, n, s):
         sc.set_option("smooth_normals", 1 if smooth else 0)
+        sc.set_option("textures", 1 if textures else 0)
         sc.render_nee(n, s)
         sc.set_option("smooth_normals", 0)
+        sc.set_option("textures", 0)
 
     def ctx(seed=None):
         sc = api.Scene(W, H, device=0).load(spec)
@@ -145,7 +150,8 @@ def run_scene(name, W, H, bounces, ref_spp, spp, smooth=False, quality=True):
 
 def main():
     smooth = "--smooth" in sys.argv[1:]
-    a = dict(kv.split("=", 1) for kv in sys.argv[1:] if kv != "--smooth")
+    textures = 2 if "--textured" in sys.argv[1:] else 1 if "--textures-on" in sys.argv[1:] else 0
+    a = dict(kv.split("=", 1) for kv in sys.argv[1:] if not kv.startswith("--"))
     names = ["cornell", "walls", "mesh100k"] if a.get("scene", "all") == "all" else [a["scene"]]
     W, H, B = int(a.get("W", 1920)), int(a.get("H", 1080)), int(a.get("bounces", 8))
     ref, spp = int(a.get("ref", 4096)), int(a.get("spp", 64))
@@ -153,10 +159,10 @@ def main():
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     for name in names:
-        r = run_scene(name, W, H, B, ref, spp, smooth, int(a.get("quality", 1)) != 0)
+        r = run_scene(name, W, H, B, ref, spp, smooth, int(a.get("quality", 1)) != 0, textures)
         print(json.dumps(r), flush=True)
         if out_dir:
-            with open(os.path.join(out_dir, "%s%s_%dx%d.json" % (name, "_smooth" if smooth else "", W, H)), "w") as f:
+            with open(os.path.join(out_dir, "%s%s%s_%dx%d.json" % (name, "_smooth" if smooth else "", ("", "_texopt", "_textured")[textures], W, H)), "w") as f:
                 json.dump(r, f, indent=1)
 
 
