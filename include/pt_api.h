@@ -297,7 +297,8 @@ int pt_debug_environment(pt_context* ctx, int32_t* w, int32_t* h, float* row_cdf
  * Option "smooth_normals" = 1 (default 0: every path computes what it computed before, bit for bit): pt_render_nee (every strategy, with
  * and without an environment) and pt_render_adaptive_ex with path PT_ADAPT_PATH_NEE shade with the interpolated normal; pt_render,
  * pt_generate_rays, pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex with PT_ADAPT_PATH_RENDER (every variant) return
- * PT_EINVAL naming the option.  pt_render_aovs, the denoisers and pt_temporal_accumulate keep the geometric normal.
+ * PT_EINVAL naming the option.  pt_render_aovs keeps the geometric normal; pt_render_aovs_ex with PT_AOV_SHADED writes Ns into the guides
+ * the denoisers and pt_temporal_accumulate read.
  * The estimator is pt_render_nee's with these changes at a hit of segment k (float32, fma where dot3 / cross3 / madd have it:
  * dot3(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x b.x)), cross3(a, b).x = fma(a.y, b.z, -(a.z b.y)) and cyclic, madd(u, s, w) = fma(u, s, w)):
  *   N = the record's normal, Ng = N flipped against the ray (as before), hp = madd(D, t, P), vertices r1 r2 r3, packed normals n1 n2 n3;
@@ -359,7 +360,8 @@ int pt_debug_shading_normal(pt_context* ctx, const pt_ray* rays, int64_t n, int3
  * Option "textures" = 1 (default 0: every path computes what it computed before, bit for bit): pt_render_nee (every strategy, with and
  * without an environment, with and without smooth_normals) and pt_render_adaptive_ex with path PT_ADAPT_PATH_NEE use the textured
  * albedo; pt_render, pt_generate_rays, pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex with PT_ADAPT_PATH_RENDER return
- * PT_EINVAL naming the option.  pt_render_aovs, the denoisers and pt_temporal_accumulate keep the material's kd.
+ * PT_EINVAL naming the option.  pt_render_aovs keeps the material's kd; pt_render_aovs_ex with PT_AOV_SHADED writes kd' into the guides
+ * the denoisers and pt_temporal_accumulate read.
  * The textured albedo kd' of a hit at hp = madd(D, t, P) on packed triangle ti whose material has type 0 and texture T bound and which
  * has uvs (float32; fma as dot3 / cross3 / madd have it, see the smooth-normals block above):
  *   a1, a2, a3 = the three weights of the shading normal above (max0 included), A = (a1 + a2) + a3; not 0 < A < inf: kd' = kd;
@@ -423,6 +425,40 @@ int pt_render_aovs(pt_context* ctx, const pt_camera* cam, int32_t subpixels, int
 /* albedo_rgbm: {r, g, b, material index of the first sub-pixel's terminal hit or -1}; normal_depth: {nx, ny, nz, depth};
  * 16 B each per local pixel, either pointer may be NULL */
 int pt_read_aovs(pt_context* ctx, float* albedo_rgbm, float* normal_depth, int64_t npix);
+/* Shaded guides (new: the guides of what pt_render_nee shades with under options "smooth_normals" and "textures").
+ * pt_aov_defaults: subpixels 1, specular_depth 4, shading PT_AOV_GEOMETRIC.  pt_render_aovs_ex with PT_AOV_GEOMETRIC IS
+ * pt_render_aovs(ctx, cam, subpixels, specular_depth): the same kernel instance, the same bits.  With PT_AOV_SHADED it follows the two
+ * options as they are at the call, the way pt_render_nee does, and runs their lazy repack (k_pack_vertex_normals / k_pack_vertex_uvs,
+ * the texture copies) on the context's stream first.  Sub-pixel rays, raster order, sums, normalisation, depth, the material index, the
+ * miss rule and the layout are pt_render_aovs's; float32, fma where dot3 / cross3 / madd have it (the smooth-normals block above).
+ * At every hit of a chain, with the ray (P, D) and the hit distance t:
+ *   N = the record's normal, Ng = N flipped against the ray (dot3(D, N) > 0 ? -N : N), hp = madd(D, t, P);
+ *   (Ns, kd') = the shading normal and the textured albedo of the two blocks above, from ONE evaluation of a1, a2, a3 (the device
+ *   function shading_normal_albedo that k_nee calls); Ns = Ng, the same bits, when "smooth_normals" is off or the triangle has no vertex
+ *   normals (or by the fall-backs of that block); kd' = kd, the same bits, when "textures" is off, nothing is bound, the triangle has
+ *   no uvs or the type is not 0.
+ * Specular step (type 1 or 2 at chain depth d < specular_depth), evaluated with X = Ns:
+ *   w = D - (X * dot3(X, D)) * 2.0f; for type 2, n = the material's n (1.0f / n when inside), cosa = dot3(-D, X),
+ *   disc = 1.0f - (fmaf(-cosa, cosa, 1.0f) / n) / n, and iff disc > 0 the step refracts: w = madd(X, cosa / n - sqrtf(disc), D / n);
+ *   geometric side (the rule of the estimator, without the LCG draw): if dot3(w, Ng) <= 0 for a reflection or >= 0 for a refraction, the
+ *   whole step -- direction, cosa, disc, the choice -- is evaluated again with X = Ng, and that evaluation stands;
+ *   the next ray is D' = normalize(w) from hp + 0.001f Ng (reflection) or hp - 0.001f Ng (refraction); a mirror multiplies the tint by
+ *   its F0, a refraction toggles `inside`, as in pt_render_aovs.
+ * Terminal hit: albedo = tint x a with a = kd' + emission (type 0), kd + emission (type 3), F0 (a terminal mirror), 1 (a terminal
+ * dielectric); the normal is Ns.
+ * With both options off -- or on, with no vertex normals recorded and nothing bound -- the shaded guides are pt_render_aovs's bit for bit.
+ * Touches neither colors, rnds, rays nor current_sample; allowed while an adaptive frame is held; any context (tiled ranks: their
+ * local pixels, at global pixel ids).  PT_EINVAL, checked before the device (PT_ENODEVICE on a host-only context): params NULL,
+ * subpixels outside 1..8, specular_depth outside 0..16, shading outside {0, 1}.
+ * Consumers (pt_denoise, pt_denoise_variance, pt_temporal_accumulate, pt_denoise_temporal, pt_read_aovs) use whichever guides were
+ * rendered last.  Shaded guides are a snapshot of the scene's shading data: pt_set_vertex_normals, pt_clear_vertex_normals,
+ * pt_compute_vertex_normals, pt_set_vertex_uvs, pt_clear_vertex_uvs, pt_add_texture, pt_clear_textures and pt_set_material_texture make
+ * them stale exactly as an upload does (the consumers return PT_EINVAL until guides are rendered again, and the first guides after that
+ * drop the temporal history); geometric guides are not affected by those calls, and changing the two options invalidates neither. */
+enum { PT_AOV_GEOMETRIC = 0, PT_AOV_SHADED = 1 };
+typedef struct { int32_t subpixels, specular_depth, shading; } pt_aov_params;
+void pt_aov_defaults(pt_aov_params* p);
+int pt_render_aovs_ex(pt_context* ctx, const pt_camera* cam, const pt_aov_params* params);
 /* The filter (Dammertz et al. 2010, the spatial part of SVGF), L = iterations:
  *   x0 = c / max(a, 1e-3) per channel with demodulate (a: the guides' albedo), else c;
  *   iteration i = 0..L-1, step s = 2^i, taps q = p + s (dx, dy), dx, dy in -2..2; taps outside the frame are skipped:
@@ -439,9 +475,9 @@ typedef struct { int32_t iterations; float sigma_color, sigma_normal, sigma_dept
  * sweep of tools/denoise_bench.py at 1920x1080, 8 bounces -- the same on the Cornell box and on MESH-100k.  The RMSE gain is
  * small (3-4 %: caustic fireflies dominate the error), see profiles/denoise/README.md */
 void pt_denoise_defaults(pt_denoise_params* p);
-/* Filters the context's colors (the bound framebuffer, if any) with the last pt_render_aovs guides into a buffer of its
- * own; colors is never written.  World-1 contexts only.  PT_EINVAL without guides, after pt_upload_triangles /
- * pt_upload_materials made them stale, for iterations outside 1..10 or negative / NaN sigmas.  Two launches' worth of
+/* Filters the context's colors (the bound framebuffer, if any) with the last pt_render_aovs / pt_render_aovs_ex guides into a buffer
+ * of its own; colors is never written.  World-1 contexts only.  PT_EINVAL without guides, after pt_upload_triangles /
+ * pt_upload_materials (or, for shaded guides, an authoring call listed above) made them stale, for iterations outside 1..10 or negative / NaN sigmas.  Two launches' worth of
  * buffers (32 B/px) are allocated on first use. */
 int pt_denoise(pt_context* ctx, const pt_denoise_params* p);
 int pt_read_denoised(pt_context* ctx, float* out_rgba, int64_t npix);   /* float3 @ 16 B, colors' layout (row 0 = bottom) */

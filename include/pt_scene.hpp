@@ -142,6 +142,8 @@ public:
     void render_aovs(int subpixels = 1, int specular_depth = 4) {
         ck(pt_render_aovs(ctx, &camera, subpixels, specular_depth));
     }
+    // the same through pt_render_aovs_ex: p.shading = PT_AOV_SHADED writes the shading normal and the textured albedo of the NEE path
+    void render_aovs(const pt_camera& cam, const pt_aov_params& p) { ck(pt_render_aovs_ex(ctx, &cam, &p)); }
     void denoise(const pt_denoise_params* p = nullptr) {
         pt_denoise_params d;
         pt_denoise_defaults(&d);

@@ -52,7 +52,7 @@ EXPORTS = [
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
-    "pt_render_aovs", "pt_read_aovs", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
+    "pt_render_aovs", "pt_read_aovs", "pt_aov_defaults", "pt_render_aovs_ex", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
     "pt_set_option", "pt_get_stat", "pt_debug_bvh_sizes", "pt_debug_bvh_copy", "pt_debug_wide_nodes", "pt_debug_encounter_rank", "pt_debug_tile_cost", "pt_debug_adaptive_list", "pt_debug_launch_plan",
@@ -145,6 +145,8 @@ def _load():
     sig("pt_debug_reproject", C.c_int, vp, vp, i32, i32, f32, fp)
     sig("pt_render_aovs", C.c_int, vp, vp, i32, i32)
     sig("pt_read_aovs", C.c_int, vp, vp, vp, i64)
+    sig("pt_aov_defaults", None, vp)
+    sig("pt_render_aovs_ex", C.c_int, vp, vp, vp)
     sig("pt_denoise_defaults", None, vp)
     sig("pt_denoise", C.c_int, vp, vp)
     sig("pt_read_denoised", C.c_int, vp, vp, i64)
@@ -340,6 +342,25 @@ class DenoiseVarianceParams(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+PT_AOV_GEOMETRIC, PT_AOV_SHADED = 0, 1
+AOV_SHADING = {"geometric": PT_AOV_GEOMETRIC, "shaded": PT_AOV_SHADED}
+
+
+class AovParams(C.Structure):
+    """pt_aov_params (include/pt_api.h)."""
+    _fields_ = [("subpixels", C.c_int32), ("specular_depth", C.c_int32), ("shading", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def aov_defaults():
+    """pt_aov_defaults as a dict: subpixels, specular_depth, shading."""
+    p = AovParams()
+    LIB.pt_aov_defaults(C.byref(p))
+    return p.as_dict()
 
 
 def denoise_variance_defaults():
@@ -774,9 +795,17 @@ class Scene:
         return ptr
 
     # -- guide buffers + a-trous denoiser (include/pt_api.h pins both)
-    def render_aovs(self, subpixels=1, specular_depth=4):
-        """Guide buffers of the current view (pt_render_aovs): albedo, normal, depth per local pixel; touches no render state."""
-        self._ck(LIB.pt_render_aovs(self._h, _ptr(self.camera), int(subpixels), int(specular_depth)))
+    def render_aovs(self, subpixels=1, specular_depth=4, shading="geometric"):
+        """Guide buffers of the current view: albedo, normal, depth per local pixel; touches no render state.  shading="geometric"
+        (pt_render_aovs): the geometric normal and the material's kd; "shaded" (pt_render_aovs_ex, PT_AOV_SHADED): the shading normal and
+        the textured albedo of the NEE path under options "smooth_normals" / "textures" as they are now."""
+        if shading not in AOV_SHADING:
+            raise ValueError("shading must be 'geometric' or 'shaded', not %r" % (shading,))
+        if AOV_SHADING[shading] == PT_AOV_GEOMETRIC:
+            self._ck(LIB.pt_render_aovs(self._h, _ptr(self.camera), int(subpixels), int(specular_depth)))
+            return
+        p = AovParams(int(subpixels), int(specular_depth), PT_AOV_SHADED)
+        self._ck(LIB.pt_render_aovs_ex(self._h, _ptr(self.camera), C.byref(p)))
 
     def read_aovs(self):
         """(albedo_rgbm, normal_depth), each (local_pixels, 4) float32: {r, g, b, material or -1}, {nx, ny, nz, depth or -1}."""

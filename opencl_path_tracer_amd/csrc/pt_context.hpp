@@ -140,6 +140,8 @@ struct pt_context {
     float4* d_dn = nullptr;
     float4* d_denoised = nullptr;
     bool aov_valid = false;            // pt_render_aovs ran and no pt_upload_triangles / pt_upload_materials has made its guides stale
+    bool aov_shaded = false;           // the guides are shaded ones (pt_render_aovs_ex, PT_AOV_SHADED): the authoring calls for vertex normals,
+                                       // uvs, textures and bindings make them stale too (shaded_guides_stale, pt_host.cpp)
     // option "moments": render launches fold the second moment into colors[].w; moments_valid = every launch of the current frame did
     // (note_moments); the variance read-out (pt_read_variance, pt_denoise_variance) lives in d_variance, allocated on first use
     int moments = 0;

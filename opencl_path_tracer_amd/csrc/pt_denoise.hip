@@ -1,6 +1,7 @@
 // pt_denoise.hip -- guide buffers (pt_render_aovs) and the edge-avoiding a-trous filter over them (pt_denoise).
 //   k_aovs      one lane per local pixel, persistent blocks: n x n fixed sub-pixel camera rays through the render kernels'
 //               traversal (pt_device.hpp), a short deterministic specular chain, then albedo / normal / depth (include/pt_api.h)
+//               k_aovs<.., AovShade>: the same pass with the shading normal and the textured albedo of the NEE path (pt_render_aovs_ex)
 //   k_atrous    one launch per iteration, 32x8 blocks, 5x5 taps at step 2^i; demodulation fused into the first launch and
 //               remodulation into the last
 // The specular step below restates what shade_hit does for types 1 and 2 without the random draw.
@@ -9,8 +10,20 @@
 namespace ptamd {
 
 // ---------------------------------------------------------------------------- AOV pass
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spec_depth, long long npix, float4* albedo_rgbm, float4* normal_depth) {
+// The shaded form (pt_render_aovs_ex with PT_AOV_SHADED) takes one more argument, an AovShade: every chain hit then runs
+// shading_normal_albedo() as k_nee does, the specular step is evaluated with Ns and falls back to Ng on the wrong geometric side, offsets
+// use Ng, and the terminal hit gives Ns and the textured albedo (pinned in include/pt_api.h).  The loads that adds happen once per chain
+// hit, outside the traversal.  Without the argument the kernel compiles to what it was before the shaded form existed.
+struct AovShade {
+    const float4* vn;              // packed vertex normals; nullptr: option smooth_normals is off
+    TexView tv;                    // tv.uv == nullptr: option textures is off
+};
+PT_DEV const AovShade& only(const AovShade& s) { return s; }
+
+template <int MODE, int BLOCK, class... SH>
+__global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spec_depth, long long npix, float4* albedo_rgbm, float4* normal_depth,
+                                                SH... shade) {
+    constexpr bool SHADED = sizeof...(SH) != 0;
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
@@ -43,6 +56,51 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
                         const int mi = p.meta[ti].mati;
                         const pt_material* __restrict__ m = &p.mats[mi];
                         const int type = m->type;
+                        if constexpr (SHADED) {
+                            const f3 Ng = dot3(D, N) > 0.0f ? -N : N;
+                            const f3 hp = madd(D, t, P);
+                            f3 kd = mk(0.f, 0.f, 0.f);
+                            if (type == 0 || type == 3) kd = ldf3(m->kd);
+                            const AovShade& sh = only(shade...);
+                            const f3 Ns = shading_normal_albedo(sh.vn, sh.tv, p.tris, ti, D, hp, N, Ng, sh.tv.uv ? type : -1, mi, &kd);
+                            if ((type == 1 || type == 2) && d < spec_depth) {
+                                float n = 1.0f;
+                                if (type == 2) {
+                                    n = m->n;
+                                    if (inside) n = 1.0f / n;
+                                }
+                                f3 dnew;
+                                bool refr;
+                                auto eval = [&](f3 Nx) {
+                                    dnew = D - (Nx * dot3(Nx, D)) * 2.0f;
+                                    refr = false;
+                                    if (type == 2) {
+                                        const float cosa = dot3(-D, Nx);
+                                        const float disc = 1.0f - (fmaf_(-cosa, cosa, 1.0f) / n) / n;
+                                        if (disc > 0.0f) {
+                                            const f3 dn = mk(D.x / n, D.y / n, D.z / n);
+                                            dnew = madd(Nx, cosa / n - __builtin_sqrtf(disc), dn);
+                                            refr = true;
+                                        }
+                                    }
+                                };
+                                eval(Ns);
+                                const float g = dot3(dnew, Ng);
+                                if (refr ? g >= 0.0f : g <= 0.0f) eval(Ng);      // the wrong geometric side: once more with Ng, and that stands
+                                if (type == 1) tint = tint * ldf3(m->F0);
+                                if (refr) inside = !inside;
+                                D = normalize3(dnew);
+                                P = madd(Ng, refr ? -0.001f : 0.001f, hp);
+                                ti = closest_hit<MODE, false>(sv, P, D, stk, &t, &wc);
+                                if (ti < 0) break;          // escaped: albedo 0, normal 0
+                                continue;
+                            }
+                            const f3 a = type == 1 ? ldf3(m->F0) : type == 2 ? mk(1.f, 1.f, 1.f) : kd + ldf3(m->emission);
+                            alb = tint * a;
+                            nrm = Ns;
+                            mat = (float)mi;
+                            break;
+                        }
                         if (dot3(D, N) > 0.0f) N = -N;
                         if ((type == 1 || type == 2) && d < spec_depth) {
                             const f3 hp = madd(D, t, P);
@@ -89,6 +147,12 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
         }
         normal_depth[i] = make_float4(nout.x, nout.y, nout.z, hits ? st / (float)hits : -1.0f);
     }
+}
+
+hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
+                              const float4* vn, const TexView& tv, int cu_count, hipStream_t stream) {
+    return launch_lanes([](auto s) { return k_aovs<s.mode, s.block, AovShade>; }, p, npix, cu_count, stream, subpixels, specular_depth,
+                        (long long)npix, albedo_rgbm, normal_depth, AovShade{vn, tv});
 }
 
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,

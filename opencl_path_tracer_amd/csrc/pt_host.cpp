@@ -497,6 +497,41 @@ int pt_render_aovs(pt_context* ctx, const pt_camera* cam, int32_t subpixels, int
     // the old scene, and every accumulate needs guides, so this is where it is dropped
     if (!ctx->aov_valid) ctx->temporal_history = false;
     ctx->aov_valid = true;
+    ctx->aov_shaded = false;
+    ctx->aov_cam = *cam;
+    ++ctx->aov_serial;
+    return PT_OK;
+}
+void pt_aov_defaults(pt_aov_params* p) {
+    if (!p) return;
+    p->subpixels = 1;
+    p->specular_depth = 4;
+    p->shading = PT_AOV_GEOMETRIC;
+}
+int pt_render_aovs_ex(pt_context* ctx, const pt_camera* cam, const pt_aov_params* ap) {
+    if (!ctx) return PT_EINVAL;
+    if (!ap) return fail(ctx, PT_EINVAL, "pt_render_aovs_ex: params is NULL");
+    if (ap->subpixels < 1 || ap->subpixels > 8) return fail(ctx, PT_EINVAL, "pt_render_aovs_ex: subpixels must be 1..8");
+    if (ap->specular_depth < 0 || ap->specular_depth > 16) return fail(ctx, PT_EINVAL, "pt_render_aovs_ex: specular_depth must be 0..16");
+    if (ap->shading != PT_AOV_GEOMETRIC && ap->shading != PT_AOV_SHADED)
+        return fail(ctx, PT_EINVAL, "pt_render_aovs_ex: shading must be PT_AOV_GEOMETRIC or PT_AOV_SHADED");
+    if (ap->shading == PT_AOV_GEOMETRIC) return pt_render_aovs(ctx, cam, ap->subpixels, ap->specular_depth);
+    PT_NEED_DEVICE(ctx);
+    int rc = check_ready(ctx, cam);
+    if (rc != PT_OK) return rc;
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    const float4* vn = nullptr;        // option smooth_normals: the packed vertex normals
+    if ((rc = smooth_prepare(ctx, &vn)) != PT_OK) return rc;
+    TexView tv;                        // option textures: uvs, texels, descriptors, bindings
+    if ((rc = texture_prepare(ctx, &tv)) != PT_OK) return rc;
+    if (!ctx->d_aov) PT_HIP(ctx, hipMalloc((void**)&ctx->d_aov, 2 * sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
+    RenderParams p;
+    fill_params(ctx, cam, &p);         // the render kernels' node placement
+    PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->cu_count,
+                                   ctx->stream));
+    if (!ctx->aov_valid) ctx->temporal_history = false;      // (as pt_render_aovs: the first guides after stale ones)
+    ctx->aov_valid = true;
+    ctx->aov_shaded = true;
     ctx->aov_cam = *cam;
     ++ctx->aov_serial;
     return PT_OK;
@@ -887,6 +922,12 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     return PT_OK;
 }
 
+// Shaded guides (pt_render_aovs_ex, PT_AOV_SHADED) are a snapshot of the vertex normals, uvs, textures and bindings: an authoring call
+// for any of them makes them stale, as an upload makes any guides stale.  Geometric guides read none of that and stay valid.
+static void shaded_guides_stale(pt_context* ctx) {
+    if (ctx->aov_shaded) ctx->aov_valid = false;
+}
+
 // ---- smooth shading from vertex normals (kernels: pt_smooth.hip, pt_nee.hip; pinned in include/pt_api.h)
 static bool vn_has(const float* n) {
     for (int c = 0; c < 3; ++c) {
@@ -905,6 +946,7 @@ int pt_set_vertex_normals(pt_context* ctx, int64_t first, int64_t count, const f
     if (ctx->vnormals.size() < (size_t)(first + count) * 9) ctx->vnormals.resize((size_t)(first + count) * 9, 0.0f);
     std::memcpy(ctx->vnormals.data() + (size_t)first * 9, normals, sizeof(float) * 9 * (size_t)count);
     ctx->vnormals_dirty = true;
+    shaded_guides_stale(ctx);
     return PT_OK;
 }
 
@@ -912,6 +954,7 @@ int pt_clear_vertex_normals(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
     ctx->vnormals.clear();
     ctx->vnormals_dirty = true;
+    shaded_guides_stale(ctx);
     return PT_OK;
 }
 
@@ -1000,6 +1043,7 @@ int pt_compute_vertex_normals(pt_context* ctx, int32_t object, float crease_degr
             if (!good[i]) std::fill_n(ctx->vnormals.data() + (b + i) * 9, 9, 0.0f);
     }
     ctx->vnormals_dirty = true;
+    shaded_guides_stale(ctx);
     return PT_OK;
 }
 }  // extern "C"
@@ -1127,6 +1171,7 @@ int pt_add_texture(pt_context* ctx, const float* rgb, int32_t w, int32_t h, cons
     ctx->tex_texels.insert(ctx->tex_texels.end(), tex.begin(), tex.end());
     ctx->tex_desc.push_back(TexDesc{(uint32_t)first, w, h, p.filter});
     ctx->tex_dirty = true;
+    shaded_guides_stale(ctx);
     return (int)ctx->tex_desc.size() - 1;
 }
 
@@ -1136,6 +1181,7 @@ int pt_clear_textures(pt_context* ctx) {
     ctx->tex_desc.clear();
     ctx->mat_tex.clear();
     ctx->tex_dirty = true;
+    shaded_guides_stale(ctx);
     return PT_OK;
 }
 
@@ -1146,6 +1192,7 @@ int pt_set_material_texture(pt_context* ctx, int32_t material, int32_t texture) 
     if (ctx->mat_tex.size() <= (size_t)material) ctx->mat_tex.resize((size_t)material + 1, -1);
     ctx->mat_tex[(size_t)material] = texture;
     ctx->tex_dirty = true;
+    shaded_guides_stale(ctx);
     return PT_OK;
 }
 
@@ -1179,6 +1226,7 @@ int pt_set_vertex_uvs(pt_context* ctx, int64_t first, int64_t count, const float
     if (ctx->vuvs.size() < (size_t)(first + count) * 6) ctx->vuvs.resize((size_t)(first + count) * 6, std::numeric_limits<float>::quiet_NaN());
     std::memcpy(ctx->vuvs.data() + (size_t)first * 6, uvs, sizeof(float) * 6 * (size_t)count);
     ctx->vuvs_dirty = true;
+    shaded_guides_stale(ctx);
     return PT_OK;
 }
 
@@ -1186,6 +1234,7 @@ int pt_clear_vertex_uvs(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
     ctx->vuvs.clear();
     ctx->vuvs_dirty = true;
+    shaded_guides_stale(ctx);
     return PT_OK;
 }
 

@@ -404,6 +404,10 @@ struct TexView {
     const TexDesc* desc;         // [textures]
     const int32_t* mat_tex;      // [materials on the device] texture of a type-0 material, else -1
 };
+// the shaded guides (pt_render_aovs_ex with PT_AOV_SHADED; pt_denoise.hip): vn == nullptr: option smooth_normals is off, tv.uv == nullptr:
+// option textures is off
+hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
+                              const float4* vn, const TexView& tv, int cu_count, hipStream_t stream);
 // env == nullptr: the instances without an environment.  tiled (the rounds of pt_render_adaptive_ex): k_nee_tiles / k_nee_env_tiles over
 // the p.n_tiles 8x8 frame tiles of p.tile_list (null: the frame's tiles in order), one lane per pixel of a tile; npix is then not read
 // vn != nullptr (option smooth_normals): the smooth instances, which shade with the interpolated normal of the packed vertex normals vn

@@ -1,7 +1,7 @@
 """Temporal accumulation with reprojection (Scene.temporal_accumulate, pt_temporal_accumulate): kernel time, quality, parameter sweep.
 
-usage: python tools/temporal_bench.py [scene=cornell|mesh100k|both] [W=1920 H=1080] [bounces=8] [spp=4] [frames=16] [ref=1024]
-                                      [reps=20] [sweep=0|1] [out=FILE]
+usage: python tools/temporal_bench.py [scene=cornell|mesh100k|both|cornell_st] [W=1920 H=1080] [bounces=8] [spp=4] [frames=16] [ref=1024]
+                                      [reps=20] [sweep=0|1] [guides=geometric|shaded] [out=FILE]
 
 Per scene, at W x H and `bounces` bounces, with option moments = 1 and guides from render_aovs(1, 4):
   * the time of one pt_temporal_accumulate (defaults, a history in place): HIP events around each synchronised call after a warm-up,
@@ -10,6 +10,9 @@ Per scene, at W x H and `bounces` bounces, with option moments = 1 and guides fr
     sideways by half a pixel's footprint at 1,300 units; RMSE of the last raw frame, of the accumulated colour, of pt_denoise_temporal
     and of pt_denoise_variance on the last frame, against a `ref`-spp frame of the final camera with other seeds;
   * sweep=1: the pan sequence over max_history x normal_cos x depth_tolerance.
+scene=cornell_st is cornell_box(smooth=True, textured=True) under options smooth_normals and textures, rendered by render_nee (MIS);
+guides=shaded renders every frame's guides with render_aovs(1, 4, shading="shaded").  "kept_history" is the share of pixels whose
+accumulated sample count exceeds the frame's own, over the frame and over the pixels whose guide material is a sphere's.
 One JSON line per scene on stdout."""
 import ctypes as C
 import json
@@ -32,9 +35,32 @@ READ_B, HIST_B, WRITE_B = 48, 40, 44
 def scene_spec(name):
     if name == "cornell":
         return scenes.cornell_box()
+    if name == "cornell_st":
+        return scenes.cornell_box(smooth=True, textured=True)
     if name == "mesh100k":
         return scenes.displaced_grid_mesh(100000)
-    raise SystemExit("scene must be cornell, mesh100k or both")
+    raise SystemExit("scene must be cornell, cornell_st, mesh100k or both")
+
+
+GUIDES = "geometric"          # guides=... on the command line
+
+
+def make_scene(spec, W, H, bounces):
+    """the scene; cornell_st shades with vertex normals and textures, which only the NEE path does (frame() renders accordingly)"""
+    sc = api.Scene(W, H).load(spec)
+    sc.iterations = bounces
+    sc.nee = bool(spec.normals or spec.textures)
+    if sc.nee:
+        sc.set_option("smooth_normals", 1)
+        sc.set_option("textures", 1)
+    return sc
+
+
+def render(sc, n):
+    if sc.nee:
+        sc.render_nee(n, "mis")
+    else:
+        sc.render(n)
 
 
 def views(spec, W, steps, mode):
@@ -52,8 +78,8 @@ def views(spec, W, steps, mode):
 def frame(sc, view, spp):
     sc.set_view(*view)
     sc.current_sample = 0
-    sc.render(spp)
-    sc.render_aovs(1, 4)
+    render(sc, spp)
+    sc.render_aovs(1, 4, shading=GUIDES)
 
 
 def accumulate(sc, **kw):
@@ -67,20 +93,18 @@ def rmse(a, gt):
 
 
 def reference(spec, W, H, bounces, view, ref_spp):
-    ref = api.Scene(W, H).load(spec)
-    ref.iterations = bounces
+    ref = make_scene(spec, W, H, bounces)
     ref.set_view(*view)
     ref.upload_seeds(np.random.default_rng(12345).integers(1, 2 ** 31 - 1, W * H, dtype=np.int64).astype(np.int32))
     for _ in range(ref_spp // 64):
-        ref.render(64)
+        render(ref, 64)
     gt = ref.read_colors()[:, :3].astype(np.float64)
     ref.close()
     return gt
 
 
 def sequence(spec, W, H, bounces, spp, vs, gt, filters=True, **kw):
-    sc = api.Scene(W, H).load(spec)
-    sc.iterations = bounces
+    sc = make_scene(spec, W, H, bounces)
     sc.set_option("moments", 1)
     for v in vs:
         frame(sc, v, spp)
@@ -88,6 +112,11 @@ def sequence(spec, W, H, bounces, spp, vs, gt, filters=True, **kw):
     rgbv, n = sc.read_temporal()
     r = {"temporal": rmse(rgbv, gt), "raw": rmse(sc.read_colors(), gt), "mean_n": float(n.mean()),
          "mean_temporal": float(rgbv[:, :3].astype(np.float64).mean()), "mean_ref": float(gt.mean())}
+    mat = sc.read_aovs()[0][:, 3]
+    spheres = (mat == scenes.CHROMIUM) | (mat == scenes.GLASS)
+    r["kept_history"] = float(np.mean(n > spp))
+    if spheres.any():
+        r["kept_history_spheres"] = float(np.mean(n[spheres] > spp))
     if filters:
         r["denoise_temporal"] = rmse(sc.denoise_temporal(), gt)
         r["denoise_variance"] = rmse(sc.denoise_variance(), gt)
@@ -96,8 +125,7 @@ def sequence(spec, W, H, bounces, spp, vs, gt, filters=True, **kw):
 
 
 def time_accumulate(spec, W, H, bounces, spp, reps):
-    sc = api.Scene(W, H).load(spec)
-    sc.iterations = bounces
+    sc = make_scene(spec, W, H, bounces)
     sc.set_option("moments", 1)
     vs = views(spec, W, reps + 3, "pan")
     ts = []
@@ -118,7 +146,7 @@ def time_accumulate(spec, W, H, bounces, spp, reps):
 
 def run(name, W, H, bounces, spp, frames, ref_spp, reps, sweep):
     spec = scene_spec(name)
-    res = {"scene": name, "W": W, "H": H, "bounces": bounces, "spp": spp, "frames": frames, "ref_spp": ref_spp,
+    res = {"scene": name, "W": W, "H": H, "bounces": bounces, "spp": spp, "frames": frames, "ref_spp": ref_spp, "guides": GUIDES,
            "defaults": api.temporal_defaults()}
     ms = time_accumulate(spec, W, H, bounces, spp, reps)
     mb = W * H * (READ_B + HIST_B + WRITE_B) / 1e6
@@ -139,7 +167,9 @@ def run(name, W, H, bounces, spp, frames, ref_spp, reps, sweep):
 
 
 def main():
+    global GUIDES
     kv = dict(a.split("=", 1) for a in sys.argv[1:])
+    GUIDES = kv.get("guides", "geometric")
     names = ("cornell", "mesh100k") if kv.get("scene", "both") == "both" else (kv["scene"],)
     out = []
     for name in names:
