@@ -390,6 +390,55 @@ int pt_debug_vertex_uvs(const pt_context* ctx, float* uvs, int32_t* has);
  * out_tri[i] = add-order triangle or -1, out_rgbt[4 i ..] = {kd'.rgb, t} ({0, 0, 0, -1} for a miss) */
 int pt_debug_albedo(pt_context* ctx, const pt_ray* rays, int64_t n, int32_t* out_tri, float* out_rgbt);
 
+/* ---- a rough-metal (GGX) material for pt_render_nee (new: opt-in with option "glossy"; the reference has chalk, a perfect mirror, perfect
+ * glass and a lamp, and leaves the ray alone at any other material type) -----------
+ * Option "glossy" = 1 (default 0: every path computes what it computed before, bit for bit, and type 4 stays inert): pt_render_nee (every
+ * strategy, with and without an environment, smooth_normals and textures) and pt_render_adaptive_ex with PT_ADAPT_PATH_NEE shade a hit on
+ * a material of type 4 as the lobe vertex below; pt_render, pt_generate_rays, pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex
+ * with PT_ADAPT_PATH_RENDER return PT_EINVAL naming the option, checked before the device (PT_ENODEVICE).  With the option on and no
+ * material of type 4 among those uploaded last, the host launches the kernels it launches with the option off: the frame (colors, rnds,
+ * rays) is the option-off frame bit for bit.
+ * Roughness.  alpha = pt_material_roughness(shininess) = the float nearest to min(1, max(0.03, sqrt(2 / (shininess + 2)))) evaluated in
+ * double; 1 when shininess is not finite or negative.  pt_upload_materials writes it into field n of the DEVICE copy of a type-4 material
+ * (n is read for type 2 only); the host records are what they were.  kd, ks, emission and a texture binding of a type-4 material are
+ * ignored; F0 (pt_material_init: from N and K) is its colour.
+ * The vertex (float32; fma where dot3 / cross3 / madd have it, see the smooth-normals block above; sqrtf and / IEEE;
+ * normalize(v) = v * (1.0f / sqrtf(dot3(v, v)))).  A type-4 hit is a lobe vertex for every rule that speaks of lobe vertices: it takes a
+ * light sample when k + 1 < iterations, the next emitter hit or sky miss is weighted by W_b, under smooth_normals it follows the
+ * geometric-side rules of lobe vertices and offsets use Ng.  It draws exactly two LCG values rnd1, rnd2 after its light sample.
+ *   N = the shading normal (Ns under smooth_normals), (Z, X) the frame diffuse_direction builds from N (prog.cl:205-212; X = cross3(N, Z));
+ *   local coordinates v = (dot3(v, X), dot3(v, Z), dot3(v, N)); o = local(-D).
+ *   Sampling (visible normals, Heitz 2018):
+ *     Vh = normalize(alpha o.x, alpha o.y, o.z); l2 = fmaf(Vh.y, Vh.y, Vh.x Vh.x);
+ *     T1 = l2 > 0 ? (-Vh.y / sqrtf(l2), Vh.x / sqrtf(l2), 0) : (1, 0, 0); T2 = cross3(Vh, T1);
+ *     r = sqrtf(rnd1); (s, c) = the sine and cosine diffuse_direction takes of (float)(6.283185307179586 * (double)rnd2);
+ *     t1 = r c; t2 = r s; q = 0.5f (1.0f + Vh.z); t2 = fmaf(q, t2, (1.0f - q) sqrtf(max0(fmaf(-t1, t1, 1.0f))));
+ *     Nh = madd(Vh, sqrtf(max0(fmaf(-t2, t2, fmaf(-t1, t1, 1.0f)))), madd(T2, t2, T1 * t1));
+ *     h = normalize(alpha Nh.x, alpha Nh.y, max0(Nh.z)); w = madd(h, 2.0f dot3(o, h), -o), local;
+ *     the world direction before normalisation is madd(Z, w.y, madd(N, w.z, X * w.x)), handed to the tail every vertex shares.
+ *   Lobe terms (unit local vectors; a2 = alpha alpha):
+ *     D(h) = a2 / (pi (d d)) with d = fmaf(a2, h.z h.z, fmaf(h.y, h.y, h.x h.x));
+ *     G1(v) = (2.0f v.z) / (v.z + sqrtf(fmaf(a2, fmaf(v.y, v.y, v.x v.x), v.z v.z))), 0 unless v.z > 0;
+ *     p_b(w) = (G1(o) D(h)) / (4.0f o.z), 0 unless o.z > 0; for a given w (a light sample), h = normalize(o + w);
+ *     g(w) = F G1(w), F = fresnel(F0, h, -o): Schlick on |dot3(h, o)| (prog.cl:219-222), the separable Smith term (G2 / G1(o) = G1(w)).
+ *   Update: factor_S *= g(w), the factor a mirror multiplies by F.  Unless w.z > 0 the path ends after the two draws, as a lobe direction
+ *   below the geometric surface ends it (rays[] holds that direction and origin).  The new origin is hp + 0.001 Ng.
+ *   Light sample at the vertex (triangle light and sky): as pinned for pt_render_nee, with p_b = p_b(w) in place of max(0, N.w) / pi and,
+ *   for the factors the vertex's own update with w would give, fS' = fS g(w) (fL, fB unchanged); rejected unless w.z > 0 (and, under
+ *   smooth_normals, dot3(w, Ng) > 0) and unless p_b(w) > 0.
+ *   W_b of the next emitter hit or sky miss uses the p_b the vertex sampled its direction with (kept from the vertex, through the one
+ *   device function that states the density).
+ *   Preview (iterations == 1): F0 + emission.
+ * The light table, the pt_nee_rand keys, ks, kd and textures are untouched.
+ * Guides: pt_render_aovs_ex with PT_AOV_SHADED and the option on gives a terminal type-4 hit the albedo tint x F0 (as a terminal mirror; it
+ * is not followed as a specular step) and the normal Ns; with the option off, and in geometric guides, the buffers are what they were.
+ * Changing the option makes no guides stale. */
+float pt_material_roughness(float shininess);
+/* the device functions of the vertex (host-only context: PT_ENODEVICE).  Per item 9 floats in: N (unit), D (unit, toward the surface),
+ * alpha, rnd1, rnd2; 8 out: the world direction w before normalisation (3), p_b as sampled, G1(w), F.x for F0 = 0.04, p_b evaluated again
+ * from normalize(w) the way a light sample evaluates it, o.z */
+int pt_debug_glossy(pt_context* ctx, int64_t n, const float* N_D_alpha_rnd, float* out);
+
 /* ---- per-pixel variance of the mean luminance (new: opt-in with option "moments"; the reference keeps the mean only) -------
  * With option "moments" = 1 every render path (pt_render in every variant, schedule and node mode, pt_trace_rays,
  * pt_render_adaptive, pt_render_nee, tiled ranks) also folds each sample's squared luminance into colors[].w, float32 in this order:

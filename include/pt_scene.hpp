@@ -137,6 +137,9 @@ public:
     void debug_vertex_uvs(float* uvs, int32_t* has) { ck(pt_debug_vertex_uvs(ctx, uvs, has)); }
     void debug_texture(int32_t texture, float* rgb, int64_t cap, int32_t* w, int32_t* h, int32_t* filter) { ck(pt_debug_texture(ctx, texture, rgb, cap, w, h, filter)); }
     void debug_albedo(const pt_ray* rays, int64_t n, int32_t* out_tri, float* out_rgbt) { ck(pt_debug_albedo(ctx, rays, n, out_tri, out_rgbt)); }
+    // the rough metal of material type 4 (set_option("glossy", 1); render_nee only): the device functions of the vertex, 9 floats in
+    // (N, D, alpha, rnd1, rnd2) and 8 out per item (pt_debug_glossy)
+    void debug_glossy(int64_t n, const float* N_D_alpha_rnd, float* out) { ck(pt_debug_glossy(ctx, n, N_D_alpha_rnd, out)); }
     // guide buffers of the current view (pt_render_aovs) and the a-trous filter over them (pt_denoise; p = NULL: the defaults)
     // (the view of the last render: a new Camera(globals) would move a moving camera once more)
     void render_aovs(int subpixels = 1, int specular_depth = 4) {

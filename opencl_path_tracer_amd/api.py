@@ -49,6 +49,7 @@ EXPORTS = [
     "pt_set_vertex_normals", "pt_clear_vertex_normals", "pt_compute_vertex_normals", "pt_debug_vertex_normals", "pt_debug_shading_normal",
     "pt_texture_defaults", "pt_add_texture", "pt_clear_textures", "pt_set_material_texture", "pt_debug_texture",
     "pt_set_vertex_uvs", "pt_clear_vertex_uvs", "pt_debug_vertex_uvs", "pt_debug_albedo", "pt_image_read_ppm",
+    "pt_material_roughness", "pt_debug_glossy",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
@@ -127,6 +128,8 @@ def _load():
     sig("pt_debug_vertex_uvs", C.c_int, vp, vp, vp)
     sig("pt_debug_albedo", C.c_int, vp, vp, i64, vp, vp)
     sig("pt_image_read_ppm", C.c_int, C.c_char_p, vp, i64, C.POINTER(i32), C.POINTER(i32))
+    sig("pt_material_roughness", f32, f32)
+    sig("pt_debug_glossy", C.c_int, vp, i64, vp, vp)
     sig("pt_environment_defaults", None, vp)
     sig("pt_set_environment", C.c_int, vp, vp, i32, i32, vp)
     sig("pt_clear_environment", C.c_int, vp)
@@ -285,6 +288,11 @@ def adaptive_defaults():
 def nee_rand(state, segment, dim):
     """pt_nee_rand: the counter-based hash the light samples of Scene.render_nee draw from (include/pt_api.h pins it)."""
     return int(LIB.pt_nee_rand(int(state) & 0xffffffff, int(segment), int(dim)))
+
+
+def material_roughness(shininess):
+    """pt_material_roughness: the GGX alpha a type-4 material of that shininess gets under option "glossy" (include/pt_api.h)."""
+    return float(LIB.pt_material_roughness(float(shininess)))
 
 
 class EnvironmentParams(C.Structure):
@@ -620,6 +628,15 @@ class Scene:
         out = np.empty((rays.shape[0], 4), dtype=np.float32)
         self._ck(LIB.pt_debug_albedo(self._h, _ptr(rays), rays.shape[0], _ptr(tri), _ptr(out)))
         return tri, out
+
+    # -- the rough metal of material type 4 (option "glossy")
+    def debug_glossy(self, items):
+        """pt_debug_glossy: items (n, 9) float32 {N, D, alpha, rnd1, rnd2} -> (n, 8) float32 {w before normalisation (world), p_b as
+        sampled, G1(w), F.x with F0 = 0.04, p_b evaluated again from w, o.z}, by the device functions the glossy k_nee instances call."""
+        items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 9)
+        out = np.empty((items.shape[0], 8), dtype=np.float32)
+        self._ck(LIB.pt_debug_glossy(self._h, items.shape[0], _ptr(items), _ptr(out)))
+        return out
 
     def upload_Triangles(self):
         self._ck(LIB.pt_upload_triangles(self._h))

@@ -210,6 +210,10 @@ struct pt_context {
     float4* d_vuvs = nullptr;
     size_t vuvs_cap = 0;               // packed triangles d_vuvs has room for
     int obj_textures_loaded = 0, obj_textures_skipped = 0;      // map_Kd lines of the last pt_add_obj
+    // rough metal (option glossy; pinned in include/pt_api.h): material type 4 is a GGX lobe vertex in pt_render_nee.  The glossy k_nee
+    // instances run only when the option is on AND the materials uploaded last hold a type-4 one; every other frame is today's launch
+    int glossy = 0;
+    bool glossy_mats = false;          // pt_upload_materials saw a material of type 4
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)

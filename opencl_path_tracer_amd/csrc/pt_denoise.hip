@@ -17,6 +17,7 @@ namespace ptamd {
 struct AovShade {
     const float4* vn;              // packed vertex normals; nullptr: option smooth_normals is off
     TexView tv;                    // tv.uv == nullptr: option textures is off
+    int glossy;                    // option glossy: a terminal type-4 hit is a metal (albedo tint x F0)
 };
 PT_DEV const AovShade& only(const AovShade& s) { return s; }
 
@@ -95,7 +96,7 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
                                 if (ti < 0) break;          // escaped: albedo 0, normal 0
                                 continue;
                             }
-                            const f3 a = type == 1 ? ldf3(m->F0) : type == 2 ? mk(1.f, 1.f, 1.f) : kd + ldf3(m->emission);
+                            const f3 a = type == 1 || (type == 4 && sh.glossy) ? ldf3(m->F0) : type == 2 ? mk(1.f, 1.f, 1.f) : kd + ldf3(m->emission);
                             alb = tint * a;
                             nrm = Ns;
                             mat = (float)mi;
@@ -150,9 +151,9 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
 }
 
 hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
-                              const float4* vn, const TexView& tv, int cu_count, hipStream_t stream) {
+                              const float4* vn, const TexView& tv, int glossy, int cu_count, hipStream_t stream) {
     return launch_lanes([](auto s) { return k_aovs<s.mode, s.block, AovShade>; }, p, npix, cu_count, stream, subpixels, specular_depth,
-                        (long long)npix, albedo_rgbm, normal_depth, AovShade{vn, tv});
+                        (long long)npix, albedo_rgbm, normal_depth, AovShade{vn, tv, glossy});
 }
 
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,

@@ -1061,6 +1061,99 @@ PT_DEV f3 fresnel(f3 F0, f3 N, f3 D) {
     return mk(fmaf_(1.0f - F0.x, p5, F0.x), fmaf_(1.0f - F0.y, p5, F0.y), fmaf_(1.0f - F0.z, p5, F0.z));
 }
 
+// ---- rough metal, material type 4 under option glossy (GGX with visible-normal sampling; include/pt_api.h pins every operation)
+// All vectors are local to the frame (X, Z, N) that frame_from_rl builds: v = (v.X, v.Z, v.N), so v.z is the cosine to the normal.
+PT_DEV float glossy_D(float alpha, f3 h) {
+    const float a2 = alpha * alpha;
+    const float d = fmaf_(a2, h.z * h.z, fmaf_(h.y, h.y, h.x * h.x));
+    return a2 / (3.14159265358979323846f * (d * d));
+}
+PT_DEV float glossy_G1(float alpha, f3 v) {
+    if (!(v.z > 0.0f)) return 0.0f;
+    return (2.0f * v.z) / (v.z + __builtin_sqrtf(fmaf_(alpha * alpha, fmaf_(v.y, v.y, v.x * v.x), v.z * v.z)));
+}
+// p_b of the direction whose half vector with o is h: the ONE statement of the density -- the sampler, the light sample and W_b go through it
+PT_DEV float glossy_pdf(float alpha, f3 o, f3 h) {
+    if (!(o.z > 0.0f)) return 0.0f;
+    return (glossy_G1(alpha, o) * glossy_D(alpha, h)) / (4.0f * o.z);
+}
+// p_b of a given unit direction w (the light sample's); *h = normalize(o + w)
+PT_DEV float glossy_pdf_of(float alpha, f3 o, f3 w, f3* h) {
+    *h = normalize3(o + w);
+    return glossy_pdf(alpha, o, *h);
+}
+// the weight g(w) = F G1(w) the vertex multiplies factor_S by; the ray direction in the frame is -o
+PT_DEV f3 glossy_weight(float alpha, f3 F0, f3 o, f3 h, f3 w) { return fresnel(F0, h, -o) * glossy_G1(alpha, w); }
+PT_DEV f3 to_local(f3 v, f3 X, f3 Z, f3 N) { return mk(dot3(v, X), dot3(v, Z), dot3(v, N)); }
+// visible-normal sampling (Heitz 2018) from the disc point (t1, t2) = sqrt(rnd1) (cos, sin)(2 pi rnd2): the half vector h and the
+// reflected direction w = 2 (o.h) h - o, both local
+PT_DEV f3 glossy_sample(float alpha, f3 o, float t1, float t2, f3* h_out) {
+    const f3 Vh = normalize3(mk(alpha * o.x, alpha * o.y, o.z));
+    const float l2 = fmaf_(Vh.y, Vh.y, Vh.x * Vh.x);
+    f3 T1 = mk(1.0f, 0.0f, 0.0f);
+    if (l2 > 0.0f) {
+        const float l = __builtin_sqrtf(l2);
+        T1 = mk(-Vh.y / l, Vh.x / l, 0.0f);
+    }
+    const f3 T2 = cross3(Vh, T1);
+    const float q = 0.5f * (1.0f + Vh.z);
+    t2 = fmaf_(q, t2, (1.0f - q) * __builtin_sqrtf(max0(fmaf_(-t1, t1, 1.0f))));
+    const float t3 = __builtin_sqrtf(max0(fmaf_(-t2, t2, fmaf_(-t1, t1, 1.0f))));
+    const f3 Nh = madd(Vh, t3, madd(T2, t2, T1 * t1));
+    const f3 h = normalize3(mk(alpha * Nh.x, alpha * Nh.y, max0(Nh.z)));
+    *h_out = h;
+    return madd(h, 2.0f * dot3(o, h), -o);
+}
+// what the sampled glossy vertex leaves behind
+struct GlossyOut {
+    f3 F;            // g(w) = F g1w, as glossy_weight states it
+    float g1w;
+    float pb;        // p_b as sampled
+    float wz;        // w.z: the path ends unless it is > 0
+    float oz;        // (pt_debug_glossy)
+};
+// The direction (before normalisation) of a lobe vertex in the glossy instances: diffuse_direction's frame, roots, sincos and world
+// sum, shared by the lanes of both kinds; only the local coordinates in between differ (gl: a type-4 vertex).  A diffuse lane gets
+// diffuse_direction's bits.
+template <bool SK>
+PT_DEV f3 lobe_direction_glossy(f3 N, f3 D, bool gl, float alpha, f3 F0, float rnd1, float rnd2, GlossyOut* out) {
+    bool yaxis;
+    const float l2 = frame_l2(N, &yaxis);
+    float rl, r;
+    if (wave_all(rsqrt_window(l2) && rnd1 >= kSqrtWindowLo && rnd1 < 1.0f)) {
+        rl = rsqrt_core(l2);
+        r = sqrt_core(rnd1);
+    } else {
+        rl = 1.0f / __builtin_sqrtf(l2);
+        r = __builtin_sqrtf(rnd1);
+    }
+    f3 Z, X;
+    frame_from_rl(N, yaxis, rl, &Z, &X);
+    const float theta = (float)(6.283185307179586 * (double)rnd2);
+    float sn, cs;
+    spec_sincos<SK>(theta, &sn, &cs);
+    float x = r * cs, y = r * sn, z;
+    if (gl) {
+        const f3 o = to_local(-D, X, Z, N);
+        f3 h;
+        const f3 w = glossy_sample(alpha, o, x, y, &h);
+        out->pb = glossy_pdf(alpha, o, h);
+        out->g1w = glossy_G1(alpha, w);
+        out->F = fresnel(F0, h, -o);
+        out->wz = w.z;
+        out->oz = o.z;
+        x = w.x;
+        y = w.y;
+        z = w.z;
+    } else {
+        z = sqrt_rn(1.0f - rnd1);
+    }
+    f3 d = X * x;
+    d = madd(N, z, d);
+    d = madd(Z, y, d);
+    return d;
+}
+
 // ---------------------------------------------------------------------------- path state + shading
 // The path state of prog.cl:307-316: ray (P, D), LCG state and inside-glass flag are plain local variables of the
 // caller; the four factors and the colour travel as one PathRegs.  (Round 3 also tried them in global memory behind the
@@ -1096,10 +1189,14 @@ struct PathRegs {
 // A hook with `textured` set (it has `smooth` too) also supplies the albedo of a type-0 vertex (option textures, pinned in
 // include/pt_api.h): shading_normal_albedo() below, one evaluation of the barycentric weights for the normal and the uv; every
 // statement that does so sits under `if constexpr (HOOK::textured)`.
+// A hook with `glossy` set (it has `textured` too) makes material type 4 a lobe vertex, the rough metal of option glossy (pinned in
+// include/pt_api.h): lobe_direction_glossy() above in place of diffuse_direction, the vertex's p_b kept in the hook; every statement
+// that does so sits under `if constexpr (HOOK::glossy)`.
 struct NoShadeHook {
     static constexpr bool active = false;
     static constexpr bool smooth = false;
     static constexpr bool textured = false;
+    static constexpr bool glossy = false;
 };
 
 // The interpolated shading normal of a hit at hp = madd(D, t, P) on packed triangle ti (include/pt_api.h pins every operation): vn =
@@ -1240,12 +1337,23 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     if constexpr (HOOK::textured) {
         static_assert(HOOK::smooth && !REC, "the textured instances are built on the smooth ones");
         N = hook->shading_attributes_at(p, tris, ti, rD, hp, flip ? -N : N, N, type, m);
-        if (p.iterations == 1) st.setC(hook->albedo(m) + ldf3(m->emission));
+        if constexpr (HOOK::glossy) {
+            if (p.iterations == 1) st.setC((type == 4 ? ldf3(m->F0) : hook->albedo(m)) + ldf3(m->emission));
+        } else {
+            if (p.iterations == 1) st.setC(hook->albedo(m) + ldf3(m->emission));
+        }
     } else if constexpr (HOOK::smooth) N = hook->shading_normal_at(tris, ti, rD, hp, flip ? -N : N, N);
     // Every material that continues the path ends the same way: normalise the new direction, step off the surface
     // along +-N.  The two sampling branches below only produce the direction BEFORE normalisation and the side; the
     // tail is shared, so a wave that holds both kinds of hit runs one normalisation (IEEE sqrt + divide), not two.
-    const bool lobe = type == 0 || type == 3, spec = type == 1 || type == 2;
+    bool lobe = type == 0 || type == 3;
+    const bool spec = type == 1 || type == 2;
+    bool gl = false;                                                        // a rough-metal vertex (type 4 under option glossy)
+    if constexpr (HOOK::glossy) {
+        static_assert(HOOK::textured, "the glossy instances are built on the textured ones");
+        gl = type == 4;
+        lobe = lobe || gl;
+    }
     f3 dnew = rD;
     float side = 0.001f;
     float inten = 0.0f;
@@ -1256,10 +1364,12 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         inten = max0(dot3(-rD, N));
         if constexpr (HOOK::active) {
             if (type == 3) wb = hook->emitter_weight(ti, t, inten, rD);
-            hook->light_sample(st, p, m, type, N, hp);                      // before the LCG draws and this hit's emission
+            if constexpr (HOOK::glossy) hook->light_sample(st, p, m, type, N, hp, rD);
+            else hook->light_sample(st, p, m, type, N, hp);                 // before the LCG draws and this hit's emission
         }
         const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
-        if constexpr (REC) dnew = diffuse_direction_rec<SK>(N, rec + (flip ? 4 : 2), rnd1, rnd2);
+        if constexpr (HOOK::glossy) dnew = hook->template lobe_vertex<SK>(st, m, gl, N, rD, rnd1, rnd2);
+        else if constexpr (REC) dnew = diffuse_direction_rec<SK>(N, rec + (flip ? 4 : 2), rnd1, rnd2);
         else dnew = diffuse_direction<SK>(N, rnd1, rnd2);
     } else if (spec) {
         // smooth shading: the vertex as a function of the normal, which may have to run twice (TWIN: NeeHook::spec_vertex restates the
@@ -1329,7 +1439,8 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         else st.setC(madd(e, inten, st.C()));
     }
     // any other type: the ray is left unchanged and the loop hits the same surface again
-    if constexpr (HOOK::active) hook->end_vertex(lobe, N);
+    if constexpr (HOOK::glossy) hook->end_vertex_glossy(lobe, gl, N, rD);
+    else if constexpr (HOOK::active) hook->end_vertex(lobe, N);
 }
 
 PT_DEV f3 running_mean(f3 acc, f3 color, int s) {   // prog.cl:379

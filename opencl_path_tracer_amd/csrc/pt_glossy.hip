@@ -1,0 +1,40 @@
+// pt_glossy.hip -- the rough metal of option glossy (material type 4; include/pt_api.h pins the vertex).
+//   k_debug_glossy   pt_debug_glossy: one thread per item runs lobe_direction_glossy() and glossy_pdf_of() (pt_device.hpp), the functions
+//                    the glossy k_nee instances call (pt_nee.hip) for the sampled direction and for a light sample, so that the sampler
+//                    and the density can be tested against each other and against float64 without a render.  No scene is read.
+#include "pt_device.hpp"
+
+namespace ptamd {
+
+// in: 9 floats per item {N.xyz, D.xyz, alpha, rnd1, rnd2}; out: 8 per item {w.xyz before normalisation (world), p_b as sampled, G1(w),
+// F.x with F0 = 0.04, p_b evaluated again from w, o.z}
+__global__ void __launch_bounds__(256) k_debug_glossy(const float* __restrict__ in, long long n, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* a = in + i * 9;
+    const f3 N = mk(a[0], a[1], a[2]), D = mk(a[3], a[4], a[5]);
+    const float alpha = a[6];
+    GlossyOut go;
+    const f3 d = lobe_direction_glossy<false>(N, D, true, alpha, mk(0.04f, 0.04f, 0.04f), a[7], a[8], &go);
+    // the density of the same direction by the light sample's route: world -> local, h = normalize(o + w)
+    f3 Z, X, h;
+    tangent_frame(N, &Z, &X);
+    const float again = glossy_pdf_of(alpha, to_local(-D, X, Z, N), to_local(normalize3(d), X, Z, N), &h);
+    float* o = out + i * 8;
+    o[0] = d.x;
+    o[1] = d.y;
+    o[2] = d.z;
+    o[3] = go.pb;
+    o[4] = go.g1w;
+    o[5] = go.F.x;
+    o[6] = again;
+    o[7] = go.oz;
+}
+
+hipError_t launch_debug_glossy(const float* in, int64_t n, float* out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_debug_glossy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, (long long)n, out);
+    return hipGetLastError();
+}
+
+}  // namespace ptamd

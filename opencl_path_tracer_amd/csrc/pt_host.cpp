@@ -70,6 +70,11 @@ void pt_material_init(pt_material* m, const float kd[3], const float ks[3], cons
     }
 }
 
+float pt_material_roughness(float shininess) {
+    if (!std::isfinite(shininess) || shininess < 0.0f) return 1.0f;
+    return (float)std::min(1.0, std::max(0.03, std::sqrt(2.0 / ((double)shininess + 2.0))));
+}
+
 void pt_triangle_init(pt_triangle* t, const float r1[3], const float r2[3], const float r3[3], uint16_t mati) {
     std::memset(t, 0, sizeof *t);
     float v1[3], v2[3], n[3];
@@ -300,13 +305,18 @@ int pt_upload_materials(pt_context* ctx) {
     ctx->tex_dirty = true;           // and the bindings on the device the type
     for (const pt_triangle& t : ctx->tris)
         if (t.mati >= ctx->mats.size()) return fail(ctx, PT_EINVAL, "a triangle references a material index that was never added");
+    ctx->glossy_mats = false;
+    for (const pt_material& m : ctx->mats) ctx->glossy_mats = ctx->glossy_mats || m.type == 4;
     if (ctx->has_device) {
         PT_HIP(ctx, hipSetDevice(ctx->device));
         // device copy: _pad marks materials whose specular lobe is identically zero (ks == 0, finite
         // shininess >= 0): the kernel then skips pow(), the product ks*pow being +0 either way
         std::vector<pt_material> dm(ctx->mats);
-        for (pt_material& m : dm)
+        // a type-4 material carries its roughness in n, which only type 2 reads otherwise (option glossy)
+        for (pt_material& m : dm) {
             m._pad = (m.ks.s[0] == 0.0f && m.ks.s[1] == 0.0f && m.ks.s[2] == 0.0f && std::isfinite(m.shininess) && m.shininess >= 0.0f) ? 1 : 0;
+            if (m.type == 4) m.n = pt_material_roughness(m.shininess);
+        }
         ctx->shaderec_dirty = true;
         int rc = upload_vec(ctx, &ctx->d_mats, dm.data(), sizeof(pt_material) * dm.size());
         if (rc != PT_OK) return rc;
@@ -527,7 +537,7 @@ int pt_render_aovs_ex(pt_context* ctx, const pt_camera* cam, const pt_aov_params
     if (!ctx->d_aov) PT_HIP(ctx, hipMalloc((void**)&ctx->d_aov, 2 * sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
-    PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->cu_count,
+    PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->glossy, ctx->cu_count,
                                    ctx->stream));
     if (!ctx->aov_valid) ctx->temporal_history = false;      // (as pt_render_aovs: the first guides after stale ones)
     ctx->aov_valid = true;
@@ -907,6 +917,7 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     if ((rc = smooth_prepare(ctx, &vn)) != PT_OK) return rc;
     TexView tv;                        // option textures: uvs, texels, descriptors, bindings
     if ((rc = texture_prepare(ctx, &tv)) != PT_OK) return rc;
+    const bool glossy = ctx->glossy && ctx->glossy_mats;      // option glossy without a type-4 material: today's instances
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
     p.iterations = iterations;
@@ -916,7 +927,7 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     note_frame(ctx, p.first_sample, cam);
     EventPair* ep;
     if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-    PT_HIP(ctx, launch_nee(p, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, false, vn, tv.uv ? &tv : nullptr));
+    PT_HIP(ctx, launch_nee(p, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, false, vn, tv.uv || glossy ? &tv : nullptr, glossy));
     if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
     ctx->current_sample += nsamples;
     return PT_OK;
@@ -1109,6 +1120,25 @@ int pt_debug_shading_normal(pt_context* ctx, const pt_ray* rays, int64_t n, int3
     }
     for (int64_t i = 0; i < n; ++i)
         if (out_tri[i] >= 0) out_tri[i] = ctx->orig[(size_t)out_tri[i]];      // packed -> add order
+    return PT_OK;
+}
+
+// ---- rough metal (option glossy; kernels: pt_glossy.hip, pt_nee.hip; pinned in include/pt_api.h)
+int pt_debug_glossy(pt_context* ctx, int64_t n, const float* N_D_alpha_rnd, float* out) {
+    PT_NEED_DEVICE(ctx);
+    if (n < 0 || (n > 0 && (!N_D_alpha_rnd || !out))) return fail(ctx, PT_EINVAL, "pt_debug_glossy: n >= 0, both arrays non-null");
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) (void)hipFree(p); }
+    } d_in, d_out;
+    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * 9 * (size_t)n));
+    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 8 * (size_t)n));
+    PT_HIP(ctx, hipMemcpy(d_in.p, N_D_alpha_rnd, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice));
+    PT_HIP(ctx, launch_debug_glossy((const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 8 * (size_t)n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -1428,6 +1458,9 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value) {
     } else if (k == "textures") {
         if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "textures must be 0 (the material's kd) or 1 (pt_render_nee multiplies kd by the bound albedo texture)");
         ctx->textures = (int)value;
+    } else if (k == "glossy") {
+        if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "glossy must be 0 (material type 4 is inert) or 1 (pt_render_nee shades it as a rough metal)");
+        ctx->glossy = (int)value;
     } else if (k == "timing") {
         ctx->timing = value ? 1 : 0;
     } else if (k == "count_work") {

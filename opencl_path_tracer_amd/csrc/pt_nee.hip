@@ -16,6 +16,9 @@
 //   k_nee*_smooth, k_nee*_tex  the same four kernels with smooth shading from vertex normals (option smooth_normals, DESIGN.md section
 //           5.9) and, built on that code, with albedo textures (option textures, section 5.10): NeeHook<.., SMOOTH, TEX>; what they add
 //           sits under `if constexpr (SMOOTH)` / `if constexpr (TEX)` here and under HOOK::smooth / HOOK::textured in shade_hit.
+//   k_nee*_glossy  the textured kernels with the rough metal of option glossy (material type 4): NeeHook<.., GLOSSY>;
+//           what they add sits under `if constexpr (GLOSSY)` here and under HOOK::glossy in shade_hit.  Launched only when the option is on
+//           and a type-4 material is uploaded.
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -64,13 +67,23 @@ struct TexSlot<true> {
     f3 kd = mk(0.f, 0.f, 0.f);     // the current vertex's albedo kd' (its material's kd where nothing is bound)
 };
 
+// what a hook carries for the rough metal (option glossy): nothing without it
+template <bool GLOSSY>
+struct GlossySlot {};
+template <>
+struct GlossySlot<true> {
+    float pb = 0.0f;               // p_b of the direction the previous lobe vertex sampled (these instances keep it instead of Nprev)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
-template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false>
+template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false>
 struct NeeHook {
     static_assert(SMOOTH || !TEX, "the textured instances are built on the smooth code");
+    static_assert(TEX || !GLOSSY, "the glossy instances are built on the textured code");
     static constexpr bool active = true;
     static constexpr bool smooth = SMOOTH;
     static constexpr bool textured = TEX;
+    static constexpr bool glossy = GLOSSY;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -84,6 +97,44 @@ struct NeeHook {
     EnvSlot<ENV> env;
     SmoothSlot<SMOOTH> sm;
     TexSlot<TEX> tx;
+    GlossySlot<GLOSSY> gs;
+
+    // GLOSSY: p_b of the unit direction w at the type-4 vertex with normal N reached along rD, and the factor_S its own update with w
+    // would give -- through glossy_pdf, as the sampled direction's (lobe_direction_glossy)
+    PT_DEV float glossy_light(const pt_material* __restrict__ m, f3 N, f3 rD, f3 w, f3 fS, f3* fs) const {
+        f3 Z, X;
+        tangent_frame(N, &Z, &X);
+        const float alpha = m->n;
+        const f3 o = to_local(-rD, X, Z, N), wl = to_local(w, X, Z, N);
+        f3 h;
+        const float pb = glossy_pdf_of(alpha, o, wl, &h);
+        *fs = fS * glossy_weight(alpha, ldf3(m->F0), o, h, wl);
+        return pb;
+    }
+    // GLOSSY: the sampled direction (before normalisation) of a lobe vertex of either kind; a type-4 vertex (gl) also multiplies
+    // factor_S by g(w), keeps its p_b and ends the path unless w.z > 0
+    template <bool SK, class ST>
+    PT_DEV f3 lobe_vertex(ST& st, const pt_material* __restrict__ m, bool gl, f3 N, f3 rD, float rnd1, float rnd2) {
+        float alpha = 1.0f;
+        f3 F0 = mk(0.f, 0.f, 0.f);
+        if (gl) {
+            alpha = m->n;          // (the device copy of a type-4 material carries its roughness there: pt_upload_materials)
+            F0 = ldf3(m->F0);
+        }
+        GlossyOut go;
+        const f3 d = lobe_direction_glossy<SK>(N, rD, gl, alpha, F0, rnd1, rnd2, &go);
+        if (gl) {
+            st.setS(st.S() * (go.F * go.g1w));
+            gs.pb = go.pb;
+            if (!(go.wz > 0.0f)) sm.dead = true;
+        }
+        return d;
+    }
+    // GLOSSY: end_vertex; a cosine lobe's p_b of the new direction rD is what emitter_weight / miss would compute from Nprev
+    PT_DEV void end_vertex_glossy(bool lobe, bool gl, f3 N, f3 rD) {
+        after_lobe = lobe;
+        if (lobe && !gl) gs.pb = max0(dot3(N, rD)) * kInvPi;
+    }
 
     // the albedo of the current type-0 vertex: the material's kd, or under TEX what shading_attributes_at left
     PT_DEV f3 albedo(const pt_material* __restrict__ m) const {
@@ -98,7 +149,9 @@ struct NeeHook {
         sm.flip = dot3(rD, N) > 0.0f;      // shade_hit's flip
         f3 kd = mk(0.f, 0.f, 0.f);
         if (type == 0 || p.iterations == 1) kd = ldf3(m->kd);
-        const f3 Ns = shading_normal_albedo(sm.vn, tx.v, tris, ti, rD, hp, N, Ng, type, (int)(m - p.mats), &kd);
+        int ttype = type;              // GLOSSY: the instances also run with option textures off (a view with uv = null): no lookup then
+        if constexpr (GLOSSY) ttype = tx.v.uv ? type : -1;
+        const f3 Ns = shading_normal_albedo(sm.vn, tx.v, tris, ti, rD, hp, N, Ng, ttype, (int)(m - p.mats), &kd);
         tx.kd = kd;
         return Ns;
     }
@@ -179,7 +232,9 @@ struct NeeHook {
         if constexpr (ENV) pa *= 1.0f - env.v.p_env;                 // the light table is chosen with probability 1 - P_env
         if (!(pa > 0.0f && inten > 0.0f)) return 1.0f;
         if (!mis) return 0.0f;
-        const float pb = max0(dot3(Nprev, rD)) * kInvPi;
+        float pb;
+        if constexpr (GLOSSY) pb = gs.pb;
+        else pb = max0(dot3(Nprev, rD)) * kInvPi;
         const float pl = pa * (t * t) / inten;
         const float rr = pl / pb;          // pb = 0: rr = inf, weight 0
         return 1.0f / fmaf_(rr, rr, 1.0f);
@@ -188,10 +243,12 @@ struct NeeHook {
     // a point y on a light, the bracket an emitter hit at y on segment k + 1 would add, for the lobe vertex hp (normal N)
     // (TWIN: the triangle branch and the tail of light_sample_env below restate this body, so that k_nee's code stays what it was;
     // a change to one belongs in the other)
-    PT_DEV void light_sample(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp) {
+    // (rD: the direction the vertex was reached along; only the GLOSSY instances pass and read it.  shade_hit keeps the six-argument call
+    // for every other hook, so that nothing about the existing instances' calls changes)
+    PT_DEV void light_sample(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD = mk(0.f, 0.f, 0.f)) {
         if (!nee || k + 1 >= p.iterations) return;
         if constexpr (ENV) {
-            light_sample_env(st, p, m, type, N, hp);
+            light_sample_env(st, p, m, type, N, hp, rD);
             return;
         }
         const float u0 = nee_unit(nee_rand(key, k, 0)), u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
@@ -216,7 +273,13 @@ struct NeeHook {
         if (!(cosx > 0.0f && cosy > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
         if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // the sample must be above the geometric surface too
         if (shadow_hit<MODE>(sv, o, w, r * 1.0001f, stk, wc) != li) return;
-        const float pb = cosx * kInvPi;
+        float pb = cosx * kInvPi;
+        f3 fs = st.S();
+        if constexpr (GLOSSY)
+            if (type == 4) {
+                pb = glossy_light(m, N, rD, w, fs, &fs);
+                if (!(pb > 0.0f)) return;      // no density (or a half vector that cannot be normalised): the sample adds nothing
+            }
         const float q = pb / pl;
         const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
         f3 fl = st.L(), fb = st.B();
@@ -230,14 +293,14 @@ struct NeeHook {
             }
             fb = fb * (ldf3(m->ks) * pw);
         }
-        const f3 e = ((ldf3(p.mats[p.meta[li].mati].emission) * (fl + fb)) * st.S()) * st.R();
+        const f3 e = ((ldf3(p.mats[p.meta[li].mati].emission) * (fl + fb)) * fs) * st.R();
         if (wl < __builtin_inff()) st.setC(madd(e, cosy * wl, st.C()));
     }
 
     // ENV: the sky with probability P_env (u_sel, keyed with ~key), else a light of the table with its pdf times 1 - P_env.  Both
     // branches only produce the shadow ray and what it would add; the traversal and the weighting are shared, so a wave that holds
     // both kinds of sample runs one traversal.  (TWIN: the triangle branch and the tail restate light_sample above.)
-    PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp) {
+    PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD) {
         const EnvView& ev = env.v;
         const float u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
         const f3 o = madd(geo(N), 0.001f, hp);
@@ -304,7 +367,13 @@ struct NeeHook {
         if (!(cosx > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
         if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // as in light_sample
         if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
-        const float pb = cosx * kInvPi;
+        float pb = cosx * kInvPi;
+        f3 fs = st.S();
+        if constexpr (GLOSSY)
+            if (type == 4) {
+                pb = glossy_light(m, N, rD, w, fs, &fs);
+                if (!(pb > 0.0f)) return;      // no density (or a half vector that cannot be normalised): the sample adds nothing
+            }
         const float q = pb / pl;
         const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
         f3 fl = st.L(), fb = st.B();
@@ -318,7 +387,7 @@ struct NeeHook {
             }
             fb = fb * (ldf3(m->ks) * pw);
         }
-        e = ((e * (fl + fb)) * st.S()) * st.R();
+        e = ((e * (fl + fb)) * fs) * st.R();
         if (wl < __builtin_inff()) st.setC(madd(e, g * wl, st.C()));
     }
 
@@ -337,7 +406,9 @@ struct NeeHook {
         const float pl = ev.p_env * tx.w;
         if (nee && after_lobe && pl > 0.0f) {
             if (mis) {
-                const float pb = max0(dot3(Nprev, rD)) * kInvPi;
+                float pb;
+                if constexpr (GLOSSY) pb = gs.pb;
+                else pb = max0(dot3(Nprev, rD)) * kInvPi;
                 const float rr = pl / pb;      // pb = 0: rr = inf, weight 0
                 wb = 1.0f / fmaf_(rr, rr, 1.0f);
             } else {
@@ -356,13 +427,14 @@ struct NeeHook {
 // SMOOTH (option smooth_normals; k_nee*_smooth below): the hook supplies the shading normal from the packed vertex normals vn; what it
 // adds here sits under `if constexpr (SMOOTH)`
 // TEX (option textures; k_nee*_tex below; on the SMOOTH code only): the hook also supplies the albedo of a type-0 vertex from the view tv
-template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false>
+// GLOSSY (option glossy; k_nee*_glossy below; on the TEX code only): material type 4 is the rough-metal lobe vertex
+template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (TEX) hook.tx.v = *tv;
     if constexpr (ENV) {
@@ -492,6 +564,24 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_tex(RenderParams p, Nee
     nee_frame<MODE, BLOCK, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv);
 }
 
+// the glossy instances (option glossy with a type-4 material uploaded): the textured kernels, the same arguments (tv.uv = null: textures off)
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_glossy(RenderParams p, NeeTable lt, const float4* vn, TexView tv, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_glossy(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_glossy(RenderParams p, NeeTable lt, const float4* vn, TexView tv) {
+    nee_frame<MODE, BLOCK, false, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_glossy(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv) {
+    nee_frame<MODE, BLOCK, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -508,7 +598,16 @@ static hipError_t launch_lanes_env_tiles_smooth(PICK pick, const RenderParams& p
 }
 
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled, const float4* vn,
-                      const TexView* tv) {
+                      const TexView* tv, bool glossy) {
+    if (glossy) {      // (tv is never null here: the host hands a view with uv = null when option textures is off)
+        if (tiled) {
+            const int64_t items = (int64_t)p.n_tiles * 64;
+            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_glossy<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv);
+            return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_tiles_glossy<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv);
+        }
+        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_glossy<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, (long long)npix);
+        return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_glossy<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, (long long)npix);
+    }
     if (tv) {
         if (tiled) {
             const int64_t items = (int64_t)p.n_tiles * 64;

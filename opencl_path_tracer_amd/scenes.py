@@ -134,16 +134,22 @@ def checker_texture(n, a, b):
     return np.where(even, np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)).astype(np.float32)
 
 
-def cornell_box(segments=32, rings=16, smooth=False, textured=False):
+def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False):
     """Scene CB of SURVEY 8(d): 12 wall/lamp triangles + two tessellated spheres
     (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects.
     smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals).
     textured: the floor carries uvs (one repeat per 1,600 units) and WHITE_DIFFUSE an 8 x 8 checker with nearest filtering, so under
-    option textures the floor shows checks of 200 units; the other white walls have no uvs and keep their kd."""
+    option textures the floor shows checks of 200 units; the other white walls have no uvs and keep their kd.
+    glossy: the chromium sphere gets a copy of its material with type 4 and shininess 50, appended to the materials: a rough metal under
+    option glossy (and inert without it)."""
     spec = SceneSpec(materials=list(BUILTIN_MATERIALS), name="cornell_box")
     spec.objects.append(cornell_walls())
     s1 = uv_sphere((250.0, 200.0, 300.0), 200.0, segments, rings)
-    spec.objects.append((s1, np.full(s1.shape[0], CHROMIUM, dtype=np.uint16)))
+    chromium = CHROMIUM
+    if glossy:
+        spec.materials.append(tuple(BUILTIN_MATERIALS[CHROMIUM][:5]) + (50.0, 4))
+        chromium = len(spec.materials) - 1
+    spec.objects.append((s1, np.full(s1.shape[0], chromium, dtype=np.uint16)))
     s2 = uv_sphere((750.0, 200.0, -200.0), 200.0, segments, rings)
     spec.objects.append((s2, np.full(s2.shape[0], GLASS, dtype=np.uint16)))
     if smooth:
