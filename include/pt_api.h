@@ -725,9 +725,40 @@ int pt_debug_closest_hit(pt_context* ctx, const pt_ray* rays, int64_t n, float* 
  * input k = ea | eb << 8 | ia << 16 | ib << 19 | signs << 22, 2^24 in all; PT_MATH_DIV_RANDOM: hashed bit patterns;
  * PT_MATH_DIV_NORMAL: hashed normal pairs with exponents -63 .. 63).  out[0] = inputs whose result differs in any bit
  * (or whose window admits a zero, denormal, inf or NaN), out[1] = inputs inside the fast path's window, out[2] = out[0];
- * bad[2 j], bad[2 j + 1] = the bit patterns (x or a, b) of up to bad_cap of the mismatching inputs. */
-enum { PT_MATH_SQRT = 0, PT_MATH_RSQRT = 1, PT_MATH_DIV_GRID = 2, PT_MATH_DIV_RANDOM = 3, PT_MATH_DIV_NORMAL = 4 };
+ * bad[2 j], bad[2 j + 1] = the bit patterns (x or a, b) of up to bad_cap of the mismatching inputs.
+ * PT_MATH_LCG: the device LCG (prog.cl:72-77) on seed = the input's low 32 bits as an int32: the new seed and the float it returns
+ * against n = (uint64)(int64)seed * 48271 % 2147483647 written out with a 64-bit multiply and remainder, (float)n / 2147483648.0f;
+ * "inside the window" = seed >= 0, the seeds that take the hand-reduced Mersenne path; bad[2 j] = the seed, bad[2 j + 1] = the new
+ * seed the device gave. */
+enum { PT_MATH_SQRT = 0, PT_MATH_RSQRT = 1, PT_MATH_DIV_GRID = 2, PT_MATH_DIV_RANDOM = 3, PT_MATH_DIV_NORMAL = 4, PT_MATH_LCG = 5 };
 int pt_debug_math(pt_context* ctx, int32_t fn, int64_t first, int64_t n, int64_t out[3], uint32_t* bad, int64_t bad_cap);
+/* The spec math and sampling primitives of the render kernels on caller-supplied items, so that each can be
+ * compared bit for bit with its counterpart in the CPU oracle without a render.  `in` holds n items of a fixed number of 32-bit words
+ * (floats as their bit patterns), `out` receives a fixed number of words per item; every fn calls the device function the kernels
+ * call and restates nothing:
+ *   fn                                      words in                         words out
+ *   PT_SPEC_SINCOS, PT_SPEC_SINCOS_SK       1: theta                         2: sin, cos       spec_sincos<false> / <true>
+ *   PT_SPEC_POW, PT_SPEC_POW_SK             2: x, y                          1: pow(x, y)      spec_pow<false> / <true>
+ *   PT_SPEC_POW5                            1: x                             1: x^5            spec_pow5
+ *   PT_SPEC_LCG                             1: seed (int32)                  2: new seed (int32), the float returned   lcg_rand
+ *   PT_SPEC_DIFFUSE, PT_SPEC_DIFFUSE_SK     8: P.xyz, N.xyz, rnd1, rnd2      8: the new ray {P.xyz, 0, D.xyz, 0} as a diffuse hit builds it
+ *                                                                               (prog.cl:205-218): D = normalize(diffuse_direction<false> /
+ *                                                                               <true>(N, rnd1, rnd2)), P = madd(N, 0.001f, P)
+ *   PT_SPEC_DIFFUSE_REC, PT_SPEC_DIFFUSE_REC_SK   as above                   as above, through diffuse_direction_rec<false> / <true> with the
+ *                                                                               frame of N laid out as a shading record holds it
+ *   PT_SPEC_FRESNEL                         9: F0.xyz, N.xyz, D.xyz          3: fresnel(F0, N, D) (prog.cl:219-222)
+ * The _SK functions are the instances whose double constants are pinned to scalar registers (the kernels with 72-96 VGPRs run them),
+ * the others leave the constants to the compiler (the 128-VGPR instance).
+ * Item layout: one thread per item in blocks of 256 threads, no grid-stride loop: item i runs on lane i % 64 of wave i / 64 (four
+ * waves per block), and a last wave that n does not fill runs with its remaining lanes off.  So the caller decides which inputs share
+ * a wave -- the cosine-lobe functions pick their square-root cores with one branch per wave.
+ * PT_EINVAL: unknown fn, n < 0, or a NULL array with n > 0 (checked before the context's device is, so a host-only context reports
+ * them too); n = 0 does nothing and returns PT_OK; otherwise a host-only context gives PT_ENODEVICE. */
+enum {
+    PT_SPEC_SINCOS = 0, PT_SPEC_SINCOS_SK = 1, PT_SPEC_POW = 2, PT_SPEC_POW_SK = 3, PT_SPEC_POW5 = 4, PT_SPEC_LCG = 5,
+    PT_SPEC_DIFFUSE = 6, PT_SPEC_DIFFUSE_SK = 7, PT_SPEC_DIFFUSE_REC = 8, PT_SPEC_DIFFUSE_REC_SK = 9, PT_SPEC_FRESNEL = 10
+};
+int pt_debug_spec(pt_context* ctx, int32_t fn, int64_t n, const uint32_t* in, uint32_t* out);
 /* The authored scene (what the reference keeps in Scene::tris / Scene::mats, main.cpp:366-371):
  * triangles in add order, materials, and the first triangle of every object. */
 int pt_debug_scene_sizes(const pt_context* ctx, int64_t* ntris, int64_t* nmats, int64_t* nobjs);

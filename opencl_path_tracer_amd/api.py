@@ -57,7 +57,7 @@ EXPORTS = [
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
     "pt_set_option", "pt_get_stat", "pt_debug_bvh_sizes", "pt_debug_bvh_copy", "pt_debug_wide_nodes", "pt_debug_encounter_rank", "pt_debug_tile_cost", "pt_debug_adaptive_list", "pt_debug_launch_plan",
-    "pt_debug_scene_sizes", "pt_debug_scene_copy", "pt_debug_closest_hit", "pt_debug_math",
+    "pt_debug_scene_sizes", "pt_debug_scene_copy", "pt_debug_closest_hit", "pt_debug_math", "pt_debug_spec",
     "pt_slab_pixel_count", "pt_frame_size", "pt_comm_available", "pt_comm_unique_id", "pt_comm_init", "pt_gather_frame", "pt_device_frame", "pt_read_frame",
     "pt_write_pfm", "pt_write_ppm", "pt_image_write_pfm", "pt_image_write_ppm", "pt_debug_gather_index", "pt_debug_deinterleave",
 ]
@@ -193,6 +193,7 @@ def _load():
     sig("pt_image_write_ppm", C.c_int, C.c_char_p, vp, i32, i32)
     sig("pt_debug_gather_index", C.c_int, i32, i32, i32, i32, i64, vp)
     sig("pt_debug_math", C.c_int, vp, i32, i64, i64, vp, vp, i64)
+    sig("pt_debug_spec", C.c_int, vp, i32, i64, vp, vp)
     sig("pt_debug_deinterleave", C.c_int, vp, vp, i64, vp)
     return L
 
@@ -259,7 +260,13 @@ def adaptive_rounds(min_spp, max_spp):
 
 
 PT_NEE_BSDF, PT_NEE_LIGHT, PT_NEE_MIS = 0, 1, 2
-PT_MATH_SQRT, PT_MATH_RSQRT, PT_MATH_DIV_GRID, PT_MATH_DIV_RANDOM, PT_MATH_DIV_NORMAL = 0, 1, 2, 3, 4   # pt_debug_math enumerations
+PT_MATH_SQRT, PT_MATH_RSQRT, PT_MATH_DIV_GRID, PT_MATH_DIV_RANDOM, PT_MATH_DIV_NORMAL, PT_MATH_LCG = 0, 1, 2, 3, 4, 5   # pt_debug_math enumerations
+# pt_debug_spec functions, and the 32-bit words each takes and gives per item
+(PT_SPEC_SINCOS, PT_SPEC_SINCOS_SK, PT_SPEC_POW, PT_SPEC_POW_SK, PT_SPEC_POW5, PT_SPEC_LCG, PT_SPEC_DIFFUSE, PT_SPEC_DIFFUSE_SK,
+ PT_SPEC_DIFFUSE_REC, PT_SPEC_DIFFUSE_REC_SK, PT_SPEC_FRESNEL) = range(11)
+SPEC_WORDS = {PT_SPEC_SINCOS: (1, 2), PT_SPEC_SINCOS_SK: (1, 2), PT_SPEC_POW: (2, 1), PT_SPEC_POW_SK: (2, 1), PT_SPEC_POW5: (1, 1),
+              PT_SPEC_LCG: (1, 2), PT_SPEC_DIFFUSE: (8, 8), PT_SPEC_DIFFUSE_SK: (8, 8), PT_SPEC_DIFFUSE_REC: (8, 8),
+              PT_SPEC_DIFFUSE_REC_SK: (8, 8), PT_SPEC_FRESNEL: (9, 3)}
 NEE_STRATEGIES = {"bsdf": PT_NEE_BSDF, "light": PT_NEE_LIGHT, "mis": PT_NEE_MIS}
 
 
@@ -1036,6 +1043,19 @@ class Scene:
         bad = np.zeros((max(int(bad_cap), 1), 2), dtype=np.uint32)
         self._ck(LIB.pt_debug_math(self._h, int(fn), int(first), int(n), _ptr(out), _ptr(bad), int(bad_cap)))
         return int(out[0]), int(out[1]), bad[:min(int(out[2]), int(bad_cap))]
+
+    def debug_spec(self, fn, items):
+        """pt_debug_spec: function fn (PT_SPEC_*) of the kernels' spec math on items, an (n, SPEC_WORDS[fn][0]) array of 32-bit words
+        (float32 items are passed as their bit patterns) -> (n, SPEC_WORDS[fn][1]) uint32; view it as float32 or int32 as the function's
+        columns ask.  Item i runs on lane i % 64 of wave i / 64."""
+        wi, wo = SPEC_WORDS[int(fn)]
+        items = np.ascontiguousarray(items)
+        if items.dtype.itemsize != 4:
+            raise ValueError("debug_spec: items must be 32-bit words")
+        items = items.view(np.uint32).reshape(-1, wi)
+        out = np.empty((items.shape[0], wo), dtype=np.uint32)
+        self._ck(LIB.pt_debug_spec(self._h, int(fn), items.shape[0], _ptr(items), _ptr(out)))
+        return out
 
     def debug_encounter_rank(self, n):
         out = np.empty(n, dtype=np.int32)

@@ -1,6 +1,7 @@
 // pt_debug.hip -- test entry points of libptamd.so: closest hit of caller-supplied rays through the
 // same traversal code (pt_device.hpp) and the same node placement the render kernels use; the IEEE
-// divide / sqrt cores of pt_device.hpp against the compiler's expansions on enumerated inputs.
+// divide / sqrt cores of pt_device.hpp against the compiler's expansions on enumerated inputs; the spec math and sampling primitives
+// of pt_device.hpp on caller-supplied items.
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -91,11 +92,106 @@ __global__ void __launch_bounds__(256) k_debug_math(int fn, unsigned long long f
     atomicAdd(&out[1], inside);
 }
 
+// PT_MATH_LCG, a kernel of its own so that k_debug_math stays as it is: lcg_rand on seed = the input's low 32 bits against the
+// 64-bit multiply and remainder of prog.cl:72-77 written out (for seed >= 0 -- out[1] counts those -- a different formulation of the
+// same operation: lcg_rand reduces by the Mersenne modulus by hand).  out[] as in k_debug_math; bad[2 j] = seed, bad[2 j + 1] = the
+// new seed lcg_rand left.
+__global__ void __launch_bounds__(256) k_debug_math_lcg(unsigned long long first, unsigned long long n, unsigned long long* out, uint32_t* bad,
+                                                        long long bad_cap) {
+    unsigned long long miss = 0, inside = 0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const int seed0 = (int)(uint32_t)(first + i);
+        int seed = seed0;
+        const float rnd = lcg_rand(seed);
+        const unsigned long long ref = (unsigned long long)(long long)seed0 * 48271ull % 2147483647ull;
+        inside += seed0 >= 0;
+        if ((unsigned long long)(uint32_t)seed != ref || __float_as_uint(rnd) != __float_as_uint((float)ref / 2147483648.0f)) {
+            ++miss;
+            const long long j = (long long)atomicAdd(&out[2], 1ull);
+            if (j < bad_cap) {
+                bad[2 * j] = (uint32_t)seed0;
+                bad[2 * j + 1] = (uint32_t)seed;
+            }
+        }
+    }
+    atomicAdd(&out[0], miss);
+    atomicAdd(&out[1], inside);
+}
+
 hipError_t launch_debug_math(int fn, unsigned long long first, unsigned long long n, unsigned long long* out, uint32_t* bad, long long bad_cap, int cu_count,
                              hipStream_t stream) {
     const unsigned long long blocks = std::min<unsigned long long>((n + 255) / 256, (unsigned long long)cu_count * 32);
     if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_debug_math, dim3((unsigned)blocks), dim3(256), 0, stream, fn, first, n, out, bad, bad_cap);
+    if (fn == PT_MATH_LCG) hipLaunchKernelGGL(k_debug_math_lcg, dim3((unsigned)blocks), dim3(256), 0, stream, first, n, out, bad, bad_cap);
+    else hipLaunchKernelGGL(k_debug_math, dim3((unsigned)blocks), dim3(256), 0, stream, fn, first, n, out, bad, bad_cap);
+    return hipGetLastError();
+}
+
+// pt_debug_spec: function FN (PT_SPEC_* in pt_api.h) of pt_device.hpp on item i = the thread's index; spec_words_in(FN) words in and
+// spec_words_out(FN) out per item, floats as their bit patterns.
+// Item layout, which the callers' wave tests depend on: one thread per item, blocks of 256, no grid-stride loop -- item i runs on lane
+// i % 64 of wave i / 64, and the lanes of the last wave past n have left before any wave-level vote (wave_all) is taken.
+template <int FN>
+__global__ void __launch_bounds__(256) k_debug_spec(const uint32_t* __restrict__ in, long long n, uint32_t* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* a = in + i * spec_words_in(FN);
+    uint32_t* o = out + i * spec_words_out(FN);
+    const auto f = [a](int k) { return __uint_as_float(a[k]); };
+    const auto v = [a](int k) { return mk(__uint_as_float(a[k]), __uint_as_float(a[k + 1]), __uint_as_float(a[k + 2])); };
+    if constexpr (FN == PT_SPEC_SINCOS || FN == PT_SPEC_SINCOS_SK) {
+        float s, c;
+        spec_sincos<FN == PT_SPEC_SINCOS_SK>(f(0), &s, &c);
+        o[0] = __float_as_uint(s);
+        o[1] = __float_as_uint(c);
+    } else if constexpr (FN == PT_SPEC_POW || FN == PT_SPEC_POW_SK) {
+        o[0] = __float_as_uint(spec_pow<FN == PT_SPEC_POW_SK>(f(0), f(1)));
+    } else if constexpr (FN == PT_SPEC_POW5) {
+        o[0] = __float_as_uint(spec_pow5(f(0)));
+    } else if constexpr (FN == PT_SPEC_LCG) {
+        int seed = (int)a[0];
+        const float rnd = lcg_rand(seed);
+        o[0] = (uint32_t)seed;
+        o[1] = __float_as_uint(rnd);
+    } else if constexpr (FN == PT_SPEC_FRESNEL) {
+        const f3 F = fresnel(v(0), v(3), v(6));
+        o[0] = __float_as_uint(F.x);
+        o[1] = __float_as_uint(F.y);
+        o[2] = __float_as_uint(F.z);
+    } else {                                      // the new ray of a diffuse hit at P with normal N, as shade_hit builds it
+        constexpr bool SK = FN == PT_SPEC_DIFFUSE_SK || FN == PT_SPEC_DIFFUSE_REC_SK;
+        const f3 P = v(0), N = v(3);
+        const float rnd1 = f(6), rnd2 = f(7);
+        f3 d;
+        if constexpr (FN == PT_SPEC_DIFFUSE_REC || FN == PT_SPEC_DIFFUSE_REC_SK) {
+            f3 Z, X;
+            tangent_frame(N, &Z, &X);
+            const float4 frame[2] = {make_float4(Z.x, Z.y, Z.z, X.x), make_float4(X.y, X.z, 0.0f, 0.0f)};      // ShadeRec::frame[o]
+            d = diffuse_direction_rec<SK>(N, frame, rnd1, rnd2);
+        } else {
+            d = diffuse_direction<SK>(N, rnd1, rnd2);
+        }
+        const f3 D = normalize3(d), O = madd(N, 0.001f, P);
+        o[0] = __float_as_uint(O.x);
+        o[1] = __float_as_uint(O.y);
+        o[2] = __float_as_uint(O.z);
+        o[3] = 0u;
+        o[4] = __float_as_uint(D.x);
+        o[5] = __float_as_uint(D.y);
+        o[6] = __float_as_uint(D.z);
+        o[7] = 0u;
+    }
+}
+
+hipError_t launch_debug_spec(int fn, const uint32_t* in, int64_t n, uint32_t* out, hipStream_t stream) {
+    using Kernel = void (*)(const uint32_t*, long long, uint32_t*);
+    static const Kernel kernels[] = {k_debug_spec<PT_SPEC_SINCOS>,      k_debug_spec<PT_SPEC_SINCOS_SK>,  k_debug_spec<PT_SPEC_POW>,
+                                     k_debug_spec<PT_SPEC_POW_SK>,      k_debug_spec<PT_SPEC_POW5>,       k_debug_spec<PT_SPEC_LCG>,
+                                     k_debug_spec<PT_SPEC_DIFFUSE>,     k_debug_spec<PT_SPEC_DIFFUSE_SK>, k_debug_spec<PT_SPEC_DIFFUSE_REC>,
+                                     k_debug_spec<PT_SPEC_DIFFUSE_REC_SK>, k_debug_spec<PT_SPEC_FRESNEL>};
+    if (fn < 0 || fn > PT_SPEC_FRESNEL) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(kernels[fn], dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, (long long)n, out);
     return hipGetLastError();
 }
 

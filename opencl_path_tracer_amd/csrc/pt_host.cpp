@@ -1648,7 +1648,7 @@ struct EventOwner {
 
 int pt_debug_math(pt_context* ctx, int32_t fn, int64_t first, int64_t n, int64_t out[3], uint32_t* bad, int64_t bad_cap) {
     PT_NEED_DEVICE(ctx);
-    if (fn < PT_MATH_SQRT || fn > PT_MATH_DIV_NORMAL || first < 0 || n < 0 || !out || bad_cap < 0 || (bad_cap > 0 && !bad))
+    if (fn < PT_MATH_SQRT || fn > PT_MATH_LCG || first < 0 || n < 0 || !out || bad_cap < 0 || (bad_cap > 0 && !bad))
         return fail(ctx, PT_EINVAL, "pt_debug_math: bad arguments");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     DeviceBuf d_out, d_bad;
@@ -1663,6 +1663,24 @@ int pt_debug_math(pt_context* ctx, int32_t fn, int64_t first, int64_t n, int64_t
     for (int i = 0; i < 3; ++i) out[i] = (int64_t)h[i];
     const int64_t k = std::min<int64_t>(out[2], bad_cap);
     if (k > 0) PT_HIP(ctx, hipMemcpy(bad, d_bad.p, 2 * sizeof(uint32_t) * (size_t)k, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_debug_spec(pt_context* ctx, int32_t fn, int64_t n, const uint32_t* in, uint32_t* out) {
+    if (!ctx) return PT_EINVAL;
+    const size_t wi = (size_t)spec_words_in(fn), wo = (size_t)spec_words_out(fn);
+    if (wi == 0) return fail(ctx, PT_EINVAL, "pt_debug_spec: unknown fn");
+    if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, PT_EINVAL, "pt_debug_spec: n >= 0, both arrays non-null");
+    if (n == 0) return PT_OK;
+    PT_NEED_DEVICE(ctx);
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceBuf d_in, d_out;
+    PT_HIP(ctx, d_in.alloc(sizeof(uint32_t) * wi * (size_t)n));
+    PT_HIP(ctx, d_out.alloc(sizeof(uint32_t) * wo * (size_t)n));
+    PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(uint32_t) * wi * (size_t)n, hipMemcpyHostToDevice));
+    PT_HIP(ctx, launch_debug_spec(fn, (const uint32_t*)d_in.p, n, (uint32_t*)d_out.p, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(uint32_t) * wo * (size_t)n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

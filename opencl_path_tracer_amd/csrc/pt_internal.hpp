@@ -350,6 +350,20 @@ hipError_t launch_compact_tiles(const uint8_t* active, int32_t n, int32_t* list,
 hipError_t launch_debug_closest_hit(const RenderParams& p, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri, int cu_count, hipStream_t stream);
 hipError_t launch_debug_math(int fn, unsigned long long first, unsigned long long n, unsigned long long* out, uint32_t* bad, long long bad_cap, int cu_count,
                              hipStream_t stream);
+// pt_debug_spec (pt_debug.hip): 32-bit words per item of function fn (PT_SPEC_* in pt_api.h), 0 for an unknown fn
+constexpr int spec_words_in(int fn) {
+    return fn == PT_SPEC_SINCOS || fn == PT_SPEC_SINCOS_SK || fn == PT_SPEC_POW5 || fn == PT_SPEC_LCG ? 1
+         : fn == PT_SPEC_POW || fn == PT_SPEC_POW_SK ? 2
+         : fn >= PT_SPEC_DIFFUSE && fn <= PT_SPEC_DIFFUSE_REC_SK ? 8
+         : fn == PT_SPEC_FRESNEL ? 9 : 0;
+}
+constexpr int spec_words_out(int fn) {
+    return fn == PT_SPEC_SINCOS || fn == PT_SPEC_SINCOS_SK || fn == PT_SPEC_LCG ? 2
+         : fn == PT_SPEC_POW || fn == PT_SPEC_POW_SK || fn == PT_SPEC_POW5 ? 1
+         : fn >= PT_SPEC_DIFFUSE && fn <= PT_SPEC_DIFFUSE_REC_SK ? 8
+         : fn == PT_SPEC_FRESNEL ? 3 : 0;
+}
+hipError_t launch_debug_spec(int fn, const uint32_t* in, int64_t n, uint32_t* out, hipStream_t stream);
 // guide buffers and the a-trous filter (pt_denoise.hip; the filter is pinned in include/pt_api.h next to pt_denoise)
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
                        int cu_count, hipStream_t stream);

@@ -84,6 +84,12 @@ def lib():
     sig("orc_new_ray_specular", None, vp, vp, vp, vp)
     sig("orc_new_ray_refractive", None, vp, vp, vp, vp, f32, vp, ip, f32)
     sig("orc_fresnel", None, vp, vp, vp, vp)
+    sig("orc_spec_sincosf_n", None, vp, vp, vp, i64)
+    sig("orc_spec_powf_n", None, vp, vp, vp, i64)
+    sig("orc_spec_pow5_n", None, vp, vp, i64)
+    sig("orc_rand_n", None, vp, vp, vp, i64)
+    sig("orc_new_ray_diffuse_n", None, vp, vp, i64)
+    sig("orc_fresnel_n", None, vp, vp, i64)
     sig("orc_reinhard_tone_map", None, fp, fp)
     sig("orc_filmic_tone_map", None, fp, fp)
     sig("orc_frame_create", vp, i32, i32)
@@ -121,6 +127,60 @@ def seed_sequence(n):
     out = np.empty(n, dtype=np.int32)
     lib().orc_seed_sequence(_ptr(out), n)
     return out
+
+
+def _f32(a, cols=None):
+    """a as contiguous float32; arrays of 32-bit words (uint32 / int32 bit patterns) are viewed, not converted"""
+    a = np.ascontiguousarray(a)
+    a = a.view(np.float32) if a.dtype in (np.uint32, np.int32) else a.astype(np.float32, copy=False)
+    return a.reshape(-1) if cols is None else a.reshape(-1, cols)
+
+
+def spec_sincosf_n(theta):
+    """orc_spec_sincosf of every theta: (sin, cos), float32 arrays"""
+    theta = _f32(theta)
+    s, c = np.empty_like(theta), np.empty_like(theta)
+    lib().orc_spec_sincosf_n(_ptr(theta), _ptr(s), _ptr(c), theta.size)
+    return s, c
+
+
+def spec_powf_n(x, y):
+    x, y = _f32(x), _f32(y)
+    assert x.size == y.size
+    out = np.empty_like(x)
+    lib().orc_spec_powf_n(_ptr(x), _ptr(y), _ptr(out), x.size)
+    return out
+
+
+def spec_pow5_n(x):
+    x = _f32(x)
+    out = np.empty_like(x)
+    lib().orc_spec_pow5_n(_ptr(x), _ptr(out), x.size)
+    return out
+
+
+def rand_n(seed):
+    """one orc_rand step from every seed: (new seeds int32, floats)"""
+    seed = np.ascontiguousarray(seed, dtype=np.int32).reshape(-1)
+    new, rnd = np.empty_like(seed), np.empty(seed.size, dtype=np.float32)
+    lib().orc_rand_n(_ptr(seed), _ptr(new), _ptr(rnd), seed.size)
+    return new, rnd
+
+
+def new_ray_diffuse_n(items):
+    """orc_new_ray_diffuse of every item (n, 8) {P.xyz, N.xyz, rnd1, rnd2}: (n, 8) float32 {P.xyz, 0, D.xyz, 0}"""
+    items = _f32(items, 8)
+    out = np.zeros(items.shape[0], dtype=RAY)
+    lib().orc_new_ray_diffuse_n(_ptr(out), _ptr(items), items.shape[0])
+    return out.view(np.float32).reshape(-1, 8)
+
+
+def fresnel_n(items):
+    """orc_fresnel of every item (n, 9) {F0.xyz, N.xyz, D.xyz}: (n, 3) float32"""
+    items = _f32(items, 9)
+    out = np.zeros((items.shape[0], 4), dtype=np.float32)
+    lib().orc_fresnel_n(_ptr(out), _ptr(items), items.shape[0])
+    return out[:, :3]
 
 
 def make_material(kd, ks, em, N, K, shininess, mtype):

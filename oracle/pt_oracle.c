@@ -747,6 +747,28 @@ void orc_new_ray_refractive(orc_ray* out, const orc_f3* P, const orc_f3* N, cons
 }
 void orc_fresnel(orc_f3* out, const orc_f3* F0, const orc_f3* N, const orc_f3* D) { st(out, fresnel(ld(F0), ld(N), ld(D))); }
 
+/* the unit-level functions over arrays (tests only): each a loop over the scalar function, nothing else */
+void orc_spec_sincosf_n(const float* theta, float* s, float* c, int64_t n) { for (int64_t i = 0; i < n; ++i) orc_spec_sincosf(theta[i], &s[i], &c[i]); }
+void orc_spec_powf_n(const float* x, const float* y, float* out, int64_t n) { for (int64_t i = 0; i < n; ++i) out[i] = orc_spec_powf(x[i], y[i]); }
+void orc_spec_pow5_n(const float* x, float* out, int64_t n) { for (int64_t i = 0; i < n; ++i) out[i] = orc_spec_pow5(x[i]); }
+void orc_rand_n(const int32_t* seed, int32_t* new_seed, float* rnd, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) { new_seed[i] = seed[i]; rnd[i] = orc_rand(&new_seed[i]); }
+}
+void orc_new_ray_diffuse_n(orc_ray* out, const float* items, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        const float* a = items + 8 * i;
+        const orc_f3 P = { a[0], a[1], a[2], 0.0f }, N = { a[3], a[4], a[5], 0.0f };
+        orc_new_ray_diffuse(&out[i], &P, &N, a[6], a[7]);
+    }
+}
+void orc_fresnel_n(orc_f3* out, const float* items, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        const float* a = items + 9 * i;
+        const orc_f3 F0 = { a[0], a[1], a[2], 0.0f }, N = { a[3], a[4], a[5], 0.0f }, D = { a[6], a[7], a[8], 0.0f };
+        orc_fresnel(&out[i], &F0, &N, &D);
+    }
+}
+
 /* ------------------------------------------------------------------ frame + kernels */
 struct orc_frame {
     int W, H;

@@ -115,6 +115,15 @@ void orc_fresnel(orc_f3* out, const orc_f3* F0, const orc_f3* N, const orc_f3* D
 void orc_reinhard_tone_map(float out[4], const float c[3]);                                      /* prog.cl:264-269 */
 void orc_filmic_tone_map(float out[4], const float c[3]);                                        /* prog.cl:259-263 */
 
+/* ---- the same unit-level functions over arrays of n inputs: plain loops over the scalar functions above, for tests that compare
+ * millions of inputs (one ctypes call instead of n) */
+void orc_spec_sincosf_n(const float* theta, float* s, float* c, int64_t n);
+void orc_spec_powf_n(const float* x, const float* y, float* out, int64_t n);
+void orc_spec_pow5_n(const float* x, float* out, int64_t n);
+void orc_rand_n(const int32_t* seed, int32_t* new_seed, float* rnd, int64_t n);      /* one step from each seed */
+void orc_new_ray_diffuse_n(orc_ray* out, const float* items, int64_t n);    /* items: 8 floats each, P.xyz N.xyz rnd1 rnd2 */
+void orc_fresnel_n(orc_f3* out, const float* items, int64_t n);             /* items: 9 floats each, F0.xyz N.xyz D.xyz */
+
 /* ---- frame buffers + kernels */
 orc_frame* orc_frame_create(int width, int height);
 void orc_frame_destroy(orc_frame*);

@@ -104,6 +104,59 @@ def test_spec_pow_within_opencl_bounds(oracle):
     assert L.orc_spec_pow5(float(x)) == np.float32(np.float32(np.float32(x * x) * np.float32(x * x)) * x)
 
 
+def test_array_entry_points_equal_the_scalar_functions(oracle):
+    """orc_*_n are loops over the scalar functions: the same bits on a few hundred inputs each, edge inputs included."""
+    L = oracle.lib()
+    rng = np.random.RandomState(23)
+    u32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    edge = np.array([0.0, -0.0, 1e-45, 2.0 ** -126, 1.0, 2.0, 8.0, 1e30, np.inf, -np.inf, np.nan, -1.0], dtype=np.float32)
+    s, c = C.c_float(), C.c_float()
+    # sincos on its domain [0, 8]
+    th = np.concatenate([rng.rand(300) * 8, [0.0, 1e-45, 2.0 ** -126, math.pi / 4, 2 * math.pi, 8.0]]).astype(np.float32)
+    gs, gc = oracle.spec_sincosf_n(th)
+    for i, t in enumerate(th):
+        L.orc_spec_sincosf(float(t), C.byref(s), C.byref(c))
+        assert u32(gs[i]) == u32(s.value) and u32(gc[i]) == u32(c.value), t
+    # pow and pow5, NaN and all
+    same = lambda a, b: u32(a) == u32(b) or (np.isnan(a) and np.isnan(b))
+    x = np.concatenate([rng.rand(300), edge]).astype(np.float32)
+    y = np.concatenate([rng.rand(300) * 200 - 50, edge[::-1]]).astype(np.float32)
+    gp, g5 = oracle.spec_powf_n(x, y), oracle.spec_pow5_n(x)
+    for i in range(x.size):
+        assert same(gp[i], np.float32(L.orc_spec_powf(float(x[i]), float(y[i])))), (x[i], y[i])
+        assert same(g5[i], np.float32(L.orc_spec_pow5(float(x[i])))), x[i]
+    # LCG: one step from each seed, negative seeds included
+    seeds = np.concatenate([rng.randint(-2 ** 31, 2 ** 31, 300), [0, 1, 2147483646, 2147483647, -1, -2 ** 31]]).astype(np.int32)
+    new, rnd = oracle.rand_n(seeds)
+    for i, v in enumerate(seeds):
+        sd = C.c_int(int(v))
+        f = L.orc_rand(C.byref(sd))
+        assert new[i] == sd.value and u32(rnd[i]) == u32(f), v
+    # the diffuse ray and fresnel
+    items = rng.randn(300, 9).astype(np.float32)
+    items[:, 3:6] /= np.linalg.norm(items[:, 3:6], axis=1)[:, None]
+    items[:, 6:8] = rng.rand(300, 2)
+    items[:4, 3:6] = [(0, 1, 0), (0, -1, 0), (0.001, 1, 0.001), (1, 0, 0)]
+    items[:4, 6] = [1.0, 2.0 ** -31, 0.5, 1.0]
+    got = oracle.new_ray_diffuse_n(items[:, :8])
+    r = np.zeros(1, dtype=oracle.RAY)
+    f3 = lambda v: np.array([(v[0], v[1], v[2], 0.0)], dtype=oracle.F3)
+    for i, a in enumerate(items):
+        P, N = f3(a[0:3]), f3(a[3:6])
+        L.orc_new_ray_diffuse(r.ctypes.data, P.ctypes.data, N.ctypes.data, C.c_float(a[6]), C.c_float(a[7]))
+        assert np.array_equal(got[i].view(np.uint32), r.view(np.uint32).reshape(-1)), a
+    items[:, 6:9] /= np.linalg.norm(items[:, 6:9], axis=1)[:, None]
+    items[:, 0:3] = rng.rand(300, 3)
+    items[:3, 0:3] = [(1, 1, 1), (0, 0, 0), (0, 0.5, 1)]
+    items[:3, 6:9] = items[:3, 3:6]
+    got = oracle.fresnel_n(items)
+    o = np.zeros(1, dtype=oracle.F3)
+    for i, a in enumerate(items):
+        F0, N, D = f3(a[0:3]), f3(a[3:6]), f3(a[6:9])
+        L.orc_fresnel(o.ctypes.data, F0.ctypes.data, N.ctypes.data, D.ctypes.data)
+        assert np.array_equal(got[i].view(np.uint32), o.view(np.uint32).reshape(-1)[:3]), a
+
+
 def test_material_constructor(oracle):
     # main.cpp:101-111 on the CHROMIUM row (main.cpp:760), evaluated independently in numpy f32
     N = np.array([3.10, 3.05, 2.05], dtype=np.float32)
