@@ -439,6 +439,51 @@ float pt_material_roughness(float shininess);
  * from normalize(w) the way a light sample evaluates it, o.z */
 int pt_debug_glossy(pt_context* ctx, int64_t n, const float* N_D_alpha_rnd, float* out);
 
+/* ---- a coated-diffuse (plastic) material for pt_render_nee (new: opt-in with option "coated") -----------
+ * Option "coated" = 1 (default 0: every path computes what it computed before, bit for bit, and type 5 stays inert): pt_render_nee (every
+ * strategy, with and without an environment, smooth_normals, textures and glossy) and pt_render_adaptive_ex with PT_ADAPT_PATH_NEE shade a
+ * hit on a material of type 5 as the two-lobe vertex below, a diffuse base under a rough dielectric coat; pt_render, pt_generate_rays,
+ * pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex with PT_ADAPT_PATH_RENDER return PT_EINVAL naming the option, checked before
+ * the device (PT_ENODEVICE).  With the option on and no material of type 5 among those uploaded last, the host launches the kernels it
+ * launches with the option off (those of option glossy included): the frame (colors, rnds, rays) is the option-off frame bit for bit.
+ * Whether type 4 is the rough metal in a frame that shades type 5 follows option glossy, as everywhere else.
+ * Material.  alpha = pt_material_roughness(shininess), written into field n of the DEVICE copy of a type-5 material as for type 4; F0 from
+ * pt_material_init (N = 1.5, K = 0: 0.04); kd' = kd, times the bound texture's texel under option textures (the lookup runs for type 0 or
+ * 5 in these frames; pt_set_material_texture accepts any material).  ks and emission of a type-5 material are ignored; it is no light.
+ * The vertex (float32, the conventions of the rough-metal block above, whose D, G1, p_glossy(h) = (G1(o) D(h)) / (4.0f o.z) and
+ * fresnel it reuses; F(c) = fresnel on the cosine |c|).  A type-5 hit is a lobe vertex for every rule that speaks of lobe vertices: light
+ * sample when k + 1 < iterations, W_b at the next emitter hit or sky miss, the geometric-side rules under smooth_normals, offsets along Ng,
+ * exactly two LCG values rnd1, rnd2 after its light sample.  N, the frame (Z, X), local coordinates and o = local(-D) as for type 4.
+ *   Lobe choice:  Fo = F(o.z); fm = ((Fo.x + Fo.y) + Fo.z) / 3.0f; km = ((kd'.x + kd'.y) + kd'.z) / 3.0f; s = fmaf(1.0f - fm, km, fm);
+ *     ps = s > 0 ? fm / s : 0.5f, clamped to [0.1f, 0.9f]; u_sel = (pt_nee_rand(~key, k, 1) >> 8) * 2^-24 (key as for the light samples; ~key
+ *     with dimension 0 is the environment's selection); the coat lobe is chosen iff u_sel < ps.  Nothing is drawn from the LCG for it.
+ *   Coat lobe: w and h by the visible-normal sequence of type 4 on the same disc point of rnd1, rnd2.
+ *   Base lobe: w = (r c, r s, sqrt(1.0f - rnd1)), diffuse_direction's cosine lobe (the bits of a type-0 lane); h = normalize(o + w).
+ *   The world direction before normalisation is madd(Z, w.y, madd(N, w.z, X * w.x)) for both.
+ *   Terms, for w with half vector h (c = max0(w.z)):
+ *     pg = p_glossy(h); p_b(w) = fmaf(ps, pg, ((1.0f - ps) c) * (1/pi)f)                       -- the mixture, whichever lobe drew w
+ *     spec(w) = (F(|dot3(h, o)|) G1(w)) * pg                                                    [= F D(h) G1(o) G1(w) / (4 o.z)]
+ *     diff(w) = (((1 - F(o.z)) * (1 - F(c))) * kd') * (c * (c * (1/pi)f))                       (componentwise)
+ *     g(w) = (spec(w) + diff(w)) * (1.0f / p_b(w)), 0 unless p_b(w) > 0
+ *   Update: factor_S *= g(w); factor_L and factor_B are untouched.  Unless w.z > 0 and p_b(w) > 0 the path ends after the two draws, as at
+ *   a type-4 vertex.  The new origin is hp + 0.001 Ng.
+ *   Light sample at the vertex (triangle light and sky): as pinned for type 4 with the mixture: for the sample's unit w, ps as above and
+ *   h = normalize(o + w), p_b = p_b(w), fS' = fS g(w) (fL, fB unchanged); rejected unless w.z > 0 (and, under smooth_normals,
+ *   dot3(w, Ng) > 0) and unless p_b(w) > 0.  It is evaluated after the shadow ray.
+ *   W_b of the next emitter hit or sky miss uses the mixture's p_b of the sampled w, kept from the vertex (one device function states
+ *   the density for the sampler, the light sample and W_b).
+ *   Preview (iterations == 1): kd' + emission.
+ * A texture draws no random number here either, but ps is a function of kd': a texture on a type-5 material can change which lobe a
+ * vertex picks and so the rest of the path; rnds and rays are those of the untextured frame exactly when it leaves km unchanged.
+ * The light table, the OBJ reader and every existing pt_nee_rand key are untouched.
+ * Guides: pt_render_aovs_ex with PT_AOV_SHADED and the option on gives a terminal type-5 hit the albedo tint x kd' and the normal Ns; with
+ * the option off, and in geometric guides, the buffers are what they were.  Changing the option makes no guides stale. */
+/* the device functions of the vertex (host-only context: PT_ENODEVICE), one thread per item, item i on lane i % 64.  Per item 12 floats
+ * in: N (unit), D (unit, toward the surface), alpha, F0 (grey), kd (grey), rnd1, rnd2, u_sel; 10 out: the world direction w before
+ * normalisation (3), ps, 1 if the coat lobe drew w else 0, p_b as sampled, g.x as sampled, p_b and g.x evaluated again from normalize(w)
+ * the way a light sample evaluates them, o.z */
+int pt_debug_coated(pt_context* ctx, int64_t n, const float* in, float* out);
+
 /* ---- per-pixel variance of the mean luminance (new: opt-in with option "moments"; the reference keeps the mean only) -------
  * With option "moments" = 1 every render path (pt_render in every variant, schedule and node mode, pt_trace_rays,
  * pt_render_adaptive, pt_render_nee, tiled ranks) also folds each sample's squared luminance into colors[].w, float32 in this order:

@@ -140,6 +140,9 @@ public:
     // the rough metal of material type 4 (set_option("glossy", 1); render_nee only): the device functions of the vertex, 9 floats in
     // (N, D, alpha, rnd1, rnd2) and 8 out per item (pt_debug_glossy)
     void debug_glossy(int64_t n, const float* N_D_alpha_rnd, float* out) { ck(pt_debug_glossy(ctx, n, N_D_alpha_rnd, out)); }
+    // the coated diffuse of material type 5 (set_option("coated", 1); render_nee only): the device functions of the vertex, 12 floats in
+    // (N, D, alpha, F0, kd, rnd1, rnd2, u_sel) and 10 out per item (pt_debug_coated)
+    void debug_coated(int64_t n, const float* in, float* out) { ck(pt_debug_coated(ctx, n, in, out)); }
     // the spec math and sampling primitives of the kernels on n items of 32-bit words (pt_debug_spec; fn = PT_SPEC_*)
     void debug_spec(int32_t fn, int64_t n, const uint32_t* in, uint32_t* out) { ck(pt_debug_spec(ctx, fn, n, in, out)); }
     // guide buffers of the current view (pt_render_aovs) and the a-trous filter over them (pt_denoise; p = NULL: the defaults)

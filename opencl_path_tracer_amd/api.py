@@ -49,7 +49,7 @@ EXPORTS = [
     "pt_set_vertex_normals", "pt_clear_vertex_normals", "pt_compute_vertex_normals", "pt_debug_vertex_normals", "pt_debug_shading_normal",
     "pt_texture_defaults", "pt_add_texture", "pt_clear_textures", "pt_set_material_texture", "pt_debug_texture",
     "pt_set_vertex_uvs", "pt_clear_vertex_uvs", "pt_debug_vertex_uvs", "pt_debug_albedo", "pt_image_read_ppm",
-    "pt_material_roughness", "pt_debug_glossy",
+    "pt_material_roughness", "pt_debug_glossy", "pt_debug_coated",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
@@ -130,6 +130,7 @@ def _load():
     sig("pt_image_read_ppm", C.c_int, C.c_char_p, vp, i64, C.POINTER(i32), C.POINTER(i32))
     sig("pt_material_roughness", f32, f32)
     sig("pt_debug_glossy", C.c_int, vp, i64, vp, vp)
+    sig("pt_debug_coated", C.c_int, vp, i64, vp, vp)
     sig("pt_environment_defaults", None, vp)
     sig("pt_set_environment", C.c_int, vp, vp, i32, i32, vp)
     sig("pt_clear_environment", C.c_int, vp)
@@ -643,6 +644,16 @@ class Scene:
         items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 9)
         out = np.empty((items.shape[0], 8), dtype=np.float32)
         self._ck(LIB.pt_debug_glossy(self._h, items.shape[0], _ptr(items), _ptr(out)))
+        return out
+
+    # -- the coated diffuse of material type 5 (option "coated")
+    def debug_coated(self, items):
+        """pt_debug_coated: items (n, 12) float32 {N, D, alpha, F0, kd, rnd1, rnd2, u_sel} -> (n, 10) float32 {w before normalisation
+        (world), ps, 1 if the coat lobe drew w else 0, p_b as sampled, g.x as sampled, p_b and g.x evaluated again from w, o.z}, by the
+        device functions the coated k_nee instances call."""
+        items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 12)
+        out = np.empty((items.shape[0], 10), dtype=np.float32)
+        self._ck(LIB.pt_debug_coated(self._h, items.shape[0], _ptr(items), _ptr(out)))
         return out
 
     def upload_Triangles(self):

@@ -214,6 +214,10 @@ struct pt_context {
     // instances run only when the option is on AND the materials uploaded last hold a type-4 one; every other frame is today's launch
     int glossy = 0;
     bool glossy_mats = false;          // pt_upload_materials saw a material of type 4
+    // coated diffuse (option coated; pinned in include/pt_api.h): material type 5 is a two-lobe vertex in pt_render_nee.  The coated k_nee
+    // instances run only when the option is on AND the materials uploaded last hold a type-5 one; every other frame is today's launch
+    int coated = 0;
+    bool coated_mats = false;          // pt_upload_materials saw a material of type 5
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)

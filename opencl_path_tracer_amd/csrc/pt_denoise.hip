@@ -18,6 +18,7 @@ struct AovShade {
     const float4* vn;              // packed vertex normals; nullptr: option smooth_normals is off
     TexView tv;                    // tv.uv == nullptr: option textures is off
     int glossy;                    // option glossy: a terminal type-4 hit is a metal (albedo tint x F0)
+    int coated;                    // option coated: a terminal type-5 hit is a plastic (albedo tint x kd')
 };
 PT_DEV const AovShade& only(const AovShade& s) { return s; }
 
@@ -61,9 +62,10 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
                             const f3 Ng = dot3(D, N) > 0.0f ? -N : N;
                             const f3 hp = madd(D, t, P);
                             f3 kd = mk(0.f, 0.f, 0.f);
-                            if (type == 0 || type == 3) kd = ldf3(m->kd);
                             const AovShade& sh = only(shade...);
-                            const f3 Ns = shading_normal_albedo(sh.vn, sh.tv, p.tris, ti, D, hp, N, Ng, sh.tv.uv ? type : -1, mi, &kd);
+                            const bool plastic = type == 5 && sh.coated;
+                            if (type == 0 || type == 3 || plastic) kd = ldf3(m->kd);
+                            const f3 Ns = shading_normal_albedo(sh.vn, sh.tv, p.tris, ti, D, hp, N, Ng, sh.tv.uv ? (plastic ? 0 : type) : -1, mi, &kd);
                             if ((type == 1 || type == 2) && d < spec_depth) {
                                 float n = 1.0f;
                                 if (type == 2) {
@@ -96,7 +98,7 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
                                 if (ti < 0) break;          // escaped: albedo 0, normal 0
                                 continue;
                             }
-                            const f3 a = type == 1 || (type == 4 && sh.glossy) ? ldf3(m->F0) : type == 2 ? mk(1.f, 1.f, 1.f) : kd + ldf3(m->emission);
+                            const f3 a = type == 1 || (type == 4 && sh.glossy) ? ldf3(m->F0) : type == 2 ? mk(1.f, 1.f, 1.f) : plastic ? kd : kd + ldf3(m->emission);
                             alb = tint * a;
                             nrm = Ns;
                             mat = (float)mi;
@@ -151,9 +153,9 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
 }
 
 hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
-                              const float4* vn, const TexView& tv, int glossy, int cu_count, hipStream_t stream) {
+                              const float4* vn, const TexView& tv, int glossy, int coated, int cu_count, hipStream_t stream) {
     return launch_lanes([](auto s) { return k_aovs<s.mode, s.block, AovShade>; }, p, npix, cu_count, stream, subpixels, specular_depth,
-                        (long long)npix, albedo_rgbm, normal_depth, AovShade{vn, tv, glossy});
+                        (long long)npix, albedo_rgbm, normal_depth, AovShade{vn, tv, glossy, coated});
 }
 
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,

@@ -1154,6 +1154,105 @@ PT_DEV f3 lobe_direction_glossy(f3 N, f3 D, bool gl, float alpha, f3 F0, float r
     return d;
 }
 
+// ---- coated diffuse, material type 5 under option coated (a diffuse base under a rough dielectric coat; include/pt_api.h pins every
+// operation).  Local vectors as above; D, G1, glossy_pdf, glossy_weight and fresnel are the rough metal's.
+constexpr float kOneOverPi = 0.318309886183790672f;
+PT_DEV f3 coated_F(f3 F0, float c) { return fresnel(F0, mk(0.0f, 0.0f, 1.0f), mk(0.0f, 0.0f, -c)); }      // F(c): fresnel's |dot3| is |c|
+// the probability of the coat lobe at the vertex seen along o with albedo kd'
+PT_DEV float coated_ps(f3 F0, f3 kd, f3 o) {
+    const f3 Fo = coated_F(F0, o.z);
+    const float fm = ((Fo.x + Fo.y) + Fo.z) / 3.0f;
+    const float km = ((kd.x + kd.y) + kd.z) / 3.0f;
+    const float s = fmaf_(1.0f - fm, km, fm);
+    const float ps = s > 0.0f ? fm / s : 0.5f;
+    return ps < 0.1f ? 0.1f : ps > 0.9f ? 0.9f : ps;
+}
+// p_b of the local direction w whose half vector with o is h, the mixture of the two lobes -- the ONE statement of the density: the
+// sampler (whichever lobe drew w), the light sample and W_b go through it.  *g = (spec(w) + diff(w)) / p_b(w), 0 unless p_b > 0
+PT_DEV float coated_pdf_weight(float alpha, f3 F0, f3 kd, float ps, f3 o, f3 h, f3 w, f3* g) {
+    const float pg = glossy_pdf(alpha, o, h);
+    const float c = max0(w.z);
+    const float pb = fmaf_(ps, pg, ((1.0f - ps) * c) * kOneOverPi);
+    const f3 spec = glossy_weight(alpha, F0, o, h, w) * pg;
+    const f3 Fo = coated_F(F0, o.z), Fw = coated_F(F0, c);
+    const f3 diff = ((mk(1.0f - Fo.x, 1.0f - Fo.y, 1.0f - Fo.z) * mk(1.0f - Fw.x, 1.0f - Fw.y, 1.0f - Fw.z)) * kd) * (c * (c * kOneOverPi));
+    const float ip = pb > 0.0f ? 1.0f / pb : 0.0f;
+    *g = (spec + diff) * ip;
+    return pb;
+}
+// the same for a given unit direction w (the light sample's): ps and h = normalize(o + w) from scratch
+PT_DEV float coated_pdf_weight_of(float alpha, f3 F0, f3 kd, f3 o, f3 w, f3* g) {
+    return coated_pdf_weight(alpha, F0, kd, coated_ps(F0, kd, o), o, normalize3(o + w), w, g);
+}
+// what the sampled coated vertex leaves behind
+struct CoatedOut {
+    f3 g;            // g(w)
+    float pb;        // p_b as sampled (the mixture)
+    float wz;        // w.z: the path ends unless it is > 0
+    float ps;        // (pt_debug_coated)
+    float oz;
+    bool coat;       // the coat lobe drew w
+};
+// lobe_direction_glossy with the coated vertex as a third kind of lane (ct; u_sel chooses its lobe): the frame, the roots, the sincos and
+// the world sum are shared by all three, glossy_sample by the metal and the coat lobe, sqrt(1 - rnd1) by the cosine lobes.  A diffuse
+// lane gets diffuse_direction's bits and a type-4 lane lobe_direction_glossy's.
+template <bool SK>
+PT_DEV f3 lobe_direction_coated(f3 N, f3 D, bool gl, bool ct, float alpha, f3 F0, f3 kd, float u_sel, float rnd1, float rnd2, GlossyOut* out, CoatedOut* co) {
+    bool yaxis;
+    const float l2 = frame_l2(N, &yaxis);
+    float rl, r;
+    if (wave_all(rsqrt_window(l2) && rnd1 >= kSqrtWindowLo && rnd1 < 1.0f)) {
+        rl = rsqrt_core(l2);
+        r = sqrt_core(rnd1);
+    } else {
+        rl = 1.0f / __builtin_sqrtf(l2);
+        r = __builtin_sqrtf(rnd1);
+    }
+    f3 Z, X;
+    frame_from_rl(N, yaxis, rl, &Z, &X);
+    const float theta = (float)(6.283185307179586 * (double)rnd2);
+    float sn, cs;
+    spec_sincos<SK>(theta, &sn, &cs);
+    float x = r * cs, y = r * sn, z = 0.0f;
+    f3 o = mk(0.f, 0.f, 1.f), h = o;
+    float ps = 0.0f;
+    bool vis = gl;             // the lane samples visible normals: a metal, or the coat lobe of a coated vertex
+    if (gl || ct) o = to_local(-D, X, Z, N);
+    if (ct) {
+        ps = coated_ps(F0, kd, o);
+        vis = u_sel < ps;
+    }
+    if (vis) {
+        const f3 w = glossy_sample(alpha, o, x, y, &h);
+        x = w.x;
+        y = w.y;
+        z = w.z;
+    } else {
+        z = sqrt_rn(1.0f - rnd1);
+    }
+    if (gl) {
+        const f3 w = mk(x, y, z);
+        out->pb = glossy_pdf(alpha, o, h);
+        out->g1w = glossy_G1(alpha, w);
+        out->F = fresnel(F0, h, -o);
+        out->wz = z;
+        out->oz = o.z;
+    }
+    if (ct) {
+        const f3 w = mk(x, y, z);
+        if (!vis) h = normalize3(o + w);
+        co->pb = coated_pdf_weight(alpha, F0, kd, ps, o, h, w, &co->g);
+        co->wz = z;
+        co->ps = ps;
+        co->oz = o.z;
+        co->coat = vis;
+    }
+    f3 d = X * x;
+    d = madd(N, z, d);
+    d = madd(Z, y, d);
+    return d;
+}
+
 // ---------------------------------------------------------------------------- path state + shading
 // The path state of prog.cl:307-316: ray (P, D), LCG state and inside-glass flag are plain local variables of the
 // caller; the four factors and the colour travel as one PathRegs.  (Round 3 also tried them in global memory behind the
@@ -1192,11 +1291,15 @@ struct PathRegs {
 // A hook with `glossy` set (it has `textured` too) makes material type 4 a lobe vertex, the rough metal of option glossy (pinned in
 // include/pt_api.h): lobe_direction_glossy() above in place of diffuse_direction, the vertex's p_b kept in the hook; every statement
 // that does so sits under `if constexpr (HOOK::glossy)`.
+// A hook with `coated` set (it has `glossy` too) makes material type 5 a lobe vertex, the coated diffuse of option coated (pinned in
+// include/pt_api.h): lobe_direction_coated() above, the mixture's p_b kept in the hook; whether type 4 is live there is the hook's
+// run-time answer (option glossy).  Every statement that does so sits under `if constexpr (HOOK::coated)`.
 struct NoShadeHook {
     static constexpr bool active = false;
     static constexpr bool smooth = false;
     static constexpr bool textured = false;
     static constexpr bool glossy = false;
+    static constexpr bool coated = false;
 };
 
 // The interpolated shading normal of a hit at hp = madd(D, t, P) on packed triangle ti (include/pt_api.h pins every operation): vn =
@@ -1337,7 +1440,9 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     if constexpr (HOOK::textured) {
         static_assert(HOOK::smooth && !REC, "the textured instances are built on the smooth ones");
         N = hook->shading_attributes_at(p, tris, ti, rD, hp, flip ? -N : N, N, type, m);
-        if constexpr (HOOK::glossy) {
+        if constexpr (HOOK::coated) {
+            if (p.iterations == 1) st.setC((type == 4 && hook->metal_live() ? ldf3(m->F0) : hook->albedo(m)) + ldf3(m->emission));
+        } else if constexpr (HOOK::glossy) {
             if (p.iterations == 1) st.setC((type == 4 ? ldf3(m->F0) : hook->albedo(m)) + ldf3(m->emission));
         } else {
             if (p.iterations == 1) st.setC(hook->albedo(m) + ldf3(m->emission));
@@ -1352,7 +1457,14 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     if constexpr (HOOK::glossy) {
         static_assert(HOOK::textured, "the glossy instances are built on the textured ones");
         gl = type == 4;
+        if constexpr (HOOK::coated) gl = gl && hook->metal_live();
         lobe = lobe || gl;
+    }
+    bool ct = false;                                                        // a coated-diffuse vertex (type 5 under option coated)
+    if constexpr (HOOK::coated) {
+        static_assert(HOOK::glossy, "the coated instances are built on the glossy ones");
+        ct = type == 5;
+        lobe = lobe || ct;
     }
     f3 dnew = rD;
     float side = 0.001f;
@@ -1368,7 +1480,8 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
             else hook->light_sample(st, p, m, type, N, hp);                 // before the LCG draws and this hit's emission
         }
         const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
-        if constexpr (HOOK::glossy) dnew = hook->template lobe_vertex<SK>(st, m, gl, N, rD, rnd1, rnd2);
+        if constexpr (HOOK::coated) dnew = hook->template lobe_vertex_coated<SK>(st, m, gl, ct, N, rD, rnd1, rnd2);
+        else if constexpr (HOOK::glossy) dnew = hook->template lobe_vertex<SK>(st, m, gl, N, rD, rnd1, rnd2);
         else if constexpr (REC) dnew = diffuse_direction_rec<SK>(N, rec + (flip ? 4 : 2), rnd1, rnd2);
         else dnew = diffuse_direction<SK>(N, rnd1, rnd2);
     } else if (spec) {
@@ -1439,7 +1552,8 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         else st.setC(madd(e, inten, st.C()));
     }
     // any other type: the ray is left unchanged and the loop hits the same surface again
-    if constexpr (HOOK::glossy) hook->end_vertex_glossy(lobe, gl, N, rD);
+    if constexpr (HOOK::coated) hook->end_vertex_glossy(lobe, gl || ct, N, rD);
+    else if constexpr (HOOK::glossy) hook->end_vertex_glossy(lobe, gl, N, rD);
     else if constexpr (HOOK::active) hook->end_vertex(lobe, N);
 }
 

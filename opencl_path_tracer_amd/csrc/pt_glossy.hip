@@ -2,6 +2,7 @@
 //   k_debug_glossy   pt_debug_glossy: one thread per item runs lobe_direction_glossy() and glossy_pdf_of() (pt_device.hpp), the functions
 //                    the glossy k_nee instances call (pt_nee.hip) for the sampled direction and for a light sample, so that the sampler
 //                    and the density can be tested against each other and against float64 without a render.  No scene is read.
+//   k_debug_coated   pt_debug_coated: the same for the coated diffuse of option coated (material type 5).
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -34,6 +35,43 @@ __global__ void __launch_bounds__(256) k_debug_glossy(const float* __restrict__ 
 hipError_t launch_debug_glossy(const float* in, int64_t n, float* out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_debug_glossy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, (long long)n, out);
+    return hipGetLastError();
+}
+
+// pt_debug_coated: lobe_direction_coated() and coated_pdf_weight_of() (pt_device.hpp), the functions the coated k_nee instances call for
+// the sampled direction and for a light sample.  in: 12 floats per item {N.xyz, D.xyz, alpha, F0, kd, rnd1, rnd2, u_sel} (F0 and kd grey);
+// out: 10 per item {w.xyz before normalisation (world), ps, 1 if the coat lobe drew w else 0, p_b as sampled, g.x as sampled, p_b and g.x
+// evaluated again from normalize(w), o.z}.  One thread per item: item i runs on lane i % 64
+__global__ void __launch_bounds__(256) k_debug_coated(const float* __restrict__ in, long long n, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* a = in + i * 12;
+    const f3 N = mk(a[0], a[1], a[2]), D = mk(a[3], a[4], a[5]);
+    const float alpha = a[6];
+    const f3 F0 = mk(a[7], a[7], a[7]), kd = mk(a[8], a[8], a[8]);
+    GlossyOut go;
+    CoatedOut co;
+    const f3 d = lobe_direction_coated<false>(N, D, false, true, alpha, F0, kd, a[11], a[9], a[10], &go, &co);
+    // the same direction by the light sample's route: world -> local, ps and h = normalize(o + w) from scratch
+    f3 Z, X, g;
+    tangent_frame(N, &Z, &X);
+    const float again = coated_pdf_weight_of(alpha, F0, kd, to_local(-D, X, Z, N), to_local(normalize3(d), X, Z, N), &g);
+    float* o = out + i * 10;
+    o[0] = d.x;
+    o[1] = d.y;
+    o[2] = d.z;
+    o[3] = co.ps;
+    o[4] = co.coat ? 1.0f : 0.0f;
+    o[5] = co.pb;
+    o[6] = co.g.x;
+    o[7] = again;
+    o[8] = g.x;
+    o[9] = co.oz;
+}
+
+hipError_t launch_debug_coated(const float* in, int64_t n, float* out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_debug_coated, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, (long long)n, out);
     return hipGetLastError();
 }
 

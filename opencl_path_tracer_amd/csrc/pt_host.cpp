@@ -306,16 +306,20 @@ int pt_upload_materials(pt_context* ctx) {
     for (const pt_triangle& t : ctx->tris)
         if (t.mati >= ctx->mats.size()) return fail(ctx, PT_EINVAL, "a triangle references a material index that was never added");
     ctx->glossy_mats = false;
-    for (const pt_material& m : ctx->mats) ctx->glossy_mats = ctx->glossy_mats || m.type == 4;
+    ctx->coated_mats = false;
+    for (const pt_material& m : ctx->mats) {
+        ctx->glossy_mats = ctx->glossy_mats || m.type == 4;
+        ctx->coated_mats = ctx->coated_mats || m.type == 5;
+    }
     if (ctx->has_device) {
         PT_HIP(ctx, hipSetDevice(ctx->device));
         // device copy: _pad marks materials whose specular lobe is identically zero (ks == 0, finite
         // shininess >= 0): the kernel then skips pow(), the product ks*pow being +0 either way
         std::vector<pt_material> dm(ctx->mats);
-        // a type-4 material carries its roughness in n, which only type 2 reads otherwise (option glossy)
+        // a type-4 or type-5 material carries its roughness in n, which only type 2 reads otherwise (options glossy, coated)
         for (pt_material& m : dm) {
             m._pad = (m.ks.s[0] == 0.0f && m.ks.s[1] == 0.0f && m.ks.s[2] == 0.0f && std::isfinite(m.shininess) && m.shininess >= 0.0f) ? 1 : 0;
-            if (m.type == 4) m.n = pt_material_roughness(m.shininess);
+            if (m.type == 4 || m.type == 5) m.n = pt_material_roughness(m.shininess);
         }
         ctx->shaderec_dirty = true;
         int rc = upload_vec(ctx, &ctx->d_mats, dm.data(), sizeof(pt_material) * dm.size());
@@ -537,7 +541,7 @@ int pt_render_aovs_ex(pt_context* ctx, const pt_camera* cam, const pt_aov_params
     if (!ctx->d_aov) PT_HIP(ctx, hipMalloc((void**)&ctx->d_aov, 2 * sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
-    PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->glossy, ctx->cu_count,
+    PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->glossy, ctx->coated, ctx->cu_count,
                                    ctx->stream));
     if (!ctx->aov_valid) ctx->temporal_history = false;      // (as pt_render_aovs: the first guides after stale ones)
     ctx->aov_valid = true;
@@ -917,7 +921,8 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     if ((rc = smooth_prepare(ctx, &vn)) != PT_OK) return rc;
     TexView tv;                        // option textures: uvs, texels, descriptors, bindings
     if ((rc = texture_prepare(ctx, &tv)) != PT_OK) return rc;
-    const bool glossy = ctx->glossy && ctx->glossy_mats;      // option glossy without a type-4 material: today's instances
+    const bool coated = ctx->coated && ctx->coated_mats;      // option coated without a type-5 material: today's instances
+    const bool glossy = ctx->glossy && (ctx->glossy_mats || coated);      // option glossy without a type-4 material: today's instances
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
     p.iterations = iterations;
@@ -927,7 +932,7 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     note_frame(ctx, p.first_sample, cam);
     EventPair* ep;
     if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-    PT_HIP(ctx, launch_nee(p, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, false, vn, tv.uv || glossy ? &tv : nullptr, glossy));
+    PT_HIP(ctx, launch_nee(p, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, false, vn, tv.uv || glossy || coated ? &tv : nullptr, glossy, coated));
     if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
     ctx->current_sample += nsamples;
     return PT_OK;
@@ -1142,6 +1147,25 @@ int pt_debug_glossy(pt_context* ctx, int64_t n, const float* N_D_alpha_rnd, floa
     return PT_OK;
 }
 
+// ---- coated diffuse (option coated; kernels: pt_glossy.hip, pt_nee.hip; pinned in include/pt_api.h)
+int pt_debug_coated(pt_context* ctx, int64_t n, const float* in, float* out) {
+    PT_NEED_DEVICE(ctx);
+    if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, PT_EINVAL, "pt_debug_coated: n >= 0, both arrays non-null");
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) (void)hipFree(p); }
+    } d_in, d_out;
+    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * 12 * (size_t)n));
+    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 10 * (size_t)n));
+    PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(float) * 12 * (size_t)n, hipMemcpyHostToDevice));
+    PT_HIP(ctx, launch_debug_coated((const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 // ---- albedo textures with UV coordinates (kernels: pt_texture.hip, pt_nee.hip; pinned in include/pt_api.h)
 // a float in [0, 65504] as an IEEE half, round to nearest even
 static uint16_t float_to_half(float f) {
@@ -1286,12 +1310,13 @@ int texture_prepare(pt_context* ctx, TexView* tv, bool force) {
     if (!ctx->textures && !force) return PT_OK;
     PT_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->tex_dirty || !ctx->d_mat_tex) {
-        // (every array keeps one readable record; a binding is -1 wherever the material on the device is not of type 0)
+        // (every array keeps one readable record; a binding is -1 wherever the material on the device is not of type 0 or 5; only the
+        // coated instances and the shaded guides under option coated look a type-5 binding up)
         const size_t nmat = std::max<size_t>((size_t)ctx->mats_on_device, 1), ntex = std::max<size_t>(ctx->tex_desc.size(), 1),
                      ntexel = std::max<size_t>(ctx->tex_texels.size(), 1);
         std::vector<int32_t> bind(nmat, -1);
         for (size_t i = 0; i < std::min<size_t>({(size_t)ctx->mats_on_device, ctx->mat_tex.size(), ctx->mats.size()}); ++i)
-            if (ctx->mats[i].type == 0 && ctx->mat_tex[i] >= 0 && ctx->mat_tex[i] < (int32_t)ctx->tex_desc.size()) bind[i] = ctx->mat_tex[i];
+            if ((ctx->mats[i].type == 0 || ctx->mats[i].type == 5) && ctx->mat_tex[i] >= 0 && ctx->mat_tex[i] < (int32_t)ctx->tex_desc.size()) bind[i] = ctx->mat_tex[i];
         std::vector<TexDesc> desc(ctx->tex_desc);
         desc.resize(ntex, TexDesc{0, 1, 1, 0});
         if (ctx->d_mat_tex) { PT_HIP(ctx, hipFree(ctx->d_mat_tex)); ctx->d_mat_tex = nullptr; }
@@ -1461,6 +1486,9 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value) {
     } else if (k == "glossy") {
         if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "glossy must be 0 (material type 4 is inert) or 1 (pt_render_nee shades it as a rough metal)");
         ctx->glossy = (int)value;
+    } else if (k == "coated") {
+        if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "coated must be 0 (material type 5 is inert) or 1 (pt_render_nee shades it as a diffuse base under a rough dielectric coat)");
+        ctx->coated = (int)value;
     } else if (k == "timing") {
         ctx->timing = value ? 1 : 0;
     } else if (k == "count_work") {

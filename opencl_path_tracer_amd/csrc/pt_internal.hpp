@@ -419,9 +419,9 @@ struct TexView {
     const int32_t* mat_tex;      // [materials on the device] texture of a type-0 material, else -1
 };
 // the shaded guides (pt_render_aovs_ex with PT_AOV_SHADED; pt_denoise.hip): vn == nullptr: option smooth_normals is off, tv.uv == nullptr:
-// option textures is off, glossy: option glossy (a terminal type-4 hit gives tint x F0)
+// option textures is off, glossy: option glossy (a terminal type-4 hit gives tint x F0), coated: option coated (a terminal type-5 hit gives tint x kd')
 hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
-                              const float4* vn, const TexView& tv, int glossy, int cu_count, hipStream_t stream);
+                              const float4* vn, const TexView& tv, int glossy, int coated, int cu_count, hipStream_t stream);
 // env == nullptr: the instances without an environment.  tiled (the rounds of pt_render_adaptive_ex): k_nee_tiles / k_nee_env_tiles over
 // the p.n_tiles 8x8 frame tiles of p.tile_list (null: the frame's tiles in order), one lane per pixel of a tile; npix is then not read
 // vn != nullptr (option smooth_normals): the smooth instances, which shade with the interpolated normal of the packed vertex normals vn
@@ -429,14 +429,18 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
 // which they read as "no triangle has vertex normals" (the pinned rule "no vertex normals: Ns = Ng, the same bits" makes that exact)
 // glossy (option glossy with a type-4 material uploaded; tv must then be non-null, with uv = null when option textures is off): the glossy
 // instances, built on the textured code
+// coated (option coated with a type-5 material uploaded; tv non-null as for glossy): the coated instances, built on the glossy code; glossy
+// is then option glossy itself and travels as a kernel argument (type 4 is live in the launch or inert)
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled = false,
-                      const float4* vn = nullptr, const TexView* tv = nullptr, bool glossy = false);
+                      const float4* vn = nullptr, const TexView* tv = nullptr, bool glossy = false, bool coated = false);
 // albedo textures (pt_texture.hip): add-order uvs (6 floats per triangle, n_src triangles; the rest has none) -> 2 float4 per packed triangle
 hipError_t launch_pack_vertex_uvs(const float* src, int64_t n_src, const int32_t* orig, int32_t n, float4* out, hipStream_t stream);
 hipError_t launch_debug_albedo(const RenderParams& p, const float4* vn, const TexView& tv, const pt_ray* rays, int64_t n, int32_t* out_tri, float4* out_rgbt,
                                int cu_count, hipStream_t stream);
 // rough metal (pt_glossy.hip): pt_debug_glossy's kernel, 9 floats in and 8 out per item
 hipError_t launch_debug_glossy(const float* in, int64_t n, float* out, hipStream_t stream);
+// coated diffuse (pt_glossy.hip): pt_debug_coated's kernel, 12 floats in and 10 out per item
+hipError_t launch_debug_coated(const float* in, int64_t n, float* out, hipStream_t stream);
 // smooth shading (pt_smooth.hip): add-order normals (9 floats per triangle, n_src triangles; the rest has none) -> 3 float4 per packed triangle
 hipError_t launch_pack_vertex_normals(const float* src, int64_t n_src, const int32_t* orig, int32_t n, float4* out, hipStream_t stream);
 hipError_t launch_debug_shading_normal(const RenderParams& p, const float4* vn, const pt_ray* rays, int64_t n, int32_t* out_tri, float4* out_ns, int cu_count,

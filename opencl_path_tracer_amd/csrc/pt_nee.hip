@@ -19,6 +19,9 @@
 //   k_nee*_glossy  the textured kernels with the rough metal of option glossy (material type 4): NeeHook<.., GLOSSY>;
 //           what they add sits under `if constexpr (GLOSSY)` here and under HOOK::glossy in shade_hit.  Launched only when the option is on
 //           and a type-4 material is uploaded.
+//   k_nee*_coated  the glossy kernels with the coated diffuse of option coated (material type 5): NeeHook<.., COAT>;
+//           what they add sits under `if constexpr (COAT)` here and under HOOK::coated in shade_hit.  Launched only when the option is on
+//           and a type-5 material is uploaded; whether type 4 is live in them is a run-time field (option glossy), as the strategy is.
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -75,15 +78,25 @@ struct GlossySlot<true> {
     float pb = 0.0f;               // p_b of the direction the previous lobe vertex sampled (these instances keep it instead of Nprev)
 };
 
+// what a hook carries for the coated diffuse (option coated): nothing without it
+template <bool COAT>
+struct CoatSlot {};
+template <>
+struct CoatSlot<true> {
+    bool metal = false;            // option glossy: type 4 is the rough metal in this launch (else inert, as in the instances without it)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
-template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false>
+template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false>
 struct NeeHook {
     static_assert(SMOOTH || !TEX, "the textured instances are built on the smooth code");
     static_assert(TEX || !GLOSSY, "the glossy instances are built on the textured code");
     static constexpr bool active = true;
     static constexpr bool smooth = SMOOTH;
     static constexpr bool textured = TEX;
+    static_assert(GLOSSY || !COAT, "the coated instances are built on the glossy code");
     static constexpr bool glossy = GLOSSY;
+    static constexpr bool coated = COAT;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -98,6 +111,52 @@ struct NeeHook {
     SmoothSlot<SMOOTH> sm;
     TexSlot<TEX> tx;
     GlossySlot<GLOSSY> gs;
+    CoatSlot<COAT> ct;
+
+    // COAT: type 4 is live (option glossy)
+    PT_DEV bool metal_live() const {
+        if constexpr (COAT) return ct.metal;
+        else return GLOSSY;
+    }
+    // COAT: the mixture's p_b of the unit direction w at the type-5 vertex with normal N reached along rD, and the factor_S its own update
+    // with w would give -- through coated_pdf_weight, as the sampled direction's (lobe_direction_coated)
+    PT_DEV float coated_light(const pt_material* __restrict__ m, f3 N, f3 rD, f3 w, f3 fS, f3* fs) const {
+        f3 Z, X;
+        tangent_frame(N, &Z, &X);
+        f3 g;
+        const float pb = coated_pdf_weight_of(m->n, ldf3(m->F0), albedo(m), to_local(-rD, X, Z, N), to_local(w, X, Z, N), &g);
+        *fs = fS * g;
+        return pb;
+    }
+    // COAT: lobe_vertex with the coated vertex (ct_) as a third kind: it multiplies factor_S by g(w), keeps the mixture's p_b and ends the
+    // path unless w.z > 0 and p_b > 0.  Its lobe is chosen by a hash value keyed like the environment's selection, dimension 1
+    template <bool SK, class ST>
+    PT_DEV f3 lobe_vertex_coated(ST& st, const pt_material* __restrict__ m, bool gl, bool ct_, f3 N, f3 rD, float rnd1, float rnd2) {
+        float alpha = 1.0f, u_sel = 0.0f;
+        f3 F0 = mk(0.f, 0.f, 0.f), kd = F0;
+        if (gl || ct_) {
+            alpha = m->n;          // (the device copy of a type-4 or type-5 material carries its roughness there: pt_upload_materials)
+            F0 = ldf3(m->F0);
+        }
+        if (ct_) {
+            kd = albedo(m);
+            u_sel = nee_unit(nee_rand(~key, k, 1));
+        }
+        GlossyOut go;
+        CoatedOut co;
+        const f3 d = lobe_direction_coated<SK>(N, rD, gl, ct_, alpha, F0, kd, u_sel, rnd1, rnd2, &go, &co);
+        if (gl) {
+            st.setS(st.S() * (go.F * go.g1w));
+            gs.pb = go.pb;
+            if (!(go.wz > 0.0f)) sm.dead = true;
+        }
+        if (ct_) {
+            st.setS(st.S() * co.g);
+            gs.pb = co.pb;
+            if (!(co.wz > 0.0f && co.pb > 0.0f)) sm.dead = true;
+        }
+        return d;
+    }
 
     // GLOSSY: p_b of the unit direction w at the type-4 vertex with normal N reached along rD, and the factor_S its own update with w
     // would give -- through glossy_pdf, as the sampled direction's (lobe_direction_glossy)
@@ -149,8 +208,10 @@ struct NeeHook {
         sm.flip = dot3(rD, N) > 0.0f;      // shade_hit's flip
         f3 kd = mk(0.f, 0.f, 0.f);
         if (type == 0 || p.iterations == 1) kd = ldf3(m->kd);
+        if constexpr (COAT) if (type == 5) kd = ldf3(m->kd);
         int ttype = type;              // GLOSSY: the instances also run with option textures off (a view with uv = null): no lookup then
-        if constexpr (GLOSSY) ttype = tx.v.uv ? type : -1;
+        if constexpr (COAT) ttype = type == 5 ? 0 : type;      // COAT: the lookup runs for type 0 or 5
+        if constexpr (GLOSSY) ttype = tx.v.uv ? ttype : -1;
         const f3 Ns = shading_normal_albedo(sm.vn, tx.v, tris, ti, rD, hp, N, Ng, ttype, (int)(m - p.mats), &kd);
         tx.kd = kd;
         return Ns;
@@ -280,6 +341,11 @@ struct NeeHook {
                 pb = glossy_light(m, N, rD, w, fs, &fs);
                 if (!(pb > 0.0f)) return;      // no density (or a half vector that cannot be normalised): the sample adds nothing
             }
+        if constexpr (COAT)
+            if (type == 5) {
+                pb = coated_light(m, N, rD, w, fs, &fs);
+                if (!(pb > 0.0f)) return;
+            }
         const float q = pb / pl;
         const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
         f3 fl = st.L(), fb = st.B();
@@ -374,6 +440,11 @@ struct NeeHook {
                 pb = glossy_light(m, N, rD, w, fs, &fs);
                 if (!(pb > 0.0f)) return;      // no density (or a half vector that cannot be normalised): the sample adds nothing
             }
+        if constexpr (COAT)
+            if (type == 5) {
+                pb = coated_light(m, N, rD, w, fs, &fs);
+                if (!(pb > 0.0f)) return;
+            }
         const float q = pb / pl;
         const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
         f3 fl = st.L(), fb = st.B();
@@ -428,15 +499,18 @@ struct NeeHook {
 // adds here sits under `if constexpr (SMOOTH)`
 // TEX (option textures; k_nee*_tex below; on the SMOOTH code only): the hook also supplies the albedo of a type-0 vertex from the view tv
 // GLOSSY (option glossy; k_nee*_glossy below; on the TEX code only): material type 4 is the rough-metal lobe vertex
-template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false>
-PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr) {
+// COAT (option coated; k_nee*_coated below; on the GLOSSY code only): material type 5 is the coated-diffuse lobe vertex; metal: option glossy
+template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false>
+PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr,
+                      int metal = 0) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (TEX) hook.tx.v = *tv;
+    if constexpr (COAT) hook.ct.metal = metal != 0;
     if constexpr (ENV) {
         hook.env = env;
         hook.nee = lt.strategy != 0;       // the sky is a light (the host launches this instance only for a map with a distribution)
@@ -582,6 +656,24 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_glossy(RenderParams p, 
     nee_frame<MODE, BLOCK, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv);
 }
 
+// the coated instances (option coated with a type-5 material uploaded): the glossy kernels with one more argument, metal (option glossy)
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_coated(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int metal, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, metal);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_coated(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int metal, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, metal);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_coated(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int metal) {
+    nee_frame<MODE, BLOCK, false, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, metal);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_coated(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int metal) {
+    nee_frame<MODE, BLOCK, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, metal);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -598,7 +690,17 @@ static hipError_t launch_lanes_env_tiles_smooth(PICK pick, const RenderParams& p
 }
 
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled, const float4* vn,
-                      const TexView* tv, bool glossy) {
+                      const TexView* tv, bool glossy, bool coated) {
+    if (coated) {      // (tv is never null here either; glossy: type 4 is live in the launch)
+        const int metal = glossy ? 1 : 0;
+        if (tiled) {
+            const int64_t items = (int64_t)p.n_tiles * 64;
+            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_coated<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv, metal);
+            return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_tiles_coated<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv, metal);
+        }
+        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_coated<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, metal, (long long)npix);
+        return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_coated<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, metal, (long long)npix);
+    }
     if (glossy) {      // (tv is never null here: the host hands a view with uv = null when option textures is off)
         if (tiled) {
             const int64_t items = (int64_t)p.n_tiles * 64;

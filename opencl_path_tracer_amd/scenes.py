@@ -134,14 +134,16 @@ def checker_texture(n, a, b):
     return np.where(even, np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)).astype(np.float32)
 
 
-def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False):
+def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False):
     """Scene CB of SURVEY 8(d): 12 wall/lamp triangles + two tessellated spheres
     (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects.
     smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals).
     textured: the floor carries uvs (one repeat per 1,600 units) and WHITE_DIFFUSE an 8 x 8 checker with nearest filtering, so under
     option textures the floor shows checks of 200 units; the other white walls have no uvs and keep their kd.
     glossy: the chromium sphere gets a copy of its material with type 4 and shininess 50, appended to the materials: a rough metal under
-    option glossy (and inert without it)."""
+    option glossy (and inert without it).
+    coated: the other sphere gets, in place of GLASS, a red plastic appended to the materials: type 5, kd (0.7, 0.1, 0.1), N = 1.5 and
+    K = 0 (F0 = 0.04), shininess 300; a diffuse base under a rough dielectric coat under option coated (and inert without it)."""
     spec = SceneSpec(materials=list(BUILTIN_MATERIALS), name="cornell_box")
     spec.objects.append(cornell_walls())
     s1 = uv_sphere((250.0, 200.0, 300.0), 200.0, segments, rings)
@@ -151,7 +153,11 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
         chromium = len(spec.materials) - 1
     spec.objects.append((s1, np.full(s1.shape[0], chromium, dtype=np.uint16)))
     s2 = uv_sphere((750.0, 200.0, -200.0), 200.0, segments, rings)
-    spec.objects.append((s2, np.full(s2.shape[0], GLASS, dtype=np.uint16)))
+    glass = GLASS
+    if coated:
+        spec.materials.append(((0.7, 0.1, 0.1), (0, 0, 0), (0, 0, 0), (1.5, 1.5, 1.5), (0, 0, 0), 300.0, 5))
+        glass = len(spec.materials) - 1
+    spec.objects.append((s2, np.full(s2.shape[0], glass, dtype=np.uint16)))
     if smooth:
         spec.normals = [None, uv_sphere_normals((250.0, 200.0, 300.0), 200.0, segments, rings),
                         uv_sphere_normals((750.0, 200.0, -200.0), 200.0, segments, rings)]
