@@ -484,6 +484,45 @@ int pt_debug_glossy(pt_context* ctx, int64_t n, const float* N_D_alpha_rnd, floa
  * the way a light sample evaluates them, o.z */
 int pt_debug_coated(pt_context* ctx, int64_t n, const float* in, float* out);
 
+/* ---- a thin-lens camera (depth of field) for pt_render_nee (new: opt-in with pt_set_lens) -----------
+ * pt_camera stays the reference's 80-byte pinhole record; the lens lives in the context, as the environment does.  With no lens set, after
+ * pt_clear_lens, or with aperture == 0 every path launches the kernels it launched before and computes what it computed before, bit for
+ * bit.  While a lens with aperture > 0 is set, pt_render_nee (every strategy, with and without an environment and every option) and
+ * pt_render_adaptive_ex with PT_ADAPT_PATH_NEE start each sample's path on the lens ray below; pt_render, pt_generate_rays, pt_trace_rays,
+ * pt_render_adaptive and pt_render_adaptive_ex with PT_ADAPT_PATH_RENDER return PT_EINVAL naming pt_clear_lens, checked before the device
+ * (PT_ENODEVICE).  pt_render_aovs, pt_render_aovs_ex, the denoisers and pt_temporal_accumulate keep the pinhole view and run as before:
+ * the guides are sharp where the frame is not.  Setting or clearing the lens makes no guides stale.
+ * The lens ray (float32; fma wherever dot3, madd and normalize3 use it: dot3(a, b) = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)),
+ * madd(u, s, w) = fmaf(u, s, w) per component, normalize3(a) = a * (1.0f / sqrtf(dot3(a, a))); division and sqrtf are IEEE).  Per sample, S
+ * is the pixel's LCG state at the start of the sample (the light samples' key); the two LCG draws rnd1, rnd2 of the sub-pixel position
+ * happen exactly as without a lens, and pp is the pinhole's point on the image plane (prog.cl:86-90):
+ *   d  = pp - eye                                       (the pinhole direction before normalisation)
+ *   f  = normalize3(lookat - eye);  Rh = normalize3(right);  Uh = normalize3(up)             (constants of a launch)
+ *   Q  = madd(d, focus_distance / dot3(d, f), eye)      (the point in focus: on the plane at axial distance focus_distance)
+ *   u1 = (pt_nee_rand(~S, -1, 0) >> 8) * 2^-24;  u2 = (pt_nee_rand(~S, -1, 1) >> 8) * 2^-24
+ *   r  = sqrtf(u1);  (s, c) = the sine and cosine the cosine lobe takes of (float)(6.283185307179586 * (double)u2)   
+ *   O  = madd(Uh, aperture * (r * s), madd(Rh, aperture * (r * c), eye))
+ *   P  = O;  D = normalize3(Q - O)
+ * Segment -1 of the complemented key is free: ~S carries dimension 0 (the environment's selection) and dimension 1 (the coat's lobe
+ * choice) of segments >= 0, and the hash's counter 3 segment + dim + 1 is -2 or -1 for the lens, so every light sample and lobe choice
+ * keeps its number.  The lens draws nothing from the LCG: rnds ends where a float64 replay with the same seeds ends.  The eye of the
+ * type-0 highlight stays cam.eye.  The sample weight is 1 (a thin lens with a uniform disc needs no factor). */
+typedef struct {
+    float aperture;        /* lens radius in scene units, >= 0 and finite; 0 = pinhole */
+    float focus_distance;  /* > 0 and finite: distance of the plane in focus from cam.eye, measured ALONG the optical axis */
+    float _pad[2];
+} pt_lens_params;
+void pt_lens_defaults(pt_lens_params* p);      /* {0, 1, 0, 0} */
+/* PT_EINVAL for an aperture that is negative, NaN or infinite, or a focus_distance that is not finite and > 0 */
+int pt_set_lens(pt_context* ctx, const pt_lens_params* p);
+int pt_clear_lens(pt_context* ctx);
+/* autofocus: the axial distance of the first hit of pixel (x, y)'s centre ray (camera_get_ray(gid, cam, 0.5f, 0.5f), gid = y XM + x; row 0
+ * as in the buffers): t * dot3(D, f); +inf on a miss.  Needs an uploaded scene and a device (host-only context: PT_ENODEVICE). */
+int pt_focus_at(pt_context* ctx, const pt_camera* cam, int32_t x, int32_t y, float* distance);
+/* the device's lens ray on caller-supplied items (as pt_debug_glossy; host-only context: PT_ENODEVICE): per item {gid, S} (two int32; the
+ * two LCG draws are taken from S), out 6 floats P, D.  The kernel calls the device function the lens instances of k_nee call. */
+int pt_debug_lens(pt_context* ctx, const pt_camera* cam, const pt_lens_params* lens, int64_t n, const int32_t* gid_state, float* out);
+
 /* ---- per-pixel variance of the mean luminance (new: opt-in with option "moments"; the reference keeps the mean only) -------
  * With option "moments" = 1 every render path (pt_render in every variant, schedule and node mode, pt_trace_rays,
  * pt_render_adaptive, pt_render_nee, tiled ranks) also folds each sample's squared luminance into colors[].w, float32 in this order:

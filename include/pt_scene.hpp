@@ -143,6 +143,23 @@ public:
     // the coated diffuse of material type 5 (set_option("coated", 1); render_nee only): the device functions of the vertex, 12 floats in
     // (N, D, alpha, F0, kd, rnd1, rnd2, u_sel) and 10 out per item (pt_debug_coated)
     void debug_coated(int64_t n, const float* in, float* out) { ck(pt_debug_coated(ctx, n, in, out)); }
+    // a thin lens for render_nee and the NEE path of render_adaptive (pt_set_lens; aperture = the lens radius, 0: the pinhole; focus_distance
+    // along the optical axis).  While aperture > 0 only they render; the guides keep the pinhole view.  focus_at: the axial distance of the
+    // first hit under pixel (x, y) of the last render's view, +inf on a miss; debug_lens: the device's lens ray of n items {gid, S}, 6 floats each
+    void set_lens(float aperture, float focus_distance) {
+        const pt_lens_params p = {aperture, focus_distance, {0.0f, 0.0f}};
+        ck(pt_set_lens(ctx, &p));
+    }
+    void clear_lens() { ck(pt_clear_lens(ctx)); }
+    float focus_at(int32_t x, int32_t y) {
+        float d = 0.0f;
+        ck(pt_focus_at(ctx, &camera, x, y, &d));
+        return d;
+    }
+    void debug_lens(float aperture, float focus_distance, int64_t n, const int32_t* gid_state, float* out) {
+        const pt_lens_params p = {aperture, focus_distance, {0.0f, 0.0f}};
+        ck(pt_debug_lens(ctx, &camera, &p, n, gid_state, out));
+    }
     // the spec math and sampling primitives of the kernels on n items of 32-bit words (pt_debug_spec; fn = PT_SPEC_*)
     void debug_spec(int32_t fn, int64_t n, const uint32_t* in, uint32_t* out) { ck(pt_debug_spec(ctx, fn, n, in, out)); }
     // guide buffers of the current view (pt_render_aovs) and the a-trous filter over them (pt_denoise; p = NULL: the defaults)

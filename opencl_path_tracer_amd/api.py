@@ -50,6 +50,7 @@ EXPORTS = [
     "pt_texture_defaults", "pt_add_texture", "pt_clear_textures", "pt_set_material_texture", "pt_debug_texture",
     "pt_set_vertex_uvs", "pt_clear_vertex_uvs", "pt_debug_vertex_uvs", "pt_debug_albedo", "pt_image_read_ppm",
     "pt_material_roughness", "pt_debug_glossy", "pt_debug_coated",
+    "pt_lens_defaults", "pt_set_lens", "pt_clear_lens", "pt_focus_at", "pt_debug_lens",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
@@ -131,6 +132,11 @@ def _load():
     sig("pt_material_roughness", f32, f32)
     sig("pt_debug_glossy", C.c_int, vp, i64, vp, vp)
     sig("pt_debug_coated", C.c_int, vp, i64, vp, vp)
+    sig("pt_lens_defaults", None, vp)
+    sig("pt_set_lens", C.c_int, vp, vp)
+    sig("pt_clear_lens", C.c_int, vp)
+    sig("pt_focus_at", C.c_int, vp, vp, i32, i32, fp)
+    sig("pt_debug_lens", C.c_int, vp, vp, vp, i64, vp, vp)
     sig("pt_environment_defaults", None, vp)
     sig("pt_set_environment", C.c_int, vp, vp, i32, i32, vp)
     sig("pt_clear_environment", C.c_int, vp)
@@ -315,6 +321,21 @@ def environment_defaults():
     """pt_environment_defaults as a dict: scale, yaw_degrees, select."""
     p = EnvironmentParams()
     LIB.pt_environment_defaults(C.byref(p))
+    return p.as_dict()
+
+
+class LensParams(C.Structure):
+    """pt_lens_params (include/pt_api.h): aperture = the lens radius (0: the pinhole), focus_distance along the optical axis."""
+    _fields_ = [("aperture", C.c_float), ("focus_distance", C.c_float), ("_pad", C.c_float * 2)]
+
+    def as_dict(self):
+        return {"aperture": self.aperture, "focus_distance": self.focus_distance}
+
+
+def lens_defaults():
+    """pt_lens_defaults as a dict: aperture, focus_distance."""
+    p = LensParams()
+    LIB.pt_lens_defaults(C.byref(p))
     return p.as_dict()
 
 
@@ -654,6 +675,33 @@ class Scene:
         items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 12)
         out = np.empty((items.shape[0], 10), dtype=np.float32)
         self._ck(LIB.pt_debug_coated(self._h, items.shape[0], _ptr(items), _ptr(out)))
+        return out
+
+    # -- the thin lens of render_nee and render_adaptive(path="nee") (include/pt_api.h pins the lens ray)
+    def set_lens(self, aperture, focus_distance):
+        """pt_set_lens: aperture = the lens radius in scene units (0: the pinhole, today's kernels and bits), focus_distance = the distance
+        of the plane in focus from the eye along the optical axis.  While aperture > 0 only render_nee and render_adaptive(path="nee")
+        render; the guide buffers keep the pinhole view."""
+        p = LensParams(float(aperture), float(focus_distance))
+        self._ck(LIB.pt_set_lens(self._h, C.byref(p)))
+
+    def clear_lens(self):
+        self._ck(LIB.pt_clear_lens(self._h))
+
+    def focus_at(self, x, y):
+        """pt_focus_at: the axial distance of the first hit of pixel (x, y)'s centre ray under the current camera, +inf on a miss."""
+        d = C.c_float()
+        self._ck(LIB.pt_focus_at(self._h, _ptr(self.camera), int(x), int(y), C.byref(d)))
+        return float(d.value)
+
+    def debug_lens(self, aperture, focus_distance, items, camera=None):
+        """pt_debug_lens: items (n, 2) int32 {gid, S} -> (n, 6) float32 {P, D}, the lens ray of the sample of pixel gid that starts at LCG
+        state S, by the device function the lens instances of k_nee call (camera: a CAMERA record, default the scene's)."""
+        items = np.ascontiguousarray(items, dtype=np.int32).reshape(-1, 2)
+        out = np.empty((items.shape[0], 6), dtype=np.float32)
+        p = LensParams(float(aperture), float(focus_distance))
+        cam = self.camera if camera is None else np.ascontiguousarray(camera, dtype=CAMERA)
+        self._ck(LIB.pt_debug_lens(self._h, _ptr(cam), C.byref(p), items.shape[0], _ptr(items), _ptr(out)))
         return out
 
     def upload_Triangles(self):

@@ -218,6 +218,10 @@ struct pt_context {
     // instances run only when the option is on AND the materials uploaded last hold a type-5 one; every other frame is today's launch
     int coated = 0;
     bool coated_mats = false;          // pt_upload_materials saw a material of type 5
+    // thin lens (pt_set_lens; pinned in include/pt_api.h): pt_render_nee and the NEE path of pt_render_adaptive_ex start their paths on the
+    // lens ray while lens_set && lens_aperture > 0 (the lens instances of k_nee); every other frame is today's launch
+    bool lens_set = false;
+    float lens_aperture = 0.0f, lens_focus = 1.0f;
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -265,6 +269,8 @@ int light_table_ready(pt_context* ctx);                            // pt_host.cp
 float env_select(const pt_context* ctx, bool no_lights);           // pt_env.cpp: the effective P_env
 // pt_host.cpp: the light table on the device and the environment's view (*sky: a map with a distribution is set) for a launch_nee
 int nee_prepare(pt_context* ctx, int32_t strategy, NeeTable* lt, EnvView* env, bool* sky);
+// a lens with aperture > 0 is set: only pt_render_nee and the NEE path of pt_render_adaptive_ex render
+inline bool lens_on(const pt_context* ctx) { return ctx->lens_set && ctx->lens_aperture > 0.0f; }
 // pt_host.cpp: the packed vertex normals on the device for a smooth launch (repacked if stale); *vn = null when the option is off, unless force
 int smooth_prepare(pt_context* ctx, const float4** vn, bool force = false);
 // pt_host.cpp: the textures, bindings and packed uvs on the device for a textured launch (refreshed if stale); tv->uv = null when the

@@ -326,6 +326,28 @@ PT_DEV void camera_get_ray(int id, const pt_camera& cam, float rnd1, float rnd2,
     const int X = (int)cam.XM;
     camera_get_ray_xy((float)(id % X), (float)(id / X), cam, rnd1, rnd2, P, D);
 }
+// The thin-lens ray of the same sub-pixel position (pt_set_lens; include/pt_api.h pins every operation): from a point of the lens disc,
+// drawn from two hash values of segment -1 of the complemented key S, through the point in focus on the pinhole ray.  The lens
+// instances of k_nee and k_debug_lens call this one function.
+PT_DEV void lens_get_ray_xy(float px, float py, const pt_camera& cam, const LensView& lv, float rnd1, float rnd2, unsigned S, f3* P, f3* D) {
+    const int X = (int)cam.XM;
+    const int Y = (int)cam.YM;
+    const float x = px + rnd1;
+    const float y = py + rnd2;
+    const f3 right = ldf3(cam.right) * ((2.0f * x) / (float)X - 1.0f);
+    const f3 up = ldf3(cam.up) * ((2.0f * y) / (float)Y - 1.0f);
+    const f3 pp = (ldf3(cam.lookat) + right) + up;
+    const f3 eye = ldf3(cam.eye);
+    const f3 d = pp - eye;
+    const f3 Q = madd(d, lv.focus / dot3(d, mk(lv.f[0], lv.f[1], lv.f[2])), eye);
+    const float u1 = (float)(nee_rand(~S, -1, 0) >> 8) * 5.9604644775390625e-08f, u2 = (float)(nee_rand(~S, -1, 1) >> 8) * 5.9604644775390625e-08f;
+    const float r = __builtin_sqrtf(u1);
+    float sn, cs;
+    spec_sincos<false>((float)(6.283185307179586 * (double)u2), &sn, &cs);
+    const f3 O = madd(mk(lv.Uh[0], lv.Uh[1], lv.Uh[2]), lv.aperture * (r * sn), madd(mk(lv.Rh[0], lv.Rh[1], lv.Rh[2]), lv.aperture * (r * cs), eye));
+    *P = O;
+    *D = normalize3(Q - O);
+}
 
 // ---------------------------------------------------------------------------- traversal
 // dynamic LDS of every traversal kernel: [per-lane stacks][staged nodes][big-triangle list] (setup_traversal)
@@ -1300,6 +1322,7 @@ struct NoShadeHook {
     static constexpr bool textured = false;
     static constexpr bool glossy = false;
     static constexpr bool coated = false;
+    static constexpr bool lens = false;
 };
 
 // The interpolated shading normal of a hit at hp = madd(D, t, P) on packed triangle ti (include/pt_api.h pins every operation): vn =
@@ -1464,6 +1487,7 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     if constexpr (HOOK::coated) {
         static_assert(HOOK::glossy, "the coated instances are built on the glossy ones");
         ct = type == 5;
+        if constexpr (HOOK::lens) ct = ct && hook->coat_live();             // (the lens instances serve option coated = 0 too)
         lobe = lobe || ct;
     }
     f3 dnew = rD;

@@ -932,7 +932,10 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     note_frame(ctx, p.first_sample, cam);
     EventPair* ep;
     if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-    PT_HIP(ctx, launch_nee(p, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, false, vn, tv.uv || glossy || coated ? &tv : nullptr, glossy, coated));
+    const bool lens = lens_on(ctx);        // a lens: the lens instances, whatever the options say
+    const LensView lv = lens_view(*cam, ctx->lens_aperture, ctx->lens_focus);
+    PT_HIP(ctx, launch_nee(p, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, false, vn, tv.uv || glossy || coated || lens ? &tv : nullptr,
+                           lens ? ctx->glossy != 0 : glossy, lens ? ctx->coated != 0 : coated, lens ? &lv : nullptr));
     if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
     ctx->current_sample += nsamples;
     return PT_OK;
@@ -1163,6 +1166,80 @@ int pt_debug_coated(pt_context* ctx, int64_t n, const float* in, float* out) {
     PT_HIP(ctx, launch_debug_coated((const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// ---- thin lens (pt_set_lens; kernels: pt_lens.hip, pt_nee.hip; pinned in include/pt_api.h)
+void pt_lens_defaults(pt_lens_params* p) {
+    if (!p) return;
+    p->aperture = 0.0f;
+    p->focus_distance = 1.0f;
+    p->_pad[0] = p->_pad[1] = 0.0f;
+}
+
+static std::string lens_check(const pt_lens_params* p) {
+    if (!p) return "params is NULL";
+    if (!(p->aperture >= 0.0f && std::isfinite(p->aperture))) return "aperture must be >= 0 and finite";
+    if (!(p->focus_distance > 0.0f && std::isfinite(p->focus_distance))) return "focus_distance must be > 0 and finite";
+    return "";
+}
+
+int pt_set_lens(pt_context* ctx, const pt_lens_params* p) {
+    if (!ctx) return PT_EINVAL;
+    const std::string why = lens_check(p);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_set_lens: " + why);
+    ctx->lens_set = true;
+    ctx->lens_aperture = p->aperture;
+    ctx->lens_focus = p->focus_distance;
+    return PT_OK;
+}
+
+int pt_clear_lens(pt_context* ctx) {
+    if (!ctx) return PT_EINVAL;
+    ctx->lens_set = false;
+    ctx->lens_aperture = 0.0f;
+    ctx->lens_focus = 1.0f;
+    return PT_OK;
+}
+
+int pt_focus_at(pt_context* ctx, const pt_camera* cam, int32_t x, int32_t y, float* distance) {
+    PT_NEED_DEVICE(ctx);
+    if (!distance) return fail(ctx, PT_EINVAL, "pt_focus_at: distance is NULL");
+    int rc = check_ready(ctx, cam);
+    if (rc != PT_OK) return rc;
+    if (x < 0 || x >= ctx->W || y < 0 || y >= ctx->H) return fail(ctx, PT_EINVAL, "pt_focus_at: (x, y) must be a pixel of the frame");
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    fill_params(ctx, cam, &p);
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) (void)hipFree(p); }
+    } d_out;
+    PT_HIP(ctx, hipMalloc(&d_out.p, 16));
+    PT_HIP(ctx, launch_focus_at(p, lens_view(*cam, 0.0f, 1.0f), y * ctx->W + x, (float*)d_out.p, ctx->cu_count, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(distance, d_out.p, sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_debug_lens(pt_context* ctx, const pt_camera* cam, const pt_lens_params* lens, int64_t n, const int32_t* gid_state, float* out) {
+    PT_NEED_DEVICE(ctx);
+    if (!cam || n < 0 || (n > 0 && (!gid_state || !out))) return fail(ctx, PT_EINVAL, "pt_debug_lens: camera non-null, n >= 0, both arrays non-null");
+    const std::string why = lens_check(lens);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_debug_lens: " + why);
+    if (!((int32_t)cam->XM > 0 && (int32_t)cam->YM > 0)) return fail(ctx, PT_EINVAL, "pt_debug_lens: camera XM/YM must be positive");
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) (void)hipFree(p); }
+    } d_in, d_out;
+    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(int32_t) * 2 * (size_t)n));
+    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 6 * (size_t)n));
+    PT_HIP(ctx, hipMemcpy(d_in.p, gid_state, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice));
+    PT_HIP(ctx, launch_debug_lens(*cam, lens_view(*cam, lens->aperture, lens->focus_distance), (const int32_t*)d_in.p, n, (float*)d_out.p, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 6 * (size_t)n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -418,6 +418,27 @@ struct TexView {
     const TexDesc* desc;         // [textures]
     const int32_t* mat_tex;      // [materials on the device] texture of a type-0 material, else -1
 };
+// the thin lens of pt_render_nee (pt_set_lens; pinned in include/pt_api.h): the parameters and the launch's constants f, Rh, Uh
+struct LensView {
+    float aperture, focus;
+    float f[3], Rh[3], Uh[3];
+};
+// normalize3 of pt_device.hpp on the host: dot3's fma placement, then a * (1.0f / sqrtf(l2)), IEEE
+inline void lens_normalize(const float* a, float* out) {
+    const float l2 = __builtin_fmaf(a[2], a[2], __builtin_fmaf(a[1], a[1], a[0] * a[0]));
+    const float s = 1.0f / __builtin_sqrtf(l2);
+    for (int i = 0; i < 3; ++i) out[i] = a[i] * s;
+}
+inline LensView lens_view(const pt_camera& cam, float aperture, float focus) {
+    LensView lv;
+    lv.aperture = aperture;
+    lv.focus = focus;
+    const float ahead[3] = {cam.lookat.s[0] - cam.eye.s[0], cam.lookat.s[1] - cam.eye.s[1], cam.lookat.s[2] - cam.eye.s[2]};
+    lens_normalize(ahead, lv.f);
+    lens_normalize(cam.right.s, lv.Rh);
+    lens_normalize(cam.up.s, lv.Uh);
+    return lv;
+}
 // the shaded guides (pt_render_aovs_ex with PT_AOV_SHADED; pt_denoise.hip): vn == nullptr: option smooth_normals is off, tv.uv == nullptr:
 // option textures is off, glossy: option glossy (a terminal type-4 hit gives tint x F0), coated: option coated (a terminal type-5 hit gives tint x kd')
 hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
@@ -431,8 +452,15 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
 // instances, built on the textured code
 // coated (option coated with a type-5 material uploaded; tv non-null as for glossy): the coated instances, built on the glossy code; glossy
 // is then option glossy itself and travels as a kernel argument (type 4 is live in the launch or inert)
+// lens (a lens with aperture > 0 is set, pt_set_lens; tv non-null as for glossy): the lens instances, built on the coated code, whatever
+// the options say; glossy and coated are then the options themselves and travel as a kernel argument, vn and tv->uv are null where
+// their option is off
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled = false,
-                      const float4* vn = nullptr, const TexView* tv = nullptr, bool glossy = false, bool coated = false);
+                      const float4* vn = nullptr, const TexView* tv = nullptr, bool glossy = false, bool coated = false, const LensView* lens = nullptr);
+// thin lens (pt_lens.hip): pt_debug_lens's kernel, {gid, S} in and 6 floats out per item; pt_focus_at's, the axial distance of pixel gid's
+// centre-ray hit into *out (+inf: a miss)
+hipError_t launch_debug_lens(const pt_camera& cam, const LensView& lv, const int32_t* gid_state, int64_t n, float* out, hipStream_t stream);
+hipError_t launch_focus_at(const RenderParams& p, const LensView& lv, int32_t gid, float* out, int cu_count, hipStream_t stream);
 // albedo textures (pt_texture.hip): add-order uvs (6 floats per triangle, n_src triangles; the rest has none) -> 2 float4 per packed triangle
 hipError_t launch_pack_vertex_uvs(const float* src, int64_t n_src, const int32_t* orig, int32_t n, float4* out, hipStream_t stream);
 hipError_t launch_debug_albedo(const RenderParams& p, const float4* vn, const TexView& tv, const pt_ray* rays, int64_t n, int32_t* out_tri, float4* out_rgbt,

@@ -22,6 +22,10 @@
 //   k_nee*_coated  the glossy kernels with the coated diffuse of option coated (material type 5): NeeHook<.., COAT>;
 //           what they add sits under `if constexpr (COAT)` here and under HOOK::coated in shade_hit.  Launched only when the option is on
 //           and a type-5 material is uploaded; whether type 4 is live in them is a run-time field (option glossy), as the strategy is.
+//   k_nee*_lens  the coated kernels with the thin-lens camera of pt_set_lens: nee_frame<.., LENS> starts each
+//           sample on lens_get_ray_xy (pt_device.hpp) instead of camera_get_ray_xy; what it adds sits under `if constexpr (LENS)`.  One
+//           family serves every option combination, so whether type 5 is live is a run-time field in them too (option coated), next to
+//           type 4's; normals and uvs are bound or null as in the instances below them.  Launched only while a lens with aperture > 0 is set.
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -86,9 +90,19 @@ struct CoatSlot<true> {
     bool metal = false;            // option glossy: type 4 is the rough metal in this launch (else inert, as in the instances without it)
 };
 
+// what a frame carries for the thin lens (pt_set_lens): nothing without it
+template <bool LENS>
+struct LensSlot {};
+template <>
+struct LensSlot<true> {
+    LensView v;                    // aperture, focus distance and the launch's f, Rh, Uh (lens_view, pt_internal.hpp)
+    bool coat = true;              // option coated: type 5 is the coated diffuse in this launch (else inert, as in the instances without it)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
-template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false>
+template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false>
 struct NeeHook {
+    static_assert(COAT || !LENS, "the lens instances are built on the coated code");
     static_assert(SMOOTH || !TEX, "the textured instances are built on the smooth code");
     static_assert(TEX || !GLOSSY, "the glossy instances are built on the textured code");
     static constexpr bool active = true;
@@ -97,6 +111,7 @@ struct NeeHook {
     static_assert(GLOSSY || !COAT, "the coated instances are built on the glossy code");
     static constexpr bool glossy = GLOSSY;
     static constexpr bool coated = COAT;
+    static constexpr bool lens = LENS;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -112,7 +127,13 @@ struct NeeHook {
     TexSlot<TEX> tx;
     GlossySlot<GLOSSY> gs;
     CoatSlot<COAT> ct;
+    LensSlot<LENS> ln;
 
+    // LENS: type 5 is live (option coated; a run-time answer in the lens instances only: the coated ones run only when it is)
+    PT_DEV bool coat_live() const {
+        if constexpr (LENS) return ln.coat;
+        else return COAT;
+    }
     // COAT: type 4 is live (option glossy)
     PT_DEV bool metal_live() const {
         if constexpr (COAT) return ct.metal;
@@ -208,9 +229,15 @@ struct NeeHook {
         sm.flip = dot3(rD, N) > 0.0f;      // shade_hit's flip
         f3 kd = mk(0.f, 0.f, 0.f);
         if (type == 0 || p.iterations == 1) kd = ldf3(m->kd);
-        if constexpr (COAT) if (type == 5) kd = ldf3(m->kd);
         int ttype = type;              // GLOSSY: the instances also run with option textures off (a view with uv = null): no lookup then
-        if constexpr (COAT) ttype = type == 5 ? 0 : type;      // COAT: the lookup runs for type 0 or 5
+        if constexpr (LENS) {          // LENS: as COAT below where type 5 is live in the launch (option coated)
+            const bool live = type == 5 && ln.coat;
+            if (live) kd = ldf3(m->kd);
+            ttype = live ? 0 : type;
+        } else {
+            if constexpr (COAT) if (type == 5) kd = ldf3(m->kd);
+            if constexpr (COAT) ttype = type == 5 ? 0 : type;      // COAT: the lookup runs for type 0 or 5
+        }
         if constexpr (GLOSSY) ttype = tx.v.uv ? ttype : -1;
         const f3 Ns = shading_normal_albedo(sm.vn, tx.v, tris, ti, rD, hp, N, Ng, ttype, (int)(m - p.mats), &kd);
         tx.kd = kd;
@@ -500,17 +527,22 @@ struct NeeHook {
 // TEX (option textures; k_nee*_tex below; on the SMOOTH code only): the hook also supplies the albedo of a type-0 vertex from the view tv
 // GLOSSY (option glossy; k_nee*_glossy below; on the TEX code only): material type 4 is the rough-metal lobe vertex
 // COAT (option coated; k_nee*_coated below; on the GLOSSY code only): material type 5 is the coated-diffuse lobe vertex; metal: option glossy
-template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false>
+// LENS (pt_set_lens; k_nee*_lens below; on the COAT code only): each sample starts on the thin-lens ray; metal bit 1: option coated
+template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr,
-                      int metal = 0) {
+                      int metal = 0, const LensView* lens = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (TEX) hook.tx.v = *tv;
-    if constexpr (COAT) hook.ct.metal = metal != 0;
+    if constexpr (LENS) {
+        hook.ct.metal = (metal & 1) != 0;
+        hook.ln.coat = (metal & 2) != 0;
+        hook.ln.v = *lens;
+    } else if constexpr (COAT) hook.ct.metal = metal != 0;
     if constexpr (ENV) {
         hook.env = env;
         hook.nee = lt.strategy != 0;       // the sky is a light (the host launches this instance only for a map with a distribution)
@@ -554,7 +586,8 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
             bool inside = false;
             {
                 const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
-                camera_get_ray_xy(pix_x, pix_y, p.cam, rnd1, rnd2, &rP, &rD);
+                if constexpr (LENS) lens_get_ray_xy(pix_x, pix_y, p.cam, hook.ln.v, rnd1, rnd2, hook.key, &rP, &rD);
+                else camera_get_ray_xy(pix_x, pix_y, p.cam, rnd1, rnd2, &rP, &rD);
             }
             for (int k = 0; k < p.iterations; ++k) {
                 float t;
@@ -674,6 +707,25 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_coated(RenderParams p, 
     nee_frame<MODE, BLOCK, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, metal);
 }
 
+// the lens instances (a lens with aperture > 0 is set): the coated kernels with the lens view as one more argument; flags: bit 0 option
+// glossy, bit 1 option coated (vn = null, tv.uv = null: smooth_normals, textures off)
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_lens(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_lens(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_lens(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv) {
+    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_lens(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv) {
+    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -690,7 +742,17 @@ static hipError_t launch_lanes_env_tiles_smooth(PICK pick, const RenderParams& p
 }
 
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled, const float4* vn,
-                      const TexView* tv, bool glossy, bool coated) {
+                      const TexView* tv, bool glossy, bool coated, const LensView* lens) {
+    if (lens) {        // (tv is never null here; glossy, coated: the options themselves)
+        const int flags = (glossy ? 1 : 0) | (coated ? 2 : 0);
+        if (tiled) {
+            const int64_t items = (int64_t)p.n_tiles * 64;
+            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_lens<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv, flags, *lens);
+            return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_tiles_lens<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv, flags, *lens);
+        }
+        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_lens<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, flags, *lens, (long long)npix);
+        return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_lens<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, flags, *lens, (long long)npix);
+    }
     if (coated) {      // (tv is never null here either; glossy: type 4 is live in the launch)
         const int metal = glossy ? 1 : 0;
         if (tiled) {

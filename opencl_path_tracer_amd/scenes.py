@@ -171,6 +171,37 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
     return spec
 
 
+FOCUS_ROW_SPHERES = [((-2.4, -1.1, 5.0), 0), ((-0.8, -1.1, 8.0), 4), ((0.8, -1.1, 12.0), 5), ((2.4, -1.1, 17.0), 6)]
+
+
+def focus_row(segments=8, rings=4):
+    """A depth-of-field scene for Scene.set_lens: a grey floor (y = -2) under an area light (y = 6), seen from the origin along +z, and on
+    it a diagonal row of four spheres of radius 0.9 at depths 5, 8, 12 and 17: a red type-0 one with a specular lobe, a glass one, a
+    rough-gold type-4 one (option glossy) and a blue type-5 plastic one (option coated), each with its analytic vertex normals (option
+    smooth_normals).  Nothing closes the scene, so a sky set with Scene.set_environment is seen above the floor."""
+    gold = BUILTIN_MATERIALS[GOLD]
+    mats = [
+        ((0.6, 0.1, 0.1), (0.2, 0.2, 0.2), (0, 0, 0), (0, 0, 0), (0, 0, 0), 20.0, 0),      # 0 red, specular lobe
+        ((0.5, 0.5, 0.5), (0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0), 1.0, 0),             # 1 floor
+        ((0, 0, 0), (0, 0, 0), (6.0, 5.0, 4.0), (0, 0, 0), (0, 0, 0), 0.0, 3),             # 2 lamp
+        ((0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0), 0.0, 0),                   # 3 (spare: black)
+        BUILTIN_MATERIALS[GLASS],                                                            # 4 glass
+        tuple(gold[:5]) + (50.0, 4),                                                         # 5 rough gold
+        ((0.1, 0.2, 0.6), (0, 0, 0), (0, 0, 0), (1.5, 1.5, 1.5), (0, 0, 0), 20.0, 5),      # 6 blue plastic
+    ]
+    spec = SceneSpec(materials=mats, name="focus_row", shift=(-500.0, -500.0, 1299.0378))
+    x0, x1, z0, z1 = -8.0, 8.0, 0.5, 30.0
+    tris = [((x0, -2.0, z0), (x1, -2.0, z0), (x1, -2.0, z1)), ((x0, -2.0, z0), (x1, -2.0, z1), (x0, -2.0, z1)),
+            ((-3.0, 6.0, 4.0), (3.0, 6.0, 4.0), (3.0, 6.0, 16.0)), ((-3.0, 6.0, 4.0), (3.0, 6.0, 16.0), (-3.0, 6.0, 16.0))]
+    spec.objects.append((np.asarray(tris, dtype=np.float32), np.asarray([1, 1, 2, 2], dtype=np.uint16)))
+    spec.normals = [None]
+    for c, m in FOCUS_ROW_SPHERES:
+        v = uv_sphere(c, 0.9, segments, rings)
+        spec.objects.append((v, np.full(len(v), m, dtype=np.uint16)))
+        spec.normals.append(uv_sphere_normals(c, 0.9, segments, rings))
+    return spec
+
+
 def sun_and_sky(width=64, height=32, sun_dir=(0.3, 0.8, 0.5), sun_radius_deg=5.0, sun_radiance=(400.0, 360.0, 300.0),
                 zenith=(0.25, 0.45, 0.9), horizon=(0.8, 0.85, 0.9), ground=(0.1, 0.09, 0.08)):
     """A procedural lat-long map (height, width, 3) float32 for Scene.set_environment, row 0 at the +y pole: a sky that fades from
