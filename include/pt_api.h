@@ -800,6 +800,10 @@ int pt_debug_bvh_copy(const pt_context* ctx, float* nodes, float* tris, int32_t*
  * qlo_y, qhi_y}, {qlo_z, qhi_z, -, -}, {4 child references}); *count = how many there are (0: not built), at most
  * `capacity` are copied */
 int pt_debug_wide_nodes(const pt_context* ctx, void* out, int64_t capacity, int64_t* count);
+/* The big-triangle list as the traversal tests it (stat "flat_triangles" entries, in packed order): packets = 12 floats each,
+ * {r1, r2, r3, N} -- the packed triangle with its corners possibly rotated cyclically, never anything else; bit i of *pair_mask
+ * = entries i and i + 1 are the halves of one wall (same N words, same r1 words) and are tested in one evaluation. */
+int pt_debug_flat_list(const pt_context* ctx, float* packets, uint32_t* pair_mask);
 /* Closest hit of n caller-supplied rays through the device traversal (kd_intersect, prog.cl:144-184):
  * out_t[i] = t (-1 on a miss), out_tri[i] = add-order index of the triangle hit (-1 on a miss). */
 int pt_debug_closest_hit(pt_context* ctx, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri);

@@ -57,7 +57,7 @@ EXPORTS = [
     "pt_render_aovs", "pt_read_aovs", "pt_aov_defaults", "pt_render_aovs_ex", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
-    "pt_set_option", "pt_get_stat", "pt_debug_bvh_sizes", "pt_debug_bvh_copy", "pt_debug_wide_nodes", "pt_debug_encounter_rank", "pt_debug_tile_cost", "pt_debug_adaptive_list", "pt_debug_launch_plan",
+    "pt_set_option", "pt_get_stat", "pt_debug_bvh_sizes", "pt_debug_bvh_copy", "pt_debug_wide_nodes", "pt_debug_flat_list", "pt_debug_encounter_rank", "pt_debug_tile_cost", "pt_debug_adaptive_list", "pt_debug_launch_plan",
     "pt_debug_scene_sizes", "pt_debug_scene_copy", "pt_debug_closest_hit", "pt_debug_math", "pt_debug_spec",
     "pt_slab_pixel_count", "pt_frame_size", "pt_comm_available", "pt_comm_unique_id", "pt_comm_init", "pt_gather_frame", "pt_device_frame", "pt_read_frame",
     "pt_write_pfm", "pt_write_ppm", "pt_image_write_pfm", "pt_image_write_ppm", "pt_debug_gather_index", "pt_debug_deinterleave",
@@ -179,6 +179,7 @@ def _load():
     sig("pt_debug_bvh_sizes", C.c_int, vp, C.POINTER(i64), C.POINTER(i64))
     sig("pt_debug_bvh_copy", C.c_int, vp, vp, vp, vp, vp)
     sig("pt_debug_wide_nodes", C.c_int, vp, vp, i64, C.POINTER(i64))
+    sig("pt_debug_flat_list", C.c_int, vp, vp, C.POINTER(C.c_uint32))
     sig("pt_debug_encounter_rank", C.c_int, vp, vp, i64)
     sig("pt_debug_tile_cost", C.c_int, vp, vp, i64)
     sig("pt_debug_adaptive_list", C.c_int, vp, vp, i64, C.POINTER(i64))
@@ -1070,6 +1071,15 @@ class Scene:
         orig = np.zeros(nt.value, dtype=np.int32)
         self._ck(LIB.pt_debug_bvh_copy(self._h, _ptr(nodes), _ptr(tris), _ptr(meta), _ptr(orig)))
         return nodes, tris, meta, orig
+
+    def debug_flat_list(self):
+        """The big-triangle list as the traversal tests it: (packets (n, 12) float32, pair mask) -- bit i of the mask: entries i
+        and i + 1 are tested as one pair."""
+        n = int(self.stat("flat_triangles"))
+        pk = np.zeros((n, 12), dtype=np.float32)
+        m = C.c_uint32()
+        self._ck(LIB.pt_debug_flat_list(self._h, _ptr(pk), C.byref(m)))
+        return pk, m.value
 
     def debug_wide_nodes(self):
         """The 4-wide quantised nodes (pt_wide.cpp) as a structured array; empty when they were not built."""

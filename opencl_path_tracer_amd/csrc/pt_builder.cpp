@@ -701,6 +701,92 @@ int build_and_pack(pt_context* ctx) {
     return PT_OK;
 }
 
+// Coplanar pairs of the big-triangle list: the two halves of a wall meet the ray in the same plane, so
+// the plane part of their exact tests -- num = dot3(r1 - P, N), den = dot3(D, N), the quotient t and the point pt -- is computed
+// from the same bits twice.  Trav::flat_pass (kNodesLds) tests a marked pair once: fpair_mask bit i = listed triangles i and
+// i + 1 are a pair, i its head.  A pair is two NEIGHBOURS of the list (packed order, ranks and meta stay what they are) that
+//   - share a box group (group_flat_boxes),
+//   - carry bit-identical N words in the test copy (compared as words, never with ==),
+//   - share a corner, bit for bit, that each of them can have as r1.
+// The packets themselves are never touched: the oracle takes t from the AUTHORED r1, and light sampling, uv and vertex-normal
+// interpolation read the packet's corners in authored order.  What may differ is the list's TEST copy, which only flat_pass
+// reads (staged in LDS by setup_traversal): there a triangle's corners can be rotated cyclically (fpair_rot, two bits each),
+// which keeps the three edge functions as a set -- each is f(from, to) = dot3(cross3(to - from, pt - from), N) -- and so the
+// accepted set.  num, however, is taken from r1, and for a general plane another corner rounds differently.  So a triangle is
+// rotated only where num cannot tell the corners apart: N has two components that are exactly +-0 and the three corners have
+// the same WORD on the remaining axis.  Then dot3 adds two products that are exactly +-0 (the coordinates are finite) to
+// (r.k - P.k) * N.k, the same for every corner -- at most the sign of a num that is zero differs, and t = +-0 is rejected
+// either way.  Every authored axis-aligned wall qualifies; a tilted quad pairs only if its halves already start at the
+// same corner.
+// The same triangles are the ones whose halves get N words that differ although the plane is one: cross products of
+// different edges leave +0 in one half and -0 in the other ((0, -1, 0) and (0, -1, -0) for the Cornell box's lamp; five of
+// its six walls).  With two zero components and corners that agree on the third axis, the sign of a zero component reaches
+// no result either: in num, den and each edge function it only decides the sign of a sum that is exactly zero, and a zero
+// num or den is rejected whatever its sign (t is +-0, +-inf or NaN; with t = +inf the point is not finite and no edge
+// function is >= 0), while an edge function that is +-0 passes >= 0 whatever its sign.  So for such a pair the test copy
+// carries the zero components of N as +0 (fpair_canon), and only then are the N words compared.  One ulp in a non-zero
+// component, or a zero sign on a plane that is not axis-aligned, leaves the two unpaired.
+static bool corner_free(const float* v) {           // v: r1 r2 r3 N of a packet; true: num is the same for every corner
+    uint32_t nw[3], cw[3][3];
+    std::memcpy(nw, v + 9, sizeof nw);
+    for (int c = 0; c < 3; ++c) std::memcpy(cw[c], v + 3 * c, sizeof cw[c]);
+    int axis = -1, zeros = 0;
+    for (int a = 0; a < 3; ++a) {
+        if ((nw[a] & 0x7fffffffu) == 0) ++zeros;
+        else axis = a;
+    }
+    if (zeros != 2 || !std::isfinite(v[9 + axis])) return false;
+    for (int c = 0; c < 3; ++c)
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(v[3 * c + a])) return false;
+    return cw[0][axis] == cw[1][axis] && cw[1][axis] == cw[2][axis];
+}
+void plan_flat_pairs(pt_context* ctx) {
+    ctx->fpair_mask = 0;
+    ctx->fpair_rot = 0;
+    ctx->fpair_canon = 0;
+    for (int i = 0; i + 1 < ctx->n_flat; ++i) {
+        int gi = -1, gj = -1;
+        for (int b = 0; b < ctx->n_fbox; ++b) {
+            if (ctx->fbox_mask[b] >> i & 1u) gi = b;
+            if (ctx->fbox_mask[b] >> (i + 1) & 1u) gj = b;
+        }
+        const float* A = ctx->packets[(size_t)i].v;
+        const float* B = ctx->packets[(size_t)i + 1].v;
+        if (gi < 0 || gi != gj) continue;
+        const bool fa = corner_free(A), fb = corner_free(B);
+        uint32_t na[3], nb[3];
+        std::memcpy(na, A + 9, sizeof na);
+        std::memcpy(nb, B + 9, sizeof nb);
+        bool canon = false;
+        if (fa && fb)
+            for (int a = 0; a < 3; ++a) {
+                if (na[a] == 0x80000000u) { na[a] = 0; canon = true; }
+                if (nb[a] == 0x80000000u) { nb[a] = 0; canon = true; }
+            }
+        if (std::memcmp(na, nb, sizeof na) != 0) continue;
+        // the first shared corner, in A's order and then B's, that both can start at (rotation 0 needs no licence)
+        int ra = -1, rb = -1;
+        for (int ca = 0; ca < 3 && ra < 0; ++ca)
+            for (int cb = 0; cb < 3 && ra < 0; ++cb)
+                if ((ca == 0 || fa) && (cb == 0 || fb) && std::memcmp(A + 3 * ca, B + 3 * cb, 12) == 0) { ra = ca; rb = cb; }
+        if (ra < 0) continue;
+        ctx->fpair_mask |= 1u << i;
+        if (canon) ctx->fpair_canon |= 3u << i;
+        ctx->fpair_rot |= (uint64_t)ra << (2 * i) | (uint64_t)rb << (2 * (i + 1));
+        ++i;                                          // a triangle belongs to one pair at most
+    }
+}
+// packet k of the list as flat_pass tests it: corner (c + rot) % 3 of the packet is corner c; -0 in N is +0 under fpair_canon
+void flat_test_packet(const pt_context* ctx, int k, float out[12]) {
+    const float* v = ctx->packets[(size_t)k].v;
+    const int rot = (int)(ctx->fpair_rot >> (2 * k) & 3u);
+    for (int j = 0; j < 12; ++j) out[j] = v[j < 9 ? (j + 3 * rot) % 9 : j];
+    if (ctx->fpair_canon >> k & 1u)
+        for (int j = 9; j < 12; ++j)
+            if (out[j] == 0.0f) out[j] = 0.0f;
+}
+
 // bounding boxes of the complex objects (more than 16 triangles), for the wavefront cost classes
 // boxes of the objects with more than 16 triangles (the wavefront variant's ray cost classes); `boxes` = the padded bounds of
 // every add-order triangle if the caller has them already

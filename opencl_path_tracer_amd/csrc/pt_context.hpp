@@ -72,6 +72,9 @@ struct pt_context {
     int n_fbox = 0;             // its distinct bounding boxes: representative packet and the listed triangles each one covers
     uint8_t fbox_rep[32] = {};
     uint32_t fbox_mask[32] = {};
+    uint32_t fpair_mask = 0;    // bit i: listed triangles i and i + 1 are the halves of one wall, tested once (plan_flat_pairs)
+    uint32_t fpair_canon = 0;   // bit i: the zero components of listed triangle i's N are +0 in the test copy
+    uint64_t fpair_rot = 0;     // two bits per listed triangle: cyclic rotation of its corners in the list's TEST copy (0: as authored)
 
     // ---- device buffers
     float4* d_nodes = nullptr;
@@ -404,6 +407,8 @@ void parallel_for(size_t n, size_t grain, int threads, F fn) {
 // ---- pt_builder.cpp
 int deepest_interior_node(const std::vector<Node64>& nodes);
 int reindex_treelet(std::vector<Node64>& nodes, int interior_depth, int want);
+void plan_flat_pairs(pt_context* ctx);
+void flat_test_packet(const pt_context* ctx, int k, float out[12]);
 
 // ---- pt_launch.cpp
 int32_t count_local_rows(int32_t H, int32_t rank, int32_t world, int32_t rb);

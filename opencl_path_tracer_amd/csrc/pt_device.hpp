@@ -375,6 +375,8 @@ struct SceneView {
     int n_fbox;                // their distinct padded boxes (the halves of a wall share one) ...
     const char* lds_fbox;      // ... 48 B each: per axis {lo, hi, hi, lo} (planes picked by address, like a staged node)
     const unsigned* lds_fmask; // ... and which listed triangles each one covers
+    unsigned fpair;            // bit i: listed triangles i and i + 1 are a coplanar pair with the same N and r1 words in lds_flat, i its
+                               // head (pt_builder.cpp plan_flat_pairs); wave-uniform, read by kNodesLds only
     // kNodesWide: the lane's stack continues in global memory past its LDS entries (a 4-wide traversal can have three
     // children pending per level, far more than it usually has; LDS holds what keeps six waves per SIMD resident)
     // (all three wave-uniform, i.e. scalar registers: which entry an address is, and whose, is read off the address
@@ -443,6 +445,53 @@ PT_DEV float tri_test(const float4 a, const float4 b, const float4 c, f3 P, f3 V
         res = ok ? t : -1.0f;
     }
     return res;
+}
+
+// tri_test<QUOT> on the two halves of a wall at once: packets pk[0..2] (A) and pk[3..5] (B) whose N words and r1 words are the
+// same (the host's pairing, plan_flat_pairs).  Everything tri_test derives from r1, N and the ray -- num, den, the early-out,
+// the reciprocal, the quotient t and the point pt -- is the same IEEE operations on the same bits for both, so it is evaluated
+// once; only the edge functions differ, each written exactly as in tri_test.  *tA / *tB: what tri_test returns for A / B when
+// both are called with this `limit`.  (Called one after the other, B would see the limit A's hit leaves behind: a smaller one,
+// which can only turn a B that no longer wins or ties into an early -1 -- the caller's keep-closest logic ignores it either way.)
+// B's words are read after A's edge functions, so that the two triangles' corners need not be live together.
+template <bool QUOT>
+PT_DEV void tri_test_pair(const float4* pk, f3 P, f3 Vd, float limit, WorkCount* wc, float* tA, float* tB) {
+    const float4 a = pk[0], b = pk[1], c = pk[2];
+    const f3 r1 = mk(a.x, a.y, a.z), r2 = mk(a.w, b.x, b.y), r3 = mk(b.z, b.w, c.x), N = mk(c.y, c.z, c.w);
+    const float num = dot3(r1 - P, N), den = dot3(Vd, N);
+    float resA = -1.0f, resB = -1.0f;
+    bool cand;
+    if (QUOT) {
+        const float q = num * __builtin_amdgcn_rcpf(den);
+        cand = !(q < 0.0f) && !(q > limit);
+    } else {
+        const bool same_sign = (num > 0.0f && den > 0.0f) || (num < 0.0f && den < 0.0f);
+        cand = same_sign && num * __builtin_amdgcn_rcpf(den) <= limit;
+    }
+    if (cand) {
+        if (wc) { count_low(wc, 2); if (first_active_lane()) wc->low[5]++; }
+        const float r0 = __builtin_amdgcn_rcpf(den);
+        const float t = wave_all(div_window(den, r0, num * r0)) ? div_core(num, den, r0) : num / den;
+        const f3 pt = madd(Vd, t, P);
+        const bool front = !(t < 0.0f) && (t > 0.0f);
+        {
+            const float c1 = dot3(cross3(r2 - r1, pt - r1), N);
+            const float c2 = dot3(cross3(r3 - r2, pt - r2), N);
+            const float c3 = dot3(cross3(r1 - r3, pt - r3), N);
+            resA = (front && (c1 >= 0.0f) && (c2 >= 0.0f) && (c3 >= 0.0f)) ? t : -1.0f;
+        }
+        {
+            const float w = pk[3].w, x = pk[5].x;
+            const float4 e = pk[4];
+            const f3 s2 = mk(w, e.x, e.y), s3 = mk(e.z, e.w, x);
+            const float c1 = dot3(cross3(s2 - r1, pt - r1), N);
+            const float c2 = dot3(cross3(s3 - s2, pt - s2), N);
+            const float c3 = dot3(cross3(r1 - s3, pt - s3), N);
+            resB = (front && (c1 >= 0.0f) && (c2 >= 0.0f) && (c3 >= 0.0f)) ? t : -1.0f;
+        }
+    }
+    *tA = resA;
+    *tB = resB;
 }
 
 // Per-lane traversal stack in LDS, laid out [entry][lane] (consecutive lanes -> consecutive
@@ -869,11 +918,24 @@ struct Trav {
     PT_DEV void tri_update(const SceneView& sv, const float4 a, const float4 b, const float4 c, int ti, WorkCount* wc) {
         if (COUNT) { wc->tris++; if (first_active_lane()) wc->wtris++; count_low(wc, 1); }
         const float t = tri_test<MODE == kNodesLds>(a, b, c, P, D, best_t * 1.000002f, COUNT ? wc : nullptr);
+        keep_closest(sv, t, ti);
+    }
+    PT_DEV void keep_closest(const SceneView& sv, float t, int ti) {
         if (t > 0.0f) {
             bool better = t < best_t;
             if (t == best_t && best >= 0) better = sv.meta[ti].rank < sv.meta[best].rank;
             if (better) { best_t = t; best = ti; }
         }
+    }
+    // the pair of listed triangles ti, ti + 1 (packets pk[0..5] of the LDS copy): one evaluation, then A and B in list order --
+    // the order in which tri_update meets them one by one, so a tie between the halves (a hit on the diagonal) goes the same way
+    template <bool COUNT>
+    PT_DEV void pair_update(const SceneView& sv, const float4* pk, int ti, WorkCount* wc) {
+        if (COUNT) { wc->tris += 2; if (first_active_lane()) wc->wtris++; count_low(wc, 1); }
+        float tA, tB;
+        tri_test_pair<MODE == kNodesLds>(pk, P, D, best_t * 1.000002f, COUNT ? wc : nullptr, &tA, &tB);
+        keep_closest(sv, tA, ti);
+        keep_closest(sv, tB, ti + 1);
     }
 
     // The big-triangle list (the host keeps walls, floors ... out of the tree: pt_builder.cpp build_and_pack), tested
@@ -915,21 +977,30 @@ struct Trav {
 #pragma clang loop unroll(disable)
             while (mask != 0) {
                 const int i = __ffs((int)mask) - 1;
-                mask &= mask - 1;
+                // the head of a pair whose partner is a candidate too (they share the box, so always): the partner's r1 and N are
+                // the head's words, its q the same bits -- one evaluation decides both
+                const unsigned grp = (1u | ((((sv.fpair & (mask >> 1)) >> i) & 1u) << 1)) << i;
+                mask &= ~grp;
                 const float4* pk = sv.lds_flat + i * 3;
                 const float4 a = pk[0], c = pk[2];
                 const f3 N = mk(c.y, c.z, c.w);
                 const float q = dot3(mk(a.x, a.y, a.z) - P, N) * __builtin_amdgcn_rcpf(dot3(D, N));
-                keep |= (!(q < 0.0f) && !(q > limit)) ? (1u << i) : 0u;        // tri_test<true>'s early-out
+                keep |= (!(q < 0.0f) && !(q > limit)) ? grp : 0u;              // tri_test<true>'s early-out
             }
         }
-        //  2. the exact test on what is left
+        //  2. the exact test on what is left: a pair in ONE iteration (half the iterations for a wall, each of which costs the wave
+        //     its full length as long as one lane has a candidate; one divide and one pt for both halves -- tri_test_pair)
 #pragma clang loop unroll(disable)
         while (keep != 0) {
             const int i = __ffs((int)keep) - 1;
-            keep &= keep - 1;
             const float4* pk = sv.lds_flat + i * 3;
-            tri_update<COUNT>(sv, pk[0], pk[1], pk[2], i, wc);
+            if (MODE == kNodesLds && (((sv.fpair & (keep >> 1)) >> i) & 1u) != 0) {
+                keep &= ~(3u << i);
+                pair_update<COUNT>(sv, pk, i, wc);
+            } else {       // a single triangle, or a head whose partner was not kept
+                keep &= keep - 1;
+                tri_update<COUNT>(sv, pk[0], pk[1], pk[2], i, wc);
+            }
         }
     }
 
@@ -1657,8 +1728,20 @@ PT_DEV void setup_traversal(const RenderParams& p, SceneView* sv, LaneStack<type
     sv->ovf = p.stack_ovf ? p.stack_ovf + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * BLOCK : nullptr;
     sv->ovf_stride = (unsigned)p.stack_ovf_lanes;
     float4* lds_flat = reinterpret_cast<float4*>(pt_lds_raw + traversal_nodes_end_dev<MODE, BLOCK>(p));
-    for (int i = threadIdx.x; i < p.n_flat * 3; i += BLOCK) lds_flat[i] = p.tris[i];
+    // (the copy flat_pass tests: corner (c + rot) % 3 of the packet is its corner c, so that the halves of a paired wall start at
+    // the same corner -- fpair_rot, plan_flat_pairs; N stays but for the sign of its zeros, fpair_canon)
+    {
+        const float* src = reinterpret_cast<const float*>(p.tris);
+        float* dst = reinterpret_cast<float*>(lds_flat);
+        for (int i = threadIdx.x; i < p.n_flat * 12; i += BLOCK) {
+            const int t = i / 12, j = i - t * 12;
+            const int rot = MODE == kNodesLds ? (int)(p.fpair_rot >> (2 * t)) & 3 : 0;      // (the other node modes test no pairs)
+            const float v = src[t * 12 + (j < 9 ? (j + 3 * rot) % 9 : j)];
+            dst[i] = (MODE == kNodesLds && j >= 9 && (p.fpair_canon >> t & 1u) != 0 && v == 0.0f) ? 0.0f : v;      // (-0 in N -> +0)
+        }
+    }
     sv->lds_flat = lds_flat;
+    sv->fpair = p.fpair_mask;
     // padded boxes of the listed triangles (what padded_bounds() gives a triangle in a leaf: 1e-5 of the largest
     // coordinate + 1e-6), per axis {lo, hi, hi, lo} so that (entry, exit) is one 8-byte read at + 0 or + 8
     float* lds_fbox = reinterpret_cast<float*>(lds_flat + p.n_flat * 3);

@@ -1720,6 +1720,14 @@ int pt_debug_wide_nodes(const pt_context* ctx, void* out, int64_t capacity, int6
     return PT_OK;
 }
 
+int pt_debug_flat_list(const pt_context* ctx, float* packets, uint32_t* pair_mask) {
+    if (!ctx || !ctx->tris_uploaded) return PT_EINVAL;
+    if (packets)
+        for (int k = 0; k < ctx->n_flat; ++k) flat_test_packet(ctx, k, packets + 12 * k);
+    if (pair_mask) *pair_mask = ctx->fpair_mask;
+    return PT_OK;
+}
+
 int pt_debug_bvh_copy(const pt_context* cctx, float* nodes, float* tris, int32_t* meta, int32_t* orig) {
     if (!cctx || !cctx->tris_uploaded) return PT_EINVAL;
     pt_context* ctx = const_cast<pt_context*>(cctx);            // (the host mirror of a device-built tree is filled on demand)

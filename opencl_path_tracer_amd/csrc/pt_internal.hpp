@@ -147,6 +147,9 @@ struct RenderParams {
     int32_t n_fbox;              // their distinct boxes (the two triangles of a wall share one): box b is that of packet fbox_rep[b]
     uint8_t fbox_rep[32];        // and covers the listed triangles in fbox_mask[b]
     uint32_t fbox_mask[32];
+    uint32_t fpair_mask;         // bit i: listed triangles i and i + 1 share plane words and r1 words in the staged copy: one test (Trav::flat_pass)
+    uint32_t fpair_canon;        // bit i: the staged copy of listed triangle i has +0 where the packet's N has -0
+    uint64_t fpair_rot;          // two bits per listed triangle: the staged copy's corners are the packet's, rotated by that many (setup_traversal)
     int32_t node_mode;           // kNodesLds / kNodesGlobal / kNodesTreelet / kNodesWide: where the traversal reads BVH nodes from (and which)
     int32_t treelet_nodes;       // kNodesTreelet: nodes [0, treelet_nodes) are staged in LDS
     int32_t stack_entries;       // per-lane stack entries in LDS: all a BVH2 traversal can need (sentinel + deepest interior node + the slot

@@ -61,6 +61,7 @@ int plan_node_placement(pt_context* ctx, const float4* d_bvh2, bool* wide_on_dev
     if (wide_on_device) *wide_on_device = false;
     ctx->treelet_nodes = 0;
     group_flat_boxes(ctx);
+    plan_flat_pairs(ctx);
     ctx->interior_depth = deepest_interior_node(ctx->nodes);
     clk.lap("list boxes + interior depth");
     if (ctx->interior_depth + 2 > kStackEntries) return fail(ctx, PT_ESCENE, "internal: BVH deeper than the traversal stack");
@@ -144,6 +145,9 @@ void fill_params(const pt_context* ctx, const pt_camera* cam, RenderParams* p) {
     p->n_fbox = ctx->n_fbox;
     std::memcpy(p->fbox_rep, ctx->fbox_rep, sizeof p->fbox_rep);
     std::memcpy(p->fbox_mask, ctx->fbox_mask, sizeof p->fbox_mask);
+    p->fpair_mask = ctx->fpair_mask;
+    p->fpair_rot = ctx->fpair_rot;
+    p->fpair_canon = ctx->fpair_canon;
     p->stack_entries = stack_entries_for(ctx->interior_depth);
     p->stack_ovf = nullptr;
     p->stack_ovf_lanes = 0;
