@@ -523,6 +523,50 @@ int pt_focus_at(pt_context* ctx, const pt_camera* cam, int32_t x, int32_t y, flo
  * two LCG draws are taken from S), out 6 floats P, D.  The kernel calls the device function the lens instances of k_nee call. */
 int pt_debug_lens(pt_context* ctx, const pt_camera* cam, const pt_lens_params* lens, int64_t n, const int32_t* gid_state, float* out);
 
+/* ---- a rough-dielectric (frosted glass) material for pt_render_nee (new: opt-in with option "frosted") -----------
+ * Option "frosted" = 1 (default 0: every path computes what it computed before, bit for bit, and type 6 stays inert): pt_render_nee (every
+ * strategy, with and without an environment, a lens, smooth_normals, textures, glossy and coated) and pt_render_adaptive_ex with
+ * PT_ADAPT_PATH_NEE shade a hit on a material of type 6 as the vertex below, GGX microfacet reflection and refraction (Walter et al.
+ * 2007); pt_render, pt_generate_rays, pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex with PT_ADAPT_PATH_RENDER return
+ * PT_EINVAL naming the option, checked before the device (PT_ENODEVICE).  With the option on and no material of type 6 among those
+ * uploaded last, the host launches the kernels it launches with the option off: the frame (colors, rnds, rays) is the option-off frame
+ * bit for bit.
+ * Material.  n and F0 are what pt_material_init gives a type-2 material from N and K; alpha = pt_material_roughness(shininess), written
+ * into field shininess of the DEVICE copy of a type-6 material (field n holds the index of refraction; only type 0 reads shininess
+ * otherwise); host records stay as they are.  kd, ks, emission and a texture binding of a type-6 material are ignored; it is no light.
+ * The vertex (float32, the conventions of the rough-metal block above, whose visible-normal sampler, D, G1, p_glossy(h) and fresnel it
+ * reuses).  A type-6 hit is a lobe vertex for these rules: it takes a light sample when k + 1 < iterations; it draws exactly two LCG
+ * values rnd1, rnd2 after its light sample; under smooth_normals it follows the geometric-side rules.  N, the frame (Z, X), local
+ * coordinates and o = local(-D) as for type 4; eta = n, or 1.0f / n when the path is inside (as type 2 does it).
+ *   Half vector: h by the visible-normal sequence of type 4 on (rnd1, rnd2), the bits of a type-4 lane given the same inputs.
+ *   Fresnel: c = dot3(o, h); F = fresnel(F0, h, -o); disc = 1.0f - (fmaf(-c, c, 1.0f) / eta) / eta; Fm = ((F.x + F.y) + F.z) / 3.0f;
+ *     when disc <= 0 (total internal reflection) Fm = 1 and F = (1, 1, 1).
+ *   Lobe choice: u_sel = (pt_nee_rand(~key, k, 1) >> 8) * 2^-24, the key a type-5 vertex uses for its choice (a vertex has one type);
+ *     the vertex reflects iff u_sel < Fm.  Nothing is drawn from the LCG for it.
+ *   Reflection: w = madd(h, 2.0f c, -o); p_b(w) = Fm * p_glossy(h); g(w) = (F G1(w)) * (1.0f / Fm).  The path ends unless w.z > 0 (under
+ *     smooth_normals also unless dot3(w, Ng) > 0).  The new origin is hp + 0.001 Ng.
+ *   Refraction: w = madd(h, c / eta - sqrtf(disc), (-o) / eta) (type 2's direction with h for the normal, componentwise divisions);
+ *     g(w) = ((1 - F) G1((w.x, w.y, -w.z))) * (1.0f / (1.0f - Fm)); no 1 / eta^2 factor, as type 2 has none.  The path ends unless
+ *     w.z < 0 (under smooth_normals also unless dot3(w, Ng) < 0).  `inside` toggles.  The new origin is hp - 0.001 Ng.
+ *   Update: factor_R *= g(w); factor_L, factor_B and factor_S are untouched.  The world direction before normalisation,
+ *   madd(Z, w.y, madd(N, w.z, X * w.x)), goes to the tail every vertex shares.
+ *   Light sample at the vertex (triangle light and sky), reflection side only: for the sample's unit w with w.z > 0 (and, under
+ *   smooth_normals, dot3(w, Ng) > 0), h = normalize(o + w); c, F, disc and Fm as above; p_b = Fm * p_glossy(h), fR' = fR g(w) (fL, fB, fS
+ *   unchanged); rejected unless p_b > 0; evaluated after the shadow ray.  A sample with w.z <= 0 is rejected: light sampling does not
+ *   reach through the surface.
+ *   Weight of the next hit: after a reflected direction W_b of the next emitter hit or sky miss uses the p_b the vertex sampled with (one
+ *   device function states it for the sampler and the light sample); after a refracted direction the next emitter hit or sky miss has
+ *   weight 1 in every strategy, as after a type-1 / type-2 vertex: no light sample produces that direction.
+ *   Preview (iterations == 1): kd + emission, as for an inert type.
+ * Guides: pt_render_aovs_ex with PT_AOV_SHADED and the option on gives a terminal type-6 hit the albedo tint x 1 (as a terminal
+ * dielectric) and the normal Ns; it is not followed as a specular step.  With the option off, and in geometric guides, the buffers are
+ * what they were.  Changing the option makes no guides stale. */
+/* the device functions of the vertex (host-only context: PT_ENODEVICE), one thread per item, item i on lane i % 64.  Per item 12 floats
+ * in: N (unit), D (unit, toward the surface), alpha, F0 (grey), eta, rnd1, rnd2, u_sel; 10 out: the world direction w before
+ * normalisation (3), Fm, 1 if the vertex reflects else 0, p_b as sampled (0 for a refraction), g.x as sampled, p_b and g.x evaluated again
+ * from normalize(w) the way a light sample evaluates them (0, 0 for a refraction), o.z */
+int pt_debug_frosted(pt_context* ctx, int64_t n, const float* in, float* out);
+
 /* ---- per-pixel variance of the mean luminance (new: opt-in with option "moments"; the reference keeps the mean only) -------
  * With option "moments" = 1 every render path (pt_render in every variant, schedule and node mode, pt_trace_rays,
  * pt_render_adaptive, pt_render_nee, tiled ranks) also folds each sample's squared luminance into colors[].w, float32 in this order:

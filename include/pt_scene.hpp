@@ -143,6 +143,9 @@ public:
     // the coated diffuse of material type 5 (set_option("coated", 1); render_nee only): the device functions of the vertex, 12 floats in
     // (N, D, alpha, F0, kd, rnd1, rnd2, u_sel) and 10 out per item (pt_debug_coated)
     void debug_coated(int64_t n, const float* in, float* out) { ck(pt_debug_coated(ctx, n, in, out)); }
+    // the rough dielectric of material type 6 (set_option("frosted", 1); render_nee only): the device functions of the vertex, 12 floats in
+    // (N, D, alpha, F0, eta, rnd1, rnd2, u_sel) and 10 out per item (pt_debug_frosted)
+    void debug_frosted(int64_t n, const float* in, float* out) { ck(pt_debug_frosted(ctx, n, in, out)); }
     // a thin lens for render_nee and the NEE path of render_adaptive (pt_set_lens; aperture = the lens radius, 0: the pinhole; focus_distance
     // along the optical axis).  While aperture > 0 only they render; the guides keep the pinhole view.  focus_at: the axial distance of the
     // first hit under pixel (x, y) of the last render's view, +inf on a miss; debug_lens: the device's lens ray of n items {gid, S}, 6 floats each

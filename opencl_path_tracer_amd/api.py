@@ -49,7 +49,7 @@ EXPORTS = [
     "pt_set_vertex_normals", "pt_clear_vertex_normals", "pt_compute_vertex_normals", "pt_debug_vertex_normals", "pt_debug_shading_normal",
     "pt_texture_defaults", "pt_add_texture", "pt_clear_textures", "pt_set_material_texture", "pt_debug_texture",
     "pt_set_vertex_uvs", "pt_clear_vertex_uvs", "pt_debug_vertex_uvs", "pt_debug_albedo", "pt_image_read_ppm",
-    "pt_material_roughness", "pt_debug_glossy", "pt_debug_coated",
+    "pt_material_roughness", "pt_debug_glossy", "pt_debug_coated", "pt_debug_frosted",
     "pt_lens_defaults", "pt_set_lens", "pt_clear_lens", "pt_focus_at", "pt_debug_lens",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
@@ -132,6 +132,7 @@ def _load():
     sig("pt_material_roughness", f32, f32)
     sig("pt_debug_glossy", C.c_int, vp, i64, vp, vp)
     sig("pt_debug_coated", C.c_int, vp, i64, vp, vp)
+    sig("pt_debug_frosted", C.c_int, vp, i64, vp, vp)
     sig("pt_lens_defaults", None, vp)
     sig("pt_set_lens", C.c_int, vp, vp)
     sig("pt_clear_lens", C.c_int, vp)
@@ -703,6 +704,16 @@ class Scene:
         p = LensParams(float(aperture), float(focus_distance))
         cam = self.camera if camera is None else np.ascontiguousarray(camera, dtype=CAMERA)
         self._ck(LIB.pt_debug_lens(self._h, _ptr(cam), C.byref(p), items.shape[0], _ptr(items), _ptr(out)))
+        return out
+
+    # -- the rough dielectric of material type 6 (option "frosted")
+    def debug_frosted(self, items):
+        """pt_debug_frosted: items (n, 12) float32 {N, D, alpha, F0, eta, rnd1, rnd2, u_sel} -> (n, 10) float32 {w before normalisation
+        (world), Fm, 1 if the vertex reflects else 0, p_b as sampled (0 for a refraction), g.x as sampled, p_b and g.x evaluated again from
+        w the way a light sample does (0, 0 for a refraction), o.z}, by the device functions the frosted k_nee instances call."""
+        items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 12)
+        out = np.empty((items.shape[0], 10), dtype=np.float32)
+        self._ck(LIB.pt_debug_frosted(self._h, items.shape[0], _ptr(items), _ptr(out)))
         return out
 
     def upload_Triangles(self):

@@ -221,6 +221,10 @@ struct pt_context {
     // instances run only when the option is on AND the materials uploaded last hold a type-5 one; every other frame is today's launch
     int coated = 0;
     bool coated_mats = false;          // pt_upload_materials saw a material of type 5
+    // rough dielectric (option frosted; pinned in include/pt_api.h): material type 6 is a reflecting / refracting lobe vertex in
+    // pt_render_nee.  The frosted k_nee instances run only when the option is on AND the materials uploaded last hold a type-6 one
+    int frosted = 0;
+    bool frosted_mats = false;         // pt_upload_materials saw a material of type 6
     // thin lens (pt_set_lens; pinned in include/pt_api.h): pt_render_nee and the NEE path of pt_render_adaptive_ex start their paths on the
     // lens ray while lens_set && lens_aperture > 0 (the lens instances of k_nee); every other frame is today's launch
     bool lens_set = false;

@@ -19,6 +19,7 @@ struct AovShade {
     TexView tv;                    // tv.uv == nullptr: option textures is off
     int glossy;                    // option glossy: a terminal type-4 hit is a metal (albedo tint x F0)
     int coated;                    // option coated: a terminal type-5 hit is a plastic (albedo tint x kd')
+    int frosted;                   // option frosted: a terminal type-6 hit is a rough dielectric (albedo tint x 1)
 };
 PT_DEV const AovShade& only(const AovShade& s) { return s; }
 
@@ -98,7 +99,7 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
                                 if (ti < 0) break;          // escaped: albedo 0, normal 0
                                 continue;
                             }
-                            const f3 a = type == 1 || (type == 4 && sh.glossy) ? ldf3(m->F0) : type == 2 ? mk(1.f, 1.f, 1.f) : plastic ? kd : kd + ldf3(m->emission);
+                            const f3 a = type == 1 || (type == 4 && sh.glossy) ? ldf3(m->F0) : type == 2 || (type == 6 && sh.frosted) ? mk(1.f, 1.f, 1.f) : plastic ? kd : kd + ldf3(m->emission);
                             alb = tint * a;
                             nrm = Ns;
                             mat = (float)mi;
@@ -153,9 +154,9 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
 }
 
 hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
-                              const float4* vn, const TexView& tv, int glossy, int coated, int cu_count, hipStream_t stream) {
+                              const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream) {
     return launch_lanes([](auto s) { return k_aovs<s.mode, s.block, AovShade>; }, p, npix, cu_count, stream, subpixels, specular_depth,
-                        (long long)npix, albedo_rgbm, normal_depth, AovShade{vn, tv, glossy, coated});
+                        (long long)npix, albedo_rgbm, normal_depth, AovShade{vn, tv, glossy, coated, frosted});
 }
 
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,

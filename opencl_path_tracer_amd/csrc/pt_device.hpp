@@ -1346,6 +1346,124 @@ PT_DEV f3 lobe_direction_coated(f3 N, f3 D, bool gl, bool ct, float alpha, f3 F0
     return d;
 }
 
+// ---- rough dielectric, material type 6 under option frosted (GGX reflection and refraction through one visible-normal half vector;
+// include/pt_api.h pins every operation).  Local vectors as above; D, G1, glossy_pdf, glossy_sample and fresnel are the rough metal's.
+// the Fresnel terms at half vector h: c = o.h, F (Schlick), type 2's discriminant and the mean Fm; total internal reflection makes F and Fm 1
+struct FrostedTerms {
+    f3 F;
+    float Fm, c, disc;
+};
+PT_DEV FrostedTerms frosted_terms(f3 F0, float eta, f3 o, f3 h) {
+    FrostedTerms t;
+    t.c = dot3(o, h);
+    t.F = fresnel(F0, h, -o);
+    t.disc = 1.0f - (fmaf_(-t.c, t.c, 1.0f) / eta) / eta;
+    t.Fm = ((t.F.x + t.F.y) + t.F.z) / 3.0f;
+    if (t.disc <= 0.0f) {
+        t.Fm = 1.0f;
+        t.F = mk(1.0f, 1.0f, 1.0f);
+    }
+    return t;
+}
+// p_b and the weight g(w) of the local direction w whose half vector with o is h -- the ONE statement of both: the sampler (either lobe),
+// the light sample and W_b go through it.  refl: w is the reflected direction (p_b = Fm p_glossy(h), g = F G1(w) / Fm); else the refracted
+// one, which no light sample reaches (p_b reads 0, g = (1 - F) G1 of w mirrored to the upper side / (1 - Fm))
+PT_DEV float frosted_pdf_weight(float alpha, const FrostedTerms& t, bool refl, f3 o, f3 h, f3 w, f3* g) {
+    const f3 Fs = refl ? t.F : mk(1.0f - t.F.x, 1.0f - t.F.y, 1.0f - t.F.z);
+    const float den = refl ? t.Fm : 1.0f - t.Fm;
+    *g = (Fs * glossy_G1(alpha, mk(w.x, w.y, refl ? w.z : -w.z))) * (1.0f / den);
+    return refl ? t.Fm * glossy_pdf(alpha, o, h) : 0.0f;
+}
+// the same for a given unit direction w above the surface (the light sample's): h = normalize(o + w) and the terms from scratch
+PT_DEV float frosted_pdf_weight_of(float alpha, f3 F0, float eta, f3 o, f3 w, f3* g) {
+    const f3 h = normalize3(o + w);
+    return frosted_pdf_weight(alpha, frosted_terms(F0, eta, o, h), true, o, h, w, g);
+}
+// what the sampled frosted vertex leaves behind
+struct FrostedOut {
+    f3 g;            // g(w)
+    float pb;        // p_b as sampled (0 for a refraction)
+    float wz;        // w.z: the path ends unless it is > 0 (reflection) or < 0 (refraction)
+    float Fm;        // (pt_debug_frosted)
+    float oz;
+    bool refl;       // the vertex reflects
+};
+// lobe_direction_coated with the frosted vertex as a fourth kind of lane (fr; u_sel chooses its lobe against Fm): it shares the metal's
+// visible-normal draw, and a refracting lane only replaces the reflected direction by type 2's refracted one around h.  The Fresnel
+// terms, G1 and the weight are one sequence for both of its lobes.  Every other lane gets lobe_direction_coated's bits.
+template <bool SK>
+PT_DEV f3 lobe_direction_frosted(f3 N, f3 D, bool gl, bool ct, bool fr, float alpha, f3 F0, f3 kd, float eta, float u_sel, float rnd1, float rnd2,
+                                 GlossyOut* out, CoatedOut* co, FrostedOut* fo) {
+    bool yaxis;
+    const float l2 = frame_l2(N, &yaxis);
+    float rl, r;
+    if (wave_all(rsqrt_window(l2) && rnd1 >= kSqrtWindowLo && rnd1 < 1.0f)) {
+        rl = rsqrt_core(l2);
+        r = sqrt_core(rnd1);
+    } else {
+        rl = 1.0f / __builtin_sqrtf(l2);
+        r = __builtin_sqrtf(rnd1);
+    }
+    f3 Z, X;
+    frame_from_rl(N, yaxis, rl, &Z, &X);
+    const float theta = (float)(6.283185307179586 * (double)rnd2);
+    float sn, cs;
+    spec_sincos<SK>(theta, &sn, &cs);
+    float x = r * cs, y = r * sn, z = 0.0f;
+    f3 o = mk(0.f, 0.f, 1.f), h = o;
+    float ps = 0.0f;
+    bool vis = gl || fr;       // the lane samples visible normals: a metal, a frosted vertex, or the coat lobe of a coated vertex
+    if (gl || ct || fr) o = to_local(-D, X, Z, N);
+    if (ct) {
+        ps = coated_ps(F0, kd, o);
+        vis = u_sel < ps;
+    }
+    if (vis) {
+        const f3 w = glossy_sample(alpha, o, x, y, &h);
+        x = w.x;
+        y = w.y;
+        z = w.z;
+    } else {
+        z = sqrt_rn(1.0f - rnd1);
+    }
+    if (gl) {
+        const f3 w = mk(x, y, z);
+        out->pb = glossy_pdf(alpha, o, h);
+        out->g1w = glossy_G1(alpha, w);
+        out->F = fresnel(F0, h, -o);
+        out->wz = z;
+        out->oz = o.z;
+    }
+    if (ct) {
+        const f3 w = mk(x, y, z);
+        if (!vis) h = normalize3(o + w);
+        co->pb = coated_pdf_weight(alpha, F0, kd, ps, o, h, w, &co->g);
+        co->wz = z;
+        co->ps = ps;
+        co->oz = o.z;
+        co->coat = vis;
+    }
+    if (fr) {
+        const FrostedTerms t = frosted_terms(F0, eta, o, h);
+        const bool refl = u_sel < t.Fm;
+        if (!refl) {           // type 2's refracted direction with h for the normal (the ray direction in the frame is -o)
+            const f3 w = madd(h, t.c / eta - sqrt_rn(t.disc), mk(-o.x / eta, -o.y / eta, -o.z / eta));
+            x = w.x;
+            y = w.y;
+            z = w.z;
+        }
+        fo->pb = frosted_pdf_weight(alpha, t, refl, o, h, mk(x, y, z), &fo->g);
+        fo->wz = z;
+        fo->Fm = t.Fm;
+        fo->oz = o.z;
+        fo->refl = refl;
+    }
+    f3 d = X * x;
+    d = madd(N, z, d);
+    d = madd(Z, y, d);
+    return d;
+}
+
 // ---------------------------------------------------------------------------- path state + shading
 // The path state of prog.cl:307-316: ray (P, D), LCG state and inside-glass flag are plain local variables of the
 // caller; the four factors and the colour travel as one PathRegs.  (Round 3 also tried them in global memory behind the
@@ -1387,6 +1505,9 @@ struct PathRegs {
 // A hook with `coated` set (it has `glossy` too) makes material type 5 a lobe vertex, the coated diffuse of option coated (pinned in
 // include/pt_api.h): lobe_direction_coated() above, the mixture's p_b kept in the hook; whether type 4 is live there is the hook's
 // run-time answer (option glossy).  Every statement that does so sits under `if constexpr (HOOK::coated)`.
+// A hook with `frosted` set (it has `lens` too) makes material type 6 a lobe vertex, the rough dielectric of option frosted (pinned in
+// include/pt_api.h): lobe_direction_frosted() above; a refracted direction leaves through the surface, so the vertex may toggle `inside`
+// and step off along -Ng.  Every statement that does so sits under `if constexpr (HOOK::frosted)`.
 struct NoShadeHook {
     static constexpr bool active = false;
     static constexpr bool smooth = false;
@@ -1394,6 +1515,7 @@ struct NoShadeHook {
     static constexpr bool glossy = false;
     static constexpr bool coated = false;
     static constexpr bool lens = false;
+    static constexpr bool frosted = false;
 };
 
 // The interpolated shading normal of a hit at hp = madd(D, t, P) on packed triangle ti (include/pt_api.h pins every operation): vn =
@@ -1561,6 +1683,12 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         if constexpr (HOOK::lens) ct = ct && hook->coat_live();             // (the lens instances serve option coated = 0 too)
         lobe = lobe || ct;
     }
+    bool fr = false;                                                        // a rough-dielectric vertex (type 6 under option frosted)
+    if constexpr (HOOK::frosted) {
+        static_assert(HOOK::lens, "the frosted instances are built on the lens ones");
+        fr = type == 6;
+        lobe = lobe || fr;
+    }
     f3 dnew = rD;
     float side = 0.001f;
     float inten = 0.0f;
@@ -1571,11 +1699,13 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         inten = max0(dot3(-rD, N));
         if constexpr (HOOK::active) {
             if (type == 3) wb = hook->emitter_weight(ti, t, inten, rD);
-            if constexpr (HOOK::glossy) hook->light_sample(st, p, m, type, N, hp, rD);
+            if constexpr (HOOK::frosted) hook->light_sample(st, p, m, type, N, hp, rD, inside);
+            else if constexpr (HOOK::glossy) hook->light_sample(st, p, m, type, N, hp, rD);
             else hook->light_sample(st, p, m, type, N, hp);                 // before the LCG draws and this hit's emission
         }
         const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
-        if constexpr (HOOK::coated) dnew = hook->template lobe_vertex_coated<SK>(st, m, gl, ct, N, rD, rnd1, rnd2);
+        if constexpr (HOOK::frosted) dnew = hook->template lobe_vertex_frosted<SK>(st, m, gl, ct, fr, N, rD, rnd1, rnd2, inside, &side);
+        else if constexpr (HOOK::coated) dnew = hook->template lobe_vertex_coated<SK>(st, m, gl, ct, N, rD, rnd1, rnd2);
         else if constexpr (HOOK::glossy) dnew = hook->template lobe_vertex<SK>(st, m, gl, N, rD, rnd1, rnd2);
         else if constexpr (REC) dnew = diffuse_direction_rec<SK>(N, rec + (flip ? 4 : 2), rnd1, rnd2);
         else dnew = diffuse_direction<SK>(N, rnd1, rnd2);
@@ -1616,7 +1746,9 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         }
     }
     if (lobe || spec) {
-        if constexpr (HOOK::smooth) hook->leaves_surface(lobe, dnew);           // a lobe direction below the geometric surface ends the path
+        // a lobe direction below the geometric surface ends the path (frosted: a refracted one, side < 0, that is not below it)
+        if constexpr (HOOK::frosted) hook->leaves_surface_frosted(lobe, side < 0.0f, dnew);
+        else if constexpr (HOOK::smooth) hook->leaves_surface(lobe, dnew);
         rD = normalize3(dnew);
         if constexpr (HOOK::smooth) rP = madd(hook->geo(N), side, hp);
         else rP = madd(N, side, hp);
@@ -1647,7 +1779,9 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         else st.setC(madd(e, inten, st.C()));
     }
     // any other type: the ray is left unchanged and the loop hits the same surface again
-    if constexpr (HOOK::coated) hook->end_vertex_glossy(lobe, gl || ct, N, rD);
+    // (frosted: after a refracted direction the next emitter hit or sky miss has weight 1, as after a specular vertex)
+    if constexpr (HOOK::frosted) hook->end_vertex_glossy(lobe && !(fr && side < 0.0f), gl || ct || fr, N, rD);
+    else if constexpr (HOOK::coated) hook->end_vertex_glossy(lobe, gl || ct, N, rD);
     else if constexpr (HOOK::glossy) hook->end_vertex_glossy(lobe, gl, N, rD);
     else if constexpr (HOOK::active) hook->end_vertex(lobe, N);
 }

@@ -307,9 +307,11 @@ int pt_upload_materials(pt_context* ctx) {
         if (t.mati >= ctx->mats.size()) return fail(ctx, PT_EINVAL, "a triangle references a material index that was never added");
     ctx->glossy_mats = false;
     ctx->coated_mats = false;
+    ctx->frosted_mats = false;
     for (const pt_material& m : ctx->mats) {
         ctx->glossy_mats = ctx->glossy_mats || m.type == 4;
         ctx->coated_mats = ctx->coated_mats || m.type == 5;
+        ctx->frosted_mats = ctx->frosted_mats || m.type == 6;
     }
     if (ctx->has_device) {
         PT_HIP(ctx, hipSetDevice(ctx->device));
@@ -320,6 +322,9 @@ int pt_upload_materials(pt_context* ctx) {
         for (pt_material& m : dm) {
             m._pad = (m.ks.s[0] == 0.0f && m.ks.s[1] == 0.0f && m.ks.s[2] == 0.0f && std::isfinite(m.shininess) && m.shininess >= 0.0f) ? 1 : 0;
             if (m.type == 4 || m.type == 5) m.n = pt_material_roughness(m.shininess);
+            // a type-6 material keeps its index of refraction in n and carries its roughness in shininess, which only type 0 reads
+            // otherwise (option frosted)
+            if (m.type == 6) m.shininess = pt_material_roughness(m.shininess);
         }
         ctx->shaderec_dirty = true;
         int rc = upload_vec(ctx, &ctx->d_mats, dm.data(), sizeof(pt_material) * dm.size());
@@ -541,7 +546,7 @@ int pt_render_aovs_ex(pt_context* ctx, const pt_camera* cam, const pt_aov_params
     if (!ctx->d_aov) PT_HIP(ctx, hipMalloc((void**)&ctx->d_aov, 2 * sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
-    PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->glossy, ctx->coated, ctx->cu_count,
+    PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->glossy, ctx->coated, ctx->frosted, ctx->cu_count,
                                    ctx->stream));
     if (!ctx->aov_valid) ctx->temporal_history = false;      // (as pt_render_aovs: the first guides after stale ones)
     ctx->aov_valid = true;
@@ -932,10 +937,11 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     note_frame(ctx, p.first_sample, cam);
     EventPair* ep;
     if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-    const bool lens = lens_on(ctx);        // a lens: the lens instances, whatever the options say
-    const LensView lv = lens_view(*cam, ctx->lens_aperture, ctx->lens_focus);
+    const bool frosted = ctx->frosted && ctx->frosted_mats;      // option frosted without a type-6 material: today's instances
+    const bool lens = lens_on(ctx) || frosted;      // a lens: the lens instances, whatever the options say (so the frosted ones, built on them)
+    const LensView lv = lens_view(*cam, lens_on(ctx) ? ctx->lens_aperture : 0.0f, ctx->lens_focus);
     PT_HIP(ctx, launch_nee(p, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, false, vn, tv.uv || glossy || coated || lens ? &tv : nullptr,
-                           lens ? ctx->glossy != 0 : glossy, lens ? ctx->coated != 0 : coated, lens ? &lv : nullptr));
+                           lens ? ctx->glossy != 0 : glossy, lens ? ctx->coated != 0 : coated, lens ? &lv : nullptr, frosted));
     if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
     ctx->current_sample += nsamples;
     return PT_OK;
@@ -1164,6 +1170,25 @@ int pt_debug_coated(pt_context* ctx, int64_t n, const float* in, float* out) {
     PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 10 * (size_t)n));
     PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(float) * 12 * (size_t)n, hipMemcpyHostToDevice));
     PT_HIP(ctx, launch_debug_coated((const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// ---- rough dielectric (option frosted; kernels: pt_glossy.hip, pt_nee.hip; pinned in include/pt_api.h)
+int pt_debug_frosted(pt_context* ctx, int64_t n, const float* in, float* out) {
+    PT_NEED_DEVICE(ctx);
+    if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, PT_EINVAL, "pt_debug_frosted: n >= 0, both arrays non-null");
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) (void)hipFree(p); }
+    } d_in, d_out;
+    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * 12 * (size_t)n));
+    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 10 * (size_t)n));
+    PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(float) * 12 * (size_t)n, hipMemcpyHostToDevice));
+    PT_HIP(ctx, launch_debug_frosted((const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost));
     return PT_OK;
@@ -1566,6 +1591,9 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value) {
     } else if (k == "coated") {
         if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "coated must be 0 (material type 5 is inert) or 1 (pt_render_nee shades it as a diffuse base under a rough dielectric coat)");
         ctx->coated = (int)value;
+    } else if (k == "frosted") {
+        if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "frosted must be 0 (material type 6 is inert) or 1 (pt_render_nee shades it as a rough dielectric)");
+        ctx->frosted = (int)value;
     } else if (k == "timing") {
         ctx->timing = value ? 1 : 0;
     } else if (k == "count_work") {

@@ -443,9 +443,10 @@ inline LensView lens_view(const pt_camera& cam, float aperture, float focus) {
     return lv;
 }
 // the shaded guides (pt_render_aovs_ex with PT_AOV_SHADED; pt_denoise.hip): vn == nullptr: option smooth_normals is off, tv.uv == nullptr:
-// option textures is off, glossy: option glossy (a terminal type-4 hit gives tint x F0), coated: option coated (a terminal type-5 hit gives tint x kd')
+// option textures is off, glossy: option glossy (a terminal type-4 hit gives tint x F0), coated: option coated (a terminal type-5 hit gives tint x kd'),
+// frosted: option frosted (a terminal type-6 hit gives tint x 1)
 hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
-                              const float4* vn, const TexView& tv, int glossy, int coated, int cu_count, hipStream_t stream);
+                              const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream);
 // env == nullptr: the instances without an environment.  tiled (the rounds of pt_render_adaptive_ex): k_nee_tiles / k_nee_env_tiles over
 // the p.n_tiles 8x8 frame tiles of p.tile_list (null: the frame's tiles in order), one lane per pixel of a tile; npix is then not read
 // vn != nullptr (option smooth_normals): the smooth instances, which shade with the interpolated normal of the packed vertex normals vn
@@ -458,8 +459,11 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
 // lens (a lens with aperture > 0 is set, pt_set_lens; tv non-null as for glossy): the lens instances, built on the coated code, whatever
 // the options say; glossy and coated are then the options themselves and travel as a kernel argument, vn and tv->uv are null where
 // their option is off
+// frosted (option frosted with a type-6 material uploaded; tv and lens non-null): the frosted instances, built on the lens code; glossy and
+// coated are the options themselves, and the lens is live in the launch iff lens->aperture > 0 (else the pinhole ray)
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled = false,
-                      const float4* vn = nullptr, const TexView* tv = nullptr, bool glossy = false, bool coated = false, const LensView* lens = nullptr);
+                      const float4* vn = nullptr, const TexView* tv = nullptr, bool glossy = false, bool coated = false, const LensView* lens = nullptr,
+                      bool frosted = false);
 // thin lens (pt_lens.hip): pt_debug_lens's kernel, {gid, S} in and 6 floats out per item; pt_focus_at's, the axial distance of pixel gid's
 // centre-ray hit into *out (+inf: a miss)
 hipError_t launch_debug_lens(const pt_camera& cam, const LensView& lv, const int32_t* gid_state, int64_t n, float* out, hipStream_t stream);
@@ -472,6 +476,8 @@ hipError_t launch_debug_albedo(const RenderParams& p, const float4* vn, const Te
 hipError_t launch_debug_glossy(const float* in, int64_t n, float* out, hipStream_t stream);
 // coated diffuse (pt_glossy.hip): pt_debug_coated's kernel, 12 floats in and 10 out per item
 hipError_t launch_debug_coated(const float* in, int64_t n, float* out, hipStream_t stream);
+// rough dielectric (pt_glossy.hip): pt_debug_frosted's kernel, 12 floats in and 10 out per item
+hipError_t launch_debug_frosted(const float* in, int64_t n, float* out, hipStream_t stream);
 // smooth shading (pt_smooth.hip): add-order normals (9 floats per triangle, n_src triangles; the rest has none) -> 3 float4 per packed triangle
 hipError_t launch_pack_vertex_normals(const float* src, int64_t n_src, const int32_t* orig, int32_t n, float4* out, hipStream_t stream);
 hipError_t launch_debug_shading_normal(const RenderParams& p, const float4* vn, const pt_ray* rays, int64_t n, int32_t* out_tri, float4* out_ns, int cu_count,

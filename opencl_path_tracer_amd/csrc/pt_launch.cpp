@@ -366,6 +366,7 @@ static void launch_cfg(pt_context* ctx, const RenderParams& p, LaunchConfig* lc)
 }
 
 int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
+    if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_generate_rays: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_generate_rays: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
     if (ctx && ctx->coated) return fail(ctx, PT_EINVAL, "pt_generate_rays: option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
     if (ctx && ctx->glossy) return fail(ctx, PT_EINVAL, "pt_generate_rays: option glossy is on and only pt_render_nee shades the rough metal of material type 4 (pt_set_option(ctx, \"glossy\", 0) turns it off)");
@@ -383,6 +384,7 @@ int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
 }
 
 int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t current_sample) {
+    if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_trace_rays: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_trace_rays: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
     if (ctx && ctx->coated) return fail(ctx, PT_EINVAL, "pt_trace_rays: option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
     if (ctx && ctx->glossy) return fail(ctx, PT_EINVAL, "pt_trace_rays: option glossy is on and only pt_render_nee shades the rough metal of material type 4 (pt_set_option(ctx, \"glossy\", 0) turns it off)");
@@ -588,6 +590,7 @@ static int launch_megakernel(pt_context* ctx, RenderParams& p, const int32_t* ti
 }
 
 int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples) {
+    if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_render: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_render: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
     if (ctx && ctx->coated) return fail(ctx, PT_EINVAL, "pt_render: option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
     if (ctx && ctx->glossy) return fail(ctx, PT_EINVAL, "pt_render: option glossy is on and only pt_render_nee shades the rough metal of material type 4 (pt_set_option(ctx, \"glossy\", 0) turns it off)");
@@ -658,6 +661,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
                   " tiles does not fit the 31-bit work-item counter of one launch";
     }
     if (!why.empty()) return fail(ctx, PT_EINVAL, who + ": " + why);
+    if (!nee && ctx->frosted) return fail(ctx, PT_EINVAL, who + ": option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (!nee && lens_on(ctx)) return fail(ctx, PT_EINVAL, who + ": a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
     if (!nee && ctx->coated) return fail(ctx, PT_EINVAL, who + ": option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
     if (!nee && ctx->glossy) return fail(ctx, PT_EINVAL, who + ": option glossy is on and only pt_render_nee shades the rough metal of material type 4 (pt_set_option(ctx, \"glossy\", 0) turns it off)");
@@ -684,8 +688,9 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
     if (nee && (rc = texture_prepare(ctx, &tv)) != PT_OK) return rc;
     const bool coated = nee && ctx->coated && ctx->coated_mats;      // option coated without a type-5 material: today's instances
     const bool glossy = nee && ctx->glossy && (ctx->glossy_mats || coated);      // option glossy without a type-4 material: today's instances
-    const bool lens = nee && lens_on(ctx);  // a lens: the lens instances, whatever the options say
-    const LensView lv = lens_view(*cam, ctx->lens_aperture, ctx->lens_focus);
+    const bool frosted = nee && ctx->frosted && ctx->frosted_mats;      // option frosted without a type-6 material: today's instances
+    const bool lens = nee && (lens_on(ctx) || frosted);  // a lens: the lens instances, whatever the options say (so the frosted ones, built on them)
+    const LensView lv = lens_view(*cam, lens_on(ctx) ? ctx->lens_aperture : 0.0f, ctx->lens_focus);
     const int32_t n_frame = local_tiles(ctx);
     if (!ctx->d_adapt_spp) {
         PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_spp, sizeof(int32_t) * (size_t)n_frame));
@@ -720,7 +725,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
             EventPair* ep;
             if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
             PT_HIP(ctx, launch_nee(pr, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, true, vn, tv.uv || glossy || coated || lens ? &tv : nullptr,
-                                   lens ? ctx->glossy != 0 : glossy, lens ? ctx->coated != 0 : coated, lens ? &lv : nullptr));
+                                   lens ? ctx->glossy != 0 : glossy, lens ? ctx->coated != 0 : coated, lens ? &lv : nullptr, frosted));
             if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
         } else if ((rc = launch_megakernel(ctx, pr, list, n_active)) != PT_OK) {
             return rc;

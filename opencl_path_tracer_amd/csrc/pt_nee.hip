@@ -26,6 +26,10 @@
 //           sample on lens_get_ray_xy (pt_device.hpp) instead of camera_get_ray_xy; what it adds sits under `if constexpr (LENS)`.  One
 //           family serves every option combination, so whether type 5 is live is a run-time field in them too (option coated), next to
 //           type 4's; normals and uvs are bound or null as in the instances below them.  Launched only while a lens with aperture > 0 is set.
+//   k_nee*_frosted  the lens kernels with the rough dielectric of option frosted (material type 6): NeeHook<.., FROST>;
+//           what they add sits under `if constexpr (FROST)` here and under HOOK::frosted in shade_hit.  Launched only when the option is on
+//           and a type-6 material is uploaded; whether a lens is set is one more run-time field in them (flags bit 2), so this one family
+//           serves every combination of options and lens.
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -99,9 +103,18 @@ struct LensSlot<true> {
     bool coat = true;              // option coated: type 5 is the coated diffuse in this launch (else inert, as in the instances without it)
 };
 
+// what a frame carries for the rough dielectric (option frosted): nothing without it
+template <bool FROST>
+struct FrostSlot {};
+template <>
+struct FrostSlot<true> {
+    bool lens = true;              // a lens with aperture > 0 is set in this launch (else the pinhole ray, as in the instances without one)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
-template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false>
+template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false, bool FROST = false>
 struct NeeHook {
+    static_assert(LENS || !FROST, "the frosted instances are built on the lens code");
     static_assert(COAT || !LENS, "the lens instances are built on the coated code");
     static_assert(SMOOTH || !TEX, "the textured instances are built on the smooth code");
     static_assert(TEX || !GLOSSY, "the glossy instances are built on the textured code");
@@ -112,6 +125,7 @@ struct NeeHook {
     static constexpr bool glossy = GLOSSY;
     static constexpr bool coated = COAT;
     static constexpr bool lens = LENS;
+    static constexpr bool frosted = FROST;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -128,6 +142,67 @@ struct NeeHook {
     GlossySlot<GLOSSY> gs;
     CoatSlot<COAT> ct;
     LensSlot<LENS> ln;
+    FrostSlot<FROST> frs;
+
+    // FROST: the reflection lobe's p_b of the unit direction w at the type-6 vertex with normal N reached along rD (ins: inside the
+    // medium), and the factor_R its own update with w would give -- through frosted_pdf_weight, as the sampled direction's
+    PT_DEV float frosted_light(const pt_material* __restrict__ m, f3 N, f3 rD, f3 w, bool ins, f3 fR, f3* fr) const {
+        f3 Z, X;
+        tangent_frame(N, &Z, &X);
+        const float n = m->n;
+        f3 g;
+        const float pb = frosted_pdf_weight_of(m->shininess, ldf3(m->F0), ins ? 1.0f / n : n, to_local(-rD, X, Z, N), to_local(w, X, Z, N), &g);
+        *fr = fR * g;
+        return pb;
+    }
+    // FROST: lobe_vertex_coated with the frosted vertex (fr_) as a fourth kind: it multiplies factor_R by g(w); a reflection keeps its p_b
+    // and ends the path unless w.z > 0, a refraction toggles `inside`, leaves along -Ng (*side) and ends the path unless w.z < 0.  Its
+    // lobe is chosen by the hash value a coated vertex uses (a vertex has one type)
+    template <bool SK, class ST>
+    PT_DEV f3 lobe_vertex_frosted(ST& st, const pt_material* __restrict__ m, bool gl, bool ct_, bool fr_, f3 N, f3 rD, float rnd1, float rnd2, bool& inside,
+                                  float* side) {
+        float alpha = 1.0f, u_sel = 0.0f, eta = 1.0f;
+        f3 F0 = mk(0.f, 0.f, 0.f), kd = F0;
+        if (gl || ct_) alpha = m->n;       // (the device copy of a type-4 or type-5 material carries its roughness there: pt_upload_materials)
+        if (fr_) {
+            alpha = m->shininess;          // (that of a type-6 material here; its n is the index of refraction)
+            eta = m->n;
+            if (inside) eta = 1.0f / eta;
+        }
+        if (gl || ct_ || fr_) F0 = ldf3(m->F0);
+        if (ct_) kd = albedo(m);
+        if (ct_ || fr_) u_sel = nee_unit(nee_rand(~key, k, 1));
+        GlossyOut go;
+        CoatedOut co;
+        FrostedOut fo;
+        const f3 d = lobe_direction_frosted<SK>(N, rD, gl, ct_, fr_, alpha, F0, kd, eta, u_sel, rnd1, rnd2, &go, &co, &fo);
+        if (gl) {
+            st.setS(st.S() * (go.F * go.g1w));
+            gs.pb = go.pb;
+            if (!(go.wz > 0.0f)) sm.dead = true;
+        }
+        if (ct_) {
+            st.setS(st.S() * co.g);
+            gs.pb = co.pb;
+            if (!(co.wz > 0.0f && co.pb > 0.0f)) sm.dead = true;
+        }
+        if (fr_) {
+            st.setR(st.R() * fo.g);
+            gs.pb = fo.pb;
+            if (!fo.refl) {
+                inside = !inside;
+                *side = -0.001f;
+            }
+            if (!(fo.refl ? fo.wz > 0.0f : fo.wz < 0.0f)) sm.dead = true;
+        }
+        return d;
+    }
+    // FROST: leaves_surface where a refracted direction (through) must be below the geometric surface instead
+    PT_DEV void leaves_surface_frosted(bool lobe, bool through, f3 dnew) {
+        if (!lobe) return;
+        const float g = dot3(dnew, geo(dnew));
+        if (through ? g >= 0.0f : g <= 0.0f) sm.dead = true;
+    }
 
     // LENS: type 5 is live (option coated; a run-time answer in the lens instances only: the coated ones run only when it is)
     PT_DEV bool coat_live() const {
@@ -333,10 +408,12 @@ struct NeeHook {
     // a change to one belongs in the other)
     // (rD: the direction the vertex was reached along; only the GLOSSY instances pass and read it.  shade_hit keeps the six-argument call
     // for every other hook, so that nothing about the existing instances' calls changes)
-    PT_DEV void light_sample(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD = mk(0.f, 0.f, 0.f)) {
+    // (ins: the path is inside a dielectric; only the FROST instances pass and read it)
+    PT_DEV void light_sample(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD = mk(0.f, 0.f, 0.f),
+                             bool ins = false) {
         if (!nee || k + 1 >= p.iterations) return;
         if constexpr (ENV) {
-            light_sample_env(st, p, m, type, N, hp, rD);
+            light_sample_env(st, p, m, type, N, hp, rD, ins);
             return;
         }
         const float u0 = nee_unit(nee_rand(key, k, 0)), u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
@@ -373,6 +450,12 @@ struct NeeHook {
                 pb = coated_light(m, N, rD, w, fs, &fs);
                 if (!(pb > 0.0f)) return;
             }
+        f3 fr = st.R();
+        if constexpr (FROST)
+            if (type == 6) {
+                pb = frosted_light(m, N, rD, w, ins, fr, &fr);
+                if (!(pb > 0.0f)) return;
+            }
         const float q = pb / pl;
         const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
         f3 fl = st.L(), fb = st.B();
@@ -386,14 +469,14 @@ struct NeeHook {
             }
             fb = fb * (ldf3(m->ks) * pw);
         }
-        const f3 e = ((ldf3(p.mats[p.meta[li].mati].emission) * (fl + fb)) * fs) * st.R();
+        const f3 e = ((ldf3(p.mats[p.meta[li].mati].emission) * (fl + fb)) * fs) * fr;
         if (wl < __builtin_inff()) st.setC(madd(e, cosy * wl, st.C()));
     }
 
     // ENV: the sky with probability P_env (u_sel, keyed with ~key), else a light of the table with its pdf times 1 - P_env.  Both
     // branches only produce the shadow ray and what it would add; the traversal and the weighting are shared, so a wave that holds
     // both kinds of sample runs one traversal.  (TWIN: the triangle branch and the tail restate light_sample above.)
-    PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD) {
+    PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins) {
         const EnvView& ev = env.v;
         const float u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
         const f3 o = madd(geo(N), 0.001f, hp);
@@ -472,6 +555,12 @@ struct NeeHook {
                 pb = coated_light(m, N, rD, w, fs, &fs);
                 if (!(pb > 0.0f)) return;
             }
+        f3 fr = st.R();
+        if constexpr (FROST)
+            if (type == 6) {
+                pb = frosted_light(m, N, rD, w, ins, fr, &fr);
+                if (!(pb > 0.0f)) return;
+            }
         const float q = pb / pl;
         const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
         f3 fl = st.L(), fb = st.B();
@@ -485,7 +574,7 @@ struct NeeHook {
             }
             fb = fb * (ldf3(m->ks) * pw);
         }
-        e = ((e * (fl + fb)) * fs) * st.R();
+        e = ((e * (fl + fb)) * fs) * fr;
         if (wl < __builtin_inff()) st.setC(madd(e, g * wl, st.C()));
     }
 
@@ -528,20 +617,23 @@ struct NeeHook {
 // GLOSSY (option glossy; k_nee*_glossy below; on the TEX code only): material type 4 is the rough-metal lobe vertex
 // COAT (option coated; k_nee*_coated below; on the GLOSSY code only): material type 5 is the coated-diffuse lobe vertex; metal: option glossy
 // LENS (pt_set_lens; k_nee*_lens below; on the COAT code only): each sample starts on the thin-lens ray; metal bit 1: option coated
-template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false>
+// FROST (option frosted; k_nee*_frosted below; on the LENS code only): material type 6 is the rough-dielectric lobe vertex; metal bit 2: a lens is set
+template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false,
+          bool FROST = false>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr,
                       int metal = 0, const LensView* lens = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (TEX) hook.tx.v = *tv;
     if constexpr (LENS) {
         hook.ct.metal = (metal & 1) != 0;
         hook.ln.coat = (metal & 2) != 0;
         hook.ln.v = *lens;
+        if constexpr (FROST) hook.frs.lens = (metal & 4) != 0;
     } else if constexpr (COAT) hook.ct.metal = metal != 0;
     if constexpr (ENV) {
         hook.env = env;
@@ -586,7 +678,10 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
             bool inside = false;
             {
                 const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
-                if constexpr (LENS) lens_get_ray_xy(pix_x, pix_y, p.cam, hook.ln.v, rnd1, rnd2, hook.key, &rP, &rD);
+                if constexpr (FROST) {
+                    if (hook.frs.lens) lens_get_ray_xy(pix_x, pix_y, p.cam, hook.ln.v, rnd1, rnd2, hook.key, &rP, &rD);
+                    else camera_get_ray_xy(pix_x, pix_y, p.cam, rnd1, rnd2, &rP, &rD);
+                } else if constexpr (LENS) lens_get_ray_xy(pix_x, pix_y, p.cam, hook.ln.v, rnd1, rnd2, hook.key, &rP, &rD);
                 else camera_get_ray_xy(pix_x, pix_y, p.cam, rnd1, rnd2, &rP, &rD);
             }
             for (int k = 0; k < p.iterations; ++k) {
@@ -726,6 +821,25 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_lens(RenderParams p, Ne
     nee_frame<MODE, BLOCK, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv);
 }
 
+// the frosted instances (option frosted with a type-6 material uploaded): the lens kernels, the same arguments; flags bit 2: a lens with
+// aperture > 0 is set (else lv is not read and each sample starts on the pinhole ray)
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_frosted(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_frosted(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_frosted(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv) {
+    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_frosted(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv) {
+    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -742,7 +856,17 @@ static hipError_t launch_lanes_env_tiles_smooth(PICK pick, const RenderParams& p
 }
 
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled, const float4* vn,
-                      const TexView* tv, bool glossy, bool coated, const LensView* lens) {
+                      const TexView* tv, bool glossy, bool coated, const LensView* lens, bool frosted) {
+    if (frosted) {     // (tv and lens are never null here; glossy, coated: the options themselves; the lens is live iff its aperture is > 0)
+        const int flags = (glossy ? 1 : 0) | (coated ? 2 : 0) | (lens->aperture > 0.0f ? 4 : 0);
+        if (tiled) {
+            const int64_t items = (int64_t)p.n_tiles * 64;
+            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_frosted<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv, flags, *lens);
+            return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_tiles_frosted<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv, flags, *lens);
+        }
+        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_frosted<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, flags, *lens, (long long)npix);
+        return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_frosted<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, flags, *lens, (long long)npix);
+    }
     if (lens) {        // (tv is never null here; glossy, coated: the options themselves)
         const int flags = (glossy ? 1 : 0) | (coated ? 2 : 0);
         if (tiled) {

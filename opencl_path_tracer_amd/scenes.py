@@ -134,7 +134,7 @@ def checker_texture(n, a, b):
     return np.where(even, np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)).astype(np.float32)
 
 
-def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False):
+def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False, frosted=False):
     """Scene CB of SURVEY 8(d): 12 wall/lamp triangles + two tessellated spheres
     (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects.
     smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals).
@@ -143,7 +143,11 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
     glossy: the chromium sphere gets a copy of its material with type 4 and shininess 50, appended to the materials: a rough metal under
     option glossy (and inert without it).
     coated: the other sphere gets, in place of GLASS, a red plastic appended to the materials: type 5, kd (0.7, 0.1, 0.1), N = 1.5 and
-    K = 0 (F0 = 0.04), shininess 300; a diffuse base under a rough dielectric coat under option coated (and inert without it)."""
+    K = 0 (F0 = 0.04), shininess 300; a diffuse base under a rough dielectric coat under option coated (and inert without it).
+    frosted: the other sphere gets, in place of GLASS, a copy of GLASS with type 6 and shininess 30, appended to the materials: a rough
+    dielectric (frosted glass) under option frosted (and inert without it).  The sphere wears one material: not together with coated."""
+    if coated and frosted:
+        raise ValueError("cornell_box: coated and frosted both replace the glass sphere's material")
     spec = SceneSpec(materials=list(BUILTIN_MATERIALS), name="cornell_box")
     spec.objects.append(cornell_walls())
     s1 = uv_sphere((250.0, 200.0, 300.0), 200.0, segments, rings)
@@ -156,6 +160,9 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
     glass = GLASS
     if coated:
         spec.materials.append(((0.7, 0.1, 0.1), (0, 0, 0), (0, 0, 0), (1.5, 1.5, 1.5), (0, 0, 0), 300.0, 5))
+        glass = len(spec.materials) - 1
+    if frosted:
+        spec.materials.append(tuple(BUILTIN_MATERIALS[GLASS][:5]) + (30.0, 6))
         glass = len(spec.materials) - 1
     spec.objects.append((s2, np.full(s2.shape[0], glass, dtype=np.uint16)))
     if smooth:
