@@ -283,6 +283,9 @@ int smooth_prepare(pt_context* ctx, const float4** vn, bool force = false);
 // pt_host.cpp: the textures, bindings and packed uvs on the device for a textured launch (refreshed if stale); tv->uv = null when the
 // option is off, unless force
 int texture_prepare(pt_context* ctx, TexView* tv, bool force = false);
+// pt_host.cpp: the NEE launch the context's options, materials and lens ask for (NeeLaunch, pt_internal.hpp), with the vertex normals and
+// textures prepared on the device; nee_on = false (no NEE launch will follow): nothing is prepared.  env and tiled are left clear: the caller sets them
+int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch* nl);
 int host_threads(const pt_context* ctx);                        // threads of the host-side scene path (option build_threads)
 
 #define PT_HIP(ctx, call)                                                                   \

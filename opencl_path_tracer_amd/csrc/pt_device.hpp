@@ -1205,47 +1205,6 @@ struct GlossyOut {
     float wz;        // w.z: the path ends unless it is > 0
     float oz;        // (pt_debug_glossy)
 };
-// The direction (before normalisation) of a lobe vertex in the glossy instances: diffuse_direction's frame, roots, sincos and world
-// sum, shared by the lanes of both kinds; only the local coordinates in between differ (gl: a type-4 vertex).  A diffuse lane gets
-// diffuse_direction's bits.
-template <bool SK>
-PT_DEV f3 lobe_direction_glossy(f3 N, f3 D, bool gl, float alpha, f3 F0, float rnd1, float rnd2, GlossyOut* out) {
-    bool yaxis;
-    const float l2 = frame_l2(N, &yaxis);
-    float rl, r;
-    if (wave_all(rsqrt_window(l2) && rnd1 >= kSqrtWindowLo && rnd1 < 1.0f)) {
-        rl = rsqrt_core(l2);
-        r = sqrt_core(rnd1);
-    } else {
-        rl = 1.0f / __builtin_sqrtf(l2);
-        r = __builtin_sqrtf(rnd1);
-    }
-    f3 Z, X;
-    frame_from_rl(N, yaxis, rl, &Z, &X);
-    const float theta = (float)(6.283185307179586 * (double)rnd2);
-    float sn, cs;
-    spec_sincos<SK>(theta, &sn, &cs);
-    float x = r * cs, y = r * sn, z;
-    if (gl) {
-        const f3 o = to_local(-D, X, Z, N);
-        f3 h;
-        const f3 w = glossy_sample(alpha, o, x, y, &h);
-        out->pb = glossy_pdf(alpha, o, h);
-        out->g1w = glossy_G1(alpha, w);
-        out->F = fresnel(F0, h, -o);
-        out->wz = w.z;
-        out->oz = o.z;
-        x = w.x;
-        y = w.y;
-        z = w.z;
-    } else {
-        z = sqrt_rn(1.0f - rnd1);
-    }
-    f3 d = X * x;
-    d = madd(N, z, d);
-    d = madd(Z, y, d);
-    return d;
-}
 
 // ---- coated diffuse, material type 5 under option coated (a diffuse base under a rough dielectric coat; include/pt_api.h pins every
 // operation).  Local vectors as above; D, G1, glossy_pdf, glossy_weight and fresnel are the rough metal's.
@@ -1286,65 +1245,6 @@ struct CoatedOut {
     float oz;
     bool coat;       // the coat lobe drew w
 };
-// lobe_direction_glossy with the coated vertex as a third kind of lane (ct; u_sel chooses its lobe): the frame, the roots, the sincos and
-// the world sum are shared by all three, glossy_sample by the metal and the coat lobe, sqrt(1 - rnd1) by the cosine lobes.  A diffuse
-// lane gets diffuse_direction's bits and a type-4 lane lobe_direction_glossy's.
-template <bool SK>
-PT_DEV f3 lobe_direction_coated(f3 N, f3 D, bool gl, bool ct, float alpha, f3 F0, f3 kd, float u_sel, float rnd1, float rnd2, GlossyOut* out, CoatedOut* co) {
-    bool yaxis;
-    const float l2 = frame_l2(N, &yaxis);
-    float rl, r;
-    if (wave_all(rsqrt_window(l2) && rnd1 >= kSqrtWindowLo && rnd1 < 1.0f)) {
-        rl = rsqrt_core(l2);
-        r = sqrt_core(rnd1);
-    } else {
-        rl = 1.0f / __builtin_sqrtf(l2);
-        r = __builtin_sqrtf(rnd1);
-    }
-    f3 Z, X;
-    frame_from_rl(N, yaxis, rl, &Z, &X);
-    const float theta = (float)(6.283185307179586 * (double)rnd2);
-    float sn, cs;
-    spec_sincos<SK>(theta, &sn, &cs);
-    float x = r * cs, y = r * sn, z = 0.0f;
-    f3 o = mk(0.f, 0.f, 1.f), h = o;
-    float ps = 0.0f;
-    bool vis = gl;             // the lane samples visible normals: a metal, or the coat lobe of a coated vertex
-    if (gl || ct) o = to_local(-D, X, Z, N);
-    if (ct) {
-        ps = coated_ps(F0, kd, o);
-        vis = u_sel < ps;
-    }
-    if (vis) {
-        const f3 w = glossy_sample(alpha, o, x, y, &h);
-        x = w.x;
-        y = w.y;
-        z = w.z;
-    } else {
-        z = sqrt_rn(1.0f - rnd1);
-    }
-    if (gl) {
-        const f3 w = mk(x, y, z);
-        out->pb = glossy_pdf(alpha, o, h);
-        out->g1w = glossy_G1(alpha, w);
-        out->F = fresnel(F0, h, -o);
-        out->wz = z;
-        out->oz = o.z;
-    }
-    if (ct) {
-        const f3 w = mk(x, y, z);
-        if (!vis) h = normalize3(o + w);
-        co->pb = coated_pdf_weight(alpha, F0, kd, ps, o, h, w, &co->g);
-        co->wz = z;
-        co->ps = ps;
-        co->oz = o.z;
-        co->coat = vis;
-    }
-    f3 d = X * x;
-    d = madd(N, z, d);
-    d = madd(Z, y, d);
-    return d;
-}
 
 // ---- rough dielectric, material type 6 under option frosted (GGX reflection and refraction through one visible-normal half vector;
 // include/pt_api.h pins every operation).  Local vectors as above; D, G1, glossy_pdf, glossy_sample and fresnel are the rough metal's.
@@ -1388,12 +1288,24 @@ struct FrostedOut {
     float oz;
     bool refl;       // the vertex reflects
 };
-// lobe_direction_coated with the frosted vertex as a fourth kind of lane (fr; u_sel chooses its lobe against Fm): it shares the metal's
-// visible-normal draw, and a refracting lane only replaces the reflected direction by type 2's refracted one around h.  The Fresnel
-// terms, G1 and the weight are one sequence for both of its lobes.  Every other lane gets lobe_direction_coated's bits.
-template <bool SK>
-PT_DEV f3 lobe_direction_frosted(f3 N, f3 D, bool gl, bool ct, bool fr, float alpha, f3 F0, f3 kd, float eta, float u_sel, float rnd1, float rnd2,
-                                 GlossyOut* out, CoatedOut* co, FrostedOut* fo) {
+// what the metal's sampled direction w (half vector h) leaves behind
+PT_DEV void glossy_out(float alpha, f3 F0, f3 o, f3 h, f3 w, GlossyOut* out) {
+    out->pb = glossy_pdf(alpha, o, h);
+    out->g1w = glossy_G1(alpha, w);
+    out->F = fresnel(F0, h, -o);
+    out->wz = w.z;
+    out->oz = o.z;
+}
+// The direction (before normalisation) of a lobe vertex in the instances with rough materials: diffuse_direction's frame, roots, sincos
+// and world sum, shared by the lanes of every kind; only the local coordinates in between differ.  gl: a type-4 vertex (the metal); ct: a
+// type-5 one (coated; u_sel chooses its lobe against ps); fr: a type-6 one (frosted; u_sel chooses reflection against Fm).  The metal, the
+// coat lobe and the frosted vertex share one visible-normal draw, the cosine lobes sqrt(1 - rnd1); a refracting lane only replaces the
+// reflected direction by type 2's refracted one around h, and the Fresnel terms, G1 and the weight are one sequence for both of its lobes.
+// A diffuse lane gets diffuse_direction's bits.  Without COAT (ct and fr false, co and fo unread) the metal is the only rough kind and
+// has one block of its own: the glossy instances compile to other code from the general arm.
+template <bool SK, bool COAT>
+PT_DEV f3 lobe_direction_rough(f3 N, f3 D, bool gl, bool ct, bool fr, float alpha, f3 F0, f3 kd, float eta, float u_sel, float rnd1, float rnd2,
+                               GlossyOut* out, CoatedOut* co, FrostedOut* fo) {
     bool yaxis;
     const float l2 = frame_l2(N, &yaxis);
     float rl, r;
@@ -1410,53 +1322,60 @@ PT_DEV f3 lobe_direction_frosted(f3 N, f3 D, bool gl, bool ct, bool fr, float al
     float sn, cs;
     spec_sincos<SK>(theta, &sn, &cs);
     float x = r * cs, y = r * sn, z = 0.0f;
-    f3 o = mk(0.f, 0.f, 1.f), h = o;
-    float ps = 0.0f;
-    bool vis = gl || fr;       // the lane samples visible normals: a metal, a frosted vertex, or the coat lobe of a coated vertex
-    if (gl || ct || fr) o = to_local(-D, X, Z, N);
-    if (ct) {
-        ps = coated_ps(F0, kd, o);
-        vis = u_sel < ps;
-    }
-    if (vis) {
-        const f3 w = glossy_sample(alpha, o, x, y, &h);
-        x = w.x;
-        y = w.y;
-        z = w.z;
-    } else {
-        z = sqrt_rn(1.0f - rnd1);
-    }
-    if (gl) {
-        const f3 w = mk(x, y, z);
-        out->pb = glossy_pdf(alpha, o, h);
-        out->g1w = glossy_G1(alpha, w);
-        out->F = fresnel(F0, h, -o);
-        out->wz = z;
-        out->oz = o.z;
-    }
-    if (ct) {
-        const f3 w = mk(x, y, z);
-        if (!vis) h = normalize3(o + w);
-        co->pb = coated_pdf_weight(alpha, F0, kd, ps, o, h, w, &co->g);
-        co->wz = z;
-        co->ps = ps;
-        co->oz = o.z;
-        co->coat = vis;
-    }
-    if (fr) {
-        const FrostedTerms t = frosted_terms(F0, eta, o, h);
-        const bool refl = u_sel < t.Fm;
-        if (!refl) {           // type 2's refracted direction with h for the normal (the ray direction in the frame is -o)
-            const f3 w = madd(h, t.c / eta - sqrt_rn(t.disc), mk(-o.x / eta, -o.y / eta, -o.z / eta));
+    if constexpr (!COAT) {
+        if (gl) {
+            const f3 o = to_local(-D, X, Z, N);
+            f3 h;
+            const f3 w = glossy_sample(alpha, o, x, y, &h);
+            glossy_out(alpha, F0, o, h, w, out);
             x = w.x;
             y = w.y;
             z = w.z;
+        } else {
+            z = sqrt_rn(1.0f - rnd1);
         }
-        fo->pb = frosted_pdf_weight(alpha, t, refl, o, h, mk(x, y, z), &fo->g);
-        fo->wz = z;
-        fo->Fm = t.Fm;
-        fo->oz = o.z;
-        fo->refl = refl;
+    } else {
+        f3 o = mk(0.f, 0.f, 1.f), h = o;
+        float ps = 0.0f;
+        bool vis = gl || fr;   // the lane samples visible normals: a metal, a frosted vertex, or the coat lobe of a coated vertex
+        if (gl || ct || fr) o = to_local(-D, X, Z, N);
+        if (ct) {
+            ps = coated_ps(F0, kd, o);
+            vis = u_sel < ps;
+        }
+        if (vis) {
+            const f3 w = glossy_sample(alpha, o, x, y, &h);
+            x = w.x;
+            y = w.y;
+            z = w.z;
+        } else {
+            z = sqrt_rn(1.0f - rnd1);
+        }
+        if (gl) glossy_out(alpha, F0, o, h, mk(x, y, z), out);
+        if (ct) {
+            const f3 w = mk(x, y, z);
+            if (!vis) h = normalize3(o + w);
+            co->pb = coated_pdf_weight(alpha, F0, kd, ps, o, h, w, &co->g);
+            co->wz = z;
+            co->ps = ps;
+            co->oz = o.z;
+            co->coat = vis;
+        }
+        if (fr) {
+            const FrostedTerms t = frosted_terms(F0, eta, o, h);
+            const bool refl = u_sel < t.Fm;
+            if (!refl) {       // type 2's refracted direction with h for the normal (the ray direction in the frame is -o)
+                const f3 w = madd(h, t.c / eta - sqrt_rn(t.disc), mk(-o.x / eta, -o.y / eta, -o.z / eta));
+                x = w.x;
+                y = w.y;
+                z = w.z;
+            }
+            fo->pb = frosted_pdf_weight(alpha, t, refl, o, h, mk(x, y, z), &fo->g);
+            fo->wz = z;
+            fo->Fm = t.Fm;
+            fo->oz = o.z;
+            fo->refl = refl;
+        }
     }
     f3 d = X * x;
     d = madd(N, z, d);
@@ -1499,15 +1418,12 @@ struct PathRegs {
 // A hook with `textured` set (it has `smooth` too) also supplies the albedo of a type-0 vertex (option textures, pinned in
 // include/pt_api.h): shading_normal_albedo() below, one evaluation of the barycentric weights for the normal and the uv; every
 // statement that does so sits under `if constexpr (HOOK::textured)`.
-// A hook with `glossy` set (it has `textured` too) makes material type 4 a lobe vertex, the rough metal of option glossy (pinned in
-// include/pt_api.h): lobe_direction_glossy() above in place of diffuse_direction, the vertex's p_b kept in the hook; every statement
-// that does so sits under `if constexpr (HOOK::glossy)`.
-// A hook with `coated` set (it has `glossy` too) makes material type 5 a lobe vertex, the coated diffuse of option coated (pinned in
-// include/pt_api.h): lobe_direction_coated() above, the mixture's p_b kept in the hook; whether type 4 is live there is the hook's
-// run-time answer (option glossy).  Every statement that does so sits under `if constexpr (HOOK::coated)`.
-// A hook with `frosted` set (it has `lens` too) makes material type 6 a lobe vertex, the rough dielectric of option frosted (pinned in
-// include/pt_api.h): lobe_direction_frosted() above; a refracted direction leaves through the surface, so the vertex may toggle `inside`
-// and step off along -Ng.  Every statement that does so sits under `if constexpr (HOOK::frosted)`.
+// A hook with `glossy` set (it has `textured` too) makes rough materials lobe vertices (all pinned in include/pt_api.h): type 4, the rough
+// metal of option glossy; with `coated` also type 5, the coated diffuse; with `frosted` (it has `lens`) also type 6, the rough dielectric,
+// whose refracted direction leaves through the surface, so the vertex may toggle `inside` and step off along -Ng.  The hook's lobe_vertex()
+// draws the direction (lobe_direction_rough() above, in place of diffuse_direction) and keeps the vertex's p_b; whether type 4 or 5 is
+// live in a launch is the hook's answer (metal_live(), coat_live()).  The preview colour, light_sample, lobe_vertex, leaves_surface and end_vertex are
+// one call each for every hook: what a hook's flags do not cover in their arguments it does not read.
 struct NoShadeHook {
     static constexpr bool active = false;
     static constexpr bool smooth = false;
@@ -1656,13 +1572,7 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     if constexpr (HOOK::textured) {
         static_assert(HOOK::smooth && !REC, "the textured instances are built on the smooth ones");
         N = hook->shading_attributes_at(p, tris, ti, rD, hp, flip ? -N : N, N, type, m);
-        if constexpr (HOOK::coated) {
-            if (p.iterations == 1) st.setC((type == 4 && hook->metal_live() ? ldf3(m->F0) : hook->albedo(m)) + ldf3(m->emission));
-        } else if constexpr (HOOK::glossy) {
-            if (p.iterations == 1) st.setC((type == 4 ? ldf3(m->F0) : hook->albedo(m)) + ldf3(m->emission));
-        } else {
-            if (p.iterations == 1) st.setC(hook->albedo(m) + ldf3(m->emission));
-        }
+        if (p.iterations == 1) st.setC((type == 4 && hook->metal_live() ? ldf3(m->F0) : hook->albedo(m)) + ldf3(m->emission));
     } else if constexpr (HOOK::smooth) N = hook->shading_normal_at(tris, ti, rD, hp, flip ? -N : N, N);
     // Every material that continues the path ends the same way: normalise the new direction, step off the surface
     // along +-N.  The two sampling branches below only produce the direction BEFORE normalisation and the side; the
@@ -1699,14 +1609,10 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         inten = max0(dot3(-rD, N));
         if constexpr (HOOK::active) {
             if (type == 3) wb = hook->emitter_weight(ti, t, inten, rD);
-            if constexpr (HOOK::frosted) hook->light_sample(st, p, m, type, N, hp, rD, inside);
-            else if constexpr (HOOK::glossy) hook->light_sample(st, p, m, type, N, hp, rD);
-            else hook->light_sample(st, p, m, type, N, hp);                 // before the LCG draws and this hit's emission
+            hook->light_sample(st, p, m, type, N, hp, rD, inside);          // before the LCG draws and this hit's emission
         }
         const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
-        if constexpr (HOOK::frosted) dnew = hook->template lobe_vertex_frosted<SK>(st, m, gl, ct, fr, N, rD, rnd1, rnd2, inside, &side);
-        else if constexpr (HOOK::coated) dnew = hook->template lobe_vertex_coated<SK>(st, m, gl, ct, N, rD, rnd1, rnd2);
-        else if constexpr (HOOK::glossy) dnew = hook->template lobe_vertex<SK>(st, m, gl, N, rD, rnd1, rnd2);
+        if constexpr (HOOK::glossy) dnew = hook->template lobe_vertex<SK>(st, m, gl, ct, fr, N, rD, rnd1, rnd2, inside, &side);
         else if constexpr (REC) dnew = diffuse_direction_rec<SK>(N, rec + (flip ? 4 : 2), rnd1, rnd2);
         else dnew = diffuse_direction<SK>(N, rnd1, rnd2);
     } else if (spec) {
@@ -1747,8 +1653,7 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     }
     if (lobe || spec) {
         // a lobe direction below the geometric surface ends the path (frosted: a refracted one, side < 0, that is not below it)
-        if constexpr (HOOK::frosted) hook->leaves_surface_frosted(lobe, side < 0.0f, dnew);
-        else if constexpr (HOOK::smooth) hook->leaves_surface(lobe, dnew);
+        if constexpr (HOOK::smooth) hook->leaves_surface(lobe, side < 0.0f, dnew);
         rD = normalize3(dnew);
         if constexpr (HOOK::smooth) rP = madd(hook->geo(N), side, hp);
         else rP = madd(N, side, hp);
@@ -1780,10 +1685,7 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     }
     // any other type: the ray is left unchanged and the loop hits the same surface again
     // (frosted: after a refracted direction the next emitter hit or sky miss has weight 1, as after a specular vertex)
-    if constexpr (HOOK::frosted) hook->end_vertex_glossy(lobe && !(fr && side < 0.0f), gl || ct || fr, N, rD);
-    else if constexpr (HOOK::coated) hook->end_vertex_glossy(lobe, gl || ct, N, rD);
-    else if constexpr (HOOK::glossy) hook->end_vertex_glossy(lobe, gl, N, rD);
-    else if constexpr (HOOK::active) hook->end_vertex(lobe, N);
+    if constexpr (HOOK::active) hook->end_vertex(lobe && !(fr && side < 0.0f), gl || ct || fr, N, rD);
 }
 
 PT_DEV f3 running_mean(f3 acc, f3 color, int s) {   // prog.cl:379

@@ -1,5 +1,5 @@
 // pt_glossy.hip -- the rough metal of option glossy (material type 4; include/pt_api.h pins the vertex).
-//   k_debug_glossy   pt_debug_glossy: one thread per item runs lobe_direction_glossy() and glossy_pdf_of() (pt_device.hpp), the functions
+//   k_debug_glossy   pt_debug_glossy: one thread per item runs lobe_direction_rough() and glossy_pdf_of() (pt_device.hpp), the functions
 //                    the glossy k_nee instances call (pt_nee.hip) for the sampled direction and for a light sample, so that the sampler
 //                    and the density can be tested against each other and against float64 without a render.  No scene is read.
 //   k_debug_coated   pt_debug_coated: the same for the coated diffuse of option coated (material type 5).
@@ -17,7 +17,8 @@ __global__ void __launch_bounds__(256) k_debug_glossy(const float* __restrict__ 
     const f3 N = mk(a[0], a[1], a[2]), D = mk(a[3], a[4], a[5]);
     const float alpha = a[6];
     GlossyOut go;
-    const f3 d = lobe_direction_glossy<false>(N, D, true, alpha, mk(0.04f, 0.04f, 0.04f), a[7], a[8], &go);
+    const f3 F0 = mk(0.04f, 0.04f, 0.04f);
+    const f3 d = lobe_direction_rough<false, false>(N, D, true, false, false, alpha, F0, F0, 1.0f, 0.0f, a[7], a[8], &go, nullptr, nullptr);
     // the density of the same direction by the light sample's route: world -> local, h = normalize(o + w)
     f3 Z, X, h;
     tangent_frame(N, &Z, &X);
@@ -39,7 +40,7 @@ hipError_t launch_debug_glossy(const float* in, int64_t n, float* out, hipStream
     return hipGetLastError();
 }
 
-// pt_debug_coated: lobe_direction_coated() and coated_pdf_weight_of() (pt_device.hpp), the functions the coated k_nee instances call for
+// pt_debug_coated: lobe_direction_rough() and coated_pdf_weight_of() (pt_device.hpp), the functions the coated k_nee instances call for
 // the sampled direction and for a light sample.  in: 12 floats per item {N.xyz, D.xyz, alpha, F0, kd, rnd1, rnd2, u_sel} (F0 and kd grey);
 // out: 10 per item {w.xyz before normalisation (world), ps, 1 if the coat lobe drew w else 0, p_b as sampled, g.x as sampled, p_b and g.x
 // evaluated again from normalize(w), o.z}.  One thread per item: item i runs on lane i % 64
@@ -52,7 +53,7 @@ __global__ void __launch_bounds__(256) k_debug_coated(const float* __restrict__ 
     const f3 F0 = mk(a[7], a[7], a[7]), kd = mk(a[8], a[8], a[8]);
     GlossyOut go;
     CoatedOut co;
-    const f3 d = lobe_direction_coated<false>(N, D, false, true, alpha, F0, kd, a[11], a[9], a[10], &go, &co);
+    const f3 d = lobe_direction_rough<false, true>(N, D, false, true, false, alpha, F0, kd, 1.0f, a[11], a[9], a[10], &go, &co, nullptr);
     // the same direction by the light sample's route: world -> local, ps and h = normalize(o + w) from scratch
     f3 Z, X, g;
     tangent_frame(N, &Z, &X);
@@ -76,7 +77,7 @@ hipError_t launch_debug_coated(const float* in, int64_t n, float* out, hipStream
     return hipGetLastError();
 }
 
-// pt_debug_frosted: lobe_direction_frosted() and frosted_pdf_weight_of() (pt_device.hpp), the functions the frosted k_nee instances call for
+// pt_debug_frosted: lobe_direction_rough() and frosted_pdf_weight_of() (pt_device.hpp), the functions the frosted k_nee instances call for
 // the sampled direction and for a light sample.  in: 12 floats per item {N.xyz, D.xyz, alpha, F0 (grey), eta, rnd1, rnd2, u_sel}; out: 10
 // per item {w.xyz before normalisation (world), Fm, 1 if the vertex reflects else 0, p_b as sampled (0 for a refraction), g.x as sampled,
 // p_b and g.x evaluated again from normalize(w) (0, 0 for a refraction), o.z}.  One thread per item: item i runs on lane i % 64
@@ -90,7 +91,7 @@ __global__ void __launch_bounds__(256) k_debug_frosted(const float* __restrict__
     GlossyOut go;
     CoatedOut co;
     FrostedOut fo;
-    const f3 d = lobe_direction_frosted<false>(N, D, false, false, true, alpha, F0, F0, eta, a[11], a[9], a[10], &go, &co, &fo);
+    const f3 d = lobe_direction_rough<false, true>(N, D, false, false, true, alpha, F0, F0, eta, a[11], a[9], a[10], &go, &co, &fo);
     // a reflected direction once more by the light sample's route: world -> local, h = normalize(o + w) and the terms from scratch
     float again = 0.0f;
     f3 g = mk(0.f, 0.f, 0.f);

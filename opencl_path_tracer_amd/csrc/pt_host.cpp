@@ -906,6 +906,23 @@ int nee_prepare(pt_context* ctx, int32_t strategy, NeeTable* ltp, EnvView* envp,
     *skyp = sky;
     return PT_OK;
 }
+int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch* nl) {
+    *nl = NeeLaunch{nullptr, false, nullptr, TexView{nullptr, nullptr, nullptr, nullptr}, kNeePlain, 0, lens_view(*cam, lens_on(ctx) ? ctx->lens_aperture : 0.0f, ctx->lens_focus)};
+    if (!nee_on) return PT_OK;
+    int rc;
+    if ((rc = smooth_prepare(ctx, &nl->vn)) != PT_OK) return rc;
+    if ((rc = texture_prepare(ctx, &nl->tv)) != PT_OK) return rc;
+    const bool coated = ctx->coated && ctx->coated_mats, glossy = ctx->glossy && (ctx->glossy_mats || coated);
+    nl->family = ctx->frosted && ctx->frosted_mats ? kNeeFrosted
+                 : lens_on(ctx)                    ? kNeeLens
+                 : coated                          ? kNeeCoated
+                 : glossy                          ? kNeeGlossy
+                 : nl->tv.uv                       ? kNeeTex
+                 : nl->vn                          ? kNeeSmooth
+                                                   : kNeePlain;
+    nl->flags = (ctx->glossy ? 1 : 0) | (ctx->coated ? 2 : 0) | (lens_on(ctx) ? 4 : 0);
+    return PT_OK;
+}
 }  // namespace ptamd
 extern "C" {
 int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples, int32_t strategy) {
@@ -922,12 +939,9 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     EnvView env;
     bool sky = false;
     if ((rc = nee_prepare(ctx, strategy, &lt, &env, &sky)) != PT_OK) return rc;
-    const float4* vn = nullptr;        // option smooth_normals: the packed vertex normals
-    if ((rc = smooth_prepare(ctx, &vn)) != PT_OK) return rc;
-    TexView tv;                        // option textures: uvs, texels, descriptors, bindings
-    if ((rc = texture_prepare(ctx, &tv)) != PT_OK) return rc;
-    const bool coated = ctx->coated && ctx->coated_mats;      // option coated without a type-5 material: today's instances
-    const bool glossy = ctx->glossy && (ctx->glossy_mats || coated);      // option glossy without a type-4 material: today's instances
+    NeeLaunch nl;                      // the kernel family and what it reads: vertex normals, textures, lens
+    if ((rc = nee_launch_for(ctx, cam, true, &nl)) != PT_OK) return rc;
+    nl.env = sky ? &env : nullptr;
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
     p.iterations = iterations;
@@ -937,11 +951,7 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     note_frame(ctx, p.first_sample, cam);
     EventPair* ep;
     if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-    const bool frosted = ctx->frosted && ctx->frosted_mats;      // option frosted without a type-6 material: today's instances
-    const bool lens = lens_on(ctx) || frosted;      // a lens: the lens instances, whatever the options say (so the frosted ones, built on them)
-    const LensView lv = lens_view(*cam, lens_on(ctx) ? ctx->lens_aperture : 0.0f, ctx->lens_focus);
-    PT_HIP(ctx, launch_nee(p, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, false, vn, tv.uv || glossy || coated || lens ? &tv : nullptr,
-                           lens ? ctx->glossy != 0 : glossy, lens ? ctx->coated != 0 : coated, lens ? &lv : nullptr, frosted));
+    PT_HIP(ctx, launch_nee(p, lt, nl, ctx->npix, ctx->cu_count, ctx->stream));
     if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
     ctx->current_sample += nsamples;
     return PT_OK;

@@ -447,23 +447,24 @@ inline LensView lens_view(const pt_camera& cam, float aperture, float focus) {
 // frosted: option frosted (a terminal type-6 hit gives tint x 1)
 hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
                               const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream);
-// env == nullptr: the instances without an environment.  tiled (the rounds of pt_render_adaptive_ex): k_nee_tiles / k_nee_env_tiles over
-// the p.n_tiles 8x8 frame tiles of p.tile_list (null: the frame's tiles in order), one lane per pixel of a tile; npix is then not read
-// vn != nullptr (option smooth_normals): the smooth instances, which shade with the interpolated normal of the packed vertex normals vn
-// tv != nullptr (option textures): the textured instances, built on the smooth code; with smooth_normals off they are handed vn = null,
-// which they read as "no triangle has vertex normals" (the pinned rule "no vertex normals: Ns = Ng, the same bits" makes that exact)
-// glossy (option glossy with a type-4 material uploaded; tv must then be non-null, with uv = null when option textures is off): the glossy
-// instances, built on the textured code
-// coated (option coated with a type-5 material uploaded; tv non-null as for glossy): the coated instances, built on the glossy code; glossy
-// is then option glossy itself and travels as a kernel argument (type 4 is live in the launch or inert)
-// lens (a lens with aperture > 0 is set, pt_set_lens; tv non-null as for glossy): the lens instances, built on the coated code, whatever
-// the options say; glossy and coated are then the options themselves and travel as a kernel argument, vn and tv->uv are null where
-// their option is off
-// frosted (option frosted with a type-6 material uploaded; tv and lens non-null): the frosted instances, built on the lens code; glossy and
-// coated are the options themselves, and the lens is live in the launch iff lens->aperture > 0 (else the pinhole ray)
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled = false,
-                      const float4* vn = nullptr, const TexView* tv = nullptr, bool glossy = false, bool coated = false, const LensView* lens = nullptr,
-                      bool frosted = false);
+// one launch of the NEE kernels (pt_nee.hip), as nee_launch_for (pt_context.hpp) fills it from the context.  Each family is the one before it
+// with one more feature compiled in; a launch takes the first family that covers what the frame needs
+enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted };
+struct NeeLaunch {
+    const EnvView* env;          // null: the instances without an environment
+    bool tiled;                  // the rounds of pt_render_adaptive_ex: k_nee*_tiles over the p.n_tiles 8x8 frame tiles of p.tile_list (null: the
+                                 // frame's tiles in order), one lane per pixel of a tile; npix is then not read
+    const float4* vn;            // the packed vertex normals; null: option smooth_normals is off, which the families from kNeeTex on read as "no
+                                 // triangle has vertex normals" (the pinned rule "no vertex normals: Ns = Ng, the same bits" makes that exact)
+    TexView tv;                  // uv == null: option textures is off (no lookup in the families from kNeeGlossy on); not read below kNeeTex
+    int family;                  // NeeFamily.  An option whose material type is not uploaded asks for nothing; a lens with aperture > 0 takes
+                                 // kNeeLens whatever the options say; option frosted with a type-6 material takes kNeeFrosted, lens or not
+    int flags;                   // the options themselves, for the families in which they are run-time fields: bit 0 glossy (type 4 is live;
+                                 // read from kNeeCoated on), bit 1 coated (type 5 is live; from kNeeLens on), bit 2 a lens with aperture > 0 is
+                                 // set (kNeeFrosted; else each sample starts on the pinhole ray)
+    LensView lens;               // read from kNeeLens on
+};
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
 // thin lens (pt_lens.hip): pt_debug_lens's kernel, {gid, S} in and 6 floats out per item; pt_focus_at's, the axial distance of pixel gid's
 // centre-ray hit into *out (+inf: a miss)
 hipError_t launch_debug_lens(const pt_camera& cam, const LensView& lv, const int32_t* gid_state, int64_t n, float* out, hipStream_t stream);

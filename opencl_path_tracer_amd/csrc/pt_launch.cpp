@@ -682,15 +682,10 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
     EnvView env;
     bool sky = false;
     if (nee && (rc = nee_prepare(ctx, ap->strategy, &lt, &env, &sky)) != PT_OK) return rc;
-    const float4* vn = nullptr;             // option smooth_normals: the packed vertex normals
-    if (nee && (rc = smooth_prepare(ctx, &vn)) != PT_OK) return rc;
-    TexView tv{nullptr, nullptr, nullptr, nullptr};      // option textures: uvs, texels, descriptors, bindings
-    if (nee && (rc = texture_prepare(ctx, &tv)) != PT_OK) return rc;
-    const bool coated = nee && ctx->coated && ctx->coated_mats;      // option coated without a type-5 material: today's instances
-    const bool glossy = nee && ctx->glossy && (ctx->glossy_mats || coated);      // option glossy without a type-4 material: today's instances
-    const bool frosted = nee && ctx->frosted && ctx->frosted_mats;      // option frosted without a type-6 material: today's instances
-    const bool lens = nee && (lens_on(ctx) || frosted);  // a lens: the lens instances, whatever the options say (so the frosted ones, built on them)
-    const LensView lv = lens_view(*cam, lens_on(ctx) ? ctx->lens_aperture : 0.0f, ctx->lens_focus);
+    NeeLaunch nl;                           // the kernel family of the NEE rounds and what it reads: vertex normals, textures, lens
+    if ((rc = nee_launch_for(ctx, cam, nee, &nl)) != PT_OK) return rc;
+    nl.env = sky ? &env : nullptr;
+    nl.tiled = true;
     const int32_t n_frame = local_tiles(ctx);
     if (!ctx->d_adapt_spp) {
         PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_spp, sizeof(int32_t) * (size_t)n_frame));
@@ -724,8 +719,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
             pr.n_tiles = n_active;
             EventPair* ep;
             if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-            PT_HIP(ctx, launch_nee(pr, lt, sky ? &env : nullptr, ctx->npix, ctx->cu_count, ctx->stream, true, vn, tv.uv || glossy || coated || lens ? &tv : nullptr,
-                                   lens ? ctx->glossy != 0 : glossy, lens ? ctx->coated != 0 : coated, lens ? &lv : nullptr, frosted));
+            PT_HIP(ctx, launch_nee(pr, lt, nl, ctx->npix, ctx->cu_count, ctx->stream));
             if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
         } else if ((rc = launch_megakernel(ctx, pr, list, n_active)) != PT_OK) {
             return rc;

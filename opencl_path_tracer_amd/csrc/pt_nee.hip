@@ -1,42 +1,30 @@
 // pt_nee.hip -- next-event estimation with multiple importance sampling (pt_render_nee; the estimator is pinned in include/pt_api.h).
-//   k_nee   one lane per local pixel, persistent blocks (like k_aovs): every sample of the pixel back to back, path state in
-//           registers.  Each segment is shade_hit (pt_device.hpp) with a light hook, NeeHook: the MIS weight of an emitter hit
-//           after a lobe vertex and, at a lobe vertex, a light sample: one shadow ray whose search is cut just past the sampled
-//           point.  The light sample's three numbers come from a counter-based hash (nee_rand, pt_internal.hpp) of (LCG state at
-//           the start of the sample, segment, dimension), never from the LCG, so the BSDF path draws exactly what pt_render draws
-//           and rnds / rays come out the same in every strategy.
-//   k_nee_env  the same frame under an environment map (pt_set_environment): a miss adds the sky, and a lobe vertex samples either
-//           the sky or a triangle light, chosen by one more hash value.  One body, nee_frame<MODE, BLOCK, ENV>; every statement that
-//           touches the environment sits under `if constexpr (ENV)`, so k_nee is the code it was.
-//   k_nee_tiles, k_nee_env_tiles  the same body over a list of 8x8 frame tiles (the rounds of pt_render_adaptive_ex): work item j is
-//           pixel j & 63 of tile frame_tile(p, j >> 6), so a wave is a tile as in k_render.  nee_frame<..., TILED>; the work it adds
-//           sits under `if constexpr (TILED)`.  Three declarations do not, because both branches use them after the branch (the loop
-//           counter j with the pixel i = j, lrow / x, and the pixel counter `rendered`, which is dead in the untiled instances): the
-//           untiled kernels compile to the code they were (the same kernel-resource lines).
-//   k_nee*_smooth, k_nee*_tex  the same four kernels with smooth shading from vertex normals (option smooth_normals, DESIGN.md section
-//           5.9) and, built on that code, with albedo textures (option textures, section 5.10): NeeHook<.., SMOOTH, TEX>; what they add
-//           sits under `if constexpr (SMOOTH)` / `if constexpr (TEX)` here and under HOOK::smooth / HOOK::textured in shade_hit.
-//   k_nee*_glossy  the textured kernels with the rough metal of option glossy (material type 4): NeeHook<.., GLOSSY>;
-//           what they add sits under `if constexpr (GLOSSY)` here and under HOOK::glossy in shade_hit.  Launched only when the option is on
-//           and a type-4 material is uploaded.
-//   k_nee*_coated  the glossy kernels with the coated diffuse of option coated (material type 5): NeeHook<.., COAT>;
-//           what they add sits under `if constexpr (COAT)` here and under HOOK::coated in shade_hit.  Launched only when the option is on
-//           and a type-5 material is uploaded; whether type 4 is live in them is a run-time field (option glossy), as the strategy is.
-//   k_nee*_lens  the coated kernels with the thin-lens camera of pt_set_lens: nee_frame<.., LENS> starts each
-//           sample on lens_get_ray_xy (pt_device.hpp) instead of camera_get_ray_xy; what it adds sits under `if constexpr (LENS)`.  One
-//           family serves every option combination, so whether type 5 is live is a run-time field in them too (option coated), next to
-//           type 4's; normals and uvs are bound or null as in the instances below them.  Launched only while a lens with aperture > 0 is set.
-//   k_nee*_frosted  the lens kernels with the rough dielectric of option frosted (material type 6): NeeHook<.., FROST>;
-//           what they add sits under `if constexpr (FROST)` here and under HOOK::frosted in shade_hit.  Launched only when the option is on
-//           and a type-6 material is uploaded; whether a lens is set is one more run-time field in them (flags bit 2), so this one family
-//           serves every combination of options and lens.
+// One body, nee_frame<MODE, BLOCK, flags...>: one lane per local pixel, persistent blocks (like k_aovs), every sample of the pixel back to
+// back, path state in registers.  Each segment is shade_hit (pt_device.hpp) with a light hook, NeeHook<MODE, flags...>: the MIS weight of
+// an emitter hit after a lobe vertex and, at a lobe vertex, a light sample: one shadow ray whose search is cut just past the sampled point.
+// The light sample's three numbers come from a counter-based hash (nee_rand, pt_internal.hpp) of (LCG state at the start of the sample,
+// segment, dimension), never from the LCG, so the BSDF path draws exactly what pt_render draws and rnds / rays come out the same in every
+// strategy.  What a feature adds sits under `if constexpr (FLAG)` here and under HOOK::flag in shade_hit, and what it carries in a *Slot
+// that is empty without it, so an instance compiles to the code it was before the features it lacks existed:
+//   ENV     an environment map (pt_set_environment): a miss adds the sky, and a lobe vertex samples either the sky or a triangle light,
+//           chosen by one more hash value
+//   TILED   the work is a list of 8x8 frame tiles (the rounds of pt_render_adaptive_ex): item j is pixel j & 63 of tile
+//           frame_tile(p, j >> 6), so a wave is a tile as in k_render.  Three declarations sit outside the flag because both branches use
+//           them afterwards (the loop counter j with the pixel i = j, lrow / x, and the pixel counter `rendered`, dead when untiled)
+//   SMOOTH  smooth shading from vertex normals (option smooth_normals)
+//   TEX     albedo textures (option textures, section 5.10)
+//   GLOSSY  material type 4 is the rough metal (option glossy, section 5.12)
+//   COAT    material type 5 is the coated diffuse (option coated, section 5.13); whether type 4 is live is a run-time field from here on
+//   LENS    each sample starts on the thin-lens ray (pt_set_lens, section 5.14); whether type 5 is live is a run-time field from here on
+//   FROST   material type 6 is the rough dielectric (option frosted, section 5.15); whether a lens is set is a run-time field (flags bit 2)
+// Each flag from SMOOTH on requires the one before it.  The kernels are the seven families the host can ask for (NeeFamily, pt_internal.hpp)
+// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted: each is the one before it with one more flag -- times ENV and TILED
+// (k_nee_env*, k_nee_tiles*, k_nee_env_tiles*).  In a family whose option is off the data is null (vn, tv.uv) or the field clear.
 #include "pt_device.hpp"
 
 namespace ptamd {
 
 PT_DEV float nee_unit(unsigned h) { return (float)(h >> 8) * 5.9604644775390625e-08f; }   // [0, 1), 24 bits
-
-constexpr float kInvPi = 0.318309886183790672f;
 
 // closest hit of (o, w) among the triangles nearer than `limit` (-1: none): the traversal starts with best_t = limit, so the
 // big-triangle list and every node box behind the light sample are pruned from the first test
@@ -144,6 +132,16 @@ struct NeeHook {
     LensSlot<LENS> ln;
     FrostSlot<FROST> frs;
 
+    // LENS: type 5 is live (option coated; a run-time answer in the lens instances only: the coated ones run only when it is)
+    PT_DEV bool coat_live() const {
+        if constexpr (LENS) return ln.coat;
+        else return COAT;
+    }
+    // COAT: type 4 is live (option glossy)
+    PT_DEV bool metal_live() const {
+        if constexpr (COAT) return ct.metal;
+        else return GLOSSY;
+    }
     // FROST: the reflection lobe's p_b of the unit direction w at the type-6 vertex with normal N reached along rD (ins: inside the
     // medium), and the factor_R its own update with w would give -- through frosted_pdf_weight, as the sampled direction's
     PT_DEV float frosted_light(const pt_material* __restrict__ m, f3 N, f3 rD, f3 w, bool ins, f3 fR, f3* fr) const {
@@ -155,67 +153,8 @@ struct NeeHook {
         *fr = fR * g;
         return pb;
     }
-    // FROST: lobe_vertex_coated with the frosted vertex (fr_) as a fourth kind: it multiplies factor_R by g(w); a reflection keeps its p_b
-    // and ends the path unless w.z > 0, a refraction toggles `inside`, leaves along -Ng (*side) and ends the path unless w.z < 0.  Its
-    // lobe is chosen by the hash value a coated vertex uses (a vertex has one type)
-    template <bool SK, class ST>
-    PT_DEV f3 lobe_vertex_frosted(ST& st, const pt_material* __restrict__ m, bool gl, bool ct_, bool fr_, f3 N, f3 rD, float rnd1, float rnd2, bool& inside,
-                                  float* side) {
-        float alpha = 1.0f, u_sel = 0.0f, eta = 1.0f;
-        f3 F0 = mk(0.f, 0.f, 0.f), kd = F0;
-        if (gl || ct_) alpha = m->n;       // (the device copy of a type-4 or type-5 material carries its roughness there: pt_upload_materials)
-        if (fr_) {
-            alpha = m->shininess;          // (that of a type-6 material here; its n is the index of refraction)
-            eta = m->n;
-            if (inside) eta = 1.0f / eta;
-        }
-        if (gl || ct_ || fr_) F0 = ldf3(m->F0);
-        if (ct_) kd = albedo(m);
-        if (ct_ || fr_) u_sel = nee_unit(nee_rand(~key, k, 1));
-        GlossyOut go;
-        CoatedOut co;
-        FrostedOut fo;
-        const f3 d = lobe_direction_frosted<SK>(N, rD, gl, ct_, fr_, alpha, F0, kd, eta, u_sel, rnd1, rnd2, &go, &co, &fo);
-        if (gl) {
-            st.setS(st.S() * (go.F * go.g1w));
-            gs.pb = go.pb;
-            if (!(go.wz > 0.0f)) sm.dead = true;
-        }
-        if (ct_) {
-            st.setS(st.S() * co.g);
-            gs.pb = co.pb;
-            if (!(co.wz > 0.0f && co.pb > 0.0f)) sm.dead = true;
-        }
-        if (fr_) {
-            st.setR(st.R() * fo.g);
-            gs.pb = fo.pb;
-            if (!fo.refl) {
-                inside = !inside;
-                *side = -0.001f;
-            }
-            if (!(fo.refl ? fo.wz > 0.0f : fo.wz < 0.0f)) sm.dead = true;
-        }
-        return d;
-    }
-    // FROST: leaves_surface where a refracted direction (through) must be below the geometric surface instead
-    PT_DEV void leaves_surface_frosted(bool lobe, bool through, f3 dnew) {
-        if (!lobe) return;
-        const float g = dot3(dnew, geo(dnew));
-        if (through ? g >= 0.0f : g <= 0.0f) sm.dead = true;
-    }
-
-    // LENS: type 5 is live (option coated; a run-time answer in the lens instances only: the coated ones run only when it is)
-    PT_DEV bool coat_live() const {
-        if constexpr (LENS) return ln.coat;
-        else return COAT;
-    }
-    // COAT: type 4 is live (option glossy)
-    PT_DEV bool metal_live() const {
-        if constexpr (COAT) return ct.metal;
-        else return GLOSSY;
-    }
     // COAT: the mixture's p_b of the unit direction w at the type-5 vertex with normal N reached along rD, and the factor_S its own update
-    // with w would give -- through coated_pdf_weight, as the sampled direction's (lobe_direction_coated)
+    // with w would give -- through coated_pdf_weight, as the sampled direction's (lobe_direction_rough)
     PT_DEV float coated_light(const pt_material* __restrict__ m, f3 N, f3 rD, f3 w, f3 fS, f3* fs) const {
         f3 Z, X;
         tangent_frame(N, &Z, &X);
@@ -224,38 +163,8 @@ struct NeeHook {
         *fs = fS * g;
         return pb;
     }
-    // COAT: lobe_vertex with the coated vertex (ct_) as a third kind: it multiplies factor_S by g(w), keeps the mixture's p_b and ends the
-    // path unless w.z > 0 and p_b > 0.  Its lobe is chosen by a hash value keyed like the environment's selection, dimension 1
-    template <bool SK, class ST>
-    PT_DEV f3 lobe_vertex_coated(ST& st, const pt_material* __restrict__ m, bool gl, bool ct_, f3 N, f3 rD, float rnd1, float rnd2) {
-        float alpha = 1.0f, u_sel = 0.0f;
-        f3 F0 = mk(0.f, 0.f, 0.f), kd = F0;
-        if (gl || ct_) {
-            alpha = m->n;          // (the device copy of a type-4 or type-5 material carries its roughness there: pt_upload_materials)
-            F0 = ldf3(m->F0);
-        }
-        if (ct_) {
-            kd = albedo(m);
-            u_sel = nee_unit(nee_rand(~key, k, 1));
-        }
-        GlossyOut go;
-        CoatedOut co;
-        const f3 d = lobe_direction_coated<SK>(N, rD, gl, ct_, alpha, F0, kd, u_sel, rnd1, rnd2, &go, &co);
-        if (gl) {
-            st.setS(st.S() * (go.F * go.g1w));
-            gs.pb = go.pb;
-            if (!(go.wz > 0.0f)) sm.dead = true;
-        }
-        if (ct_) {
-            st.setS(st.S() * co.g);
-            gs.pb = co.pb;
-            if (!(co.wz > 0.0f && co.pb > 0.0f)) sm.dead = true;
-        }
-        return d;
-    }
-
     // GLOSSY: p_b of the unit direction w at the type-4 vertex with normal N reached along rD, and the factor_S its own update with w
-    // would give -- through glossy_pdf, as the sampled direction's (lobe_direction_glossy)
+    // would give -- through glossy_pdf, as the sampled direction's (lobe_direction_rough)
     PT_DEV float glossy_light(const pt_material* __restrict__ m, f3 N, f3 rD, f3 w, f3 fS, f3* fs) const {
         f3 Z, X;
         tangent_frame(N, &Z, &X);
@@ -266,31 +175,63 @@ struct NeeHook {
         *fs = fS * glossy_weight(alpha, ldf3(m->F0), o, h, wl);
         return pb;
     }
-    // GLOSSY: the sampled direction (before normalisation) of a lobe vertex of either kind; a type-4 vertex (gl) also multiplies
-    // factor_S by g(w), keeps its p_b and ends the path unless w.z > 0
+    // GLOSSY: the sampled direction (before normalisation) of a lobe vertex of any kind (lobe_direction_rough).  A rough vertex also
+    // multiplies a factor by g(w), keeps its p_b and may end the path: the metal (gl) factor_S, unless w.z > 0; COAT: the coated vertex (ct_)
+    // factor_S, unless w.z > 0 and p_b > 0; FROST: the frosted one (fr_) factor_R -- a reflection unless w.z > 0, while a refraction toggles
+    // `inside`, leaves along -Ng (*side) and ends the path unless w.z < 0.  The lobe of a coated or frosted vertex is chosen by a hash value
+    // keyed like the environment's selection, dimension 1 (a vertex has one type)
     template <bool SK, class ST>
-    PT_DEV f3 lobe_vertex(ST& st, const pt_material* __restrict__ m, bool gl, f3 N, f3 rD, float rnd1, float rnd2) {
-        float alpha = 1.0f;
-        f3 F0 = mk(0.f, 0.f, 0.f);
-        if (gl) {
-            alpha = m->n;          // (the device copy of a type-4 material carries its roughness there: pt_upload_materials)
-            F0 = ldf3(m->F0);
+    PT_DEV f3 lobe_vertex(ST& st, const pt_material* __restrict__ m, bool gl, bool ct_, bool fr_, f3 N, f3 rD, float rnd1, float rnd2, bool& inside,
+                          float* side) {
+        float alpha = 1.0f, u_sel = 0.0f, eta = 1.0f;
+        f3 F0 = mk(0.f, 0.f, 0.f), kd = F0;
+        if constexpr (FROST) {
+            if (gl || ct_) alpha = m->n;   // (the device copy of a type-4 or type-5 material carries its roughness there: pt_upload_materials)
+            if (fr_) {
+                alpha = m->shininess;      // (that of a type-6 material here; its n is the index of refraction)
+                eta = m->n;
+                if (inside) eta = 1.0f / eta;
+            }
+            if (gl || ct_ || fr_) F0 = ldf3(m->F0);
+            if (ct_) kd = albedo(m);
+            if (ct_ || fr_) u_sel = nee_unit(nee_rand(~key, k, 1));
+        } else {                           // (the same without fr_, in the order the instances without FROST were compiled from)
+            if (gl || ct_) {
+                alpha = m->n;
+                F0 = ldf3(m->F0);
+            }
+            if (ct_) {
+                kd = albedo(m);
+                u_sel = nee_unit(nee_rand(~key, k, 1));
+            }
         }
         GlossyOut go;
-        const f3 d = lobe_direction_glossy<SK>(N, rD, gl, alpha, F0, rnd1, rnd2, &go);
+        CoatedOut co;
+        FrostedOut fo;
+        const f3 d = lobe_direction_rough<SK, COAT>(N, rD, gl, ct_, fr_, alpha, F0, kd, eta, u_sel, rnd1, rnd2, &go, &co, &fo);
         if (gl) {
             st.setS(st.S() * (go.F * go.g1w));
             gs.pb = go.pb;
             if (!(go.wz > 0.0f)) sm.dead = true;
         }
+        if constexpr (COAT)
+            if (ct_) {
+                st.setS(st.S() * co.g);
+                gs.pb = co.pb;
+                if (!(co.wz > 0.0f && co.pb > 0.0f)) sm.dead = true;
+            }
+        if constexpr (FROST)
+            if (fr_) {
+                st.setR(st.R() * fo.g);
+                gs.pb = fo.pb;
+                if (!fo.refl) {
+                    inside = !inside;
+                    *side = -0.001f;
+                }
+                if (!(fo.refl ? fo.wz > 0.0f : fo.wz < 0.0f)) sm.dead = true;
+            }
         return d;
     }
-    // GLOSSY: end_vertex; a cosine lobe's p_b of the new direction rD is what emitter_weight / miss would compute from Nprev
-    PT_DEV void end_vertex_glossy(bool lobe, bool gl, f3 N, f3 rD) {
-        after_lobe = lobe;
-        if (lobe && !gl) gs.pb = max0(dot3(N, rD)) * kInvPi;
-    }
-
     // the albedo of the current type-0 vertex: the material's kd, or under TEX what shading_attributes_at left
     PT_DEV f3 albedo(const pt_material* __restrict__ m) const {
         if constexpr (TEX) return tx.kd;
@@ -334,9 +275,12 @@ struct NeeHook {
         sm.flip = dot3(rD, N) > 0.0f;      // shade_hit's flip
         return shading_normal(sm.vn, tris, ti, rD, hp, N, Ng);
     }
-    // SMOOTH: a lobe vertex whose sampled direction (before normalisation) is not above the geometric surface ends the path
-    PT_DEV void leaves_surface(bool lobe, f3 dnew) {
-        if (lobe && dot3(dnew, geo(dnew)) <= 0.0f) sm.dead = true;
+    // SMOOTH: a lobe vertex whose sampled direction (before normalisation) is not above the geometric surface ends the path; FROST: a refracted
+    // one (through) that is not below it
+    PT_DEV void leaves_surface(bool lobe, bool through, f3 dnew) {
+        if (!lobe) return;
+        const float g = dot3(dnew, geo(dnew));
+        if (FROST && through ? g >= 0.0f : g <= 0.0f) sm.dead = true;
     }
     // SMOOTH: the mirror / dielectric vertex of shade_hit evaluated with Ns; if the direction it picks is on the wrong geometric side
     // (a reflection not above, a refraction not below the surface), once more with Ng and the same LCG value, and that stands
@@ -397,26 +341,14 @@ struct NeeHook {
         if (!mis) return 0.0f;
         float pb;
         if constexpr (GLOSSY) pb = gs.pb;
-        else pb = max0(dot3(Nprev, rD)) * kInvPi;
+        else pb = max0(dot3(Nprev, rD)) * kOneOverPi;
         const float pl = pa * (t * t) / inten;
         const float rr = pl / pb;          // pb = 0: rr = inf, weight 0
         return 1.0f / fmaf_(rr, rr, 1.0f);
     }
 
-    // a point y on a light, the bracket an emitter hit at y on segment k + 1 would add, for the lobe vertex hp (normal N)
-    // (TWIN: the triangle branch and the tail of light_sample_env below restate this body, so that k_nee's code stays what it was;
-    // a change to one belongs in the other)
-    // (rD: the direction the vertex was reached along; only the GLOSSY instances pass and read it.  shade_hit keeps the six-argument call
-    // for every other hook, so that nothing about the existing instances' calls changes)
-    // (ins: the path is inside a dielectric; only the FROST instances pass and read it)
-    PT_DEV void light_sample(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD = mk(0.f, 0.f, 0.f),
-                             bool ins = false) {
-        if (!nee || k + 1 >= p.iterations) return;
-        if constexpr (ENV) {
-            light_sample_env(st, p, m, type, N, hp, rD, ins);
-            return;
-        }
-        const float u0 = nee_unit(nee_rand(key, k, 0)), u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
+    // the light table's triangle that u0 draws (returned), *y the point on it that (u1, u2) draw and *Ny its normal
+    PT_DEV int light_point(const RenderParams& p, float u0, float u1, float u2, f3* y, f3* Ny) const {
         int lo = 0, hi = lt.n - 1;        // first light with cdf > u0
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
@@ -425,20 +357,28 @@ struct NeeHook {
         }
         const int li = lt.tri[lo];
         const float4 a = p.tris[li * 3], b = p.tris[li * 3 + 1], cc = p.tris[li * 3 + 2];
-        const f3 v1 = mk(a.x, a.y, a.z), v2 = mk(a.w, b.x, b.y), v3 = mk(b.z, b.w, cc.x), Ny = mk(cc.y, cc.z, cc.w);
+        const f3 v1 = mk(a.x, a.y, a.z), v2 = mk(a.w, b.x, b.y), v3 = mk(b.z, b.w, cc.x);
+        *Ny = mk(cc.y, cc.z, cc.w);
         const float su = __builtin_sqrtf(u1);
-        const f3 y = madd(v3 - v1, su * (1.0f - u2), madd(v2 - v1, u2 * su, v1));
-        const f3 o = madd(geo(N), 0.001f, hp);
+        *y = madd(v3 - v1, su * (1.0f - u2), madd(v2 - v1, u2 * su, v1));
+        return li;
+    }
+    // that point seen from o: the unit direction to it (returned), *r2 and *r the squared distance and the distance, *cosy the emitter's cosine
+    PT_DEV static f3 light_direction(f3 o, f3 y, f3 Ny, float* r2, float* r, float* cosy) {
         const f3 d = y - o;
-        const float r2 = dot3(d, d);
-        const float r = __builtin_sqrtf(r2);
-        const f3 w = mk(d.x / r, d.y / r, d.z / r);
-        const float cosx = dot3(N, w), cosy = __builtin_fabsf(dot3(w, Ny));
-        const float pl = lt.pdf_area[li] * r2 / cosy;
-        if (!(cosx > 0.0f && cosy > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
-        if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // the sample must be above the geometric surface too
-        if (shadow_hit<MODE>(sv, o, w, r * 1.0001f, stk, wc) != li) return;
-        float pb = cosx * kInvPi;
+        *r2 = dot3(d, d);
+        *r = __builtin_sqrtf(*r2);
+        const f3 w = mk(d.x / *r, d.y / *r, d.z / *r);
+        *cosy = __builtin_fabsf(dot3(w, Ny));
+        return w;
+    }
+    // what an unoccluded light sample adds: the bracket an emitter hit (or, ENV, a miss) along w on segment k + 1 would add, for the lobe
+    // vertex hp (normal N, cosx = N.w, reached along rD; ins: inside a dielectric).  pl: the sample's p_l; g: the emitter's cosine (1 for the
+    // sky); e: its radiance with ENV (the sky's texel or the triangle's emission, which light_sample_env has before the traversal).  Without ENV
+    // e is not read: the emission of triangle li is loaded here, after the traversal, where those instances always read it
+    PT_DEV void light_add(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins, f3 w, float cosx,
+                          float pl, float g, int li, f3 e) const {
+        float pb = cosx * kOneOverPi;
         f3 fs = st.S();
         if constexpr (GLOSSY)
             if (type == 4) {
@@ -469,13 +409,36 @@ struct NeeHook {
             }
             fb = fb * (ldf3(m->ks) * pw);
         }
-        const f3 e = ((ldf3(p.mats[p.meta[li].mati].emission) * (fl + fb)) * fs) * fr;
-        if (wl < __builtin_inff()) st.setC(madd(e, cosy * wl, st.C()));
+        if constexpr (!ENV) e = ldf3(p.mats[p.meta[li].mati].emission);
+        e = ((e * (fl + fb)) * fs) * fr;
+        if (wl < __builtin_inff()) st.setC(madd(e, g * wl, st.C()));
+    }
+
+    // a point y on a light, the bracket an emitter hit at y on segment k + 1 would add, for the lobe vertex hp (normal N)
+    // (rD: the direction the vertex was reached along, read for a rough vertex; ins: the path is inside a dielectric, read for a type-6 one)
+    PT_DEV void light_sample(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins) {
+        if (!nee || k + 1 >= p.iterations) return;
+        if constexpr (ENV) {
+            light_sample_env(st, p, m, type, N, hp, rD, ins);
+            return;
+        }
+        const float u0 = nee_unit(nee_rand(key, k, 0)), u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
+        f3 y, Ny;
+        float r2, r, cosy;
+        const int li = light_point(p, u0, u1, u2, &y, &Ny);
+        const f3 o = madd(geo(N), 0.001f, hp);
+        const f3 w = light_direction(o, y, Ny, &r2, &r, &cosy);
+        const float cosx = dot3(N, w);
+        const float pl = lt.pdf_area[li] * r2 / cosy;
+        if (!(cosx > 0.0f && cosy > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
+        if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // the sample must be above the geometric surface too
+        if (shadow_hit<MODE>(sv, o, w, r * 1.0001f, stk, wc) != li) return;
+        light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, cosy, li, mk(0.f, 0.f, 0.f));
     }
 
     // ENV: the sky with probability P_env (u_sel, keyed with ~key), else a light of the table with its pdf times 1 - P_env.  Both
     // branches only produce the shadow ray and what it would add; the traversal and the weighting are shared, so a wave that holds
-    // both kinds of sample runs one traversal.  (TWIN: the triangle branch and the tail restate light_sample above.)
+    // both kinds of sample runs one traversal
     PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins) {
         const EnvView& ev = env.v;
         const float u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
@@ -517,65 +480,19 @@ struct NeeHook {
             want = -1;
         } else {
             if (lt.n <= 0) return;            // (P_env is 1 then: not reached)
-            const float u0 = nee_unit(nee_rand(key, k, 0));
-            int lo = 0, hi = lt.n - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (lt.cdf[mid] > u0) hi = mid;
-                else lo = mid + 1;
-            }
-            const int li = lt.tri[lo];
-            const float4 a = p.tris[li * 3], b = p.tris[li * 3 + 1], cc = p.tris[li * 3 + 2];
-            const f3 v1 = mk(a.x, a.y, a.z), v2 = mk(a.w, b.x, b.y), v3 = mk(b.z, b.w, cc.x), Ny = mk(cc.y, cc.z, cc.w);
-            const float su = __builtin_sqrtf(u1);
-            const f3 y = madd(v3 - v1, su * (1.0f - u2), madd(v2 - v1, u2 * su, v1));
-            const f3 d = y - o;
-            const float r2 = dot3(d, d);
-            const float r = __builtin_sqrtf(r2);
-            w = mk(d.x / r, d.y / r, d.z / r);
-            g = __builtin_fabsf(dot3(w, Ny));
-            pl = (lt.pdf_area[li] * (1.0f - ev.p_env)) * r2 / g;       // g = 0: inf or NaN, rejected below
-            e = ldf3(p.mats[p.meta[li].mati].emission);
+            f3 y, Ny;
+            float r2, r;
+            want = light_point(p, nee_unit(nee_rand(key, k, 0)), u1, u2, &y, &Ny);
+            w = light_direction(o, y, Ny, &r2, &r, &g);
+            pl = (lt.pdf_area[want] * (1.0f - ev.p_env)) * r2 / g;     // g = 0: inf or NaN, rejected below
+            e = ldf3(p.mats[p.meta[want].mati].emission);
             limit = r * 1.0001f;
-            want = li;
         }
         const float cosx = dot3(N, w);
         if (!(cosx > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
         if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // as in light_sample
         if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
-        float pb = cosx * kInvPi;
-        f3 fs = st.S();
-        if constexpr (GLOSSY)
-            if (type == 4) {
-                pb = glossy_light(m, N, rD, w, fs, &fs);
-                if (!(pb > 0.0f)) return;      // no density (or a half vector that cannot be normalised): the sample adds nothing
-            }
-        if constexpr (COAT)
-            if (type == 5) {
-                pb = coated_light(m, N, rD, w, fs, &fs);
-                if (!(pb > 0.0f)) return;
-            }
-        f3 fr = st.R();
-        if constexpr (FROST)
-            if (type == 6) {
-                pb = frosted_light(m, N, rD, w, ins, fr, &fr);
-                if (!(pb > 0.0f)) return;
-            }
-        const float q = pb / pl;
-        const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
-        f3 fl = st.L(), fb = st.B();
-        if (type == 0) {           // as in light_sample
-            fl = fl * (albedo(m) * cosx);
-            float pw = 1.0f;
-            if (!m->_pad) {
-                const f3 view = normalize3(eye - hp);
-                const f3 halfway = normalize3(view + w);
-                pw = spec_pow<false>(max0(dot3(N, halfway)), m->shininess);
-            }
-            fb = fb * (ldf3(m->ks) * pw);
-        }
-        e = ((e * (fl + fb)) * fs) * fr;
-        if (wl < __builtin_inff()) st.setC(madd(e, g * wl, st.C()));
+        light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e);
     }
 
     // ENV: a miss on segment kk along rD (the path ends there)
@@ -595,7 +512,7 @@ struct NeeHook {
             if (mis) {
                 float pb;
                 if constexpr (GLOSSY) pb = gs.pb;
-                else pb = max0(dot3(Nprev, rD)) * kInvPi;
+                else pb = max0(dot3(Nprev, rD)) * kOneOverPi;
                 const float rr = pl / pb;      // pb = 0: rr = inf, weight 0
                 wb = 1.0f / fmaf_(rr, rr, 1.0f);
             } else {
@@ -605,9 +522,15 @@ struct NeeHook {
         st.setC(madd(((e * (st.L() + st.B())) * st.S()) * st.R(), wb, st.C()));      // prog.cl:371-373
     }
 
-    PT_DEV void end_vertex(bool lobe, f3 N) {
+    // the vertex ends (rD: the new direction; rough: the lobe vertex kept its own p_b).  GLOSSY: a cosine lobe's p_b of rD is what emitter_weight
+    // / miss would compute from Nprev, which the other instances keep
+    PT_DEV void end_vertex(bool lobe, bool rough, f3 N, f3 rD) {
         after_lobe = lobe;
-        Nprev = N;
+        if constexpr (GLOSSY) {
+            if (lobe && !rough) gs.pb = max0(dot3(N, rD)) * kOneOverPi;
+        } else {
+            Nprev = N;
+        }
     }
 };
 
@@ -855,74 +778,56 @@ static hipError_t launch_lanes_env_tiles_smooth(PICK pick, const RenderParams& p
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const EnvView* env, int64_t npix, int cu_count, hipStream_t stream, bool tiled, const float4* vn,
-                      const TexView* tv, bool glossy, bool coated, const LensView* lens, bool frosted) {
-    if (frosted) {     // (tv and lens are never null here; glossy, coated: the options themselves; the lens is live iff its aperture is > 0)
-        const int flags = (glossy ? 1 : 0) | (coated ? 2 : 0) | (lens->aperture > 0.0f ? 4 : 0);
-        if (tiled) {
-            const int64_t items = (int64_t)p.n_tiles * 64;
-            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_frosted<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv, flags, *lens);
-            return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_tiles_frosted<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv, flags, *lens);
-        }
-        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_frosted<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, flags, *lens, (long long)npix);
-        return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_frosted<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, flags, *lens, (long long)npix);
-    }
-    if (lens) {        // (tv is never null here; glossy, coated: the options themselves)
-        const int flags = (glossy ? 1 : 0) | (coated ? 2 : 0);
-        if (tiled) {
-            const int64_t items = (int64_t)p.n_tiles * 64;
-            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_lens<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv, flags, *lens);
-            return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_tiles_lens<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv, flags, *lens);
-        }
-        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_lens<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, flags, *lens, (long long)npix);
-        return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_lens<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, flags, *lens, (long long)npix);
-    }
-    if (coated) {      // (tv is never null here either; glossy: type 4 is live in the launch)
-        const int metal = glossy ? 1 : 0;
-        if (tiled) {
-            const int64_t items = (int64_t)p.n_tiles * 64;
-            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_coated<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv, metal);
-            return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_tiles_coated<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv, metal);
-        }
-        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_coated<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, metal, (long long)npix);
-        return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_coated<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, metal, (long long)npix);
-    }
-    if (glossy) {      // (tv is never null here: the host hands a view with uv = null when option textures is off)
-        if (tiled) {
-            const int64_t items = (int64_t)p.n_tiles * 64;
-            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_glossy<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv);
-            return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_tiles_glossy<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv);
-        }
-        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_glossy<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, (long long)npix);
-        return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_glossy<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, (long long)npix);
-    }
-    if (tv) {
-        if (tiled) {
-            const int64_t items = (int64_t)p.n_tiles * 64;
-            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_tex<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn, *tv);
-            return launch_lanes([](auto s) { return k_nee_tiles_tex<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn, *tv);
-        }
-        // (k_nee_env_tex needs 3 VGPRs more than k_nee_env_smooth, which sits at the 128-VGPR cap of a 1,024-thread workgroup: the
-        // 512-thread treelet shape of k_nee_env_tiles_smooth keeps it out of scratch)
-        if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tex<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, *tv, (long long)npix);
-        return launch_lanes([](auto s) { return k_nee_tex<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, *tv, (long long)npix);
-    }
-    if (vn) {
-        if (tiled) {
-            const int64_t items = (int64_t)p.n_tiles * 64;
-            if (env) return launch_lanes_env_tiles_smooth([](auto s) { return k_nee_env_tiles_smooth<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env, vn);
-            return launch_lanes([](auto s) { return k_nee_tiles_smooth<s.mode, s.block>; }, p, items, cu_count, stream, lt, vn);
-        }
-        if (env) return launch_lanes([](auto s) { return k_nee_env_smooth<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, vn, (long long)npix);
-        return launch_lanes([](auto s) { return k_nee_smooth<s.mode, s.block>; }, p, npix, cu_count, stream, lt, vn, (long long)npix);
-    }
-    if (tiled) {
-        const int64_t items = (int64_t)p.n_tiles * 64;
-        if (env) return launch_lanes([](auto s) { return k_nee_env_tiles<s.mode, s.block>; }, p, items, cu_count, stream, lt, *env);
-        return launch_lanes([](auto s) { return k_nee_tiles<s.mode, s.block>; }, p, items, cu_count, stream, lt);
-    }
-    if (env) return launch_lanes([](auto s) { return k_nee_env<s.mode, s.block>; }, p, npix, cu_count, stream, lt, *env, (long long)npix);
-    return launch_lanes([](auto s) { return k_nee<s.mode, s.block>; }, p, npix, cu_count, stream, lt, (long long)npix);
+// one kernel of a family: WIDE picks the 512-thread treelet shape above.  launch_lanes_t keys its static LdsMark on the type of `pick`, so every
+// kernel arrives through a lambda of its own (NEE_PICK)
+template <bool WIDE, class PICK, class... A>
+static hipError_t launch_nee_kernel(PICK pick, const RenderParams& p, int64_t n, int cu_count, hipStream_t stream, A... args) {
+    if constexpr (WIDE) return launch_lanes_env_tiles_smooth(pick, p, n, cu_count, stream, args...);
+    else return launch_lanes(pick, p, n, cu_count, stream, args...);
 }
+// the four kernels of one family -- k, its _env, _tiles and _env_tiles forms -- with the family's own arguments `a` between the environment and
+// the pixel count.  SHAPES: which of the four launch in the 512-thread treelet shape (launch_lanes_env_tiles_smooth)
+enum : int { kWidePlain = 1, kWideEnv = 2, kWideTiles = 4, kWideEnvTiles = 8, kWideAll = 15 };
+template <int SHAPES, class K, class KE, class KT, class KET, class... A>
+static hipError_t launch_nee_family(K k, KE ke, KT kt, KET ket, const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count,
+                                    hipStream_t stream, A... a) {
+    if (nl.tiled) {
+        const int64_t items = (int64_t)p.n_tiles * 64;
+        if (nl.env) return launch_nee_kernel<(SHAPES & kWideEnvTiles) != 0>(ket, p, items, cu_count, stream, lt, *nl.env, a...);
+        return launch_nee_kernel<(SHAPES & kWideTiles) != 0>(kt, p, items, cu_count, stream, lt, a...);
+    }
+    if (nl.env) return launch_nee_kernel<(SHAPES & kWideEnv) != 0>(ke, p, npix, cu_count, stream, lt, *nl.env, a..., (long long)npix);
+    return launch_nee_kernel<(SHAPES & kWidePlain) != 0>(k, p, npix, cu_count, stream, lt, a..., (long long)npix);
+}
+#define NEE_PICK(K) [](auto s) { return K<s.mode, s.block>; }
+
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+    switch (nl.family) {
+    case kNeePlain:
+        return launch_nee_family<0>(NEE_PICK(k_nee), NEE_PICK(k_nee_env), NEE_PICK(k_nee_tiles), NEE_PICK(k_nee_env_tiles), p, lt, nl, npix, cu_count, stream);
+    case kNeeSmooth:
+        return launch_nee_family<kWideEnvTiles>(NEE_PICK(k_nee_smooth), NEE_PICK(k_nee_env_smooth), NEE_PICK(k_nee_tiles_smooth), NEE_PICK(k_nee_env_tiles_smooth), p, lt, nl, npix,
+                                    cu_count, stream, nl.vn);
+    // (k_nee_env_tex needs 3 VGPRs more than k_nee_env_smooth, which sits at the 128-VGPR cap of a 1,024-thread workgroup: the 512-thread
+    // treelet shape of k_nee_env_tiles_smooth keeps it out of scratch)
+    case kNeeTex:
+        return launch_nee_family<kWideEnv | kWideEnvTiles>(NEE_PICK(k_nee_tex), NEE_PICK(k_nee_env_tex), NEE_PICK(k_nee_tiles_tex), NEE_PICK(k_nee_env_tiles_tex), p, lt, nl, npix, cu_count,
+                                        stream, nl.vn, nl.tv);
+    case kNeeGlossy:
+        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_glossy), NEE_PICK(k_nee_env_glossy), NEE_PICK(k_nee_tiles_glossy), NEE_PICK(k_nee_env_tiles_glossy), p, lt, nl, npix,
+                                     cu_count, stream, nl.vn, nl.tv);
+    case kNeeCoated:
+        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_coated), NEE_PICK(k_nee_env_coated), NEE_PICK(k_nee_tiles_coated), NEE_PICK(k_nee_env_tiles_coated), p, lt, nl, npix,
+                                     cu_count, stream, nl.vn, nl.tv, nl.flags & 1);
+    case kNeeLens:
+        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_lens), NEE_PICK(k_nee_env_lens), NEE_PICK(k_nee_tiles_lens), NEE_PICK(k_nee_env_tiles_lens), p, lt, nl, npix, cu_count,
+                                     stream, nl.vn, nl.tv, nl.flags & 3, nl.lens);
+    case kNeeFrosted:
+        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_frosted), NEE_PICK(k_nee_env_frosted), NEE_PICK(k_nee_tiles_frosted), NEE_PICK(k_nee_env_tiles_frosted), p, lt, nl, npix,
+                                     cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens);
+    }
+    return hipErrorInvalidValue;
+}
+#undef NEE_PICK
 
 }  // namespace ptamd
