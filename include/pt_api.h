@@ -270,6 +270,71 @@ int pt_env_lookup(int32_t w, int32_t h, float yaw_degrees, const float dir[3], i
  * Any pointer may be NULL.  PT_EINVAL when no environment is set */
 int pt_debug_environment(pt_context* ctx, int32_t* w, int32_t* h, float* row_cdf, float* col_cdf, float* pdf, int64_t cap, float* P_env);
 
+/* ---- point, spot and directional lights for pt_render_nee (new: opt-in with pt_set_lights; the reference lights with emitters only) ----
+ * A set of analytic ("delta") lights lights the scene through light samples only.  Only pt_render_nee and the NEE path of
+ * pt_render_adaptive_ex draw them.  Without a set -- never set, cleared, count 0, or every light black -- every path launches the kernels
+ * it launched before and computes what it computed before, bit for bit.  Everything below is stated in the reference's integrand, as the
+ * estimator of pt_render_nee is: p_b and the primed factors are what a light sample of that block computes for each vertex type (0, with
+ * a texture; 3; 4; 5; 6 on the reflection lobe only).
+ * Set: a light's selection weight is `weight`, or intensity.r + intensity.g + intensity.b when weight is 0; a light whose weight is
+ *   still 0 (black) stays in the set but is never picked.  The host normalises direction in double and stores floats; the cdf over the
+ *   set is float, proportional to the running sum of the weights (summed and normalised in double; 1 from the last pickable light on);
+ *   P_light(j) = (ceil(cdf[j] 2^24) - ceil(cdf[j-1] 2^24)) / 2^24, the share of the 2^24 values of u0 that pick light j (the counting
+ *   rule of the light table).  A set has a pickable light iff some P_light > 0.
+ * Selection, at a lobe vertex x of segment k with k + 1 < iterations, strategies LIGHT and MIS, while the set has a pickable light:
+ *   u_ana = pt_nee_rand(~S, k, 2) >> 8 times 2^-24 (dimensions 0 and 1 of the complemented key are the sky's and the coat / frost lobe's
+ *   selectors); u_ana < P_ana: the analytic set; else the sky / light-table sample as before, its p_l times 1 - P_ana (in the weights
+ *   W_b of emitter hits and sky misses after a lobe vertex too).
+ *   P_ana = ceil(select 2^24) / 2^24; 1 when the light table is empty and no environment with a distribution is set; 0 when no light
+ *   is pickable.
+ *   Inside the set u0 = pt_nee_rand(S, k, 0) (the triangle draw, which this branch does not use) picks the first light with cdf > u0.
+ * Sample: o = x + 0.001 Ng' (the origin every light sample uses).
+ *   POINT: d = P - o, r^2 = d.d, rejected unless r^2 > 0 and finite; r = sqrtf(r^2), w = d / r; visible iff no triangle is hit from o
+ *     along w nearer than exactly r.
+ *   DIRECTIONAL: w = -direction (unit); visible iff no triangle is hit from o along w at any distance.
+ *   Rejected unless N.w > 0 (under "smooth_normals": unless it is also above the geometric surface).
+ *   Cone: c = dot(-w, axis); 1 if c >= cos_inner; else 0 if c <= cos_outer; else s^2 (3 - 2 s), s = (c - cos_outer) / (cos_inner -
+ *     cos_outer), tested in that order.  cos_outer = -1 is "no cone": direction and cos_inner are then not read (the factor is 1), and a
+ *     directional light has none.
+ *   Adds intensity cone (fL' + fB') fS' fR' p_b(w) / (P_ana P_light d), d = r^2 (POINT) or 1 (DIRECTIONAL): the weight of a delta-light
+ *     sample is p_b / p_l in PT_NEE_LIGHT and in PT_NEE_MIS, because no other strategy can find the light.
+ *   POINT intensity is radiant intensity I (what an emitter's E x area x |cos_y| is at a distance), DIRECTIONAL intensity the irradiance
+ *   E_perp on a surface facing the light.  In the reference's integrand a diffuse floor facing the light shows kd E_perp / pi, and
+ *   kd I cos^2 / (pi r^2) under a point light (the second cosine is p_b's).
+ * No LCG draw is added: rnds and rays after a frame are pt_render's.  The lights are not visible to the camera or through specular
+ * chains; the guides, the denoisers, the variance read-out and temporal accumulation are not affected.
+ * While a set with a pickable light is held, pt_render, pt_generate_rays, pt_trace_rays, pt_render_adaptive, pt_render_nee with
+ * PT_NEE_BSDF (which is pt_render bit for bit and would drop the lights) and pt_render_adaptive_ex with PT_ADAPT_PATH_RENDER or with
+ * strategy PT_NEE_BSDF return PT_EINVAL naming pt_clear_lights, checked before the device.
+ * The set lives in the context: pt_upload_triangles / pt_upload_materials keep it (P_ana is worked out at each launch from the light
+ * table of the scene as uploaded), every rank of a tiled frame sets its own copy, a host-only context validates and stores. */
+#define PT_LIGHT_POINT 0        /* also the spot light: a point light with a cone */
+#define PT_LIGHT_DIRECTIONAL 1
+#define PT_LIGHTS_MAX 4096
+typedef struct {
+    int32_t type;
+    float position[3];          /* POINT: where it is (scene coordinates, as triangles are added) */
+    float direction[3];         /* POINT: the cone's axis, the way the light points (read only when cos_outer > -1);
+                                   DIRECTIONAL: the way the light travels.  Need not be unit, must be non-zero where read */
+    float intensity[3];         /* POINT: radiant intensity I (what an emitter's E x area x |cos| is at a distance);
+                                   DIRECTIONAL: irradiance E_perp on a surface facing the light */
+    float cos_inner, cos_outer; /* POINT: full strength inside cos_inner, nothing outside cos_outer; -1, -1 = no cone */
+    float weight;               /* selection weight; 0 = automatic: intensity r + g + b */
+} pt_light;
+typedef struct { float select; } pt_lights_params;      /* pt_lights_defaults: select = 0.5 */
+void pt_lights_defaults(pt_lights_params* p);
+/* Replaces the whole set (count == 0 is pt_clear_lights); p = NULL: the defaults.  A device context uploads the records; PT_EHIP if
+ * that fails, and the context then holds no set.  PT_EINVAL, with the set left as it was: lights NULL
+ * with count > 0, count < 0 or above PT_LIGHTS_MAX, select outside [0, 1], an unknown type, a non-finite field, a negative intensity,
+ * a negative weight, cos_inner / cos_outer not ordered -1 <= cos_outer <= cos_inner <= 1, a zero direction where it is read */
+int pt_set_lights(pt_context* ctx, const pt_light* lights, int32_t count, const pt_lights_params* p);
+int pt_clear_lights(pt_context* ctx);
+/* what the kernel samples (host data): *n = lights in the set; for the first min(cap, *n) lights, records = 16 floats each as uploaded
+ * ({position.xyz, type as int32 bits}, {axis.xyz, cos_inner}, {intensity.rgb, cos_outer}, {P_light, 0, 0, 0}; axis unit, or 0 where it is
+ * not read; cos -1, -1 for a directional light), cdf and P_light one float each; *P_ana the effective value for the scene as uploaded
+ * (the light table is built if the scene is uploaded, else taken as empty).  Any pointer but n may be NULL */
+int pt_debug_lights(pt_context* ctx, float* records, float* cdf, float* P_light, int64_t cap, int64_t* n, float* P_ana);
+
 /* ---- smooth shading from vertex normals for pt_render_nee (new: opt-in with option "smooth_normals"; the reference shades with the
  * triangle's geometric normal only) -----------
  * Authoring (host data; all of it works on a host-only context, none of it rebuilds the BVH).  Triangles are counted in add order over

@@ -122,6 +122,10 @@ public:
     // a lat-long map lighting render_nee (pt_set_environment; rgb: w x h x 3 floats, row 0 at the +y pole; p = NULL: the defaults)
     void set_environment(const float* rgb, int w, int h, const pt_environment_params* p = nullptr) { ck(pt_set_environment(ctx, rgb, w, h, p)); }
     void clear_environment() { ck(pt_clear_environment(ctx)); }
+    // point, spot and directional lights for render_nee (pt_set_lights replaces the whole set; p = NULL: the defaults).  While a pickable
+    // light is held only render_nee with PT_NEE_LIGHT / PT_NEE_MIS and the NEE path of render_adaptive render
+    void set_lights(const pt_light* lights, int32_t count, const pt_lights_params* p = nullptr) { ck(pt_set_lights(ctx, lights, count, p)); }
+    void clear_lights() { ck(pt_clear_lights(ctx)); }
     // vertex normals for smooth shading (set_option("smooth_normals", 1); render_nee only): normals = count x 9 floats, n1 n2 n3 per
     // triangle in add order starting at first_triangle; compute_vertex_normals derives them per object (obj = -1: every object)
     void set_vertex_normals(const float* normals, int64_t count, int64_t first_triangle = 0) { ck(pt_set_vertex_normals(ctx, first_triangle, count, normals)); }

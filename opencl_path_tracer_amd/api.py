@@ -52,6 +52,7 @@ EXPORTS = [
     "pt_material_roughness", "pt_debug_glossy", "pt_debug_coated", "pt_debug_frosted",
     "pt_lens_defaults", "pt_set_lens", "pt_clear_lens", "pt_focus_at", "pt_debug_lens",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
+    "pt_lights_defaults", "pt_set_lights", "pt_clear_lights", "pt_debug_lights",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
     "pt_render_aovs", "pt_read_aovs", "pt_aov_defaults", "pt_render_aovs_ex", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
@@ -143,6 +144,10 @@ def _load():
     sig("pt_clear_environment", C.c_int, vp)
     sig("pt_env_lookup", C.c_int, i32, i32, f32, fp, C.POINTER(i32), C.POINTER(i32))
     sig("pt_debug_environment", C.c_int, vp, C.POINTER(i32), C.POINTER(i32), vp, vp, vp, i64, fp)
+    sig("pt_lights_defaults", None, vp)
+    sig("pt_set_lights", C.c_int, vp, vp, i32, vp)
+    sig("pt_clear_lights", C.c_int, vp)
+    sig("pt_debug_lights", C.c_int, vp, vp, vp, vp, i64, C.POINTER(i64), fp)
     sig("pt_image_read_pfm", C.c_int, C.c_char_p, vp, i64, C.POINTER(i32), C.POINTER(i32))
     sig("pt_read_variance", C.c_int, vp, vp, i64)
     sig("pt_device_variance", vp, vp)
@@ -324,6 +329,59 @@ def environment_defaults():
     p = EnvironmentParams()
     LIB.pt_environment_defaults(C.byref(p))
     return p.as_dict()
+
+
+LIGHT_POINT, LIGHT_DIRECTIONAL, LIGHTS_MAX = 0, 1, 4096
+
+
+class Light(C.Structure):
+    """pt_light (include/pt_api.h)."""
+    _fields_ = [("type", C.c_int32), ("position", C.c_float * 3), ("direction", C.c_float * 3), ("intensity", C.c_float * 3),
+                ("cos_inner", C.c_float), ("cos_outer", C.c_float), ("weight", C.c_float)]
+
+
+class LightsParams(C.Structure):
+    """pt_lights_params (include/pt_api.h)."""
+    _fields_ = [("select", C.c_float)]
+
+
+def lights_defaults():
+    """pt_lights_defaults as a dict: select."""
+    p = LightsParams()
+    LIB.pt_lights_defaults(C.byref(p))
+    return {"select": p.select}
+
+
+def _light(ltype, position, direction, intensity, cos_inner, cos_outer, weight):
+    return Light(int(ltype), (C.c_float * 3)(*[float(v) for v in position]), (C.c_float * 3)(*[float(v) for v in direction]),
+                 (C.c_float * 3)(*[float(v) for v in intensity]), float(cos_inner), float(cos_outer), float(weight))
+
+
+def point_light(position, intensity, weight=0):
+    """An omnidirectional point light of radiant intensity `intensity` (rgb); weight 0: selected in proportion to r + g + b."""
+    return _light(LIGHT_POINT, position, (0.0, 0.0, 0.0), intensity, -1.0, -1.0, weight)
+
+
+def spot_light(position, direction, intensity, inner_degrees, outer_degrees, weight=0):
+    """A point light with a cone around `direction` (the way it points): full strength within inner_degrees of the axis, nothing
+    beyond outer_degrees, a smoothstep between."""
+    return _light(LIGHT_POINT, position, direction, intensity, np.cos(np.radians(float(inner_degrees))), np.cos(np.radians(float(outer_degrees))), weight)
+
+
+def directional_light(direction, irradiance, weight=0):
+    """A light from infinity travelling along `direction`; irradiance (rgb) is what a surface facing it receives."""
+    return _light(LIGHT_DIRECTIONAL, (0.0, 0.0, 0.0), direction, irradiance, -1.0, -1.0, weight)
+
+
+def light_from(d):
+    """A Light from its description as scenes.SceneSpec.lights holds it: dict(kind="point" | "spot" | "directional", ...) with the
+    arguments of point_light / spot_light / directional_light."""
+    d = dict(d)
+    kind = d.pop("kind")
+    make = {"point": point_light, "spot": spot_light, "directional": directional_light}
+    if kind not in make:
+        raise KeyError("a light's kind must be one of %s, not %r" % (", ".join(sorted(make)), kind))
+    return make[kind](**d)
 
 
 class LensParams(C.Structure):
@@ -749,6 +807,8 @@ class Scene:
             first += int(np.asarray(verts).shape[0])
         self.upload_Triangles()
         self.upload_Materials()
+        if getattr(spec, "lights", None):                       # optional: what set_lights takes, with spec.lights_select
+            self.set_lights(spec.lights, select=getattr(spec, "lights_select", 0.5))
         self.set_view(spec.fov, spec.yaw, spec.pitch, spec.shift)
         return self
 
@@ -872,6 +932,31 @@ class Scene:
         pdf = np.zeros((h.value, w.value), dtype=np.float32)
         self._ck(LIB.pt_debug_environment(self._h, C.byref(w), C.byref(h), _ptr(row), _ptr(col), _ptr(pdf), col.size, C.byref(pe)))
         return {"row_cdf": row, "col_cdf": col, "pdf": pdf, "P_env": float(pe.value)}
+
+    # -- point, spot and directional lights for render_nee (include/pt_api.h pins the set, the selection and the estimator)
+    def set_lights(self, lights, select=0.5):
+        """pt_set_lights: replaces the whole set with `lights` (api.point_light / spot_light / directional_light, or their descriptions
+        as light_from takes them; an empty list clears it); select = the probability a lobe vertex samples the set rather than the sky or an emitter.  While a pickable light is held
+        only render_nee ("light" / "mis") and render_adaptive(path="nee") render."""
+        lights = [l if isinstance(l, Light) else light_from(l) for l in lights]
+        arr = (Light * max(len(lights), 1))(*lights)
+        p = LightsParams(float(select))
+        self._ck(LIB.pt_set_lights(self._h, arr, len(lights), C.byref(p)))
+
+    def clear_lights(self):
+        self._ck(LIB.pt_clear_lights(self._h))
+
+    def debug_lights(self):
+        """What render_nee samples: {"records" (n, 16) float32 as uploaded ({position, type bits}, {axis, cos_inner}, {intensity,
+        cos_outer}, {P_light, 0, 0, 0}), "cdf" (n,), "P_light" (n,), "P_ana": the effective probability of choosing the set at a lobe
+        vertex of the scene as uploaded}."""
+        n, pa = C.c_int64(), C.c_float()
+        self._ck(LIB.pt_debug_lights(self._h, None, None, None, 0, C.byref(n), None))
+        rec = np.zeros((n.value, 16), dtype=np.float32)
+        cdf = np.zeros(n.value, dtype=np.float32)
+        pl = np.zeros(n.value, dtype=np.float32)
+        self._ck(LIB.pt_debug_lights(self._h, _ptr(rec), _ptr(cdf), _ptr(pl), n.value, C.byref(n), C.byref(pa)))
+        return {"records": rec, "cdf": cdf, "P_light": pl, "P_ana": float(pa.value)}
 
     # -- per-pixel variance of the mean luminance (option "moments"; include/pt_api.h pins both the fold and the read-out)
     def read_variance(self):

@@ -229,6 +229,16 @@ struct pt_context {
     // lens ray while lens_set && lens_aperture > 0 (the lens instances of k_nee); every other frame is today's launch
     bool lens_set = false;
     float lens_aperture = 0.0f, lens_focus = 1.0f;
+    // analytic lights (pt_set_lights, pt_lights.cpp; pinned in include/pt_api.h): the set as validated, and what the kernel samples -- per
+    // light a 16-float record (LightsView, pt_internal.hpp), the float cdf and P_light by the counting rule.  lights_pickable: some
+    // P_light > 0; only then do pt_render_nee and the NEE path of pt_render_adaptive_ex launch the lights instances of k_nee, and do the
+    // other paths refuse.  Device copies made by pt_set_lights
+    std::vector<pt_light> lights;
+    std::vector<float> lights_rec, lights_cdf, lights_plight;
+    float lights_select = 0.5f;
+    bool lights_pickable = false;
+    float4* d_lights_rec = nullptr;
+    float* d_lights_cdf = nullptr;
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -276,6 +286,14 @@ int light_table_ready(pt_context* ctx);                            // pt_host.cp
 float env_select(const pt_context* ctx, bool no_lights);           // pt_env.cpp: the effective P_env
 // pt_host.cpp: the light table on the device and the environment's view (*sky: a map with a distribution is set) for a launch_nee
 int nee_prepare(pt_context* ctx, int32_t strategy, NeeTable* lt, EnvView* env, bool* sky);
+// pt_lights.cpp: the effective P_ana (no_other: the light table is empty and no environment with a distribution is set)
+float lights_select(const pt_context* ctx, bool no_other);
+// a light set with a pickable light is held: only pt_render_nee (LIGHT, MIS) and the NEE path of pt_render_adaptive_ex render; the text the
+// other paths refuse with
+inline bool lights_on(const pt_context* ctx) { return ctx->lights_pickable; }
+inline std::string lights_refusal(const std::string& who) {
+    return who + ": a light set is held and only pt_render_nee with PT_NEE_LIGHT or PT_NEE_MIS samples analytic lights (pt_clear_lights removes it)";
+}
 // a lens with aperture > 0 is set: only pt_render_nee and the NEE path of pt_render_adaptive_ex render
 inline bool lens_on(const pt_context* ctx) { return ctx->lens_set && ctx->lens_aperture > 0.0f; }
 // pt_host.cpp: the packed vertex normals on the device for a smooth launch (repacked if stale); *vn = null when the option is off, unless force

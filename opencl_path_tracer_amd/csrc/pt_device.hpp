@@ -1422,7 +1422,7 @@ struct PathRegs {
 // metal of option glossy; with `coated` also type 5, the coated diffuse; with `frosted` (it has `lens`) also type 6, the rough dielectric,
 // whose refracted direction leaves through the surface, so the vertex may toggle `inside` and step off along -Ng.  The hook's lobe_vertex()
 // draws the direction (lobe_direction_rough() above, in place of diffuse_direction) and keeps the vertex's p_b; whether type 4 or 5 is
-// live in a launch is the hook's answer (metal_live(), coat_live()).  The preview colour, light_sample, lobe_vertex, leaves_surface and end_vertex are
+// live in a launch is the hook's answer (metal_live(), coat_live(); with `lights` also type 6: frost_live()).  The preview colour, light_sample, lobe_vertex, leaves_surface and end_vertex are
 // one call each for every hook: what a hook's flags do not cover in their arguments it does not read.
 struct NoShadeHook {
     static constexpr bool active = false;
@@ -1432,6 +1432,7 @@ struct NoShadeHook {
     static constexpr bool coated = false;
     static constexpr bool lens = false;
     static constexpr bool frosted = false;
+    static constexpr bool lights = false;
 };
 
 // The interpolated shading normal of a hit at hp = madd(D, t, P) on packed triangle ti (include/pt_api.h pins every operation): vn =
@@ -1597,6 +1598,7 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     if constexpr (HOOK::frosted) {
         static_assert(HOOK::lens, "the frosted instances are built on the lens ones");
         fr = type == 6;
+        if constexpr (HOOK::lights) fr = fr && hook->frost_live();          // (the lights instances serve option frosted = 0 too)
         lobe = lobe || fr;
     }
     f3 dnew = rD;

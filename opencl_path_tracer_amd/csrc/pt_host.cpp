@@ -255,6 +255,8 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->d_env_texels) (void)hipFree(ctx->d_env_texels);
         if (ctx->d_env_row_cdf) (void)hipFree(ctx->d_env_row_cdf);
         if (ctx->d_env_col_cdf) (void)hipFree(ctx->d_env_col_cdf);
+        if (ctx->d_lights_rec) (void)hipFree(ctx->d_lights_rec);
+        if (ctx->d_lights_cdf) (void)hipFree(ctx->d_lights_cdf);
         if (ctx->d_wf_state) (void)hipFree(ctx->d_wf_state);
         if (ctx->d_wf_queues) (void)hipFree(ctx->d_wf_queues);
         if (ctx->d_wf_counters) (void)hipFree(ctx->d_wf_counters);
@@ -913,14 +915,20 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
     if ((rc = smooth_prepare(ctx, &nl->vn)) != PT_OK) return rc;
     if ((rc = texture_prepare(ctx, &nl->tv)) != PT_OK) return rc;
     const bool coated = ctx->coated && ctx->coated_mats, glossy = ctx->glossy && (ctx->glossy_mats || coated);
-    nl->family = ctx->frosted && ctx->frosted_mats ? kNeeFrosted
+    const bool frosted = ctx->frosted && ctx->frosted_mats;
+    if (lights_on(ctx)) {              // (after nee_prepare: the light table is the uploaded scene's)
+        const bool no_other = ctx->nee_tri.empty() && !(ctx->env_set && ctx->env_dist);
+        nl->lights = LightsView{ctx->d_lights_rec, ctx->d_lights_cdf, (int32_t)ctx->lights.size(), lights_select(ctx, no_other)};
+    }
+    nl->family = lights_on(ctx)                    ? kNeeLights
+                 : frosted                         ? kNeeFrosted
                  : lens_on(ctx)                    ? kNeeLens
                  : coated                          ? kNeeCoated
                  : glossy                          ? kNeeGlossy
                  : nl->tv.uv                       ? kNeeTex
                  : nl->vn                          ? kNeeSmooth
                                                    : kNeePlain;
-    nl->flags = (ctx->glossy ? 1 : 0) | (ctx->coated ? 2 : 0) | (lens_on(ctx) ? 4 : 0);
+    nl->flags = (ctx->glossy ? 1 : 0) | (ctx->coated ? 2 : 0) | (lens_on(ctx) ? 4 : 0) | (frosted ? 8 : 0);
     return PT_OK;
 }
 }  // namespace ptamd
@@ -929,6 +937,7 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     if (!ctx) return PT_EINVAL;
     if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "pt_render_nee: iterations/nsamples must be >= 0");
     if (strategy < PT_NEE_BSDF || strategy > PT_NEE_MIS) return fail(ctx, PT_EINVAL, "pt_render_nee: strategy must be PT_NEE_BSDF, PT_NEE_LIGHT or PT_NEE_MIS");
+    if (strategy == PT_NEE_BSDF && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_render_nee with PT_NEE_BSDF"));
     PT_NEED_DEVICE(ctx);
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;

@@ -426,6 +426,15 @@ struct LensView {
     float aperture, focus;
     float f[3], Rh[3], Uh[3];
 };
+// the analytic lights of pt_render_nee (pt_set_lights; pinned in include/pt_api.h).  A record is four float4s:
+//   { position.xyz, bits(type) }  { axis.xyz, cos_inner }  { intensity.rgb, cos_outer }  { P_light, 0, 0, 0 }
+// axis: unit, the way the light points (POINT with a cone) or travels (DIRECTIONAL); zero for a point light without a cone
+struct LightsView {
+    const float4* rec;           // [n][4]
+    const float* cdf;            // [n], proportional to the selection weights; the last entry is 1
+    int32_t n;
+    float p_ana;                 // the effective P_ana of the launch (a multiple of 2^-24)
+};
 // normalize3 of pt_device.hpp on the host: dot3's fma placement, then a * (1.0f / sqrtf(l2)), IEEE
 inline void lens_normalize(const float* a, float* out) {
     const float l2 = __builtin_fmaf(a[2], a[2], __builtin_fmaf(a[1], a[1], a[0] * a[0]));
@@ -449,7 +458,7 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
                               const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream);
 // one launch of the NEE kernels (pt_nee.hip), as nee_launch_for (pt_context.hpp) fills it from the context.  Each family is the one before it
 // with one more feature compiled in; a launch takes the first family that covers what the frame needs
-enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted };
+enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights };
 struct NeeLaunch {
     const EnvView* env;          // null: the instances without an environment
     bool tiled;                  // the rounds of pt_render_adaptive_ex: k_nee*_tiles over the p.n_tiles 8x8 frame tiles of p.tile_list (null: the
@@ -458,11 +467,14 @@ struct NeeLaunch {
                                  // triangle has vertex normals" (the pinned rule "no vertex normals: Ns = Ng, the same bits" makes that exact)
     TexView tv;                  // uv == null: option textures is off (no lookup in the families from kNeeGlossy on); not read below kNeeTex
     int family;                  // NeeFamily.  An option whose material type is not uploaded asks for nothing; a lens with aperture > 0 takes
-                                 // kNeeLens whatever the options say; option frosted with a type-6 material takes kNeeFrosted, lens or not
+                                 // kNeeLens whatever the options say; option frosted with a type-6 material takes kNeeFrosted, lens or not;
+                                 // a light set with a pickable light (pt_set_lights) takes kNeeLights whatever else is on
     int flags;                   // the options themselves, for the families in which they are run-time fields: bit 0 glossy (type 4 is live;
                                  // read from kNeeCoated on), bit 1 coated (type 5 is live; from kNeeLens on), bit 2 a lens with aperture > 0 is
-                                 // set (kNeeFrosted; else each sample starts on the pinhole ray)
+                                 // set (from kNeeFrosted on; else each sample starts on the pinhole ray), bit 3 frosted with a type-6 material
+                                 // uploaded (type 6 is live; read by kNeeLights)
     LensView lens;               // read from kNeeLens on
+    LightsView lights;           // read by kNeeLights
 };
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
 // thin lens (pt_lens.hip): pt_debug_lens's kernel, {gid, S} in and 6 floats out per item; pt_focus_at's, the axial distance of pixel gid's

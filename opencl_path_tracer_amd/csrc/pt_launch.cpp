@@ -366,6 +366,7 @@ static void launch_cfg(pt_context* ctx, const RenderParams& p, LaunchConfig* lc)
 }
 
 int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
+    if (ctx && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_generate_rays"));
     if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_generate_rays: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_generate_rays: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
     if (ctx && ctx->coated) return fail(ctx, PT_EINVAL, "pt_generate_rays: option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
@@ -384,6 +385,7 @@ int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
 }
 
 int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t current_sample) {
+    if (ctx && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_trace_rays"));
     if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_trace_rays: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_trace_rays: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
     if (ctx && ctx->coated) return fail(ctx, PT_EINVAL, "pt_trace_rays: option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
@@ -590,6 +592,7 @@ static int launch_megakernel(pt_context* ctx, RenderParams& p, const int32_t* ti
 }
 
 int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples) {
+    if (ctx && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_render"));
     if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_render: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_render: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
     if (ctx && ctx->coated) return fail(ctx, PT_EINVAL, "pt_render: option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
@@ -661,6 +664,8 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
                   " tiles does not fit the 31-bit work-item counter of one launch";
     }
     if (!why.empty()) return fail(ctx, PT_EINVAL, who + ": " + why);
+    if (lights_on(ctx) && (!nee || ap->strategy == PT_NEE_BSDF))
+        return fail(ctx, PT_EINVAL, lights_refusal(nee ? who + " with strategy PT_NEE_BSDF" : who));
     if (!nee && ctx->frosted) return fail(ctx, PT_EINVAL, who + ": option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (!nee && lens_on(ctx)) return fail(ctx, PT_EINVAL, who + ": a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
     if (!nee && ctx->coated) return fail(ctx, PT_EINVAL, who + ": option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");

@@ -17,8 +17,10 @@
 //   COAT    material type 5 is the coated diffuse (option coated, section 5.13); whether type 4 is live is a run-time field from here on
 //   LENS    each sample starts on the thin-lens ray (pt_set_lens, section 5.14); whether type 5 is live is a run-time field from here on
 //   FROST   material type 6 is the rough dielectric (option frosted, section 5.15); whether a lens is set is a run-time field (flags bit 2)
-// Each flag from SMOOTH on requires the one before it.  The kernels are the seven families the host can ask for (NeeFamily, pt_internal.hpp)
-// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted: each is the one before it with one more flag -- times ENV and TILED
+//   LIGHTS  analytic point, spot and directional lights (pt_set_lights, section 5.16): a lobe vertex samples the set, the sky or a triangle
+//           light; whether type 6 is live is a run-time field from here on (flags bit 3)
+// Each flag from SMOOTH on requires the one before it.  The kernels are the eight families the host can ask for (NeeFamily, pt_internal.hpp)
+// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights: each is the one before it with one more flag -- times ENV and TILED
 // (k_nee_env*, k_nee_tiles*, k_nee_env_tiles*).  In a family whose option is off the data is null (vn, tv.uv) or the field clear.
 #include "pt_device.hpp"
 
@@ -99,9 +101,20 @@ struct FrostSlot<true> {
     bool lens = true;              // a lens with aperture > 0 is set in this launch (else the pinhole ray, as in the instances without one)
 };
 
+// what a hook carries for the analytic lights (pt_set_lights): nothing without them
+template <bool LIGHTS>
+struct LightsSlot {};
+template <>
+struct LightsSlot<true> {
+    LightsView v;                  // records, cdf, count and the launch's P_ana
+    bool frost = true;             // option frosted with a type-6 material uploaded: type 6 is live in this launch (else inert, as in the instances without it)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
-template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false, bool FROST = false>
+template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false, bool FROST = false,
+          bool LIGHTS = false>
 struct NeeHook {
+    static_assert(FROST || !LIGHTS, "the lights instances are built on the frosted code");
     static_assert(LENS || !FROST, "the frosted instances are built on the lens code");
     static_assert(COAT || !LENS, "the lens instances are built on the coated code");
     static_assert(SMOOTH || !TEX, "the textured instances are built on the smooth code");
@@ -114,6 +127,7 @@ struct NeeHook {
     static constexpr bool coated = COAT;
     static constexpr bool lens = LENS;
     static constexpr bool frosted = FROST;
+    static constexpr bool lights = LIGHTS;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -131,7 +145,13 @@ struct NeeHook {
     CoatSlot<COAT> ct;
     LensSlot<LENS> ln;
     FrostSlot<FROST> frs;
+    LightsSlot<LIGHTS> lg;
 
+    // LIGHTS: type 6 is live (option frosted; a run-time answer in the lights instances only: the frosted ones run only when it is)
+    PT_DEV bool frost_live() const {
+        if constexpr (LIGHTS) return lg.frost;
+        else return FROST;
+    }
     // LENS: type 5 is live (option coated; a run-time answer in the lens instances only: the coated ones run only when it is)
     PT_DEV bool coat_live() const {
         if constexpr (LENS) return ln.coat;
@@ -337,6 +357,7 @@ struct NeeHook {
         if (!nee || !after_lobe) return 1.0f;
         float pa = lt.pdf_area[ti];
         if constexpr (ENV) pa *= 1.0f - env.v.p_env;                 // the light table is chosen with probability 1 - P_env
+        if constexpr (LIGHTS) pa *= 1.0f - lg.v.p_ana;               // ... and the sky or the table with probability 1 - P_ana
         if (!(pa > 0.0f && inten > 0.0f)) return 1.0f;
         if (!mis) return 0.0f;
         float pb;
@@ -375,9 +396,10 @@ struct NeeHook {
     // what an unoccluded light sample adds: the bracket an emitter hit (or, ENV, a miss) along w on segment k + 1 would add, for the lobe
     // vertex hp (normal N, cosx = N.w, reached along rD; ins: inside a dielectric).  pl: the sample's p_l; g: the emitter's cosine (1 for the
     // sky); e: its radiance with ENV (the sky's texel or the triangle's emission, which light_sample_env has before the traversal).  Without ENV
-    // e is not read: the emission of triangle li is loaded here, after the traversal, where those instances always read it
+    // e is not read: the emission of triangle li is loaded here, after the traversal, where those instances always read it.  LIGHTS: e comes
+    // with the sample as with ENV; delta: an analytic light's sample, which no other strategy can find: its weight is p_b / p_l under MIS too
     PT_DEV void light_add(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins, f3 w, float cosx,
-                          float pl, float g, int li, f3 e) const {
+                          float pl, float g, int li, f3 e, bool delta = false) const {
         float pb = cosx * kOneOverPi;
         f3 fs = st.S();
         if constexpr (GLOSSY)
@@ -392,12 +414,13 @@ struct NeeHook {
             }
         f3 fr = st.R();
         if constexpr (FROST)
-            if (type == 6) {
+            if (type == 6 && frost_live()) {
                 pb = frosted_light(m, N, rD, w, ins, fr, &fr);
                 if (!(pb > 0.0f)) return;
             }
         const float q = pb / pl;
-        const float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
+        float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
+        if constexpr (LIGHTS) if (delta) wl = q;
         f3 fl = st.L(), fb = st.B();
         if (type == 0) {           // the factors the vertex's own update with w would give (shade_hit)
             fl = fl * (albedo(m) * cosx);
@@ -409,7 +432,7 @@ struct NeeHook {
             }
             fb = fb * (ldf3(m->ks) * pw);
         }
-        if constexpr (!ENV) e = ldf3(p.mats[p.meta[li].mati].emission);
+        if constexpr (!ENV && !LIGHTS) e = ldf3(p.mats[p.meta[li].mati].emission);
         e = ((e * (fl + fb)) * fs) * fr;
         if (wl < __builtin_inff()) st.setC(madd(e, g * wl, st.C()));
     }
@@ -418,7 +441,7 @@ struct NeeHook {
     // (rD: the direction the vertex was reached along, read for a rough vertex; ins: the path is inside a dielectric, read for a type-6 one)
     PT_DEV void light_sample(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins) {
         if (!nee || k + 1 >= p.iterations) return;
-        if constexpr (ENV) {
+        if constexpr (ENV || LIGHTS) {
             light_sample_env(st, p, m, type, N, hp, rD, ins);
             return;
         }
@@ -436,55 +459,112 @@ struct NeeHook {
         light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, cosy, li, mk(0.f, 0.f, 0.f));
     }
 
+    // LIGHTS: the analytic light that u0 draws from the set's cdf, seen from o: false if it adds nothing (a point light at o, or o outside its
+    // cone); else *w the unit direction to it, *limit the search's cut (its distance r; none for a directional light), *e its intensity x
+    // cone / d (d = r^2, or 1 for a directional light) and *pl = P_ana P_light.  One record load: the light picked
+    PT_DEV bool analytic_direction(float u0, f3 o, f3* w, float* limit, f3* e, float* pl) const {
+        const LightsView& lv = lg.v;
+        int lo = 0, hi = lv.n - 1;        // first light with cdf > u0
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (lv.cdf[mid] > u0) hi = mid;
+            else lo = mid + 1;
+        }
+        const float4 q0 = lv.rec[lo * 4], q1 = lv.rec[lo * 4 + 1], q2 = lv.rec[lo * 4 + 2], q3 = lv.rec[lo * 4 + 3];
+        const f3 axis = mk(q1.x, q1.y, q1.z);
+        float d = 1.0f;
+        *limit = __builtin_inff();
+        if (__float_as_int(q0.w) == PT_LIGHT_DIRECTIONAL) {
+            *w = -axis;
+        } else {
+            const f3 dv = mk(q0.x, q0.y, q0.z) - o;
+            d = dot3(dv, dv);
+            if (!(d > 0.0f && d < __builtin_inff())) return false;
+            const float r = __builtin_sqrtf(d);
+            *w = mk(dv.x / r, dv.y / r, dv.z / r);
+            *limit = r;
+        }
+        const float c = dot3(-*w, axis);
+        float cone = 1.0f;                // full inside cos_inner (q1.w), nothing outside cos_outer (q2.w), smoothstep between
+        if (!(c >= q1.w)) {
+            if (c <= q2.w) return false;
+            const float s = (c - q2.w) / (q1.w - q2.w);
+            cone = (s * s) * (3.0f - 2.0f * s);
+        }
+        *e = mk(q2.x, q2.y, q2.z) * (cone / d);
+        *pl = lv.p_ana * q3.x;
+        return true;
+    }
+    // the sample is the sky's (u_sel, keyed with ~key, against P_env); never without ENV
+    PT_DEV bool picks_sky() const {
+        if constexpr (ENV) return nee_unit(nee_rand(~key, k, 0)) < env.v.p_env;
+        else return false;
+    }
+
     // ENV: the sky with probability P_env (u_sel, keyed with ~key), else a light of the table with its pdf times 1 - P_env.  Both
     // branches only produce the shadow ray and what it would add; the traversal and the weighting are shared, so a wave that holds
     // both kinds of sample runs one traversal
+    // LIGHTS: before either, the analytic set with probability P_ana (keyed with ~key, dimension 2): a third branch of the same kind, and
+    // the other two's p_l take the factor 1 - P_ana.  Without ENV there is no sky branch
     PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins) {
-        const EnvView& ev = env.v;
         const float u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
         const f3 o = madd(geo(N), 0.001f, hp);
         f3 w, e;
-        float limit, pl, g;            // the search's cut, p_l, the emitter's cosine (1 for the sky)
+        float limit, pl, g;            // the search's cut, p_l, the emitter's cosine (1 for the sky and for an analytic light)
         int want;                      // what the shadow ray must return
-        if (nee_unit(nee_rand(~key, k, 0)) < ev.p_env) {
-            int lo = 0, hi = ev.h - 1;        // first row with cdf > u1, then first column of that row with cdf > u2
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (ev.row_cdf[mid] > u1) hi = mid;
-                else lo = mid + 1;
+        bool delta = false;            // LIGHTS: the sample is an analytic light's
+        if constexpr (LIGHTS) delta = nee_unit(nee_rand(~key, k, 2)) < lg.v.p_ana;
+        if (LIGHTS && delta) {
+            if constexpr (LIGHTS) {
+                if (!analytic_direction(nee_unit(nee_rand(key, k, 0)), o, &w, &limit, &e, &pl)) return;
+                g = 1.0f;
+                want = -1;
             }
-            const int row = lo;
-            const float rb = row ? ev.row_cdf[row - 1] : 0.0f;
-            const float t1 = (u1 - rb) / (ev.row_cdf[row] - rb);
-            const float* __restrict__ cc = ev.col_cdf + (size_t)row * ev.w;
-            lo = 0;
-            hi = ev.w - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (cc[mid] > u2) hi = mid;
-                else lo = mid + 1;
+        } else if (picks_sky()) {
+            if constexpr (ENV) {
+                const EnvView& ev = env.v;
+                int lo = 0, hi = ev.h - 1;        // first row with cdf > u1, then first column of that row with cdf > u2
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (ev.row_cdf[mid] > u1) hi = mid;
+                    else lo = mid + 1;
+                }
+                const int row = lo;
+                const float rb = row ? ev.row_cdf[row - 1] : 0.0f;
+                const float t1 = (u1 - rb) / (ev.row_cdf[row] - rb);
+                const float* __restrict__ cc = ev.col_cdf + (size_t)row * ev.w;
+                lo = 0;
+                hi = ev.w - 1;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (cc[mid] > u2) hi = mid;
+                    else lo = mid + 1;
+                }
+                const int col = lo;
+                const float cb = col ? cc[col - 1] : 0.0f;
+                const float t2 = (u2 - cb) / (cc[col] - cb);
+                const float4 tx = ev.texels[(size_t)row * ev.w + col];
+                const float c0 = cosf(3.14159265358979323846f * (float)row / (float)ev.h), c1 = cosf(3.14159265358979323846f * (float)(row + 1) / (float)ev.h);
+                const float ct = c0 - t1 * (c0 - c1);
+                const float sn = __builtin_sqrtf(max0(fmaf_(-ct, ct, 1.0f)));
+                const float phi = fmaf_(6.28318530717958647692f, ((float)col + t2) / (float)ev.w, ev.yaw);
+                w = mk(sn * cosf(phi), ct, sn * sinf(phi));
+                e = mk(tx.x, tx.y, tx.z) * ev.scale;
+                pl = ev.p_env * tx.w;
+                if constexpr (LIGHTS) pl *= 1.0f - lg.v.p_ana;
+                g = 1.0f;
+                limit = __builtin_inff();
+                want = -1;
             }
-            const int col = lo;
-            const float cb = col ? cc[col - 1] : 0.0f;
-            const float t2 = (u2 - cb) / (cc[col] - cb);
-            const float4 tx = ev.texels[(size_t)row * ev.w + col];
-            const float c0 = cosf(3.14159265358979323846f * (float)row / (float)ev.h), c1 = cosf(3.14159265358979323846f * (float)(row + 1) / (float)ev.h);
-            const float ct = c0 - t1 * (c0 - c1);
-            const float sn = __builtin_sqrtf(max0(fmaf_(-ct, ct, 1.0f)));
-            const float phi = fmaf_(6.28318530717958647692f, ((float)col + t2) / (float)ev.w, ev.yaw);
-            w = mk(sn * cosf(phi), ct, sn * sinf(phi));
-            e = mk(tx.x, tx.y, tx.z) * ev.scale;
-            pl = ev.p_env * tx.w;
-            g = 1.0f;
-            limit = __builtin_inff();
-            want = -1;
         } else {
-            if (lt.n <= 0) return;            // (P_env is 1 then: not reached)
+            if (lt.n <= 0) return;            // (P_env or P_ana is 1 then: not reached)
             f3 y, Ny;
             float r2, r;
             want = light_point(p, nee_unit(nee_rand(key, k, 0)), u1, u2, &y, &Ny);
             w = light_direction(o, y, Ny, &r2, &r, &g);
-            pl = (lt.pdf_area[want] * (1.0f - ev.p_env)) * r2 / g;     // g = 0: inf or NaN, rejected below
+            if constexpr (ENV) pl = (lt.pdf_area[want] * (1.0f - env.v.p_env)) * r2 / g;     // g = 0: inf or NaN, rejected below
+            else pl = lt.pdf_area[want] * r2 / g;
+            if constexpr (LIGHTS) pl *= 1.0f - lg.v.p_ana;
             e = ldf3(p.mats[p.meta[want].mati].emission);
             limit = r * 1.0001f;
         }
@@ -492,7 +572,8 @@ struct NeeHook {
         if (!(cosx > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
         if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // as in light_sample
         if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
-        light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e);
+        if constexpr (LIGHTS) light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e, delta);
+        else light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e);
     }
 
     // ENV: a miss on segment kk along rD (the path ends there)
@@ -507,7 +588,8 @@ struct NeeHook {
             return;
         }
         float wb = 1.0f;
-        const float pl = ev.p_env * tx.w;
+        float pl = ev.p_env * tx.w;
+        if constexpr (LIGHTS) pl *= 1.0f - lg.v.p_ana;
         if (nee && after_lobe && pl > 0.0f) {
             if (mis) {
                 float pb;
@@ -541,15 +623,16 @@ struct NeeHook {
 // COAT (option coated; k_nee*_coated below; on the GLOSSY code only): material type 5 is the coated-diffuse lobe vertex; metal: option glossy
 // LENS (pt_set_lens; k_nee*_lens below; on the COAT code only): each sample starts on the thin-lens ray; metal bit 1: option coated
 // FROST (option frosted; k_nee*_frosted below; on the LENS code only): material type 6 is the rough-dielectric lobe vertex; metal bit 2: a lens is set
+// LIGHTS (pt_set_lights; k_nee*_lights below; on the FROST code only): a lobe vertex may sample an analytic light; metal bit 3: option frosted
 template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false,
-          bool FROST = false>
+          bool FROST = false, bool LIGHTS = false>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr,
-                      int metal = 0, const LensView* lens = nullptr) {
+                      int metal = 0, const LensView* lens = nullptr, const LightsView* lights = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (TEX) hook.tx.v = *tv;
     if constexpr (LENS) {
@@ -561,6 +644,11 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
     if constexpr (ENV) {
         hook.env = env;
         hook.nee = lt.strategy != 0;       // the sky is a light (the host launches this instance only for a map with a distribution)
+    }
+    if constexpr (LIGHTS) {
+        hook.lg.v = *lights;
+        hook.lg.frost = (metal & 8) != 0;
+        hook.nee = lt.strategy != 0;       // the set is a light (the host launches these instances only for a set with a pickable light)
     }
     const int camX = (int)p.cam.XM;
     unsigned rendered = 0;                     // TILED: pixels this lane rendered (statistic "samples", as k_render counts them)
@@ -763,6 +851,26 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_frosted(RenderParams p,
     nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv);
 }
 
+// the lights instances (a light set with a pickable light is held): the frosted kernels with the lights' view as one more argument; flags bit 3:
+// option frosted with a type-6 material uploaded (else type 6 is inert)
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_lights(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_lights(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
+                                                          long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_lights(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg) {
+    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_lights(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg) {
+    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -824,7 +932,10 @@ hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch
                                      stream, nl.vn, nl.tv, nl.flags & 3, nl.lens);
     case kNeeFrosted:
         return launch_nee_family<kWideAll>(NEE_PICK(k_nee_frosted), NEE_PICK(k_nee_env_frosted), NEE_PICK(k_nee_tiles_frosted), NEE_PICK(k_nee_env_tiles_frosted), p, lt, nl, npix,
-                                     cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens);
+                                     cu_count, stream, nl.vn, nl.tv, nl.flags & 7, nl.lens);
+    case kNeeLights:
+        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_lights), NEE_PICK(k_nee_env_lights), NEE_PICK(k_nee_tiles_lights), NEE_PICK(k_nee_env_tiles_lights), p, lt, nl, npix,
+                                     cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights);
     }
     return hipErrorInvalidValue;
 }

@@ -38,6 +38,9 @@ class SceneSpec:
     uvs: list = field(default_factory=list)          # optional, per object: corner uvs (n,3,2) f32 (NaN: none) or None
     textures: list = field(default_factory=list)     # optional: (h,w,3) f32 images, or (image, dict(filter=, srgb=)) (Scene.add_texture)
     material_textures: dict = field(default_factory=dict)   # optional: {index into materials: index into textures}
+    lights: list = field(default_factory=list)       # optional: analytic lights as api.light_from takes them, dict(kind="point" | "spot" |
+                                                     # "directional", ...) (Scene.load applies them with Scene.set_lights)
+    lights_select: float = 0.5                       # ... and set_lights' select
 
     @property
     def ntris(self):
@@ -134,7 +137,11 @@ def checker_texture(n, a, b):
     return np.where(even, np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)).astype(np.float32)
 
 
-def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False, frosted=False):
+LAMP_LIGHT_Y = 990.0           # cornell_box(lamp="point" / "spot"): the light hangs this high, under the ceiling at 1000
+LAMP_SPOT_DEGREES = (60.0, 90.0)      # ... and the spot's inner and outer half angles
+
+
+def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False, frosted=False, lamp="quad"):
     """Scene CB of SURVEY 8(d): 12 wall/lamp triangles + two tessellated spheres
     (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects.
     smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals).
@@ -145,11 +152,31 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
     coated: the other sphere gets, in place of GLASS, a red plastic appended to the materials: type 5, kd (0.7, 0.1, 0.1), N = 1.5 and
     K = 0 (F0 = 0.04), shininess 300; a diffuse base under a rough dielectric coat under option coated (and inert without it).
     frosted: the other sphere gets, in place of GLASS, a copy of GLASS with type 6 and shininess 30, appended to the materials: a rough
-    dielectric (frosted glass) under option frosted (and inert without it).  The sphere wears one material: not together with coated."""
+    dielectric (frosted glass) under option frosted (and inert without it).  The sphere wears one material: not together with coated.
+    lamp: "quad" (default) the reference's emitting quad; "point" / "spot" remove it and hang an analytic light of the same total power
+    below its centre (Scene.set_lights through Scene.load; only render_nee renders the scene then).  The quad of area A and emission E
+    radiates pi E A; a point light of intensity I radiates 4 pi I, so I = E A / 4; the spot points down, full inside 60 degrees of its
+    axis and dark from 90 on, and the smoothstep between integrates to half its width: 2 pi I (1 - cos 60 + cos 60 / 2), so
+    I = E A / 1.5."""
     if coated and frosted:
         raise ValueError("cornell_box: coated and frosted both replace the glass sphere's material")
+    if lamp not in ("quad", "point", "spot"):
+        raise ValueError("cornell_box: lamp must be \"quad\", \"point\" or \"spot\"")
     spec = SceneSpec(materials=list(BUILTIN_MATERIALS), name="cornell_box")
-    spec.objects.append(cornell_walls())
+    walls, wall_mats = cornell_walls()
+    if lamp != "quad":
+        quad = walls[:2].astype(np.float64)                  # the lamp's two triangles come first
+        area = 0.5 * sum(np.linalg.norm(np.cross(t[1] - t[0], t[2] - t[0])) for t in quad)
+        centre = quad.reshape(-1, 3).mean(axis=0)
+        emission = np.asarray(BUILTIN_MATERIALS[LAMP][2], dtype=np.float64)
+        position = (float(centre[0]), LAMP_LIGHT_Y, float(centre[2]))
+        if lamp == "point":
+            spec.lights = [dict(kind="point", position=position, intensity=tuple(emission * area / 4.0))]
+        else:
+            spec.lights = [dict(kind="spot", position=position, direction=(0.0, -1.0, 0.0), intensity=tuple(emission * area / 1.5),
+                                inner_degrees=LAMP_SPOT_DEGREES[0], outer_degrees=LAMP_SPOT_DEGREES[1])]
+        walls, wall_mats = walls[2:], wall_mats[2:]
+    spec.objects.append((walls, wall_mats))
     s1 = uv_sphere((250.0, 200.0, 300.0), 200.0, segments, rings)
     chromium = CHROMIUM
     if glossy:
@@ -171,7 +198,7 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
     if textured:
         walls = spec.objects[0][0]
         uv = np.full((walls.shape[0], 3, 2), np.nan, dtype=np.float32)
-        uv[10:12] = walls[10:12][:, :, [0, 2]] / np.float32(1600.0)        # the floor: (x, z)
+        uv[-2:] = walls[-2:][:, :, [0, 2]] / np.float32(1600.0)            # the floor, the last two wall triangles: (x, z)
         spec.uvs = [uv, None, None]
         spec.textures = [(checker_texture(8, (1.0, 1.0, 1.0), (0.25, 0.25, 0.25)), dict(filter=0, srgb=0))]
         spec.material_textures = {WHITE_DIFFUSE: 0}
