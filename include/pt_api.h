@@ -335,6 +335,65 @@ int pt_clear_lights(pt_context* ctx);
  * (the light table is built if the scene is uploaded, else taken as empty).  Any pointer but n may be NULL */
 int pt_debug_lights(pt_context* ctx, float* records, float* cdf, float* P_light, int64_t cap, int64_t* n, float* P_ana);
 
+/* ---- a homogeneous participating medium (fog) for pt_render_nee (new: opt-in with pt_set_medium; the reference renders vacuum) ----
+ * One medium per context, set like the lens and the environment; it is not part of the scene, so uploads keep it.  Only pt_render_nee
+ * (every strategy) and the NEE path of pt_render_adaptive_ex render it.  Without one -- never set, cleared, or sigma_t = 0 -- every path
+ * launches the kernels it launched before and computes what it computed before, bit for bit.
+ * The medium fills its axis-aligned box [lo, hi] wherever the path is not inside a dielectric (the `inside` flag of the specular and frosted
+ * vertices is false).  It draws from a third hash stream, pt_nee_rand(S ^ 0x5bd1e995, k, dim) (S the LCG state at the start of the sample,
+ * k the segment; the light samples own S and ~S), never from the LCG: rnds after a frame are pt_render's for every path that never scatters.
+ * All arithmetic below is float32 with no contraction; log1pf, expf, sinf, cosf are the device library's (OCML: within 2 ulp, 1 ulp, 2 ulp,
+ * 2 ulp), divides and square roots IEEE.
+ * Clip(P, D, t): the part [a, b] of [0, t] inside the box, by slabs: a = 0, b = t; per axis x, y, z with i = 1 / D.axis: if |i| is finite,
+ *   t0 = (lo - P) i, t1 = (hi - P) i, a = max(a, min(t0, t1)), b = min(b, max(t0, t1)) (max(a, v): v > a ? v : a; min(b, v): v < b ? v : b);
+ *   else (the ray is parallel to the slab) b = -inf unless lo <= P <= hi.  L = max(b - a, 0) (0 for every NaN).
+ * Free flight on segment k, after the closest hit (t its distance, +inf on a miss), while not inside a dielectric: [a, b] = Clip(P, D, t);
+ *   if L > 0: u = (pt_nee_rand(S ^ 0x5bd1e995, k, 0) >> 8) 2^-24, d = -log1pf(-u) / sigma_t (-log(1 - u) with its relative precision kept for a small u); the segment scatters iff d < L, at distance
+ *   s = a + d, x = fma(D, s, P) per component.  Otherwise the surface hit (or the miss) proceeds as without a medium, with no factor:
+ *   surviving has probability exp(-sigma_t L), which is the transmittance, so the two cancel.
+ * Scatter vertex (it consumes segment k as a surface vertex does):
+ *   1 factor_S *= albedo; an all-zero product ends the path.
+ *   2 with strategy LIGHT or MIS and k + 1 < iterations, one light sample as at a lobe vertex: the same three-way selection (analytic set,
+ *     sky, light table), the same hash values of S and ~S at segment k; origin x itself (no offset), no cosine test at the vertex,
+ *     p_b = HG(g, dot(D, w)); the factors are those after step 1; p_l, the emitter's cosine, the delta rule and the weight q / (q^2 + 1)
+ *     (q = p_b / p_l; q alone for LIGHT and for a delta light) as at a surface vertex; times the transmittance T below.
+ *   3 new direction: u1, u2 from dimensions 1 and 2 of the medium's stream; c = 1 - 2 u1 when |g| < 1e-3, else
+ *     r = (1 - g g) / ((1 - g) + (2 g) u1), c = ((1 + g g) - r r) / (2 g); s = sqrtf(max(1 - c c, 0)), phi = 6.2831855f u2;
+ *     w = X (s cosf(phi)) + Z (s sinf(phi)) + D c in the tangent frame (Z, X) of D that the diffuse vertex builds around its normal,
+ *     normalised as every new direction is; the next segment starts at x.  The vertex is a lobe vertex for what follows: an emitter hit or
+ *     a sky miss on segment k + 1 is weighted with p_b = HG(g, c).
+ *     HG(g, c) = (1 - g g) / (12.566371f (q sqrtf(q))), q = (1 + g g) - (2 g) c.
+ *   4 no emission; `inside` is unchanged.  With iterations = 1 a frame is the flat preview of the surface, and a sample that scatters is black.
+ * Transmittance: every light sample whose vertex is not inside a dielectric -- at surface lobe vertices and at scatter vertices -- is
+ *   multiplied by T = expf(-(sigma_t l)), l = the L of Clip(o, w, limit) for the shadow ray's origin o, direction w and cut `limit`
+ *   (T = 1 exactly when l = 0).  limit is +inf for the sky and for directional lights: an unbounded medium gives those T = 0, so give the
+ *   fog a box to let a sun in.  The weights of emitter hits and sky misses stay functions of the directional densities p_b and p_l only:
+ *   both strategies carry the same transmittance along a direction -- the BSDF strategy as the probability of surviving the free flight,
+ *   the light strategy as the factor T -- so it cancels in the balance and the weights still sum to one per direction.
+ * With PT_NEE_BSDF the medium scatters and no light sample is taken.  A scatter vertex draws nothing from the LCG, so a path that scatters
+ * ends with other rnds than pt_render's.  The guides (pt_render_aovs*), the denoisers and temporal accumulation keep the fog-free view, as
+ * they keep the pinhole view under a lens.
+ * While a medium with sigma_t > 0 is held, pt_render, pt_generate_rays, pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex with
+ * PT_ADAPT_PATH_RENDER return PT_EINVAL naming pt_clear_medium, checked before the device.  Every rank of a tiled frame sets its own copy;
+ * a host-only context validates and stores. */
+typedef struct pt_medium {
+    float sigma_t;      /* extinction per unit length, finite, >= 0; 0: no medium */
+    float albedo[3];    /* single-scattering albedo, each in [0, 1] */
+    float g;            /* Henyey-Greenstein asymmetry, |g| <= 0.99 */
+    float lo[3], hi[3]; /* axis-aligned bounds; -inf / +inf: unbounded on that side; lo < hi on every axis */
+} pt_medium;            /* 44 bytes */
+void pt_medium_defaults(pt_medium* m);      /* {0, {1, 1, 1}, 0, {-inf, -inf, -inf}, {+inf, +inf, +inf}} */
+/* PT_EINVAL, naming pt_set_medium and the field, with the held medium left as it was: a NaN anywhere, sigma_t negative or infinite, an
+ * albedo outside [0, 1], |g| > 0.99, lo >= hi on an axis; ctx or m NULL */
+int pt_set_medium(pt_context* ctx, const pt_medium* m);
+int pt_clear_medium(pt_context* ctx);
+/* the held record into *m (the defaults when none is held); returns 1 if one is held, 0 if not, PT_EINVAL for a NULL argument */
+int pt_get_medium(const pt_context* ctx, pt_medium* m);
+/* the device functions of the held medium (sigma_t > 0) on given numbers, n items: in, 12 floats each {P.xyz, D.xyz (unit), t, u, u1, u2,
+ * limit, spare}; out, 10 floats each {a, b of Clip(P, D, t), 1 if d < L else 0, d = -log1pf(-u) / sigma_t, the new direction from
+ * (u1, u2) around D (unit), its p_b, T of Clip(P, D, limit), 0}.  PT_EINVAL when no medium with sigma_t > 0 is held */
+int pt_debug_medium(pt_context* ctx, const float* in, int64_t n, float* out);
+
 /* ---- smooth shading from vertex normals for pt_render_nee (new: opt-in with option "smooth_normals"; the reference shades with the
  * triangle's geometric normal only) -----------
  * Authoring (host data; all of it works on a host-only context, none of it rebuilds the BVH).  Triangles are counted in add order over

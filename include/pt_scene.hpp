@@ -126,6 +126,10 @@ public:
     // light is held only render_nee with PT_NEE_LIGHT / PT_NEE_MIS and the NEE path of render_adaptive render
     void set_lights(const pt_light* lights, int32_t count, const pt_lights_params* p = nullptr) { ck(pt_set_lights(ctx, lights, count, p)); }
     void clear_lights() { ck(pt_clear_lights(ctx)); }
+    // a homogeneous medium (fog) for render_nee (pt_set_medium; start from pt_medium_defaults).  While one with sigma_t > 0 is held only
+    // render_nee and the NEE path of render_adaptive render; uploads keep it
+    void set_medium(const pt_medium& m) { ck(pt_set_medium(ctx, &m)); }
+    void clear_medium() { ck(pt_clear_medium(ctx)); }
     // vertex normals for smooth shading (set_option("smooth_normals", 1); render_nee only): normals = count x 9 floats, n1 n2 n3 per
     // triangle in add order starting at first_triangle; compute_vertex_normals derives them per object (obj = -1: every object)
     void set_vertex_normals(const float* normals, int64_t count, int64_t first_triangle = 0) { ck(pt_set_vertex_normals(ctx, first_triangle, count, normals)); }

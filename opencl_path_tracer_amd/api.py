@@ -53,6 +53,7 @@ EXPORTS = [
     "pt_lens_defaults", "pt_set_lens", "pt_clear_lens", "pt_focus_at", "pt_debug_lens",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_lights_defaults", "pt_set_lights", "pt_clear_lights", "pt_debug_lights",
+    "pt_medium_defaults", "pt_set_medium", "pt_clear_medium", "pt_get_medium", "pt_debug_medium",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
     "pt_render_aovs", "pt_read_aovs", "pt_aov_defaults", "pt_render_aovs_ex", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
@@ -148,6 +149,11 @@ def _load():
     sig("pt_set_lights", C.c_int, vp, vp, i32, vp)
     sig("pt_clear_lights", C.c_int, vp)
     sig("pt_debug_lights", C.c_int, vp, vp, vp, vp, i64, C.POINTER(i64), fp)
+    sig("pt_medium_defaults", None, vp)
+    sig("pt_set_medium", C.c_int, vp, vp)
+    sig("pt_clear_medium", C.c_int, vp)
+    sig("pt_get_medium", C.c_int, vp, vp)
+    sig("pt_debug_medium", C.c_int, vp, vp, i64, vp)
     sig("pt_image_read_pfm", C.c_int, C.c_char_p, vp, i64, C.POINTER(i32), C.POINTER(i32))
     sig("pt_read_variance", C.c_int, vp, vp, i64)
     sig("pt_device_variance", vp, vp)
@@ -382,6 +388,21 @@ def light_from(d):
     if kind not in make:
         raise KeyError("a light's kind must be one of %s, not %r" % (", ".join(sorted(make)), kind))
     return make[kind](**d)
+
+
+class Medium(C.Structure):
+    """pt_medium (include/pt_api.h): a homogeneous participating medium, 44 bytes."""
+    _fields_ = [("sigma_t", C.c_float), ("albedo", C.c_float * 3), ("g", C.c_float), ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+    def as_dict(self):
+        return {"sigma_t": float(self.sigma_t), "albedo": tuple(self.albedo), "g": float(self.g), "lo": tuple(self.lo), "hi": tuple(self.hi)}
+
+
+def medium_defaults():
+    """pt_medium_defaults as a dict: sigma_t 0, albedo (1, 1, 1), g 0, lo (-inf, -inf, -inf), hi (+inf, +inf, +inf)."""
+    m = Medium()
+    LIB.pt_medium_defaults(C.byref(m))
+    return m.as_dict()
 
 
 class LensParams(C.Structure):
@@ -764,6 +785,42 @@ class Scene:
         self._ck(LIB.pt_debug_lens(self._h, _ptr(cam), C.byref(p), items.shape[0], _ptr(items), _ptr(out)))
         return out
 
+    # -- the homogeneous medium of render_nee and render_adaptive(path="nee") (include/pt_api.h pins the free flight and the scatter vertex)
+    def set_medium(self, sigma_t, albedo=(1, 1, 1), g=0.0, bounds=None):
+        """pt_set_medium: fog of extinction sigma_t per unit length (0: none, today's kernels and bits), single-scattering albedo (rgb or a
+        number) and Henyey-Greenstein asymmetry g, inside bounds = (lo, hi), two corners of an axis-aligned box (None: everywhere; -inf /
+        +inf leave a side open).  While sigma_t > 0 only render_nee and render_adaptive(path="nee") render; the guide buffers keep the
+        fog-free view.  An unbounded medium hides the sky and directional lights from the light samples: give it a box to let a sun in."""
+        m = Medium()
+        LIB.pt_medium_defaults(C.byref(m))
+        m.sigma_t, m.g = float(sigma_t), float(g)
+        m.albedo = (C.c_float * 3)(*[float(v) for v in (albedo if np.ndim(albedo) else (albedo,) * 3)])
+        if bounds is not None:
+            lo, hi = bounds
+            m.lo = (C.c_float * 3)(*[float(v) for v in lo])
+            m.hi = (C.c_float * 3)(*[float(v) for v in hi])
+        self._ck(LIB.pt_set_medium(self._h, C.byref(m)))
+
+    def clear_medium(self):
+        self._ck(LIB.pt_clear_medium(self._h))
+
+    def medium(self):
+        """pt_get_medium: the held medium as a dict (medium_defaults()'s keys), or None when none is held."""
+        m = Medium()
+        rc = LIB.pt_get_medium(self._h, C.byref(m))
+        if rc < 0:
+            self._ck(rc)
+        return m.as_dict() if rc == 1 else None
+
+    def debug_medium(self, items):
+        """pt_debug_medium: items (n, 12) float32 {P, D (unit), t, u, u1, u2, limit, spare} -> (n, 10) float32 {a, b of the clip of [0, t]
+        to the box, 1 if the segment scatters else 0, the free-flight distance d, the new direction from (u1, u2) around D (unit), its
+        p_b, T over [0, limit], 0}, by the device functions the medium k_nee instances call on the held medium."""
+        items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 12)
+        out = np.empty((items.shape[0], 10), dtype=np.float32)
+        self._ck(LIB.pt_debug_medium(self._h, _ptr(items), items.shape[0], _ptr(out)))
+        return out
+
     # -- the rough dielectric of material type 6 (option "frosted")
     def debug_frosted(self, items):
         """pt_debug_frosted: items (n, 12) float32 {N, D, alpha, F0, eta, rnd1, rnd2, u_sel} -> (n, 10) float32 {w before normalisation
@@ -809,6 +866,8 @@ class Scene:
         self.upload_Materials()
         if getattr(spec, "lights", None):                       # optional: what set_lights takes, with spec.lights_select
             self.set_lights(spec.lights, select=getattr(spec, "lights_select", 0.5))
+        if getattr(spec, "medium", None):                       # optional: set_medium's arguments as a dict
+            self.set_medium(**spec.medium)
         self.set_view(spec.fov, spec.yaw, spec.pitch, spec.shift)
         return self
 

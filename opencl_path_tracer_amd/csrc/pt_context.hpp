@@ -239,6 +239,12 @@ struct pt_context {
     bool lights_pickable = false;
     float4* d_lights_rec = nullptr;
     float* d_lights_cdf = nullptr;
+    // the homogeneous medium (pt_set_medium, pt_medium.cpp; pinned in include/pt_api.h): the record as validated (the defaults when none is
+    // set).  Only while sigma_t > 0 do pt_render_nee and the NEE path of pt_render_adaptive_ex launch the medium instances of k_nee, and do
+    // the other paths refuse.  Not part of the scene: uploads keep it
+    pt_medium medium = {0.0f, {1.0f, 1.0f, 1.0f}, 0.0f, {-std::numeric_limits<float>::infinity(), -std::numeric_limits<float>::infinity(), -std::numeric_limits<float>::infinity()},
+                        {std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity()}};
+    bool medium_set = false;
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -293,6 +299,13 @@ float lights_select(const pt_context* ctx, bool no_other);
 inline bool lights_on(const pt_context* ctx) { return ctx->lights_pickable; }
 inline std::string lights_refusal(const std::string& who) {
     return who + ": a light set is held and only pt_render_nee with PT_NEE_LIGHT or PT_NEE_MIS samples analytic lights (pt_clear_lights removes it)";
+}
+// pt_medium.cpp: a medium with sigma_t > 0 is held: only pt_render_nee (every strategy) and the NEE path of pt_render_adaptive_ex render; the
+// view the kernels read; the text the other paths refuse with
+inline bool medium_on(const pt_context* ctx) { return ctx->medium_set && ctx->medium.sigma_t > 0.0f; }
+MediumView medium_view(const pt_context* ctx);
+inline std::string medium_refusal(const std::string& who) {
+    return who + ": a medium with sigma_t > 0 is held and only pt_render_nee renders it (pt_clear_medium removes it)";
 }
 // a lens with aperture > 0 is set: only pt_render_nee and the NEE path of pt_render_adaptive_ex render
 inline bool lens_on(const pt_context* ctx) { return ctx->lens_set && ctx->lens_aperture > 0.0f; }

@@ -1409,6 +1409,61 @@ struct PathRegs {
     PT_DEV void setC(f3 v) { color = v; }
 };
 
+// ---- homogeneous medium (pt_set_medium; include/pt_api.h pins every operation).  The view is wave-uniform: lo, hi, sigma_t and g are scalar
+// operands of the lanes' arithmetic.
+// Clip: the part [*a, b] of [0, t] of the ray (P, D) inside the medium's box, by slabs; b is returned, and the length inside is max0(b - *a)
+PT_DEV float medium_clip(const MediumView& mv, f3 P, f3 D, float t, float* a_out) {
+    float a = 0.0f, b = t;
+    const float p[3] = {P.x, P.y, P.z}, dd[3] = {D.x, D.y, D.z};
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        const float inv = 1.0f / dd[ax];
+        if (__builtin_fabsf(inv) < __builtin_inff()) {
+            const float t0 = (mv.lo[ax] - p[ax]) * inv, t1 = (mv.hi[ax] - p[ax]) * inv;
+            const float nr = t0 < t1 ? t0 : t1, fr = t0 < t1 ? t1 : t0;
+            a = nr > a ? nr : a;
+            b = fr < b ? fr : b;
+        } else if (!(p[ax] >= mv.lo[ax] && p[ax] <= mv.hi[ax])) {
+            b = -__builtin_inff();       // parallel to the slab and outside it
+        }
+    }
+    *a_out = a;
+    return b;
+}
+// the free-flight distance of the unit number u in [0, 1): log1pf keeps its relative precision for a small u, where logf(1 - u) -- the
+// hardware's log2 scaled -- only has an absolute one
+PT_DEV float medium_flight(float sigma_t, float u) { return -log1pf(-u) / sigma_t; }
+// Henyey-Greenstein's density of the cosine c between the direction of travel before and after the vertex
+PT_DEV float medium_hg(float g, float c) {
+    const float g2 = g * g;
+    const float q = (1.0f + g2) - (2.0f * g) * c;
+    return (1.0f - g2) / (12.566370614359172f * (q * __builtin_sqrtf(q)));
+}
+// the direction (before normalisation) that (u1, u2) draw from it around the unit direction D, and its *pb
+PT_DEV f3 medium_direction(float g, f3 D, float u1, float u2, float* pb) {
+    float c;
+    if (__builtin_fabsf(g) < 1e-3f) {
+        c = 1.0f - 2.0f * u1;
+    } else {
+        const float g2 = g * g;
+        const float r = (1.0f - g2) / ((1.0f - g) + (2.0f * g) * u1);
+        c = ((1.0f + g2) - r * r) / (2.0f * g);
+    }
+    *pb = medium_hg(g, c);
+    const float s = __builtin_sqrtf(max0(1.0f - c * c));
+    const float phi = 6.28318530717958647692f * u2;
+    f3 Z, X;
+    tangent_frame(D, &Z, &X);
+    return madd(D, c, madd(Z, s * sinf(phi), X * (s * cosf(phi))));
+}
+// T of the ray (o, w) cut at `limit`: 1 exactly when no part of it lies in the box
+PT_DEV float medium_transmittance(const MediumView& mv, f3 o, f3 w, float limit) {
+    float a;
+    const float b = medium_clip(mv, o, w, limit, &a);
+    const float l = max0(b - a);
+    return l > 0.0f ? expf(-(mv.sigma_t * l)) : 1.0f;
+}
+
 // The light hook of shade_hit: three points in the segment body where k_nee (pt_nee.hip) adds next-event estimation.  Every
 // statement that touches the hook sits under `if constexpr (HOOK::active)`, so the default instantiation (k_render, wf_shade)
 // compiles exactly as without it -- plain empty inline methods change k_render's register allocation.
@@ -1424,6 +1479,10 @@ struct PathRegs {
 // draws the direction (lobe_direction_rough() above, in place of diffuse_direction) and keeps the vertex's p_b; whether type 4 or 5 is
 // live in a launch is the hook's answer (metal_live(), coat_live(); with `lights` also type 6: frost_live()).  The preview colour, light_sample, lobe_vertex, leaves_surface and end_vertex are
 // one call each for every hook: what a hook's flags do not cover in their arguments it does not read.
+// A hook with `medium` set (it has `lights`) may send a lane in at a scatter vertex of the medium instead of a hit (hook->scatters(); hp is
+// then the vertex, ti is not read): the lane joins the lobe vertices for the one call of light_sample() -- so a wave that holds surface and
+// scatter vertices runs one shadow traversal -- with type -1, and does nothing else here: no preview colour, no LCG draw, no new ray (the
+// caller draws the direction from the phase function).
 struct NoShadeHook {
     static constexpr bool active = false;
     static constexpr bool smooth = false;
@@ -1433,6 +1492,7 @@ struct NoShadeHook {
     static constexpr bool lens = false;
     static constexpr bool frosted = false;
     static constexpr bool lights = false;
+    static constexpr bool medium = false;
 };
 
 // The interpolated shading normal of a hit at hp = madd(D, t, P) on packed triangle ti (include/pt_api.h pins every operation): vn =
@@ -1539,6 +1599,12 @@ PT_DEV f3 shading_normal_albedo(const float4* __restrict__ vn, const TexView& tv
 template <bool SK, bool REC = false, class ST, class HOOK = NoShadeHook>
 PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const RenderParams& p, const float4* tris, const TriMeta* meta, int ti, float t,
                       HOOK* hook = nullptr) {
+    bool sc = false;                                                        // medium: the lane is at a scatter vertex, not at a hit
+    if constexpr (HOOK::medium) {
+        sc = hook->scatters();
+        // (a miss may scatter: the loads below stay in bounds)
+        if (sc || ti < 0) ti = 0;
+    }
     f3 N, kd;
     int type;
     bool plain;                                                             // type 0: ks is +0 and the pow is skipped
@@ -1558,6 +1624,7 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
         N = mk(c.y, c.z, c.w);
         m = &p.mats[meta[ti].mati];
         type = m->type;
+        if constexpr (HOOK::medium) if (sc) type = -1;
         kd = mk(0.0f, 0.0f, 0.0f);      // (read from the material where it is needed)
         plain = false;
     }
@@ -1570,7 +1637,12 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     // geometric-side rules
     // textures: the same call also leaves the vertex's albedo kd' in the hook (hook->albedo), which the preview colour, the factor_L
     // update below and the light sample read instead of the material's kd
-    if constexpr (HOOK::textured) {
+    if constexpr (HOOK::medium) {
+        if (!sc) {
+            N = hook->shading_attributes_at(p, tris, ti, rD, hp, flip ? -N : N, N, type, m);
+            if (p.iterations == 1) st.setC((type == 4 && hook->metal_live() ? ldf3(m->F0) : hook->albedo(m)) + ldf3(m->emission));
+        }
+    } else if constexpr (HOOK::textured) {
         static_assert(HOOK::smooth && !REC, "the textured instances are built on the smooth ones");
         N = hook->shading_attributes_at(p, tris, ti, rD, hp, flip ? -N : N, N, type, m);
         if (p.iterations == 1) st.setC((type == 4 && hook->metal_live() ? ldf3(m->F0) : hook->albedo(m)) + ldf3(m->emission));
@@ -1605,7 +1677,7 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
     float side = 0.001f;
     float inten = 0.0f;
     float wb = 1.0f;                                                        // the hook's weight of this hit's emission
-    if (lobe) {
+    if (lobe || sc) {
         // diffuse (prog.cl:329-340) and emitter (prog.cl:358-366) both continue with a cosine-
         // sampled ray drawn from two LCG values; the emitter's cosine uses the OLD direction.
         inten = max0(dot3(-rD, N));
@@ -1613,10 +1685,12 @@ PT_DEV void shade_hit(f3& rP, f3& rD, ST& st, int& seed, bool& inside, const Ren
             if (type == 3) wb = hook->emitter_weight(ti, t, inten, rD);
             hook->light_sample(st, p, m, type, N, hp, rD, inside);          // before the LCG draws and this hit's emission
         }
-        const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
-        if constexpr (HOOK::glossy) dnew = hook->template lobe_vertex<SK>(st, m, gl, ct, fr, N, rD, rnd1, rnd2, inside, &side);
-        else if constexpr (REC) dnew = diffuse_direction_rec<SK>(N, rec + (flip ? 4 : 2), rnd1, rnd2);
-        else dnew = diffuse_direction<SK>(N, rnd1, rnd2);
+        if (!sc) {
+            const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
+            if constexpr (HOOK::glossy) dnew = hook->template lobe_vertex<SK>(st, m, gl, ct, fr, N, rD, rnd1, rnd2, inside, &side);
+            else if constexpr (REC) dnew = diffuse_direction_rec<SK>(N, rec + (flip ? 4 : 2), rnd1, rnd2);
+            else dnew = diffuse_direction<SK>(N, rnd1, rnd2);
+        }
     } else if (spec) {
         // smooth shading: the vertex as a function of the normal, which may have to run twice (TWIN: NeeHook::spec_vertex restates the
         // branch below; a change to one belongs in the other)

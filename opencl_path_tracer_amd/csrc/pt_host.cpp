@@ -920,7 +920,10 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
         const bool no_other = ctx->nee_tri.empty() && !(ctx->env_set && ctx->env_dist);
         nl->lights = LightsView{ctx->d_lights_rec, ctx->d_lights_cdf, (int32_t)ctx->lights.size(), lights_select(ctx, no_other)};
     }
-    nl->family = lights_on(ctx)                    ? kNeeLights
+    else nl->lights = LightsView{nullptr, nullptr, 0, 0.0f};      // (kNeeMedium without a set: P_ana = 0, the branch is never taken)
+    if (medium_on(ctx)) nl->medium = medium_view(ctx);
+    nl->family = medium_on(ctx)                    ? kNeeMedium
+                 : lights_on(ctx)                  ? kNeeLights
                  : frosted                         ? kNeeFrosted
                  : lens_on(ctx)                    ? kNeeLens
                  : coated                          ? kNeeCoated
@@ -928,7 +931,7 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
                  : nl->tv.uv                       ? kNeeTex
                  : nl->vn                          ? kNeeSmooth
                                                    : kNeePlain;
-    nl->flags = (ctx->glossy ? 1 : 0) | (ctx->coated ? 2 : 0) | (lens_on(ctx) ? 4 : 0) | (frosted ? 8 : 0);
+    nl->flags = (ctx->glossy ? 1 : 0) | (ctx->coated ? 2 : 0) | (lens_on(ctx) ? 4 : 0) | (frosted ? 8 : 0) | (lights_on(ctx) ? 16 : 0);
     return PT_OK;
 }
 }  // namespace ptamd

@@ -435,6 +435,14 @@ struct LightsView {
     int32_t n;
     float p_ana;                 // the effective P_ana of the launch (a multiple of 2^-24)
 };
+// the homogeneous medium of pt_render_nee (pt_set_medium; pinned in include/pt_api.h): pt_medium's fields as the kernel reads them, all
+// wave-uniform (a kernel argument by value, so they stay in scalar registers)
+struct MediumView {
+    float sigma_t;               // > 0 in every launch of the medium instances
+    float albedo[3];
+    float g;
+    float lo[3], hi[3];          // -inf / +inf: unbounded on that side
+};
 // normalize3 of pt_device.hpp on the host: dot3's fma placement, then a * (1.0f / sqrtf(l2)), IEEE
 inline void lens_normalize(const float* a, float* out) {
     const float l2 = __builtin_fmaf(a[2], a[2], __builtin_fmaf(a[1], a[1], a[0] * a[0]));
@@ -458,7 +466,7 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
                               const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream);
 // one launch of the NEE kernels (pt_nee.hip), as nee_launch_for (pt_context.hpp) fills it from the context.  Each family is the one before it
 // with one more feature compiled in; a launch takes the first family that covers what the frame needs
-enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights };
+enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium };
 struct NeeLaunch {
     const EnvView* env;          // null: the instances without an environment
     bool tiled;                  // the rounds of pt_render_adaptive_ex: k_nee*_tiles over the p.n_tiles 8x8 frame tiles of p.tile_list (null: the
@@ -468,13 +476,16 @@ struct NeeLaunch {
     TexView tv;                  // uv == null: option textures is off (no lookup in the families from kNeeGlossy on); not read below kNeeTex
     int family;                  // NeeFamily.  An option whose material type is not uploaded asks for nothing; a lens with aperture > 0 takes
                                  // kNeeLens whatever the options say; option frosted with a type-6 material takes kNeeFrosted, lens or not;
-                                 // a light set with a pickable light (pt_set_lights) takes kNeeLights whatever else is on
+                                 // a light set with a pickable light (pt_set_lights) takes kNeeLights whatever else is on; a medium with
+                                 // sigma_t > 0 (pt_set_medium) takes kNeeMedium whatever else is on, lights or not
     int flags;                   // the options themselves, for the families in which they are run-time fields: bit 0 glossy (type 4 is live;
                                  // read from kNeeCoated on), bit 1 coated (type 5 is live; from kNeeLens on), bit 2 a lens with aperture > 0 is
                                  // set (from kNeeFrosted on; else each sample starts on the pinhole ray), bit 3 frosted with a type-6 material
-                                 // uploaded (type 6 is live; read by kNeeLights)
+                                 // uploaded (type 6 is live; read from kNeeLights on), bit 4 a light set with a pickable light is held (read
+                                 // by kNeeMedium; else `lights` is an empty set with P_ana = 0)
     LensView lens;               // read from kNeeLens on
-    LightsView lights;           // read by kNeeLights
+    LightsView lights;           // read from kNeeLights on
+    MediumView medium;           // read by kNeeMedium
 };
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
 // thin lens (pt_lens.hip): pt_debug_lens's kernel, {gid, S} in and 6 floats out per item; pt_focus_at's, the axial distance of pixel gid's
@@ -487,6 +498,8 @@ hipError_t launch_debug_albedo(const RenderParams& p, const float4* vn, const Te
                                int cu_count, hipStream_t stream);
 // rough metal (pt_glossy.hip): pt_debug_glossy's kernel, 9 floats in and 8 out per item
 hipError_t launch_debug_glossy(const float* in, int64_t n, float* out, hipStream_t stream);
+// homogeneous medium (pt_medium.hip): pt_debug_medium's kernel, 12 floats in and 10 out per item
+hipError_t launch_debug_medium(const MediumView& mv, const float* in, int64_t n, float* out, hipStream_t stream);
 // coated diffuse (pt_glossy.hip): pt_debug_coated's kernel, 12 floats in and 10 out per item
 hipError_t launch_debug_coated(const float* in, int64_t n, float* out, hipStream_t stream);
 // rough dielectric (pt_glossy.hip): pt_debug_frosted's kernel, 12 floats in and 10 out per item

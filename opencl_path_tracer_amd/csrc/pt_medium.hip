@@ -1,0 +1,41 @@
+// pt_medium.hip -- the homogeneous medium of pt_set_medium (include/pt_api.h pins every operation).
+//   k_debug_medium   pt_debug_medium: one thread per item runs medium_clip(), medium_flight(), medium_direction() and
+//                    medium_transmittance() (pt_device.hpp), the functions the medium k_nee instances call (pt_nee.hip) for the free
+//                    flight of a segment, the scatter vertex's new direction and the transmittance of a light sample, so that they can be
+//                    tested against float64 without a render.  No scene is read; the numbers the kernels hash are given.
+#include "pt_device.hpp"
+
+namespace ptamd {
+
+// in: 12 floats per item {P.xyz, D.xyz, t, u, u1, u2, limit, spare}; out: 10 per item {a, b, 1 if the segment scatters else 0, d,
+// the new direction (unit) from (u1, u2) around D, its p_b, T of the ray (P, D) over [0, limit]}
+__global__ void __launch_bounds__(256) k_debug_medium(MediumView mv, const float* __restrict__ in, long long n, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* q = in + i * 12;
+    const f3 P = mk(q[0], q[1], q[2]), D = mk(q[3], q[4], q[5]);
+    float a;
+    const float b = medium_clip(mv, P, D, q[6], &a);
+    const float d = medium_flight(mv.sigma_t, q[7]);
+    float pb;
+    const f3 w = normalize3(medium_direction(mv.g, D, q[8], q[9], &pb));
+    float* o = out + i * 10;
+    o[0] = a;
+    o[1] = b;
+    o[2] = d < max0(b - a) ? 1.0f : 0.0f;
+    o[3] = d;
+    o[4] = w.x;
+    o[5] = w.y;
+    o[6] = w.z;
+    o[7] = pb;
+    o[8] = medium_transmittance(mv, P, D, q[10]);
+    o[9] = 0.0f;
+}
+
+hipError_t launch_debug_medium(const MediumView& mv, const float* in, int64_t n, float* out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_debug_medium, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, mv, in, (long long)n, out);
+    return hipGetLastError();
+}
+
+}  // namespace ptamd

@@ -19,8 +19,11 @@
 //   FROST   material type 6 is the rough dielectric (option frosted, section 5.15); whether a lens is set is a run-time field (flags bit 2)
 //   LIGHTS  analytic point, spot and directional lights (pt_set_lights, section 5.16): a lobe vertex samples the set, the sky or a triangle
 //           light; whether type 6 is live is a run-time field from here on (flags bit 3)
-// Each flag from SMOOTH on requires the one before it.  The kernels are the eight families the host can ask for (NeeFamily, pt_internal.hpp)
-// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights: each is the one before it with one more flag -- times ENV and TILED
+//   MEDIUM  a homogeneous participating medium (pt_set_medium, section 5.17): a segment may end at a scatter vertex before its hit, and every
+//           light sample outside a dielectric carries the transmittance of its shadow ray; whether a pickable light set is held is a
+//           run-time field (flags bit 4)
+// Each flag from SMOOTH on requires the one before it.  The kernels are the nine families the host can ask for (NeeFamily, pt_internal.hpp)
+// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights, _medium: each is the one before it with one more flag -- times ENV and TILED
 // (k_nee_env*, k_nee_tiles*, k_nee_env_tiles*).  In a family whose option is off the data is null (vn, tv.uv) or the field clear.
 #include "pt_device.hpp"
 
@@ -110,10 +113,21 @@ struct LightsSlot<true> {
     bool frost = true;             // option frosted with a type-6 material uploaded: type 6 is live in this launch (else inert, as in the instances without it)
 };
 
+// what a hook carries for the medium (pt_set_medium): nothing without it
+template <bool MEDIUM>
+struct MediumSlot {};
+template <>
+struct MediumSlot<true> {
+    MediumView v;                  // sigma_t, albedo, g and the box: wave-uniform
+    bool sc = false;               // the current segment ended at a scatter vertex (shade_hit then only takes the light sample)
+    float T = 1.0f;                // the transmittance of the current light sample's shadow ray (light_sample_env to light_add)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
 template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false, bool FROST = false,
-          bool LIGHTS = false>
+          bool LIGHTS = false, bool MEDIUM = false>
 struct NeeHook {
+    static_assert(LIGHTS || !MEDIUM, "the medium instances are built on the lights code");
     static_assert(FROST || !LIGHTS, "the lights instances are built on the frosted code");
     static_assert(LENS || !FROST, "the frosted instances are built on the lens code");
     static_assert(COAT || !LENS, "the lens instances are built on the coated code");
@@ -128,6 +142,7 @@ struct NeeHook {
     static constexpr bool lens = LENS;
     static constexpr bool frosted = FROST;
     static constexpr bool lights = LIGHTS;
+    static constexpr bool medium = MEDIUM;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -146,7 +161,39 @@ struct NeeHook {
     LensSlot<LENS> ln;
     FrostSlot<FROST> frs;
     LightsSlot<LIGHTS> lg;
+    MediumSlot<MEDIUM> md;
 
+    // MEDIUM: the lane enters shade_hit at a scatter vertex
+    PT_DEV bool scatters() const {
+        if constexpr (MEDIUM) return md.sc;
+        else return false;
+    }
+    // MEDIUM: the free flight of segment k along (rP, rD), whose closest hit is at t (+inf: a miss): the distance of the scatter vertex, or -1
+    // when the segment reaches its end.  A segment with nothing inside the box draws no number (d >= 0 is never below L = 0)
+    PT_DEV float free_flight(f3 rP, f3 rD, float t) const {
+        float a;
+        const float b = medium_clip(md.v, rP, rD, t, &a);
+        const float L = max0(b - a);
+        if (!(L > 0.0f)) return -1.0f;
+        const float d = medium_flight(md.v.sigma_t, nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 0)));
+        return d < L ? a + d : -1.0f;
+    }
+    // MEDIUM: the scatter vertex's own factor; false: the albedo left nothing and the path ends
+    PT_DEV bool scatter_albedo(PathRegs& st) const {
+        const f3 fs = st.S() * mk(md.v.albedo[0], md.v.albedo[1], md.v.albedo[2]);
+        st.setS(fs);
+        return fs.x != 0.0f || fs.y != 0.0f || fs.z != 0.0f;
+    }
+    // MEDIUM: the scatter vertex at distance s ends: the next segment starts there, along a direction of the phase function; a lobe vertex
+    // for what follows, with its p_b kept where the rough vertices keep theirs
+    PT_DEV void scatter_direction(f3& rP, f3& rD, float s) {
+        if constexpr (MEDIUM) {
+            const float u1 = nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 1)), u2 = nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 2));
+            rP = madd(rD, s, rP);
+            rD = normalize3(medium_direction(md.v.g, rD, u1, u2, &gs.pb));
+            after_lobe = true;
+        }
+    }
     // LIGHTS: type 6 is live (option frosted; a run-time answer in the lights instances only: the frosted ones run only when it is)
     PT_DEV bool frost_live() const {
         if constexpr (LIGHTS) return lg.frost;
@@ -398,9 +445,11 @@ struct NeeHook {
     // sky); e: its radiance with ENV (the sky's texel or the triangle's emission, which light_sample_env has before the traversal).  Without ENV
     // e is not read: the emission of triangle li is loaded here, after the traversal, where those instances always read it.  LIGHTS: e comes
     // with the sample as with ENV; delta: an analytic light's sample, which no other strategy can find: its weight is p_b / p_l under MIS too
+    // MEDIUM: type -1 is a scatter vertex of the medium (p_b the phase function's, N and cosx not read); the sample carries md.T
     PT_DEV void light_add(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins, f3 w, float cosx,
                           float pl, float g, int li, f3 e, bool delta = false) const {
         float pb = cosx * kOneOverPi;
+        if constexpr (MEDIUM) if (type < 0) pb = medium_hg(md.v.g, dot3(rD, w));
         f3 fs = st.S();
         if constexpr (GLOSSY)
             if (type == 4) {
@@ -434,6 +483,7 @@ struct NeeHook {
         }
         if constexpr (!ENV && !LIGHTS) e = ldf3(p.mats[p.meta[li].mati].emission);
         e = ((e * (fl + fb)) * fs) * fr;
+        if constexpr (MEDIUM) e = e * md.T;
         if (wl < __builtin_inff()) st.setC(madd(e, g * wl, st.C()));
     }
 
@@ -508,7 +558,9 @@ struct NeeHook {
     // the other two's p_l take the factor 1 - P_ana.  Without ENV there is no sky branch
     PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins) {
         const float u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
-        const f3 o = madd(geo(N), 0.001f, hp);
+        const bool mvx = MEDIUM && type < 0;       // MEDIUM: a scatter vertex of the medium: the origin is hp itself, and no cosine is tested
+        f3 o = hp;
+        if (!mvx) o = madd(geo(N), 0.001f, hp);
         f3 w, e;
         float limit, pl, g;            // the search's cut, p_l, the emitter's cosine (1 for the sky and for an analytic light)
         int want;                      // what the shadow ray must return
@@ -569,8 +621,9 @@ struct NeeHook {
             limit = r * 1.0001f;
         }
         const float cosx = dot3(N, w);
-        if (!(cosx > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
-        if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // as in light_sample
+        if (!((mvx || cosx > 0.0f) && pl > 0.0f && pl < __builtin_inff())) return;
+        if constexpr (SMOOTH) if (!(mvx || dot3(geo(N), w) > 0.0f)) return;   // as in light_sample
+        if constexpr (MEDIUM) md.T = ins ? 1.0f : medium_transmittance(md.v, o, w, limit);      // (for a vertex outside a dielectric)
         if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
         if constexpr (LIGHTS) light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e, delta);
         else light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e);
@@ -624,15 +677,17 @@ struct NeeHook {
 // LENS (pt_set_lens; k_nee*_lens below; on the COAT code only): each sample starts on the thin-lens ray; metal bit 1: option coated
 // FROST (option frosted; k_nee*_frosted below; on the LENS code only): material type 6 is the rough-dielectric lobe vertex; metal bit 2: a lens is set
 // LIGHTS (pt_set_lights; k_nee*_lights below; on the FROST code only): a lobe vertex may sample an analytic light; metal bit 3: option frosted
+// MEDIUM (pt_set_medium; k_nee*_medium below; on the LIGHTS code only): between closest_hit and shade_hit a segment may end at a scatter vertex of
+// the medium; metal bit 4: a light set with a pickable light is held
 template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false,
-          bool FROST = false, bool LIGHTS = false>
+          bool FROST = false, bool LIGHTS = false, bool MEDIUM = false>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr,
-                      int metal = 0, const LensView* lens = nullptr, const LightsView* lights = nullptr) {
+                      int metal = 0, const LensView* lens = nullptr, const LightsView* lights = nullptr, const MediumView* medium = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS, MEDIUM> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (TEX) hook.tx.v = *tv;
     if constexpr (LENS) {
@@ -648,8 +703,10 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
     if constexpr (LIGHTS) {
         hook.lg.v = *lights;
         hook.lg.frost = (metal & 8) != 0;
-        hook.nee = lt.strategy != 0;       // the set is a light (the host launches these instances only for a set with a pickable light)
+        // the set is a light (the host launches the lights instances only for a set with a pickable light; the medium ones say whether one is held)
+        if (!MEDIUM || (metal & 16) != 0) hook.nee = lt.strategy != 0;
     }
+    if constexpr (MEDIUM) hook.md.v = *medium;
     const int camX = (int)p.cam.XM;
     unsigned rendered = 0;                     // TILED: pixels this lane rendered (statistic "samples", as k_render counts them)
     if constexpr (TILED) npix = (long long)p.n_tiles * 64;      // work items: 64 per listed tile
@@ -698,12 +755,29 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
             for (int k = 0; k < p.iterations; ++k) {
                 float t;
                 const int ti = closest_hit<MODE, false>(sv, rP, rD, stk, &t, &wc);
-                if (ti < 0) {                      // prog.cl:367-376: black without an environment
-                    if constexpr (ENV) hook.miss(st, rD, k);
-                    break;
+                if constexpr (MEDIUM) {
+                    // the free flight of the segment; then the scatter vertex: its factor here, its light sample in shade_hit's one call of
+                    // light_sample (the lane does nothing else there), its new direction after it
+                    hook.k = k;
+                    float ts = -1.0f;              // the distance of this segment's scatter vertex; < 0: it reaches its hit or misses
+                    if (!inside) ts = hook.free_flight(rP, rD, ti < 0 ? __builtin_inff() : t);
+                    const bool sc = ts >= 0.0f;
+                    hook.md.sc = sc;
+                    if (ti < 0 && !sc) {
+                        if constexpr (ENV) hook.miss(st, rD, k);
+                        break;
+                    }
+                    if (sc && !hook.scatter_albedo(st)) break;
+                    shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, sc ? ts : t, &hook);
+                    if (sc) hook.scatter_direction(rP, rD, ts);
+                } else {
+                    if (ti < 0) {                  // prog.cl:367-376: black without an environment
+                        if constexpr (ENV) hook.miss(st, rD, k);
+                        break;
+                    }
+                    hook.k = k;
+                    shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, t, &hook);
                 }
-                hook.k = k;
-                shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, t, &hook);
                 if constexpr (SMOOTH) if (hook.sm.dead) break;
             }
             acc = running_mean(acc, st.C(), s);
@@ -871,6 +945,28 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_lights(RenderParams p, 
     nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg);
 }
 
+// the medium instances (a medium with sigma_t > 0 is held): the lights kernels with the medium's view as one more argument; flags bit 4: a light
+// set with a pickable light is held (else lg is an empty set with P_ana = 0, and without an emitter or a sky no light sample is taken)
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_medium(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
+                                                      long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg, &mv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_medium(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
+                                                          MediumView mv, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg, &mv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_medium(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv) {
+    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg, &mv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_medium(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
+                                                                MediumView mv) {
+    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -909,6 +1005,16 @@ static hipError_t launch_nee_family(K k, KE ke, KT kt, KET ket, const RenderPara
 }
 #define NEE_PICK(K) [](auto s) { return K<s.mode, s.block>; }
 
+// The medium family is compiled in a translation unit of its own (pt_nee_medium.hip includes this file with PT_NEE_MEDIUM_TU defined and
+// gets launch_nee_medium only): compiled next to the other families, its instances cost 48 of them two instructions in their uv fetch
+// (the compiler no longer derives for a helper they share that its triangle index is never negative; profiles/medium/README.md)
+hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
+#ifdef PT_NEE_MEDIUM_TU
+hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+    return launch_nee_family<kWideAll>(NEE_PICK(k_nee_medium), NEE_PICK(k_nee_env_medium), NEE_PICK(k_nee_tiles_medium), NEE_PICK(k_nee_env_tiles_medium), p, lt, nl, npix,
+                                       cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium);
+}
+#else
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     switch (nl.family) {
     case kNeePlain:
@@ -935,10 +1041,12 @@ hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch
                                      cu_count, stream, nl.vn, nl.tv, nl.flags & 7, nl.lens);
     case kNeeLights:
         return launch_nee_family<kWideAll>(NEE_PICK(k_nee_lights), NEE_PICK(k_nee_env_lights), NEE_PICK(k_nee_tiles_lights), NEE_PICK(k_nee_env_tiles_lights), p, lt, nl, npix,
-                                     cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights);
+                                     cu_count, stream, nl.vn, nl.tv, nl.flags & 15, nl.lens, nl.lights);
+    case kNeeMedium: return launch_nee_medium(p, lt, nl, npix, cu_count, stream);
     }
     return hipErrorInvalidValue;
 }
+#endif
 #undef NEE_PICK
 
 }  // namespace ptamd

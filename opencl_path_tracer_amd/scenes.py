@@ -41,6 +41,8 @@ class SceneSpec:
     lights: list = field(default_factory=list)       # optional: analytic lights as api.light_from takes them, dict(kind="point" | "spot" |
                                                      # "directional", ...) (Scene.load applies them with Scene.set_lights)
     lights_select: float = 0.5                       # ... and set_lights' select
+    medium: dict = field(default_factory=dict)       # optional: a homogeneous medium, Scene.set_medium's arguments: dict(sigma_t=, albedo=,
+                                                     # g=, bounds=(lo, hi)) (Scene.load applies it)
 
     @property
     def ntris(self):
@@ -141,7 +143,10 @@ LAMP_LIGHT_Y = 990.0           # cornell_box(lamp="point" / "spot"): the light h
 LAMP_SPOT_DEGREES = (60.0, 90.0)      # ... and the spot's inner and outer half angles
 
 
-def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False, frosted=False, lamp="quad"):
+CORNELL_ROOM = ((-100.0, 0.0, -1000.0), (1100.0, 1000.0, 1000.0))      # cornell_box(fog=...): the fog's box, the room wall to wall
+
+
+def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False, frosted=False, lamp="quad", fog=0.0):
     """Scene CB of SURVEY 8(d): 12 wall/lamp triangles + two tessellated spheres
     (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects.
     smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals).
@@ -157,7 +162,9 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
     below its centre (Scene.set_lights through Scene.load; only render_nee renders the scene then).  The quad of area A and emission E
     radiates pi E A; a point light of intensity I radiates 4 pi I, so I = E A / 4; the spot points down, full inside 60 degrees of its
     axis and dark from 90 on, and the smoothstep between integrates to half its width: 2 pi I (1 - cos 60 + cos 60 / 2), so
-    I = E A / 1.5."""
+    I = E A / 1.5.
+    fog: sigma_t > 0 fills the room (CORNELL_ROOM) with a white medium of that extinction per unit, albedo 0.9 and g = 0.6
+    (Scene.set_medium through Scene.load; only render_nee renders the scene then).  1e-3 is a mean free path of the room's width."""
     if coated and frosted:
         raise ValueError("cornell_box: coated and frosted both replace the glass sphere's material")
     if lamp not in ("quad", "point", "spot"):
@@ -202,6 +209,44 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
         spec.uvs = [uv, None, None]
         spec.textures = [(checker_texture(8, (1.0, 1.0, 1.0), (0.25, 0.25, 0.25)), dict(filter=0, srgb=0))]
         spec.material_textures = {WHITE_DIFFUSE: 0}
+    if fog > 0.0:
+        spec.medium = dict(sigma_t=float(fog), albedo=(0.9, 0.9, 0.9), g=0.6, bounds=CORNELL_ROOM)
+    return spec
+
+
+def light_shaft(sigma_t=0.12):
+    """The beam picture for Scene.set_medium: a dark closed room (x in [-6, 6], y in [-3, 5], z in [-1, 14]) with grey walls, seen from the
+    origin along +z; a spot light under the ceiling at the back left shines down and to the right through a slot (1.2 wide along x, 5
+    deep along z) in a black occluder at y = 3, and bounded fog (albedo 0.95, g = 0.7, the room's own box) makes the shaft visible between
+    the slot and the lit patch on the floor.  No emitter and no sky: only the spot lights the scene (Scene.set_lights through
+    Scene.load), and only render_nee renders it."""
+    mats = [
+        ((0.5, 0.5, 0.5), (0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0), 1.0, 0),             # 0 walls
+        ((0.02, 0.02, 0.02), (0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0), 1.0, 0),          # 1 the occluder
+    ]
+
+    def quad(a, b, c, d):
+        return [(a, b, c), (a, c, d)]
+    x0, x1, y0, y1, z0, z1 = -6.0, 6.0, -3.0, 5.0, -1.0, 14.0
+    tris, mo = [], []
+    for q, m in ((quad((x0, y0, z0), (x1, y0, z0), (x1, y0, z1), (x0, y0, z1)), 0),      # floor
+                 (quad((x0, y1, z0), (x0, y1, z1), (x1, y1, z1), (x1, y1, z0)), 0),      # ceiling
+                 (quad((x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)), 0),      # back
+                 (quad((x0, y0, z0), (x0, y0, z1), (x0, y1, z1), (x0, y1, z0)), 0),      # left
+                 (quad((x1, y0, z0), (x1, y1, z0), (x1, y1, z1), (x1, y0, z1)), 0),      # right
+                 (quad((x0, y0, z0), (x0, y1, z0), (x1, y1, z0), (x1, y0, z0)), 0)):     # behind the camera
+        tris += q
+        mo += [m] * len(q)
+    sx0, sx1, sz0, sz1, oy = -2.6, -1.4, 6.0, 11.0, 3.0                                   # the slot in the occluder
+    for q in (quad((x0, oy, z0), (sx0, oy, z0), (sx0, oy, z1), (x0, oy, z1)), quad((sx1, oy, z0), (x1, oy, z0), (x1, oy, z1), (sx1, oy, z1)),
+              quad((sx0, oy, z0), (sx1, oy, z0), (sx1, oy, sz0), (sx0, oy, sz0)), quad((sx0, oy, sz1), (sx1, oy, sz1), (sx1, oy, z1), (sx0, oy, z1))):
+        tris += q
+        mo += [1] * len(q)
+    spec = SceneSpec(materials=mats, name="light_shaft", shift=(-500.0, -500.0, 1299.0378))
+    spec.objects.append((np.asarray(tris, dtype=np.float32), np.asarray(mo, dtype=np.uint16)))
+    spec.lights = [dict(kind="spot", position=(-3.2, 4.8, 8.5), direction=(0.45, -1.0, 0.0), intensity=(900.0, 850.0, 700.0),
+                        inner_degrees=25.0, outer_degrees=40.0)]
+    spec.medium = dict(sigma_t=float(sigma_t), albedo=(0.95, 0.95, 0.95), g=0.7, bounds=((x0, y0, z0), (x1, y1, z1)))
     return spec
 
 
