@@ -953,7 +953,10 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value);
  * HIP-event durations of the dominant kernel), "kernel_launches", "bvh_nodes", "bvh_depth", "stack_entries"
  * (per-lane BVH2 traversal stack: deepest interior node + 2), "bvh_build_ms" (pt_upload_triangles as a whole),
  * "bvh_on_device", "triangles", "lds_bytes", "waves_per_simd", "node_mode" (0 whole tree in LDS, 1 BVH2 nodes through
- * L1/L2, 2 treelet, 3 4-wide nodes through L1/L2), "treelet_nodes", "wide_nodes" (how many 4-wide nodes),
+ * L1/L2, 2 treelet, 3 4-wide nodes through L1/L2), "nee_family" / "nee_form" / "nee_block" (what the last launch of
+ * pt_render_nee or of an NEE round of pt_render_adaptive_ex took: the kernel family 0..8 -- plain, smooth, tex, glossy,
+ * coated, lens, frosted, lights, medium --, the form -- bit 0 an environment is drawn, bit 1 tiled -- and the workgroup
+ * size; -1 each before the first such launch), "treelet_nodes", "wide_nodes" (how many 4-wide nodes),
  * "wide_pending" (their worst-case stack), "flat_triangles", "flat_boxes" (their distinct bounding boxes), and with
  * count_work: "node_visits", "tri_tests", "wave_node_steps", "wave_tri_steps", "tile_lane_steps", "wave_shade_steps",
  * "wave_trips", "wave_rounds" */

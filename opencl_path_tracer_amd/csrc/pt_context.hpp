@@ -275,6 +275,7 @@ struct pt_context {
     int64_t kernel_launches = 0;
     size_t last_lds_bytes = 0;
     int last_waves_per_simd = 4;
+    int nee_family = -1, nee_form = -1, nee_block = -1;      // what the last NEE launch took (launch_nee_noted); -1: none yet
 
     std::string err;
     char info[256] = {0};
@@ -317,6 +318,9 @@ int texture_prepare(pt_context* ctx, TexView* tv, bool force = false);
 // pt_host.cpp: the NEE launch the context's options, materials and lens ask for (NeeLaunch, pt_internal.hpp), with the vertex normals and
 // textures prepared on the device; nee_on = false (no NEE launch will follow): nothing is prepared.  env and tiled are left clear: the caller sets them
 int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch* nl);
+// pt_host.cpp: launch_nee on the context's stream; what the launch took -- the family, the form (bit 0 an environment is drawn, bit 1
+// tiled) and the workgroup size the launcher chose -- is kept for pt_get_stat ("nee_family", "nee_form", "nee_block")
+hipError_t launch_nee_noted(pt_context* ctx, const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl);
 int host_threads(const pt_context* ctx);                        // threads of the host-side scene path (option build_threads)
 
 #define PT_HIP(ctx, call)                                                                   \

@@ -1891,6 +1891,9 @@ template <int MODE, int BLOCK>
 struct LaneShape {
     static constexpr int mode = MODE, block = BLOCK;
 };
+// the workgroup size of the calling thread's last launch_lanes_t launch (host data; 0: none since the caller cleared it): how a caller
+// reports the shape its launch took without a second copy of the switch statements that choose it (launch_nee)
+inline thread_local int t_lanes_block = 0;
 // `mark` is keyed on (PICK, MODE, BLOCK) -- PICK is the caller's own lambda -- so there is one per kernel instance
 template <int MODE, int BLOCK, class PICK, class... A>
 hipError_t launch_lanes_t(PICK pick, const RenderParams& p, int64_t n, int cu_count, hipStream_t stream, A... args) {
@@ -1903,6 +1906,7 @@ hipError_t launch_lanes_t(PICK pick, const RenderParams& p, int64_t n, int cu_co
     const int blocks = (int)std::min<long long>(need, (long long)cu_count * (2048 / BLOCK));
     if (p.stack_ovf && (long long)blocks * BLOCK > (long long)p.stack_ovf_lanes) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK), lds, stream, p, args...);
+    t_lanes_block = BLOCK;
     return hipGetLastError();
 }
 template <class PICK, class... A>

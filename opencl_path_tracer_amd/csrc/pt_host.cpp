@@ -934,6 +934,18 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
     nl->flags = (ctx->glossy ? 1 : 0) | (ctx->coated ? 2 : 0) | (lens_on(ctx) ? 4 : 0) | (frosted ? 8 : 0) | (lights_on(ctx) ? 16 : 0);
     return PT_OK;
 }
+hipError_t launch_nee_noted(pt_context* ctx, const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl) {
+    NeeLaunch noted = nl;
+    int block = 0;
+    noted.block = &block;
+    const hipError_t e = launch_nee(p, lt, noted, ctx->npix, ctx->cu_count, ctx->stream);
+    if (block > 0) {                   // (a round over an empty tile list launches nothing and leaves the record as it was)
+        ctx->nee_family = nl.family;
+        ctx->nee_form = (nl.env ? 1 : 0) | (nl.tiled ? 2 : 0);
+        ctx->nee_block = block;
+    }
+    return e;
+}
 }  // namespace ptamd
 extern "C" {
 int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples, int32_t strategy) {
@@ -963,7 +975,7 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     note_frame(ctx, p.first_sample, cam);
     EventPair* ep;
     if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-    PT_HIP(ctx, launch_nee(p, lt, nl, ctx->npix, ctx->cu_count, ctx->stream));
+    PT_HIP(ctx, launch_nee_noted(ctx, p, lt, nl));
     if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
     ctx->current_sample += nsamples;
     return PT_OK;
@@ -1725,6 +1737,9 @@ int pt_get_stat(pt_context* ctx, const char* key, double* out) {
         *out = (double)p.node_mode;
         return PT_OK;
     }
+    if (k == "nee_family") { *out = (double)ctx->nee_family; return PT_OK; }
+    if (k == "nee_form") { *out = (double)ctx->nee_form; return PT_OK; }
+    if (k == "nee_block") { *out = (double)ctx->nee_block; return PT_OK; }
     if (k == "kernel_launches") { *out = (double)ctx->kernel_launches; return PT_OK; }
     PT_NEED_DEVICE(ctx);
     PT_HIP(ctx, hipSetDevice(ctx->device));

@@ -486,6 +486,8 @@ struct NeeLaunch {
     LensView lens;               // read from kNeeLens on
     LightsView lights;           // read from kNeeLights on
     MediumView medium;           // read by kNeeMedium
+    int* block;                  // out, may be null: the workgroup size the launch took, as launch_lanes / launch_lanes_env_tiles_smooth chose
+                                 // it (0: nothing was launched, an empty tile list)
 };
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
 // thin lens (pt_lens.hip): pt_debug_lens's kernel, {gid, S} in and 6 floats out per item; pt_focus_at's, the axial distance of pixel gid's

@@ -728,7 +728,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
             pr.n_tiles = n_active;
             EventPair* ep;
             if ((rc = time_begin(ctx, &ep)) != PT_OK) return rc;
-            PT_HIP(ctx, launch_nee(pr, lt, nl, ctx->npix, ctx->cu_count, ctx->stream));
+            PT_HIP(ctx, launch_nee_noted(ctx, pr, lt, nl));
             if ((rc = time_end(ctx, ep)) != PT_OK) return rc;
         } else if ((rc = launch_megakernel(ctx, pr, list, n_active)) != PT_OK) {
             return rc;

@@ -1015,7 +1015,7 @@ hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const Ne
                                        cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium);
 }
 #else
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+static hipError_t launch_nee_of_family(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     switch (nl.family) {
     case kNeePlain:
         return launch_nee_family<0>(NEE_PICK(k_nee), NEE_PICK(k_nee_env), NEE_PICK(k_nee_tiles), NEE_PICK(k_nee_env_tiles), p, lt, nl, npix, cu_count, stream);
@@ -1045,6 +1045,12 @@ hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch
     case kNeeMedium: return launch_nee_medium(p, lt, nl, npix, cu_count, stream);
     }
     return hipErrorInvalidValue;
+}
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+    t_lanes_block = 0;
+    const hipError_t e = launch_nee_of_family(p, lt, nl, npix, cu_count, stream);
+    if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit or in pt_nee_medium.hip's)
+    return e;
 }
 #endif
 #undef NEE_PICK
