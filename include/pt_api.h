@@ -952,8 +952,11 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value);
 /* stats: "segments" path segments executed since the last reset, "samples", "kernel_ms" (sum of
  * HIP-event durations of the dominant kernel), "kernel_launches", "bvh_nodes", "bvh_depth", "stack_entries"
  * (per-lane BVH2 traversal stack: deepest interior node + 2), "bvh_build_ms" (pt_upload_triangles as a whole),
- * "bvh_on_device", "triangles", "lds_bytes", "waves_per_simd", "node_mode" (0 whole tree in LDS, 1 BVH2 nodes through
- * L1/L2, 2 treelet, 3 4-wide nodes through L1/L2), "nee_family" / "nee_form" / "nee_block" (what the last launch of
+ * "bvh_on_device", "bvh_median_splits" (ranges the host builder split at the median in the last pt_upload_triangles --
+ * coincident centroids, a cost that is not finite, or a depth the traversal stack could not take; the device SAH builder
+ * hands such a scene back to the host, so the count is 0 whenever "bvh_on_device" is 1), "triangles", "lds_bytes",
+ * "waves_per_simd", "node_mode" (0 whole tree in LDS, 1 BVH2 nodes through L1/L2, 2 treelet, 3 4-wide nodes through
+ * L1/L2), "nee_family" / "nee_form" / "nee_block" (what the last launch of
  * pt_render_nee or of an NEE round of pt_render_adaptive_ex took: the kernel family 0..8 -- plain, smooth, tex, glossy,
  * coated, lens, frosted, lights, medium --, the form -- bit 0 an environment is drawn, bit 1 tiled -- and the workgroup
  * size; -1 each before the first such launch), "treelet_nodes", "wide_nodes" (how many 4-wide nodes),

@@ -157,6 +157,7 @@ struct BvhBuilder {
     std::vector<Node64> nodes;
     std::vector<int32_t> order;  // packed triangle order (add-order indices)
     int max_depth_seen = 0;
+    int median_splits = 0;       // ranges split at the median (counted with relaxed atomic adds: split() runs on several threads)
     int max_leaf = kMaxLeaf;     // leaf size limit of this attempt
     bool force_leaf = false;     // true: every subtree of <= max_leaf triangles becomes a leaf
     float visit_cost = 1.0f;     // SAH price of one node visit, in exact triangle tests
@@ -325,6 +326,7 @@ struct BvhBuilder {
             if (mid == lo || mid == hi || depth + 1 + need_levels(big) > kMaxDepth) median = true;
         }
         if (median) {
+            __atomic_fetch_add(&median_splits, 1, __ATOMIC_RELAXED);
             int a = 0;
             float e = -1.f;
             for (int k = 0; k < 3; ++k) { float ex = cb.hi[k] - cb.lo[k]; if (ex > e) { e = ex; a = k; } }
@@ -674,6 +676,7 @@ int build_and_pack(pt_context* ctx) {
     if (rc != PT_OK) return rc;
     clk.lap("SAH build");
     ctx->n_flat = (int)flat.size();
+    ctx->bvh_median_splits = bld.median_splits;
     if (bld.max_depth_seen > kMaxDepth) return fail(ctx, PT_ESCENE, "internal: BVH deeper than the traversal stack");
     ctx->bvh_depth = bld.max_depth_seen;
     ctx->nodes.swap(bld.nodes);
@@ -1237,6 +1240,7 @@ int pt_upload_triangles(pt_context* ctx) {
     ctx->nee_valid = false;          // and the light table its packed order
     ctx->vnormals_dirty = true;      // and the packed vertex normals
     ctx->vuvs_dirty = true;          // and uvs
+    ctx->bvh_median_splits = 0;      // (only the host builder splits at the median: build_and_pack counts)
     if (ctx->tri_shift != (int32_t)ctx->tris.size())
         return fail(ctx, PT_EINVAL, "triangles were added after the last end_Obj; close the object first (main.cpp:536)");
     const auto t0 = std::chrono::steady_clock::now();

@@ -122,6 +122,7 @@ struct pt_context {
     int timing = 0;
     int count_work = 0;
     int bvh_on_device = 0;
+    int bvh_median_splits = 0;   // ranges the host builder split at the median in the last upload (what the device SAH builder hands back)
     double bvh_build_ms = 0.0;
     int cu_count = 256;
     int persistent = 1;   // 1: megakernel waves pull tiles from a counter (grid = what fits the chip)

@@ -1719,6 +1719,7 @@ int pt_get_stat(pt_context* ctx, const char* key, double* out) {
     if (k == "stack_entries") { *out = (double)stack_entries_for(ctx->interior_depth); return PT_OK; }
     if (k == "bvh_build_ms") { *out = ctx->bvh_build_ms; return PT_OK; }
     if (k == "bvh_on_device") { *out = (double)ctx->bvh_on_device; return PT_OK; }
+    if (k == "bvh_median_splits") { *out = (double)ctx->bvh_median_splits; return PT_OK; }
     if (k == "triangles") { *out = (double)ctx->orig.size(); return PT_OK; }
     if (k == "lds_bytes") { *out = (double)ctx->last_lds_bytes; return PT_OK; }
     if (k == "waves_per_simd") { *out = (double)ctx->last_waves_per_simd; return PT_OK; }

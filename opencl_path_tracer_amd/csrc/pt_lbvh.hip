@@ -223,7 +223,7 @@ __global__ void __launch_bounds__(256) k_ploc_nn(const Box* cbox, int m, int* nn
         const int j = i + d;
         if (d == 0 || j < 0 || j >= m) continue;
         const float c = union_half_area(me, tile[threadIdx.x + R + d]);
-        bool better = c < best;
+        bool better = c < best || bj < 0;       // (the first candidate always: a union area that overflows to +inf is still a partner)
         if (c == best && bj >= 0) {
             const int a0 = min(i, j), a1 = max(i, j), b0 = min(i, bj), b1 = max(i, bj);
             better = a0 < b0 || (a0 == b0 && a1 < b1);
