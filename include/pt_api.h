@@ -394,6 +394,48 @@ int pt_get_medium(const pt_context* ctx, pt_medium* m);
  * (u1, u2) around D (unit), its p_b, T of Clip(P, D, limit), 0}.  PT_EINVAL when no medium with sigma_t > 0 is held */
 int pt_debug_medium(pt_context* ctx, const float* in, int64_t n, float* out);
 
+/* ---- a voxel density grid for the medium (new: opt-in with pt_set_medium_density; smoke, clouds, mist that thins with height) ----
+ * nx x ny x nz equal cells of the medium's box [lo, hi]; voxel (i, j, k), i along x, holds density[(k ny + j) nx + i], and the extinction
+ * at a point of it is sigma_t x density[voxel]; the albedo and g stay pt_medium's.  The grid is kept as float32 in the context like the
+ * medium -- uploads keep it, every rank of a tiled frame sets its own copy, a host-only context validates and stores -- and is live only
+ * while a medium with sigma_t > 0 is held too.  Live, pt_render_nee and the NEE path of pt_render_adaptive_ex launch the grid instances
+ * of k_nee (stat "nee_family" 9), and return PT_EINVAL naming the bound when lo or hi is infinite on an axis, checked before the device.
+ * pt_clear_medium_density restores the homogeneous medium bit for bit.  The guides, the denoisers and temporal accumulation keep the
+ * medium-free view, and the other render paths refuse as they do for any medium with sigma_t > 0.
+ * The estimator is that of pt_set_medium above with the free flight and the transmittance replaced by a walk; the streams and their
+ * dimensions, steps 1-4 of the scatter vertex, the `inside` rule and the weights are unchanged.  All float32, no contraction:
+ * cell = (hi - lo) / (float)n and icell = (float)n / (hi - lo) per axis (IEEE divides, computed once when the launch is prepared).
+ * Walk(P, D, t, tau): [a, b] = Clip(P, D, t); nothing to do unless L = max(b - a, 0) > 0.  t_cur = a, acc = 0.  Per axis, with i = 1 / D.axis
+ *   (Clip's): the index is floorf((fma(D.axis, a, P.axis) - lo) icell), raised to 0 where it is not above 0 (a NaN too) and lowered to
+ *   n - 1 where it is not below; if |i| is finite: step = +1 for i > 0 else -1, kb = index + (1 for i > 0 else 0), the plane is hi when
+ *   kb = n else lo + (float)kb cell, tnext = (plane - P.axis) i, tdelta = cell |i|; else the axis never steps: tnext = +inf.
+ *   Then at most nx + ny + nz + 3 times (a counted loop: termination does not depend on rounding):
+ *     rho = density[(k ny + j) nx + i], sigma = sigma_t rho, t_exit = min(min(min(tnext_x, tnext_y), tnext_z), b) (min(p, q): q < p ? q : p),
+ *     seg = max(t_exit - t_cur, 0);
+ *     if sigma > 0: d = (tau - acc) / sigma, and the walk scatters in this voxel iff d < seg, at s = t_cur + d (the device skips the divide
+ *       where tau - acc >= 2 (sigma seg), which decides the same);
+ *     else, or without a scatter: acc = acc + sigma seg; the walk ends if t_exit >= b; else the axis of the smallest tnext steps, x before y
+ *     before z on ties (x if tnext_x <= tnext_y and tnext_x <= tnext_z, else y if tnext_y <= tnext_z, else z): index += step, tnext +=
+ *     tdelta, and the walk ends if the index left [0, n - 1]; t_cur = t_exit.
+ * Free flight on segment k: u as for pt_medium (dimension 0 of S ^ 0x5bd1e995), tau = -log1pf(-u), Walk(P, D, t, tau); the segment scatters
+ *   iff the walk does, at x = fma(D, s, P); a surviving segment takes no factor.
+ * Transmittance of a light sample: T = expf(-acc) of Walk(o, w, limit, +inf) (no voxel reaches tau); T = 1 exactly when acc = 0.
+ * A 1 x 1 x 1 grid of density 1.0f computes d = tau / sigma_t, d < b - a, s = a + d and T = expf(-(sigma_t (b - a))): the homogeneous
+ * medium's frame bit for bit (tnext is Clip's own far slab on every axis, so t_exit = b). */
+#define PT_GRID_MAX_DIM 256
+/* PT_EINVAL, naming pt_set_medium_density, with the held grid left as it was: ctx or density NULL, a dimension outside [1, PT_GRID_MAX_DIM],
+ * a density that is negative or not finite */
+int pt_set_medium_density(pt_context* ctx, const float* density, int32_t nx, int32_t ny, int32_t nz);
+int pt_clear_medium_density(pt_context* ctx);
+/* the held grid: dims = {nx, ny, nz} ({0, 0, 0} when none is held) and up to cap densities into out (out may be NULL when cap is 0);
+ * returns 1 if a grid is held, 0 if not, PT_EINVAL for a NULL ctx or dims or a negative cap */
+int pt_debug_medium_density(pt_context* ctx, float* out, int64_t cap, int32_t dims[3]);
+/* the device walk of the live grid on given numbers, n items: in, 12 floats each {P.xyz, D.xyz (unit), t, u, limit, 3 spare}; out, 8 floats
+ * each {a, b of Clip(P, D, t), 1 if Walk(P, D, t, -log1pf(-u)) scatters else 0, its s (-1 without a scatter), acc of Walk(P, D, t, +inf)
+ * (the optical depth over [0, t]), T over [0, limit], the voxels the free-flight walk visited, the linear index of the voxel it scattered
+ * in (-1 without)}.  PT_EINVAL when no grid is live or a bound of the box is infinite */
+int pt_debug_grid(pt_context* ctx, const float* in, int64_t n, float* out);
+
 /* ---- smooth shading from vertex normals for pt_render_nee (new: opt-in with option "smooth_normals"; the reference shades with the
  * triangle's geometric normal only) -----------
  * Authoring (host data; all of it works on a host-only context, none of it rebuilds the BVH).  Triangles are counted in add order over
@@ -957,8 +999,8 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value);
  * hands such a scene back to the host, so the count is 0 whenever "bvh_on_device" is 1), "triangles", "lds_bytes",
  * "waves_per_simd", "node_mode" (0 whole tree in LDS, 1 BVH2 nodes through L1/L2, 2 treelet, 3 4-wide nodes through
  * L1/L2), "nee_family" / "nee_form" / "nee_block" (what the last launch of
- * pt_render_nee or of an NEE round of pt_render_adaptive_ex took: the kernel family 0..8 -- plain, smooth, tex, glossy,
- * coated, lens, frosted, lights, medium --, the form -- bit 0 an environment is drawn, bit 1 tiled -- and the workgroup
+ * pt_render_nee or of an NEE round of pt_render_adaptive_ex took: the kernel family 0..9 -- plain, smooth, tex, glossy,
+ * coated, lens, frosted, lights, medium, grid (a medium with a live density grid) --, the form -- bit 0 an environment is drawn, bit 1 tiled -- and the workgroup
  * size; -1 each before the first such launch), "treelet_nodes", "wide_nodes" (how many 4-wide nodes),
  * "wide_pending" (their worst-case stack), "flat_triangles", "flat_boxes" (their distinct bounding boxes), and with
  * count_work: "node_visits", "tri_tests", "wave_node_steps", "wave_tri_steps", "tile_lane_steps", "wave_shade_steps",

@@ -130,6 +130,12 @@ public:
     // render_nee and the NEE path of render_adaptive render; uploads keep it
     void set_medium(const pt_medium& m) { ck(pt_set_medium(ctx, &m)); }
     void clear_medium() { ck(pt_clear_medium(ctx)); }
+    // a voxel density for that medium (pt_set_medium_density): density[(k * ny + j) * nx + i] over nx x ny x nz equal cells of its box, which
+    // must be finite to render; the extinction is sigma_t x density.  medium_density reads it back (returns whether one is held)
+    void set_medium_density(const float* density, int32_t nx, int32_t ny, int32_t nz) { ck(pt_set_medium_density(ctx, density, nx, ny, nz)); }
+    void clear_medium_density() { ck(pt_clear_medium_density(ctx)); }
+    bool medium_density(float* out, int64_t cap, int32_t dims[3]) { return ck(pt_debug_medium_density(ctx, out, cap, dims)) == 1; }
+    void debug_grid(const float* in, int64_t n, float* out) { ck(pt_debug_grid(ctx, in, n, out)); }
     // vertex normals for smooth shading (set_option("smooth_normals", 1); render_nee only): normals = count x 9 floats, n1 n2 n3 per
     // triangle in add order starting at first_triangle; compute_vertex_normals derives them per object (obj = -1: every object)
     void set_vertex_normals(const float* normals, int64_t count, int64_t first_triangle = 0) { ck(pt_set_vertex_normals(ctx, first_triangle, count, normals)); }

@@ -54,6 +54,7 @@ EXPORTS = [
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_lights_defaults", "pt_set_lights", "pt_clear_lights", "pt_debug_lights",
     "pt_medium_defaults", "pt_set_medium", "pt_clear_medium", "pt_get_medium", "pt_debug_medium",
+    "pt_set_medium_density", "pt_clear_medium_density", "pt_debug_medium_density", "pt_debug_grid",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
     "pt_render_aovs", "pt_read_aovs", "pt_aov_defaults", "pt_render_aovs_ex", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
@@ -154,6 +155,10 @@ def _load():
     sig("pt_clear_medium", C.c_int, vp)
     sig("pt_get_medium", C.c_int, vp, vp)
     sig("pt_debug_medium", C.c_int, vp, vp, i64, vp)
+    sig("pt_set_medium_density", C.c_int, vp, vp, i32, i32, i32)
+    sig("pt_clear_medium_density", C.c_int, vp)
+    sig("pt_debug_medium_density", C.c_int, vp, vp, i64, vp)
+    sig("pt_debug_grid", C.c_int, vp, vp, i64, vp)
     sig("pt_image_read_pfm", C.c_int, C.c_char_p, vp, i64, C.POINTER(i32), C.POINTER(i32))
     sig("pt_read_variance", C.c_int, vp, vp, i64)
     sig("pt_device_variance", vp, vp)
@@ -280,6 +285,7 @@ def adaptive_rounds(min_spp, max_spp):
 
 
 PT_NEE_BSDF, PT_NEE_LIGHT, PT_NEE_MIS = 0, 1, 2
+PT_GRID_MAX_DIM = 256          # pt_set_medium_density: the largest dimension of a density grid
 PT_MATH_SQRT, PT_MATH_RSQRT, PT_MATH_DIV_GRID, PT_MATH_DIV_RANDOM, PT_MATH_DIV_NORMAL, PT_MATH_LCG = 0, 1, 2, 3, 4, 5   # pt_debug_math enumerations
 # pt_debug_spec functions, and the 32-bit words each takes and gives per item
 (PT_SPEC_SINCOS, PT_SPEC_SINCOS_SK, PT_SPEC_POW, PT_SPEC_POW_SK, PT_SPEC_POW5, PT_SPEC_LCG, PT_SPEC_DIFFUSE, PT_SPEC_DIFFUSE_SK,
@@ -821,6 +827,41 @@ class Scene:
         self._ck(LIB.pt_debug_medium(self._h, _ptr(items), items.shape[0], _ptr(out)))
         return out
 
+    # -- the medium's voxel density (include/pt_api.h pins the walk)
+    def set_medium_density(self, density):
+        """pt_set_medium_density: density (nz, ny, nx), finite and >= 0, each dimension in [1, PT_GRID_MAX_DIM]: the extinction in voxel
+        (i, j, k) of nx x ny x nz equal cells of the medium's box is sigma_t x density[k, j, i].  Kept as float32; live while a medium
+        with sigma_t > 0 is held, whose box must then be finite to render."""
+        d = np.asarray(density)
+        if d.ndim != 3:
+            raise ValueError("set_medium_density: density must have shape (nz, ny, nx)")
+        d = np.ascontiguousarray(d, dtype=np.float32)
+        self._ck(LIB.pt_set_medium_density(self._h, _ptr(d), d.shape[2], d.shape[1], d.shape[0]))
+
+    def clear_medium_density(self):
+        self._ck(LIB.pt_clear_medium_density(self._h))
+
+    def medium_density(self):
+        """pt_debug_medium_density: the held grid as (nz, ny, nx) float32, or None when none is held."""
+        dims = (C.c_int32 * 3)()
+        rc = LIB.pt_debug_medium_density(self._h, None, 0, dims)
+        if rc < 0:
+            self._ck(rc)
+        if rc != 1:
+            return None
+        out = np.empty((dims[2], dims[1], dims[0]), dtype=np.float32)
+        self._ck(LIB.pt_debug_medium_density(self._h, _ptr(out), out.size, dims))
+        return out
+
+    def debug_grid(self, items):
+        """pt_debug_grid: items (n, 12) float32 {P, D (unit), t, u, limit, 3 spare} -> (n, 8) float32 {a, b of the clip of [0, t] to the
+        box, 1 if the free flight of u scatters else 0, its distance s (-1 without), the optical depth over [0, t], T over [0, limit],
+        the voxels visited, the linear voxel index of the scatter (-1 without)}, by the walk the grid k_nee instances call."""
+        items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 12)
+        out = np.empty((items.shape[0], 8), dtype=np.float32)
+        self._ck(LIB.pt_debug_grid(self._h, _ptr(items), items.shape[0], _ptr(out)))
+        return out
+
     # -- the rough dielectric of material type 6 (option "frosted")
     def debug_frosted(self, items):
         """pt_debug_frosted: items (n, 12) float32 {N, D, alpha, F0, eta, rnd1, rnd2, u_sel} -> (n, 10) float32 {w before normalisation
@@ -868,6 +909,8 @@ class Scene:
             self.set_lights(spec.lights, select=getattr(spec, "lights_select", 0.5))
         if getattr(spec, "medium", None):                       # optional: set_medium's arguments as a dict
             self.set_medium(**spec.medium)
+        if getattr(spec, "medium_density", None) is not None:   # optional: set_medium_density's array
+            self.set_medium_density(spec.medium_density)
         self.set_view(spec.fov, spec.yaw, spec.pitch, spec.shift)
         return self
 

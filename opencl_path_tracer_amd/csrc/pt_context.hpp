@@ -246,6 +246,12 @@ struct pt_context {
     pt_medium medium = {0.0f, {1.0f, 1.0f, 1.0f}, 0.0f, {-std::numeric_limits<float>::infinity(), -std::numeric_limits<float>::infinity(), -std::numeric_limits<float>::infinity()},
                         {std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity()}};
     bool medium_set = false;
+    // the medium's density grid (pt_set_medium_density, pt_medium.cpp): float32 as validated, density[(k * ny + j) * nx + i]; live only while a
+    // medium with sigma_t > 0 is held too (grid_on).  Like the medium it is not part of the scene.  The device copy is made when it is set
+    std::vector<float> grid;
+    int32_t grid_n[3] = {0, 0, 0};
+    bool grid_set = false;
+    float* d_grid = nullptr;
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -306,6 +312,11 @@ inline std::string lights_refusal(const std::string& who) {
 // view the kernels read; the text the other paths refuse with
 inline bool medium_on(const pt_context* ctx) { return ctx->medium_set && ctx->medium.sigma_t > 0.0f; }
 MediumView medium_view(const pt_context* ctx);
+// a density grid is live: the NEE launches take kNeeGrid; the view the kernels read (the box must be finite: grid_unbounded names the bound that
+// is not, or is empty)
+inline bool grid_on(const pt_context* ctx) { return medium_on(ctx) && ctx->grid_set; }
+GridView grid_view(const pt_context* ctx);
+std::string grid_unbounded(const pt_context* ctx);
 inline std::string medium_refusal(const std::string& who) {
     return who + ": a medium with sigma_t > 0 is held and only pt_render_nee renders it (pt_clear_medium removes it)";
 }

@@ -1464,6 +1464,99 @@ PT_DEV float medium_transmittance(const MediumView& mv, f3 o, f3 w, float limit)
     return l > 0.0f ? expf(-(mv.sigma_t * l)) : 1.0f;
 }
 
+// ---- density grid of the medium (pt_set_medium_density; include/pt_api.h pins every operation): regular tracking
+// through gv.n[0] x gv.n[1] x gv.n[2] piecewise-constant voxels of the medium's box, which is finite wherever this is called.
+// Walk(P, D, t, tau): a 3-D DDA over the part [a, b] of [0, t] inside the box that accumulates the optical depth `acc` voxel by voxel and
+// stops in the voxel where it reaches tau.  FLIGHT = false is the walk with tau = +inf (no voxel can reach it): the test is compiled out.
+// The view and the box are wave-uniform (scalar operands); a lane carries three tnext, three tdelta, three indices and their steps, t_cur
+// and acc.  The loop is counted -- n[0] + n[1] + n[2] + 3 trips at most, more than any straight line visits -- so no rounding can
+// keep a lane in it, and every index is tested against the grid before the next load.  One scattered 4-byte load per trip; no divide
+// in the loop but the one that decides a scatter, taken only where the depth left is within a factor two of the voxel's.
+struct GridWalk {
+    float a, b;          // Clip(P, D, t)
+    float s;             // the scatter distance (t_cur + d), or -1
+    float acc;           // the optical depth accumulated before the walk ended
+    int visited;         // voxels visited
+    int voxel;           // the linear index of the voxel the walk scattered in, or -1
+};
+template <bool FLIGHT>
+PT_DEV GridWalk grid_walk(const MediumView& mv, const GridView& gv, f3 P, f3 D, float t, float tau) {
+    GridWalk w;
+    w.b = medium_clip(mv, P, D, t, &w.a);
+    w.s = -1.0f;
+    w.acc = 0.0f;
+    w.visited = 0;
+    w.voxel = -1;
+    if (!(max0(w.b - w.a) > 0.0f)) return w;
+    const float p[3] = {P.x, P.y, P.z}, dd[3] = {D.x, D.y, D.z};
+    float tn[3], td[3];
+    int ix[3], st[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        const float inv = 1.0f / dd[ax];                                    // (Clip's own reciprocal)
+        const float top = (float)(gv.n[ax] - 1);
+        float g = __builtin_floorf((fmaf_(dd[ax], w.a, p[ax]) - mv.lo[ax]) * gv.inv_cell[ax]);
+        g = g > 0.0f ? g : 0.0f;                                            // (a NaN lands on 0)
+        g = g < top ? g : top;
+        ix[ax] = (int)g;
+        if (__builtin_fabsf(inv) < __builtin_inff()) {
+            const bool up = inv > 0.0f;
+            const int kb = ix[ax] + (up ? 1 : 0);                           // the plane the ray leaves the voxel through
+            const float plane = kb == gv.n[ax] ? mv.hi[ax] : mv.lo[ax] + (float)kb * gv.cell[ax];
+            st[ax] = up ? 1 : -1;
+            tn[ax] = (plane - p[ax]) * inv;
+            td[ax] = gv.cell[ax] * __builtin_fabsf(inv);
+        } else {                                                            // parallel to the planes: the axis never steps
+            st[ax] = 0;
+            tn[ax] = __builtin_inff();
+            td[ax] = 0.0f;
+        }
+    }
+    float tx = tn[0], ty = tn[1], tz = tn[2];
+    int i = ix[0], j = ix[1], k = ix[2];
+    float tc = w.a, acc = 0.0f;
+    const int trips = gv.n[0] + gv.n[1] + gv.n[2] + 3;
+    for (int trip = 0; trip < trips; ++trip) {
+        const int idx = (k * gv.n[1] + j) * gv.n[0] + i;                    // in the grid: clamped at entry, tested after every step
+        const float sigma = mv.sigma_t * gv.rho[idx];
+        ++w.visited;
+        float te = ty < tx ? ty : tx;
+        te = tz < te ? tz : te;
+        te = w.b < te ? w.b : te;
+        const float seg = max0(te - tc);
+        if constexpr (FLIGHT) {
+            // d < seg needs tau - acc < sigma seg up to rounding: where even twice that is not reached the divide is skipped, its answer known
+            const float left = tau - acc;
+            if (sigma > 0.0f && left < 2.0f * (sigma * seg)) {
+                const float d = left / sigma;
+                if (d < seg) {
+                    w.s = tc + d;
+                    w.voxel = idx;
+                    break;
+                }
+            }
+        }
+        acc = acc + sigma * seg;
+        if (te >= w.b) break;
+        if (tx <= ty && tx <= tz) {
+            i += st[0];
+            tx += td[0];
+            if ((unsigned)i >= (unsigned)gv.n[0]) break;
+        } else if (ty <= tz) {
+            j += st[1];
+            ty += td[1];
+            if ((unsigned)j >= (unsigned)gv.n[1]) break;
+        } else {
+            k += st[2];
+            tz += td[2];
+            if ((unsigned)k >= (unsigned)gv.n[2]) break;
+        }
+        tc = te;
+    }
+    w.acc = acc;
+    return w;
+}
+
 // The light hook of shade_hit: three points in the segment body where k_nee (pt_nee.hip) adds next-event estimation.  Every
 // statement that touches the hook sits under `if constexpr (HOOK::active)`, so the default instantiation (k_render, wf_shade)
 // compiles exactly as without it -- plain empty inline methods change k_render's register allocation.

@@ -257,6 +257,7 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->d_env_col_cdf) (void)hipFree(ctx->d_env_col_cdf);
         if (ctx->d_lights_rec) (void)hipFree(ctx->d_lights_rec);
         if (ctx->d_lights_cdf) (void)hipFree(ctx->d_lights_cdf);
+        if (ctx->d_grid) (void)hipFree(ctx->d_grid);
         if (ctx->d_wf_state) (void)hipFree(ctx->d_wf_state);
         if (ctx->d_wf_queues) (void)hipFree(ctx->d_wf_queues);
         if (ctx->d_wf_counters) (void)hipFree(ctx->d_wf_counters);
@@ -922,7 +923,9 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
     }
     else nl->lights = LightsView{nullptr, nullptr, 0, 0.0f};      // (kNeeMedium without a set: P_ana = 0, the branch is never taken)
     if (medium_on(ctx)) nl->medium = medium_view(ctx);
-    nl->family = medium_on(ctx)                    ? kNeeMedium
+    if (grid_on(ctx)) nl->grid = grid_view(ctx);
+    nl->family = grid_on(ctx)                      ? kNeeGrid
+                 : medium_on(ctx)                  ? kNeeMedium
                  : lights_on(ctx)                  ? kNeeLights
                  : frosted                         ? kNeeFrosted
                  : lens_on(ctx)                    ? kNeeLens
@@ -953,6 +956,7 @@ int pt_render_nee(pt_context* ctx, const pt_camera* cam, int32_t iterations, int
     if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "pt_render_nee: iterations/nsamples must be >= 0");
     if (strategy < PT_NEE_BSDF || strategy > PT_NEE_MIS) return fail(ctx, PT_EINVAL, "pt_render_nee: strategy must be PT_NEE_BSDF, PT_NEE_LIGHT or PT_NEE_MIS");
     if (strategy == PT_NEE_BSDF && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_render_nee with PT_NEE_BSDF"));
+    if (grid_on(ctx) && !grid_unbounded(ctx).empty()) return fail(ctx, PT_EINVAL, "pt_render_nee: " + grid_unbounded(ctx));
     PT_NEED_DEVICE(ctx);
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;

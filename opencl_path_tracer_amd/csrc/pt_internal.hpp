@@ -443,6 +443,14 @@ struct MediumView {
     float g;
     float lo[3], hi[3];          // -inf / +inf: unbounded on that side
 };
+// the density grid of the medium (pt_set_medium_density; pinned in include/pt_api.h): nx x ny x nz equal cells of the medium's box, which is
+// finite in every launch that reads one.  A kernel argument by value: the pointer, the dimensions and the cell sizes stay in scalar registers
+struct GridView {
+    const float* rho;            // density[(k * ny + j) * nx + i], each finite and >= 0
+    int32_t n[3];                // nx, ny, nz, each in [1, PT_GRID_MAX_DIM]
+    float cell[3];               // (hi - lo) / n per axis, float32
+    float inv_cell[3];           // n / (hi - lo) per axis, float32
+};
 // normalize3 of pt_device.hpp on the host: dot3's fma placement, then a * (1.0f / sqrtf(l2)), IEEE
 inline void lens_normalize(const float* a, float* out) {
     const float l2 = __builtin_fmaf(a[2], a[2], __builtin_fmaf(a[1], a[1], a[0] * a[0]));
@@ -466,7 +474,7 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
                               const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream);
 // one launch of the NEE kernels (pt_nee.hip), as nee_launch_for (pt_context.hpp) fills it from the context.  Each family is the one before it
 // with one more feature compiled in; a launch takes the first family that covers what the frame needs
-enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium };
+enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium, kNeeGrid };
 struct NeeLaunch {
     const EnvView* env;          // null: the instances without an environment
     bool tiled;                  // the rounds of pt_render_adaptive_ex: k_nee*_tiles over the p.n_tiles 8x8 frame tiles of p.tile_list (null: the
@@ -477,15 +485,17 @@ struct NeeLaunch {
     int family;                  // NeeFamily.  An option whose material type is not uploaded asks for nothing; a lens with aperture > 0 takes
                                  // kNeeLens whatever the options say; option frosted with a type-6 material takes kNeeFrosted, lens or not;
                                  // a light set with a pickable light (pt_set_lights) takes kNeeLights whatever else is on; a medium with
-                                 // sigma_t > 0 (pt_set_medium) takes kNeeMedium whatever else is on, lights or not
+                                 // sigma_t > 0 (pt_set_medium) takes kNeeMedium whatever else is on, lights or not; a live density grid
+                                 // (pt_set_medium_density with such a medium) takes kNeeGrid whatever else is on
     int flags;                   // the options themselves, for the families in which they are run-time fields: bit 0 glossy (type 4 is live;
                                  // read from kNeeCoated on), bit 1 coated (type 5 is live; from kNeeLens on), bit 2 a lens with aperture > 0 is
                                  // set (from kNeeFrosted on; else each sample starts on the pinhole ray), bit 3 frosted with a type-6 material
                                  // uploaded (type 6 is live; read from kNeeLights on), bit 4 a light set with a pickable light is held (read
-                                 // by kNeeMedium; else `lights` is an empty set with P_ana = 0)
+                                 // from kNeeMedium on; else `lights` is an empty set with P_ana = 0)
     LensView lens;               // read from kNeeLens on
     LightsView lights;           // read from kNeeLights on
-    MediumView medium;           // read by kNeeMedium
+    MediumView medium;           // read from kNeeMedium on
+    GridView grid;               // read by kNeeGrid
     int* block;                  // out, may be null: the workgroup size the launch took, as launch_lanes / launch_lanes_env_tiles_smooth chose
                                  // it (0: nothing was launched, an empty tile list)
 };
@@ -502,6 +512,8 @@ hipError_t launch_debug_albedo(const RenderParams& p, const float4* vn, const Te
 hipError_t launch_debug_glossy(const float* in, int64_t n, float* out, hipStream_t stream);
 // homogeneous medium (pt_medium.hip): pt_debug_medium's kernel, 12 floats in and 10 out per item
 hipError_t launch_debug_medium(const MediumView& mv, const float* in, int64_t n, float* out, hipStream_t stream);
+// density grid (pt_medium.hip): pt_debug_grid's kernel, 12 floats in and 8 out per item
+hipError_t launch_debug_grid(const MediumView& mv, const GridView& gv, const float* in, int64_t n, float* out, hipStream_t stream);
 // coated diffuse (pt_glossy.hip): pt_debug_coated's kernel, 12 floats in and 10 out per item
 hipError_t launch_debug_coated(const float* in, int64_t n, float* out, hipStream_t stream);
 // rough dielectric (pt_glossy.hip): pt_debug_frosted's kernel, 12 floats in and 10 out per item

@@ -668,6 +668,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
     }
     if (!why.empty()) return fail(ctx, PT_EINVAL, who + ": " + why);
     if (!nee && medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal(who));
+    if (nee && grid_on(ctx) && !grid_unbounded(ctx).empty()) return fail(ctx, PT_EINVAL, who + ": " + grid_unbounded(ctx));
     if (lights_on(ctx) && (!nee || ap->strategy == PT_NEE_BSDF))
         return fail(ctx, PT_EINVAL, lights_refusal(nee ? who + " with strategy PT_NEE_BSDF" : who));
     if (!nee && ctx->frosted) return fail(ctx, PT_EINVAL, who + ": option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");

@@ -3,6 +3,8 @@
 //                    medium_transmittance() (pt_device.hpp), the functions the medium k_nee instances call (pt_nee.hip) for the free
 //                    flight of a segment, the scatter vertex's new direction and the transmittance of a light sample, so that they can be
 //                    tested against float64 without a render.  No scene is read; the numbers the kernels hash are given.
+//   k_debug_grid     pt_debug_grid: one thread per item runs grid_walk() (pt_device.hpp), the walk the grid k_nee instances call for the
+//                    free flight and the transmittance through the density grid of pt_set_medium_density
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -35,6 +37,34 @@ __global__ void __launch_bounds__(256) k_debug_medium(MediumView mv, const float
 hipError_t launch_debug_medium(const MediumView& mv, const float* in, int64_t n, float* out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_debug_medium, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, mv, in, (long long)n, out);
+    return hipGetLastError();
+}
+
+// in: 12 floats per item {P.xyz, D.xyz, t, u, limit, 3 spare}; out: 8 per item {a, b of Clip(P, D, t), 1 if the free flight of u scatters
+// in [0, t] else 0, its distance s (-1 without a scatter), the optical depth over [0, t], T over [0, limit], the voxels the free flight
+// visited, the linear index of the voxel it scattered in (-1 without)}
+__global__ void __launch_bounds__(256) k_debug_grid(MediumView mv, GridView gv, const float* __restrict__ in, long long n, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* q = in + i * 12;
+    const f3 P = mk(q[0], q[1], q[2]), D = mk(q[3], q[4], q[5]);
+    const GridWalk fl = grid_walk<true>(mv, gv, P, D, q[6], -log1pf(-q[7]));
+    const float depth = grid_walk<false>(mv, gv, P, D, q[6], __builtin_inff()).acc;
+    const float through = grid_walk<false>(mv, gv, P, D, q[8], __builtin_inff()).acc;
+    float* o = out + i * 8;
+    o[0] = fl.a;
+    o[1] = fl.b;
+    o[2] = fl.voxel >= 0 ? 1.0f : 0.0f;
+    o[3] = fl.s;
+    o[4] = depth;
+    o[5] = through != 0.0f ? expf(-through) : 1.0f;
+    o[6] = (float)fl.visited;
+    o[7] = (float)fl.voxel;
+}
+
+hipError_t launch_debug_grid(const MediumView& mv, const GridView& gv, const float* in, int64_t n, float* out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_debug_grid, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, mv, gv, in, (long long)n, out);
     return hipGetLastError();
 }
 

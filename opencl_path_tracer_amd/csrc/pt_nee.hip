@@ -22,8 +22,10 @@
 //   MEDIUM  a homogeneous participating medium (pt_set_medium, section 5.17): a segment may end at a scatter vertex before its hit, and every
 //           light sample outside a dielectric carries the transmittance of its shadow ray; whether a pickable light set is held is a
 //           run-time field (flags bit 4)
-// Each flag from SMOOTH on requires the one before it.  The kernels are the nine families the host can ask for (NeeFamily, pt_internal.hpp)
-// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights, _medium: each is the one before it with one more flag -- times ENV and TILED
+//   GRID    the medium's extinction is sigma_t times a voxel density (pt_set_medium_density, section 5.20): the free flight and the transmittance
+//           walk the grid (grid_walk, pt_device.hpp); everything else is MEDIUM's
+// Each flag from SMOOTH on requires the one before it.  The kernels are the ten families the host can ask for (NeeFamily, pt_internal.hpp)
+// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights, _medium, _grid: each is the one before it with one more flag -- times ENV and TILED
 // (k_nee_env*, k_nee_tiles*, k_nee_env_tiles*).  In a family whose option is off the data is null (vn, tv.uv) or the field clear.
 #include "pt_device.hpp"
 
@@ -123,10 +125,19 @@ struct MediumSlot<true> {
     float T = 1.0f;                // the transmittance of the current light sample's shadow ray (light_sample_env to light_add)
 };
 
+// what a hook carries for the medium's density grid (pt_set_medium_density): nothing without it
+template <bool GRID>
+struct GridSlot {};
+template <>
+struct GridSlot<true> {
+    GridView v;                    // the densities, the dimensions and the cell sizes: wave-uniform
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
 template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false, bool FROST = false,
-          bool LIGHTS = false, bool MEDIUM = false>
+          bool LIGHTS = false, bool MEDIUM = false, bool GRID = false>
 struct NeeHook {
+    static_assert(MEDIUM || !GRID, "the grid instances are built on the medium code");
     static_assert(LIGHTS || !MEDIUM, "the medium instances are built on the lights code");
     static_assert(FROST || !LIGHTS, "the lights instances are built on the frosted code");
     static_assert(LENS || !FROST, "the frosted instances are built on the lens code");
@@ -162,6 +173,7 @@ struct NeeHook {
     FrostSlot<FROST> frs;
     LightsSlot<LIGHTS> lg;
     MediumSlot<MEDIUM> md;
+    GridSlot<GRID> gr;
 
     // MEDIUM: the lane enters shade_hit at a scatter vertex
     PT_DEV bool scatters() const {
@@ -170,7 +182,13 @@ struct NeeHook {
     }
     // MEDIUM: the free flight of segment k along (rP, rD), whose closest hit is at t (+inf: a miss): the distance of the scatter vertex, or -1
     // when the segment reaches its end.  A segment with nothing inside the box draws no number (d >= 0 is never below L = 0)
+    // GRID: the same through the voxels: tau = -log1pf(-u) of the same number against the optical depth the walk accumulates
     PT_DEV float free_flight(f3 rP, f3 rD, float t) const {
+        if constexpr (GRID) {
+            const float tau = -log1pf(-nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 0)));      // (a hash, not a draw: unused where the clip is empty)
+            const GridWalk w = grid_walk<true>(md.v, gr.v, rP, rD, t, tau);
+            return w.voxel >= 0 ? max0(w.s) : -1.0f;       // (s < 0 would take an accumulated depth a rounding past tau in a voxel at the origin)
+        }
         float a;
         const float b = medium_clip(md.v, rP, rD, t, &a);
         const float L = max0(b - a);
@@ -623,7 +641,13 @@ struct NeeHook {
         const float cosx = dot3(N, w);
         if (!((mvx || cosx > 0.0f) && pl > 0.0f && pl < __builtin_inff())) return;
         if constexpr (SMOOTH) if (!(mvx || dot3(geo(N), w) > 0.0f)) return;   // as in light_sample
-        if constexpr (MEDIUM) md.T = ins ? 1.0f : medium_transmittance(md.v, o, w, limit);      // (for a vertex outside a dielectric)
+        if constexpr (GRID) {          // (for a vertex outside a dielectric)
+            md.T = 1.0f;
+            if (!ins) {
+                const float depth = grid_walk<false>(md.v, gr.v, o, w, limit, __builtin_inff()).acc;
+                if (depth != 0.0f) md.T = expf(-depth);
+            }
+        } else if constexpr (MEDIUM) md.T = ins ? 1.0f : medium_transmittance(md.v, o, w, limit);
         if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
         if constexpr (LIGHTS) light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e, delta);
         else light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e);
@@ -679,15 +703,17 @@ struct NeeHook {
 // LIGHTS (pt_set_lights; k_nee*_lights below; on the FROST code only): a lobe vertex may sample an analytic light; metal bit 3: option frosted
 // MEDIUM (pt_set_medium; k_nee*_medium below; on the LIGHTS code only): between closest_hit and shade_hit a segment may end at a scatter vertex of
 // the medium; metal bit 4: a light set with a pickable light is held
+// GRID (pt_set_medium_density; k_nee*_grid below; on the MEDIUM code only): the hook's free flight and transmittance walk the density grid
 template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false,
-          bool FROST = false, bool LIGHTS = false, bool MEDIUM = false>
+          bool FROST = false, bool LIGHTS = false, bool MEDIUM = false, bool GRID = false>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr,
-                      int metal = 0, const LensView* lens = nullptr, const LightsView* lights = nullptr, const MediumView* medium = nullptr) {
+                      int metal = 0, const LensView* lens = nullptr, const LightsView* lights = nullptr, const MediumView* medium = nullptr,
+                      const GridView* grid = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS, MEDIUM> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS, MEDIUM, GRID> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (TEX) hook.tx.v = *tv;
     if constexpr (LENS) {
@@ -707,6 +733,7 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
         if (!MEDIUM || (metal & 16) != 0) hook.nee = lt.strategy != 0;
     }
     if constexpr (MEDIUM) hook.md.v = *medium;
+    if constexpr (GRID) hook.gr.v = *grid;
     const int camX = (int)p.cam.XM;
     unsigned rendered = 0;                     // TILED: pixels this lane rendered (statistic "samples", as k_render counts them)
     if constexpr (TILED) npix = (long long)p.n_tiles * 64;      // work items: 64 per listed tile
@@ -967,6 +994,28 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_medium(RenderParams p, 
     nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv);
 }
 
+// the grid instances (a medium with sigma_t > 0 and a density grid are held): the medium kernels with the grid's view as one more argument
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_grid(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
+                                                    GridView gv, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_grid(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
+                                                        MediumView mv, GridView gv, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_grid(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
+                                                          GridView gv) {
+    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_grid(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
+                                                              MediumView mv, GridView gv) {
+    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -1008,11 +1057,18 @@ static hipError_t launch_nee_family(K k, KE ke, KT kt, KET ket, const RenderPara
 // The medium family is compiled in a translation unit of its own (pt_nee_medium.hip includes this file with PT_NEE_MEDIUM_TU defined and
 // gets launch_nee_medium only): compiled next to the other families, its instances cost 48 of them two instructions in their uv fetch
 // (the compiler no longer derives for a helper they share that its triangle index is never negative; profiles/medium/README.md)
+// The grid family likewise (pt_nee_grid.hip, PT_NEE_GRID_TU, launch_nee_grid), so that the medium instances compile as they did before it
 hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
-#ifdef PT_NEE_MEDIUM_TU
+hipError_t launch_nee_grid(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
+#if defined(PT_NEE_MEDIUM_TU)
 hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     return launch_nee_family<kWideAll>(NEE_PICK(k_nee_medium), NEE_PICK(k_nee_env_medium), NEE_PICK(k_nee_tiles_medium), NEE_PICK(k_nee_env_tiles_medium), p, lt, nl, npix,
                                        cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium);
+}
+#elif defined(PT_NEE_GRID_TU)
+hipError_t launch_nee_grid(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+    return launch_nee_family<kWideAll>(NEE_PICK(k_nee_grid), NEE_PICK(k_nee_env_grid), NEE_PICK(k_nee_tiles_grid), NEE_PICK(k_nee_env_tiles_grid), p, lt, nl, npix,
+                                       cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium, nl.grid);
 }
 #else
 static hipError_t launch_nee_of_family(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
@@ -1043,13 +1099,14 @@ static hipError_t launch_nee_of_family(const RenderParams& p, const NeeTable& lt
         return launch_nee_family<kWideAll>(NEE_PICK(k_nee_lights), NEE_PICK(k_nee_env_lights), NEE_PICK(k_nee_tiles_lights), NEE_PICK(k_nee_env_tiles_lights), p, lt, nl, npix,
                                      cu_count, stream, nl.vn, nl.tv, nl.flags & 15, nl.lens, nl.lights);
     case kNeeMedium: return launch_nee_medium(p, lt, nl, npix, cu_count, stream);
+    case kNeeGrid: return launch_nee_grid(p, lt, nl, npix, cu_count, stream);
     }
     return hipErrorInvalidValue;
 }
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     t_lanes_block = 0;
     const hipError_t e = launch_nee_of_family(p, lt, nl, npix, cu_count, stream);
-    if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit or in pt_nee_medium.hip's)
+    if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit, in pt_nee_medium.hip's or in pt_nee_grid.hip's)
     return e;
 }
 #endif

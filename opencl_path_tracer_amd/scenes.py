@@ -43,6 +43,8 @@ class SceneSpec:
     lights_select: float = 0.5                       # ... and set_lights' select
     medium: dict = field(default_factory=dict)       # optional: a homogeneous medium, Scene.set_medium's arguments: dict(sigma_t=, albedo=,
                                                      # g=, bounds=(lo, hi)) (Scene.load applies it)
+    medium_density: object = None                    # optional: a voxel density for that medium, an array (nz, ny, nx) as
+                                                     # Scene.set_medium_density takes it (Scene.load applies it after the medium)
 
     @property
     def ntris(self):
@@ -146,7 +148,23 @@ LAMP_SPOT_DEGREES = (60.0, 90.0)      # ... and the spot's inner and outer half 
 CORNELL_ROOM = ((-100.0, 0.0, -1000.0), (1100.0, 1000.0, 1000.0))      # cornell_box(fog=...): the fog's box, the room wall to wall
 
 
-def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False, frosted=False, lamp="quad", fog=0.0):
+def smoke_plume(n=32):
+    """A procedural density (n, n, n) float32 for Scene.set_medium_density, index (k, j, i) = (z, y, x) with y up: a plume that rises
+    from the middle of the floor of the medium's box, widens and thins with height and sways along x, over a thin ground mist.
+    Densities lie in [0, 4]; outside the plume and above the mist they are exactly 0 (empty voxels the walk crosses for free)."""
+    c = (np.arange(n, dtype=np.float64) + 0.5) / n
+    z, y, x = np.meshgrid(c, c, c, indexing="ij")
+    cx = 0.5 + 0.12 * np.sin(7.0 * y) * y                       # the axis sways with height
+    cz = 0.5 + 0.08 * np.sin(5.0 * y + 1.0) * y
+    radius = 0.06 + 0.22 * y                                    # and the plume widens
+    r2 = ((x - cx) ** 2 + (z - cz) ** 2) / (radius * radius)
+    puff = 0.75 + 0.25 * np.sin(19.0 * x + 3.0 * y) * np.sin(17.0 * z - 5.0 * y) * np.sin(23.0 * y)
+    plume = np.where(r2 < 1.0, 4.0 * (1.0 - r2) * (1.0 - 0.7 * y) * puff, 0.0)
+    mist = np.where(y < 0.1, 0.5 * (1.0 - y / 0.1), 0.0)
+    return np.maximum(plume, mist).astype(np.float32)
+
+
+def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False, frosted=False, lamp="quad", fog=0.0, density=None):
     """Scene CB of SURVEY 8(d): 12 wall/lamp triangles + two tessellated spheres
     (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects.
     smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals).
@@ -164,7 +182,9 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
     axis and dark from 90 on, and the smoothstep between integrates to half its width: 2 pi I (1 - cos 60 + cos 60 / 2), so
     I = E A / 1.5.
     fog: sigma_t > 0 fills the room (CORNELL_ROOM) with a white medium of that extinction per unit, albedo 0.9 and g = 0.6
-    (Scene.set_medium through Scene.load; only render_nee renders the scene then).  1e-3 is a mean free path of the room's width."""
+    (Scene.set_medium through Scene.load; only render_nee renders the scene then).  1e-3 is a mean free path of the room's width.
+    density: with fog, a voxel density (nz, ny, nx) over the room, such as smoke_plume(): the extinction is fog x density
+    (Scene.set_medium_density through Scene.load)."""
     if coated and frosted:
         raise ValueError("cornell_box: coated and frosted both replace the glass sphere's material")
     if lamp not in ("quad", "point", "spot"):
@@ -211,6 +231,10 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
         spec.material_textures = {WHITE_DIFFUSE: 0}
     if fog > 0.0:
         spec.medium = dict(sigma_t=float(fog), albedo=(0.9, 0.9, 0.9), g=0.6, bounds=CORNELL_ROOM)
+        if density is not None:
+            spec.medium_density = np.ascontiguousarray(density, dtype=np.float32)
+    elif density is not None:
+        raise ValueError("cornell_box: density needs fog > 0 (the medium whose extinction it scales)")
     return spec
 
 
