@@ -340,7 +340,7 @@ int pt_debug_lights(pt_context* ctx, float* records, float* cdf, float* P_light,
  * (every strategy) and the NEE path of pt_render_adaptive_ex render it.  Without one -- never set, cleared, or sigma_t = 0 -- every path
  * launches the kernels it launched before and computes what it computed before, bit for bit.
  * The medium fills its axis-aligned box [lo, hi] wherever the path is not inside a dielectric (the `inside` flag of the specular and frosted
- * vertices is false).  It draws from a third hash stream, pt_nee_rand(S ^ 0x5bd1e995, k, dim) (S the LCG state at the start of the sample,
+ * vertices is false).  (Inside one, the interior bound to its material applies instead: pt_set_material_interior below.)  It draws from a third hash stream, pt_nee_rand(S ^ 0x5bd1e995, k, dim) (S the LCG state at the start of the sample,
  * k the segment; the light samples own S and ~S), never from the LCG: rnds after a frame are pt_render's for every path that never scatters.
  * All arithmetic below is float32 with no contraction; log1pf, expf, sinf, cosf are the device library's (OCML: within 2 ulp, 1 ulp, 2 ulp,
  * 2 ulp), divides and square roots IEEE.
@@ -435,6 +435,54 @@ int pt_debug_medium_density(pt_context* ctx, float* out, int64_t cap, int32_t di
  * (the optical depth over [0, t]), T over [0, limit], the voxels the free-flight walk visited, the linear index of the voxel it scattered
  * in (-1 without)}.  PT_EINVAL when no grid is live or a bound of the box is infinite */
 int pt_debug_grid(pt_context* ctx, const float* in, int64_t n, float* out);
+
+/* ---- interiors of dielectrics (new: opt-in with pt_set_material_interior; coloured glass, murky liquids, wax, jade, milk) ----
+ * An interior is a medium bound to a material of type 2 (glass) or 6 (frosted glass, option "frosted") and active exactly while the path is
+ * inside it (the `inside` flag of the specular and frosted vertices is true): chromatic Beer-Lambert absorption sigma_a and grey scattering
+ * sigma_s with a Henyey-Greenstein g.  Only pt_render_nee (every strategy, PT_NEE_BSDF too: no light sample is involved) and the NEE path of
+ * pt_render_adaptive_ex render it.  A binding lives like a texture binding (pt_set_material_texture): the material is any index added so far,
+ * it is kept across uploads and on a host-only context, every rank of a tiled frame sets its own copy, and a binding on a material whose type
+ * on the device is neither 2 nor 6 is ignored where the table for the device is made, as a texture on a non-diffuse material is.  The table reads
+ * the type alone, not option "frosted": with the option off a type-6 surface is inert and no path enters through it, but a path that is inside
+ * type-2 glass and whose segment ends on a bound type-6 triangle takes that binding's interior on the segment all the same.  A binding is
+ * live as soon as it exists, even an all-zero one: while any is live the NEE launches take the interior instances of k_nee (stat "nee_family"
+ * 10), which serve frames with and without a medium and its density grid, and pt_render, pt_generate_rays, pt_trace_rays, pt_render_adaptive
+ * and pt_render_adaptive_ex with PT_ADAPT_PATH_RENDER return PT_EINVAL naming pt_clear_material_interiors, checked before the device.
+ * Without a binding every path launches the kernels it launched before and computes the same bits.  The guides, the denoisers and temporal
+ * accumulation keep the interior-free view.
+ * The estimator, float32 with no contraction (log1pf, expf: the device library's; the divide IEEE), on segment k while `inside` is true:
+ *   ti is the closest hit, at distance t.  The interior is the one bound to the material of triangle ti -- the surface the path will leave
+ *   through, so the path carries no extra state.  A miss (a leaky mesh) or a material without a binding: no interior on this segment.
+ *   Free flight, only if sigma_s > 0: u = (pt_nee_rand(S ^ 0x5bd1e995, k, 0) >> 8) 2^-24 -- dimension 0 of the medium's stream, which the
+ *     exterior medium never draws while inside --, d = -log1pf(-u) / sigma_s; the segment scatters iff d < t; l = d when it scatters, else t.
+ *   Absorption: per channel c, factor_S[c] *= expf(-(sigma_a[c] l)); a channel with sigma_a[c] == 0 multiplies by exactly 1.  An all-zero
+ *     product ends the path.  Surviving the free flight takes no other factor: its probability is the scattering transmittance.
+ *   Scatter vertex (it consumes segment k): no light sample in any strategy (a shadow ray from inside ends on the object's own boundary);
+ *     the new direction is the medium's step 3 with the interior's g and u1, u2 from dimensions 1 and 2 of the same stream; the next segment
+ *     starts at fma(D, d, P) per component.  It is no lobe vertex for what follows: an emitter hit or a sky miss on segment k + 1 has weight
+ *     1 in every strategy, as after a frosted refraction.  `inside` is unchanged and nothing is drawn from the LCG.
+ *   Surface hit: after the absorption factor the vertex proceeds exactly as without an interior.
+ * So with absorption only rnds and rays after a frame are the unbound frame's; with scattering they differ only for paths that scatter.
+ * The medium of pt_set_medium and its grid keep applying wherever `inside` is false; both kinds may be set at once.
+ * Light inside a scattering object arrives only by paths that refract out and find a light: good under a sky or large emitters, noisy
+ * under a tiny lamp (light sampling through a refracting boundary is not done). */
+typedef struct pt_interior {
+    float sigma_a[3];   /* absorption per unit length, per channel, finite, >= 0 */
+    float sigma_s;      /* scattering per unit length (grey), finite, >= 0 */
+    float g;            /* Henyey-Greenstein asymmetry, |g| <= 0.99 */
+} pt_interior;          /* 20 bytes */
+void pt_interior_defaults(pt_interior* in);      /* all zero */
+/* PT_EINVAL, naming pt_set_material_interior and the field, with the held binding left as it was: ctx or interior NULL, material not the index
+ * of a material added so far, a NaN, a negative or infinite coefficient, |g| > 0.99 */
+int pt_set_material_interior(pt_context* ctx, int32_t material, const pt_interior* interior);
+int pt_clear_material_interiors(pt_context* ctx);
+/* the binding of `material` into *interior (all zero when it holds none); returns 1 if one is held, 0 if not, PT_EINVAL for a NULL argument
+ * or a material that was never added */
+int pt_get_material_interior(const pt_context* ctx, int32_t material, pt_interior* interior);
+/* the device functions of an interior on given numbers, n items: in, 12 floats each {sigma_a.rgb, sigma_s, g, t, u, u1, u2, D.xyz (unit)};
+ * out, 10 floats each {d = -log1pf(-u) / sigma_s (-1 when sigma_s is 0: nothing is drawn), 1 if d < t else 0, l, the absorption factor per
+ * channel, the new direction from (u1, u2) around D (unit), 0}.  No binding is needed */
+int pt_debug_interior(pt_context* ctx, const float* in, int64_t n, float* out);
 
 /* ---- smooth shading from vertex normals for pt_render_nee (new: opt-in with option "smooth_normals"; the reference shades with the
  * triangle's geometric normal only) -----------
@@ -999,8 +1047,8 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value);
  * hands such a scene back to the host, so the count is 0 whenever "bvh_on_device" is 1), "triangles", "lds_bytes",
  * "waves_per_simd", "node_mode" (0 whole tree in LDS, 1 BVH2 nodes through L1/L2, 2 treelet, 3 4-wide nodes through
  * L1/L2), "nee_family" / "nee_form" / "nee_block" (what the last launch of
- * pt_render_nee or of an NEE round of pt_render_adaptive_ex took: the kernel family 0..9 -- plain, smooth, tex, glossy,
- * coated, lens, frosted, lights, medium, grid (a medium with a live density grid) --, the form -- bit 0 an environment is drawn, bit 1 tiled -- and the workgroup
+ * pt_render_nee or of an NEE round of pt_render_adaptive_ex took: the kernel family 0..10 -- plain, smooth, tex, glossy,
+ * coated, lens, frosted, lights, medium, grid (a medium with a live density grid), interior (a material holds an interior) --, the form -- bit 0 an environment is drawn, bit 1 tiled -- and the workgroup
  * size; -1 each before the first such launch), "treelet_nodes", "wide_nodes" (how many 4-wide nodes),
  * "wide_pending" (their worst-case stack), "flat_triangles", "flat_boxes" (their distinct bounding boxes), and with
  * count_work: "node_visits", "tri_tests", "wave_node_steps", "wave_tri_steps", "tile_lane_steps", "wave_shade_steps",

@@ -136,6 +136,12 @@ public:
     void clear_medium_density() { ck(pt_clear_medium_density(ctx)); }
     bool medium_density(float* out, int64_t cap, int32_t dims[3]) { return ck(pt_debug_medium_density(ctx, out, cap, dims)) == 1; }
     void debug_grid(const float* in, int64_t n, float* out) { ck(pt_debug_grid(ctx, in, n, out)); }
+    // the medium inside a type-2 or type-6 material (pt_set_material_interior): chromatic absorption, grey scattering, a Henyey-Greenstein g; live
+    // as soon as it is bound, kept across uploads like a texture binding.  material_interior reads it back (returns whether one is held)
+    void set_material_interior(int32_t material, const pt_interior& in) { ck(pt_set_material_interior(ctx, material, &in)); }
+    void clear_material_interiors() { ck(pt_clear_material_interiors(ctx)); }
+    bool material_interior(int32_t material, pt_interior* out) { return ck(pt_get_material_interior(ctx, material, out)) == 1; }
+    void debug_interior(const float* in, int64_t n, float* out) { ck(pt_debug_interior(ctx, in, n, out)); }
     // vertex normals for smooth shading (set_option("smooth_normals", 1); render_nee only): normals = count x 9 floats, n1 n2 n3 per
     // triangle in add order starting at first_triangle; compute_vertex_normals derives them per object (obj = -1: every object)
     void set_vertex_normals(const float* normals, int64_t count, int64_t first_triangle = 0) { ck(pt_set_vertex_normals(ctx, first_triangle, count, normals)); }

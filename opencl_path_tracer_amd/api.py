@@ -55,6 +55,7 @@ EXPORTS = [
     "pt_lights_defaults", "pt_set_lights", "pt_clear_lights", "pt_debug_lights",
     "pt_medium_defaults", "pt_set_medium", "pt_clear_medium", "pt_get_medium", "pt_debug_medium",
     "pt_set_medium_density", "pt_clear_medium_density", "pt_debug_medium_density", "pt_debug_grid",
+    "pt_interior_defaults", "pt_set_material_interior", "pt_clear_material_interiors", "pt_get_material_interior", "pt_debug_interior",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
     "pt_render_aovs", "pt_read_aovs", "pt_aov_defaults", "pt_render_aovs_ex", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
@@ -159,6 +160,11 @@ def _load():
     sig("pt_clear_medium_density", C.c_int, vp)
     sig("pt_debug_medium_density", C.c_int, vp, vp, i64, vp)
     sig("pt_debug_grid", C.c_int, vp, vp, i64, vp)
+    sig("pt_interior_defaults", None, vp)
+    sig("pt_set_material_interior", C.c_int, vp, i32, vp)
+    sig("pt_clear_material_interiors", C.c_int, vp)
+    sig("pt_get_material_interior", C.c_int, vp, i32, vp)
+    sig("pt_debug_interior", C.c_int, vp, vp, i64, vp)
     sig("pt_image_read_pfm", C.c_int, C.c_char_p, vp, i64, C.POINTER(i32), C.POINTER(i32))
     sig("pt_read_variance", C.c_int, vp, vp, i64)
     sig("pt_device_variance", vp, vp)
@@ -402,6 +408,30 @@ class Medium(C.Structure):
 
     def as_dict(self):
         return {"sigma_t": float(self.sigma_t), "albedo": tuple(self.albedo), "g": float(self.g), "lo": tuple(self.lo), "hi": tuple(self.hi)}
+
+
+class Interior(C.Structure):
+    """pt_interior (include/pt_api.h): the medium inside a type-2 or type-6 material, 20 bytes."""
+    _fields_ = [("sigma_a", C.c_float * 3), ("sigma_s", C.c_float), ("g", C.c_float)]
+
+    def as_dict(self):
+        return dict(sigma_a=tuple(self.sigma_a), sigma_s=self.sigma_s, g=self.g)
+
+
+def interior_defaults():
+    """pt_interior_defaults as a dict: sigma_a (0, 0, 0), sigma_s 0, g 0."""
+    p = Interior()
+    LIB.pt_interior_defaults(C.byref(p))
+    return p.as_dict()
+
+
+def interior_from_tint(color, distance):
+    """The sigma_a (rgb, float64) that tints white light to `color` over `distance` of travel inside: -ln(color) / distance per channel
+    (Beer-Lambert).  color in (0, 1] per channel (1: no absorption), distance > 0."""
+    c = np.asarray(color, dtype=np.float64).reshape(3)
+    if not (np.all(c > 0.0) and np.all(c <= 1.0)) or not float(distance) > 0.0:
+        raise ValueError("interior_from_tint: color must lie in (0, 1] per channel and distance must be > 0")
+    return tuple(float(v) for v in (-np.log(c) / float(distance) + 0.0))
 
 
 def medium_defaults():
@@ -862,6 +892,37 @@ class Scene:
         self._ck(LIB.pt_debug_grid(self._h, _ptr(items), items.shape[0], _ptr(out)))
         return out
 
+    # -- interiors of dielectrics (include/pt_api.h pins the free flight, the absorption factor and the scatter vertex)
+    def set_material_interior(self, material, sigma_a=(0, 0, 0), sigma_s=0.0, g=0.0):
+        """pt_set_material_interior: the medium inside `material` (type 2, or 6 under option frosted): absorption sigma_a per unit length (rgb
+        or a number; interior_from_tint gives it from a colour), grey scattering sigma_s and Henyey-Greenstein g.  Live as soon as it is
+        bound, an all-zero one too: only render_nee and render_adaptive(path="nee") render then; the guide buffers keep the interior-free
+        view.  Kept across uploads, like a texture binding."""
+        p = Interior()
+        p.sigma_a = (C.c_float * 3)(*[float(v) for v in (sigma_a if np.ndim(sigma_a) else (sigma_a,) * 3)])
+        p.sigma_s, p.g = float(sigma_s), float(g)
+        self._ck(LIB.pt_set_material_interior(self._h, int(material), C.byref(p)))
+
+    def clear_material_interiors(self):
+        self._ck(LIB.pt_clear_material_interiors(self._h))
+
+    def material_interior(self, material):
+        """pt_get_material_interior: the binding of `material` as a dict (interior_defaults()'s keys), or None when it holds none."""
+        p = Interior()
+        rc = LIB.pt_get_material_interior(self._h, int(material), C.byref(p))
+        if rc < 0:
+            raise PtError(rc, "pt_get_material_interior: material must be the index of a material added so far")
+        return p.as_dict() if rc == 1 else None
+
+    def debug_interior(self, items):
+        """pt_debug_interior: items (n, 12) float32 {sigma_a.rgb, sigma_s, g, t, u, u1, u2, D (unit)} -> (n, 10) float32 {the free-flight
+        distance d (-1 when sigma_s is 0), 1 if the segment scatters (d < t) else 0, the length l absorbed over, the absorption factor
+        rgb, the new direction from (u1, u2) around D (unit), 0}, by the device functions the interior k_nee instances call."""
+        items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 12)
+        out = np.empty((items.shape[0], 10), dtype=np.float32)
+        self._ck(LIB.pt_debug_interior(self._h, _ptr(items), items.shape[0], _ptr(out)))
+        return out
+
     # -- the rough dielectric of material type 6 (option "frosted")
     def debug_frosted(self, items):
         """pt_debug_frosted: items (n, 12) float32 {N, D, alpha, F0, eta, rnd1, rnd2, u_sel} -> (n, 10) float32 {w before normalisation
@@ -911,6 +972,8 @@ class Scene:
             self.set_medium(**spec.medium)
         if getattr(spec, "medium_density", None) is not None:   # optional: set_medium_density's array
             self.set_medium_density(spec.medium_density)
+        for mi, kw in (getattr(spec, "interiors", None) or {}).items():      # optional: {index into spec.materials: set_material_interior's arguments}
+            self.set_material_interior(nm.value + int(mi), **kw)
         self.set_view(spec.fov, spec.yaw, spec.pitch, spec.shift)
         return self
 

@@ -252,6 +252,15 @@ struct pt_context {
     int32_t grid_n[3] = {0, 0, 0};
     bool grid_set = false;
     float* d_grid = nullptr;
+    // interiors of dielectrics (pt_set_material_interior, pt_interior.cpp): per material index the record and whether one is bound, kept like a
+    // texture binding -- across uploads, on a host-only context too, not part of the scene.  interior_live counts the bindings; the device table
+    // (two float4 per material on the device, bound only where its type is 2 or 6) is rebuilt by interior_prepare when a binding or the
+    // materials changed
+    std::vector<pt_interior> interiors;
+    std::vector<uint8_t> interior_bound;
+    int32_t interior_live = 0;
+    bool interior_dirty = true;
+    float4* d_interior = nullptr;
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -317,6 +326,13 @@ MediumView medium_view(const pt_context* ctx);
 inline bool grid_on(const pt_context* ctx) { return medium_on(ctx) && ctx->grid_set; }
 GridView grid_view(const pt_context* ctx);
 std::string grid_unbounded(const pt_context* ctx);
+// an interior binding is live (even an all-zero one): the NEE launches take kNeeInterior; the table the kernels read, made on the device when stale;
+// the text the other paths refuse with
+inline bool interior_on(const pt_context* ctx) { return ctx->interior_live > 0; }
+int interior_prepare(pt_context* ctx, InteriorView* iv);
+inline std::string interior_refusal(const std::string& who) {
+    return who + ": a material holds an interior and only pt_render_nee renders it (pt_clear_material_interiors removes every binding)";
+}
 inline std::string medium_refusal(const std::string& who) {
     return who + ": a medium with sigma_t > 0 is held and only pt_render_nee renders it (pt_clear_medium removes it)";
 }

@@ -1464,6 +1464,21 @@ PT_DEV float medium_transmittance(const MediumView& mv, f3 o, f3 w, float limit)
     return l > 0.0f ? expf(-(mv.sigma_t * l)) : 1.0f;
 }
 
+// ---- interiors of dielectrics (pt_set_material_interior; include/pt_api.h pins every operation): the medium bound to
+// the type-2 or type-6 material a path inside it will leave through, read per lane from the launch's table
+// the free flight of the unit number u on a segment whose hit is at t: the distance of the scatter vertex, or -1 when the segment reaches its
+// hit (sigma_s = 0 draws nothing)
+PT_DEV float interior_flight(float sigma_s, float u, float t) {
+    if (!(sigma_s > 0.0f)) return -1.0f;
+    const float d = medium_flight(sigma_s, u);
+    return d < t ? d : -1.0f;
+}
+// Beer-Lambert over the length l, per channel; a channel without absorption is exactly 1
+PT_DEV f3 interior_absorb(f3 sigma_a, float l) {
+    return mk(sigma_a.x != 0.0f ? expf(-(sigma_a.x * l)) : 1.0f, sigma_a.y != 0.0f ? expf(-(sigma_a.y * l)) : 1.0f,
+              sigma_a.z != 0.0f ? expf(-(sigma_a.z * l)) : 1.0f);
+}
+
 // ---- density grid of the medium (pt_set_medium_density; include/pt_api.h pins every operation): regular tracking
 // through gv.n[0] x gv.n[1] x gv.n[2] piecewise-constant voxels of the medium's box, which is finite wherever this is called.
 // Walk(P, D, t, tau): a 3-D DDA over the part [a, b] of [0, t] inside the box that accumulates the optical depth `acc` voxel by voxel and

@@ -258,6 +258,7 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->d_lights_rec) (void)hipFree(ctx->d_lights_rec);
         if (ctx->d_lights_cdf) (void)hipFree(ctx->d_lights_cdf);
         if (ctx->d_grid) (void)hipFree(ctx->d_grid);
+        if (ctx->d_interior) (void)hipFree(ctx->d_interior);
         if (ctx->d_wf_state) (void)hipFree(ctx->d_wf_state);
         if (ctx->d_wf_queues) (void)hipFree(ctx->d_wf_queues);
         if (ctx->d_wf_counters) (void)hipFree(ctx->d_wf_counters);
@@ -306,6 +307,7 @@ int pt_upload_materials(pt_context* ctx) {
     ctx->aov_valid = false;
     ctx->nee_valid = false;          // the light table reads emission and type
     ctx->tex_dirty = true;           // and the bindings on the device the type
+    ctx->interior_dirty = true;      // (the interiors' table too)
     for (const pt_triangle& t : ctx->tris)
         if (t.mati >= ctx->mats.size()) return fail(ctx, PT_EINVAL, "a triangle references a material index that was never added");
     ctx->glossy_mats = false;
@@ -924,7 +926,9 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
     else nl->lights = LightsView{nullptr, nullptr, 0, 0.0f};      // (kNeeMedium without a set: P_ana = 0, the branch is never taken)
     if (medium_on(ctx)) nl->medium = medium_view(ctx);
     if (grid_on(ctx)) nl->grid = grid_view(ctx);
-    nl->family = grid_on(ctx)                      ? kNeeGrid
+    if (interior_on(ctx) && (rc = interior_prepare(ctx, &nl->interior)) != PT_OK) return rc;
+    nl->family = interior_on(ctx)                  ? kNeeInterior
+                 : grid_on(ctx)                    ? kNeeGrid
                  : medium_on(ctx)                  ? kNeeMedium
                  : lights_on(ctx)                  ? kNeeLights
                  : frosted                         ? kNeeFrosted
@@ -935,6 +939,7 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
                  : nl->vn                          ? kNeeSmooth
                                                    : kNeePlain;
     nl->flags = (ctx->glossy ? 1 : 0) | (ctx->coated ? 2 : 0) | (lens_on(ctx) ? 4 : 0) | (frosted ? 8 : 0) | (lights_on(ctx) ? 16 : 0);
+    if (interior_on(ctx)) nl->flags |= (medium_on(ctx) ? 32 : 0) | (grid_on(ctx) ? 64 : 0);      // (kNeeInterior serves frames with and without either)
     return PT_OK;
 }
 hipError_t launch_nee_noted(pt_context* ctx, const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl) {

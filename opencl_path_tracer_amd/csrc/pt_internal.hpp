@@ -451,6 +451,11 @@ struct GridView {
     float cell[3];               // (hi - lo) / n per axis, float32
     float inv_cell[3];           // n / (hi - lo) per axis, float32
 };
+// the interiors bound to materials (pt_set_material_interior; pinned in include/pt_api.h): per material on the device two float4,
+// {sigma_a.rgb, sigma_s} and {g, bound (1 or 0), 0, 0}; bound is 0 wherever the material is not of type 2 or 6 or holds no binding
+struct InteriorView {
+    const float4* rec;
+};
 // normalize3 of pt_device.hpp on the host: dot3's fma placement, then a * (1.0f / sqrtf(l2)), IEEE
 inline void lens_normalize(const float* a, float* out) {
     const float l2 = __builtin_fmaf(a[2], a[2], __builtin_fmaf(a[1], a[1], a[0] * a[0]));
@@ -474,7 +479,7 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
                               const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream);
 // one launch of the NEE kernels (pt_nee.hip), as nee_launch_for (pt_context.hpp) fills it from the context.  Each family is the one before it
 // with one more feature compiled in; a launch takes the first family that covers what the frame needs
-enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium, kNeeGrid };
+enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium, kNeeGrid, kNeeInterior };
 struct NeeLaunch {
     const EnvView* env;          // null: the instances without an environment
     bool tiled;                  // the rounds of pt_render_adaptive_ex: k_nee*_tiles over the p.n_tiles 8x8 frame tiles of p.tile_list (null: the
@@ -486,16 +491,19 @@ struct NeeLaunch {
                                  // kNeeLens whatever the options say; option frosted with a type-6 material takes kNeeFrosted, lens or not;
                                  // a light set with a pickable light (pt_set_lights) takes kNeeLights whatever else is on; a medium with
                                  // sigma_t > 0 (pt_set_medium) takes kNeeMedium whatever else is on, lights or not; a live density grid
-                                 // (pt_set_medium_density with such a medium) takes kNeeGrid whatever else is on
+                                 // (pt_set_medium_density with such a medium) takes kNeeGrid whatever else is on; a live interior binding
+                                 // (pt_set_material_interior) takes kNeeInterior whatever else is on, medium and grid or not
     int flags;                   // the options themselves, for the families in which they are run-time fields: bit 0 glossy (type 4 is live;
                                  // read from kNeeCoated on), bit 1 coated (type 5 is live; from kNeeLens on), bit 2 a lens with aperture > 0 is
                                  // set (from kNeeFrosted on; else each sample starts on the pinhole ray), bit 3 frosted with a type-6 material
                                  // uploaded (type 6 is live; read from kNeeLights on), bit 4 a light set with a pickable light is held (read
-                                 // from kNeeMedium on; else `lights` is an empty set with P_ana = 0)
+                                 // from kNeeMedium on; else `lights` is an empty set with P_ana = 0), bit 5 a medium with sigma_t > 0 is held
+                                 // and bit 6 its density grid is live (read by kNeeInterior, which serves frames without either)
     LensView lens;               // read from kNeeLens on
     LightsView lights;           // read from kNeeLights on
     MediumView medium;           // read from kNeeMedium on
-    GridView grid;               // read by kNeeGrid
+    GridView grid;               // read from kNeeGrid on
+    InteriorView interior;       // read by kNeeInterior
     int* block;                  // out, may be null: the workgroup size the launch took, as launch_lanes / launch_lanes_env_tiles_smooth chose
                                  // it (0: nothing was launched, an empty tile list)
 };
@@ -514,6 +522,8 @@ hipError_t launch_debug_glossy(const float* in, int64_t n, float* out, hipStream
 hipError_t launch_debug_medium(const MediumView& mv, const float* in, int64_t n, float* out, hipStream_t stream);
 // density grid (pt_medium.hip): pt_debug_grid's kernel, 12 floats in and 8 out per item
 hipError_t launch_debug_grid(const MediumView& mv, const GridView& gv, const float* in, int64_t n, float* out, hipStream_t stream);
+// interiors (pt_medium.hip): pt_debug_interior's kernel, 12 floats in and 10 out per item
+hipError_t launch_debug_interior(const float* in, int64_t n, float* out, hipStream_t stream);
 // coated diffuse (pt_glossy.hip): pt_debug_coated's kernel, 12 floats in and 10 out per item
 hipError_t launch_debug_coated(const float* in, int64_t n, float* out, hipStream_t stream);
 // rough dielectric (pt_glossy.hip): pt_debug_frosted's kernel, 12 floats in and 10 out per item

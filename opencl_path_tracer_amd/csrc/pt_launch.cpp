@@ -367,6 +367,7 @@ static void launch_cfg(pt_context* ctx, const RenderParams& p, LaunchConfig* lc)
 
 int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
     if (ctx && medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal("pt_generate_rays"));
+    if (ctx && interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal("pt_generate_rays"));
     if (ctx && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_generate_rays"));
     if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_generate_rays: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_generate_rays: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
@@ -387,6 +388,7 @@ int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
 
 int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t current_sample) {
     if (ctx && medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal("pt_trace_rays"));
+    if (ctx && interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal("pt_trace_rays"));
     if (ctx && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_trace_rays"));
     if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_trace_rays: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_trace_rays: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
@@ -595,6 +597,7 @@ static int launch_megakernel(pt_context* ctx, RenderParams& p, const int32_t* ti
 
 int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples) {
     if (ctx && medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal("pt_render"));
+    if (ctx && interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal("pt_render"));
     if (ctx && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_render"));
     if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_render: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_render: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
@@ -668,6 +671,7 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
     }
     if (!why.empty()) return fail(ctx, PT_EINVAL, who + ": " + why);
     if (!nee && medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal(who));
+    if (!nee && interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal(who));
     if (nee && grid_on(ctx) && !grid_unbounded(ctx).empty()) return fail(ctx, PT_EINVAL, who + ": " + grid_unbounded(ctx));
     if (lights_on(ctx) && (!nee || ap->strategy == PT_NEE_BSDF))
         return fail(ctx, PT_EINVAL, lights_refusal(nee ? who + " with strategy PT_NEE_BSDF" : who));

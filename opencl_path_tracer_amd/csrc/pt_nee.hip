@@ -24,8 +24,11 @@
 //           run-time field (flags bit 4)
 //   GRID    the medium's extinction is sigma_t times a voxel density (pt_set_medium_density, section 5.20): the free flight and the transmittance
 //           walk the grid (grid_walk, pt_device.hpp); everything else is MEDIUM's
-// Each flag from SMOOTH on requires the one before it.  The kernels are the ten families the host can ask for (NeeFamily, pt_internal.hpp)
-// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights, _medium, _grid: each is the one before it with one more flag -- times ENV and TILED
+//   INTERIOR  a type-2 or type-6 material may hold an interior (pt_set_material_interior, section 5.21): a segment inside such a dielectric takes
+//           Beer-Lambert absorption and may end at a scatter vertex of the interior; whether a medium is held and whether its grid is live are
+//           run-time fields (flags bits 5 and 6)
+// Each flag from SMOOTH on requires the one before it.  The kernels are the eleven families the host can ask for (NeeFamily, pt_internal.hpp)
+// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights, _medium, _grid, _interior: each is the one before it with one more flag -- times ENV and TILED
 // (k_nee_env*, k_nee_tiles*, k_nee_env_tiles*).  In a family whose option is off the data is null (vn, tv.uv) or the field clear.
 #include "pt_device.hpp"
 
@@ -133,10 +136,21 @@ struct GridSlot<true> {
     GridView v;                    // the densities, the dimensions and the cell sizes: wave-uniform
 };
 
+// what a hook carries for the interiors of dielectrics (pt_set_material_interior): nothing without them
+template <bool INTERIOR>
+struct InteriorSlot {};
+template <>
+struct InteriorSlot<true> {
+    InteriorView v;                // the table: two float4 per material on the device
+    bool medium = true;            // a medium with sigma_t > 0 is held in this launch (else no free flight outside and T = 1, as in the instances without one)
+    bool grid = true;              // ... and its density grid is live (else the homogeneous medium's flight and transmittance)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
 template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false, bool FROST = false,
-          bool LIGHTS = false, bool MEDIUM = false, bool GRID = false>
+          bool LIGHTS = false, bool MEDIUM = false, bool GRID = false, bool INTERIOR = false>
 struct NeeHook {
+    static_assert(GRID || !INTERIOR, "the interior instances are built on the grid code");
     static_assert(MEDIUM || !GRID, "the grid instances are built on the medium code");
     static_assert(LIGHTS || !MEDIUM, "the medium instances are built on the lights code");
     static_assert(FROST || !LIGHTS, "the lights instances are built on the frosted code");
@@ -174,6 +188,7 @@ struct NeeHook {
     LightsSlot<LIGHTS> lg;
     MediumSlot<MEDIUM> md;
     GridSlot<GRID> gr;
+    InteriorSlot<INTERIOR> in;
 
     // MEDIUM: the lane enters shade_hit at a scatter vertex
     PT_DEV bool scatters() const {
@@ -184,7 +199,13 @@ struct NeeHook {
     // when the segment reaches its end.  A segment with nothing inside the box draws no number (d >= 0 is never below L = 0)
     // GRID: the same through the voxels: tau = -log1pf(-u) of the same number against the optical depth the walk accumulates
     PT_DEV float free_flight(f3 rP, f3 rD, float t) const {
-        if constexpr (GRID) {
+        if constexpr (INTERIOR) {          // (the grid is a run-time answer here)
+            if (in.grid) {
+                const float tau = -log1pf(-nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 0)));
+                const GridWalk w = grid_walk<true>(md.v, gr.v, rP, rD, t, tau);
+                return w.voxel >= 0 ? max0(w.s) : -1.0f;
+            }
+        } else if constexpr (GRID) {
             const float tau = -log1pf(-nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 0)));      // (a hash, not a draw: unused where the clip is empty)
             const GridWalk w = grid_walk<true>(md.v, gr.v, rP, rD, t, tau);
             return w.voxel >= 0 ? max0(w.s) : -1.0f;       // (s < 0 would take an accumulated depth a rounding past tau in a voxel at the origin)
@@ -210,6 +231,36 @@ struct NeeHook {
             rP = madd(rD, s, rP);
             rD = normalize3(medium_direction(md.v.g, rD, u1, u2, &gs.pb));
             after_lobe = true;
+        }
+    }
+    // INTERIOR: a medium with sigma_t > 0 is held (a run-time answer in the interior instances only: the medium ones run only when one is)
+    PT_DEV bool medium_live() const {
+        if constexpr (INTERIOR) return in.medium;
+        else return MEDIUM;
+    }
+    // INTERIOR: the free flight of segment k inside a dielectric whose hit is at t, through the interior q0 = {sigma_a.rgb, sigma_s}: the
+    // distance of the scatter vertex, or -1 when the segment reaches its hit.  The exterior medium never draws while inside, so dimension 0
+    // of its stream at this segment is free
+    PT_DEV float interior_flight(const float4 q0, float t) const {
+        if (!(q0.w > 0.0f)) return -1.0f;          // (no hash without scattering)
+        return ptamd::interior_flight(q0.w, nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 0)), t);
+    }
+    // INTERIOR: Beer-Lambert over the length l of the segment inside; false: the factor left nothing and the path ends
+    PT_DEV bool interior_absorb(PathRegs& st, const float4 q0, float l) const {
+        const f3 fs = st.S() * ptamd::interior_absorb(mk(q0.x, q0.y, q0.z), l);
+        st.setS(fs);
+        return fs.x != 0.0f || fs.y != 0.0f || fs.z != 0.0f;
+    }
+    // INTERIOR: scatter_direction with the vertex's own g and the after-lobe answer: a scatter vertex of an interior is no lobe vertex for what
+    // follows (an emitter hit or a sky miss on the next segment has weight 1, as after a refraction)
+    PT_DEV void scatter_direction(f3& rP, f3& rD, float s, float g, bool lobe) {
+        if constexpr (MEDIUM) {
+            const float u1 = nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 1)), u2 = nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 2));
+            float pb;
+            rP = madd(rD, s, rP);
+            rD = normalize3(medium_direction(g, rD, u1, u2, &pb));
+            if (lobe) gs.pb = pb;
+            after_lobe = lobe;
         }
     }
     // LIGHTS: type 6 is live (option frosted; a run-time answer in the lights instances only: the frosted ones run only when it is)
@@ -641,7 +692,15 @@ struct NeeHook {
         const float cosx = dot3(N, w);
         if (!((mvx || cosx > 0.0f) && pl > 0.0f && pl < __builtin_inff())) return;
         if constexpr (SMOOTH) if (!(mvx || dot3(geo(N), w) > 0.0f)) return;   // as in light_sample
-        if constexpr (GRID) {          // (for a vertex outside a dielectric)
+        if constexpr (INTERIOR) {      // (the medium and its grid are run-time answers here)
+            md.T = 1.0f;
+            if (!ins && in.medium) {
+                if (in.grid) {
+                    const float depth = grid_walk<false>(md.v, gr.v, o, w, limit, __builtin_inff()).acc;
+                    if (depth != 0.0f) md.T = expf(-depth);
+                } else md.T = medium_transmittance(md.v, o, w, limit);
+            }
+        } else if constexpr (GRID) {   // (for a vertex outside a dielectric)
             md.T = 1.0f;
             if (!ins) {
                 const float depth = grid_walk<false>(md.v, gr.v, o, w, limit, __builtin_inff()).acc;
@@ -704,16 +763,18 @@ struct NeeHook {
 // MEDIUM (pt_set_medium; k_nee*_medium below; on the LIGHTS code only): between closest_hit and shade_hit a segment may end at a scatter vertex of
 // the medium; metal bit 4: a light set with a pickable light is held
 // GRID (pt_set_medium_density; k_nee*_grid below; on the MEDIUM code only): the hook's free flight and transmittance walk the density grid
+// INTERIOR (pt_set_material_interior; k_nee*_interior below; on the GRID code only): a segment inside a dielectric whose material holds an interior
+// takes its absorption and may end at its scatter vertex; metal bit 5: a medium with sigma_t > 0 is held, bit 6: its grid is live
 template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false,
-          bool FROST = false, bool LIGHTS = false, bool MEDIUM = false, bool GRID = false>
+          bool FROST = false, bool LIGHTS = false, bool MEDIUM = false, bool GRID = false, bool INTERIOR = false>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr,
                       int metal = 0, const LensView* lens = nullptr, const LightsView* lights = nullptr, const MediumView* medium = nullptr,
-                      const GridView* grid = nullptr) {
+                      const GridView* grid = nullptr, const InteriorView* interior = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS, MEDIUM, GRID> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS, MEDIUM, GRID, INTERIOR> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (TEX) hook.tx.v = *tv;
     if constexpr (LENS) {
@@ -734,6 +795,11 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
     }
     if constexpr (MEDIUM) hook.md.v = *medium;
     if constexpr (GRID) hook.gr.v = *grid;
+    if constexpr (INTERIOR) {
+        hook.in.v = *interior;
+        hook.in.medium = (metal & 32) != 0;
+        hook.in.grid = (metal & 64) != 0;
+    }
     const int camX = (int)p.cam.XM;
     unsigned rendered = 0;                     // TILED: pixels this lane rendered (statistic "samples", as k_render counts them)
     if constexpr (TILED) npix = (long long)p.n_tiles * 64;      // work items: 64 per listed tile
@@ -782,7 +848,40 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
             for (int k = 0; k < p.iterations; ++k) {
                 float t;
                 const int ti = closest_hit<MODE, false>(sv, rP, rD, stk, &t, &wc);
-                if constexpr (MEDIUM) {
+                if constexpr (INTERIOR) {
+                    // MEDIUM's body below with the interior in the `else` of `if (!inside)`: the segment runs inside the dielectric whose
+                    // boundary it hits at ti, the surface the path will leave through, and the interior is the one bound to that material.
+                    // Only lanes that are inside look the table up.  Its scatter vertex takes no light sample (a shadow ray from inside ends
+                    // on the object's own boundary), so the lane skips shade_hit
+                    hook.k = k;
+                    float ts = -1.0f;              // the distance of this segment's scatter vertex; < 0: it reaches its hit or misses
+                    float ig = 0.0f;               // the g of the interior it scatters in
+                    bool isc = false, dead = false;
+                    if (!inside) {
+                        if (hook.medium_live()) ts = hook.free_flight(rP, rD, ti < 0 ? __builtin_inff() : t);
+                    } else if (ti >= 0) {
+                        const float4* __restrict__ rec = hook.in.v.rec + 2 * (size_t)p.meta[ti].mati;
+                        const float4 q1 = rec[1];
+                        if (q1.y != 0.0f) {
+                            const float4 q0 = rec[0];
+                            ts = hook.interior_flight(q0, t);
+                            isc = ts >= 0.0f;
+                            dead = !hook.interior_absorb(st, q0, isc ? ts : t);
+                            ig = q1.x;
+                        }
+                    }
+                    if (dead) break;
+                    const bool sc = ts >= 0.0f && !isc;
+                    hook.md.sc = sc;
+                    if (ti < 0 && !sc) {
+                        if constexpr (ENV) hook.miss(st, rD, k);
+                        break;
+                    }
+                    if (sc && !hook.scatter_albedo(st)) break;
+                    if (!isc) shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, sc ? ts : t, &hook);
+                    if (sc) hook.scatter_direction(rP, rD, ts);
+                    if (isc) hook.scatter_direction(rP, rD, ts, ig, false);
+                } else if constexpr (MEDIUM) {
                     // the free flight of the segment; then the scatter vertex: its factor here, its light sample in shade_hit's one call of
                     // light_sample (the lane does nothing else there), its new direction after it
                     hook.k = k;
@@ -1016,6 +1115,29 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_grid(RenderParams p, Ne
     nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv);
 }
 
+// the interior instances (a material holds an interior): the grid kernels with the interiors' table as one more argument; flags bit 5: a medium with
+// sigma_t > 0 is held (else mv is all zero and never read), bit 6: its grid is live (else gv is never read)
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_interior(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
+                                                        GridView gv, InteriorView iv, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_interior(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
+                                                            MediumView mv, GridView gv, InteriorView iv, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_interior(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
+                                                              GridView gv, InteriorView iv) {
+    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_interior(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv,
+                                                                  LightsView lg, MediumView mv, GridView gv, InteriorView iv) {
+    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -1059,7 +1181,9 @@ static hipError_t launch_nee_family(K k, KE ke, KT kt, KET ket, const RenderPara
 // (the compiler no longer derives for a helper they share that its triangle index is never negative; profiles/medium/README.md)
 // The grid family likewise (pt_nee_grid.hip, PT_NEE_GRID_TU, launch_nee_grid), so that the medium instances compile as they did before it
 hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
+// The interior family likewise (pt_nee_interior.hip, PT_NEE_INTERIOR_TU, launch_nee_interior)
 hipError_t launch_nee_grid(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
+hipError_t launch_nee_interior(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
 #if defined(PT_NEE_MEDIUM_TU)
 hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     return launch_nee_family<kWideAll>(NEE_PICK(k_nee_medium), NEE_PICK(k_nee_env_medium), NEE_PICK(k_nee_tiles_medium), NEE_PICK(k_nee_env_tiles_medium), p, lt, nl, npix,
@@ -1069,6 +1193,11 @@ hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const Ne
 hipError_t launch_nee_grid(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     return launch_nee_family<kWideAll>(NEE_PICK(k_nee_grid), NEE_PICK(k_nee_env_grid), NEE_PICK(k_nee_tiles_grid), NEE_PICK(k_nee_env_tiles_grid), p, lt, nl, npix,
                                        cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium, nl.grid);
+}
+#elif defined(PT_NEE_INTERIOR_TU)
+hipError_t launch_nee_interior(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+    return launch_nee_family<kWideAll>(NEE_PICK(k_nee_interior), NEE_PICK(k_nee_env_interior), NEE_PICK(k_nee_tiles_interior), NEE_PICK(k_nee_env_tiles_interior), p, lt, nl,
+                                       npix, cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium, nl.grid, nl.interior);
 }
 #else
 static hipError_t launch_nee_of_family(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
@@ -1100,13 +1229,14 @@ static hipError_t launch_nee_of_family(const RenderParams& p, const NeeTable& lt
                                      cu_count, stream, nl.vn, nl.tv, nl.flags & 15, nl.lens, nl.lights);
     case kNeeMedium: return launch_nee_medium(p, lt, nl, npix, cu_count, stream);
     case kNeeGrid: return launch_nee_grid(p, lt, nl, npix, cu_count, stream);
+    case kNeeInterior: return launch_nee_interior(p, lt, nl, npix, cu_count, stream);
     }
     return hipErrorInvalidValue;
 }
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     t_lanes_block = 0;
     const hipError_t e = launch_nee_of_family(p, lt, nl, npix, cu_count, stream);
-    if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit, in pt_nee_medium.hip's or in pt_nee_grid.hip's)
+    if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit, in pt_nee_medium.hip's, pt_nee_grid.hip's or pt_nee_interior.hip's)
     return e;
 }
 #endif

@@ -45,6 +45,8 @@ class SceneSpec:
                                                      # g=, bounds=(lo, hi)) (Scene.load applies it)
     medium_density: object = None                    # optional: a voxel density for that medium, an array (nz, ny, nx) as
                                                      # Scene.set_medium_density takes it (Scene.load applies it after the medium)
+    interiors: dict = field(default_factory=dict)    # optional: {index into materials: Scene.set_material_interior's arguments as a dict}, the
+                                                     # medium inside a type-2 or type-6 material (Scene.load applies it)
 
     @property
     def ntris(self):
@@ -164,7 +166,7 @@ def smoke_plume(n=32):
     return np.maximum(plume, mist).astype(np.float32)
 
 
-def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False, frosted=False, lamp="quad", fog=0.0, density=None):
+def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=False, coated=False, frosted=False, lamp="quad", fog=0.0, density=None, tint=None, wax=0.0):
     """Scene CB of SURVEY 8(d): 12 wall/lamp triangles + two tessellated spheres
     (radius 200; CHROMIUM at (250,200,300), GLASS at (750,200,-200)), 3 objects.
     smooth: the spheres carry their analytic vertex normals (shaded with them under option smooth_normals).
@@ -184,7 +186,13 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
     fog: sigma_t > 0 fills the room (CORNELL_ROOM) with a white medium of that extinction per unit, albedo 0.9 and g = 0.6
     (Scene.set_medium through Scene.load; only render_nee renders the scene then).  1e-3 is a mean free path of the room's width.
     density: with fog, a voxel density (nz, ny, nx) over the room, such as smoke_plume(): the extinction is fog x density
-    (Scene.set_medium_density through Scene.load)."""
+    (Scene.set_medium_density through Scene.load).
+    tint, wax: the glass sphere (GLASS, or its frosted copy) gets an interior (Scene.set_material_interior through Scene.load; only render_nee
+    renders the scene then).  tint: the colour (rgb in (0, 1]) white light has left after crossing the sphere's diameter, 400 units:
+    sigma_a = -ln(tint) / 400.  wax > 0: grey scattering with that many mean free paths per diameter, sigma_s = wax / 400, and g = 0.8.
+    Not together with coated, whose plastic has no inside."""
+    if (tint is not None or wax > 0.0) and coated:
+        raise ValueError("cornell_box: tint and wax fill the glass sphere, which coated replaces with an opaque plastic")
     if coated and frosted:
         raise ValueError("cornell_box: coated and frosted both replace the glass sphere's material")
     if lamp not in ("quad", "point", "spot"):
@@ -235,6 +243,12 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
             spec.medium_density = np.ascontiguousarray(density, dtype=np.float32)
     elif density is not None:
         raise ValueError("cornell_box: density needs fog > 0 (the medium whose extinction it scales)")
+    if tint is not None or wax > 0.0:
+        c = np.ones(3) if tint is None else np.asarray(tint, dtype=np.float64).reshape(3)
+        if not (np.all(c > 0.0) and np.all(c <= 1.0)):
+            raise ValueError("cornell_box: tint must lie in (0, 1] per channel")
+        spec.interiors = {glass: dict(sigma_a=tuple(float(v) for v in (-np.log(c) / 400.0 + 0.0)), sigma_s=float(wax) / 400.0,
+                                      g=0.8 if wax > 0.0 else 0.0)}
     return spec
 
 
