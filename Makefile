@@ -10,7 +10,7 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-s
 
 all: $(PKG)/libptamd.so oracle tests/cpp/dropin check-isa
 
-SRCS    := $(CSRC)/pt_host.cpp $(CSRC)/pt_builder.cpp $(CSRC)/pt_launch.cpp $(CSRC)/pt_obj.cpp $(CSRC)/pt_kernels.hip $(CSRC)/pt_wavefront.hip $(CSRC)/pt_debug.hip $(CSRC)/pt_lbvh.hip $(CSRC)/pt_sahdev.hip $(CSRC)/pt_widedev.hip $(CSRC)/pt_comm.hip $(CSRC)/pt_adaptive.hip $(CSRC)/pt_denoise.hip $(CSRC)/pt_nee.hip $(CSRC)/pt_temporal.hip $(CSRC)/pt_shaderec.hip $(CSRC)/pt_smooth.hip $(CSRC)/pt_texture.hip $(CSRC)/pt_glossy.hip $(CSRC)/pt_lens.hip $(CSRC)/pt_image.cpp $(CSRC)/pt_wide.cpp $(CSRC)/pt_env.cpp $(CSRC)/pt_lights.cpp $(CSRC)/pt_medium.cpp $(CSRC)/pt_interior.cpp $(CSRC)/pt_medium.hip $(CSRC)/pt_nee_medium.hip $(CSRC)/pt_nee_grid.hip $(CSRC)/pt_nee_interior.hip
+SRCS    := $(CSRC)/pt_host.cpp $(CSRC)/pt_builder.cpp $(CSRC)/pt_launch.cpp $(CSRC)/pt_obj.cpp $(CSRC)/pt_kernels.hip $(CSRC)/pt_wavefront.hip $(CSRC)/pt_debug.hip $(CSRC)/pt_lbvh.hip $(CSRC)/pt_sahdev.hip $(CSRC)/pt_widedev.hip $(CSRC)/pt_comm.hip $(CSRC)/pt_adaptive.hip $(CSRC)/pt_denoise.hip $(CSRC)/pt_nee.hip $(CSRC)/pt_temporal.hip $(CSRC)/pt_shaderec.hip $(CSRC)/pt_smooth.hip $(CSRC)/pt_texture.hip $(CSRC)/pt_glossy.hip $(CSRC)/pt_lens.hip $(CSRC)/pt_image.cpp $(CSRC)/pt_wide.cpp $(CSRC)/pt_env.cpp $(CSRC)/pt_lights.cpp $(CSRC)/pt_medium.cpp $(CSRC)/pt_interior.cpp $(CSRC)/pt_lighttree.cpp $(CSRC)/pt_medium.hip $(CSRC)/pt_nee_medium.hip $(CSRC)/pt_nee_grid.hip $(CSRC)/pt_nee_interior.hip $(CSRC)/pt_nee_lighttree.hip
 HDRS    := $(CSRC)/pt_internal.hpp $(CSRC)/pt_context.hpp $(CSRC)/pt_device.hpp include/pt_api.h
 OBJS    := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 
@@ -26,6 +26,8 @@ build/pt_nee_medium.hip.o: $(CSRC)/pt_nee.hip
 build/pt_nee_grid.hip.o: $(CSRC)/pt_nee.hip
 # (and pt_nee_interior.hip for the interior family)
 build/pt_nee_interior.hip.o: $(CSRC)/pt_nee.hip
+# (and pt_nee_lighttree.hip for the light-tree family)
+build/pt_nee_lighttree.hip.o: $(CSRC)/pt_nee.hip
 
 # A/B builds of the kernels for experiments: make ab AB=name ABFLAGS="-DPT_X=1" -> $(PKG)/libptamd_name.so
 # (select it with PTAMD_LIB=... ; never loaded by default).  Always from scratch, every compile checked, explicit objects.
@@ -52,8 +54,8 @@ check-isa: build/isa/pt_kernels.s build/isa/pt_wavefront.s tools/check_isa.py
 # Host-side scene path (pt_add_obj: parallel parse, threaded encounter ranks; pt_upload_triangles: thread pool, parallel SAH
 # top, splice, 4-wide collapse) under ThreadSanitizer and under AddressSanitizer + UBSan, on a generated 200k-triangle OBJ,
 # one context and then two at once.  CPU only (host-only contexts); the device objects are linked in unchanged.
-HOSTSRC := pt_host.cpp pt_builder.cpp pt_launch.cpp pt_obj.cpp pt_wide.cpp pt_image.cpp pt_env.cpp pt_lights.cpp pt_medium.cpp pt_interior.cpp
-DEVOBJ  := build/pt_kernels.hip.o build/pt_wavefront.hip.o build/pt_debug.hip.o build/pt_lbvh.hip.o build/pt_sahdev.hip.o build/pt_widedev.hip.o build/pt_comm.hip.o build/pt_adaptive.hip.o build/pt_denoise.hip.o build/pt_nee.hip.o build/pt_temporal.hip.o build/pt_shaderec.hip.o build/pt_smooth.hip.o build/pt_texture.hip.o build/pt_glossy.hip.o build/pt_lens.hip.o build/pt_medium.hip.o build/pt_nee_medium.hip.o build/pt_nee_grid.hip.o build/pt_nee_interior.hip.o
+HOSTSRC := pt_host.cpp pt_builder.cpp pt_launch.cpp pt_obj.cpp pt_wide.cpp pt_image.cpp pt_env.cpp pt_lights.cpp pt_medium.cpp pt_interior.cpp pt_lighttree.cpp
+DEVOBJ  := build/pt_kernels.hip.o build/pt_wavefront.hip.o build/pt_debug.hip.o build/pt_lbvh.hip.o build/pt_sahdev.hip.o build/pt_widedev.hip.o build/pt_comm.hip.o build/pt_adaptive.hip.o build/pt_denoise.hip.o build/pt_nee.hip.o build/pt_temporal.hip.o build/pt_shaderec.hip.o build/pt_smooth.hip.o build/pt_texture.hip.o build/pt_glossy.hip.o build/pt_lens.hip.o build/pt_medium.hip.o build/pt_nee_medium.hip.o build/pt_nee_grid.hip.o build/pt_nee_interior.hip.o build/pt_nee_lighttree.hip.o
 SANFLAGS := -O1 -g -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -Iinclude -I$(CSRC)
 sanitize-host: $(DEVOBJ)
 	@for san in thread address,undefined; do d=build/san_$$(echo $$san | tr , _); mkdir -p $$d; \

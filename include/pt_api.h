@@ -484,6 +484,55 @@ int pt_get_material_interior(const pt_context* ctx, int32_t material, pt_interio
  * channel, the new direction from (u1, u2) around D (unit), 0}.  No binding is needed */
 int pt_debug_interior(pt_context* ctx, const float* in, int64_t n, float* out);
 
+/* ---- a light hierarchy for pt_render_nee (new: opt-in with option "light_tree"; many emitters) -----------
+ * Option "light_tree" = 1 (default 0: every frame is what it was, bit for bit): the triangle-light branch of the light sample picks its
+ * triangle by walking a binary tree over the light table, with a probability P that depends on the vertex, and the weight of an emitter hit
+ * uses the same P.  Everything else of the estimator stays: the point on the triangle, the shadow ray, the contribution, the sky branch and
+ * P_env, the analytic branch and P_ana, the hash streams and the LCG (rnds and rays after a frame are the option-off frame's).  The option is
+ * inert where no triangle-light sample is taken: pt_render, the wavefront path, PT_NEE_BSDF, a scene without emitting triangles.  With the
+ * option on and a non-empty light table the NEE launches take the light-tree instances of k_nee (stat "nee_family" 11), which serve frames
+ * with and without an interior binding, a medium and its grid.
+ * The tree (built on the host next to the light table, deterministic, invalidated with the table; stats "light_tree_nodes",
+ * "light_tree_depth"): one light per leaf; a light's weight phi is the table's, area (E.r + E.g + E.b), in double.  A node holds the box of its
+ * lights' vertices as a sphere -- centre c = the box's centre rounded to float32, radius r = the largest distance in double from that c to a
+ * corner of the box, rounded up to float32 and then one ulp more, so the sphere contains the box -- and phi = phi(left) + phi(right), summed in
+ * double and rounded to float32 once per node.  A node of more than one light splits at the spatial median of its lights' centroids
+ * ((r1 + r2 + r3) / 3 in double) along the longest axis of the centroids' box (z before y before x on a tie; left: centroid < median, in the
+ * order the lights had); when that leaves a side empty, or when the node's depth d and count n have d + 1 + ceil(log2(n - 1)) > 64, it
+ * splits into the first ceil(n / 2) and the rest of its lights ordered by the centroid's coordinate on that axis (stable).  So no leaf is
+ * deeper than 64.  Nodes lie depth first, the left child at node + 1, and the lights in leaf order (tree order): a node covers the tree-order
+ * lights [first, first + count).
+ * The walk from origin o with cull normal G and a number u in [0, 1), float32 with no contraction (dot products as fma(z, z', fma(y, y', x x'))):
+ *   importance of a child: 0 if fma-dot(G, c - o) < -r (its sphere lies entirely below the horizon), else phi / max(|c - o|^2, r^2);
+ *   if iL + iR is not a positive finite number (both culled; a light at o), iL, iR = the two phi; pL = iL / (iL + iR) (0.5 if that is no
+ *   number in [0, 1]); u < pL: left, u = u / pL, P *= pL; else right, u = (u - pL) / (1 - pL), P *= 1 - pL; u >= 1 becomes 1 - 2^-24.
+ *   At a leaf the light is picked with probability P (1 for a table of one light).  No orientation cones (the emitters are two-sided) and no
+ *   cosine bound (sqrt(1 - cos^2) is ill-conditioned where it would matter; the cull removes what a room's own walls cannot see).
+ * At a lobe vertex: o is the shadow ray's origin, G the geometric normal on the ray's side (the zero vector at a scatter vertex of the medium,
+ * where nothing is culled), u = u0, dimension 0 of the light sample's stream; no extra number is drawn.
+ *   p_l = P inv_area r^2 / |cos_y|, times 1 - P_env and 1 - P_ana as before, inv_area = (float)(1 / area), the value P_sel / area has for a
+ *   table of one light.
+ * An emitter hit after a lobe vertex: the weight walk descends from the root towards the hit triangle's leaf by the nodes' ranges, with the o
+ * and G of that previous lobe vertex, and multiplies the same branch probabilities in the same order; p_l = P inv_area t^2 / cos as before.
+ * The pick's P of a light and the weight walk's P of that light are the same float.
+ * Two limits: P is a product of rounded branch probabilities, not an exact count of u0 values as P_sel is (the P of all lights sum to 1
+ * within depth 2^-22), and the 24 bits of u0 cannot reach a leaf whose probability is below 2^-24. */
+/* the tree (host only, as pt_debug_light_table): *n_nodes, *n_lights = the counts; the first min(node_cap, *n_nodes) nodes, 8 floats each {c.xyz,
+ * r, phi, bits(first), bits(count), bits(right child; the left one is node + 1; count 1: a leaf)}, and the first min(light_cap, *n_lights)
+ * tree-order lights as add-order triangle indices are written (either array may be NULL) */
+int pt_debug_light_tree(pt_context* ctx, float* nodes, int64_t node_cap, int64_t* n_nodes, int32_t* orig_tri, int64_t light_cap, int64_t* n_lights);
+typedef struct pt_light_tree_eval {
+    int32_t tri;        /* the add-order triangle the walk picked (-1: an empty table) */
+    float p;            /* its probability P */
+    float p_weight;     /* the weight walk's P of tris[i] (0 where tris[i] is no light) */
+    int32_t slot;       /* the picked light's tree-order index */
+} pt_light_tree_eval;   /* 16 bytes */
+/* both walks on given numbers, n items: points (o, 3 floats each), normals (G, 3 floats each), u0 and tris (add-order triangle indices) in,
+ * out[i] as above; on_device = 0: by the library's host code (any context with the scene uploaded, host-only too), 1: by the kernel
+ * k_debug_light_tree, which calls what the light-tree instances of k_nee call.  Option "light_tree" need not be on */
+int pt_debug_light_tree_eval(pt_context* ctx, const float* points, const float* normals, const float* u0, const int32_t* tris, int64_t n,
+                             pt_light_tree_eval* out, int32_t on_device);
+
 /* ---- smooth shading from vertex normals for pt_render_nee (new: opt-in with option "smooth_normals"; the reference shades with the
  * triangle's geometric normal only) -----------
  * Authoring (host data; all of it works on a host-only context, none of it rebuilds the BVH).  Triangles are counted in add order over

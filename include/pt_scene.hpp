@@ -142,6 +142,15 @@ public:
     void clear_material_interiors() { ck(pt_clear_material_interiors(ctx)); }
     bool material_interior(int32_t material, pt_interior* out) { return ck(pt_get_material_interior(ctx, material, out)) == 1; }
     void debug_interior(const float* in, int64_t n, float* out) { ck(pt_debug_interior(ctx, in, n, out)); }
+    // the light hierarchy of render_nee (set_option("light_tree", 1); pt_debug_light_tree, pt_debug_light_tree_eval): the nodes (8 floats each) and
+    // the tree-order lights read back, and both walks evaluated per item by the host code or, on_device, by k_debug_light_tree
+    void debug_light_tree(float* nodes, int64_t node_cap, int64_t* n_nodes, int32_t* orig_tri, int64_t light_cap, int64_t* n_lights) {
+        ck(pt_debug_light_tree(ctx, nodes, node_cap, n_nodes, orig_tri, light_cap, n_lights));
+    }
+    void debug_light_tree_eval(const float* points, const float* normals, const float* u0, const int32_t* tris, int64_t n, pt_light_tree_eval* out,
+                               bool on_device = false) {
+        ck(pt_debug_light_tree_eval(ctx, points, normals, u0, tris, n, out, on_device ? 1 : 0));
+    }
     // vertex normals for smooth shading (set_option("smooth_normals", 1); render_nee only): normals = count x 9 floats, n1 n2 n3 per
     // triangle in add order starting at first_triangle; compute_vertex_normals derives them per object (obj = -1: every object)
     void set_vertex_normals(const float* normals, int64_t count, int64_t first_triangle = 0) { ck(pt_set_vertex_normals(ctx, first_triangle, count, normals)); }

@@ -56,6 +56,7 @@ EXPORTS = [
     "pt_medium_defaults", "pt_set_medium", "pt_clear_medium", "pt_get_medium", "pt_debug_medium",
     "pt_set_medium_density", "pt_clear_medium_density", "pt_debug_medium_density", "pt_debug_grid",
     "pt_interior_defaults", "pt_set_material_interior", "pt_clear_material_interiors", "pt_get_material_interior", "pt_debug_interior",
+    "pt_debug_light_tree", "pt_debug_light_tree_eval",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
     "pt_render_aovs", "pt_read_aovs", "pt_aov_defaults", "pt_render_aovs_ex", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
@@ -165,6 +166,8 @@ def _load():
     sig("pt_clear_material_interiors", C.c_int, vp)
     sig("pt_get_material_interior", C.c_int, vp, i32, vp)
     sig("pt_debug_interior", C.c_int, vp, vp, i64, vp)
+    sig("pt_debug_light_tree", C.c_int, vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64))
+    sig("pt_debug_light_tree_eval", C.c_int, vp, vp, vp, vp, vp, i64, vp, i32)
     sig("pt_image_read_pfm", C.c_int, C.c_char_p, vp, i64, C.POINTER(i32), C.POINTER(i32))
     sig("pt_read_variance", C.c_int, vp, vp, i64)
     sig("pt_device_variance", vp, vp)
@@ -432,6 +435,11 @@ def interior_from_tint(color, distance):
     if not (np.all(c > 0.0) and np.all(c <= 1.0)) or not float(distance) > 0.0:
         raise ValueError("interior_from_tint: color must lie in (0, 1] per channel and distance must be > 0")
     return tuple(float(v) for v in (-np.log(c) / float(distance) + 0.0))
+
+
+# a node of pt_debug_light_tree (8 words) and pt_light_tree_eval (include/pt_api.h)
+LIGHT_TREE_NODE = np.dtype([("c", np.float32, 3), ("r", np.float32), ("phi", np.float32), ("first", np.int32), ("count", np.int32), ("right", np.int32)])
+LIGHT_TREE_EVAL = np.dtype([("tri", np.int32), ("p", np.float32), ("p_weight", np.float32), ("slot", np.int32)])
 
 
 def medium_defaults():
@@ -1069,6 +1077,33 @@ class Scene:
         cdf = np.zeros(n.value, dtype=np.float32)
         self._ck(LIB.pt_debug_light_table(self._h, _ptr(tri), _ptr(cdf), n.value, C.byref(n)))
         return tri, cdf
+
+    # -- the light hierarchy of render_nee (option "light_tree"; include/pt_api.h pins the tree, the walk and the probabilities)
+    def debug_light_tree(self):
+        """pt_debug_light_tree: (nodes, orig_tri).  nodes is a structured array, one record per node in depth-first order, with the fields
+        c (3 float32), r, phi (float32) and first, count, right (int32): the sphere around the node's lights, their summed weight, its range
+        [first, first + count) of tree-order lights and its right child (the left one is the next node; count 1: a leaf).  orig_tri: the
+        add-order triangle index of every light in tree order.  Host only; works on a host-only context."""
+        nn, nl = C.c_int64(), C.c_int64()
+        self._ck(LIB.pt_debug_light_tree(self._h, None, 0, C.byref(nn), None, 0, C.byref(nl)))
+        nodes = np.zeros(nn.value, dtype=LIGHT_TREE_NODE)
+        tri = np.zeros(nl.value, dtype=np.int32)
+        self._ck(LIB.pt_debug_light_tree(self._h, _ptr(nodes), nn.value, C.byref(nn), _ptr(tri), nl.value, C.byref(nl)))
+        return nodes, tri
+
+    def debug_light_tree_eval(self, points, normals, u0, tris, on_device=False):
+        """pt_debug_light_tree_eval: both walks of the light hierarchy per item -- points (n, 3) the origins o, normals (n, 3) the cull normals
+        G (zero: nothing is culled), u0 (n,) in [0, 1), tris (n,) add-order triangle indices.  Returns a structured array with the fields
+        tri (the add-order triangle the walk picks with u0), p (its probability P), p_weight (the weight walk's P of tris[i], 0 where that is
+        no light) and slot (the pick's tree-order index).  on_device: by the kernel k_debug_light_tree instead of the library's host code."""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = points.shape[0]
+        normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(n, 3)
+        u0 = np.ascontiguousarray(u0, dtype=np.float32).reshape(n)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(n)
+        out = np.zeros(n, dtype=LIGHT_TREE_EVAL)
+        self._ck(LIB.pt_debug_light_tree_eval(self._h, _ptr(points), _ptr(normals), _ptr(u0), _ptr(tris), n, _ptr(out), 1 if on_device else 0))
+        return out
 
     # -- environment lighting for render_nee (include/pt_api.h pins the map, its distribution and the estimator)
     def set_environment(self, rgb, **params):

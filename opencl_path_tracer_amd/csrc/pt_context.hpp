@@ -178,6 +178,20 @@ struct pt_context {
     float* d_nee_cdf = nullptr;
     float* d_nee_pdf_area = nullptr;
     bool nee_uploaded = false;         // the device copies hold the current table
+    std::vector<double> nee_phi, nee_area;     // per light, in table order: area x (E.r + E.g + E.b) and the area, as the table summed them
+    // the light hierarchy over that table (option light_tree, pt_lighttree.cpp; pinned in include/pt_api.h): built on the host at first use
+    // after the table (lt_valid; a new table invalidates it).  Eight floats per node; packed triangle and (float)(1 / area) per light in tree
+    // order; the tree-order index per packed triangle (-1 for non-lights)
+    int light_tree = 0;                // option light_tree
+    std::vector<float> lt_nodes;
+    std::vector<int32_t> lt_tri, lt_slot;
+    std::vector<float> lt_inv_area;
+    int32_t lt_depth = 0;
+    bool lt_valid = false, lt_uploaded = false;
+    float4* d_lt_nodes = nullptr;
+    int32_t* d_lt_tri = nullptr;
+    int32_t* d_lt_slot = nullptr;
+    float* d_lt_inv_area = nullptr;
     // the environment of pt_render_nee (pt_set_environment, pt_env.cpp): the map with p_env = P(texel) / Omega(row) in .w, the row
     // marginal cdf [h] and the per-row column cdfs [h][w]; env_dist: some weight is non-zero.  Device copies made by pt_set_environment.
     bool env_set = false, env_dist = false;
@@ -333,6 +347,11 @@ int interior_prepare(pt_context* ctx, InteriorView* iv);
 inline std::string interior_refusal(const std::string& who) {
     return who + ": a material holds an interior and only pt_render_nee renders it (pt_clear_material_interiors removes every binding)";
 }
+// the light hierarchy (pt_lighttree.cpp): built for the current light table (light_tree_ready, which makes the table first; host only), then
+// the view of its device copies, made when stale (light_tree_prepare); light_tree_host is the same view over the host arrays
+int light_tree_ready(pt_context* ctx);
+int light_tree_prepare(pt_context* ctx, LightTreeView* v);
+LightTreeView light_tree_host(const pt_context* ctx);
 inline std::string medium_refusal(const std::string& who) {
     return who + ": a medium with sigma_t > 0 is held and only pt_render_nee renders it (pt_clear_medium removes it)";
 }

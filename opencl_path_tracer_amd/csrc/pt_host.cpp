@@ -259,6 +259,10 @@ void pt_destroy(pt_context* ctx) {
         if (ctx->d_lights_cdf) (void)hipFree(ctx->d_lights_cdf);
         if (ctx->d_grid) (void)hipFree(ctx->d_grid);
         if (ctx->d_interior) (void)hipFree(ctx->d_interior);
+        if (ctx->d_lt_nodes) (void)hipFree(ctx->d_lt_nodes);
+        if (ctx->d_lt_tri) (void)hipFree(ctx->d_lt_tri);
+        if (ctx->d_lt_inv_area) (void)hipFree(ctx->d_lt_inv_area);
+        if (ctx->d_lt_slot) (void)hipFree(ctx->d_lt_slot);
         if (ctx->d_wf_state) (void)hipFree(ctx->d_wf_state);
         if (ctx->d_wf_queues) (void)hipFree(ctx->d_wf_queues);
         if (ctx->d_wf_counters) (void)hipFree(ctx->d_wf_counters);
@@ -841,6 +845,9 @@ static int nee_table(pt_context* ctx) {
         ctx->nee_pdf_area[(size_t)ctx->nee_tri[j]] = (float)((upto - below) / 16777216.0 / area[j]);
         below = upto;
     }
+    ctx->nee_phi.swap(wgt);          // (the light hierarchy's weights, pt_lighttree.cpp)
+    ctx->nee_area.swap(area);
+    ctx->lt_valid = false;
     ctx->nee_valid = true;
     ctx->nee_uploaded = false;
     return PT_OK;
@@ -927,7 +934,10 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
     if (medium_on(ctx)) nl->medium = medium_view(ctx);
     if (grid_on(ctx)) nl->grid = grid_view(ctx);
     if (interior_on(ctx) && (rc = interior_prepare(ctx, &nl->interior)) != PT_OK) return rc;
-    nl->family = interior_on(ctx)                  ? kNeeInterior
+    const bool ltree = ctx->light_tree && !ctx->nee_tri.empty();      // (after nee_prepare, as above)
+    if (ltree && (rc = light_tree_prepare(ctx, &nl->ltree)) != PT_OK) return rc;
+    nl->family = ltree                             ? kNeeLightTree
+                 : interior_on(ctx)                ? kNeeInterior
                  : grid_on(ctx)                    ? kNeeGrid
                  : medium_on(ctx)                  ? kNeeMedium
                  : lights_on(ctx)                  ? kNeeLights
@@ -939,7 +949,8 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
                  : nl->vn                          ? kNeeSmooth
                                                    : kNeePlain;
     nl->flags = (ctx->glossy ? 1 : 0) | (ctx->coated ? 2 : 0) | (lens_on(ctx) ? 4 : 0) | (frosted ? 8 : 0) | (lights_on(ctx) ? 16 : 0);
-    if (interior_on(ctx)) nl->flags |= (medium_on(ctx) ? 32 : 0) | (grid_on(ctx) ? 64 : 0);      // (kNeeInterior serves frames with and without either)
+    if (interior_on(ctx) || ltree) nl->flags |= (medium_on(ctx) ? 32 : 0) | (grid_on(ctx) ? 64 : 0);      // (kNeeInterior serves frames with and without either)
+    if (ltree && interior_on(ctx)) nl->flags |= 128;      // (and kNeeLightTree frames with and without an interior binding)
     return PT_OK;
 }
 hipError_t launch_nee_noted(pt_context* ctx, const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl) {
@@ -1637,6 +1648,9 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value) {
     } else if (k == "frosted") {
         if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "frosted must be 0 (material type 6 is inert) or 1 (pt_render_nee shades it as a rough dielectric)");
         ctx->frosted = (int)value;
+    } else if (k == "light_tree") {
+        if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "light_tree must be 0 (a light sample picks its triangle from the table's cdf) or 1 (pt_render_nee picks it by walking the light hierarchy)");
+        ctx->light_tree = (int)value;
     } else if (k == "timing") {
         ctx->timing = value ? 1 : 0;
     } else if (k == "count_work") {
@@ -1745,6 +1759,12 @@ int pt_get_stat(pt_context* ctx, const char* key, double* out) {
         RenderParams p;
         fill_params(ctx, &cam, &p);
         *out = (double)p.node_mode;
+        return PT_OK;
+    }
+    if (k == "light_tree_nodes" || k == "light_tree_depth") {      // (builds the tree of the uploaded scene if it is stale; host only)
+        const int rc = light_tree_ready(ctx);
+        if (rc != PT_OK) return rc;
+        *out = k == "light_tree_nodes" ? (double)(ctx->lt_nodes.size() / 8) : (double)ctx->lt_depth;
         return PT_OK;
     }
     if (k == "nee_family") { *out = (double)ctx->nee_family; return PT_OK; }

@@ -456,6 +456,80 @@ struct GridView {
 struct InteriorView {
     const float4* rec;
 };
+// the light hierarchy over the light table (option light_tree; pinned in include/pt_api.h; built by pt_lighttree.cpp).
+// A node is two float4, {c.xyz, r} and {phi, bits(first), bits(count), bits(right)}: the sphere around the box of its lights' vertices, the sum
+// of their weights, its range [first, first + count) of tree-order light indices and its right child (the left one is node + 1; count 1: a leaf)
+struct LightTreeView {
+    const float4* nodes;         // [2 * n_nodes]
+    const int32_t* tri;          // [n_lights] packed triangle of each light, in tree order
+    const float* inv_area;       // [n_lights] (float)(1 / area), in tree order
+    const int32_t* slot;         // [packed triangles] tree-order light index, -1 for non-lights
+    int32_t n_nodes, n_lights;   // 0, 0: no lights
+};
+constexpr int kLightTreeMaxDepth = 64;     // the loop bound of both walks; the builder keeps every leaf at or above it
+__host__ __device__ __forceinline__ int lt_bits(float f) { return __builtin_bit_cast(int, f); }
+// the importance of the child {q0 = (c, r), phi} from the origin o with the cull normal G (0: nothing is culled): 0 if its sphere lies
+// entirely below the horizon, else phi / max(|c - o|^2, r^2); dot3's fma placement
+__host__ __device__ __forceinline__ float lt_importance(const float4 q0, float phi, float ox, float oy, float oz, float gx, float gy, float gz) {
+    const float dx = q0.x - ox, dy = q0.y - oy, dz = q0.z - oz;
+    if (__builtin_fmaf(gz, dz, __builtin_fmaf(gy, dy, gx * dx)) < -q0.w) return 0.0f;
+    const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)), r2 = q0.w * q0.w;
+    return phi / (d2 > r2 ? d2 : r2);
+}
+// pL, the probability of the left of two children: iL / (iL + iR), with the two phi in place of importances whose sum is not a positive
+// finite number (both culled, or a light at the origin); 0.5 if that has no value either
+__host__ __device__ __forceinline__ float lt_branch(const float4 l0, float phiL, const float4 r0, float phiR, float ox, float oy, float oz, float gx, float gy,
+                                                    float gz) {
+    float iL = lt_importance(l0, phiL, ox, oy, oz, gx, gy, gz), iR = lt_importance(r0, phiR, ox, oy, oz, gx, gy, gz);
+    float s = iL + iR;
+    if (!(s > 0.0f && s < __builtin_inff())) {
+        iL = phiL;
+        iR = phiR;
+        s = iL + iR;
+    }
+    const float pL = iL / s;
+    return pL >= 0.0f && pL <= 1.0f ? pL : 0.5f;
+}
+// The walk.  PICK: the leaf that u draws (returned: its tree-order light index, *P its probability); else the probability of the leaf `target`
+// (*P; the same branch probabilities multiplied in the same order).  -1 and *P = 0 where there is no such leaf.  A loop of at most
+// kLightTreeMaxDepth trips; every node index is tested against the count before the loads that use it
+template <bool PICK>
+__host__ __device__ __forceinline__ int lt_walk(const LightTreeView& v, float ox, float oy, float oz, float gx, float gy, float gz, float u, int target, float* P) {
+    *P = 0.0f;
+    if (v.n_nodes <= 0 || (!PICK && (unsigned)target >= (unsigned)v.n_lights)) return -1;
+    float prob = 1.0f;
+    int node = 0;
+    float4 q1 = v.nodes[1];
+    for (int trip = 0; trip <= kLightTreeMaxDepth; ++trip) {
+        if (lt_bits(q1.z) <= 1) {          // a leaf
+            const int s = lt_bits(q1.y);
+            if ((unsigned)s >= (unsigned)v.n_lights || (!PICK && s != target)) return -1;
+            *P = prob;
+            return s;
+        }
+        const int L = node + 1, R = lt_bits(q1.w);
+        if ((unsigned)L >= (unsigned)v.n_nodes || (unsigned)R >= (unsigned)v.n_nodes) return -1;
+        const float4 l0 = v.nodes[2 * L], l1 = v.nodes[2 * L + 1], r0 = v.nodes[2 * R], r1 = v.nodes[2 * R + 1];
+        const float pL = lt_branch(l0, l1.x, r0, r1.x, ox, oy, oz, gx, gy, gz);
+        bool left;
+        if constexpr (PICK) left = u < pL;
+        else left = target < lt_bits(l1.y) + lt_bits(l1.z);
+        if (left) {
+            if constexpr (PICK) u = u / pL;
+            prob *= pL;
+            node = L;
+            q1 = l1;
+        } else {
+            const float pR = 1.0f - pL;
+            if constexpr (PICK) u = (u - pL) / pR;
+            prob *= pR;
+            node = R;
+            q1 = r1;
+        }
+        if constexpr (PICK) if (!(u < 1.0f)) u = 0.99999994f;      // (1 - 2^-24)
+    }
+    return -1;
+}
 // normalize3 of pt_device.hpp on the host: dot3's fma placement, then a * (1.0f / sqrtf(l2)), IEEE
 inline void lens_normalize(const float* a, float* out) {
     const float l2 = __builtin_fmaf(a[2], a[2], __builtin_fmaf(a[1], a[1], a[0] * a[0]));
@@ -479,7 +553,7 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
                               const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream);
 // one launch of the NEE kernels (pt_nee.hip), as nee_launch_for (pt_context.hpp) fills it from the context.  Each family is the one before it
 // with one more feature compiled in; a launch takes the first family that covers what the frame needs
-enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium, kNeeGrid, kNeeInterior };
+enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium, kNeeGrid, kNeeInterior, kNeeLightTree };
 struct NeeLaunch {
     const EnvView* env;          // null: the instances without an environment
     bool tiled;                  // the rounds of pt_render_adaptive_ex: k_nee*_tiles over the p.n_tiles 8x8 frame tiles of p.tile_list (null: the
@@ -492,18 +566,21 @@ struct NeeLaunch {
                                  // a light set with a pickable light (pt_set_lights) takes kNeeLights whatever else is on; a medium with
                                  // sigma_t > 0 (pt_set_medium) takes kNeeMedium whatever else is on, lights or not; a live density grid
                                  // (pt_set_medium_density with such a medium) takes kNeeGrid whatever else is on; a live interior binding
-                                 // (pt_set_material_interior) takes kNeeInterior whatever else is on, medium and grid or not
+                                 // (pt_set_material_interior) takes kNeeInterior whatever else is on, medium and grid or not; option light_tree
+                                 // with a non-empty light table takes kNeeLightTree whatever else is on, an interior binding or not
     int flags;                   // the options themselves, for the families in which they are run-time fields: bit 0 glossy (type 4 is live;
                                  // read from kNeeCoated on), bit 1 coated (type 5 is live; from kNeeLens on), bit 2 a lens with aperture > 0 is
                                  // set (from kNeeFrosted on; else each sample starts on the pinhole ray), bit 3 frosted with a type-6 material
                                  // uploaded (type 6 is live; read from kNeeLights on), bit 4 a light set with a pickable light is held (read
                                  // from kNeeMedium on; else `lights` is an empty set with P_ana = 0), bit 5 a medium with sigma_t > 0 is held
-                                 // and bit 6 its density grid is live (read by kNeeInterior, which serves frames without either)
+                                 // and bit 6 its density grid is live (read from kNeeInterior on, which serves frames without either), bit 7 an
+                                 // interior binding is live (read by kNeeLightTree; else `interior` is never read)
     LensView lens;               // read from kNeeLens on
     LightsView lights;           // read from kNeeLights on
     MediumView medium;           // read from kNeeMedium on
     GridView grid;               // read from kNeeGrid on
-    InteriorView interior;       // read by kNeeInterior
+    InteriorView interior;       // read from kNeeInterior on
+    LightTreeView ltree;         // read by kNeeLightTree
     int* block;                  // out, may be null: the workgroup size the launch took, as launch_lanes / launch_lanes_env_tiles_smooth chose
                                  // it (0: nothing was launched, an empty tile list)
 };
@@ -524,6 +601,9 @@ hipError_t launch_debug_medium(const MediumView& mv, const float* in, int64_t n,
 hipError_t launch_debug_grid(const MediumView& mv, const GridView& gv, const float* in, int64_t n, float* out, hipStream_t stream);
 // interiors (pt_medium.hip): pt_debug_interior's kernel, 12 floats in and 10 out per item
 hipError_t launch_debug_interior(const float* in, int64_t n, float* out, hipStream_t stream);
+// light hierarchy (pt_nee_lighttree.hip): pt_debug_light_tree_eval's kernel, per item {o, G, u0} (7 floats) and a tree-order target in,
+// {picked tree-order light, bits(P), bits(the weight walk's P of the target), 0} out
+hipError_t launch_debug_light_tree(const LightTreeView& v, const float* in, const int32_t* target, int64_t n, int32_t* out, hipStream_t stream);
 // coated diffuse (pt_glossy.hip): pt_debug_coated's kernel, 12 floats in and 10 out per item
 hipError_t launch_debug_coated(const float* in, int64_t n, float* out, hipStream_t stream);
 // rough dielectric (pt_glossy.hip): pt_debug_frosted's kernel, 12 floats in and 10 out per item

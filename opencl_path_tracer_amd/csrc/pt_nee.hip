@@ -27,8 +27,11 @@
 //   INTERIOR  a type-2 or type-6 material may hold an interior (pt_set_material_interior, section 5.21): a segment inside such a dielectric takes
 //           Beer-Lambert absorption and may end at a scatter vertex of the interior; whether a medium is held and whether its grid is live are
 //           run-time fields (flags bits 5 and 6)
-// Each flag from SMOOTH on requires the one before it.  The kernels are the eleven families the host can ask for (NeeFamily, pt_internal.hpp)
-// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights, _medium, _grid, _interior: each is the one before it with one more flag -- times ENV and TILED
+//   LTREE   the triangle-light branch of a light sample picks its triangle by walking the light hierarchy (option light_tree, section 5.22), and
+//           an emitter hit's weight walks it towards the hit triangle from the previous lobe vertex, whose origin and cull normal the hook
+//           keeps; whether an interior binding is live is a run-time field (flags bit 7)
+// Each flag from SMOOTH on requires the one before it.  The kernels are the twelve families the host can ask for (NeeFamily, pt_internal.hpp)
+// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights, _medium, _grid, _interior, _lighttree: each is the one before it with one more flag -- times ENV and TILED
 // (k_nee_env*, k_nee_tiles*, k_nee_env_tiles*).  In a family whose option is off the data is null (vn, tv.uv) or the field clear.
 #include "pt_device.hpp"
 
@@ -146,10 +149,22 @@ struct InteriorSlot<true> {
     bool grid = true;              // ... and its density grid is live (else the homogeneous medium's flight and transmittance)
 };
 
+// what a hook carries for the light hierarchy (option light_tree): nothing without it
+template <bool LTREE>
+struct LightTreeSlot {};
+template <>
+struct LightTreeSlot<true> {
+    LightTreeView v;               // nodes, tree-order lights, their inv_area, the packed triangles' tree-order indices
+    f3 o = mk(0.f, 0.f, 0.f);      // the previous lobe vertex's shadow-ray origin and cull normal (zero at a scatter vertex of the medium): what
+    f3 G = mk(0.f, 0.f, 0.f);      // the weight walk of an emitter hit on the next segment starts from
+    bool interior = true;          // an interior binding is live in this launch (else no table is read, as in the instances without one)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
 template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false, bool FROST = false,
-          bool LIGHTS = false, bool MEDIUM = false, bool GRID = false, bool INTERIOR = false>
+          bool LIGHTS = false, bool MEDIUM = false, bool GRID = false, bool INTERIOR = false, bool LTREE = false>
 struct NeeHook {
+    static_assert(INTERIOR || !LTREE, "the light-tree instances are built on the interior code");
     static_assert(GRID || !INTERIOR, "the interior instances are built on the grid code");
     static_assert(MEDIUM || !GRID, "the grid instances are built on the medium code");
     static_assert(LIGHTS || !MEDIUM, "the medium instances are built on the lights code");
@@ -189,7 +204,13 @@ struct NeeHook {
     MediumSlot<MEDIUM> md;
     GridSlot<GRID> gr;
     InteriorSlot<INTERIOR> in;
+    LightTreeSlot<LTREE> lts;
 
+    // LTREE: an interior binding is live (a run-time answer in the light-tree instances only: the interior ones run only when one is)
+    PT_DEV bool interior_live() const {
+        if constexpr (LTREE) return lts.interior;
+        else return INTERIOR;
+    }
     // MEDIUM: the lane enters shade_hit at a scatter vertex
     PT_DEV bool scatters() const {
         if constexpr (MEDIUM) return md.sc;
@@ -471,7 +492,15 @@ struct NeeHook {
     // the weight of an emitter hit's emission (at distance t, cosine inten, along rD)
     PT_DEV float emitter_weight(int ti, float t, float inten, f3 rD) const {
         if (!nee || !after_lobe) return 1.0f;
-        float pa = lt.pdf_area[ti];
+        float pa;
+        if constexpr (LTREE) {             // the weight walk from the previous lobe vertex: the P the pick there had for this triangle
+            pa = 0.0f;
+            const int s = lts.v.slot[ti];
+            if (s >= 0 && inten > 0.0f) {
+                float P;
+                if (lt_walk<false>(lts.v, lts.o.x, lts.o.y, lts.o.z, lts.G.x, lts.G.y, lts.G.z, 0.0f, s, &P) >= 0) pa = P * lts.v.inv_area[s];
+            }
+        } else pa = lt.pdf_area[ti];
         if constexpr (ENV) pa *= 1.0f - env.v.p_env;                 // the light table is chosen with probability 1 - P_env
         if constexpr (LIGHTS) pa *= 1.0f - lg.v.p_ana;               // ... and the sky or the table with probability 1 - P_ana
         if (!(pa > 0.0f && inten > 0.0f)) return 1.0f;
@@ -493,6 +522,20 @@ struct NeeHook {
             else lo = mid + 1;
         }
         const int li = lt.tri[lo];
+        const float4 a = p.tris[li * 3], b = p.tris[li * 3 + 1], cc = p.tris[li * 3 + 2];
+        const f3 v1 = mk(a.x, a.y, a.z), v2 = mk(a.w, b.x, b.y), v3 = mk(b.z, b.w, cc.x);
+        *Ny = mk(cc.y, cc.z, cc.w);
+        const float su = __builtin_sqrtf(u1);
+        *y = madd(v3 - v1, su * (1.0f - u2), madd(v2 - v1, u2 * su, v1));
+        return li;
+    }
+    // LTREE: the same with the triangle that the walk of the light hierarchy from o (cull normal lts.G) draws with u0; *pa = P x inv_area
+    PT_DEV int tree_light_point(const RenderParams& p, f3 o, float u0, float u1, float u2, f3* y, f3* Ny, float* pa) const {
+        float P;
+        const int s = lt_walk<true>(lts.v, o.x, o.y, o.z, lts.G.x, lts.G.y, lts.G.z, u0, -1, &P);
+        if (s < 0) return -1;
+        *pa = P * lts.v.inv_area[s];
+        const int li = lts.v.tri[s];
         const float4 a = p.tris[li * 3], b = p.tris[li * 3 + 1], cc = p.tris[li * 3 + 2];
         const f3 v1 = mk(a.x, a.y, a.z), v2 = mk(a.w, b.x, b.y), v3 = mk(b.z, b.w, cc.x);
         *Ny = mk(cc.y, cc.z, cc.w);
@@ -630,6 +673,10 @@ struct NeeHook {
         const bool mvx = MEDIUM && type < 0;       // MEDIUM: a scatter vertex of the medium: the origin is hp itself, and no cosine is tested
         f3 o = hp;
         if (!mvx) o = madd(geo(N), 0.001f, hp);
+        if constexpr (LTREE) {             // (kept for the emitter hit of the next segment, whichever branch this sample takes)
+            lts.o = o;
+            lts.G = mvx ? mk(0.f, 0.f, 0.f) : geo(N);
+        }
         f3 w, e;
         float limit, pl, g;            // the search's cut, p_l, the emitter's cosine (1 for the sky and for an analytic light)
         int want;                      // what the shadow ray must return
@@ -680,11 +727,17 @@ struct NeeHook {
         } else {
             if (lt.n <= 0) return;            // (P_env or P_ana is 1 then: not reached)
             f3 y, Ny;
-            float r2, r;
-            want = light_point(p, nee_unit(nee_rand(key, k, 0)), u1, u2, &y, &Ny);
+            float r2, r, pa;
+            if constexpr (LTREE) {
+                want = tree_light_point(p, o, nee_unit(nee_rand(key, k, 0)), u1, u2, &y, &Ny, &pa);
+                if (want < 0) return;         // (a tree that does not cover its table: not reached)
+            } else {
+                want = light_point(p, nee_unit(nee_rand(key, k, 0)), u1, u2, &y, &Ny);
+                pa = lt.pdf_area[want];
+            }
             w = light_direction(o, y, Ny, &r2, &r, &g);
-            if constexpr (ENV) pl = (lt.pdf_area[want] * (1.0f - env.v.p_env)) * r2 / g;     // g = 0: inf or NaN, rejected below
-            else pl = lt.pdf_area[want] * r2 / g;
+            if constexpr (ENV) pl = (pa * (1.0f - env.v.p_env)) * r2 / g;     // g = 0: inf or NaN, rejected below
+            else pl = pa * r2 / g;
             if constexpr (LIGHTS) pl *= 1.0f - lg.v.p_ana;
             e = ldf3(p.mats[p.meta[want].mati].emission);
             limit = r * 1.0001f;
@@ -765,16 +818,18 @@ struct NeeHook {
 // GRID (pt_set_medium_density; k_nee*_grid below; on the MEDIUM code only): the hook's free flight and transmittance walk the density grid
 // INTERIOR (pt_set_material_interior; k_nee*_interior below; on the GRID code only): a segment inside a dielectric whose material holds an interior
 // takes its absorption and may end at its scatter vertex; metal bit 5: a medium with sigma_t > 0 is held, bit 6: its grid is live
+// LTREE (option light_tree; k_nee*_lighttree below; on the INTERIOR code only): a light sample's triangle and an emitter hit's weight come from
+// the walk of the light hierarchy; metal bit 7: an interior binding is live
 template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false,
-          bool FROST = false, bool LIGHTS = false, bool MEDIUM = false, bool GRID = false, bool INTERIOR = false>
+          bool FROST = false, bool LIGHTS = false, bool MEDIUM = false, bool GRID = false, bool INTERIOR = false, bool LTREE = false>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr,
                       int metal = 0, const LensView* lens = nullptr, const LightsView* lights = nullptr, const MediumView* medium = nullptr,
-                      const GridView* grid = nullptr, const InteriorView* interior = nullptr) {
+                      const GridView* grid = nullptr, const InteriorView* interior = nullptr, const LightTreeView* ltree = nullptr) {
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS, MEDIUM, GRID, INTERIOR> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS, MEDIUM, GRID, INTERIOR, LTREE> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
     if constexpr (SMOOTH) hook.sm.vn = vn;
     if constexpr (TEX) hook.tx.v = *tv;
     if constexpr (LENS) {
@@ -799,6 +854,10 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
         hook.in.v = *interior;
         hook.in.medium = (metal & 32) != 0;
         hook.in.grid = (metal & 64) != 0;
+    }
+    if constexpr (LTREE) {
+        hook.lts.v = *ltree;
+        hook.lts.interior = (metal & 128) != 0;
     }
     const int camX = (int)p.cam.XM;
     unsigned rendered = 0;                     // TILED: pixels this lane rendered (statistic "samples", as k_render counts them)
@@ -859,7 +918,7 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
                     bool isc = false, dead = false;
                     if (!inside) {
                         if (hook.medium_live()) ts = hook.free_flight(rP, rD, ti < 0 ? __builtin_inff() : t);
-                    } else if (ti >= 0) {
+                    } else if (ti >= 0 && hook.interior_live()) {
                         const float4* __restrict__ rec = hook.in.v.rec + 2 * (size_t)p.meta[ti].mati;
                         const float4 q1 = rec[1];
                         if (q1.y != 0.0f) {
@@ -1138,6 +1197,31 @@ __global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_interior(RenderParams p
     nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv);
 }
 
+// the light-tree instances (option light_tree with a non-empty light table): the interior kernels with the hierarchy's view as one more argument;
+// flags bit 7: an interior binding is live (else iv is never read)
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_lighttree(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
+                                                         GridView gv, InteriorView iv, LightTreeView tr, long long npix) {
+    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv,
+                                                                                                         &tr);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_lighttree(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
+                                                             MediumView mv, GridView gv, InteriorView iv, LightTreeView tr, long long npix) {
+    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv,
+                                                                                                        &tr);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_tiles_lighttree(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
+                                                               GridView gv, InteriorView iv, LightTreeView tr) {
+    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv, &tr);
+}
+template <int MODE, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_lighttree(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv,
+                                                                   LightsView lg, MediumView mv, GridView gv, InteriorView iv, LightTreeView tr) {
+    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv, &tr);
+}
+
 // launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
 // of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
 // the staged treelet are sized for the workgroup at launch, as for every shape)
@@ -1184,6 +1268,8 @@ hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const Ne
 // The interior family likewise (pt_nee_interior.hip, PT_NEE_INTERIOR_TU, launch_nee_interior)
 hipError_t launch_nee_grid(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
 hipError_t launch_nee_interior(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
+// The light-tree family likewise (pt_nee_lighttree.hip, PT_NEE_LIGHTTREE_TU, launch_nee_lighttree), with pt_debug_light_tree_eval's kernel
+hipError_t launch_nee_lighttree(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
 #if defined(PT_NEE_MEDIUM_TU)
 hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     return launch_nee_family<kWideAll>(NEE_PICK(k_nee_medium), NEE_PICK(k_nee_env_medium), NEE_PICK(k_nee_tiles_medium), NEE_PICK(k_nee_env_tiles_medium), p, lt, nl, npix,
@@ -1198,6 +1284,32 @@ hipError_t launch_nee_grid(const RenderParams& p, const NeeTable& lt, const NeeL
 hipError_t launch_nee_interior(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     return launch_nee_family<kWideAll>(NEE_PICK(k_nee_interior), NEE_PICK(k_nee_env_interior), NEE_PICK(k_nee_tiles_interior), NEE_PICK(k_nee_env_tiles_interior), p, lt, nl,
                                        npix, cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium, nl.grid, nl.interior);
+}
+#elif defined(PT_NEE_LIGHTTREE_TU)
+hipError_t launch_nee_lighttree(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+    return launch_nee_family<kWideAll>(NEE_PICK(k_nee_lighttree), NEE_PICK(k_nee_env_lighttree), NEE_PICK(k_nee_tiles_lighttree), NEE_PICK(k_nee_env_tiles_lighttree), p, lt, nl,
+                                       npix, cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium, nl.grid, nl.interior, nl.ltree);
+}
+// in: 7 floats per item {o, G, u0} and the tree-order light whose probability the weight walk returns (-1: none); out: 4 words per item {the
+// tree-order light the pick draws, bits(its P), bits(the weight walk's P of the target), 0}: the two walks as the instances above call them
+__global__ void __launch_bounds__(256) k_debug_light_tree(LightTreeView v, const float* __restrict__ in, const int32_t* __restrict__ target, long long n,
+                                                          int32_t* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* q = in + i * 7;
+    float P, Pw;
+    const int s = lt_walk<true>(v, q[0], q[1], q[2], q[3], q[4], q[5], q[6], -1, &P);
+    lt_walk<false>(v, q[0], q[1], q[2], q[3], q[4], q[5], 0.0f, target[i], &Pw);
+    int32_t* o = out + i * 4;
+    o[0] = s;
+    o[1] = __float_as_int(P);
+    o[2] = __float_as_int(Pw);
+    o[3] = 0;
+}
+hipError_t launch_debug_light_tree(const LightTreeView& v, const float* in, const int32_t* target, int64_t n, int32_t* out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_debug_light_tree, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, v, in, target, (long long)n, out);
+    return hipGetLastError();
 }
 #else
 static hipError_t launch_nee_of_family(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
@@ -1230,13 +1342,14 @@ static hipError_t launch_nee_of_family(const RenderParams& p, const NeeTable& lt
     case kNeeMedium: return launch_nee_medium(p, lt, nl, npix, cu_count, stream);
     case kNeeGrid: return launch_nee_grid(p, lt, nl, npix, cu_count, stream);
     case kNeeInterior: return launch_nee_interior(p, lt, nl, npix, cu_count, stream);
+    case kNeeLightTree: return launch_nee_lighttree(p, lt, nl, npix, cu_count, stream);
     }
     return hipErrorInvalidValue;
 }
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
     t_lanes_block = 0;
     const hipError_t e = launch_nee_of_family(p, lt, nl, npix, cu_count, stream);
-    if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit, in pt_nee_medium.hip's, pt_nee_grid.hip's or pt_nee_interior.hip's)
+    if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit, in pt_nee_medium.hip's, pt_nee_grid.hip's, pt_nee_interior.hip's or pt_nee_lighttree.hip's)
     return e;
 }
 #endif

@@ -288,6 +288,43 @@ def light_shaft(sigma_t=0.12):
     return spec
 
 
+def many_lights(n=16, spacing=3.0, lamp=0.4):
+    """The many-emitter scene for option light_tree: a closed diffuse corridor (x in [-2, 2], y in [-1.5, 1.5], z in [-1, spacing n + 2]) seen
+    from the origin along +z, with n square lamps of side `lamp` (two triangles each) just under its ceiling, `spacing` apart along z and
+    alternating between x = -0.8 and x = 0.8.  Even lamps emit (20, 18, 15), odd ones a quarter of that.  Lamp n // 2 lies a unit below the
+    floor instead, where nothing sees it: a light the table holds and every floor point's horizon culls.  The lamps come first, lamp i being
+    triangles 2 i and 2 i + 1, in one object with the walls.  n >= 2."""
+    if n < 2:
+        raise ValueError("many_lights: n must be >= 2")
+    mats = [
+        ((0.5, 0.5, 0.5), (0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0), 1.0, 0),             # 0 walls
+        ((0, 0, 0), (0, 0, 0), (20.0, 18.0, 15.0), (0, 0, 0), (0, 0, 0), 0.0, 3),          # 1 bright lamps
+        ((0, 0, 0), (0, 0, 0), (5.0, 4.5, 3.75), (0, 0, 0), (0, 0, 0), 0.0, 3),            # 2 dim lamps
+    ]
+
+    def quad(a, b, c, d):
+        return [(a, b, c), (a, c, d)]
+    x0, x1, y0, y1, z0, z1 = -2.0, 2.0, -1.5, 1.5, -1.0, float(spacing) * n + 2.0
+    tris, mo = [], []
+    h = 0.5 * float(lamp)
+    for i in range(n):
+        cx, cz = (-0.8 if i % 2 == 0 else 0.8), 1.5 + float(spacing) * i
+        cy = y0 - 1.0 if i == n // 2 else y1 - 0.05
+        tris += quad((cx - h, cy, cz - h), (cx + h, cy, cz - h), (cx + h, cy, cz + h), (cx - h, cy, cz + h))
+        mo += [1 + i % 2] * 2
+    for q in (quad((x0, y0, z0), (x1, y0, z0), (x1, y0, z1), (x0, y0, z1)),      # floor
+              quad((x0, y1, z0), (x0, y1, z1), (x1, y1, z1), (x1, y1, z0)),      # ceiling
+              quad((x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)),      # far end
+              quad((x0, y0, z0), (x0, y0, z1), (x0, y1, z1), (x0, y1, z0)),      # left
+              quad((x1, y0, z0), (x1, y1, z0), (x1, y1, z1), (x1, y0, z1)),      # right
+              quad((x0, y0, z0), (x0, y1, z0), (x1, y1, z0), (x1, y0, z0))):     # behind the camera
+        tris += q
+        mo += [0] * len(q)
+    spec = SceneSpec(materials=mats, name="many_lights_%d" % n, shift=(-500.0, -500.0, 1299.0378))
+    spec.objects.append((np.asarray(tris, dtype=np.float32), np.asarray(mo, dtype=np.uint16)))
+    return spec
+
+
 FOCUS_ROW_SPHERES = [((-2.4, -1.1, 5.0), 0), ((-0.8, -1.1, 8.0), 4), ((0.8, -1.1, 12.0), 5), ((2.4, -1.1, 17.0), 6)]
 
 
