@@ -1,6 +1,6 @@
 // pt_env.cpp -- the environment of pt_render_nee (include/pt_api.h pins the map, the distribution and the estimator): validation, the
 // sampling tables (host, double precision, stored as float), the device copies, and the host statements of the lookup and the tables.
-// The kernel side is pt_nee.hip (k_nee_env).
+// The kernel side is pt_nee.hip (the ENV instances of k_nee).
 #include "pt_context.hpp"
 
 namespace ptamd {

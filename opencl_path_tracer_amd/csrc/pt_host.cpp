@@ -919,7 +919,8 @@ int nee_prepare(pt_context* ctx, int32_t strategy, NeeTable* ltp, EnvView* envp,
     return PT_OK;
 }
 int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch* nl) {
-    *nl = NeeLaunch{nullptr, false, nullptr, TexView{nullptr, nullptr, nullptr, nullptr}, kNeePlain, 0, lens_view(*cam, lens_on(ctx) ? ctx->lens_aperture : 0.0f, ctx->lens_focus)};
+    *nl = NeeLaunch{};                 // (kNeePlain, every view null or zero)
+    nl->lens = lens_view(*cam, lens_on(ctx) ? ctx->lens_aperture : 0.0f, ctx->lens_focus);
     if (!nee_on) return PT_OK;
     int rc;
     if ((rc = smooth_prepare(ctx, &nl->vn)) != PT_OK) return rc;
@@ -948,9 +949,11 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
                  : nl->tv.uv                       ? kNeeTex
                  : nl->vn                          ? kNeeSmooth
                                                    : kNeePlain;
-    nl->flags = (ctx->glossy ? 1 : 0) | (ctx->coated ? 2 : 0) | (lens_on(ctx) ? 4 : 0) | (frosted ? 8 : 0) | (lights_on(ctx) ? 16 : 0);
-    if (interior_on(ctx) || ltree) nl->flags |= (medium_on(ctx) ? 32 : 0) | (grid_on(ctx) ? 64 : 0);      // (kNeeInterior serves frames with and without either)
-    if (ltree && interior_on(ctx)) nl->flags |= 128;      // (and kNeeLightTree frames with and without an interior binding)
+    // (every bit says what is live; a family reads the ones that are run-time answers in it: kNeeInterior serves frames with and without a medium
+    // or a grid, kNeeLightTree frames with and without an interior binding)
+    nl->flags = (ctx->glossy ? kNeeFlagGlossy : 0) | (ctx->coated ? kNeeFlagCoated : 0) | (lens_on(ctx) ? kNeeFlagLens : 0) | (frosted ? kNeeFlagFrosted : 0) |
+                (lights_on(ctx) ? kNeeFlagLights : 0) | (medium_on(ctx) ? kNeeFlagMedium : 0) | (grid_on(ctx) ? kNeeFlagGrid : 0) |
+                (interior_on(ctx) ? kNeeFlagInterior : 0);
     return PT_OK;
 }
 hipError_t launch_nee_noted(pt_context* ctx, const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl) {

@@ -554,13 +554,29 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
 // one launch of the NEE kernels (pt_nee.hip), as nee_launch_for (pt_context.hpp) fills it from the context.  Each family is the one before it
 // with one more feature compiled in; a launch takes the first family that covers what the frame needs
 enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium, kNeeGrid, kNeeInterior, kNeeLightTree };
+// the families compiled in translation units of their own, as the preprocessor needs them (pt_nee.hip's PT_NEE_TU)
+#define PT_NEE_FAMILY_MEDIUM 8
+#define PT_NEE_FAMILY_GRID 9
+#define PT_NEE_FAMILY_INTERIOR 10
+#define PT_NEE_FAMILY_LIGHTTREE 11
+static_assert(PT_NEE_FAMILY_MEDIUM == kNeeMedium && PT_NEE_FAMILY_GRID == kNeeGrid && PT_NEE_FAMILY_INTERIOR == kNeeInterior && PT_NEE_FAMILY_LIGHTTREE == kNeeLightTree,
+              "the PT_NEE_FAMILY_* macros are the NeeFamily values");
+// NeeLaunch::flags: what is live in the launch, for the families in which that is a run-time answer (a family below reads none of it: there the
+// feature is either compiled out or what the family was chosen for)
+enum NeeFlag : int {
+    kNeeFlagGlossy = 1,          // option glossy: type 4 is live (read from kNeeCoated on)
+    kNeeFlagCoated = 2,          // option coated: type 5 is live (from kNeeLens on)
+    kNeeFlagLens = 4,            // a lens with aperture > 0 is set (from kNeeFrosted on; else each sample starts on the pinhole ray)
+    kNeeFlagFrosted = 8,         // option frosted with a type-6 material uploaded: type 6 is live (from kNeeLights on)
+    kNeeFlagLights = 16,         // a light set with a pickable light is held (from kNeeMedium on; else `lights` is an empty set with P_ana = 0)
+    kNeeFlagMedium = 32,         // a medium with sigma_t > 0 is held (from kNeeInterior on, which serves frames without one)
+    kNeeFlagGrid = 64,           // ... and its density grid is live (from kNeeInterior on)
+    kNeeFlagInterior = 128,      // an interior binding is live (kNeeLightTree; else `interior` is never read)
+};
 struct NeeLaunch {
     const EnvView* env;          // null: the instances without an environment
-    bool tiled;                  // the rounds of pt_render_adaptive_ex: k_nee*_tiles over the p.n_tiles 8x8 frame tiles of p.tile_list (null: the
-                                 // frame's tiles in order), one lane per pixel of a tile; npix is then not read
-    const float4* vn;            // the packed vertex normals; null: option smooth_normals is off, which the families from kNeeTex on read as "no
-                                 // triangle has vertex normals" (the pinned rule "no vertex normals: Ns = Ng, the same bits" makes that exact)
-    TexView tv;                  // uv == null: option textures is off (no lookup in the families from kNeeGlossy on); not read below kNeeTex
+    bool tiled;                  // the rounds of pt_render_adaptive_ex: the tiled instances over the p.n_tiles 8x8 frame tiles of p.tile_list (null:
+                                 // the frame's tiles in order), one lane per pixel of a tile; npix is then not read
     int family;                  // NeeFamily.  An option whose material type is not uploaded asks for nothing; a lens with aperture > 0 takes
                                  // kNeeLens whatever the options say; option frosted with a type-6 material takes kNeeFrosted, lens or not;
                                  // a light set with a pickable light (pt_set_lights) takes kNeeLights whatever else is on; a medium with
@@ -568,21 +584,19 @@ struct NeeLaunch {
                                  // (pt_set_medium_density with such a medium) takes kNeeGrid whatever else is on; a live interior binding
                                  // (pt_set_material_interior) takes kNeeInterior whatever else is on, medium and grid or not; option light_tree
                                  // with a non-empty light table takes kNeeLightTree whatever else is on, an interior binding or not
-    int flags;                   // the options themselves, for the families in which they are run-time fields: bit 0 glossy (type 4 is live;
-                                 // read from kNeeCoated on), bit 1 coated (type 5 is live; from kNeeLens on), bit 2 a lens with aperture > 0 is
-                                 // set (from kNeeFrosted on; else each sample starts on the pinhole ray), bit 3 frosted with a type-6 material
-                                 // uploaded (type 6 is live; read from kNeeLights on), bit 4 a light set with a pickable light is held (read
-                                 // from kNeeMedium on; else `lights` is an empty set with P_ana = 0), bit 5 a medium with sigma_t > 0 is held
-                                 // and bit 6 its density grid is live (read from kNeeInterior on, which serves frames without either), bit 7 an
-                                 // interior binding is live (read by kNeeLightTree; else `interior` is never read)
+    const float4* vn;            // the packed vertex normals (from kNeeSmooth on); null: option smooth_normals is off, which the families from
+                                 // kNeeTex on read as "no triangle has vertex normals" (the pinned rule "no vertex normals: Ns = Ng, the same bits"
+                                 // makes that exact)
+    TexView tv;                  // from kNeeTex on; uv == null: option textures is off (no lookup in the families from kNeeGlossy on)
+    int flags;                   // NeeFlag bits
     LensView lens;               // read from kNeeLens on
     LightsView lights;           // read from kNeeLights on
     MediumView medium;           // read from kNeeMedium on
     GridView grid;               // read from kNeeGrid on
     InteriorView interior;       // read from kNeeInterior on
     LightTreeView ltree;         // read by kNeeLightTree
-    int* block;                  // out, may be null: the workgroup size the launch took, as launch_lanes / launch_lanes_env_tiles_smooth chose
-                                 // it (0: nothing was launched, an empty tile list)
+    int* block;                  // out, may be null: the workgroup size the launch took, as launch_lanes / launch_lanes_wide chose it (0: nothing
+                                 // was launched, an empty tile list)
 };
 hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
 // thin lens (pt_lens.hip): pt_debug_lens's kernel, {gid, S} in and 6 floats out per item; pt_focus_at's, the axial distance of pixel gid's

@@ -365,20 +365,33 @@ static void launch_cfg(pt_context* ctx, const RenderParams& p, LaunchConfig* lc)
     ctx->last_waves_per_simd = lc->waves_per_simd;
 }
 
+// What only pt_render_nee (and the NEE path of pt_render_adaptive_ex) renders, refused on behalf of `who`; PT_OK when none of it is on.
+// What an entry point asks before it needs the device ...
+static int refuse_nee_only_early(pt_context* ctx, const std::string& who) {
+    if (medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal(who));
+    if (interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal(who));
+    if (lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal(who));
+    if (ctx->frosted) return fail(ctx, PT_EINVAL, who + ": option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
+    if (lens_on(ctx)) return fail(ctx, PT_EINVAL, who + ": a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
+    if (ctx->coated) return fail(ctx, PT_EINVAL, who + ": option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
+    if (ctx->glossy) return fail(ctx, PT_EINVAL, who + ": option glossy is on and only pt_render_nee shades the rough metal of material type 4 (pt_set_option(ctx, \"glossy\", 0) turns it off)");
+    return PT_OK;
+}
+// ... and what it asks once check_ready has passed
+static int refuse_nee_only_ready(pt_context* ctx, const std::string& who) {
+    if (ctx->env_set) return fail(ctx, PT_EINVAL, who + ": an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
+    if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, who + ": option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
+    if (ctx->textures) return fail(ctx, PT_EINVAL, who + ": option textures is on and only pt_render_nee reads albedo textures (pt_set_option(ctx, \"textures\", 0) turns it off)");
+    return PT_OK;
+}
+
 int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
-    if (ctx && medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal("pt_generate_rays"));
-    if (ctx && interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal("pt_generate_rays"));
-    if (ctx && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_generate_rays"));
-    if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_generate_rays: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
-    if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_generate_rays: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
-    if (ctx && ctx->coated) return fail(ctx, PT_EINVAL, "pt_generate_rays: option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
-    if (ctx && ctx->glossy) return fail(ctx, PT_EINVAL, "pt_generate_rays: option glossy is on and only pt_render_nee shades the rough metal of material type 4 (pt_set_option(ctx, \"glossy\", 0) turns it off)");
+    int rc;
+    if (ctx && (rc = refuse_nee_only_early(ctx, "pt_generate_rays")) != PT_OK) return rc;
     PT_NEED_DEVICE(ctx);
-    int rc = check_ready(ctx, cam);
+    rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
-    if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_generate_rays: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
-    if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, "pt_generate_rays: option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
-    if (ctx->textures) return fail(ctx, PT_EINVAL, "pt_generate_rays: option textures is on and only pt_render_nee reads albedo textures (pt_set_option(ctx, \"textures\", 0) turns it off)");
+    if ((rc = refuse_nee_only_ready(ctx, "pt_generate_rays")) != PT_OK) return rc;
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     fill_params(ctx, cam, &p);
@@ -387,20 +400,13 @@ int pt_generate_rays(pt_context* ctx, const pt_camera* cam) {
 }
 
 int pt_trace_rays(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t current_sample) {
-    if (ctx && medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal("pt_trace_rays"));
-    if (ctx && interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal("pt_trace_rays"));
-    if (ctx && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_trace_rays"));
-    if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_trace_rays: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
-    if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_trace_rays: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
-    if (ctx && ctx->coated) return fail(ctx, PT_EINVAL, "pt_trace_rays: option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
-    if (ctx && ctx->glossy) return fail(ctx, PT_EINVAL, "pt_trace_rays: option glossy is on and only pt_render_nee shades the rough metal of material type 4 (pt_set_option(ctx, \"glossy\", 0) turns it off)");
+    int rc;
+    if (ctx && (rc = refuse_nee_only_early(ctx, "pt_trace_rays")) != PT_OK) return rc;
     PT_NEED_DEVICE(ctx);
-    int rc = check_ready(ctx, cam);
+    rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
     if (iterations < 0 || current_sample < 0) return fail(ctx, PT_EINVAL, "iterations/current_sample must be >= 0");
-    if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_trace_rays: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
-    if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, "pt_trace_rays: option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
-    if (ctx->textures) return fail(ctx, PT_EINVAL, "pt_trace_rays: option textures is on and only pt_render_nee reads albedo textures (pt_set_option(ctx, \"textures\", 0) turns it off)");
+    if ((rc = refuse_nee_only_ready(ctx, "pt_trace_rays")) != PT_OK) return rc;
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
@@ -596,20 +602,13 @@ static int launch_megakernel(pt_context* ctx, RenderParams& p, const int32_t* ti
 }
 
 int pt_render(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t nsamples) {
-    if (ctx && medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal("pt_render"));
-    if (ctx && interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal("pt_render"));
-    if (ctx && lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal("pt_render"));
-    if (ctx && ctx->frosted) return fail(ctx, PT_EINVAL, "pt_render: option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
-    if (ctx && lens_on(ctx)) return fail(ctx, PT_EINVAL, "pt_render: a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
-    if (ctx && ctx->coated) return fail(ctx, PT_EINVAL, "pt_render: option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
-    if (ctx && ctx->glossy) return fail(ctx, PT_EINVAL, "pt_render: option glossy is on and only pt_render_nee shades the rough metal of material type 4 (pt_set_option(ctx, \"glossy\", 0) turns it off)");
+    int rc;
+    if (ctx && (rc = refuse_nee_only_early(ctx, "pt_render")) != PT_OK) return rc;
     PT_NEED_DEVICE(ctx);
-    int rc = check_ready(ctx, cam);
+    rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
     if (iterations < 0 || nsamples < 0) return fail(ctx, PT_EINVAL, "iterations/nsamples must be >= 0");
-    if (ctx->env_set) return fail(ctx, PT_EINVAL, "pt_render: an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
-    if (ctx->smooth_normals) return fail(ctx, PT_EINVAL, "pt_render: option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
-    if (ctx->textures) return fail(ctx, PT_EINVAL, "pt_render: option textures is on and only pt_render_nee reads albedo textures (pt_set_option(ctx, \"textures\", 0) turns it off)");
+    if ((rc = refuse_nee_only_ready(ctx, "pt_render")) != PT_OK) return rc;
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");
     if (nsamples == 0) return PT_OK;
     PT_HIP(ctx, hipSetDevice(ctx->device));
@@ -670,21 +669,14 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
                   " tiles does not fit the 31-bit work-item counter of one launch";
     }
     if (!why.empty()) return fail(ctx, PT_EINVAL, who + ": " + why);
-    if (!nee && medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal(who));
-    if (!nee && interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal(who));
+    int rc;
+    if (!nee && (rc = refuse_nee_only_early(ctx, who)) != PT_OK) return rc;
     if (nee && grid_on(ctx) && !grid_unbounded(ctx).empty()) return fail(ctx, PT_EINVAL, who + ": " + grid_unbounded(ctx));
-    if (lights_on(ctx) && (!nee || ap->strategy == PT_NEE_BSDF))
-        return fail(ctx, PT_EINVAL, lights_refusal(nee ? who + " with strategy PT_NEE_BSDF" : who));
-    if (!nee && ctx->frosted) return fail(ctx, PT_EINVAL, who + ": option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
-    if (!nee && lens_on(ctx)) return fail(ctx, PT_EINVAL, who + ": a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
-    if (!nee && ctx->coated) return fail(ctx, PT_EINVAL, who + ": option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");
-    if (!nee && ctx->glossy) return fail(ctx, PT_EINVAL, who + ": option glossy is on and only pt_render_nee shades the rough metal of material type 4 (pt_set_option(ctx, \"glossy\", 0) turns it off)");
+    if (nee && lights_on(ctx) && ap->strategy == PT_NEE_BSDF) return fail(ctx, PT_EINVAL, lights_refusal(who + " with strategy PT_NEE_BSDF"));
     PT_NEED_DEVICE(ctx);
-    int rc = check_ready(ctx, cam);
+    rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
-    if (!nee && ctx->env_set) return fail(ctx, PT_EINVAL, who + ": an environment is set and only pt_render_nee draws it (pt_clear_environment removes it)");
-    if (!nee && ctx->smooth_normals) return fail(ctx, PT_EINVAL, who + ": option smooth_normals is on and only pt_render_nee shades with vertex normals (pt_set_option(ctx, \"smooth_normals\", 0) turns it off)");
-    if (!nee && ctx->textures) return fail(ctx, PT_EINVAL, who + ": option textures is on and only pt_render_nee reads albedo textures (pt_set_option(ctx, \"textures\", 0) turns it off)");
+    if (!nee && (rc = refuse_nee_only_ready(ctx, who)) != PT_OK) return rc;
     if (!nee && ctx->variant != 0) return fail(ctx, PT_EINVAL, who + ": the megakernel (variant 0) only");
     if (ctx->world != 1) return fail(ctx, PT_EINVAL, who + ": contexts of one rank (world == 1) only");
     if (ctx->adaptive_frame) return fail(ctx, PT_EINVAL, "an adaptive frame is held: pt_set_current_sample(ctx, 0) starts a new frame");

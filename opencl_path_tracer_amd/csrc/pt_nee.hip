@@ -1,39 +1,43 @@
 // pt_nee.hip -- next-event estimation with multiple importance sampling (pt_render_nee; the estimator is pinned in include/pt_api.h).
-// One body, nee_frame<MODE, BLOCK, flags...>: one lane per local pixel, persistent blocks (like k_aovs), every sample of the pixel back to
-// back, path state in registers.  Each segment is shade_hit (pt_device.hpp) with a light hook, NeeHook<MODE, flags...>: the MIS weight of
+// One body, nee_frame<FAMILY, MODE, BLOCK, ENV, TILED>: one lane per local pixel, persistent blocks (like k_aovs), every sample of the pixel back
+// to back, path state in registers.  Each segment is shade_hit (pt_device.hpp) with a light hook, NeeHook<FAMILY, MODE, ENV>: the MIS weight of
 // an emitter hit after a lobe vertex and, at a lobe vertex, a light sample: one shadow ray whose search is cut just past the sampled point.
 // The light sample's three numbers come from a counter-based hash (nee_rand, pt_internal.hpp) of (LCG state at the start of the sample,
 // segment, dimension), never from the LCG, so the BSDF path draws exactly what pt_render draws and rnds / rays come out the same in every
-// strategy.  What a feature adds sits under `if constexpr (FLAG)` here and under HOOK::flag in shade_hit, and what it carries in a *Slot
-// that is empty without it, so an instance compiles to the code it was before the features it lacks existed:
+// strategy.  FAMILY is a NeeFamily (pt_internal.hpp): each family is the one before it with one more feature compiled in, so a family names
+// the features it has -- NeeHook derives them (smooth = FAMILY >= kNeeSmooth, ...).  What a feature adds sits under `if constexpr (feature)`
+// here and under HOOK::feature in shade_hit, and what it carries in a *Slot that is empty without it, so an instance compiles to the code it
+// was before the features it lacks existed.  The two forms' flags, then the features in the families' order:
 //   ENV     an environment map (pt_set_environment): a miss adds the sky, and a lobe vertex samples either the sky or a triangle light,
 //           chosen by one more hash value
 //   TILED   the work is a list of 8x8 frame tiles (the rounds of pt_render_adaptive_ex): item j is pixel j & 63 of tile
 //           frame_tile(p, j >> 6), so a wave is a tile as in k_render.  Three declarations sit outside the flag because both branches use
 //           them afterwards (the loop counter j with the pixel i = j, lrow / x, and the pixel counter `rendered`, dead when untiled)
-//   SMOOTH  smooth shading from vertex normals (option smooth_normals)
-//   TEX     albedo textures (option textures, section 5.10)
-//   GLOSSY  material type 4 is the rough metal (option glossy, section 5.12)
-//   COAT    material type 5 is the coated diffuse (option coated, section 5.13); whether type 4 is live is a run-time field from here on
-//   LENS    each sample starts on the thin-lens ray (pt_set_lens, section 5.14); whether type 5 is live is a run-time field from here on
-//   FROST   material type 6 is the rough dielectric (option frosted, section 5.15); whether a lens is set is a run-time field (flags bit 2)
-//   LIGHTS  analytic point, spot and directional lights (pt_set_lights, section 5.16): a lobe vertex samples the set, the sky or a triangle
-//           light; whether type 6 is live is a run-time field from here on (flags bit 3)
-//   MEDIUM  a homogeneous participating medium (pt_set_medium, section 5.17): a segment may end at a scatter vertex before its hit, and every
+//   smooth  smooth shading from vertex normals (option smooth_normals)
+//   textured  albedo textures (option textures, section 5.10)
+//   glossy  material type 4 is the rough metal (option glossy, section 5.12)
+//   coated  material type 5 is the coated diffuse (option coated, section 5.13); whether type 4 is live is a run-time field from here on
+//           (kNeeFlagGlossy)
+//   lens    each sample starts on the thin-lens ray (pt_set_lens, section 5.14); whether type 5 is live is a run-time field from here on
+//           (kNeeFlagCoated)
+//   frosted  material type 6 is the rough dielectric (option frosted, section 5.15); whether a lens is set is a run-time field (kNeeFlagLens)
+//   lights  analytic point, spot and directional lights (pt_set_lights, section 5.16): a lobe vertex samples the set, the sky or a triangle
+//           light; whether type 6 is live is a run-time field from here on (kNeeFlagFrosted)
+//   medium  a homogeneous participating medium (pt_set_medium, section 5.17): a segment may end at a scatter vertex before its hit, and every
 //           light sample outside a dielectric carries the transmittance of its shadow ray; whether a pickable light set is held is a
-//           run-time field (flags bit 4)
-//   GRID    the medium's extinction is sigma_t times a voxel density (pt_set_medium_density, section 5.20): the free flight and the transmittance
-//           walk the grid (grid_walk, pt_device.hpp); everything else is MEDIUM's
-//   INTERIOR  a type-2 or type-6 material may hold an interior (pt_set_material_interior, section 5.21): a segment inside such a dielectric takes
+//           run-time field (kNeeFlagLights)
+//   grid    the medium's extinction is sigma_t times a voxel density (pt_set_medium_density, section 5.20): the free flight and the transmittance
+//           walk the grid (grid_walk, pt_device.hpp); everything else is medium's
+//   interior  a type-2 or type-6 material may hold an interior (pt_set_material_interior, section 5.21): a segment inside such a dielectric takes
 //           Beer-Lambert absorption and may end at a scatter vertex of the interior; whether a medium is held and whether its grid is live are
-//           run-time fields (flags bits 5 and 6)
-//   LTREE   the triangle-light branch of a light sample picks its triangle by walking the light hierarchy (option light_tree, section 5.22), and
+//           run-time fields (kNeeFlagMedium, kNeeFlagGrid)
+//   ltree   the triangle-light branch of a light sample picks its triangle by walking the light hierarchy (option light_tree, section 5.22), and
 //           an emitter hit's weight walks it towards the hit triangle from the previous lobe vertex, whose origin and cull normal the hook
-//           keeps; whether an interior binding is live is a run-time field (flags bit 7)
-// Each flag from SMOOTH on requires the one before it.  The kernels are the twelve families the host can ask for (NeeFamily, pt_internal.hpp)
-// -- k_nee, k_nee_smooth, _tex, _glossy, _coated, _lens, _frosted, _lights, _medium, _grid, _interior, _lighttree: each is the one before it with one more flag -- times ENV and TILED
-// (k_nee_env*, k_nee_tiles*, k_nee_env_tiles*).  In a family whose option is off the data is null (vn, tv.uv) or the field clear.
+//           keeps; whether an interior binding is live is a run-time field (kNeeFlagInterior)
+// The kernels are k_nee<FAMILY, MODE, BLOCK, ENV, TILED> for the twelve families the host can ask for.  In a family whose option is off the data
+// is null (vn, tv.uv) or the flag clear.
 #include "pt_device.hpp"
+#include <type_traits>
 
 namespace ptamd {
 
@@ -161,28 +165,14 @@ struct LightTreeSlot<true> {
 };
 
 // shade_hit's light hook: what k_nee adds to a segment
-template <int MODE, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false, bool FROST = false,
-          bool LIGHTS = false, bool MEDIUM = false, bool GRID = false, bool INTERIOR = false, bool LTREE = false>
+// and what a family compiles in: every feature up to its own (the names are what shade_hit asks a hook for, and what the comments here call them)
+template <int FAMILY, int MODE, bool ENV>
 struct NeeHook {
-    static_assert(INTERIOR || !LTREE, "the light-tree instances are built on the interior code");
-    static_assert(GRID || !INTERIOR, "the interior instances are built on the grid code");
-    static_assert(MEDIUM || !GRID, "the grid instances are built on the medium code");
-    static_assert(LIGHTS || !MEDIUM, "the medium instances are built on the lights code");
-    static_assert(FROST || !LIGHTS, "the lights instances are built on the frosted code");
-    static_assert(LENS || !FROST, "the frosted instances are built on the lens code");
-    static_assert(COAT || !LENS, "the lens instances are built on the coated code");
-    static_assert(SMOOTH || !TEX, "the textured instances are built on the smooth code");
-    static_assert(TEX || !GLOSSY, "the glossy instances are built on the textured code");
+    static_assert(FAMILY >= kNeePlain && FAMILY <= kNeeLightTree, "FAMILY is a NeeFamily");
     static constexpr bool active = true;
-    static constexpr bool smooth = SMOOTH;
-    static constexpr bool textured = TEX;
-    static_assert(GLOSSY || !COAT, "the coated instances are built on the glossy code");
-    static constexpr bool glossy = GLOSSY;
-    static constexpr bool coated = COAT;
-    static constexpr bool lens = LENS;
-    static constexpr bool frosted = FROST;
-    static constexpr bool lights = LIGHTS;
-    static constexpr bool medium = MEDIUM;
+    static constexpr bool smooth = FAMILY >= kNeeSmooth, textured = FAMILY >= kNeeTex, glossy = FAMILY >= kNeeGlossy, coated = FAMILY >= kNeeCoated;
+    static constexpr bool lens = FAMILY >= kNeeLens, frosted = FAMILY >= kNeeFrosted, lights = FAMILY >= kNeeLights, medium = FAMILY >= kNeeMedium;
+    static constexpr bool grid = FAMILY >= kNeeGrid, interior = FAMILY >= kNeeInterior, ltree = FAMILY >= kNeeLightTree;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -194,39 +184,39 @@ struct NeeHook {
     bool after_lobe = false;       // the previous vertex was a lobe vertex (its flipped normal: Nprev)
     f3 Nprev = mk(0.f, 0.f, 0.f);
     EnvSlot<ENV> env;
-    SmoothSlot<SMOOTH> sm;
-    TexSlot<TEX> tx;
-    GlossySlot<GLOSSY> gs;
-    CoatSlot<COAT> ct;
-    LensSlot<LENS> ln;
-    FrostSlot<FROST> frs;
-    LightsSlot<LIGHTS> lg;
-    MediumSlot<MEDIUM> md;
-    GridSlot<GRID> gr;
-    InteriorSlot<INTERIOR> in;
-    LightTreeSlot<LTREE> lts;
+    SmoothSlot<smooth> sm;
+    TexSlot<textured> tx;
+    GlossySlot<glossy> gs;
+    CoatSlot<coated> ct;
+    LensSlot<lens> ln;
+    FrostSlot<frosted> frs;
+    LightsSlot<lights> lg;
+    MediumSlot<medium> md;
+    GridSlot<grid> gr;
+    InteriorSlot<interior> in;
+    LightTreeSlot<ltree> lts;
 
-    // LTREE: an interior binding is live (a run-time answer in the light-tree instances only: the interior ones run only when one is)
+    // ltree: an interior binding is live (a run-time answer in the light-tree instances only: the interior ones run only when one is)
     PT_DEV bool interior_live() const {
-        if constexpr (LTREE) return lts.interior;
-        else return INTERIOR;
+        if constexpr (ltree) return lts.interior;
+        else return interior;
     }
-    // MEDIUM: the lane enters shade_hit at a scatter vertex
+    // medium: the lane enters shade_hit at a scatter vertex
     PT_DEV bool scatters() const {
-        if constexpr (MEDIUM) return md.sc;
+        if constexpr (medium) return md.sc;
         else return false;
     }
-    // MEDIUM: the free flight of segment k along (rP, rD), whose closest hit is at t (+inf: a miss): the distance of the scatter vertex, or -1
+    // medium: the free flight of segment k along (rP, rD), whose closest hit is at t (+inf: a miss): the distance of the scatter vertex, or -1
     // when the segment reaches its end.  A segment with nothing inside the box draws no number (d >= 0 is never below L = 0)
-    // GRID: the same through the voxels: tau = -log1pf(-u) of the same number against the optical depth the walk accumulates
+    // grid: the same through the voxels: tau = -log1pf(-u) of the same number against the optical depth the walk accumulates
     PT_DEV float free_flight(f3 rP, f3 rD, float t) const {
-        if constexpr (INTERIOR) {          // (the grid is a run-time answer here)
+        if constexpr (interior) {          // (the grid is a run-time answer here)
             if (in.grid) {
                 const float tau = -log1pf(-nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 0)));
                 const GridWalk w = grid_walk<true>(md.v, gr.v, rP, rD, t, tau);
                 return w.voxel >= 0 ? max0(w.s) : -1.0f;
             }
-        } else if constexpr (GRID) {
+        } else if constexpr (grid) {
             const float tau = -log1pf(-nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 0)));      // (a hash, not a draw: unused where the clip is empty)
             const GridWalk w = grid_walk<true>(md.v, gr.v, rP, rD, t, tau);
             return w.voxel >= 0 ? max0(w.s) : -1.0f;       // (s < 0 would take an accumulated depth a rounding past tau in a voxel at the origin)
@@ -238,44 +228,44 @@ struct NeeHook {
         const float d = medium_flight(md.v.sigma_t, nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 0)));
         return d < L ? a + d : -1.0f;
     }
-    // MEDIUM: the scatter vertex's own factor; false: the albedo left nothing and the path ends
+    // medium: the scatter vertex's own factor; false: the albedo left nothing and the path ends
     PT_DEV bool scatter_albedo(PathRegs& st) const {
         const f3 fs = st.S() * mk(md.v.albedo[0], md.v.albedo[1], md.v.albedo[2]);
         st.setS(fs);
         return fs.x != 0.0f || fs.y != 0.0f || fs.z != 0.0f;
     }
-    // MEDIUM: the scatter vertex at distance s ends: the next segment starts there, along a direction of the phase function; a lobe vertex
+    // medium: the scatter vertex at distance s ends: the next segment starts there, along a direction of the phase function; a lobe vertex
     // for what follows, with its p_b kept where the rough vertices keep theirs
     PT_DEV void scatter_direction(f3& rP, f3& rD, float s) {
-        if constexpr (MEDIUM) {
+        if constexpr (medium) {
             const float u1 = nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 1)), u2 = nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 2));
             rP = madd(rD, s, rP);
             rD = normalize3(medium_direction(md.v.g, rD, u1, u2, &gs.pb));
             after_lobe = true;
         }
     }
-    // INTERIOR: a medium with sigma_t > 0 is held (a run-time answer in the interior instances only: the medium ones run only when one is)
+    // interior: a medium with sigma_t > 0 is held (a run-time answer in the interior instances only: the medium ones run only when one is)
     PT_DEV bool medium_live() const {
-        if constexpr (INTERIOR) return in.medium;
-        else return MEDIUM;
+        if constexpr (interior) return in.medium;
+        else return medium;
     }
-    // INTERIOR: the free flight of segment k inside a dielectric whose hit is at t, through the interior q0 = {sigma_a.rgb, sigma_s}: the
+    // interior: the free flight of segment k inside a dielectric whose hit is at t, through the interior q0 = {sigma_a.rgb, sigma_s}: the
     // distance of the scatter vertex, or -1 when the segment reaches its hit.  The exterior medium never draws while inside, so dimension 0
     // of its stream at this segment is free
     PT_DEV float interior_flight(const float4 q0, float t) const {
         if (!(q0.w > 0.0f)) return -1.0f;          // (no hash without scattering)
         return ptamd::interior_flight(q0.w, nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 0)), t);
     }
-    // INTERIOR: Beer-Lambert over the length l of the segment inside; false: the factor left nothing and the path ends
+    // interior: Beer-Lambert over the length l of the segment inside; false: the factor left nothing and the path ends
     PT_DEV bool interior_absorb(PathRegs& st, const float4 q0, float l) const {
         const f3 fs = st.S() * ptamd::interior_absorb(mk(q0.x, q0.y, q0.z), l);
         st.setS(fs);
         return fs.x != 0.0f || fs.y != 0.0f || fs.z != 0.0f;
     }
-    // INTERIOR: scatter_direction with the vertex's own g and the after-lobe answer: a scatter vertex of an interior is no lobe vertex for what
+    // interior: scatter_direction with the vertex's own g and the after-lobe answer: a scatter vertex of an interior is no lobe vertex for what
     // follows (an emitter hit or a sky miss on the next segment has weight 1, as after a refraction)
     PT_DEV void scatter_direction(f3& rP, f3& rD, float s, float g, bool lobe) {
-        if constexpr (MEDIUM) {
+        if constexpr (medium) {
             const float u1 = nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 1)), u2 = nee_unit(nee_rand(key ^ 0x5bd1e995u, k, 2));
             float pb;
             rP = madd(rD, s, rP);
@@ -284,22 +274,22 @@ struct NeeHook {
             after_lobe = lobe;
         }
     }
-    // LIGHTS: type 6 is live (option frosted; a run-time answer in the lights instances only: the frosted ones run only when it is)
+    // lights: type 6 is live (option frosted; a run-time answer in the lights instances only: the frosted ones run only when it is)
     PT_DEV bool frost_live() const {
-        if constexpr (LIGHTS) return lg.frost;
-        else return FROST;
+        if constexpr (lights) return lg.frost;
+        else return frosted;
     }
-    // LENS: type 5 is live (option coated; a run-time answer in the lens instances only: the coated ones run only when it is)
+    // lens: type 5 is live (option coated; a run-time answer in the lens instances only: the coated ones run only when it is)
     PT_DEV bool coat_live() const {
-        if constexpr (LENS) return ln.coat;
-        else return COAT;
+        if constexpr (lens) return ln.coat;
+        else return coated;
     }
-    // COAT: type 4 is live (option glossy)
+    // coated: type 4 is live (option glossy)
     PT_DEV bool metal_live() const {
-        if constexpr (COAT) return ct.metal;
-        else return GLOSSY;
+        if constexpr (coated) return ct.metal;
+        else return glossy;
     }
-    // FROST: the reflection lobe's p_b of the unit direction w at the type-6 vertex with normal N reached along rD (ins: inside the
+    // frosted: the reflection lobe's p_b of the unit direction w at the type-6 vertex with normal N reached along rD (ins: inside the
     // medium), and the factor_R its own update with w would give -- through frosted_pdf_weight, as the sampled direction's
     PT_DEV float frosted_light(const pt_material* __restrict__ m, f3 N, f3 rD, f3 w, bool ins, f3 fR, f3* fr) const {
         f3 Z, X;
@@ -310,7 +300,7 @@ struct NeeHook {
         *fr = fR * g;
         return pb;
     }
-    // COAT: the mixture's p_b of the unit direction w at the type-5 vertex with normal N reached along rD, and the factor_S its own update
+    // coated: the mixture's p_b of the unit direction w at the type-5 vertex with normal N reached along rD, and the factor_S its own update
     // with w would give -- through coated_pdf_weight, as the sampled direction's (lobe_direction_rough)
     PT_DEV float coated_light(const pt_material* __restrict__ m, f3 N, f3 rD, f3 w, f3 fS, f3* fs) const {
         f3 Z, X;
@@ -320,7 +310,7 @@ struct NeeHook {
         *fs = fS * g;
         return pb;
     }
-    // GLOSSY: p_b of the unit direction w at the type-4 vertex with normal N reached along rD, and the factor_S its own update with w
+    // glossy: p_b of the unit direction w at the type-4 vertex with normal N reached along rD, and the factor_S its own update with w
     // would give -- through glossy_pdf, as the sampled direction's (lobe_direction_rough)
     PT_DEV float glossy_light(const pt_material* __restrict__ m, f3 N, f3 rD, f3 w, f3 fS, f3* fs) const {
         f3 Z, X;
@@ -332,9 +322,9 @@ struct NeeHook {
         *fs = fS * glossy_weight(alpha, ldf3(m->F0), o, h, wl);
         return pb;
     }
-    // GLOSSY: the sampled direction (before normalisation) of a lobe vertex of any kind (lobe_direction_rough).  A rough vertex also
-    // multiplies a factor by g(w), keeps its p_b and may end the path: the metal (gl) factor_S, unless w.z > 0; COAT: the coated vertex (ct_)
-    // factor_S, unless w.z > 0 and p_b > 0; FROST: the frosted one (fr_) factor_R -- a reflection unless w.z > 0, while a refraction toggles
+    // glossy: the sampled direction (before normalisation) of a lobe vertex of any kind (lobe_direction_rough).  A rough vertex also
+    // multiplies a factor by g(w), keeps its p_b and may end the path: the metal (gl) factor_S, unless w.z > 0; coated: the coated vertex (ct_)
+    // factor_S, unless w.z > 0 and p_b > 0; frosted: the frosted one (fr_) factor_R -- a reflection unless w.z > 0, while a refraction toggles
     // `inside`, leaves along -Ng (*side) and ends the path unless w.z < 0.  The lobe of a coated or frosted vertex is chosen by a hash value
     // keyed like the environment's selection, dimension 1 (a vertex has one type)
     template <bool SK, class ST>
@@ -342,7 +332,7 @@ struct NeeHook {
                           float* side) {
         float alpha = 1.0f, u_sel = 0.0f, eta = 1.0f;
         f3 F0 = mk(0.f, 0.f, 0.f), kd = F0;
-        if constexpr (FROST) {
+        if constexpr (frosted) {
             if (gl || ct_) alpha = m->n;   // (the device copy of a type-4 or type-5 material carries its roughness there: pt_upload_materials)
             if (fr_) {
                 alpha = m->shininess;      // (that of a type-6 material here; its n is the index of refraction)
@@ -352,7 +342,7 @@ struct NeeHook {
             if (gl || ct_ || fr_) F0 = ldf3(m->F0);
             if (ct_) kd = albedo(m);
             if (ct_ || fr_) u_sel = nee_unit(nee_rand(~key, k, 1));
-        } else {                           // (the same without fr_, in the order the instances without FROST were compiled from)
+        } else {                           // (the same without fr_, in the order the instances without frosted were compiled from)
             if (gl || ct_) {
                 alpha = m->n;
                 F0 = ldf3(m->F0);
@@ -365,19 +355,19 @@ struct NeeHook {
         GlossyOut go;
         CoatedOut co;
         FrostedOut fo;
-        const f3 d = lobe_direction_rough<SK, COAT>(N, rD, gl, ct_, fr_, alpha, F0, kd, eta, u_sel, rnd1, rnd2, &go, &co, &fo);
+        const f3 d = lobe_direction_rough<SK, coated>(N, rD, gl, ct_, fr_, alpha, F0, kd, eta, u_sel, rnd1, rnd2, &go, &co, &fo);
         if (gl) {
             st.setS(st.S() * (go.F * go.g1w));
             gs.pb = go.pb;
             if (!(go.wz > 0.0f)) sm.dead = true;
         }
-        if constexpr (COAT)
+        if constexpr (coated)
             if (ct_) {
                 st.setS(st.S() * co.g);
                 gs.pb = co.pb;
                 if (!(co.wz > 0.0f && co.pb > 0.0f)) sm.dead = true;
             }
-        if constexpr (FROST)
+        if constexpr (frosted)
             if (fr_) {
                 st.setR(st.R() * fo.g);
                 gs.pb = fo.pb;
@@ -389,12 +379,12 @@ struct NeeHook {
             }
         return d;
     }
-    // the albedo of the current type-0 vertex: the material's kd, or under TEX what shading_attributes_at left
+    // the albedo of the current type-0 vertex: the material's kd, or under textured what shading_attributes_at left
     PT_DEV f3 albedo(const pt_material* __restrict__ m) const {
-        if constexpr (TEX) return tx.kd;
+        if constexpr (textured) return tx.kd;
         else return ldf3(m->kd);
     }
-    // TEX: shading_normal_at and the vertex's albedo from one evaluation of the weights (sm.vn == nullptr: smooth_normals is off).  kd is
+    // textured: shading_normal_at and the vertex's albedo from one evaluation of the weights (sm.vn == nullptr: smooth_normals is off).  kd is
     // read where something uses it: a type-0 vertex and the preview of iterations == 1
     PT_DEV f3 shading_attributes_at(const RenderParams& p, const float4* __restrict__ tris, int ti, f3 rD, f3 hp, f3 N, f3 Ng, int type,
                                     const pt_material* __restrict__ m) {
@@ -402,23 +392,23 @@ struct NeeHook {
         sm.flip = dot3(rD, N) > 0.0f;      // shade_hit's flip
         f3 kd = mk(0.f, 0.f, 0.f);
         if (type == 0 || p.iterations == 1) kd = ldf3(m->kd);
-        int ttype = type;              // GLOSSY: the instances also run with option textures off (a view with uv = null): no lookup then
-        if constexpr (LENS) {          // LENS: as COAT below where type 5 is live in the launch (option coated)
+        int ttype = type;              // glossy: the instances also run with option textures off (a view with uv = null): no lookup then
+        if constexpr (lens) {          // lens: as coated below where type 5 is live in the launch (option coated)
             const bool live = type == 5 && ln.coat;
             if (live) kd = ldf3(m->kd);
             ttype = live ? 0 : type;
         } else {
-            if constexpr (COAT) if (type == 5) kd = ldf3(m->kd);
-            if constexpr (COAT) ttype = type == 5 ? 0 : type;      // COAT: the lookup runs for type 0 or 5
+            if constexpr (coated) if (type == 5) kd = ldf3(m->kd);
+            if constexpr (coated) ttype = type == 5 ? 0 : type;      // coated: the lookup runs for type 0 or 5
         }
-        if constexpr (GLOSSY) ttype = tx.v.uv ? ttype : -1;
+        if constexpr (glossy) ttype = tx.v.uv ? ttype : -1;
         const f3 Ns = shading_normal_albedo(sm.vn, tx.v, tris, ti, rD, hp, N, Ng, ttype, (int)(m - p.mats), &kd);
         tx.kd = kd;
         return Ns;
     }
     // the normal the offsets use: N itself, or under smooth shading (where N is the shading normal) the geometric one
     PT_DEV f3 geo(f3 N) const {
-        if constexpr (SMOOTH) {
+        if constexpr (smooth) {
             const float4 c = sv.tris[sm.ti * 3 + 2];
             const f3 Ng = mk(c.y, c.z, c.w);
             return sm.flip ? -Ng : Ng;
@@ -426,20 +416,20 @@ struct NeeHook {
             return N;
         }
     }
-    // SMOOTH: the shading normal of the hit (N the record's normal, Ng flipped against the ray); keeps Ng for the rest of the vertex
+    // smooth: the shading normal of the hit (N the record's normal, Ng flipped against the ray); keeps Ng for the rest of the vertex
     PT_DEV f3 shading_normal_at(const float4* __restrict__ tris, int ti, f3 rD, f3 hp, f3 N, f3 Ng) {
         sm.ti = ti;
         sm.flip = dot3(rD, N) > 0.0f;      // shade_hit's flip
         return shading_normal(sm.vn, tris, ti, rD, hp, N, Ng);
     }
-    // SMOOTH: a lobe vertex whose sampled direction (before normalisation) is not above the geometric surface ends the path; FROST: a refracted
+    // smooth: a lobe vertex whose sampled direction (before normalisation) is not above the geometric surface ends the path; frosted: a refracted
     // one (through) that is not below it
     PT_DEV void leaves_surface(bool lobe, bool through, f3 dnew) {
         if (!lobe) return;
         const float g = dot3(dnew, geo(dnew));
-        if (FROST && through ? g >= 0.0f : g <= 0.0f) sm.dead = true;
+        if (frosted && through ? g >= 0.0f : g <= 0.0f) sm.dead = true;
     }
-    // SMOOTH: the mirror / dielectric vertex of shade_hit evaluated with Ns; if the direction it picks is on the wrong geometric side
+    // smooth: the mirror / dielectric vertex of shade_hit evaluated with Ns; if the direction it picks is on the wrong geometric side
     // (a reflection not above, a refraction not below the surface), once more with Ng and the same LCG value, and that stands
     // (TWIN of the specular branch of shade_hit: the same expressions in the same order)
     template <class ST>
@@ -493,7 +483,7 @@ struct NeeHook {
     PT_DEV float emitter_weight(int ti, float t, float inten, f3 rD) const {
         if (!nee || !after_lobe) return 1.0f;
         float pa;
-        if constexpr (LTREE) {             // the weight walk from the previous lobe vertex: the P the pick there had for this triangle
+        if constexpr (ltree) {             // the weight walk from the previous lobe vertex: the P the pick there had for this triangle
             pa = 0.0f;
             const int s = lts.v.slot[ti];
             if (s >= 0 && inten > 0.0f) {
@@ -502,11 +492,11 @@ struct NeeHook {
             }
         } else pa = lt.pdf_area[ti];
         if constexpr (ENV) pa *= 1.0f - env.v.p_env;                 // the light table is chosen with probability 1 - P_env
-        if constexpr (LIGHTS) pa *= 1.0f - lg.v.p_ana;               // ... and the sky or the table with probability 1 - P_ana
+        if constexpr (lights) pa *= 1.0f - lg.v.p_ana;               // ... and the sky or the table with probability 1 - P_ana
         if (!(pa > 0.0f && inten > 0.0f)) return 1.0f;
         if (!mis) return 0.0f;
         float pb;
-        if constexpr (GLOSSY) pb = gs.pb;
+        if constexpr (glossy) pb = gs.pb;
         else pb = max0(dot3(Nprev, rD)) * kOneOverPi;
         const float pl = pa * (t * t) / inten;
         const float rr = pl / pb;          // pb = 0: rr = inf, weight 0
@@ -529,7 +519,7 @@ struct NeeHook {
         *y = madd(v3 - v1, su * (1.0f - u2), madd(v2 - v1, u2 * su, v1));
         return li;
     }
-    // LTREE: the same with the triangle that the walk of the light hierarchy from o (cull normal lts.G) draws with u0; *pa = P x inv_area
+    // ltree: the same with the triangle that the walk of the light hierarchy from o (cull normal lts.G) draws with u0; *pa = P x inv_area
     PT_DEV int tree_light_point(const RenderParams& p, f3 o, float u0, float u1, float u2, f3* y, f3* Ny, float* pa) const {
         float P;
         const int s = lt_walk<true>(lts.v, o.x, o.y, o.z, lts.G.x, lts.G.y, lts.G.z, u0, -1, &P);
@@ -555,33 +545,33 @@ struct NeeHook {
     // what an unoccluded light sample adds: the bracket an emitter hit (or, ENV, a miss) along w on segment k + 1 would add, for the lobe
     // vertex hp (normal N, cosx = N.w, reached along rD; ins: inside a dielectric).  pl: the sample's p_l; g: the emitter's cosine (1 for the
     // sky); e: its radiance with ENV (the sky's texel or the triangle's emission, which light_sample_env has before the traversal).  Without ENV
-    // e is not read: the emission of triangle li is loaded here, after the traversal, where those instances always read it.  LIGHTS: e comes
+    // e is not read: the emission of triangle li is loaded here, after the traversal, where those instances always read it.  lights: e comes
     // with the sample as with ENV; delta: an analytic light's sample, which no other strategy can find: its weight is p_b / p_l under MIS too
-    // MEDIUM: type -1 is a scatter vertex of the medium (p_b the phase function's, N and cosx not read); the sample carries md.T
+    // medium: type -1 is a scatter vertex of the medium (p_b the phase function's, N and cosx not read); the sample carries md.T
     PT_DEV void light_add(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins, f3 w, float cosx,
                           float pl, float g, int li, f3 e, bool delta = false) const {
         float pb = cosx * kOneOverPi;
-        if constexpr (MEDIUM) if (type < 0) pb = medium_hg(md.v.g, dot3(rD, w));
+        if constexpr (medium) if (type < 0) pb = medium_hg(md.v.g, dot3(rD, w));
         f3 fs = st.S();
-        if constexpr (GLOSSY)
+        if constexpr (glossy)
             if (type == 4) {
                 pb = glossy_light(m, N, rD, w, fs, &fs);
                 if (!(pb > 0.0f)) return;      // no density (or a half vector that cannot be normalised): the sample adds nothing
             }
-        if constexpr (COAT)
+        if constexpr (coated)
             if (type == 5) {
                 pb = coated_light(m, N, rD, w, fs, &fs);
                 if (!(pb > 0.0f)) return;
             }
         f3 fr = st.R();
-        if constexpr (FROST)
+        if constexpr (frosted)
             if (type == 6 && frost_live()) {
                 pb = frosted_light(m, N, rD, w, ins, fr, &fr);
                 if (!(pb > 0.0f)) return;
             }
         const float q = pb / pl;
         float wl = mis ? q / fmaf_(q, q, 1.0f) : q;
-        if constexpr (LIGHTS) if (delta) wl = q;
+        if constexpr (lights) if (delta) wl = q;
         f3 fl = st.L(), fb = st.B();
         if (type == 0) {           // the factors the vertex's own update with w would give (shade_hit)
             fl = fl * (albedo(m) * cosx);
@@ -593,9 +583,9 @@ struct NeeHook {
             }
             fb = fb * (ldf3(m->ks) * pw);
         }
-        if constexpr (!ENV && !LIGHTS) e = ldf3(p.mats[p.meta[li].mati].emission);
+        if constexpr (!ENV && !lights) e = ldf3(p.mats[p.meta[li].mati].emission);
         e = ((e * (fl + fb)) * fs) * fr;
-        if constexpr (MEDIUM) e = e * md.T;
+        if constexpr (medium) e = e * md.T;
         if (wl < __builtin_inff()) st.setC(madd(e, g * wl, st.C()));
     }
 
@@ -603,7 +593,7 @@ struct NeeHook {
     // (rD: the direction the vertex was reached along, read for a rough vertex; ins: the path is inside a dielectric, read for a type-6 one)
     PT_DEV void light_sample(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins) {
         if (!nee || k + 1 >= p.iterations) return;
-        if constexpr (ENV || LIGHTS) {
+        if constexpr (ENV || lights) {
             light_sample_env(st, p, m, type, N, hp, rD, ins);
             return;
         }
@@ -616,12 +606,12 @@ struct NeeHook {
         const float cosx = dot3(N, w);
         const float pl = lt.pdf_area[li] * r2 / cosy;
         if (!(cosx > 0.0f && cosy > 0.0f && pl > 0.0f && pl < __builtin_inff())) return;
-        if constexpr (SMOOTH) if (!(dot3(geo(N), w) > 0.0f)) return;          // the sample must be above the geometric surface too
+        if constexpr (smooth) if (!(dot3(geo(N), w) > 0.0f)) return;          // the sample must be above the geometric surface too
         if (shadow_hit<MODE>(sv, o, w, r * 1.0001f, stk, wc) != li) return;
         light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, cosy, li, mk(0.f, 0.f, 0.f));
     }
 
-    // LIGHTS: the analytic light that u0 draws from the set's cdf, seen from o: false if it adds nothing (a point light at o, or o outside its
+    // lights: the analytic light that u0 draws from the set's cdf, seen from o: false if it adds nothing (a point light at o, or o outside its
     // cone); else *w the unit direction to it, *limit the search's cut (its distance r; none for a directional light), *e its intensity x
     // cone / d (d = r^2, or 1 for a directional light) and *pl = P_ana P_light.  One record load: the light picked
     PT_DEV bool analytic_direction(float u0, f3 o, f3* w, float* limit, f3* e, float* pl) const {
@@ -666,24 +656,24 @@ struct NeeHook {
     // ENV: the sky with probability P_env (u_sel, keyed with ~key), else a light of the table with its pdf times 1 - P_env.  Both
     // branches only produce the shadow ray and what it would add; the traversal and the weighting are shared, so a wave that holds
     // both kinds of sample runs one traversal
-    // LIGHTS: before either, the analytic set with probability P_ana (keyed with ~key, dimension 2): a third branch of the same kind, and
+    // lights: before either, the analytic set with probability P_ana (keyed with ~key, dimension 2): a third branch of the same kind, and
     // the other two's p_l take the factor 1 - P_ana.  Without ENV there is no sky branch
     PT_DEV void light_sample_env(PathRegs& st, const RenderParams& p, const pt_material* __restrict__ m, int type, f3 N, f3 hp, f3 rD, bool ins) {
         const float u1 = nee_unit(nee_rand(key, k, 1)), u2 = nee_unit(nee_rand(key, k, 2));
-        const bool mvx = MEDIUM && type < 0;       // MEDIUM: a scatter vertex of the medium: the origin is hp itself, and no cosine is tested
+        const bool mvx = medium && type < 0;       // medium: a scatter vertex of the medium: the origin is hp itself, and no cosine is tested
         f3 o = hp;
         if (!mvx) o = madd(geo(N), 0.001f, hp);
-        if constexpr (LTREE) {             // (kept for the emitter hit of the next segment, whichever branch this sample takes)
+        if constexpr (ltree) {             // (kept for the emitter hit of the next segment, whichever branch this sample takes)
             lts.o = o;
             lts.G = mvx ? mk(0.f, 0.f, 0.f) : geo(N);
         }
         f3 w, e;
         float limit, pl, g;            // the search's cut, p_l, the emitter's cosine (1 for the sky and for an analytic light)
         int want;                      // what the shadow ray must return
-        bool delta = false;            // LIGHTS: the sample is an analytic light's
-        if constexpr (LIGHTS) delta = nee_unit(nee_rand(~key, k, 2)) < lg.v.p_ana;
-        if (LIGHTS && delta) {
-            if constexpr (LIGHTS) {
+        bool delta = false;            // lights: the sample is an analytic light's
+        if constexpr (lights) delta = nee_unit(nee_rand(~key, k, 2)) < lg.v.p_ana;
+        if (lights && delta) {
+            if constexpr (lights) {
                 if (!analytic_direction(nee_unit(nee_rand(key, k, 0)), o, &w, &limit, &e, &pl)) return;
                 g = 1.0f;
                 want = -1;
@@ -719,7 +709,7 @@ struct NeeHook {
                 w = mk(sn * cosf(phi), ct, sn * sinf(phi));
                 e = mk(tx.x, tx.y, tx.z) * ev.scale;
                 pl = ev.p_env * tx.w;
-                if constexpr (LIGHTS) pl *= 1.0f - lg.v.p_ana;
+                if constexpr (lights) pl *= 1.0f - lg.v.p_ana;
                 g = 1.0f;
                 limit = __builtin_inff();
                 want = -1;
@@ -728,7 +718,7 @@ struct NeeHook {
             if (lt.n <= 0) return;            // (P_env or P_ana is 1 then: not reached)
             f3 y, Ny;
             float r2, r, pa;
-            if constexpr (LTREE) {
+            if constexpr (ltree) {
                 want = tree_light_point(p, o, nee_unit(nee_rand(key, k, 0)), u1, u2, &y, &Ny, &pa);
                 if (want < 0) return;         // (a tree that does not cover its table: not reached)
             } else {
@@ -738,14 +728,14 @@ struct NeeHook {
             w = light_direction(o, y, Ny, &r2, &r, &g);
             if constexpr (ENV) pl = (pa * (1.0f - env.v.p_env)) * r2 / g;     // g = 0: inf or NaN, rejected below
             else pl = pa * r2 / g;
-            if constexpr (LIGHTS) pl *= 1.0f - lg.v.p_ana;
+            if constexpr (lights) pl *= 1.0f - lg.v.p_ana;
             e = ldf3(p.mats[p.meta[want].mati].emission);
             limit = r * 1.0001f;
         }
         const float cosx = dot3(N, w);
         if (!((mvx || cosx > 0.0f) && pl > 0.0f && pl < __builtin_inff())) return;
-        if constexpr (SMOOTH) if (!(mvx || dot3(geo(N), w) > 0.0f)) return;   // as in light_sample
-        if constexpr (INTERIOR) {      // (the medium and its grid are run-time answers here)
+        if constexpr (smooth) if (!(mvx || dot3(geo(N), w) > 0.0f)) return;   // as in light_sample
+        if constexpr (interior) {      // (the medium and its grid are run-time answers here)
             md.T = 1.0f;
             if (!ins && in.medium) {
                 if (in.grid) {
@@ -753,15 +743,15 @@ struct NeeHook {
                     if (depth != 0.0f) md.T = expf(-depth);
                 } else md.T = medium_transmittance(md.v, o, w, limit);
             }
-        } else if constexpr (GRID) {   // (for a vertex outside a dielectric)
+        } else if constexpr (grid) {   // (for a vertex outside a dielectric)
             md.T = 1.0f;
             if (!ins) {
                 const float depth = grid_walk<false>(md.v, gr.v, o, w, limit, __builtin_inff()).acc;
                 if (depth != 0.0f) md.T = expf(-depth);
             }
-        } else if constexpr (MEDIUM) md.T = ins ? 1.0f : medium_transmittance(md.v, o, w, limit);
+        } else if constexpr (medium) md.T = ins ? 1.0f : medium_transmittance(md.v, o, w, limit);
         if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
-        if constexpr (LIGHTS) light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e, delta);
+        if constexpr (lights) light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e, delta);
         else light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e);
     }
 
@@ -778,11 +768,11 @@ struct NeeHook {
         }
         float wb = 1.0f;
         float pl = ev.p_env * tx.w;
-        if constexpr (LIGHTS) pl *= 1.0f - lg.v.p_ana;
+        if constexpr (lights) pl *= 1.0f - lg.v.p_ana;
         if (nee && after_lobe && pl > 0.0f) {
             if (mis) {
                 float pb;
-                if constexpr (GLOSSY) pb = gs.pb;
+                if constexpr (glossy) pb = gs.pb;
                 else pb = max0(dot3(Nprev, rD)) * kOneOverPi;
                 const float rr = pl / pb;      // pb = 0: rr = inf, weight 0
                 wb = 1.0f / fmaf_(rr, rr, 1.0f);
@@ -793,11 +783,11 @@ struct NeeHook {
         st.setC(madd(((e * (st.L() + st.B())) * st.S()) * st.R(), wb, st.C()));      // prog.cl:371-373
     }
 
-    // the vertex ends (rD: the new direction; rough: the lobe vertex kept its own p_b).  GLOSSY: a cosine lobe's p_b of rD is what emitter_weight
+    // the vertex ends (rD: the new direction; rough: the lobe vertex kept its own p_b).  glossy: a cosine lobe's p_b of rD is what emitter_weight
     // / miss would compute from Nprev, which the other instances keep
     PT_DEV void end_vertex(bool lobe, bool rough, f3 N, f3 rD) {
         after_lobe = lobe;
-        if constexpr (GLOSSY) {
+        if constexpr (glossy) {
             if (lobe && !rough) gs.pb = max0(dot3(N, rD)) * kOneOverPi;
         } else {
             Nprev = N;
@@ -805,59 +795,45 @@ struct NeeHook {
     }
 };
 
-// SMOOTH (option smooth_normals; k_nee*_smooth below): the hook supplies the shading normal from the packed vertex normals vn; what it
-// adds here sits under `if constexpr (SMOOTH)`
-// TEX (option textures; k_nee*_tex below; on the SMOOTH code only): the hook also supplies the albedo of a type-0 vertex from the view tv
-// GLOSSY (option glossy; k_nee*_glossy below; on the TEX code only): material type 4 is the rough-metal lobe vertex
-// COAT (option coated; k_nee*_coated below; on the GLOSSY code only): material type 5 is the coated-diffuse lobe vertex; metal: option glossy
-// LENS (pt_set_lens; k_nee*_lens below; on the COAT code only): each sample starts on the thin-lens ray; metal bit 1: option coated
-// FROST (option frosted; k_nee*_frosted below; on the LENS code only): material type 6 is the rough-dielectric lobe vertex; metal bit 2: a lens is set
-// LIGHTS (pt_set_lights; k_nee*_lights below; on the FROST code only): a lobe vertex may sample an analytic light; metal bit 3: option frosted
-// MEDIUM (pt_set_medium; k_nee*_medium below; on the LIGHTS code only): between closest_hit and shade_hit a segment may end at a scatter vertex of
-// the medium; metal bit 4: a light set with a pickable light is held
-// GRID (pt_set_medium_density; k_nee*_grid below; on the MEDIUM code only): the hook's free flight and transmittance walk the density grid
-// INTERIOR (pt_set_material_interior; k_nee*_interior below; on the GRID code only): a segment inside a dielectric whose material holds an interior
-// takes its absorption and may end at its scatter vertex; metal bit 5: a medium with sigma_t > 0 is held, bit 6: its grid is live
-// LTREE (option light_tree; k_nee*_lighttree below; on the INTERIOR code only): a light sample's triangle and an emitter hit's weight come from
-// the walk of the light hierarchy; metal bit 7: an interior binding is live
-template <int MODE, int BLOCK, bool ENV, bool TILED = false, bool SMOOTH = false, bool TEX = false, bool GLOSSY = false, bool COAT = false, bool LENS = false,
-          bool FROST = false, bool LIGHTS = false, bool MEDIUM = false, bool GRID = false, bool INTERIOR = false, bool LTREE = false>
-PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn = nullptr, const TexView* tv = nullptr,
-                      int metal = 0, const LensView* lens = nullptr, const LightsView* lights = nullptr, const MediumView* medium = nullptr,
-                      const GridView* grid = nullptr, const InteriorView* interior = nullptr, const LightTreeView* ltree = nullptr) {
+// One frame of the FAMILY's instance
+template <int FAMILY, int MODE, int BLOCK, bool ENV, bool TILED>
+PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn, const TexView* tv, int flags,
+                      const LensView* lens, const LightsView* lights, const MediumView* medium, const GridView* grid, const InteriorView* interior,
+                      const LightTreeView* ltree) {
+    using Hook = NeeHook<FAMILY, MODE, ENV>;
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
     WorkCount wc;
-    NeeHook<MODE, ENV, SMOOTH, TEX, GLOSSY, COAT, LENS, FROST, LIGHTS, MEDIUM, GRID, INTERIOR, LTREE> hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
-    if constexpr (SMOOTH) hook.sm.vn = vn;
-    if constexpr (TEX) hook.tx.v = *tv;
-    if constexpr (LENS) {
-        hook.ct.metal = (metal & 1) != 0;
-        hook.ln.coat = (metal & 2) != 0;
+    Hook hook{lt, sv, stk, &wc, ldf3(p.cam.eye), lt.n > 0 && lt.strategy != 0, lt.strategy == 2};
+    if constexpr (Hook::smooth) hook.sm.vn = vn;
+    if constexpr (Hook::textured) hook.tx.v = *tv;
+    if constexpr (Hook::coated) hook.ct.metal = (flags & kNeeFlagGlossy) != 0;
+    if constexpr (Hook::lens) {
+        hook.ln.coat = (flags & kNeeFlagCoated) != 0;
         hook.ln.v = *lens;
-        if constexpr (FROST) hook.frs.lens = (metal & 4) != 0;
-    } else if constexpr (COAT) hook.ct.metal = metal != 0;
+    }
+    if constexpr (Hook::frosted) hook.frs.lens = (flags & kNeeFlagLens) != 0;
     if constexpr (ENV) {
         hook.env = env;
         hook.nee = lt.strategy != 0;       // the sky is a light (the host launches this instance only for a map with a distribution)
     }
-    if constexpr (LIGHTS) {
+    if constexpr (Hook::lights) {
         hook.lg.v = *lights;
-        hook.lg.frost = (metal & 8) != 0;
+        hook.lg.frost = (flags & kNeeFlagFrosted) != 0;
         // the set is a light (the host launches the lights instances only for a set with a pickable light; the medium ones say whether one is held)
-        if (!MEDIUM || (metal & 16) != 0) hook.nee = lt.strategy != 0;
+        if (!Hook::medium || (flags & kNeeFlagLights) != 0) hook.nee = lt.strategy != 0;
     }
-    if constexpr (MEDIUM) hook.md.v = *medium;
-    if constexpr (GRID) hook.gr.v = *grid;
-    if constexpr (INTERIOR) {
+    if constexpr (Hook::medium) hook.md.v = *medium;
+    if constexpr (Hook::grid) hook.gr.v = *grid;
+    if constexpr (Hook::interior) {
         hook.in.v = *interior;
-        hook.in.medium = (metal & 32) != 0;
-        hook.in.grid = (metal & 64) != 0;
+        hook.in.medium = (flags & kNeeFlagMedium) != 0;
+        hook.in.grid = (flags & kNeeFlagGrid) != 0;
     }
-    if constexpr (LTREE) {
+    if constexpr (Hook::ltree) {
         hook.lts.v = *ltree;
-        hook.lts.interior = (metal & 128) != 0;
+        hook.lts.interior = (flags & kNeeFlagInterior) != 0;
     }
     const int camX = (int)p.cam.XM;
     unsigned rendered = 0;                     // TILED: pixels this lane rendered (statistic "samples", as k_render counts them)
@@ -892,23 +868,23 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
         for (int s = p.first_sample; s < p.first_sample + p.nsamples; ++s) {
             hook.key = (unsigned)seed;
             hook.after_lobe = false;
-            if constexpr (SMOOTH) hook.sm.dead = false;
+            if constexpr (Hook::smooth) hook.sm.dead = false;
             PathRegs st;
             st.reset();
             bool inside = false;
             {
                 const float rnd1 = lcg_rand(seed), rnd2 = lcg_rand(seed);
-                if constexpr (FROST) {
+                if constexpr (Hook::frosted) {
                     if (hook.frs.lens) lens_get_ray_xy(pix_x, pix_y, p.cam, hook.ln.v, rnd1, rnd2, hook.key, &rP, &rD);
                     else camera_get_ray_xy(pix_x, pix_y, p.cam, rnd1, rnd2, &rP, &rD);
-                } else if constexpr (LENS) lens_get_ray_xy(pix_x, pix_y, p.cam, hook.ln.v, rnd1, rnd2, hook.key, &rP, &rD);
+                } else if constexpr (Hook::lens) lens_get_ray_xy(pix_x, pix_y, p.cam, hook.ln.v, rnd1, rnd2, hook.key, &rP, &rD);
                 else camera_get_ray_xy(pix_x, pix_y, p.cam, rnd1, rnd2, &rP, &rD);
             }
             for (int k = 0; k < p.iterations; ++k) {
                 float t;
                 const int ti = closest_hit<MODE, false>(sv, rP, rD, stk, &t, &wc);
-                if constexpr (INTERIOR) {
-                    // MEDIUM's body below with the interior in the `else` of `if (!inside)`: the segment runs inside the dielectric whose
+                if constexpr (Hook::interior) {
+                    // medium's body below with the interior in the `else` of `if (!inside)`: the segment runs inside the dielectric whose
                     // boundary it hits at ti, the surface the path will leave through, and the interior is the one bound to that material.
                     // Only lanes that are inside look the table up.  Its scatter vertex takes no light sample (a shadow ray from inside ends
                     // on the object's own boundary), so the lane skips shade_hit
@@ -940,7 +916,7 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
                     if (!isc) shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, sc ? ts : t, &hook);
                     if (sc) hook.scatter_direction(rP, rD, ts);
                     if (isc) hook.scatter_direction(rP, rD, ts, ig, false);
-                } else if constexpr (MEDIUM) {
+                } else if constexpr (Hook::medium) {
                     // the free flight of the segment; then the scatter vertex: its factor here, its light sample in shade_hit's one call of
                     // light_sample (the lane does nothing else there), its new direction after it
                     hook.k = k;
@@ -963,7 +939,7 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
                     hook.k = k;
                     shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, t, &hook);
                 }
-                if constexpr (SMOOTH) if (hook.sm.dead) break;
+                if constexpr (Hook::smooth) if (hook.sm.dead) break;
             }
             acc = running_mean(acc, st.C(), s);
             if (p.moments) m2 = running_moment(m2, st.C(), s);
@@ -982,251 +958,47 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
     }
 }
 
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee(RenderParams p, NeeTable lt, long long npix) {
-    nee_frame<MODE, BLOCK, false>(p, lt, EnvSlot<false>{}, npix);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env(RenderParams p, NeeTable lt, EnvView env, long long npix) {
-    nee_frame<MODE, BLOCK, true>(p, lt, EnvSlot<true>{env}, npix);
-}
-
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles(RenderParams p, NeeTable lt) {
-    nee_frame<MODE, BLOCK, false, true>(p, lt, EnvSlot<false>{}, 0);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles(RenderParams p, NeeTable lt, EnvView env) {
-    nee_frame<MODE, BLOCK, true, true>(p, lt, EnvSlot<true>{env}, 0);
-}
-
-// the smooth instances (option smooth_normals): the same four kernels with the packed vertex normals as one more argument
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_smooth(RenderParams p, NeeTable lt, const float4* vn, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true>(p, lt, EnvSlot<false>{}, npix, vn);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_smooth(RenderParams p, NeeTable lt, EnvView env, const float4* vn, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true>(p, lt, EnvSlot<true>{env}, npix, vn);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_smooth(RenderParams p, NeeTable lt, const float4* vn) {
-    nee_frame<MODE, BLOCK, false, true, true>(p, lt, EnvSlot<false>{}, 0, vn);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_smooth(RenderParams p, NeeTable lt, EnvView env, const float4* vn) {
-    nee_frame<MODE, BLOCK, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn);
-}
-
-// the textured instances (option textures): the smooth kernels with the texture view as one more argument (vn = null: smooth_normals off)
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tex(RenderParams p, NeeTable lt, const float4* vn, TexView tv, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tex(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_tex(RenderParams p, NeeTable lt, const float4* vn, TexView tv) {
-    nee_frame<MODE, BLOCK, false, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_tex(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv) {
-    nee_frame<MODE, BLOCK, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv);
+// An argument that an instance has only where ON: elsewhere the parameter is an empty NeeNone, which nothing reads
+struct NeeNone {};
+template <bool ON, class T>
+using NeeArg = std::conditional_t<ON, T, NeeNone>;
+// The kernel: k_nee<FAMILY, MODE, BLOCK, ENV, TILED>, twelve families times four forms (ENV, TILED) times the node modes' shapes.  Each view is an
+// argument of its own from the family that compiles its feature in, the flags (NeeFlag) from the first family in which one is a run-time answer
+template <int FAMILY, int MODE, int BLOCK, bool ENV, bool TILED, class F = NeeHook<FAMILY, MODE, ENV>>
+__global__ void __launch_bounds__(BLOCK)
+    k_nee(RenderParams p, NeeTable lt, NeeArg<ENV, EnvView> env, NeeArg<F::smooth, const float4*> vn, NeeArg<F::textured, TexView> tv, NeeArg<F::coated, int> flags,
+          NeeArg<F::lens, LensView> lv, NeeArg<F::lights, LightsView> lg, NeeArg<F::medium, MediumView> mv, NeeArg<F::grid, GridView> gv,
+          NeeArg<F::interior, InteriorView> iv, NeeArg<F::ltree, LightTreeView> tr, NeeArg<!TILED, long long> npix) {
+    EnvSlot<ENV> slot;
+    long long n = 0;
+    const float4* vnp = nullptr;
+    const TexView* tvp = nullptr;
+    int fl = 0;
+    const LensView* lvp = nullptr;
+    const LightsView* lgp = nullptr;
+    const MediumView* mvp = nullptr;
+    const GridView* gvp = nullptr;
+    const InteriorView* ivp = nullptr;
+    const LightTreeView* trp = nullptr;
+    if constexpr (ENV) slot.v = env;
+    if constexpr (!TILED) n = npix;
+    if constexpr (F::smooth) vnp = vn;
+    if constexpr (F::textured) tvp = &tv;
+    if constexpr (F::coated) fl = flags;
+    if constexpr (F::lens) lvp = &lv;
+    if constexpr (F::lights) lgp = &lg;
+    if constexpr (F::medium) mvp = &mv;
+    if constexpr (F::grid) gvp = &gv;
+    if constexpr (F::interior) ivp = &iv;
+    if constexpr (F::ltree) trp = &tr;
+    nee_frame<FAMILY, MODE, BLOCK, ENV, TILED>(p, lt, slot, n, vnp, tvp, fl, lvp, lgp, mvp, gvp, ivp, trp);
 }
 
-// the glossy instances (option glossy with a type-4 material uploaded): the textured kernels, the same arguments (tv.uv = null: textures off)
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_glossy(RenderParams p, NeeTable lt, const float4* vn, TexView tv, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_glossy(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_glossy(RenderParams p, NeeTable lt, const float4* vn, TexView tv) {
-    nee_frame<MODE, BLOCK, false, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_glossy(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv) {
-    nee_frame<MODE, BLOCK, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv);
-}
-
-// the coated instances (option coated with a type-5 material uploaded): the glossy kernels with one more argument, metal (option glossy)
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_coated(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int metal, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, metal);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_coated(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int metal, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, metal);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_coated(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int metal) {
-    nee_frame<MODE, BLOCK, false, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, metal);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_coated(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int metal) {
-    nee_frame<MODE, BLOCK, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, metal);
-}
-
-// the lens instances (a lens with aperture > 0 is set): the coated kernels with the lens view as one more argument; flags: bit 0 option
-// glossy, bit 1 option coated (vn = null, tv.uv = null: smooth_normals, textures off)
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_lens(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_lens(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_lens(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv) {
-    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_lens(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv) {
-    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv);
-}
-
-// the frosted instances (option frosted with a type-6 material uploaded): the lens kernels, the same arguments; flags bit 2: a lens with
-// aperture > 0 is set (else lv is not read and each sample starts on the pinhole ray)
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_frosted(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_frosted(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_frosted(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv) {
-    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_frosted(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv) {
-    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv);
-}
-
-// the lights instances (a light set with a pickable light is held): the frosted kernels with the lights' view as one more argument; flags bit 3:
-// option frosted with a type-6 material uploaded (else type 6 is inert)
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_lights(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_lights(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
-                                                          long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_lights(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg) {
-    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_lights(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg) {
-    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg);
-}
-
-// the medium instances (a medium with sigma_t > 0 is held): the lights kernels with the medium's view as one more argument; flags bit 4: a light
-// set with a pickable light is held (else lg is an empty set with P_ana = 0, and without an emitter or a sky no light sample is taken)
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_medium(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
-                                                      long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg, &mv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_medium(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
-                                                          MediumView mv, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg, &mv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_medium(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv) {
-    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg, &mv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_medium(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
-                                                                MediumView mv) {
-    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv);
-}
-
-// the grid instances (a medium with sigma_t > 0 and a density grid are held): the medium kernels with the grid's view as one more argument
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_grid(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
-                                                    GridView gv, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_grid(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
-                                                        MediumView mv, GridView gv, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_grid(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
-                                                          GridView gv) {
-    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_grid(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
-                                                              MediumView mv, GridView gv) {
-    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv);
-}
-
-// the interior instances (a material holds an interior): the grid kernels with the interiors' table as one more argument; flags bit 5: a medium with
-// sigma_t > 0 is held (else mv is all zero and never read), bit 6: its grid is live (else gv is never read)
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_interior(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
-                                                        GridView gv, InteriorView iv, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_interior(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
-                                                            MediumView mv, GridView gv, InteriorView iv, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_interior(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
-                                                              GridView gv, InteriorView iv) {
-    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_interior(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv,
-                                                                  LightsView lg, MediumView mv, GridView gv, InteriorView iv) {
-    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv);
-}
-
-// the light-tree instances (option light_tree with a non-empty light table): the interior kernels with the hierarchy's view as one more argument;
-// flags bit 7: an interior binding is live (else iv is never read)
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_lighttree(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
-                                                         GridView gv, InteriorView iv, LightTreeView tr, long long npix) {
-    nee_frame<MODE, BLOCK, false, false, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv,
-                                                                                                         &tr);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_lighttree(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg,
-                                                             MediumView mv, GridView gv, InteriorView iv, LightTreeView tr, long long npix) {
-    nee_frame<MODE, BLOCK, true, false, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, npix, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv,
-                                                                                                        &tr);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_tiles_lighttree(RenderParams p, NeeTable lt, const float4* vn, TexView tv, int flags, LensView lv, LightsView lg, MediumView mv,
-                                                               GridView gv, InteriorView iv, LightTreeView tr) {
-    nee_frame<MODE, BLOCK, false, true, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<false>{}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv, &tr);
-}
-template <int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_nee_env_tiles_lighttree(RenderParams p, NeeTable lt, EnvView env, const float4* vn, TexView tv, int flags, LensView lv,
-                                                                   LightsView lg, MediumView mv, GridView gv, InteriorView iv, LightTreeView tr) {
-    nee_frame<MODE, BLOCK, true, true, true, true, true, true, true, true, true, true, true, true, true>(p, lt, EnvSlot<true>{env}, 0, vn, &tv, flags, &lv, &lg, &mv, &gv, &iv, &tr);
-}
-
-// launch_lanes for k_nee_env_tiles_smooth, the instance with the most live state: in its 1,024-thread shape for a treelet the 128-VGPR cap
-// of sixteen waves per workgroup made it spill, so the treelet mode gets 512-thread workgroups (134 VGPRs, no scratch; the stacks and
-// the staged treelet are sized for the workgroup at launch, as for every shape)
+// launch_lanes with 512-thread workgroups for a treelet: in the mode's 1,024-thread shape the 128-VGPR cap of sixteen waves per workgroup makes
+// the instances with the most live state spill (first the smooth family's ENV TILED one: 134 VGPRs, no scratch at 512; the stacks and the
+// staged treelet are sized for the workgroup at launch, as for every shape)
 template <class PICK, class... A>
-static hipError_t launch_lanes_env_tiles_smooth(PICK pick, const RenderParams& p, int64_t n, int cu_count, hipStream_t stream, A... args) {
+static hipError_t launch_lanes_wide(PICK pick, const RenderParams& p, int64_t n, int cu_count, hipStream_t stream, A... args) {
     if (n == 0) return hipSuccess;
     switch (p.node_mode) {
     case kNodesLds: return launch_lanes_t<kNodesLds, 512>(pick, p, n, cu_count, stream, args...);
@@ -1237,59 +1009,81 @@ static hipError_t launch_lanes_env_tiles_smooth(PICK pick, const RenderParams& p
     return hipErrorInvalidValue;
 }
 
-// one kernel of a family: WIDE picks the 512-thread treelet shape above.  launch_lanes_t keys its static LdsMark on the type of `pick`, so every
-// kernel arrives through a lambda of its own (NEE_PICK)
-template <bool WIDE, class PICK, class... A>
-static hipError_t launch_nee_kernel(PICK pick, const RenderParams& p, int64_t n, int cu_count, hipStream_t stream, A... args) {
-    if constexpr (WIDE) return launch_lanes_env_tiles_smooth(pick, p, n, cu_count, stream, args...);
-    else return launch_lanes(pick, p, n, cu_count, stream, args...);
-}
-// the four kernels of one family -- k, its _env, _tiles and _env_tiles forms -- with the family's own arguments `a` between the environment and
-// the pixel count.  SHAPES: which of the four launch in the 512-thread treelet shape (launch_lanes_env_tiles_smooth)
+// which forms of a family take launch_lanes_wide: bit f is form f = ENV + 2 TILED.  The smooth family's ENV TILED instance; the textured
+// family's ENV one too (3 VGPRs more than the smooth one's, which sits at the 128-VGPR cap); every instance from the glossy family on
 enum : int { kWidePlain = 1, kWideEnv = 2, kWideTiles = 4, kWideEnvTiles = 8, kWideAll = 15 };
-template <int SHAPES, class K, class KE, class KT, class KET, class... A>
-static hipError_t launch_nee_family(K k, KE ke, KT kt, KET ket, const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count,
-                                    hipStream_t stream, A... a) {
-    if (nl.tiled) {
-        const int64_t items = (int64_t)p.n_tiles * 64;
-        if (nl.env) return launch_nee_kernel<(SHAPES & kWideEnvTiles) != 0>(ket, p, items, cu_count, stream, lt, *nl.env, a...);
-        return launch_nee_kernel<(SHAPES & kWideTiles) != 0>(kt, p, items, cu_count, stream, lt, a...);
-    }
-    if (nl.env) return launch_nee_kernel<(SHAPES & kWideEnv) != 0>(ke, p, npix, cu_count, stream, lt, *nl.env, a..., (long long)npix);
-    return launch_nee_kernel<(SHAPES & kWidePlain) != 0>(k, p, npix, cu_count, stream, lt, a..., (long long)npix);
-}
-#define NEE_PICK(K) [](auto s) { return K<s.mode, s.block>; }
+constexpr int kNeeWide[kNeeLightTree + 1] = {0,        kWideEnvTiles, kWideEnv | kWideEnvTiles, kWideAll, kWideAll, kWideAll,
+                                             kWideAll, kWideAll,      kWideAll,                 kWideAll, kWideAll, kWideAll};
 
-// The medium family is compiled in a translation unit of its own (pt_nee_medium.hip includes this file with PT_NEE_MEDIUM_TU defined and
-// gets launch_nee_medium only): compiled next to the other families, its instances cost 48 of them two instructions in their uv fetch
-// (the compiler no longer derives for a helper they share that its triangle index is never negative; profiles/medium/README.md)
-// The grid family likewise (pt_nee_grid.hip, PT_NEE_GRID_TU, launch_nee_grid), so that the medium instances compile as they did before it
-hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
-// The interior family likewise (pt_nee_interior.hip, PT_NEE_INTERIOR_TU, launch_nee_interior)
-hipError_t launch_nee_grid(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
-hipError_t launch_nee_interior(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
-// The light-tree family likewise (pt_nee_lighttree.hip, PT_NEE_LIGHTTREE_TU, launch_nee_lighttree), with pt_debug_light_tree_eval's kernel
-hipError_t launch_nee_lighttree(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
-#if defined(PT_NEE_MEDIUM_TU)
-hipError_t launch_nee_medium(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
-    return launch_nee_family<kWideAll>(NEE_PICK(k_nee_medium), NEE_PICK(k_nee_env_medium), NEE_PICK(k_nee_tiles_medium), NEE_PICK(k_nee_env_tiles_medium), p, lt, nl, npix,
-                                       cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium);
+// launch_lanes_t keys its static LdsMark on the type of `pick`, so every kernel arrives through a type of its own
+template <int FAMILY, bool ENV, bool TILED>
+struct NeePick {
+    template <class S>
+    auto operator()(S s) const { return k_nee<FAMILY, s.mode, s.block, ENV, TILED>; }
+};
+// the launch's value for an argument the instance has, NeeNone for one it has not
+template <bool ON, class T>
+static NeeArg<ON, T> nee_arg(const T& v) {
+    if constexpr (ON) return v;
+    else return NeeNone{};
 }
-#elif defined(PT_NEE_GRID_TU)
-hipError_t launch_nee_grid(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
-    return launch_nee_family<kWideAll>(NEE_PICK(k_nee_grid), NEE_PICK(k_nee_env_grid), NEE_PICK(k_nee_tiles_grid), NEE_PICK(k_nee_env_tiles_grid), p, lt, nl, npix,
-                                       cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium, nl.grid);
+template <int FAMILY, bool ENV, bool TILED>
+static hipError_t launch_nee_form(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t n, int cu_count, hipStream_t stream) {
+    using F = NeeHook<FAMILY, 0, ENV>;
+    const NeePick<FAMILY, ENV, TILED> pick;
+    const auto launch = [&](auto... a) {
+        if constexpr ((kNeeWide[FAMILY] >> (ENV + 2 * TILED) & 1) != 0) return launch_lanes_wide(pick, p, n, cu_count, stream, lt, a...);
+        else return launch_lanes(pick, p, n, cu_count, stream, lt, a...);
+    };
+    return launch(nee_arg<ENV>(nl.env ? *nl.env : EnvView{}), nee_arg<F::smooth>(nl.vn), nee_arg<F::textured>(nl.tv), nee_arg<F::coated>(nl.flags),
+                  nee_arg<F::lens>(nl.lens), nee_arg<F::lights>(nl.lights), nee_arg<F::medium>(nl.medium), nee_arg<F::grid>(nl.grid),
+                  nee_arg<F::interior>(nl.interior), nee_arg<F::ltree>(nl.ltree), nee_arg<!TILED>((long long)n));
 }
-#elif defined(PT_NEE_INTERIOR_TU)
-hipError_t launch_nee_interior(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
-    return launch_nee_family<kWideAll>(NEE_PICK(k_nee_interior), NEE_PICK(k_nee_env_interior), NEE_PICK(k_nee_tiles_interior), NEE_PICK(k_nee_env_tiles_interior), p, lt, nl,
-                                       npix, cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium, nl.grid, nl.interior);
+// the four kernels of one family: n is the pixels of the frame or, tiled, 64 work items per listed tile
+template <int FAMILY>
+static hipError_t launch_nee_family(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+    const int64_t n = nl.tiled ? (int64_t)p.n_tiles * 64 : npix;
+    if (nl.tiled) return nl.env ? launch_nee_form<FAMILY, true, true>(p, lt, nl, n, cu_count, stream) : launch_nee_form<FAMILY, false, true>(p, lt, nl, n, cu_count, stream);
+    return nl.env ? launch_nee_form<FAMILY, true, false>(p, lt, nl, n, cu_count, stream) : launch_nee_form<FAMILY, false, false>(p, lt, nl, n, cu_count, stream);
 }
-#elif defined(PT_NEE_LIGHTTREE_TU)
-hipError_t launch_nee_lighttree(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
-    return launch_nee_family<kWideAll>(NEE_PICK(k_nee_lighttree), NEE_PICK(k_nee_env_lighttree), NEE_PICK(k_nee_tiles_lighttree), NEE_PICK(k_nee_env_tiles_lighttree), p, lt, nl,
-                                       npix, cu_count, stream, nl.vn, nl.tv, nl.flags, nl.lens, nl.lights, nl.medium, nl.grid, nl.interior, nl.ltree);
+
+// The families from kNeeMedium on are each compiled in a translation unit of their own: pt_nee_medium.hip, pt_nee_grid.hip, pt_nee_interior.hip
+// and pt_nee_lighttree.hip include this file with PT_NEE_TU set to their family (PT_NEE_FAMILY_*, pt_internal.hpp) and get launch_nee_tu<PT_NEE_TU> only.  Compiled next to the
+// other families, the medium instances cost 48 of them two instructions in their uv fetch (the compiler no longer derives for a helper they
+// share that its triangle index is never negative; profiles/medium/README.md); each later family likewise, so that the ones before it compile
+// as they did before it existed
+template <int FAMILY>
+hipError_t launch_nee_tu(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream);
+#if defined(PT_NEE_TU)
+template <int FAMILY>
+hipError_t launch_nee_tu(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+    return launch_nee_family<FAMILY>(p, lt, nl, npix, cu_count, stream);
 }
+template hipError_t launch_nee_tu<PT_NEE_TU>(const RenderParams&, const NeeTable&, const NeeLaunch&, int64_t, int, hipStream_t);
+#else
+hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
+    t_lanes_block = 0;
+    hipError_t e = hipErrorInvalidValue;
+    switch (nl.family) {
+    case kNeePlain: e = launch_nee_family<kNeePlain>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeSmooth: e = launch_nee_family<kNeeSmooth>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeTex: e = launch_nee_family<kNeeTex>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeGlossy: e = launch_nee_family<kNeeGlossy>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeCoated: e = launch_nee_family<kNeeCoated>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeLens: e = launch_nee_family<kNeeLens>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeFrosted: e = launch_nee_family<kNeeFrosted>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeLights: e = launch_nee_family<kNeeLights>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeMedium: e = launch_nee_tu<kNeeMedium>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeGrid: e = launch_nee_tu<kNeeGrid>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeInterior: e = launch_nee_tu<kNeeInterior>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeLightTree: e = launch_nee_tu<kNeeLightTree>(p, lt, nl, npix, cu_count, stream); break;
+    }
+    if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit or in the family's own)
+    return e;
+}
+#endif
+
+#if defined(PT_NEE_TU) && PT_NEE_TU == PT_NEE_FAMILY_LIGHTTREE      // (pt_debug_light_tree_eval's kernel sits with the instances that make the same walks)
 // in: 7 floats per item {o, G, u0} and the tree-order light whose probability the weight walk returns (-1: none); out: 4 words per item {the
 // tree-order light the pick draws, bits(its P), bits(the weight walk's P of the target), 0}: the two walks as the instances above call them
 __global__ void __launch_bounds__(256) k_debug_light_tree(LightTreeView v, const float* __restrict__ in, const int32_t* __restrict__ target, long long n,
@@ -1311,48 +1105,6 @@ hipError_t launch_debug_light_tree(const LightTreeView& v, const float* in, cons
     hipLaunchKernelGGL(k_debug_light_tree, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, v, in, target, (long long)n, out);
     return hipGetLastError();
 }
-#else
-static hipError_t launch_nee_of_family(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
-    switch (nl.family) {
-    case kNeePlain:
-        return launch_nee_family<0>(NEE_PICK(k_nee), NEE_PICK(k_nee_env), NEE_PICK(k_nee_tiles), NEE_PICK(k_nee_env_tiles), p, lt, nl, npix, cu_count, stream);
-    case kNeeSmooth:
-        return launch_nee_family<kWideEnvTiles>(NEE_PICK(k_nee_smooth), NEE_PICK(k_nee_env_smooth), NEE_PICK(k_nee_tiles_smooth), NEE_PICK(k_nee_env_tiles_smooth), p, lt, nl, npix,
-                                    cu_count, stream, nl.vn);
-    // (k_nee_env_tex needs 3 VGPRs more than k_nee_env_smooth, which sits at the 128-VGPR cap of a 1,024-thread workgroup: the 512-thread
-    // treelet shape of k_nee_env_tiles_smooth keeps it out of scratch)
-    case kNeeTex:
-        return launch_nee_family<kWideEnv | kWideEnvTiles>(NEE_PICK(k_nee_tex), NEE_PICK(k_nee_env_tex), NEE_PICK(k_nee_tiles_tex), NEE_PICK(k_nee_env_tiles_tex), p, lt, nl, npix, cu_count,
-                                        stream, nl.vn, nl.tv);
-    case kNeeGlossy:
-        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_glossy), NEE_PICK(k_nee_env_glossy), NEE_PICK(k_nee_tiles_glossy), NEE_PICK(k_nee_env_tiles_glossy), p, lt, nl, npix,
-                                     cu_count, stream, nl.vn, nl.tv);
-    case kNeeCoated:
-        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_coated), NEE_PICK(k_nee_env_coated), NEE_PICK(k_nee_tiles_coated), NEE_PICK(k_nee_env_tiles_coated), p, lt, nl, npix,
-                                     cu_count, stream, nl.vn, nl.tv, nl.flags & 1);
-    case kNeeLens:
-        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_lens), NEE_PICK(k_nee_env_lens), NEE_PICK(k_nee_tiles_lens), NEE_PICK(k_nee_env_tiles_lens), p, lt, nl, npix, cu_count,
-                                     stream, nl.vn, nl.tv, nl.flags & 3, nl.lens);
-    case kNeeFrosted:
-        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_frosted), NEE_PICK(k_nee_env_frosted), NEE_PICK(k_nee_tiles_frosted), NEE_PICK(k_nee_env_tiles_frosted), p, lt, nl, npix,
-                                     cu_count, stream, nl.vn, nl.tv, nl.flags & 7, nl.lens);
-    case kNeeLights:
-        return launch_nee_family<kWideAll>(NEE_PICK(k_nee_lights), NEE_PICK(k_nee_env_lights), NEE_PICK(k_nee_tiles_lights), NEE_PICK(k_nee_env_tiles_lights), p, lt, nl, npix,
-                                     cu_count, stream, nl.vn, nl.tv, nl.flags & 15, nl.lens, nl.lights);
-    case kNeeMedium: return launch_nee_medium(p, lt, nl, npix, cu_count, stream);
-    case kNeeGrid: return launch_nee_grid(p, lt, nl, npix, cu_count, stream);
-    case kNeeInterior: return launch_nee_interior(p, lt, nl, npix, cu_count, stream);
-    case kNeeLightTree: return launch_nee_lighttree(p, lt, nl, npix, cu_count, stream);
-    }
-    return hipErrorInvalidValue;
-}
-hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl, int64_t npix, int cu_count, hipStream_t stream) {
-    t_lanes_block = 0;
-    const hipError_t e = launch_nee_of_family(p, lt, nl, npix, cu_count, stream);
-    if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit, in pt_nee_medium.hip's, pt_nee_grid.hip's, pt_nee_interior.hip's or pt_nee_lighttree.hip's)
-    return e;
-}
 #endif
-#undef NEE_PICK
 
 }  // namespace ptamd

@@ -1,5 +1,5 @@
-// pt_nee_grid.hip -- the grid instances of k_nee (k_nee_grid, k_nee_env_grid, k_nee_tiles_grid, k_nee_env_tiles_grid; pt_set_medium_density,
-// DESIGN.md section 5.20) and their launcher, launch_nee_grid: pt_nee.hip's one body, nee_frame, instantiated with GRID in a translation unit
-// of its own, as pt_nee_medium.hip is, so that the other nine families' instances compile exactly as they did before these existed.
-#define PT_NEE_GRID_TU 1
+// pt_nee_grid.hip -- the grid instances of k_nee (k_nee<kNeeGrid, ...>; pt_set_medium_density) and their launcher,
+// launch_nee_tu<kNeeGrid>: pt_nee.hip's one body, nee_frame, instantiated for the family in a translation unit of its own, as pt_nee_medium.hip is,
+// so that the other families' instances compile exactly as they did before these existed.
+#define PT_NEE_TU PT_NEE_FAMILY_GRID
 #include "pt_nee.hip"

@@ -1,7 +1,7 @@
 """The table of k_nee instances and the scenes that reach them (tests/test_nee_instances_host.py, tests/test_gpu_nee_instances.py;
 DESIGN.md section 5.18).  Importable without a device.
 
-pt_nee.hip compiles nine kernel families (NeeFamily, pt_internal.hpp), each in four forms (k_nee*, _env, _tiles, _env_tiles), each
+pt_nee.hip compiles nine kernel families (NeeFamily, pt_internal.hpp), each in four forms (k_nee<family, mode, block, ENV, TILED>: plain, env, tiles, env_tiles), each
 for four node modes: 144 device functions.  CELLS lists them with the scene that serves each and the workgroup size its launch must
 take; the rest of the module builds the two scenes, the ten configurations that select the families, and the node placements."""
 import functools
@@ -12,14 +12,14 @@ import numpy as np
 FAMILIES = ("plain", "smooth", "tex", "glossy", "coated", "lens", "frosted", "lights", "medium")      # stat "nee_family" 0..8
 FORMS = ("plain", "env", "tiles", "env_tiles")              # stat "nee_form" 0..3: bit 0 an environment is drawn, bit 1 tiled
 MODES = (0, 1, 2, 3)                                        # stat "node_mode": whole tree in LDS, BVH2 from global memory, treelet, 4-wide
-# launch_nee's SHAPES mask per family (kWidePlain = 1, kWideEnv = 2, kWideTiles = 4, kWideEnvTiles = 8: bit f is form f): the forms
-# that launch through launch_lanes_env_tiles_smooth, whose treelet shape has 512 threads, instead of launch_lanes, whose has 1,024
+# launch_nee's kNeeWide table per family (kWidePlain = 1, kWideEnv = 2, kWideTiles = 4, kWideEnvTiles = 8: bit f is form f): the forms
+# that launch through launch_lanes_wide, whose treelet shape has 512 threads, instead of launch_lanes, whose has 1,024
 WIDE_SHAPES = (0, 8, 2 | 8, 15, 15, 15, 15, 15, 15)
 SCENES_OF_MODE = {0: ("small",), 1: ("small", "mesh"), 2: ("mesh",), 3: ("small", "mesh")}
 
 
 def block_of(family, form, mode):
-    """the workgroup size of the instance's launch: the switch statements of launch_lanes and launch_lanes_env_tiles_smooth"""
+    """the workgroup size of the instance's launch: the switch statements of launch_lanes and launch_lanes_wide"""
     if mode in (1, 3):
         return 256
     if mode == 0:

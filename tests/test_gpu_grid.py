@@ -306,7 +306,7 @@ def test_absorption_through_two_layers(api, layers):
 
 # ---------------------------------------------------------------------------- 5: node modes
 def grid_block(mode):
-    """the 512-thread rule (launch_lanes_env_tiles_smooth): every form of the family takes it"""
+    """the 512-thread rule (launch_lanes_wide): every form of the family takes it"""
     return {0: 512, 1: 256, 2: 512, 3: 256}[mode]
 
 

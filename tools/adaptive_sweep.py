@@ -9,7 +9,7 @@ usage: python tools/adaptive_sweep.py scene=cornell|mesh100k [W=1920 H=1080] [mi
 metric / path / strategy / tonemapped go to Scene.render_adaptive (none given: the old entry); the variance metric switches option
 "moments" on.  With path=nee the uniform frames and the reference are render_nee at the same strategy; env=1 sets scenes.sun_and_sky()
 (only the NEE path draws it).  tiled_ab=1 also times, by HIP events (option "timing"), two launches of 32 samples over the whole frame:
-uniform render_nee (k_nee) against the rounds of an adaptive frame with min = max = 64 (k_nee_tiles).
+uniform render_nee (k_nee) against the rounds of an adaptive frame with min = max = 64 (its TILED instances).
 
 The reference is a uniform render of `ref` samples on its own context.  For every threshold: samples spent, wall time of the
 call (host clock around render_adaptive + sync, which includes the per-round synchronisation), the rounds with their active
@@ -123,7 +123,7 @@ def main():
             ti.render_adaptive(64, 64, 0.0, **ex)
             ti.sync()
             same = np.array_equal(un.read_colors().view(np.uint32), ti.read_colors().view(np.uint32))
-            print("tiled_ab %d: 2 x 32 samples, whole frame: k_nee %.2f ms, k_nee_tiles %.2f ms (HIP events), same bits: %s"
+            print("tiled_ab %d: 2 x 32 samples, whole frame: k_nee %.2f ms, k_nee TILED %.2f ms (HIP events), same bits: %s"
                   % (rep, un.stat("kernel_ms"), ti.stat("kernel_ms"), same))
             un.close()
             ti.close()

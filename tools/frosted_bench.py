@@ -4,7 +4,7 @@ usage: python tools/frosted_bench.py [W=1920 H=1080] [bounces=8] [spp=16] [reps=
 
 The Cornell box, render_nee(spp, "mis") through a lens (so that both frames run the same launch shape): wall clock around one launch and
 a sync, after one warm-up launch per context; `reps` launches each, the two contexts alternating (frosted: cornell_box(frosted=True) with
-the option on, k_nee_frosted; glass: cornell_box() on the lens-family kernels, k_nee_lens).  One JSON line on stdout."""
+the option on, k_nee<kNeeFrosted>; glass: cornell_box() on the lens-family kernels, k_nee<kNeeLens>).  One JSON line on stdout."""
 import json
 import sys
 import time

@@ -3,8 +3,8 @@
 usage: python tools/grid_bench.py [W=1920 H=1080] [bounces=8] [spp=16] [reps=7] [fog=0.001] [n=64]
 
 render_nee(spp, "mis"): wall clock around one launch and a sync, after one warm-up launch per context; `reps` launches each, the
-contexts alternating -- fog: cornell_box(fog=...) (k_nee_medium); unit: the same with a 1 x 1 x 1 grid of 1 (k_nee_grid computing the
-same frame: what the walk's set-up costs by itself); plume: the same with smoke_plume(n) (k_nee_grid walking n^3 voxels; the frame
+contexts alternating -- fog: cornell_box(fog=...) (k_nee<kNeeMedium>); unit: the same with a 1 x 1 x 1 grid of 1 (k_nee<kNeeGrid> computing the
+same frame: what the walk's set-up costs by itself); plume: the same with smoke_plume(n) (k_nee<kNeeGrid> walking n^3 voxels; the frame
 differs: the plume is mostly empty room with a dense column).  One JSON line on stdout."""
 import json
 import sys

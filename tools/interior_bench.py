@@ -5,7 +5,7 @@ usage: python tools/interior_bench.py [W=1920 H=1080] [bounces=8] [spp=16] [reps
 
 render_nee(spp, "mis"): wall clock around one launch and a sync, after one warm-up launch per context; `reps` launches each, the
 contexts alternating -- clear: cornell_box() (the family the scene took before: k_nee); null: the same with an all-zero interior on
-GLASS (k_nee_interior computing the same frame: what the family's run-time fields cost); tint: cornell_box(tint=(0.9, 0.5, 0.2))
+GLASS (k_nee<kNeeInterior> computing the same frame: what the family's run-time fields cost); tint: cornell_box(tint=(0.9, 0.5, 0.2))
 (absorption only: the same paths); wax: cornell_box(tint=..., wax=wax) (paths scatter inside the sphere: the frame and its path lengths
 differ).  One JSON line on stdout."""
 import json

@@ -3,7 +3,7 @@
 usage: python tools/lens_bench.py [W=1920 H=1080] [bounces=8] [spp=16] [reps=5] [aperture=25] [focus=1600]
 
 The Cornell box, render_nee(spp, "mis"): wall clock around one launch and a sync, after one warm-up launch per context; `reps` launches
-each, the two contexts alternating (lens on: k_nee_lens; lens off: the parent's k_nee, the parent's bits).  One JSON line on stdout."""
+each, the two contexts alternating (lens on: k_nee<kNeeLens>; lens off: the parent's k_nee, the parent's bits).  One JSON line on stdout."""
 import json
 import sys
 import time

@@ -4,8 +4,8 @@ power in its place, and by the quad plus one extra point light.
 usage: python tools/lights_bench.py [W=1920 H=1080] [bounces=8] [spp=16] [reps=5]
 
 render_nee(spp, "mis"): wall clock around one launch and a sync, after one warm-up launch per context; `reps` launches each, the
-contexts alternating -- quad: cornell_box() (k_nee); point: cornell_box(lamp="point"), no emitter, P_ana = 1 (k_nee_lights); quad_plus:
-cornell_box() with one more point light, P_ana = 0.5 (k_nee_lights).  For an A/B against another commit run it once per tree and
+contexts alternating -- quad: cornell_box() (k_nee); point: cornell_box(lamp="point"), no emitter, P_ana = 1 (k_nee<kNeeLights>); quad_plus:
+cornell_box() with one more point light, P_ana = 0.5 (k_nee<kNeeLights>).  For an A/B against another commit run it once per tree and
 alternate: PTAMD_TREE=<root of the other checkout, built> selects the package the script imports (the default is this tree; the symbols
 differ between commits, so PTAMD_LIB alone is not enough).  A tree from before pt_set_lights runs the quad context only.  One JSON
 line on stdout."""

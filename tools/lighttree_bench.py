@@ -5,7 +5,7 @@ usage: python tools/lighttree_bench.py [W=1920 H=1080] [bounces=4] [spp=16] [rep
 
 render_nee(spp, "mis") with option moments: wall clock around one launch and a sync, after one warm-up launch per context; `reps` launches
 each, the two contexts alternating -- off: many_lights(lamps) with the table's cdf (the family the scene took before: k_nee); on: the same
-with option light_tree (k_nee_lighttree).  variance: the mean over the pixels of Scene.read_variance() after the last launch (the variance
+with option light_tree (k_nee<kNeeLightTree>).  variance: the mean over the pixels of Scene.read_variance() after the last launch (the variance
 of the pixel's mean luminance at `spp` samples).  build=1: the wall clock of the first Scene.debug_light_tree() on host-only contexts
 holding 2, 512 and 100,000 emitting triangles (the light table and the tree; the scene's own upload is not in it).  One JSON line on
 stdout."""

@@ -3,8 +3,8 @@
 usage: python tools/medium_bench.py [W=1920 H=1080] [bounces=8] [spp=16] [reps=5] [fog=0.001]
 
 render_nee(spp, "mis"): wall clock around one launch and a sync, after one warm-up launch per context; `reps` launches each, the
-contexts alternating -- clear: cornell_box() (k_nee); far: the same with a medium whose box the scene never enters (k_nee_medium doing
-k_nee's work: what the medium instances cost by themselves); fog: cornell_box(fog=...), the room filled wall to wall (k_nee_medium with
+contexts alternating -- clear: cornell_box() (k_nee); far: the same with a medium whose box the scene never enters (k_nee<kNeeMedium> doing
+k_nee's work: what the medium instances cost by themselves); fog: cornell_box(fog=...), the room filled wall to wall (k_nee<kNeeMedium> with
 scatter vertices).  For an A/B against another commit run it once per tree and alternate: PTAMD_TREE=<root of the other checkout,
 built> selects the package the script imports.  A tree from before pt_set_medium runs the clear context only.  One JSON line on
 stdout."""
