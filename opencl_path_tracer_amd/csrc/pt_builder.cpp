@@ -1149,11 +1149,15 @@ static int build_on_device(pt_context* ctx, bool* done) {
         clk.lap("lbvh_build");
     }
     stage_free(&st);
-    auto drop = [&]() { (void)hipFree(r.d_nodes); (void)hipFree(r.d_tris); (void)hipFree(r.d_meta); (void)hipFree(r.d_orig); };
-    if (!sah && r.depth + 5 > kStackEntries) {  // deeper than the traversal stack: let the host builder do it
-        drop();
-        return PT_OK;
-    }
+    // the builder's arrays have an owner from here on: every return below frees what the context has not taken
+    DeviceArray<float4> d_nodes, d_tris;
+    DeviceArray<TriMeta> d_meta;
+    DeviceArray<int32_t> d_orig;
+    d_nodes.adopt(r.d_nodes, (size_t)r.n_nodes * (sizeof(Node64) / sizeof(float4)));
+    d_tris.adopt(r.d_tris, (size_t)n * (sizeof(TriPacket) / sizeof(float4)));
+    d_meta.adopt(r.d_meta, (size_t)n);
+    d_orig.adopt(r.d_orig, (size_t)n);
+    if (!sah && r.depth + 5 > kStackEntries) return PT_OK;      // deeper than the traversal stack: let the host builder do it
     // The device arrays are final but for the list's nf slots in front, which are written here (leaf references already count
     // from behind them).  The host keeps the nodes (SAH top, 4-wide collapse, debug getters) and the order; packets and meta
     // of the tree's triangles stay on the device until a debug getter asks for them (host_packets_stale).
@@ -1161,8 +1165,8 @@ static int build_on_device(pt_context* ctx, bool* done) {
     ctx->orig.resize((size_t)n);
     ctx->packets.assign((size_t)std::max(nf, 1), TriPacket());
     ctx->meta.assign((size_t)std::max(nf, 1), TriMeta());
-    hipError_t e = hipMemcpy(ctx->nodes.data(), r.d_nodes, sizeof(Node64) * (size_t)r.n_nodes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(ctx->orig.data() + nf, reinterpret_cast<int32_t*>(r.d_orig) + nf, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(ctx->nodes.data(), d_nodes, sizeof(Node64) * (size_t)r.n_nodes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(ctx->orig.data() + nf, d_orig + nf, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost);
     for (int k = 0; k < nf; ++k) {
         const pt_triangle& t = ctx->tris[(size_t)flat[(size_t)k]];
         float* v = ctx->packets[(size_t)k].v;
@@ -1174,9 +1178,9 @@ static int build_on_device(pt_context* ctx, bool* done) {
         ctx->meta[(size_t)k].mati = t.mati;
         ctx->orig[(size_t)k] = flat[(size_t)k];
     }
-    if (e == hipSuccess && nf > 0) e = hipMemcpy(r.d_tris, ctx->packets.data(), sizeof(TriPacket) * (size_t)nf, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nf > 0) e = hipMemcpy(r.d_meta, ctx->meta.data(), sizeof(TriMeta) * (size_t)nf, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { drop(); return fail(ctx, PT_EHIP, std::string("device BVH download: ") + hipGetErrorString(e)); }
+    if (e == hipSuccess && nf > 0) e = hipMemcpy(d_tris, ctx->packets.data(), sizeof(TriPacket) * (size_t)nf, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nf > 0) e = hipMemcpy(d_meta, ctx->meta.data(), sizeof(TriMeta) * (size_t)nf, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(ctx, PT_EHIP, std::string("device BVH download: ") + hipGetErrorString(e));
     if (sah) {
         // The SAH tree arrives in preorder: a child's index is larger than its parent's and every leaf lies inside the packed
         // triangles behind the list.  Checked before any host code walks the tree (a malformed tree must fail here, loudly,
@@ -1197,10 +1201,9 @@ static int build_on_device(pt_context* ctx, bool* done) {
             }
             if (!good) ok.store(false);
         });
-        if (!ok.load()) { drop(); return fail(ctx, PT_EHIP, "internal: the device SAH builder returned a malformed tree"); }
+        if (!ok.load()) return fail(ctx, PT_EHIP, "internal: the device SAH builder returned a malformed tree");
     }
-    (void)hipFree(r.d_orig);
-    r.d_orig = nullptr;
+    d_orig.reset();
     ctx->host_packets_stale = true;
     ctx->bvh_depth = sah ? r.depth : r.depth + 1;
     ctx->n_flat = nf;
@@ -1208,21 +1211,18 @@ static int build_on_device(pt_context* ctx, bool* done) {
     const bool retopped = !sah && sah_top_rebuild(ctx, ctx->lbvh_cluster);
     clk.lap("SAH top over clusters");
     bool wide_done = false;
-    int rc = plan_node_placement(ctx, retopped ? nullptr : r.d_nodes, &wide_done);
+    int rc = plan_node_placement(ctx, retopped ? nullptr : d_nodes.get(), &wide_done);
     clk.lap("node placement + 4-wide nodes");
-    if (rc != PT_OK) { drop(); return rc; }
+    if (rc != PT_OK) return rc;
     if (retopped) ctx->bvh_depth = ctx->interior_depth + 1;
     ctx->shaderec_dirty = true;
-    if (ctx->d_tris) (void)hipFree(ctx->d_tris);
-    if (ctx->d_meta) (void)hipFree(ctx->d_meta);
-    ctx->d_tris = r.d_tris;
-    ctx->d_meta = r.d_meta;
+    ctx->d_tris = std::move(d_tris);
+    ctx->d_meta = std::move(d_meta);
     if (retopped) {               // the nodes were recomposed on the host
-        (void)hipFree(r.d_nodes);
+        d_nodes.reset();
         if ((rc = upload_vec(ctx, &ctx->d_nodes, ctx->nodes.data(), sizeof(Node64) * ctx->nodes.size())) != PT_OK) return rc;
     } else {
-        if (ctx->d_nodes) (void)hipFree(ctx->d_nodes);
-        ctx->d_nodes = r.d_nodes;
+        ctx->d_nodes = std::move(d_nodes);
         if (ctx->treelet_nodes > 0) PT_HIP(ctx, hipMemcpy(ctx->d_nodes, ctx->nodes.data(), sizeof(Node64) * ctx->nodes.size(), hipMemcpyHostToDevice));
     }
     if (!wide_done && (rc = upload_vec(ctx, &ctx->d_nodes4, ctx->nodes4.data(), sizeof(Node4q) * ctx->nodes4.size())) != PT_OK) return rc;

@@ -8,6 +8,7 @@
 // Internal: not part of the ABI.  (`using namespace ptamd` below is deliberate: these files ARE the library.)
 #pragma once
 
+#include "pt_devbuf.hpp"
 #include "pt_internal.hpp"
 
 #include <algorithm>
@@ -31,6 +32,24 @@ namespace ptamd {
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
 };
+// Device memory.  Every device array a context holds is a DeviceArray field of pt_context: it is freed when the context is deleted
+// (pt_destroy synchronises the device first), and replaced or grown through replace / reserve / move-assignment, never by hand.  A
+// failed allocation leaves the field empty and its hipError_t in HipAlloc::last (PT_ALLOC below reports it).
+#pragma GCC visibility push(hidden)
+struct HipAlloc {
+    static inline thread_local hipError_t last = hipSuccess;
+    static bool alloc(void** p, size_t bytes) { return (last = hipMalloc(p, bytes)) == hipSuccess; }
+    static void free(void* p) { (void)hipFree(p); }
+};
+template <class T>
+using DeviceArray = DevBuf<T, HipAlloc>;
+// the untyped temporary of the debug entry points and the staging copies: at least 16 bytes, freed on every exit path
+struct DeviceBuf {
+    void* p = nullptr;
+    ~DeviceBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
+};
+#pragma GCC visibility pop
 }  // namespace ptamd
 
 struct pt_context {
@@ -44,8 +63,8 @@ struct pt_context {
 
     // ---- frame assembly (pt_comm.hip)
     void* comm = nullptr;          // ncclComm_t
-    float4* d_gathered = nullptr;  // world x slab_pix
-    float4* d_frame = nullptr;     // W x H
+    DeviceArray<float4> d_gathered;  // world x slab_pix
+    DeviceArray<float4> d_frame;     // W x H
     uint64_t render_epoch = 0;     // bumped by every call that writes colors
     uint64_t frame_epoch = ~0ull;  // render_epoch at the last pt_gather_frame: d_frame is served only while they are equal
 
@@ -77,29 +96,32 @@ struct pt_context {
     uint64_t fpair_rot = 0;     // two bits per listed triangle: cyclic rotation of its corners in the list's TEST copy (0: as authored)
 
     // ---- device buffers
-    float4* d_nodes = nullptr;
-    float4* d_nodes4 = nullptr;
-    uint32_t* d_stack_ovf = nullptr;   // kNodesWide: stack entries past the LDS part, [entry][lane of the grid]
+    DeviceArray<float4> d_nodes;
+    DeviceArray<float4> d_nodes4;
+    DeviceArray<uint32_t> d_stack_ovf;   // kNodesWide: stack entries past the LDS part, [entry][lane of the grid]
     size_t stack_ovf_lanes = 0;
-    float4* d_tris = nullptr;
-    TriMeta* d_meta = nullptr;
-    pt_material* d_mats = nullptr;
+    DeviceArray<float4> d_tris;
+    DeviceArray<TriMeta> d_meta;
+    DeviceArray<pt_material> d_mats;
     // per-triangle shading records (ShadeRec): built from d_tris, d_meta and d_mats at the next render launch that reads them after
     // any of the three was written (every writer sets shaderec_dirty; ensure_shade_records, pt_launch.cpp)
-    ShadeRec* d_shaderec = nullptr;
-    size_t shaderec_cap = 0;           // records d_shaderec has room for
+    DeviceArray<ShadeRec> d_shaderec;
     bool shaderec_dirty = true;
     int32_t mats_on_device = 0;        // materials d_mats holds (ctx->mats can run ahead of it until the next pt_upload_materials)
+    // the framebuffer: the kernels read d_rnds / d_colors, which point into rnds_own / colors_own until pt_bind_framebuffer binds the
+    // caller's arrays; a bound (borrowed) array is never freed here, and its owner is empty from then on
     int32_t* d_rnds = nullptr;
     float4* d_colors = nullptr;
-    pt_ray* d_rays = nullptr;
-    float4* d_ldr = nullptr;
-    unsigned long long* d_stats = nullptr;
+    DeviceArray<int32_t> rnds_own;
+    DeviceArray<float4> colors_own;
+    DeviceArray<pt_ray> d_rays;
+    DeviceArray<float4> d_ldr;
+    DeviceArray<unsigned long long> d_stats;
     // wavefront variant: path state + queues (allocated on first use)
-    float4* d_wf_state = nullptr;   // per local pixel: 4 float4 worth of path factors + colour (5 x 12 B), 8 + 4 float4 of ray streams (rsA, rsB; rsC), 2 float2 of hits
-    int32_t* d_wf_queues = nullptr; // 3 x npix int32 (class queues)
+    DeviceArray<float4> d_wf_state;   // per local pixel: 4 float4 worth of path factors + colour (5 x 12 B), 8 + 4 float4 of ray streams (rsA, rsB; rsC), 2 float2 of hits
+    DeviceArray<int32_t> d_wf_queues; // 3 x npix int32 (class queues)
     std::vector<float> cost_boxes;  // 6 floats per complex object (wavefront cost classes)
-    uint32_t* d_wf_counters = nullptr;   // kWfMaxChains x (kWfMaxBounces + 4) rows
+    DeviceArray<uint32_t> d_wf_counters;   // kWfMaxChains x (kWfMaxBounces + 4) rows
     hipStream_t wf_stream[kWfMaxChains] = {};   // chains 1.. of the wavefront variant (chain 0 runs on `stream`)
     hipEvent_t wf_event[kWfMaxChains] = {};
     int poll_timeout_ms = 10000;         // chained passes: a wave gives a tile's previous pass this long before it reports the hand-over lost
@@ -107,7 +129,6 @@ struct pt_context {
     bool counters_suspect = false;
     bool launched_since_check = false;   // a persistent launch has been enqueued since the work counter's error word was last read       // a launch failed or lost a hand-over: word 0 / 1 of d_tile_counter may not be back at zero
     int wf_streams = -1;                 // option wf_streams: chains of the wavefront variant (-1: kWfDefaultChains)
-    bool own_rnds = true, own_colors = true;
     hipStream_t stream = nullptr;
 
     int32_t current_sample = 0;  // main.cpp:28
@@ -126,22 +147,22 @@ struct pt_context {
     double bvh_build_ms = 0.0;
     int cu_count = 256;
     int persistent = 1;   // 1: megakernel waves pull tiles from a counter (grid = what fits the chip)
-    uint32_t* d_tile_counter = nullptr;
-    uint32_t* d_tile_done = nullptr;
-    uint32_t* d_tile_cost = nullptr;   // count_work: per tile, cycles / 64 its waves spent on it in the last launch (pt_debug_tile_cost)
+    DeviceArray<uint32_t> d_tile_counter;
+    DeviceArray<uint32_t> d_tile_done;
+    DeviceArray<uint32_t> d_tile_cost;   // count_work: per tile, cycles / 64 its waves spent on it in the last launch (pt_debug_tile_cost)
     // adaptive frames (pt_render_adaptive; allocated on first use): per local pixel the colour at half the tile's samples; per tile of
     // the local frame the samples rendered, the last noise estimate and the active flag; the active tiles in ascending order + their count
-    float4* d_adapt_snap = nullptr;
-    int32_t* d_adapt_spp = nullptr;
-    float* d_adapt_err = nullptr;
-    uint8_t* d_adapt_active = nullptr;
-    int32_t* d_adapt_list = nullptr;   // n_tiles entries, then the count word
+    DeviceArray<float4> d_adapt_snap;
+    DeviceArray<int32_t> d_adapt_spp;
+    DeviceArray<float> d_adapt_err;
+    DeviceArray<uint8_t> d_adapt_active;
+    DeviceArray<int32_t> d_adapt_list;   // n_tiles entries, then the count word
     int32_t* h_adapt_count = nullptr;  // pinned
     bool adaptive_frame = false;       // an adaptive frame is held: pt_render / pt_trace_rays / pt_render_adaptive refuse until pt_set_current_sample(0)
     // guide buffers (pt_render_aovs) and the a-trous filter (pt_denoise), allocated on first use: per local pixel albedo_rgbm then
     // normal_depth (2 x npix float4); two ping-pong frames (2 x npix float4); d_denoised points at the one the last pt_denoise left
-    float4* d_aov = nullptr;
-    float4* d_dn = nullptr;
+    DeviceArray<float4> d_aov;
+    DeviceArray<float4> d_dn;
     float4* d_denoised = nullptr;
     bool aov_valid = false;            // pt_render_aovs ran and no pt_upload_triangles / pt_upload_materials has made its guides stale
     bool aov_shaded = false;           // the guides are shaded ones (pt_render_aovs_ex, PT_AOV_SHADED): the authoring calls for vertex normals,
@@ -150,7 +171,7 @@ struct pt_context {
     // (note_moments); the variance read-out (pt_read_variance, pt_denoise_variance) lives in d_variance, allocated on first use
     int moments = 0;
     bool moments_valid = false;
-    float* d_variance = nullptr;
+    DeviceArray<float> d_variance;
     // temporal accumulation (pt_temporal_accumulate).  Every frame start bumps frame_serial and records the frame's camera (note_frame;
     // frame_cam_same while every launch of the frame used it byte for byte); pt_render_aovs records its camera and bumps aov_serial.
     // Two history sets in d_temporal, allocated on first use: per set and local pixel {r, g, b, m2}, {nx, ny, nz, depth} of the guides
@@ -161,8 +182,8 @@ struct pt_context {
     bool frame_cam_same = false;
     uint64_t aov_serial = 0;
     pt_camera aov_cam = {};
-    float4* d_temporal = nullptr;
-    float* d_temporal_var = nullptr;
+    DeviceArray<float4> d_temporal;
+    DeviceArray<float> d_temporal_var;
     int temporal_out = -1;
     bool temporal_history = false;      // set temporal_out is the history of the next accumulate (dropped when the scene is uploaded)
     pt_camera temporal_cam = {};        // the camera of that history
@@ -174,9 +195,9 @@ struct pt_context {
     std::vector<float> nee_cdf;
     std::vector<float> nee_pdf_area;
     bool nee_valid = false;
-    int32_t* d_nee_tri = nullptr;
-    float* d_nee_cdf = nullptr;
-    float* d_nee_pdf_area = nullptr;
+    DeviceArray<int32_t> d_nee_tri;
+    DeviceArray<float> d_nee_cdf;
+    DeviceArray<float> d_nee_pdf_area;
     bool nee_uploaded = false;         // the device copies hold the current table
     std::vector<double> nee_phi, nee_area;     // per light, in table order: area x (E.r + E.g + E.b) and the area, as the table summed them
     // the light hierarchy over that table (option light_tree, pt_lighttree.cpp; pinned in include/pt_api.h): built on the host at first use
@@ -188,10 +209,10 @@ struct pt_context {
     std::vector<float> lt_inv_area;
     int32_t lt_depth = 0;
     bool lt_valid = false, lt_uploaded = false;
-    float4* d_lt_nodes = nullptr;
-    int32_t* d_lt_tri = nullptr;
-    int32_t* d_lt_slot = nullptr;
-    float* d_lt_inv_area = nullptr;
+    DeviceArray<float4> d_lt_nodes;
+    DeviceArray<int32_t> d_lt_tri;
+    DeviceArray<int32_t> d_lt_slot;
+    DeviceArray<float> d_lt_inv_area;
     // the environment of pt_render_nee (pt_set_environment, pt_env.cpp): the map with p_env = P(texel) / Omega(row) in .w, the row
     // marginal cdf [h] and the per-row column cdfs [h][w]; env_dist: some weight is non-zero.  Device copies made by pt_set_environment.
     bool env_set = false, env_dist = false;
@@ -199,17 +220,16 @@ struct pt_context {
     float env_scale = 1.0f, env_yaw = 0.0f, env_select = 0.5f;   // yaw in radians
     std::vector<float4> env_texels;
     std::vector<float> env_row_cdf, env_col_cdf;
-    float4* d_env_texels = nullptr;
-    float* d_env_row_cdf = nullptr;
-    float* d_env_col_cdf = nullptr;
+    DeviceArray<float4> d_env_texels;
+    DeviceArray<float> d_env_row_cdf;
+    DeviceArray<float> d_env_col_cdf;
     // smooth shading (option smooth_normals, pt_set_vertex_normals; pinned in include/pt_api.h): 9 floats per add-order triangle as
     // recorded, all zero where a triangle has none (shorter than tris: the rest has none).  d_vnormals: 3 float4 per packed triangle,
     // packed by k_pack_vertex_normals (pt_smooth.hip) at the first smooth launch after the normals or the uploaded triangles changed
     int smooth_normals = 0;
     std::vector<float> vnormals;
     bool vnormals_dirty = true;
-    float4* d_vnormals = nullptr;
-    size_t vnormals_cap = 0;           // packed triangles d_vnormals has room for
+    DeviceArray<float4> d_vnormals;
     // albedo textures (option textures, pt_add_texture / pt_set_vertex_uvs / pt_set_material_texture; pinned in include/pt_api.h).
     // Host: every texture's texels back to back (8 B each: three halves r g b and 16 zero bits) with one descriptor per texture, the
     // binding per material (-1: none; shorter than mats: the rest has none) and 6 floats per add-order triangle (NaN where a triangle
@@ -222,11 +242,10 @@ struct pt_context {
     std::vector<int32_t> mat_tex;
     std::vector<float> vuvs;
     bool tex_dirty = true, vuvs_dirty = true;      // textures / bindings / materials; uvs / triangles
-    uint2* d_tex_texels = nullptr;
-    TexDesc* d_tex_desc = nullptr;
-    int32_t* d_mat_tex = nullptr;
-    float4* d_vuvs = nullptr;
-    size_t vuvs_cap = 0;               // packed triangles d_vuvs has room for
+    DeviceArray<uint2> d_tex_texels;
+    DeviceArray<TexDesc> d_tex_desc;
+    DeviceArray<int32_t> d_mat_tex;
+    DeviceArray<float4> d_vuvs;
     int obj_textures_loaded = 0, obj_textures_skipped = 0;      // map_Kd lines of the last pt_add_obj
     // rough metal (option glossy; pinned in include/pt_api.h): material type 4 is a GGX lobe vertex in pt_render_nee.  The glossy k_nee
     // instances run only when the option is on AND the materials uploaded last hold a type-4 one; every other frame is today's launch
@@ -252,8 +271,8 @@ struct pt_context {
     std::vector<float> lights_rec, lights_cdf, lights_plight;
     float lights_select = 0.5f;
     bool lights_pickable = false;
-    float4* d_lights_rec = nullptr;
-    float* d_lights_cdf = nullptr;
+    DeviceArray<float4> d_lights_rec;
+    DeviceArray<float> d_lights_cdf;
     // the homogeneous medium (pt_set_medium, pt_medium.cpp; pinned in include/pt_api.h): the record as validated (the defaults when none is
     // set).  Only while sigma_t > 0 do pt_render_nee and the NEE path of pt_render_adaptive_ex launch the medium instances of k_nee, and do
     // the other paths refuse.  Not part of the scene: uploads keep it
@@ -265,7 +284,7 @@ struct pt_context {
     std::vector<float> grid;
     int32_t grid_n[3] = {0, 0, 0};
     bool grid_set = false;
-    float* d_grid = nullptr;
+    DeviceArray<float> d_grid;
     // interiors of dielectrics (pt_set_material_interior, pt_interior.cpp): per material index the record and whether one is bound, kept like a
     // texture binding -- across uploads, on a host-only context too, not part of the scene.  interior_live counts the bindings; the device table
     // (two float4 per material on the device, bound only where its type is 2 or 6) is rebuilt by interior_prepare when a binding or the
@@ -274,7 +293,7 @@ struct pt_context {
     std::vector<uint8_t> interior_bound;
     int32_t interior_live = 0;
     bool interior_dirty = true;
-    float4* d_interior = nullptr;
+    DeviceArray<float4> d_interior;
     int chunk_taper = -1;  // option chunk_taper: shortest pass of a launch whose last passes taper off (0: all passes chunk_spp long; -1 default)
     int chunk_spp = -1;   // persistent megakernel work items: > 0 (pass, tile) items of that many samples, 0 whole
                           // tiles, -1 automatic (4 when the context has clearly more tiles than resident waves)
@@ -375,6 +394,12 @@ int host_threads(const pt_context* ctx);                        // threads of th
         hipError_t e_ = (call);                                                             \
         if (e_ != hipSuccess)                                                               \
             return fail(ctx, PT_EHIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+// a DeviceArray allocation (reserve / replace) that must succeed
+#define PT_ALLOC(ctx, call)                                                                 \
+    do {                                                                                    \
+        if (!(call))                                                                        \
+            return fail(ctx, PT_EHIP, std::string(#call) + ": " + hipGetErrorString(HipAlloc::last)); \
     } while (0)
 
 // a render launch of samples [first_sample, ...) through cam was enqueued: a frame starts at sample 0, and stays valid for pt_read_variance
@@ -515,16 +540,31 @@ int time_end(pt_context* ctx, EventPair* ep);
 int time_collect(pt_context* ctx);
 int sync_and_check(pt_context* ctx);
 inline int32_t local_tiles(const pt_context* c) { return ((c->W + 7) / 8) * ((c->local_rows + 7) / 8); }
+#pragma GCC visibility push(hidden)
+// `bytes` of src in a fresh allocation of *buf (what it held is freed first)
 template <class T>
-int upload_vec(pt_context* ctx, T** dptr, const void* src, size_t bytes) {
-    if (*dptr) { PT_HIP(ctx, hipFree(*dptr)); *dptr = nullptr; }
-    PT_HIP(ctx, hipMalloc((void**)dptr, std::max<size_t>(bytes, 64)));
+int upload_vec(pt_context* ctx, DeviceArray<T>* buf, const void* src, size_t bytes) {
+    PT_ALLOC(ctx, buf->replace((std::max<size_t>(bytes, 64) + sizeof(T) - 1) / sizeof(T)));
     // an (almost) empty array still has one readable, all-zero record: a zero packet can never be
     // hit, so a leaf reference into an empty scene (the wrapped root's ~0) stays harmless
-    if (bytes < 64) PT_HIP(ctx, hipMemset(*dptr, 0, 64));
-    if (bytes) PT_HIP(ctx, hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice));
+    if (bytes < 64) PT_HIP(ctx, hipMemset(buf->get(), 0, 64));
+    if (bytes) PT_HIP(ctx, hipMemcpy(buf->get(), src, bytes, hipMemcpyHostToDevice));
     return PT_OK;
 }
+// The round trip of a debug entry point: in_bytes of `in` to the device, launch(d_in, d_out) on the context's stream, out_bytes back
+template <class F>
+int debug_round_trip(pt_context* ctx, const void* in, size_t in_bytes, void* out, size_t out_bytes, F launch) {
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceBuf d_in, d_out;
+    PT_HIP(ctx, d_in.alloc(in_bytes));
+    PT_HIP(ctx, d_out.alloc(out_bytes));
+    PT_HIP(ctx, hipMemcpy(d_in.p, in, in_bytes, hipMemcpyHostToDevice));
+    PT_HIP(ctx, launch(d_in.p, d_out.p));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+#pragma GCC visibility pop
 
 // kNodesWide: room for the stack entries past the LDS part, for every lane of the largest grid a traversal kernel of
 // this context is launched with (256-thread workgroups: persistent <= 6 per CU, wf_intersect 2 x 8 per CU, the debug

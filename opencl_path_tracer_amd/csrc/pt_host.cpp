@@ -191,11 +191,13 @@ int pt_create_tiled(int device, int32_t width, int32_t height, int32_t rank, int
     ctx->has_device = true;
     const size_t np = (size_t)std::max<int64_t>(ctx->npix, 1);
     const size_t nslab = (size_t)std::max<int64_t>(ctx->slab_pix, 1);      // colors is this rank's slab of the all-gather
-    if ((e = hipMalloc((void**)&ctx->d_rays, sizeof(pt_ray) * np)) != hipSuccess) return bail("hipMalloc(rays)", e);      // main.cpp:508
-    if ((e = hipMalloc((void**)&ctx->d_rnds, sizeof(int32_t) * np)) != hipSuccess) return bail("hipMalloc(rnds)", e);     // main.cpp:509
-    if ((e = hipMalloc((void**)&ctx->d_colors, sizeof(float4) * nslab)) != hipSuccess) return bail("hipMalloc(colors)", e);  // main.cpp:520
-    if ((e = hipMalloc((void**)&ctx->d_stats, sizeof(unsigned long long) * kStatCols * kStatRows)) != hipSuccess) return bail("hipMalloc(stats)", e);
-    if ((e = hipMalloc((void**)&ctx->d_tile_counter, sizeof(uint32_t) * kTileCounterWords)) != hipSuccess) return bail("hipMalloc(tile counter)", e);
+    if (!ctx->d_rays.replace(np)) return bail("hipMalloc(rays)", HipAlloc::last);                                      // main.cpp:508
+    if (!ctx->rnds_own.replace(np)) return bail("hipMalloc(rnds)", HipAlloc::last);                                    // main.cpp:509
+    if (!ctx->colors_own.replace(nslab)) return bail("hipMalloc(colors)", HipAlloc::last);                             // main.cpp:520
+    ctx->d_rnds = ctx->rnds_own;
+    ctx->d_colors = ctx->colors_own;
+    if (!ctx->d_stats.replace((size_t)kStatCols * kStatRows)) return bail("hipMalloc(stats)", HipAlloc::last);
+    if (!ctx->d_tile_counter.replace(kTileCounterWords)) return bail("hipMalloc(tile counter)", HipAlloc::last);
     if ((e = hipMemset(ctx->d_tile_counter, 0, sizeof(uint32_t) * kTileCounterWords)) != hipSuccess) return bail("hipMemset", e);      // zeroed ONCE: the last wave of a launch leaves it zero (k_render)
     if ((e = hipMemset(ctx->d_rays, 0, sizeof(pt_ray) * np)) != hipSuccess) return bail("hipMemset", e);
     if ((e = hipMemset(ctx->d_colors, 0, sizeof(float4) * nslab)) != hipSuccess) return bail("hipMemset", e);
@@ -220,63 +222,14 @@ void pt_destroy(pt_context* ctx) {
         (void)hipSetDevice(ctx->device);
         (void)hipDeviceSynchronize();
         for (auto& e : ctx->events) { if (e.a) (void)hipEventDestroy(e.a); if (e.b) (void)hipEventDestroy(e.b); }
-        if (ctx->d_nodes) (void)hipFree(ctx->d_nodes);
-        if (ctx->d_nodes4) (void)hipFree(ctx->d_nodes4);
-        if (ctx->d_stack_ovf) (void)hipFree(ctx->d_stack_ovf);
-        if (ctx->d_tris) (void)hipFree(ctx->d_tris);
-        if (ctx->d_meta) (void)hipFree(ctx->d_meta);
-        if (ctx->d_mats) (void)hipFree(ctx->d_mats);
-        if (ctx->d_shaderec) (void)hipFree(ctx->d_shaderec);
-        if (ctx->d_vnormals) (void)hipFree(ctx->d_vnormals);
-        if (ctx->d_tex_texels) (void)hipFree(ctx->d_tex_texels);
-        if (ctx->d_tex_desc) (void)hipFree(ctx->d_tex_desc);
-        if (ctx->d_mat_tex) (void)hipFree(ctx->d_mat_tex);
-        if (ctx->d_vuvs) (void)hipFree(ctx->d_vuvs);
-        if (ctx->d_rays) (void)hipFree(ctx->d_rays);
-        if (ctx->d_ldr) (void)hipFree(ctx->d_ldr);
-        if (ctx->d_stats) (void)hipFree(ctx->d_stats);
-        if (ctx->d_tile_counter) (void)hipFree(ctx->d_tile_counter);
-        if (ctx->d_tile_done) (void)hipFree(ctx->d_tile_done);
-        if (ctx->d_tile_cost) (void)hipFree(ctx->d_tile_cost);
-        if (ctx->d_adapt_snap) (void)hipFree(ctx->d_adapt_snap);
-        if (ctx->d_adapt_spp) (void)hipFree(ctx->d_adapt_spp);
-        if (ctx->d_adapt_err) (void)hipFree(ctx->d_adapt_err);
-        if (ctx->d_adapt_active) (void)hipFree(ctx->d_adapt_active);
-        if (ctx->d_adapt_list) (void)hipFree(ctx->d_adapt_list);
-        if (ctx->h_adapt_count) (void)hipHostFree(ctx->h_adapt_count);
-        if (ctx->d_aov) (void)hipFree(ctx->d_aov);
-        if (ctx->d_dn) (void)hipFree(ctx->d_dn);
-        if (ctx->d_variance) (void)hipFree(ctx->d_variance);
-        if (ctx->d_temporal) (void)hipFree(ctx->d_temporal);
-        if (ctx->d_temporal_var) (void)hipFree(ctx->d_temporal_var);
-        if (ctx->d_nee_tri) (void)hipFree(ctx->d_nee_tri);
-        if (ctx->d_nee_cdf) (void)hipFree(ctx->d_nee_cdf);
-        if (ctx->d_nee_pdf_area) (void)hipFree(ctx->d_nee_pdf_area);
-        if (ctx->d_env_texels) (void)hipFree(ctx->d_env_texels);
-        if (ctx->d_env_row_cdf) (void)hipFree(ctx->d_env_row_cdf);
-        if (ctx->d_env_col_cdf) (void)hipFree(ctx->d_env_col_cdf);
-        if (ctx->d_lights_rec) (void)hipFree(ctx->d_lights_rec);
-        if (ctx->d_lights_cdf) (void)hipFree(ctx->d_lights_cdf);
-        if (ctx->d_grid) (void)hipFree(ctx->d_grid);
-        if (ctx->d_interior) (void)hipFree(ctx->d_interior);
-        if (ctx->d_lt_nodes) (void)hipFree(ctx->d_lt_nodes);
-        if (ctx->d_lt_tri) (void)hipFree(ctx->d_lt_tri);
-        if (ctx->d_lt_inv_area) (void)hipFree(ctx->d_lt_inv_area);
-        if (ctx->d_lt_slot) (void)hipFree(ctx->d_lt_slot);
-        if (ctx->d_wf_state) (void)hipFree(ctx->d_wf_state);
-        if (ctx->d_wf_queues) (void)hipFree(ctx->d_wf_queues);
-        if (ctx->d_wf_counters) (void)hipFree(ctx->d_wf_counters);
         for (int c = 0; c < kWfMaxChains; ++c) {
             if (ctx->wf_stream[c]) (void)hipStreamDestroy(ctx->wf_stream[c]);
             if (ctx->wf_event[c]) (void)hipEventDestroy(ctx->wf_event[c]);
         }
         if (ctx->comm) comm_destroy(ctx->comm);
-        if (ctx->d_gathered) (void)hipFree(ctx->d_gathered);
-        if (ctx->d_frame) (void)hipFree(ctx->d_frame);
-        if (ctx->own_rnds && ctx->d_rnds) (void)hipFree(ctx->d_rnds);
-        if (ctx->own_colors && ctx->d_colors) (void)hipFree(ctx->d_colors);
+        if (ctx->h_adapt_count) (void)hipHostFree(ctx->h_adapt_count);
     }
-    delete ctx;
+    delete ctx;      // frees every device array the context owns (DeviceArray, pt_context.hpp): after the synchronise above
 }
 
 const char* pt_last_error(const pt_context* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
@@ -415,8 +368,8 @@ int pt_gather_frame(pt_context* ctx) {
     }
     PT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t slab = (size_t)ctx->slab_pix;
-    if (!ctx->d_gathered) PT_HIP(ctx, hipMalloc((void**)&ctx->d_gathered, sizeof(float4) * slab * (size_t)ctx->world));
-    if (!ctx->d_frame) PT_HIP(ctx, hipMalloc((void**)&ctx->d_frame, sizeof(float4) * (size_t)ctx->W * (size_t)ctx->H));
+    PT_ALLOC(ctx, ctx->d_gathered.reserve(slab * (size_t)ctx->world));
+    PT_ALLOC(ctx, ctx->d_frame.reserve((size_t)ctx->W * (size_t)ctx->H));
     std::string err;
     const int rc = comm_all_gather(ctx->comm, ctx->d_colors, ctx->d_gathered, slab * 4, ctx->stream, &err);
     if (rc != PT_OK) return fail(ctx, rc, err);
@@ -517,7 +470,7 @@ int pt_render_aovs(pt_context* ctx, const pt_camera* cam, int32_t subpixels, int
     int rc = check_ready(ctx, cam);
     if (rc != PT_OK) return rc;
     PT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_aov) PT_HIP(ctx, hipMalloc((void**)&ctx->d_aov, 2 * sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
+    PT_ALLOC(ctx, ctx->d_aov.reserve(2 * (size_t)std::max<int64_t>(ctx->npix, 1)));
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
     PT_HIP(ctx, launch_aovs(p, subpixels, specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, ctx->cu_count, ctx->stream));
@@ -552,7 +505,7 @@ int pt_render_aovs_ex(pt_context* ctx, const pt_camera* cam, const pt_aov_params
     if ((rc = smooth_prepare(ctx, &vn)) != PT_OK) return rc;
     TexView tv;                        // option textures: uvs, texels, descriptors, bindings
     if ((rc = texture_prepare(ctx, &tv)) != PT_OK) return rc;
-    if (!ctx->d_aov) PT_HIP(ctx, hipMalloc((void**)&ctx->d_aov, 2 * sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
+    PT_ALLOC(ctx, ctx->d_aov.reserve(2 * (size_t)std::max<int64_t>(ctx->npix, 1)));
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
     PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->glossy, ctx->coated, ctx->frosted, ctx->cu_count,
@@ -593,7 +546,7 @@ int pt_denoise(pt_context* ctx, const pt_denoise_params* dp) {
     PT_NEED_DEVICE(ctx);
     PT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->npix;
-    if (!ctx->d_dn) PT_HIP(ctx, hipMalloc((void**)&ctx->d_dn, 2 * sizeof(float4) * std::max<size_t>(npix, 1)));
+    PT_ALLOC(ctx, ctx->d_dn.reserve(2 * std::max<size_t>(npix, 1)));
     for (int i = 0; i < dp->iterations; ++i) {
         AtrousStep s;
         s.step = 1 << i;
@@ -625,7 +578,7 @@ static int compute_variance(pt_context* ctx, const char* who) {
     if (!ctx->moments_valid) return fail(ctx, PT_EINVAL, std::string(who) + ": the frame was not rendered with option moments = 1 from its first sample");
     if (ctx->current_sample <= 0) return fail(ctx, PT_EINVAL, std::string(who) + ": the frame has no samples");
     PT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_variance) PT_HIP(ctx, hipMalloc((void**)&ctx->d_variance, sizeof(float) * (size_t)std::max<int64_t>(ctx->npix, 1)));
+    PT_ALLOC(ctx, ctx->d_variance.reserve((size_t)std::max<int64_t>(ctx->npix, 1)));
     PT_HIP(ctx, launch_variance(ctx->d_colors, ctx->adaptive_frame ? ctx->d_adapt_spp : nullptr, ctx->current_sample, ctx->W, ctx->npix,
                                 ctx->d_variance, ctx->stream));
     return PT_OK;
@@ -664,7 +617,7 @@ static std::string variance_params_error(const pt_denoise_variance_params* dp) {
 // the iterations of k_atrous_var over colour in0 (.xyz) and variance var with the current guides, into the two d_dn buffers
 static int atrous_var_iterations(pt_context* ctx, const pt_denoise_variance_params* dp, const float4* in0, const float* var) {
     const size_t npix = (size_t)ctx->npix;
-    if (!ctx->d_dn) PT_HIP(ctx, hipMalloc((void**)&ctx->d_dn, 2 * sizeof(float4) * std::max<size_t>(npix, 1)));
+    PT_ALLOC(ctx, ctx->d_dn.reserve(2 * std::max<size_t>(npix, 1)));
     for (int i = 0; i < dp->iterations; ++i) {
         AtrousVarStep s;
         s.step = 1 << i;
@@ -729,10 +682,9 @@ int pt_temporal_accumulate(pt_context* ctx, const pt_temporal_params* tp) {
     if (ctx->temporal_frame == ctx->frame_serial) return fail(ctx, PT_EINVAL, "pt_temporal_accumulate: this frame was already accumulated");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t np = (size_t)std::max<int64_t>(ctx->npix, 1);
-    if (!ctx->d_temporal) {
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_temporal, (4 * sizeof(float4) + 2 * sizeof(float2)) * np));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_temporal_var, sizeof(float) * np));
-    }
+    static_assert(4 * sizeof(float4) + 2 * sizeof(float2) == 5 * sizeof(float4), "the two history sets: five float4 per local pixel");
+    PT_ALLOC(ctx, ctx->d_temporal.reserve(5 * np));
+    PT_ALLOC(ctx, ctx->d_temporal_var.reserve(np));
     const int out = ctx->temporal_out == 0 ? 1 : 0, prev = 1 - out;
     TemporalArgs a;
     a.cur = ctx->frame_cam;
@@ -879,16 +831,13 @@ int nee_prepare(pt_context* ctx, int32_t strategy, NeeTable* ltp, EnvView* envp,
     if ((rc = nee_table(ctx)) != PT_OK) return rc;
     PT_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->nee_uploaded) {
-        if (ctx->d_nee_tri) PT_HIP(ctx, hipFree(ctx->d_nee_tri));
-        if (ctx->d_nee_cdf) PT_HIP(ctx, hipFree(ctx->d_nee_cdf));
-        if (ctx->d_nee_pdf_area) PT_HIP(ctx, hipFree(ctx->d_nee_pdf_area));
-        ctx->d_nee_tri = nullptr;
-        ctx->d_nee_cdf = nullptr;
-        ctx->d_nee_pdf_area = nullptr;
+        ctx->d_nee_tri.reset();
+        ctx->d_nee_cdf.reset();
+        ctx->d_nee_pdf_area.reset();
         const size_t nl = std::max<size_t>(ctx->nee_tri.size(), 1);
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_nee_tri, sizeof(int32_t) * nl));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_nee_cdf, sizeof(float) * nl));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_nee_pdf_area, sizeof(float) * ctx->nee_pdf_area.size()));
+        PT_ALLOC(ctx, ctx->d_nee_tri.replace(nl));
+        PT_ALLOC(ctx, ctx->d_nee_cdf.replace(nl));
+        PT_ALLOC(ctx, ctx->d_nee_pdf_area.replace(ctx->nee_pdf_area.size()));
         if (!ctx->nee_tri.empty()) {
             PT_HIP(ctx, hipMemcpy(ctx->d_nee_tri, ctx->nee_tri.data(), sizeof(int32_t) * ctx->nee_tri.size(), hipMemcpyHostToDevice));
             PT_HIP(ctx, hipMemcpy(ctx->d_nee_cdf, ctx->nee_cdf.data(), sizeof(float) * ctx->nee_cdf.size(), hipMemcpyHostToDevice));
@@ -1136,25 +1085,17 @@ int smooth_prepare(pt_context* ctx, const float4** vn, bool force) {
     PT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = ctx->orig.size();
     if (ctx->vnormals_dirty || !ctx->d_vnormals) {
-        if (!ctx->d_vnormals || ctx->vnormals_cap < std::max<size_t>(n, 1)) {
-            if (ctx->d_vnormals) { PT_HIP(ctx, hipFree(ctx->d_vnormals)); ctx->d_vnormals = nullptr; }
-            ctx->vnormals_cap = 0;
-            PT_HIP(ctx, hipMalloc((void**)&ctx->d_vnormals, sizeof(float4) * 3 * std::max<size_t>(n, 1)));
-            ctx->vnormals_cap = std::max<size_t>(n, 1);
-        }
+        PT_ALLOC(ctx, ctx->d_vnormals.reserve(3 * std::max<size_t>(n, 1)));
         // (an empty scene keeps one all-zero record next to its one all-zero packet, which can never be hit)
         if (n == 0) PT_HIP(ctx, hipMemsetAsync(ctx->d_vnormals, 0, sizeof(float4) * 3, ctx->stream));
         const size_t n_src = std::min(ctx->tris.size(), ctx->vnormals.size() / 9);
-        float* d_src = nullptr;
-        int32_t* d_orig = nullptr;
-        hipError_t e = hipMalloc((void**)&d_src, std::max<size_t>(sizeof(float) * 9 * n_src, 16));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_orig, std::max<size_t>(sizeof(int32_t) * n, 16));
-        if (e == hipSuccess && n_src) e = hipMemcpyAsync(d_src, ctx->vnormals.data(), sizeof(float) * 9 * n_src, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && n) e = hipMemcpyAsync(d_orig, ctx->orig.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = launch_pack_vertex_normals(d_src, (int64_t)n_src, d_orig, (int32_t)n, ctx->d_vnormals, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // the staging copies are freed below, the host vectors may change
-        if (d_src) (void)hipFree(d_src);
-        if (d_orig) (void)hipFree(d_orig);
+        DeviceBuf d_src, d_orig;
+        hipError_t e = d_src.alloc(sizeof(float) * 9 * n_src);
+        if (e == hipSuccess) e = d_orig.alloc(sizeof(int32_t) * n);
+        if (e == hipSuccess && n_src) e = hipMemcpyAsync(d_src.p, ctx->vnormals.data(), sizeof(float) * 9 * n_src, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && n) e = hipMemcpyAsync(d_orig.p, ctx->orig.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = launch_pack_vertex_normals((const float*)d_src.p, (int64_t)n_src, (const int32_t*)d_orig.p, (int32_t)n, ctx->d_vnormals, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // the staging copies end with this block, the host vectors may change
         if (e != hipSuccess) return fail(ctx, PT_EHIP, std::string("vertex normals: ") + hipGetErrorString(e));
         ctx->vnormals_dirty = false;
     }
@@ -1175,13 +1116,10 @@ int pt_debug_shading_normal(pt_context* ctx, const pt_ray* rays, int64_t n, int3
     std::memset(&cam, 0, sizeof cam);
     RenderParams p;
     fill_params(ctx, &cam, &p);
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_rays, d_tri, d_ns;
-    PT_HIP(ctx, hipMalloc(&d_rays.p, std::max<size_t>(sizeof(pt_ray) * (size_t)n, 16)));
-    PT_HIP(ctx, hipMalloc(&d_tri.p, std::max<size_t>(sizeof(int32_t) * (size_t)n, 16)));
-    PT_HIP(ctx, hipMalloc(&d_ns.p, std::max<size_t>(sizeof(float4) * (size_t)n, 16)));
+    DeviceBuf d_rays, d_tri, d_ns;
+    PT_HIP(ctx, d_rays.alloc(sizeof(pt_ray) * (size_t)n));
+    PT_HIP(ctx, d_tri.alloc(sizeof(int32_t) * (size_t)n));
+    PT_HIP(ctx, d_ns.alloc(sizeof(float4) * (size_t)n));
     if (n) PT_HIP(ctx, hipMemcpy(d_rays.p, rays, sizeof(pt_ray) * (size_t)n, hipMemcpyHostToDevice));
     PT_HIP(ctx, launch_debug_shading_normal(p, vn, (const pt_ray*)d_rays.p, n, (int32_t*)d_tri.p, (float4*)d_ns.p, ctx->cu_count, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1199,18 +1137,8 @@ int pt_debug_glossy(pt_context* ctx, int64_t n, const float* N_D_alpha_rnd, floa
     PT_NEED_DEVICE(ctx);
     if (n < 0 || (n > 0 && (!N_D_alpha_rnd || !out))) return fail(ctx, PT_EINVAL, "pt_debug_glossy: n >= 0, both arrays non-null");
     if (n == 0) return PT_OK;
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_in, d_out;
-    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * 9 * (size_t)n));
-    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 8 * (size_t)n));
-    PT_HIP(ctx, hipMemcpy(d_in.p, N_D_alpha_rnd, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice));
-    PT_HIP(ctx, launch_debug_glossy((const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 8 * (size_t)n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_round_trip(ctx, N_D_alpha_rnd, sizeof(float) * 9 * (size_t)n, out, sizeof(float) * 8 * (size_t)n,
+                            [&](void* d_in, void* d_out) { return launch_debug_glossy((const float*)d_in, n, (float*)d_out, ctx->stream); });
 }
 
 // ---- coated diffuse (option coated; kernels: pt_glossy.hip, pt_nee.hip; pinned in include/pt_api.h)
@@ -1218,18 +1146,8 @@ int pt_debug_coated(pt_context* ctx, int64_t n, const float* in, float* out) {
     PT_NEED_DEVICE(ctx);
     if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, PT_EINVAL, "pt_debug_coated: n >= 0, both arrays non-null");
     if (n == 0) return PT_OK;
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_in, d_out;
-    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * 12 * (size_t)n));
-    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 10 * (size_t)n));
-    PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(float) * 12 * (size_t)n, hipMemcpyHostToDevice));
-    PT_HIP(ctx, launch_debug_coated((const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_round_trip(ctx, in, sizeof(float) * 12 * (size_t)n, out, sizeof(float) * 10 * (size_t)n,
+                            [&](void* d_in, void* d_out) { return launch_debug_coated((const float*)d_in, n, (float*)d_out, ctx->stream); });
 }
 
 // ---- rough dielectric (option frosted; kernels: pt_glossy.hip, pt_nee.hip; pinned in include/pt_api.h)
@@ -1237,18 +1155,8 @@ int pt_debug_frosted(pt_context* ctx, int64_t n, const float* in, float* out) {
     PT_NEED_DEVICE(ctx);
     if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, PT_EINVAL, "pt_debug_frosted: n >= 0, both arrays non-null");
     if (n == 0) return PT_OK;
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_in, d_out;
-    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * 12 * (size_t)n));
-    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 10 * (size_t)n));
-    PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(float) * 12 * (size_t)n, hipMemcpyHostToDevice));
-    PT_HIP(ctx, launch_debug_frosted((const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_round_trip(ctx, in, sizeof(float) * 12 * (size_t)n, out, sizeof(float) * 10 * (size_t)n,
+                            [&](void* d_in, void* d_out) { return launch_debug_frosted((const float*)d_in, n, (float*)d_out, ctx->stream); });
 }
 
 // ---- thin lens (pt_set_lens; kernels: pt_lens.hip, pt_nee.hip; pinned in include/pt_api.h)
@@ -1293,11 +1201,8 @@ int pt_focus_at(pt_context* ctx, const pt_camera* cam, int32_t x, int32_t y, flo
     PT_HIP(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     fill_params(ctx, cam, &p);
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_out;
-    PT_HIP(ctx, hipMalloc(&d_out.p, 16));
+    DeviceBuf d_out;
+    PT_HIP(ctx, d_out.alloc(sizeof(float)));
     PT_HIP(ctx, launch_focus_at(p, lens_view(*cam, 0.0f, 1.0f), y * ctx->W + x, (float*)d_out.p, ctx->cu_count, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     PT_HIP(ctx, hipMemcpy(distance, d_out.p, sizeof(float), hipMemcpyDeviceToHost));
@@ -1311,18 +1216,9 @@ int pt_debug_lens(pt_context* ctx, const pt_camera* cam, const pt_lens_params* l
     if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_debug_lens: " + why);
     if (!((int32_t)cam->XM > 0 && (int32_t)cam->YM > 0)) return fail(ctx, PT_EINVAL, "pt_debug_lens: camera XM/YM must be positive");
     if (n == 0) return PT_OK;
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_in, d_out;
-    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(int32_t) * 2 * (size_t)n));
-    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 6 * (size_t)n));
-    PT_HIP(ctx, hipMemcpy(d_in.p, gid_state, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice));
-    PT_HIP(ctx, launch_debug_lens(*cam, lens_view(*cam, lens->aperture, lens->focus_distance), (const int32_t*)d_in.p, n, (float*)d_out.p, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 6 * (size_t)n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_round_trip(ctx, gid_state, sizeof(int32_t) * 2 * (size_t)n, out, sizeof(float) * 6 * (size_t)n, [&](void* d_in, void* d_out) {
+        return launch_debug_lens(*cam, lens_view(*cam, lens->aperture, lens->focus_distance), (const int32_t*)d_in, n, (float*)d_out, ctx->stream);
+    });
 }
 
 // ---- albedo textures with UV coordinates (kernels: pt_texture.hip, pt_nee.hip; pinned in include/pt_api.h)
@@ -1478,12 +1374,13 @@ int texture_prepare(pt_context* ctx, TexView* tv, bool force) {
             if ((ctx->mats[i].type == 0 || ctx->mats[i].type == 5) && ctx->mat_tex[i] >= 0 && ctx->mat_tex[i] < (int32_t)ctx->tex_desc.size()) bind[i] = ctx->mat_tex[i];
         std::vector<TexDesc> desc(ctx->tex_desc);
         desc.resize(ntex, TexDesc{0, 1, 1, 0});
-        if (ctx->d_mat_tex) { PT_HIP(ctx, hipFree(ctx->d_mat_tex)); ctx->d_mat_tex = nullptr; }
-        if (ctx->d_tex_desc) { PT_HIP(ctx, hipFree(ctx->d_tex_desc)); ctx->d_tex_desc = nullptr; }
-        if (ctx->d_tex_texels) { PT_HIP(ctx, hipFree(ctx->d_tex_texels)); ctx->d_tex_texels = nullptr; }
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_tex_texels, sizeof(uint64_t) * ntexel));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_tex_desc, sizeof(TexDesc) * ntex));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_mat_tex, sizeof(int32_t) * nmat));
+        ctx->d_mat_tex.reset();
+        ctx->d_tex_desc.reset();
+        ctx->d_tex_texels.reset();
+        static_assert(sizeof(uint2) == sizeof(uint64_t), "a texel is 8 bytes");
+        PT_ALLOC(ctx, ctx->d_tex_texels.replace(ntexel));
+        PT_ALLOC(ctx, ctx->d_tex_desc.replace(ntex));
+        PT_ALLOC(ctx, ctx->d_mat_tex.replace(nmat));
         if (ctx->tex_texels.empty()) PT_HIP(ctx, hipMemsetAsync(ctx->d_tex_texels, 0, sizeof(uint64_t), ctx->stream));
         else PT_HIP(ctx, hipMemcpyAsync(ctx->d_tex_texels, ctx->tex_texels.data(), sizeof(uint64_t) * ctx->tex_texels.size(), hipMemcpyHostToDevice, ctx->stream));
         PT_HIP(ctx, hipMemcpyAsync(ctx->d_tex_desc, desc.data(), sizeof(TexDesc) * ntex, hipMemcpyHostToDevice, ctx->stream));
@@ -1493,25 +1390,17 @@ int texture_prepare(pt_context* ctx, TexView* tv, bool force) {
     }
     const size_t n = ctx->orig.size();
     if (ctx->vuvs_dirty || !ctx->d_vuvs) {
-        if (!ctx->d_vuvs || ctx->vuvs_cap < std::max<size_t>(n, 1)) {
-            if (ctx->d_vuvs) { PT_HIP(ctx, hipFree(ctx->d_vuvs)); ctx->d_vuvs = nullptr; }
-            ctx->vuvs_cap = 0;
-            PT_HIP(ctx, hipMalloc((void**)&ctx->d_vuvs, sizeof(float4) * 2 * std::max<size_t>(n, 1)));
-            ctx->vuvs_cap = std::max<size_t>(n, 1);
-        }
+        PT_ALLOC(ctx, ctx->d_vuvs.reserve(2 * std::max<size_t>(n, 1)));
         // (an empty scene keeps one all-zero record next to its one all-zero packet, which can never be hit)
         if (n == 0) PT_HIP(ctx, hipMemsetAsync(ctx->d_vuvs, 0, sizeof(float4) * 2, ctx->stream));
         const size_t n_src = std::min(ctx->tris.size(), ctx->vuvs.size() / 6);
-        float* d_src = nullptr;
-        int32_t* d_orig = nullptr;
-        hipError_t e = hipMalloc((void**)&d_src, std::max<size_t>(sizeof(float) * 6 * n_src, 16));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_orig, std::max<size_t>(sizeof(int32_t) * n, 16));
-        if (e == hipSuccess && n_src) e = hipMemcpyAsync(d_src, ctx->vuvs.data(), sizeof(float) * 6 * n_src, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && n) e = hipMemcpyAsync(d_orig, ctx->orig.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = launch_pack_vertex_uvs(d_src, (int64_t)n_src, d_orig, (int32_t)n, ctx->d_vuvs, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // the staging copies are freed below, the host vectors may change
-        if (d_src) (void)hipFree(d_src);
-        if (d_orig) (void)hipFree(d_orig);
+        DeviceBuf d_src, d_orig;
+        hipError_t e = d_src.alloc(sizeof(float) * 6 * n_src);
+        if (e == hipSuccess) e = d_orig.alloc(sizeof(int32_t) * n);
+        if (e == hipSuccess && n_src) e = hipMemcpyAsync(d_src.p, ctx->vuvs.data(), sizeof(float) * 6 * n_src, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && n) e = hipMemcpyAsync(d_orig.p, ctx->orig.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = launch_pack_vertex_uvs((const float*)d_src.p, (int64_t)n_src, (const int32_t*)d_orig.p, (int32_t)n, ctx->d_vuvs, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // the staging copies end with this block, the host vectors may change
         if (e != hipSuccess) return fail(ctx, PT_EHIP, std::string("vertex uvs: ") + hipGetErrorString(e));
         ctx->vuvs_dirty = false;
     }
@@ -1534,13 +1423,10 @@ int pt_debug_albedo(pt_context* ctx, const pt_ray* rays, int64_t n, int32_t* out
     std::memset(&cam, 0, sizeof cam);
     RenderParams p;
     fill_params(ctx, &cam, &p);
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_rays, d_tri, d_out;
-    PT_HIP(ctx, hipMalloc(&d_rays.p, std::max<size_t>(sizeof(pt_ray) * (size_t)n, 16)));
-    PT_HIP(ctx, hipMalloc(&d_tri.p, std::max<size_t>(sizeof(int32_t) * (size_t)n, 16)));
-    PT_HIP(ctx, hipMalloc(&d_out.p, std::max<size_t>(sizeof(float4) * (size_t)n, 16)));
+    DeviceBuf d_rays, d_tri, d_out;
+    PT_HIP(ctx, d_rays.alloc(sizeof(pt_ray) * (size_t)n));
+    PT_HIP(ctx, d_tri.alloc(sizeof(int32_t) * (size_t)n));
+    PT_HIP(ctx, d_out.alloc(sizeof(float4) * (size_t)n));
     if (n) PT_HIP(ctx, hipMemcpy(d_rays.p, rays, sizeof(pt_ray) * (size_t)n, hipMemcpyHostToDevice));
     PT_HIP(ctx, launch_debug_albedo(p, vn, tv, (const pt_ray*)d_rays.p, n, (int32_t*)d_tri.p, (float4*)d_out.p, ctx->cu_count, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1565,7 +1451,7 @@ int pt_resolve_ldr(pt_context* ctx, int32_t which, float* out, int64_t npix) {
     if (which != 0 && which != 1) return fail(ctx, PT_EINVAL, "which must be 0 (Reinhard) or 1 (filt_im)");
     if (which == 1 && ctx->world != 1) return fail(ctx, PT_EINVAL, "filt_im needs the whole frame on one context (3x3 stencil)");
     PT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_ldr) PT_HIP(ctx, hipMalloc((void**)&ctx->d_ldr, sizeof(float4) * (size_t)std::max<int64_t>(npix, 1)));
+    PT_ALLOC(ctx, ctx->d_ldr.reserve((size_t)std::max<int64_t>(npix, 1)));
     if (which == 0) {
         PT_HIP(ctx, launch_resolve_reinhard(ctx->d_colors, ctx->d_ldr, npix, ctx->stream));
     } else {
@@ -1581,15 +1467,13 @@ int pt_bind_framebuffer(pt_context* ctx, void* d_colors, void* d_rnds) {
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (d_colors && d_colors != ctx->d_colors) {
         PT_HIP(ctx, hipMemcpy(d_colors, ctx->d_colors, sizeof(float4) * (size_t)ctx->npix, hipMemcpyDeviceToDevice));
-        if (ctx->own_colors) PT_HIP(ctx, hipFree(ctx->d_colors));
+        ctx->colors_own.reset();
         ctx->d_colors = (float4*)d_colors;
-        ctx->own_colors = false;
     }
     if (d_rnds && d_rnds != ctx->d_rnds) {
         PT_HIP(ctx, hipMemcpy(d_rnds, ctx->d_rnds, sizeof(int32_t) * (size_t)ctx->npix, hipMemcpyDeviceToDevice));
-        if (ctx->own_rnds) PT_HIP(ctx, hipFree(ctx->d_rnds));
+        ctx->rnds_own.reset();
         ctx->d_rnds = (int32_t*)d_rnds;
-        ctx->own_rnds = false;
     }
     return PT_OK;
 }
@@ -1846,11 +1730,6 @@ int pt_debug_bvh_copy(const pt_context* cctx, float* nodes, float* tris, int32_t
 }
 
 namespace {
-struct DeviceBuf {          // frees on every exit path
-    void* p = nullptr;
-    ~DeviceBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-};
 struct EventOwner {
     hipEvent_t e = nullptr;
     ~EventOwner() { if (e) (void)hipEventDestroy(e); }
@@ -1884,15 +1763,8 @@ int pt_debug_spec(pt_context* ctx, int32_t fn, int64_t n, const uint32_t* in, ui
     if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, PT_EINVAL, "pt_debug_spec: n >= 0, both arrays non-null");
     if (n == 0) return PT_OK;
     PT_NEED_DEVICE(ctx);
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    DeviceBuf d_in, d_out;
-    PT_HIP(ctx, d_in.alloc(sizeof(uint32_t) * wi * (size_t)n));
-    PT_HIP(ctx, d_out.alloc(sizeof(uint32_t) * wo * (size_t)n));
-    PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(uint32_t) * wi * (size_t)n, hipMemcpyHostToDevice));
-    PT_HIP(ctx, launch_debug_spec(fn, (const uint32_t*)d_in.p, n, (uint32_t*)d_out.p, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(uint32_t) * wo * (size_t)n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_round_trip(ctx, in, sizeof(uint32_t) * wi * (size_t)n, out, sizeof(uint32_t) * wo * (size_t)n,
+                            [&](void* d_in, void* d_out) { return launch_debug_spec(fn, (const uint32_t*)d_in, n, (uint32_t*)d_out, ctx->stream); });
 }
 
 int pt_debug_closest_hit(pt_context* ctx, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri) {
@@ -1938,16 +1810,9 @@ int pt_debug_closest_hit(pt_context* ctx, const pt_ray* rays, int64_t n, float* 
 int pt_debug_deinterleave(pt_context* ctx, const float* gathered, int64_t n_pixels, float* out_frame) {
     PT_NEED_DEVICE(ctx);
     if (!gathered || !out_frame || n_pixels != ctx->slab_pix * ctx->world) return fail(ctx, PT_EINVAL, "gathered must hold world x slab pixels");
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    DeviceBuf d_g, d_f;
-    const size_t nf = (size_t)ctx->W * (size_t)ctx->H;
-    PT_HIP(ctx, d_g.alloc(sizeof(float4) * (size_t)n_pixels));
-    PT_HIP(ctx, d_f.alloc(sizeof(float4) * nf));
-    PT_HIP(ctx, hipMemcpy(d_g.p, gathered, sizeof(float4) * (size_t)n_pixels, hipMemcpyHostToDevice));
-    PT_HIP(ctx, launch_deinterleave((const float4*)d_g.p, (float4*)d_f.p, ctx->W, ctx->H, ctx->world, ctx->rows_per_block, (long long)ctx->slab_pix, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(out_frame, d_f.p, sizeof(float4) * nf, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_round_trip(ctx, gathered, sizeof(float4) * (size_t)n_pixels, out_frame, sizeof(float4) * (size_t)ctx->W * (size_t)ctx->H, [&](void* d_g, void* d_f) {
+        return launch_deinterleave((const float4*)d_g, (float4*)d_f, ctx->W, ctx->H, ctx->world, ctx->rows_per_block, (long long)ctx->slab_pix, ctx->stream);
+    });
 }
 
 int pt_debug_scene_sizes(const pt_context* ctx, int64_t* ntris, int64_t* nmats, int64_t* nobjs) {

@@ -37,14 +37,10 @@ int interior_prepare(pt_context* ctx, InteriorView* iv) {
             r[5] = 1.0f;
         }
         PT_HIP(ctx, hipStreamSynchronize(ctx->stream));      // a frame in flight may still read the previous table
-        float4* fresh = nullptr;
+        DeviceArray<float4> fresh;
         int rc;
-        if ((rc = upload_vec(ctx, &fresh, rec.data(), sizeof(float) * rec.size())) != PT_OK) {
-            if (fresh) (void)hipFree(fresh);
-            return rc;
-        }
-        if (ctx->d_interior) (void)hipFree(ctx->d_interior);
-        ctx->d_interior = fresh;
+        if ((rc = upload_vec(ctx, &fresh, rec.data(), sizeof(float) * rec.size())) != PT_OK) return rc;
+        ctx->d_interior = std::move(fresh);
         ctx->interior_dirty = false;
     }
     iv->rec = ctx->d_interior;
@@ -107,18 +103,8 @@ int pt_debug_interior(pt_context* ctx, const float* in, int64_t n, float* out) {
     if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, PT_EINVAL, "pt_debug_interior: n < 0, or in / out is NULL");
     PT_NEED_DEVICE(ctx);
     if (n == 0) return PT_OK;
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_in, d_out;
-    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * 12 * (size_t)n));
-    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 10 * (size_t)n));
-    PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(float) * 12 * (size_t)n, hipMemcpyHostToDevice));
-    PT_HIP(ctx, launch_debug_interior((const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_round_trip(ctx, in, sizeof(float) * 12 * (size_t)n, out, sizeof(float) * 10 * (size_t)n,
+                            [&](void* d_in, void* d_out) { return launch_debug_interior((const float*)d_in, n, (float*)d_out, ctx->stream); });
 }
 
 }  // extern "C"

@@ -78,8 +78,7 @@ int plan_node_placement(pt_context* ctx, const float4* d_bvh2, bool* wide_on_dev
             bool failed = false;
             PT_HIP(ctx, wide_device_build(d_bvh2, (int)ctx->nodes.size(), ctx->stream, &d4, &n4, &pending, &failed));
             if (!failed) {
-                if (ctx->d_nodes4) (void)hipFree(ctx->d_nodes4);
-                ctx->d_nodes4 = d4;
+                ctx->d_nodes4.adopt(d4, (size_t)n4 * (sizeof(Node4q) / sizeof(float4)));
                 ctx->nodes4.resize((size_t)n4);          // host copy for the debug getter and the stack sizing
                 ctx->wide_pending = pending;
                 PT_HIP(ctx, hipMemcpy(ctx->nodes4.data(), d4, sizeof(Node4q) * (size_t)n4, hipMemcpyDeviceToHost));
@@ -97,7 +96,7 @@ int plan_node_placement(pt_context* ctx, const float4* d_bvh2, bool* wide_on_dev
 }
 
 int alloc_stack_overflow(pt_context* ctx) {
-    if (ctx->d_stack_ovf) { PT_HIP(ctx, hipFree(ctx->d_stack_ovf)); ctx->d_stack_ovf = nullptr; }
+    ctx->d_stack_ovf.reset();
     ctx->stack_ovf_lanes = 0;
     const int extra = ctx->nodes4.empty() ? 0 : wide_stack_entries(ctx->wide_pending) - ctx->wide_lds_entries;
     if (extra <= 0) return PT_OK;
@@ -105,7 +104,7 @@ int alloc_stack_overflow(pt_context* ctx) {
     // every grid that can be in flight at once: k_render (one thread per pixel at most), or kWfDefaultChains concurrent wf_intersect
     // launches of the wavefront variant (2 cost classes x 6 x 256 threads per CU each, render_wavefront)
     const size_t lanes = 256 * std::max<size_t>((size_t)ctx->cu_count * 12 * kWfDefaultChains, (n_tiles + 3) / 4);
-    PT_HIP(ctx, hipMalloc((void**)&ctx->d_stack_ovf, lanes * (size_t)extra * sizeof(uint32_t)));
+    PT_ALLOC(ctx, ctx->d_stack_ovf.replace(lanes * (size_t)extra));
     ctx->stack_ovf_lanes = lanes;
     return PT_OK;
 }
@@ -199,18 +198,13 @@ int ensure_shade_records(pt_context* ctx, RenderParams* p) {
     if (!shade_records_for(p->node_mode)) return PT_OK;
     if (ctx->shaderec_dirty) {
         const size_t n = ctx->orig.size();
-        if (!ctx->d_shaderec || ctx->shaderec_cap < std::max<size_t>(n, 1)) {
-            if (ctx->d_shaderec) { PT_HIP(ctx, hipFree(ctx->d_shaderec)); ctx->d_shaderec = nullptr; }
-            ctx->shaderec_cap = 0;
-            PT_HIP(ctx, hipMalloc((void**)&ctx->d_shaderec, sizeof(ShadeRec) * std::max<size_t>(n, 1)));
-            ctx->shaderec_cap = std::max<size_t>(n, 1);
-        }
+        PT_ALLOC(ctx, ctx->d_shaderec.reserve(std::max<size_t>(n, 1)));
         // (an empty scene keeps one all-zero record next to its one all-zero packet, which can never be hit)
         if (n == 0) PT_HIP(ctx, hipMemsetAsync(ctx->d_shaderec, 0, sizeof(ShadeRec), ctx->stream));
         PT_HIP(ctx, launch_shade_records(ctx->d_tris, ctx->d_meta, ctx->d_mats, ctx->mats_on_device, (int32_t)n, ctx->d_shaderec, ctx->stream));
         ctx->shaderec_dirty = false;
     }
-    p->shaderec = reinterpret_cast<const float4*>(ctx->d_shaderec);
+    p->shaderec = reinterpret_cast<const float4*>(ctx->d_shaderec.get());
     return PT_OK;
 }
 
@@ -442,11 +436,9 @@ static int render_wavefront(pt_context* ctx, const RenderParams& rp, int32_t nsa
     if (rp.iterations > kWfMaxBounces) return fail(ctx, PT_EINVAL, "wavefront variant supports at most 1023 iterations");
     const size_t np = (size_t)std::max<int64_t>(ctx->npix, 1);
     constexpr size_t kCounterWords = (size_t)kWfCounterStride * (kWfMaxBounces + 4);
-    if (!ctx->d_wf_state) {
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_wf_state, sizeof(float4) * 17 * np));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_wf_queues, sizeof(int32_t) * 3 * np));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_wf_counters, sizeof(uint32_t) * kCounterWords * kWfMaxChains));
-    }
+    PT_ALLOC(ctx, ctx->d_wf_state.reserve(17 * np));
+    PT_ALLOC(ctx, ctx->d_wf_queues.reserve(3 * np));
+    PT_ALLOC(ctx, ctx->d_wf_counters.reserve(kCounterWords * kWfMaxChains));
     if (ctx->npix == 0) return PT_OK;
     // chains of whole 8,192-pixel units, at least ~64k pixels each (a chain of a few thousand rays is all launch overhead)
     const int want = ctx->wf_streams > 0 ? ctx->wf_streams : kWfDefaultChains;
@@ -472,7 +464,7 @@ static int render_wavefront(pt_context* ctx, const RenderParams& rp, int32_t nsa
         const int64_t p0 = std::min<int64_t>((int64_t)c * per, ctx->npix), count = std::min<int64_t>(p0 + per, ctx->npix) - p0;
         wc.rp = rp;
         if (rp.stack_ovf) wc.rp.stack_ovf = rp.stack_ovf + (size_t)c * chain_lanes;      // (stack_ovf_lanes stays the stride between entries)
-        wc.sP = reinterpret_cast<float*>(ctx->d_wf_state);        // kWfFields x np x 12 B <= 4 x np x 16 B, indexed by local pixel
+        wc.sP = reinterpret_cast<float*>(ctx->d_wf_state.get());        // kWfFields x np x 12 B <= 4 x np x 16 B, indexed by local pixel
         for (int par = 0; par < 2; ++par)
             for (int k = 0; k < 2; ++k) {
                 wc.rsA[par][k] = ctx->d_wf_state + (size_t)(4 + (par * 2 + k) * 2 + 0) * np + p0;      // a chain's streams: its slice of each array
@@ -578,7 +570,7 @@ static int launch_megakernel(pt_context* ctx, RenderParams& p, const int32_t* ti
         if (items + (int64_t)resident_waves + 64 >= ((int64_t)1 << 31))
             return fail(ctx, PT_EINVAL, "nsamples / chunk_spp x tiles does not fit the 31-bit work-item counter of one launch: render in several calls");
         if (chunk > 0 && nsamples > chunk && p.n_tiles > 0) {
-            if (!ctx->d_tile_done) PT_HIP(ctx, hipMalloc((void**)&ctx->d_tile_done, sizeof(uint32_t) * frame_tiles));
+            PT_ALLOC(ctx, ctx->d_tile_done.reserve(frame_tiles));
             PT_HIP(ctx, hipMemsetAsync(ctx->d_tile_done, 0, sizeof(uint32_t) * (size_t)p.n_tiles, ctx->stream));
             p.tile_done = ctx->d_tile_done;
             p.chunk_spp = chunk;
@@ -587,7 +579,7 @@ static int launch_megakernel(pt_context* ctx, RenderParams& p, const int32_t* ti
     if (lc.count_work && p.n_tiles > 0) {      // per-tile cost of this launch (pt_debug_tile_cost)
         // (+ 16: in a non-persistent grid the waves past the last tile of the last workgroup (at most 15) still add their time -- the
         // atomicAdd in k_render is not conditional on the wave having pixels -- at indices up to 15 past the frame's tiles)
-        if (!ctx->d_tile_cost) PT_HIP(ctx, hipMalloc((void**)&ctx->d_tile_cost, sizeof(uint32_t) * (frame_tiles + 16)));
+        PT_ALLOC(ctx, ctx->d_tile_cost.reserve(frame_tiles + 16));
         PT_HIP(ctx, hipMemsetAsync(ctx->d_tile_cost, 0, sizeof(uint32_t) * frame_tiles, ctx->stream));      // (indexed by frame tile)
         p.tile_cost = ctx->d_tile_cost;
     }
@@ -693,15 +685,12 @@ static int adaptive_frame(pt_context* ctx, const pt_camera* cam, int32_t iterati
     nl.env = sky ? &env : nullptr;
     nl.tiled = true;
     const int32_t n_frame = local_tiles(ctx);
-    if (!ctx->d_adapt_spp) {
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_spp, sizeof(int32_t) * (size_t)n_frame));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_err, sizeof(float) * (size_t)n_frame));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_active, (size_t)n_frame));
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_list, sizeof(int32_t) * ((size_t)n_frame + 1)));
-        PT_HIP(ctx, hipHostMalloc((void**)&ctx->h_adapt_count, sizeof(int32_t), hipHostMallocDefault));
-    }
-    if (!variance && !ctx->d_adapt_snap)      // (the variance metric keeps no snapshot)
-        PT_HIP(ctx, hipMalloc((void**)&ctx->d_adapt_snap, sizeof(float4) * (size_t)std::max<int64_t>(ctx->npix, 1)));
+    PT_ALLOC(ctx, ctx->d_adapt_spp.reserve((size_t)n_frame));
+    PT_ALLOC(ctx, ctx->d_adapt_err.reserve((size_t)n_frame));
+    PT_ALLOC(ctx, ctx->d_adapt_active.reserve((size_t)n_frame));
+    PT_ALLOC(ctx, ctx->d_adapt_list.reserve((size_t)n_frame + 1));
+    if (!ctx->h_adapt_count) PT_HIP(ctx, hipHostMalloc((void**)&ctx->h_adapt_count, sizeof(int32_t), hipHostMallocDefault));
+    if (!variance) PT_ALLOC(ctx, ctx->d_adapt_snap.reserve((size_t)std::max<int64_t>(ctx->npix, 1)));      // (the variance metric keeps no snapshot)
     int32_t* d_count = ctx->d_adapt_list + n_frame;
     PT_HIP(ctx, hipMemsetAsync(ctx->d_adapt_active, 1, (size_t)n_frame, ctx->stream));
     PT_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(int32_t), ctx->stream));          // (no list before the first decision)

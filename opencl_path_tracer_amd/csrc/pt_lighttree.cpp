@@ -197,13 +197,10 @@ int pt_debug_light_tree_eval(pt_context* ctx, const float* points, const float* 
             std::memcpy(in.data() + 7 * i + 3, normals + 3 * i, 12);
             in[(size_t)(7 * i + 6)] = u0[i];
         }
-        struct Buf {
-            void* p = nullptr;
-            ~Buf() { if (p) (void)hipFree(p); }
-        } d_in, d_target, d_out;
-        PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * in.size()));
-        PT_HIP(ctx, hipMalloc(&d_target.p, sizeof(int32_t) * target.size()));
-        PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(int32_t) * raw.size()));
+        DeviceBuf d_in, d_target, d_out;
+        PT_HIP(ctx, d_in.alloc(sizeof(float) * in.size()));
+        PT_HIP(ctx, d_target.alloc(sizeof(int32_t) * target.size()));
+        PT_HIP(ctx, d_out.alloc(sizeof(int32_t) * raw.size()));
         PT_HIP(ctx, hipMemcpy(d_in.p, in.data(), sizeof(float) * in.size(), hipMemcpyHostToDevice));
         PT_HIP(ctx, hipMemcpy(d_target.p, target.data(), sizeof(int32_t) * target.size(), hipMemcpyHostToDevice));
         PT_HIP(ctx, launch_debug_light_tree(v, (const float*)d_in.p, (const int32_t*)d_target.p, n, (int32_t*)d_out.p, ctx->stream));

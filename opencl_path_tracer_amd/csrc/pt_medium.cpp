@@ -106,14 +106,10 @@ int pt_set_medium_density(pt_context* ctx, const float* density, int32_t nx, int
         // the copy first, so that a failed upload leaves the held grid as it was; a frame in flight may still read the previous one
         PT_HIP(ctx, hipSetDevice(ctx->device));
         PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float* fresh = nullptr;
+        DeviceArray<float> fresh;
         int rc;
-        if ((rc = upload_vec(ctx, &fresh, density, sizeof(float) * count)) != PT_OK) {
-            if (fresh) (void)hipFree(fresh);
-            return rc;
-        }
-        if (ctx->d_grid) (void)hipFree(ctx->d_grid);
-        ctx->d_grid = fresh;
+        if ((rc = upload_vec(ctx, &fresh, density, sizeof(float) * count)) != PT_OK) return rc;
+        ctx->d_grid = std::move(fresh);
     }
     ctx->grid.assign(density, density + count);
     for (int a = 0; a < 3; ++a) ctx->grid_n[a] = dims[a];
@@ -126,8 +122,7 @@ int pt_clear_medium_density(pt_context* ctx) {
     if (ctx->d_grid) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(ctx->d_grid);
-        ctx->d_grid = nullptr;
+        ctx->d_grid.reset();
     }
     std::vector<float>().swap(ctx->grid);
     ctx->grid_n[0] = ctx->grid_n[1] = ctx->grid_n[2] = 0;
@@ -151,18 +146,9 @@ int pt_debug_grid(pt_context* ctx, const float* in, int64_t n, float* out) {
     if (!grid_unbounded(ctx).empty()) return fail(ctx, PT_EINVAL, "pt_debug_grid: " + grid_unbounded(ctx));
     PT_NEED_DEVICE(ctx);
     if (n == 0) return PT_OK;
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_in, d_out;
-    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * 12 * (size_t)n));
-    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 8 * (size_t)n));
-    PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(float) * 12 * (size_t)n, hipMemcpyHostToDevice));
-    PT_HIP(ctx, launch_debug_grid(medium_view(ctx), grid_view(ctx), (const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 8 * (size_t)n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_round_trip(ctx, in, sizeof(float) * 12 * (size_t)n, out, sizeof(float) * 8 * (size_t)n, [&](void* d_in, void* d_out) {
+        return launch_debug_grid(medium_view(ctx), grid_view(ctx), (const float*)d_in, n, (float*)d_out, ctx->stream);
+    });
 }
 
 int pt_debug_medium(pt_context* ctx, const float* in, int64_t n, float* out) {
@@ -171,18 +157,8 @@ int pt_debug_medium(pt_context* ctx, const float* in, int64_t n, float* out) {
     if (!medium_on(ctx)) return fail(ctx, PT_EINVAL, "pt_debug_medium: no medium with sigma_t > 0 is held (pt_set_medium)");
     PT_NEED_DEVICE(ctx);
     if (n == 0) return PT_OK;
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } d_in, d_out;
-    PT_HIP(ctx, hipMalloc(&d_in.p, sizeof(float) * 12 * (size_t)n));
-    PT_HIP(ctx, hipMalloc(&d_out.p, sizeof(float) * 10 * (size_t)n));
-    PT_HIP(ctx, hipMemcpy(d_in.p, in, sizeof(float) * 12 * (size_t)n, hipMemcpyHostToDevice));
-    PT_HIP(ctx, launch_debug_medium(medium_view(ctx), (const float*)d_in.p, n, (float*)d_out.p, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(out, d_out.p, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return debug_round_trip(ctx, in, sizeof(float) * 12 * (size_t)n, out, sizeof(float) * 10 * (size_t)n,
+                            [&](void* d_in, void* d_out) { return launch_debug_medium(medium_view(ctx), (const float*)d_in, n, (float*)d_out, ctx->stream); });
 }
 
 }  // extern "C"
