@@ -1160,6 +1160,32 @@ enum {
     PT_SPEC_DIFFUSE = 6, PT_SPEC_DIFFUSE_SK = 7, PT_SPEC_DIFFUSE_REC = 8, PT_SPEC_DIFFUSE_REC_SK = 9, PT_SPEC_FRESNEL = 10
 };
 int pt_debug_spec(pt_context* ctx, int32_t fn, int64_t n, const uint32_t* in, uint32_t* out);
+/* One iteration body of the path (prog.cl:317-366) on caller-supplied items: the device function the render kernels call at a hit
+ * (shade_hit in pt_device.hpp, without a light hook), so that the vertex -- flip, preview colour, diffuse / mirror / glass / emitter
+ * branch, factor weights, the shared normalise-and-step-off tail -- can be compared bit for bit with the CPU oracle without a render.
+ * The scene is the context's own (uploaded triangles and materials); cam and iterations are what pt_render would be given (the vertex
+ * reads cam->eye for the specular lobe and iterations == 1 for the preview colour).  instance picks the template instance:
+ * PT_SHADE_SK set = double constants pinned to scalar registers, PT_SHADE_REC set = per-triangle shading records (kd, tangent frame and
+ * the `plain` flag come from the record, as in the fused kernels with the tree in LDS).
+ *   words in, PT_SHADE_WORDS_IN = 25 per item (floats as bit patterns):
+ *     0-2 ray P.xyz   3-5 ray D.xyz   6 t of the hit   7 ti, index of the PACKED triangle hit (pt_debug_bvh_copy's order; int32)
+ *     8 LCG state (int32)   9 inside-glass flag (0 / non-zero)   10-12 factor_L   13-15 factor_B   16-18 factor_S   19-21 factor_R
+ *     22-24 colour
+ *   words out, PT_SHADE_WORDS_OUT = 23 per item:
+ *     0-2 new P.xyz   3-5 new D.xyz   6 LCG state   7 inside (0 / 1)   8-10 factor_L   11-13 factor_B   14-16 factor_S   17-19 factor_R
+ *     20-22 colour
+ * Item layout as for pt_debug_spec: one thread per item in blocks of 256 threads, no grid-stride loop: item i runs on lane i % 64 of
+ * wave i / 64, and the lanes of a last wave past n leave before any wave-level vote -- the caller decides which hits share a wave
+ * (the vertex runs one normalisation for a wave that holds several kinds of hit, and its divide / square-root cores are picked with
+ * one branch per wave).
+ * PT_EINVAL, all checked on the host before anything is launched and before the context's device is asked for: unknown instance bits,
+ * n < 0, a NULL array with n > 0, a NULL camera or one whose XM / YM are not the context's frame, triangles or materials not uploaded,
+ * a ti outside [0, packed triangles) -- never a device read.  n = 0 then returns PT_OK.  Otherwise a host-only context gives
+ * PT_ENODEVICE, and PT_SHADE_REC on a context whose launches carry no shading records (tree not staged in LDS) PT_EINVAL. */
+enum { PT_SHADE_SK = 1, PT_SHADE_REC = 2 };
+#define PT_SHADE_WORDS_IN 25
+#define PT_SHADE_WORDS_OUT 23
+int pt_debug_shade(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t instance, int64_t n, const uint32_t* in, uint32_t* out);
 /* The authored scene (what the reference keeps in Scene::tris / Scene::mats, main.cpp:366-371):
  * triangles in add order, materials, and the first triangle of every object. */
 int pt_debug_scene_sizes(const pt_context* ctx, int64_t* ntris, int64_t* nmats, int64_t* nobjs);

@@ -194,6 +194,10 @@ public:
     }
     // the spec math and sampling primitives of the kernels on n items of 32-bit words (pt_debug_spec; fn = PT_SPEC_*)
     void debug_spec(int32_t fn, int64_t n, const uint32_t* in, uint32_t* out) { ck(pt_debug_spec(ctx, fn, n, in, out)); }
+    // one iteration body of the path (shade_hit) on n items of 32-bit words (pt_debug_shade; instance = PT_SHADE_* bits)
+    void debug_shade(const pt_camera& cam, int32_t iterations, int32_t instance, int64_t n, const uint32_t* in, uint32_t* out) {
+        ck(pt_debug_shade(ctx, &cam, iterations, instance, n, in, out));
+    }
     // guide buffers of the current view (pt_render_aovs) and the a-trous filter over them (pt_denoise; p = NULL: the defaults)
     // (the view of the last render: a new Camera(globals) would move a moving camera once more)
     void render_aovs(int subpixels = 1, int specular_depth = 4) {

@@ -63,7 +63,7 @@ EXPORTS = [
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
     "pt_set_option", "pt_get_stat", "pt_debug_bvh_sizes", "pt_debug_bvh_copy", "pt_debug_wide_nodes", "pt_debug_flat_list", "pt_debug_encounter_rank", "pt_debug_tile_cost", "pt_debug_adaptive_list", "pt_debug_launch_plan",
-    "pt_debug_scene_sizes", "pt_debug_scene_copy", "pt_debug_closest_hit", "pt_debug_math", "pt_debug_spec",
+    "pt_debug_scene_sizes", "pt_debug_scene_copy", "pt_debug_closest_hit", "pt_debug_math", "pt_debug_spec", "pt_debug_shade",
     "pt_slab_pixel_count", "pt_frame_size", "pt_comm_available", "pt_comm_unique_id", "pt_comm_init", "pt_gather_frame", "pt_device_frame", "pt_read_frame",
     "pt_write_pfm", "pt_write_ppm", "pt_image_write_pfm", "pt_image_write_ppm", "pt_debug_gather_index", "pt_debug_deinterleave",
 ]
@@ -228,6 +228,7 @@ def _load():
     sig("pt_debug_gather_index", C.c_int, i32, i32, i32, i32, i64, vp)
     sig("pt_debug_math", C.c_int, vp, i32, i64, i64, vp, vp, i64)
     sig("pt_debug_spec", C.c_int, vp, i32, i64, vp, vp)
+    sig("pt_debug_shade", C.c_int, vp, vp, i32, i32, i64, vp, vp)
     sig("pt_debug_deinterleave", C.c_int, vp, vp, i64, vp)
     return L
 
@@ -302,6 +303,9 @@ PT_MATH_SQRT, PT_MATH_RSQRT, PT_MATH_DIV_GRID, PT_MATH_DIV_RANDOM, PT_MATH_DIV_N
 SPEC_WORDS = {PT_SPEC_SINCOS: (1, 2), PT_SPEC_SINCOS_SK: (1, 2), PT_SPEC_POW: (2, 1), PT_SPEC_POW_SK: (2, 1), PT_SPEC_POW5: (1, 1),
               PT_SPEC_LCG: (1, 2), PT_SPEC_DIFFUSE: (8, 8), PT_SPEC_DIFFUSE_SK: (8, 8), PT_SPEC_DIFFUSE_REC: (8, 8),
               PT_SPEC_DIFFUSE_REC_SK: (8, 8), PT_SPEC_FRESNEL: (9, 3)}
+# pt_debug_shade: instance bits, and the 32-bit words per item in and out
+PT_SHADE_SK, PT_SHADE_REC = 1, 2
+SHADE_WORDS_IN, SHADE_WORDS_OUT = 25, 23
 NEE_STRATEGIES = {"bsdf": PT_NEE_BSDF, "light": PT_NEE_LIGHT, "mis": PT_NEE_MIS}
 
 
@@ -1420,6 +1424,20 @@ class Scene:
         items = items.view(np.uint32).reshape(-1, wi)
         out = np.empty((items.shape[0], wo), dtype=np.uint32)
         self._ck(LIB.pt_debug_spec(self._h, int(fn), items.shape[0], _ptr(items), _ptr(out)))
+        return out
+
+    def debug_shade(self, instance, items, iterations=None):
+        """pt_debug_shade: shade_hit<SK, REC> (instance = PT_SHADE_SK | PT_SHADE_REC bits) on items, an (n, SHADE_WORDS_IN) array of
+        32-bit words {P.xyz, D.xyz, t, packed ti, seed, inside, L, B, S, R, colour} -> (n, SHADE_WORDS_OUT) uint32 {P.xyz, D.xyz, seed,
+        inside, L, B, S, R, colour}, with the context's scene, self.camera and iterations (default self.iterations).  Item i runs on lane
+        i % 64 of wave i / 64."""
+        items = np.ascontiguousarray(items)
+        if items.dtype.itemsize != 4:
+            raise ValueError("debug_shade: items must be 32-bit words")
+        items = items.view(np.uint32).reshape(-1, SHADE_WORDS_IN)
+        out = np.empty((items.shape[0], SHADE_WORDS_OUT), dtype=np.uint32)
+        self._ck(LIB.pt_debug_shade(self._h, _ptr(self.camera), int(self.iterations if iterations is None else iterations), int(instance),
+                                    items.shape[0], _ptr(items), _ptr(out)))
         return out
 
     def debug_encounter_rank(self, n):

@@ -1,7 +1,7 @@
 // pt_debug.hip -- test entry points of libptamd.so: closest hit of caller-supplied rays through the
 // same traversal code (pt_device.hpp) and the same node placement the render kernels use; the IEEE
 // divide / sqrt cores of pt_device.hpp against the compiler's expansions on enumerated inputs; the spec math and sampling primitives
-// of pt_device.hpp on caller-supplied items.
+// of pt_device.hpp on caller-supplied items; shade_hit itself, the vertex that joins them, on caller-supplied items.
 #include "pt_device.hpp"
 
 namespace ptamd {
@@ -192,6 +192,54 @@ hipError_t launch_debug_spec(int fn, const uint32_t* in, int64_t n, uint32_t* ou
     if (fn < 0 || fn > PT_SPEC_FRESNEL) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(kernels[fn], dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, (long long)n, out);
+    return hipGetLastError();
+}
+
+// pt_debug_shade: shade_hit<SK, REC> (NoShadeHook) on item i = the thread's index, kShadeWordsIn words in and kShadeWordsOut out per
+// item (layout in pt_api.h), floats as their bit patterns.  The host has checked every ti against p.n_tris.
+// Item layout as in k_debug_spec, which the callers' wave tests depend on: one thread per item, blocks of 256, no grid-stride loop --
+// item i runs on lane i % 64 of wave i / 64, and the lanes past n have left before shade_hit takes any wave-level vote.
+template <bool SK, bool REC>
+__global__ void __launch_bounds__(256) k_debug_shade(RenderParams p, const uint32_t* __restrict__ in, long long n, uint32_t* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* a = in + i * kShadeWordsIn;
+    uint32_t* o = out + i * kShadeWordsOut;
+    const auto v = [a](int k) { return mk(__uint_as_float(a[k]), __uint_as_float(a[k + 1]), __uint_as_float(a[k + 2])); };
+    const auto put = [o](int k, f3 w) {
+        o[k] = __float_as_uint(w.x);
+        o[k + 1] = __float_as_uint(w.y);
+        o[k + 2] = __float_as_uint(w.z);
+    };
+    f3 P = v(0), D = v(3);
+    const float t = __uint_as_float(a[6]);
+    const int ti = (int)a[7];
+    int seed = (int)a[8];
+    bool inside = a[9] != 0u;
+    PathRegs st;
+    st.fL = v(10);
+    st.fB = v(13);
+    st.fS = v(16);
+    st.fR = v(19);
+    st.color = v(22);
+    shade_hit<SK, REC>(P, D, st, seed, inside, p, p.tris, p.meta, ti, t);
+    put(0, P);
+    put(3, D);
+    o[6] = (uint32_t)seed;
+    o[7] = inside ? 1u : 0u;
+    put(8, st.fL);
+    put(11, st.fB);
+    put(14, st.fS);
+    put(17, st.fR);
+    put(20, st.color);
+}
+
+hipError_t launch_debug_shade(const RenderParams& p, int instance, const uint32_t* in, int64_t n, uint32_t* out, hipStream_t stream) {
+    using Kernel = void (*)(RenderParams, const uint32_t*, long long, uint32_t*);
+    static const Kernel kernels[] = {k_debug_shade<false, false>, k_debug_shade<true, false>, k_debug_shade<false, true>, k_debug_shade<true, true>};
+    if (instance < 0 || instance > (PT_SHADE_SK | PT_SHADE_REC)) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(kernels[instance], dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, in, (long long)n, out);
     return hipGetLastError();
 }
 

@@ -1767,6 +1767,29 @@ int pt_debug_spec(pt_context* ctx, int32_t fn, int64_t n, const uint32_t* in, ui
                             [&](void* d_in, void* d_out) { return launch_debug_spec(fn, (const uint32_t*)d_in, n, (uint32_t*)d_out, ctx->stream); });
 }
 
+int pt_debug_shade(pt_context* ctx, const pt_camera* cam, int32_t iterations, int32_t instance, int64_t n, const uint32_t* in, uint32_t* out) {
+    if (!ctx) return PT_EINVAL;
+    if (instance < 0 || instance > (PT_SHADE_SK | PT_SHADE_REC)) return fail(ctx, PT_EINVAL, "pt_debug_shade: unknown instance");
+    if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, PT_EINVAL, "pt_debug_shade: n >= 0, both arrays non-null");
+    int rc = check_ready(ctx, cam);
+    if (rc != PT_OK) return rc;
+    const int64_t n_tris = (int64_t)ctx->orig.size();
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t ti = (int32_t)in[(size_t)i * kShadeWordsIn + 7];
+        if (ti < 0 || ti >= n_tris) return fail(ctx, PT_EINVAL, "pt_debug_shade: an item's ti is outside the packed triangles");
+    }
+    if (n == 0) return PT_OK;
+    PT_NEED_DEVICE(ctx);
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    fill_params(ctx, cam, &p);
+    p.iterations = iterations;
+    if ((rc = ensure_shade_records(ctx, &p)) != PT_OK) return rc;
+    if ((instance & PT_SHADE_REC) && !p.shaderec) return fail(ctx, PT_EINVAL, "pt_debug_shade: this context's launches carry no shading records");
+    return debug_round_trip(ctx, in, sizeof(uint32_t) * kShadeWordsIn * (size_t)n, out, sizeof(uint32_t) * kShadeWordsOut * (size_t)n,
+                            [&](void* d_in, void* d_out) { return launch_debug_shade(p, instance, (const uint32_t*)d_in, n, (uint32_t*)d_out, ctx->stream); });
+}
+
 int pt_debug_closest_hit(pt_context* ctx, const pt_ray* rays, int64_t n, float* out_t, int32_t* out_tri) {
     PT_NEED_DEVICE(ctx);
     if (!rays || !out_t || !out_tri || n < 0) return fail(ctx, PT_EINVAL, "bad arguments");

@@ -367,6 +367,9 @@ constexpr int spec_words_out(int fn) {
          : fn == PT_SPEC_FRESNEL ? 3 : 0;
 }
 hipError_t launch_debug_spec(int fn, const uint32_t* in, int64_t n, uint32_t* out, hipStream_t stream);
+// pt_debug_shade (pt_debug.hip): 32-bit words per item in and out (layout in pt_api.h); instance = PT_SHADE_SK | PT_SHADE_REC bits
+constexpr int kShadeWordsIn = PT_SHADE_WORDS_IN, kShadeWordsOut = PT_SHADE_WORDS_OUT;
+hipError_t launch_debug_shade(const RenderParams& p, int instance, const uint32_t* in, int64_t n, uint32_t* out, hipStream_t stream);
 // guide buffers and the a-trous filter (pt_denoise.hip; the filter is pinned in include/pt_api.h next to pt_denoise)
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
                        int cu_count, hipStream_t stream);

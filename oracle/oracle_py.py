@@ -90,6 +90,7 @@ def lib():
     sig("orc_rand_n", None, vp, vp, vp, i64)
     sig("orc_new_ray_diffuse_n", None, vp, vp, i64)
     sig("orc_fresnel_n", None, vp, vp, i64)
+    sig("orc_shade_step_n", None, vp, vp, vp, vp, vp, i32, i64)
     sig("orc_reinhard_tone_map", None, fp, fp)
     sig("orc_filmic_tone_map", None, fp, fp)
     sig("orc_frame_create", vp, i32, i32)
@@ -181,6 +182,35 @@ def fresnel_n(items):
     out = np.zeros((items.shape[0], 4), dtype=np.float32)
     lib().orc_fresnel_n(_ptr(out), _ptr(items), items.shape[0])
     return out[:, :3]
+
+
+SHADE_WORDS_IN, SHADE_WORDS_OUT = 25, 24
+
+
+def shade_step_n(items, tris, mats, cam, iterations):
+    """orc_shade_step_n: one iteration body of trace_ray per item (n, 25) of 32-bit words {P, D, -, index into tris, seed, in, L, B, S, R,
+    color} -> (n, 24) uint32 {t of the hit, P, D, seed, in, L, B, S, R, color}; tris TRIANGLE records, mats MATERIAL records, cam a
+    CAMERA record"""
+    items = np.ascontiguousarray(items)
+    assert items.dtype.itemsize == 4
+    items = items.view(np.uint32).reshape(-1, SHADE_WORDS_IN)
+    tris, mats, cam = np.ascontiguousarray(tris, dtype=TRIANGLE), np.ascontiguousarray(mats, dtype=MATERIAL), np.ascontiguousarray(cam, dtype=CAMERA)
+    idx = items[:, 7].view(np.int32)
+    assert items.shape[0] == 0 or (idx.min() >= 0 and idx.max() < tris.shape[0] and int(tris["mati"].max()) < mats.shape[0])
+    out = np.empty((items.shape[0], SHADE_WORDS_OUT), dtype=np.uint32)
+    lib().orc_shade_step_n(_ptr(out), _ptr(items), _ptr(tris), _ptr(mats), _ptr(cam), int(iterations), items.shape[0])
+    return out
+
+
+def reinhard_n(colors):
+    """orc_reinhard_tone_map of every row of colors (n, >= 3) float32 -> (n, 4) float32"""
+    colors = np.ascontiguousarray(colors, dtype=np.float32)
+    out = np.empty((colors.shape[0], 4), dtype=np.float32)
+    L = lib()
+    fp = C.POINTER(C.c_float)
+    for i in range(colors.shape[0]):
+        L.orc_reinhard_tone_map(out[i].ctypes.data_as(fp), colors[i].ctypes.data_as(fp))
+    return out
 
 
 def make_material(kd, ks, em, N, K, shininess, mtype):

@@ -798,11 +798,60 @@ static inline void gen_ray_item(orc_frame* f, const orc_camera* cam, int id) {
     ray_out(&f->rays[id], &r);
 }
 
+/* the path state next to the ray, the LCG state and the inside-glass flag: prog.cl:307-316 */
+typedef struct { v3 factor_L, factor_B, factor_S, factor_R, color; } path_t;
+
+/* prog.cl:317-366: one iteration body of trace_ray for a hit with t > 0 -- the new ray, the LCG draws, the factors and the colour */
+static inline void shade_step(const hit_t* hit, const orc_material* mat, const orc_camera* cam, int iterations, ray_t* ray, int32_t* seed, int* in,
+                              path_t* fc) {
+    if (iterations == 1) fc->color = add(ld(&mat->kd), ld(&mat->emission));   /* prog.cl:323-325 */
+    v3 N = hit->N;
+    if (dot(ray->D, N) > 0) N = neg(N);
+    if (mat->type == 0) {                                   /* prog.cl:329-340 */
+        float rnd1 = orc_rand(seed); float rnd2 = orc_rand(seed);
+        ray_t nr = new_ray_diffuse(hit->P, N, rnd1, rnd2);
+        float intensity_diffuse = max0(dot(nr.D, N));
+        fc->factor_L = mul(fc->factor_L, scale(ld(&mat->kd), intensity_diffuse));
+        v3 view = normalize(sub(ld(&cam->eye), hit->P));
+        v3 halfway = normalize(add(view, nr.D));
+        float intensity_specular = max0(dot(N, halfway));
+        fc->factor_B = mul(fc->factor_B, scale(ld(&mat->ks), orc_spec_powf(intensity_specular, mat->shininess)));
+        *ray = nr;
+    }
+    if (mat->type == 1) {                                   /* prog.cl:341-345 */
+        ray_t old = *ray;
+        *ray = new_ray_specular(hit->P, N, &old);
+        fc->factor_S = mul(fc->factor_S, fresnel(ld(&mat->F0), N, old.D));
+    }
+    if (mat->type == 2) {                                   /* prog.cl:346-357 */
+        ray_t old = *ray;
+        int before = *in;
+        float rnd = orc_rand(seed);
+        *ray = new_ray_refractive(hit->P, N, ld(&mat->F0), mat->n, &old, in, rnd);
+        v3 F = fresnel(ld(&mat->F0), N, old.D);
+        float prob = ((F.x + F.y) + F.z) / 3.0f;
+        if (before != *in) {
+            float k = 1.0f / (1.0f - prob);
+            fc->factor_R = scale(mul(fc->factor_R, V(1.0f - F.x, 1.0f - F.y, 1.0f - F.z)), k);
+        } else {
+            float k = 1.0f / prob;
+            fc->factor_R = scale(mul(fc->factor_R, F), k);
+        }
+    }
+    if (mat->type == 3) {                                   /* prog.cl:358-366 */
+        float intensity = max0(dot(neg(ray->D), N));
+        float rnd1 = orc_rand(seed); float rnd2 = orc_rand(seed);
+        ray_t nr = new_ray_diffuse(hit->P, N, rnd1, rnd2);
+        v3 e = mul(mul(mul(ld(&mat->emission), add(fc->factor_L, fc->factor_B)), fc->factor_S), fc->factor_R);
+        fc->color = madd(e, intensity, fc->color);
+        *ray = nr;
+    }
+}
+
 /* prog.cl:292-381 for one work-item; returns the number of kd_intersect calls */
 static inline int trace_ray_item(orc_frame* f, const orc_scene* s, const orc_camera* cam, int iterations, int current_sample, int mode, int id) {
-    v3 factor_L = V(1, 1, 1), factor_B = V(1, 1, 1), factor_S = V(1, 1, 1), factor_R = V(1, 1, 1);
-    v3 color = V(0, 0, 0);
-    if (current_sample == 0) st(&f->colors[id], color);
+    path_t fc = { V(1, 1, 1), V(1, 1, 1), V(1, 1, 1), V(1, 1, 1), V(0, 0, 0) };
+    if (current_sample == 0) st(&f->colors[id], fc.color);
     int in = 0;
     int segs = 0;
     ray_t ray = ray_in(&f->rays[id]);
@@ -811,49 +860,7 @@ static inline int trace_ray_item(orc_frame* f, const orc_scene* s, const orc_cam
         hit_t hit = closest_hit(s, &ray, mode);
         ++segs;
         if (hit.t > 0) {
-            const orc_material* mat = &s->mats[hit.mati];
-            if (iterations == 1) color = add(ld(&mat->kd), ld(&mat->emission));
-            v3 N = hit.N;
-            if (dot(ray.D, N) > 0) N = neg(N);
-            if (mat->type == 0) {                                   /* prog.cl:329-340 */
-                float rnd1 = orc_rand(seed); float rnd2 = orc_rand(seed);
-                ray_t nr = new_ray_diffuse(hit.P, N, rnd1, rnd2);
-                float intensity_diffuse = max0(dot(nr.D, N));
-                factor_L = mul(factor_L, scale(ld(&mat->kd), intensity_diffuse));
-                v3 view = normalize(sub(ld(&cam->eye), hit.P));
-                v3 halfway = normalize(add(view, nr.D));
-                float intensity_specular = max0(dot(N, halfway));
-                factor_B = mul(factor_B, scale(ld(&mat->ks), orc_spec_powf(intensity_specular, mat->shininess)));
-                ray = nr;
-            }
-            if (mat->type == 1) {                                   /* prog.cl:341-345 */
-                ray_t old = ray;
-                ray = new_ray_specular(hit.P, N, &old);
-                factor_S = mul(factor_S, fresnel(ld(&mat->F0), N, old.D));
-            }
-            if (mat->type == 2) {                                   /* prog.cl:346-357 */
-                ray_t old = ray;
-                int before = in;
-                float rnd = orc_rand(seed);
-                ray = new_ray_refractive(hit.P, N, ld(&mat->F0), mat->n, &old, &in, rnd);
-                v3 F = fresnel(ld(&mat->F0), N, old.D);
-                float prob = ((F.x + F.y) + F.z) / 3.0f;
-                if (before != in) {
-                    float k = 1.0f / (1.0f - prob);
-                    factor_R = scale(mul(factor_R, V(1.0f - F.x, 1.0f - F.y, 1.0f - F.z)), k);
-                } else {
-                    float k = 1.0f / prob;
-                    factor_R = scale(mul(factor_R, F), k);
-                }
-            }
-            if (mat->type == 3) {                                   /* prog.cl:358-366 */
-                float intensity = max0(dot(neg(ray.D), N));
-                float rnd1 = orc_rand(seed); float rnd2 = orc_rand(seed);
-                ray_t nr = new_ray_diffuse(hit.P, N, rnd1, rnd2);
-                v3 e = mul(mul(mul(ld(&mat->emission), add(factor_L, factor_B)), factor_S), factor_R);
-                color = madd(e, intensity, color);
-                ray = nr;
-            }
+            shade_step(&hit, &s->mats[hit.mati], cam, iterations, &ray, seed, &in, &fc);
         } else {
             break;                                                  /* prog.cl:367-376: black environment */
         }
@@ -862,12 +869,37 @@ static inline int trace_ray_item(orc_frame* f, const orc_scene* s, const orc_cam
     /* prog.cl:379 */
     v3 acc = ld(&f->colors[id]);
     float cs = (float)current_sample, cs1 = (float)(current_sample + 1);
-    acc = V(fmaf(acc.x, cs, color.x) / cs1, fmaf(acc.y, cs, color.y) / cs1, fmaf(acc.z, cs, color.z) / cs1);
+    acc = V(fmaf(acc.x, cs, fc.color.x) / cs1, fmaf(acc.y, cs, fc.color.y) / cs1, fmaf(acc.z, cs, fc.color.z) / cs1);
     st(&f->colors[id], acc);
     /* prog.cl:380 */
     float c3[3] = { acc.x, acc.y, acc.z };
     orc_reinhard_tone_map(&f->tex[(size_t)id * 4], c3);
     return segs;
+}
+
+/* shade_step over n authored items (tests only): per item triangle_intersect on tris[item's index], then -- where it hits with t > 0,
+ * as trace_ray_item asks -- shade_step with that triangle's material; a miss leaves the state as it came.  Words as in pt_oracle.h. */
+void orc_shade_step_n(uint32_t* out, const uint32_t* items, const orc_triangle* tris, const orc_material* mats, const orc_camera* cam,
+                      int iterations, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        float a[ORC_SHADE_WORDS_IN], o[ORC_SHADE_WORDS_OUT];
+        memcpy(a, items + ORC_SHADE_WORDS_IN * i, sizeof a);
+        int32_t ti, seed; uint32_t inside;
+        memcpy(&ti, &a[7], 4); memcpy(&seed, &a[8], 4); memcpy(&inside, &a[9], 4);
+        ray_t ray; ray.P = V(a[0], a[1], a[2]); ray.D = V(a[3], a[4], a[5]);
+        path_t fc = { V(a[10], a[11], a[12]), V(a[13], a[14], a[15]), V(a[16], a[17], a[18]), V(a[19], a[20], a[21]), V(a[22], a[23], a[24]) };
+        int in = inside != 0;
+        const orc_triangle* tri = &tris[ti];
+        hit_t hit = triangle_intersect(tri, &ray);
+        if (hit.t > 0) shade_step(&hit, &mats[hit.mati], cam, iterations, &ray, &seed, &in, &fc);
+        inside = (uint32_t)in;
+        o[0] = hit.t;
+        o[1] = ray.P.x; o[2] = ray.P.y; o[3] = ray.P.z; o[4] = ray.D.x; o[5] = ray.D.y; o[6] = ray.D.z;
+        memcpy(&o[7], &seed, 4); memcpy(&o[8], &inside, 4);
+        const v3 f[5] = { fc.factor_L, fc.factor_B, fc.factor_S, fc.factor_R, fc.color };
+        for (int k = 0; k < 5; ++k) { o[9 + 3 * k] = f[k].x; o[10 + 3 * k] = f[k].y; o[11 + 3 * k] = f[k].z; }
+        memcpy(out + ORC_SHADE_WORDS_OUT * i, o, sizeof o);
+    }
 }
 
 /* ---- thread pool over rows: work-items are independent (each owns rays/rnds/colors[id]) */

@@ -123,6 +123,17 @@ void orc_spec_pow5_n(const float* x, float* out, int64_t n);
 void orc_rand_n(const int32_t* seed, int32_t* new_seed, float* rnd, int64_t n);      /* one step from each seed */
 void orc_new_ray_diffuse_n(orc_ray* out, const float* items, int64_t n);    /* items: 8 floats each, P.xyz N.xyz rnd1 rnd2 */
 void orc_fresnel_n(orc_f3* out, const float* items, int64_t n);             /* items: 9 floats each, F0.xyz N.xyz D.xyz */
+/* One iteration body of trace_ray (prog.cl:317-366, the `hit.t > 0` part; the same static function trace_ray calls) on n authored
+ * items of 32-bit words, floats as their bit patterns.  Per item: triangle_intersect (prog.cl:94-112) of the item's ray with
+ * tris[index], then, if it hit with t > 0, the step with material mats[that triangle's mati]; a miss returns the state unchanged.
+ *   in,  ORC_SHADE_WORDS_IN = 25:   0-2 P  3-5 D  6 (not read)  7 index into tris (int32)  8 LCG state (int32)  9 `in` flag
+ *                                   10-12 factor_L  13-15 factor_B  16-18 factor_S  19-21 factor_R  22-24 color
+ *   out, ORC_SHADE_WORDS_OUT = 24:  0 the hit's t (-1: miss)  1-3 new P  4-6 new D  7 LCG state  8 `in` (0 / 1)
+ *                                   9-11 factor_L  12-14 factor_B  15-17 factor_S  18-20 factor_R  21-23 color */
+#define ORC_SHADE_WORDS_IN 25
+#define ORC_SHADE_WORDS_OUT 24
+void orc_shade_step_n(uint32_t* out, const uint32_t* items, const orc_triangle* tris, const orc_material* mats, const orc_camera* cam,
+                      int iterations, int64_t n);
 
 /* ---- frame buffers + kernels */
 orc_frame* orc_frame_create(int width, int height);
