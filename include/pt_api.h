@@ -986,6 +986,55 @@ int pt_denoise_temporal(pt_context* ctx, const pt_denoise_variance_params* p);
 /* host only: steps 2-3 for pixel (x, y) of cur at depth into prev: out = {x', y', sqrtf(v.v)}; PT_EINVAL when a <= 0 */
 int pt_debug_reproject(const pt_camera* cur, const pt_camera* prev, int32_t x, int32_t y, float depth, float out[3]);
 
+/* ---- variance-gated firefly filter (new: a post-process stage between a frame, or a temporal result, and the variance-guided filter;
+ * the estimator is untouched) -----
+ * pt_despeckle finds pixels whose luminance stands out of a robust statistic of their neighbourhood, confirms them with the pixel's
+ * own variance (a converged small highlight has a small relative variance, a firefly a relative standard deviation of about 1), scales
+ * them down to the limit and, with spread on, hands the removed energy to the window around them, so the frame's sum is kept.
+ * Input per pixel p = (x, y) of a W x H frame, index y W + x: colour c(p) and the variance of the mean luminance v(p), >= 0 or +inf.
+ * All arithmetic float32, fmaf where written (kernel k_despeckle):
+ *   1. l(p) = fmaf(0.0722f, b, fmaf(0.7152f, g, 0.2126f * r)) (the l pinned for the moments).  p is live iff l(p) is finite.  A pixel
+ *      that is not live is copied through bit for bit, colour and v, and gets flag 2; it is treated as outside the frame everywhere
+ *      below: nobody's neighbour, not counted, gives nothing and receives nothing.
+ *   2. The neighbours of p: the live in-frame q != p with |dx|, |dy| <= radius; K(p) their number; m(p) the rank-th largest l(q) among
+ *      them, counted with multiplicity, the smallest of them when K < rank; T(p) = fmaf(threshold, m(p), floor).
+ *   3. p is flagged (flag 1) iff it is live, K > 0, l(p) > T(p) and the variance gate passes: min_rel_sigma == 0, or v(p) == +inf, or
+ *      v(p) >= (min_rel_sigma * l(p)) * (min_rel_sigma * l(p)).
+ *   4. Flagged: s = T / l (IEEE divide), c' = c * s, e = c - c' per channel, v' = +inf if v == +inf, else (v * s) * s.  Not flagged:
+ *      c' = c, e = 0, v' = v.
+ *   5. spread == 0: the output is c', v'.
+ *   6. spread == 1: n(p) = the live in-frame pixels with |dx|, |dy| <= radius, p included; share(p) = e(p) / (float)n(p) per channel.
+ *      For every live q, over p = q + (dx, dy) in raster order (dy outer from -radius, dx inner, the centre included), flagged p only:
+ *      acc_c += share(p), acc_v = fmaf(ls, ls, acc_v) with ls = l(share(p)), both from 0.  The output is c'(q) + acc_c, v'(q) + acc_v.
+ *      A flagged pixel receives its own share.  The excess counts as a one-sample event, so its variance is its square: the luminance
+ *      term of the filter that follows is loose where energy landed, and spreads it further.  Windows are symmetric over live pixels,
+ *      so the sum of the output is the sum of c up to rounding.
+ * No atomics, deterministic: two runs give the same bits.  The result does not depend on how the kernel tiles the frame. */
+typedef struct { int32_t source, radius, rank; float threshold, floor, min_rel_sigma; int32_t spread; } pt_despeckle_params;   /* 28 bytes */
+enum { PT_DESPECKLE_FRAME = 0, PT_DESPECKLE_TEMPORAL = 1 };
+/* source FRAME, radius 2, rank 2, threshold 4, floor 0, min_rel_sigma 0.5, spread 1: trial values, not yet replaced by the best point
+ * of the sweep of tools/despeckle_bench.py (profiles/despeckle/README.md) */
+void pt_despeckle_defaults(pt_despeckle_params* p);
+/* Source PT_DESPECKLE_FRAME reads colors (the bound framebuffer, if any) and pt_read_variance's v; PT_DESPECKLE_TEMPORAL the last
+ * pt_temporal_accumulate's colour and variance.  It needs no guides.  The result goes to a buffer of its own (colour + variance, the
+ * variance once more for the filter, flags: 24 B/px, allocated on first use); colors, rnds, the denoised buffers and the temporal sets
+ * are never written, and the variance read-out is refreshed as by pt_read_variance.  World-1 contexts only.  Checked in this order:
+ * PT_EINVAL for params NULL, radius or rank outside 1..3, threshold < 1, floor < 0, min_rel_sigma < 0 (or any of them NaN), spread or
+ * source outside {0, 1}, and world; PT_ENODEVICE on a host-only context; then PT_EINVAL under the source's rule: pt_read_variance's
+ * (moments not valid, no samples) for FRAME, no accumulate yet for TEMPORAL. */
+int pt_despeckle(pt_context* ctx, const pt_despeckle_params* p);
+/* the last pt_despeckle's result: rgbv {r, g, b, v} 16 B per local pixel, flags 0 / 1 / 2; either pointer may be NULL */
+int pt_read_despeckled(pt_context* ctx, float* rgbv, int32_t* flags, int64_t npix);
+void* pt_device_despeckled(pt_context* ctx);    /* {r, g, b, v} 16 B per local pixel on the device; NULL before the first pt_despeckle */
+/* pt_denoise_variance's filter (same parameters, same guides, same output: pt_read_denoised / pt_device_denoised) run on the despeckled
+ * colour and variance, as pt_denoise_temporal runs it on the temporal result.  PT_EINVAL under the filter's rules (parameters, guides),
+ * without a despeckled result, and when the result is stale: a launch has written colors or a frame has started since, a newer
+ * accumulate ran (source TEMPORAL), or the scene was uploaded. */
+int pt_denoise_despeckled(pt_context* ctx, const pt_denoise_variance_params* p);
+/* the same kernel on a caller's frame rgbv_in ({r, g, b, v} per pixel, 1 <= w, h <= 4096) -> rgbv_out, flags; source is ignored, the
+ * other parameters are checked as above (PT_EINVAL before PT_ENODEVICE) */
+int pt_debug_despeckle(pt_context* ctx, const float* rgbv_in, int32_t w, int32_t h, const pt_despeckle_params* p, float* rgbv_out, int32_t* flags);
+
 /* ---- multi-GPU frame assembly (SURVEY 8b "RCCL communicator per context", 8e) ----------
  * The reference is single-device (main.cpp:466-476); a host that tiles the frame over N contexts with
  * pt_create_tiled assembles it with these.  One process (or thread) per GPU:

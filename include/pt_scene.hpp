@@ -252,6 +252,19 @@ public:
         pt_denoise_variance_defaults(&d);
         ck(pt_denoise_temporal(ctx, p ? p : &d));
     }
+    // the variance-gated firefly filter (pt_despeckle; p = NULL: the defaults) on the frame, or with p->source = PT_DESPECKLE_TEMPORAL on
+    // the last accumulate; the result: pt_read_despeckled / pt_device_despeckled
+    void despeckle(const pt_despeckle_params* p = nullptr) {
+        pt_despeckle_params d;
+        pt_despeckle_defaults(&d);
+        ck(pt_despeckle(ctx, p ? p : &d));
+    }
+    // the variance-guided filter on the despeckled colour and variance (pt_denoise_despeckled); result: pt_read_denoised like denoise()
+    void denoise_despeckled(const pt_denoise_variance_params* p = nullptr) {
+        pt_denoise_variance_params d;
+        pt_denoise_variance_defaults(&d);
+        ck(pt_denoise_despeckled(ctx, p ? p : &d));
+    }
     int current_sample() { int32_t s = 0; ck(pt_get_current_sample(ctx, &s)); return s; }
     void reset_samples() { ck(pt_set_current_sample(ctx, 0)); }                                // main.cpp:1046
     void finish() { ck(pt_sync(ctx)); }                                                        // queue.finish(), main.cpp:675

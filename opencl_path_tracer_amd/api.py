@@ -59,6 +59,7 @@ EXPORTS = [
     "pt_debug_light_tree", "pt_debug_light_tree_eval",
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
+    "pt_despeckle_defaults", "pt_despeckle", "pt_read_despeckled", "pt_device_despeckled", "pt_denoise_despeckled", "pt_debug_despeckle",
     "pt_render_aovs", "pt_read_aovs", "pt_aov_defaults", "pt_render_aovs_ex", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
@@ -178,6 +179,12 @@ def _load():
     sig("pt_read_temporal", C.c_int, vp, vp, vp, i64)
     sig("pt_device_temporal", vp, vp)
     sig("pt_denoise_temporal", C.c_int, vp, vp)
+    sig("pt_despeckle_defaults", None, vp)
+    sig("pt_despeckle", C.c_int, vp, vp)
+    sig("pt_read_despeckled", C.c_int, vp, vp, vp, i64)
+    sig("pt_device_despeckled", vp, vp)
+    sig("pt_denoise_despeckled", C.c_int, vp, vp)
+    sig("pt_debug_despeckle", C.c_int, vp, vp, i32, i32, vp, vp, vp)
     sig("pt_debug_reproject", C.c_int, vp, vp, i32, i32, f32, fp)
     sig("pt_render_aovs", C.c_int, vp, vp, i32, i32)
     sig("pt_read_aovs", C.c_int, vp, vp, vp, i64)
@@ -556,6 +563,35 @@ def temporal_defaults():
     p = TemporalParams()
     LIB.pt_temporal_defaults(C.byref(p))
     return p.as_dict()
+
+
+PT_DESPECKLE_FRAME, PT_DESPECKLE_TEMPORAL = 0, 1
+DESPECKLE_SOURCE = {"frame": PT_DESPECKLE_FRAME, "temporal": PT_DESPECKLE_TEMPORAL}
+
+
+class DespeckleParams(C.Structure):
+    """pt_despeckle_params (include/pt_api.h)."""
+    _fields_ = [("source", C.c_int32), ("radius", C.c_int32), ("rank", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float),
+                ("min_rel_sigma", C.c_float), ("spread", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def despeckle_defaults():
+    """pt_despeckle_defaults as a dict: source, radius, rank, threshold, floor, min_rel_sigma, spread."""
+    p = DespeckleParams()
+    LIB.pt_despeckle_defaults(C.byref(p))
+    return p.as_dict()
+
+
+def _despeckle_params(who, params):
+    p = DespeckleParams(**despeckle_defaults())
+    for k, v in params.items():
+        if k not in p.as_dict():
+            raise TypeError("unknown %s parameter %r" % (who, k))
+        setattr(p, k, DESPECKLE_SOURCE.get(v, v) if k == "source" and isinstance(v, str) else v)
+    return p
 
 
 def debug_reproject(cur, prev, x, y, depth):
@@ -1252,6 +1288,49 @@ class Scene:
             setattr(p, k, v)
         self._ck(LIB.pt_denoise_temporal(self._h, C.byref(p)))
         return self.read_denoised()
+
+    # -- variance-gated firefly filter (include/pt_api.h pins it)
+    def despeckle(self, **params):
+        """pt_despeckle with pt_despeckle_defaults overridden by params (source: PT_DESPECKLE_FRAME / PT_DESPECKLE_TEMPORAL or "frame" /
+        "temporal"): clips the pixels that stand out of their neighbourhood and whose own variance confirms it, and with spread hands
+        the clipped energy to the window around them.  Returns (rgbv, flags) like read_despeckled()."""
+        p = _despeckle_params("despeckle", params)
+        self._ck(LIB.pt_despeckle(self._h, C.byref(p)))
+        return self.read_despeckled()
+
+    def read_despeckled(self):
+        """(rgbv (local_pixels, 4) float32 {r, g, b, variance of the mean}, flags (local_pixels,) int32: 0 kept, 1 clipped, 2 not live)
+        of the last despeckle."""
+        rgbv = np.empty((self.local_pixels, 4), dtype=np.float32)
+        flags = np.empty(self.local_pixels, dtype=np.int32)
+        self._ck(LIB.pt_read_despeckled(self._h, _ptr(rgbv), _ptr(flags), flags.size))
+        return rgbv, flags
+
+    def device_despeckled(self):
+        """Device pointer of the last despeckle's {r, g, b, v} per local pixel (None before the first)."""
+        return LIB.pt_device_despeckled(self._h)
+
+    def denoise_despeckled(self, **params):
+        """denoise_variance's filter (same params) on the last despeckle's colour and variance; returns like denoise_variance."""
+        p = DenoiseVarianceParams(**denoise_variance_defaults())
+        for k, v in params.items():
+            if k not in p.as_dict():
+                raise TypeError("unknown denoise_despeckled parameter %r" % k)
+            setattr(p, k, v)
+        self._ck(LIB.pt_denoise_despeckled(self._h, C.byref(p)))
+        return self.read_denoised()
+
+    def debug_despeckle(self, rgbv, **params):
+        """pt_debug_despeckle: the despeckle kernel on a caller's frame rgbv (h, w, 4) float32 {r, g, b, v}; source is ignored.
+        Returns (rgbv (h, w, 4), flags (h, w))."""
+        a = np.ascontiguousarray(rgbv, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("rgbv must have shape (h, w, 4)")
+        p = _despeckle_params("debug_despeckle", params)
+        out = np.empty_like(a)
+        flags = np.empty(a.shape[:2], dtype=np.int32)
+        self._ck(LIB.pt_debug_despeckle(self._h, _ptr(a), a.shape[1], a.shape[0], C.byref(p), _ptr(out), _ptr(flags)))
+        return out, flags
 
     def read_denoised(self):
         out = np.empty((self.local_pixels, 4), dtype=np.float32)

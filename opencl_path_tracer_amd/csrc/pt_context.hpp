@@ -189,6 +189,15 @@ struct pt_context {
     pt_camera temporal_cam = {};        // the camera of that history
     uint64_t temporal_frame = ~0ull;    // frame_serial of the last accumulate
     uint64_t temporal_aov = ~0ull;      // aov_serial of the guides it used
+    // the firefly filter (pt_despeckle), allocated on first use: per local pixel {r, g, b, v}, then v once more as a float array (the
+    // variance-guided filter's input), then the flags (24 B).  The result is current (pt_denoise_despeckled) while despeckle_valid --
+    // pt_upload_triangles / pt_upload_materials clear it -- and the three serials below are what they were
+    DeviceArray<float4> d_despeckle;
+    bool despeckle_valid = false;
+    int32_t despeckle_source = 0;
+    uint64_t despeckle_epoch = 0;            // render_epoch: no launch has written colors since
+    uint64_t despeckle_frame = 0;            // frame_serial: no frame has started since
+    uint64_t despeckle_temporal = 0;         // temporal_frame (source PT_DESPECKLE_TEMPORAL): no newer accumulate ran
     // next-event estimation (pt_render_nee): the light table, built on the host at first use after an upload (nee_valid).  Packed
     // triangle index and cdf per light; P_sel / area per packed triangle (0 for non-lights).  Device copies allocated with it.
     std::vector<int32_t> nee_tri;

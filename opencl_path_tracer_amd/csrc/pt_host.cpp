@@ -262,6 +262,7 @@ int pt_add_triangles(pt_context* ctx, const pt_triangle* t, int64_t n) {
 int pt_upload_materials(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
     ctx->aov_valid = false;
+    ctx->despeckle_valid = false;    // (pt_despeckle's result is a frame of the old scene)
     ctx->nee_valid = false;          // the light table reads emission and type
     ctx->tex_dirty = true;           // and the bindings on the device the type
     ctx->interior_dirty = true;      // (the interiors' table too)
@@ -744,6 +745,132 @@ int pt_denoise_temporal(pt_context* ctx, const pt_denoise_variance_params* dp) {
         return fail(ctx, PT_EINVAL, "pt_denoise_temporal: pt_temporal_accumulate has not run on the current guides");
     PT_HIP(ctx, hipSetDevice(ctx->device));
     return atrous_var_iterations(ctx, dp, temporal_colour(ctx, ctx->temporal_out), ctx->d_temporal_var);
+}
+
+// ---- variance-gated firefly filter (kernel k_despeckle, pt_despeckle.hip; pinned in include/pt_api.h)
+void pt_despeckle_defaults(pt_despeckle_params* p) {
+    if (!p) return;
+    p->source = PT_DESPECKLE_FRAME;
+    p->radius = 2;
+    p->rank = 2;
+    p->threshold = 4.0f;
+    p->floor = 0.0f;
+    p->min_rel_sigma = 0.5f;
+    p->spread = 1;
+}
+// the arguments of the firefly filter: "" or what is wrong (pt_despeckle, pt_debug_despeckle)
+static std::string despeckle_params_error(const pt_despeckle_params* dp) {
+    if (!dp) return "params is NULL";
+    if (dp->radius < 1 || dp->radius > 3) return "radius must be 1..3";
+    if (dp->rank < 1 || dp->rank > 3) return "rank must be 1..3";
+    if (!(dp->threshold >= 1.0f)) return "threshold must be >= 1 (and not NaN)";
+    if (!(dp->floor >= 0.0f)) return "floor must be >= 0 (and not NaN)";
+    if (!(dp->min_rel_sigma >= 0.0f)) return "min_rel_sigma must be >= 0 (and not NaN)";
+    if (dp->spread != 0 && dp->spread != 1) return "spread must be 0 or 1";
+    if (dp->source != PT_DESPECKLE_FRAME && dp->source != PT_DESPECKLE_TEMPORAL) return "source must be PT_DESPECKLE_FRAME or PT_DESPECKLE_TEMPORAL";
+    return "";
+}
+// the three parts of d_despeckle: {r, g, b, v}, v, flags per local pixel
+static float* despeckle_var(const pt_context* ctx) { return reinterpret_cast<float*>(ctx->d_despeckle + (size_t)std::max<int64_t>(ctx->npix, 1)); }
+static int32_t* despeckle_flags(const pt_context* ctx) { return reinterpret_cast<int32_t*>(despeckle_var(ctx) + (size_t)std::max<int64_t>(ctx->npix, 1)); }
+static void despeckle_args(const pt_despeckle_params* dp, DespeckleArgs* a) {
+    a->rank = dp->rank;
+    a->threshold = dp->threshold;
+    a->floor_ = dp->floor;
+    a->min_rel_sigma = dp->min_rel_sigma;
+}
+int pt_despeckle(pt_context* ctx, const pt_despeckle_params* dp) {
+    if (!ctx) return PT_EINVAL;
+    const std::string why = despeckle_params_error(dp);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_despeckle: " + why);
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_despeckle: contexts of one rank (world == 1) only");
+    PT_NEED_DEVICE(ctx);
+    DespeckleArgs a;
+    if (dp->source == PT_DESPECKLE_TEMPORAL) {
+        if (ctx->temporal_out < 0) return fail(ctx, PT_EINVAL, "pt_despeckle: pt_temporal_accumulate has not run");
+        PT_HIP(ctx, hipSetDevice(ctx->device));
+        a.c = temporal_colour(ctx, ctx->temporal_out);
+        a.v = ctx->d_temporal_var;
+    } else {
+        const int rc = compute_variance(ctx, "pt_despeckle");          // (checks the moments)
+        if (rc != PT_OK) return rc;
+        a.c = ctx->d_colors;
+        a.v = ctx->d_variance;
+    }
+    const size_t np = (size_t)std::max<int64_t>(ctx->npix, 1);
+    static_assert(sizeof(float4) + sizeof(float) + sizeof(int32_t) == 24, "colour + variance, the variance, the flag: 24 B per local pixel");
+    PT_ALLOC(ctx, ctx->d_despeckle.reserve((np * 24 + sizeof(float4) - 1) / sizeof(float4)));
+    a.out = ctx->d_despeckle;
+    a.out_v = despeckle_var(ctx);
+    a.flags = despeckle_flags(ctx);
+    a.W = ctx->W;
+    a.H = ctx->local_rows;
+    despeckle_args(dp, &a);
+    ctx->despeckle_valid = false;
+    PT_HIP(ctx, launch_despeckle(a, dp->radius, dp->spread, ctx->stream));
+    ctx->despeckle_valid = true;
+    ctx->despeckle_source = dp->source;
+    ctx->despeckle_epoch = ctx->render_epoch;
+    ctx->despeckle_frame = ctx->frame_serial;
+    ctx->despeckle_temporal = ctx->temporal_frame;
+    return PT_OK;
+}
+int pt_read_despeckled(pt_context* ctx, float* rgbv, int32_t* flags, int64_t npix) {
+    PT_NEED_DEVICE(ctx);
+    if (npix != ctx->npix) return fail(ctx, PT_EINVAL, "npix must equal the local pixel count");
+    if (!ctx->d_despeckle) return fail(ctx, PT_EINVAL, "pt_read_despeckled: pt_despeckle has not run");
+    int rc = PT_OK;
+    if (rgbv && (rc = read_back(ctx, rgbv, ctx->d_despeckle, sizeof(float4) * (size_t)npix)) != PT_OK) return rc;
+    if (flags && (rc = read_back(ctx, flags, despeckle_flags(ctx), sizeof(int32_t) * (size_t)npix)) != PT_OK) return rc;
+    return PT_OK;
+}
+void* pt_device_despeckled(pt_context* ctx) { return ctx ? (void*)ctx->d_despeckle.get() : nullptr; }
+int pt_denoise_despeckled(pt_context* ctx, const pt_denoise_variance_params* dp) {
+    if (!ctx) return PT_EINVAL;
+    const std::string why = variance_params_error(dp);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_denoise_despeckled: " + why);
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_denoise_despeckled: contexts of one rank (world == 1) only");
+    PT_NEED_DEVICE(ctx);
+    if (!ctx->aov_valid)
+        return fail(ctx, PT_EINVAL, "pt_denoise_despeckled: no guides (pt_render_aovs has not run since the scene was last uploaded)");
+    if (!ctx->d_despeckle || !ctx->despeckle_valid) return fail(ctx, PT_EINVAL, "pt_denoise_despeckled: pt_despeckle has not run on the scene as uploaded");
+    if (ctx->despeckle_epoch != ctx->render_epoch || ctx->despeckle_frame != ctx->frame_serial)
+        return fail(ctx, PT_EINVAL, "pt_denoise_despeckled: the despeckled result is stale (a launch has written colors since pt_despeckle)");
+    if (ctx->despeckle_source == PT_DESPECKLE_TEMPORAL && ctx->despeckle_temporal != ctx->temporal_frame)
+        return fail(ctx, PT_EINVAL, "pt_denoise_despeckled: the despeckled result is stale (a newer pt_temporal_accumulate ran)");
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    return atrous_var_iterations(ctx, dp, ctx->d_despeckle, despeckle_var(ctx));
+}
+int pt_debug_despeckle(pt_context* ctx, const float* rgbv_in, int32_t w, int32_t h, const pt_despeckle_params* dp, float* rgbv_out, int32_t* flags) {
+    if (!ctx) return PT_EINVAL;
+    pt_despeckle_params p = {};
+    if (dp) {
+        p = *dp;
+        p.source = PT_DESPECKLE_FRAME;       // (ignored)
+    }
+    const std::string why = despeckle_params_error(dp ? &p : nullptr);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_debug_despeckle: " + why);
+    if (w < 1 || w > 4096 || h < 1 || h > 4096) return fail(ctx, PT_EINVAL, "pt_debug_despeckle: w and h must be 1..4096");
+    if (!rgbv_in || !rgbv_out || !flags) return fail(ctx, PT_EINVAL, "pt_debug_despeckle: NULL argument");
+    PT_NEED_DEVICE(ctx);
+    const size_t n = (size_t)w * (size_t)h;
+    std::vector<float4> out(n + (n + 3) / 4);        // {r, g, b, v} per pixel, then the flags
+    const int rc = debug_round_trip(ctx, rgbv_in, sizeof(float4) * n, out.data(), sizeof(float4) * out.size(), [&](void* d_in, void* d_out) {
+        DespeckleArgs a;
+        a.c = static_cast<const float4*>(d_in);
+        a.v = nullptr;
+        a.out = static_cast<float4*>(d_out);
+        a.out_v = nullptr;
+        a.flags = reinterpret_cast<int32_t*>(a.out + n);
+        a.W = w;
+        a.H = h;
+        despeckle_args(&p, &a);
+        return launch_despeckle(a, p.radius, p.spread, ctx->stream);
+    });
+    if (rc != PT_OK) return rc;
+    std::memcpy(rgbv_out, out.data(), sizeof(float4) * n);
+    std::memcpy(flags, out.data() + n, sizeof(int32_t) * n);
+    return PT_OK;
 }
 int pt_debug_reproject(const pt_camera* cur, const pt_camera* prev, int32_t x, int32_t y, float depth, float out[3]) {
     if (!cur || !prev || !out) return fail(nullptr, PT_EINVAL, "pt_debug_reproject: NULL argument");

@@ -672,6 +672,18 @@ struct TemporalArgs {
     float max_history, normal_cos, depth_tolerance;
 };
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
+// the variance-gated firefly filter (pt_despeckle.hip; pinned in include/pt_api.h next to pt_despeckle)
+struct DespeckleArgs {
+    const float4* c;               // the input colour, .xyz
+    const float* v;                // the variance of its mean luminance, or null: c[].w
+    float4* out;                   // {r, g, b, v}
+    float* out_v;                  // v once more, 4 B per pixel (what the variance-guided filter's first iteration reads), or null
+    int32_t* flags;
+    int32_t W, H;
+    int32_t rank;
+    float threshold, floor_, min_rel_sigma;
+};
+hipError_t launch_despeckle(const DespeckleArgs& a, int32_t radius, int32_t spread, hipStream_t stream);
 // float32 dot / cross with the fma placement of pt_device.hpp's dot3 / cross3
 __host__ __device__ __forceinline__ float rp_dot(const float* a, const float* b) { return __builtin_fmaf(a[2], b[2], __builtin_fmaf(a[1], b[1], a[0] * b[0])); }
 __host__ __device__ __forceinline__ void rp_cross(const float* a, const float* b, float* r) {
