@@ -335,6 +335,97 @@ int pt_clear_lights(pt_context* ctx);
  * (the light table is built if the scene is uploaded, else taken as empty).  Any pointer but n may be NULL */
 int pt_debug_lights(pt_context* ctx, float* records, float* cdf, float* P_light, int64_t cap, int64_t* n, float* P_ana);
 
+/* ---- sphere lights and suns with an angular size for pt_render_nee (new: opt-in with pt_set_area_lights) ----
+ * A set of area lights: spheres of uniform radiance L that emit outwards, and suns, discs of angular radius a at infinity.  Unlike the
+ * analytic lights above they have an extent: their shadows are soft, the camera, mirrors and glass see them, and the BSDF strategy finds
+ * them, so they are balanced against it under MIS like triangle lights.  Only pt_render_nee (every strategy, PT_NEE_BSDF included) and the
+ * NEE path of pt_render_adaptive_ex draw them.  Without a set -- never set, cleared, count 0, or every light black -- every path launches
+ * the kernels it launched before and computes what it computed before, bit for bit.  Stated in the reference's integrand, as the estimator
+ * of pt_render_nee is: a lobe vertex adds radiance x (fL' + fB') fS' fR' and does not divide by p_b.
+ * Table: spheres are sorted before suns (stable).  A light's selection weight is `weight`, or when that is 0 (r + g + b) 4 pi^2 R^2 for a
+ *   sphere (its power) and (r + g + b) 2 pi (1 - cos a) for a sun (its irradiance), in double.  The cdf is float, proportional to the
+ *   running weight (1 from the last pickable light on); P_light(j) = (ceil(cdf[j] 2^24) - ceil(cdf[j-1] 2^24)) / 2^24, the counting rule
+ *   of the light table.  A black light stays in the set and is never picked.  The host stores, per sun, the unit axis -direction
+ *   (normalised in double), cos a and q = 2 sin^2(a / 2), each computed in double and rounded to float.
+ * Selection, at a lobe vertex and at a scatter vertex of the medium, on segment k with k + 1 < iterations, strategies LIGHT and MIS:
+ *   u_area = pt_nee_rand(S ^ PT_AREA_KEY, k, 0) >> 8 times 2^-24.  u_area < P_area: the area set is sampled.  Otherwise everything happens
+ *   that happened before, with every p_l times 1 - P_area: in the analytic, sky, light-table and light-tree samples, and in W_b of emitter
+ *   hits and sky misses.  P_area = ceil(select 2^24) / 2^24; 1 when nothing else is pickable (an empty light table, no environment with a
+ *   distribution, no pickable analytic light); 0 when no area light is pickable.  Inside the set u0 = pt_nee_rand(S, k, 0) picks the first
+ *   light with cdf > u0, and u1, u2 (dimensions 1, 2 of S) place the sample.  Nothing is drawn from the LCG.
+ * Sphere sample from o (the offset origin every light sample uses; a scatter vertex itself): c = C - o, d^2 = c.c; rejected unless d^2
+ *   is finite and d^2 > R^2 (a sphere is transparent from inside).  s^2 = R^2 / d^2, cos_m = sqrt(max(0, 1 - s^2)), q = s^2 / (1 + cos_m)
+ *   (= 1 - cos_m without cancellation).  cos t = 1 - u1 q, sin t = sqrt(max(0, 1 - cos^2 t)), phi = 2 pi u2;
+ *   w = A cos t + Z sin t sin phi + X sin t cos phi in the frame (Z, X) of A = normalize(c) that the cosine-lobe sampler builds
+ *   (prog.cl:205-212; w is not renormalised).  p_omega = 1 / (2 pi q), p_l = P_area P_light p_omega.  The cut is
+ *   t_s = b - sqrt(max(0, b^2 - (d^2 - R^2))), b = c.w.  Rejected unless N.w > 0 (and above the geometric surface under smooth_normals); a
+ *   scatter vertex of the medium tests no cosine.
+ * Sun sample: the same cone around the stored axis with the stored q; no cut.
+ * Visibility: an area sphere is opaque on the NEE path.  A sample of sphere j counts iff no triangle is hit nearer than t_s and no other
+ *   sphere of the set whose outside holds o is met before t_s (sphere i is met at t_i = b_i - sqrt(b_i^2 - (d_i^2 - R_i^2)) when that
+ *   discriminant is >= 0 and t_i > 0).  Every other shadow ray of the path -- triangle-light, sky, analytic-light and sun samples -- is
+ *   blocked by a sphere met before its own limit as well.  Suns occlude nothing.
+ * Contribution: L (fL' + fB') fS' fR' T W_l, T the transmittance the shadow ray takes in a medium; W_l = p_b / p_l in LIGHT,
+ *   p_b p_l / (p_b^2 + p_l^2) in MIS (the power heuristic of the triangle lights).
+ * BSDF side: after the closest-hit search of a segment from P along D returned t_tri (+inf on a miss), the nearest sphere with P outside it
+ *   and 0 < t_i < t_tri ends the segment in the triangle's place, before the free flight of a medium or an interior looks at the segment's
+ *   length.  A segment that reaches the sphere ends the path: on segment 0 it adds L; else L (fL + fB) fS fR W_b (no |cos_y|; the form of a
+ *   sky miss), W_b = 1 unless the previous vertex was a lobe vertex in LIGHT or MIS: then 0 in LIGHT when p_l > 0 and p_b^2 / (p_b^2 +
+ *   p_l^2) in MIS, p_l the sphere's density seen from P.  On a miss every sun with dot(D, axis) >= cos a adds its L likewise, each with
+ *   its own W_b; then the sky adds as before.
+ *   A segment inside a dielectric (between a refraction in and the boundary it would leave through) is cut by a sphere light in the same
+ *   way: the interior bound to that boundary's material absorbs and scatters over the cut length.  Spheres are not clipped against
+ *   objects; one that overlaps a bound object shines inside it.
+ * A path that ends on a sphere makes no further LCG draw: rnds and rays after a frame are pt_render's for paths that meet no sphere.
+ * PT_NEE_BSDF takes no light sample and has W_b = 1; it is allowed with an area set (and still refused while a delta set is held).
+ * While a set with a pickable light is held, pt_render, pt_generate_rays, pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex with
+ * PT_ADAPT_PATH_RENDER return PT_EINVAL naming pt_clear_area_lights, checked before the device.
+ * Not done: the guides, the denoisers, temporal accumulation and the despeckle stage keep the view without the lights.
+ * The set lives in the context like the analytic set: uploads keep it, every rank of a tiled frame sets its own copy, a host-only context
+ * validates and stores. */
+#define PT_AREA_LIGHT_SPHERE 0
+#define PT_AREA_LIGHT_SUN 1
+#define PT_AREA_LIGHTS_MAX 64   /* small on purpose: every path segment tests every sphere */
+#define PT_AREA_KEY 0x9e3779b9u /* u_area's key is S ^ PT_AREA_KEY (taken: S, ~S, S ^ 0x5bd1e995) */
+typedef struct {
+    int32_t type;
+    float position[3];          /* SPHERE: the centre */
+    float direction[3];         /* SUN: the way the light travels.  Need not be unit, must be non-zero */
+    float radiance[3];          /* the uniform emitted radiance L */
+    float size;                 /* SPHERE: the radius, > 0; SUN: the angular radius a in radians, 0 < a <= pi / 2 */
+    float weight;               /* selection weight; 0 = automatic (see above) */
+} pt_area_light;                /* 48 bytes */
+typedef struct { float select; } pt_area_lights_params;      /* pt_area_lights_defaults: select = 0.5 */
+void pt_area_lights_defaults(pt_area_lights_params* p);
+/* Replaces the whole set (count == 0 is pt_clear_area_lights); p = NULL: the defaults.  A device context uploads the records; PT_EHIP if
+ * that fails, and the context then holds no set (as pt_set_lights).  PT_EINVAL, with the set left as it was, in this
+ * order: lights NULL with count > 0 (after count < 0 or above PT_AREA_LIGHTS_MAX), select outside [0, 1], then per light an unknown
+ * type, a non-finite field, a negative radiance, a negative weight, a size outside its range, a zero direction of a sun */
+int pt_set_area_lights(pt_context* ctx, const pt_area_light* lights, int32_t count, const pt_area_lights_params* p);
+int pt_clear_area_lights(pt_context* ctx);
+/* what the kernel samples (host data): *n = lights in the set; for the first min(cap, *n) lights in table order, records = 12 floats each
+ * as uploaded (sphere {C.xyz, R} {L.rgb, P_light} {0, 0, 0, 0}; sun {axis.xyz, cos a} {L.rgb, P_light} {q, 0, 0, 0}), order = the light's
+ * index in the array that was set, cdf and P_light; *n_sphere the number of spheres; *P_area the effective value for the scene as
+ * uploaded.  Any pointer but n may be NULL */
+int pt_debug_area_lights(pt_context* ctx, float* records, int32_t* order, float* cdf, float* P_light, int64_t cap, int64_t* n, int32_t* n_sphere,
+                         float* P_area);
+typedef struct {
+    float w[3];         /* the sampled direction */
+    float p_omega;      /* its density over solid angle */
+    float t_s;          /* the cut (+inf for a sun) */
+    int32_t accept;     /* 0: rejected (the origin is not outside the sphere); w, p_omega, t_s are then 0, 0, +inf */
+} pt_area_light_sample; /* 24 bytes */
+typedef struct {
+    int32_t sphere;     /* the nearest sphere (table order) in front of t_max, or -1 */
+    float t;            /* its distance (t_max when none) */
+    uint32_t suns[2];   /* bit s of the 64: sun number s (table order minus the number of spheres) holds the direction in its disc */
+} pt_area_light_hit;    /* 16 bytes */
+/* the device's sample and hit functions on given numbers (k_debug_area_light, which calls what the area-light instances of k_nee call;
+ * a device context with a set held).  Samples: origins (3 floats each), lights (table order), u (u1, u2 each, in [0, 1)).  Hits: rays, 7
+ * floats each {origin, unit direction, t_max}.  Either count may be 0 */
+int pt_debug_area_light_eval(pt_context* ctx, const float* origins, const int32_t* lights, const float* u, int64_t n_samples, pt_area_light_sample* samples,
+                             const float* rays, int64_t n_hits, pt_area_light_hit* hits);
+
 /* ---- a homogeneous participating medium (fog) for pt_render_nee (new: opt-in with pt_set_medium; the reference renders vacuum) ----
  * One medium per context, set like the lens and the environment; it is not part of the scene, so uploads keep it.  Only pt_render_nee
  * (every strategy) and the NEE path of pt_render_adaptive_ex render it.  Without one -- never set, cleared, or sigma_t = 0 -- every path

@@ -126,6 +126,10 @@ public:
     // light is held only render_nee with PT_NEE_LIGHT / PT_NEE_MIS and the NEE path of render_adaptive render
     void set_lights(const pt_light* lights, int32_t count, const pt_lights_params* p = nullptr) { ck(pt_set_lights(ctx, lights, count, p)); }
     void clear_lights() { ck(pt_clear_lights(ctx)); }
+    // sphere lights and suns with an angular size for render_nee (pt_set_area_lights replaces the whole set; p = NULL: the defaults).  While a
+    // non-black light is held only render_nee (every strategy) and the NEE path of render_adaptive render
+    void set_area_lights(const pt_area_light* lights, int32_t count, const pt_area_lights_params* p = nullptr) { ck(pt_set_area_lights(ctx, lights, count, p)); }
+    void clear_area_lights() { ck(pt_clear_area_lights(ctx)); }
     // a homogeneous medium (fog) for render_nee (pt_set_medium; start from pt_medium_defaults).  While one with sigma_t > 0 is held only
     // render_nee and the NEE path of render_adaptive render; uploads keep it
     void set_medium(const pt_medium& m) { ck(pt_set_medium(ctx, &m)); }

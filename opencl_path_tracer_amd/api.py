@@ -53,6 +53,7 @@ EXPORTS = [
     "pt_lens_defaults", "pt_set_lens", "pt_clear_lens", "pt_focus_at", "pt_debug_lens",
     "pt_environment_defaults", "pt_set_environment", "pt_clear_environment", "pt_env_lookup", "pt_debug_environment", "pt_image_read_pfm",
     "pt_lights_defaults", "pt_set_lights", "pt_clear_lights", "pt_debug_lights",
+    "pt_area_lights_defaults", "pt_set_area_lights", "pt_clear_area_lights", "pt_debug_area_lights", "pt_debug_area_light_eval",
     "pt_medium_defaults", "pt_set_medium", "pt_clear_medium", "pt_get_medium", "pt_debug_medium",
     "pt_set_medium_density", "pt_clear_medium_density", "pt_debug_medium_density", "pt_debug_grid",
     "pt_interior_defaults", "pt_set_material_interior", "pt_clear_material_interiors", "pt_get_material_interior", "pt_debug_interior",
@@ -153,6 +154,11 @@ def _load():
     sig("pt_set_lights", C.c_int, vp, vp, i32, vp)
     sig("pt_clear_lights", C.c_int, vp)
     sig("pt_debug_lights", C.c_int, vp, vp, vp, vp, i64, C.POINTER(i64), fp)
+    sig("pt_area_lights_defaults", None, vp)
+    sig("pt_set_area_lights", C.c_int, vp, vp, i32, vp)
+    sig("pt_clear_area_lights", C.c_int, vp)
+    sig("pt_debug_area_lights", C.c_int, vp, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i32), fp)
+    sig("pt_debug_area_light_eval", C.c_int, vp, vp, vp, vp, i64, vp, vp, i64, vp)
     sig("pt_medium_defaults", None, vp)
     sig("pt_set_medium", C.c_int, vp, vp)
     sig("pt_clear_medium", C.c_int, vp)
@@ -413,6 +419,74 @@ def light_from(d):
     make = {"point": point_light, "spot": spot_light, "directional": directional_light}
     if kind not in make:
         raise KeyError("a light's kind must be one of %s, not %r" % (", ".join(sorted(make)), kind))
+    return make[kind](**d)
+
+
+AREA_LIGHT_SPHERE, AREA_LIGHT_SUN, AREA_LIGHTS_MAX, AREA_KEY = 0, 1, 64, 0x9e3779b9
+
+
+class AreaLight(C.Structure):
+    """pt_area_light (include/pt_api.h), 48 bytes."""
+    _fields_ = [("type", C.c_int32), ("position", C.c_float * 3), ("direction", C.c_float * 3), ("radiance", C.c_float * 3),
+                ("size", C.c_float), ("weight", C.c_float)]
+
+
+class AreaLightsParams(C.Structure):
+    """pt_area_lights_params (include/pt_api.h)."""
+    _fields_ = [("select", C.c_float)]
+
+
+# pt_area_light_sample and pt_area_light_hit (include/pt_api.h)
+AREA_LIGHT_SAMPLE = np.dtype([("w", np.float32, 3), ("p_omega", np.float32), ("t_s", np.float32), ("accept", np.int32)])
+AREA_LIGHT_HIT = np.dtype([("sphere", np.int32), ("t", np.float32), ("suns", np.uint32, 2)])
+
+
+def area_lights_defaults():
+    """pt_area_lights_defaults as a dict: select."""
+    p = AreaLightsParams()
+    LIB.pt_area_lights_defaults(C.byref(p))
+    return {"select": p.select}
+
+
+def _rgb(v):
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    return np.repeat(v, 3) if v.size == 1 else v.reshape(3)
+
+
+def _area_light(ltype, position, direction, radiance, size, weight):
+    return AreaLight(int(ltype), (C.c_float * 3)(*[float(v) for v in position]), (C.c_float * 3)(*[float(v) for v in direction]),
+                     (C.c_float * 3)(*[float(v) for v in radiance]), float(size), float(weight))
+
+
+def sphere_light(center, radius, radiance=None, power=None, weight=0):
+    """A sphere light of uniform radiance (rgb): give `radiance`, or the `power` it emits in all (a sphere of radius R and radiance L emits
+    4 pi^2 R^2 L).  It casts soft shadows and is seen by the camera, in mirrors and through glass."""
+    if (radiance is None) == (power is None):
+        raise ValueError("sphere_light takes exactly one of radiance and power")
+    if radiance is None:
+        radiance = _rgb(power) / (4.0 * np.pi * np.pi * float(radius) * float(radius))
+    return _area_light(AREA_LIGHT_SPHERE, center, (0.0, 0.0, 0.0), _rgb(radiance), radius, weight)
+
+
+def sun_light(direction, angular_diameter_degrees, irradiance=None, radiance=None, weight=0):
+    """A sun: a disc at infinity of the given angular diameter whose light travels along `direction`.  Give its `radiance`, or the
+    `irradiance` E_perp a surface facing it receives: L = E_perp / (2 pi (1 - cos a)), a the angular radius."""
+    if (radiance is None) == (irradiance is None):
+        raise ValueError("sun_light takes exactly one of irradiance and radiance")
+    a = np.radians(0.5 * float(angular_diameter_degrees))
+    if radiance is None:
+        radiance = _rgb(irradiance) / (2.0 * np.pi * (2.0 * np.sin(0.5 * a) ** 2))
+    return _area_light(AREA_LIGHT_SUN, (0.0, 0.0, 0.0), direction, _rgb(radiance), a, weight)
+
+
+def area_light_from(d):
+    """An AreaLight from its description as scenes.SceneSpec.area_lights holds it: dict(kind="sphere" | "sun", ...) with the arguments of
+    sphere_light / sun_light."""
+    d = dict(d)
+    kind = d.pop("kind")
+    make = {"sphere": sphere_light, "sun": sun_light}
+    if kind not in make:
+        raise KeyError("an area light's kind must be one of %s, not %r" % (", ".join(sorted(make)), kind))
     return make[kind](**d)
 
 
@@ -1016,6 +1090,8 @@ class Scene:
         self.upload_Materials()
         if getattr(spec, "lights", None):                       # optional: what set_lights takes, with spec.lights_select
             self.set_lights(spec.lights, select=getattr(spec, "lights_select", 0.5))
+        if getattr(spec, "area_lights", None):                  # optional: what set_area_lights takes, with spec.area_lights_select
+            self.set_area_lights(spec.area_lights, select=getattr(spec, "area_lights_select", 0.5))
         if getattr(spec, "medium", None):                       # optional: set_medium's arguments as a dict
             self.set_medium(**spec.medium)
         if getattr(spec, "medium_density", None) is not None:   # optional: set_medium_density's array
@@ -1197,6 +1273,48 @@ class Scene:
         pl = np.zeros(n.value, dtype=np.float32)
         self._ck(LIB.pt_debug_lights(self._h, _ptr(rec), _ptr(cdf), _ptr(pl), n.value, C.byref(n), C.byref(pa)))
         return {"records": rec, "cdf": cdf, "P_light": pl, "P_ana": float(pa.value)}
+
+    # -- sphere lights and suns for render_nee (include/pt_api.h pins the set, the selection and the estimator)
+    def set_area_lights(self, lights, select=0.5):
+        """pt_set_area_lights: replaces the whole set with `lights` (api.sphere_light / sun_light, or their descriptions as area_light_from
+        takes them; an empty list clears it); select = the probability a lobe vertex samples the set rather than anything else.  While a
+        pickable light is held only render_nee (every strategy) and render_adaptive(path="nee") render."""
+        lights = [l if isinstance(l, AreaLight) else area_light_from(l) for l in lights]
+        arr = (AreaLight * max(len(lights), 1))(*lights)
+        p = AreaLightsParams(float(select))
+        self._ck(LIB.pt_set_area_lights(self._h, arr, len(lights), C.byref(p)))
+
+    def clear_area_lights(self):
+        self._ck(LIB.pt_clear_area_lights(self._h))
+
+    def debug_area_lights(self):
+        """What render_nee samples, in table order (spheres first): {"records" (n, 12) float32 as uploaded, "order" (n,) each light's index
+        in the list that was set, "cdf" (n,), "P_light" (n,), "n_sphere", "P_area": the effective probability of choosing the set for the
+        scene as uploaded}."""
+        n, ns, pa = C.c_int64(), C.c_int32(), C.c_float()
+        self._ck(LIB.pt_debug_area_lights(self._h, None, None, None, None, 0, C.byref(n), None, None))
+        rec = np.zeros((n.value, 12), dtype=np.float32)
+        order = np.zeros(n.value, dtype=np.int32)
+        cdf = np.zeros(n.value, dtype=np.float32)
+        pl = np.zeros(n.value, dtype=np.float32)
+        self._ck(LIB.pt_debug_area_lights(self._h, _ptr(rec), _ptr(order), _ptr(cdf), _ptr(pl), n.value, C.byref(n), C.byref(ns), C.byref(pa)))
+        return {"records": rec, "order": order, "cdf": cdf, "P_light": pl, "n_sphere": int(ns.value), "P_area": float(pa.value)}
+
+    def debug_area_light_eval(self, origins=None, lights=None, u=None, rays=None):
+        """pt_debug_area_light_eval: the device's sample function on origins (n, 3), lights (n,) in table order and u (n, 2), and its hit
+        function on rays (m, 7) {origin, unit direction, t_max}.  Returns (samples, hits) as arrays of AREA_LIGHT_SAMPLE / AREA_LIGHT_HIT."""
+        origins = np.ascontiguousarray(np.zeros((0, 3)) if origins is None else origins, dtype=np.float32).reshape(-1, 3)
+        lights = np.ascontiguousarray(np.zeros(0) if lights is None else lights, dtype=np.int32).reshape(-1)
+        u = np.ascontiguousarray(np.zeros((0, 2)) if u is None else u, dtype=np.float32).reshape(-1, 2)
+        rays = np.ascontiguousarray(np.zeros((0, 7)) if rays is None else rays, dtype=np.float32).reshape(-1, 7)
+        n, m = origins.shape[0], rays.shape[0]
+        if lights.shape[0] != n or u.shape[0] != n:
+            raise ValueError("debug_area_light_eval: origins, lights and u must have one entry per sample item")
+        samples = np.zeros(n, dtype=AREA_LIGHT_SAMPLE)
+        hits = np.zeros(m, dtype=AREA_LIGHT_HIT)
+        self._ck(LIB.pt_debug_area_light_eval(self._h, _ptr(origins) if n else None, _ptr(lights) if n else None, _ptr(u) if n else None, n,
+                                              _ptr(samples) if n else None, _ptr(rays) if m else None, m, _ptr(hits) if m else None))
+        return samples, hits
 
     # -- per-pixel variance of the mean luminance (option "moments"; include/pt_api.h pins both the fold and the read-out)
     def read_variance(self):

@@ -282,6 +282,18 @@ struct pt_context {
     bool lights_pickable = false;
     DeviceArray<float4> d_lights_rec;
     DeviceArray<float> d_lights_cdf;
+    // area lights (pt_set_area_lights, pt_arealights.cpp; pinned in include/pt_api.h): the set as validated, and what the kernel samples in
+    // table order (spheres first) -- per light a 12-float record (AreaLightsView, pt_internal.hpp), its index in the set, the float cdf and
+    // P_light by the counting rule.  area_pickable: some P_light > 0; only then do the NEE launches take the area-light instances of k_nee,
+    // and do the other paths refuse.  Device copies made by pt_set_area_lights
+    std::vector<pt_area_light> area_lights;
+    std::vector<float> area_rec, area_cdf, area_plight;
+    std::vector<int32_t> area_order;
+    int32_t area_spheres = 0;
+    float area_select = 0.5f;
+    bool area_pickable = false;
+    DeviceArray<float4> d_area_rec;
+    DeviceArray<float> d_area_cdf;
     // the homogeneous medium (pt_set_medium, pt_medium.cpp; pinned in include/pt_api.h): the record as validated (the defaults when none is
     // set).  Only while sigma_t > 0 do pt_render_nee and the NEE path of pt_render_adaptive_ex launch the medium instances of k_nee, and do
     // the other paths refuse.  Not part of the scene: uploads keep it
@@ -358,6 +370,14 @@ float lights_select(const pt_context* ctx, bool no_other);
 inline bool lights_on(const pt_context* ctx) { return ctx->lights_pickable; }
 inline std::string lights_refusal(const std::string& who) {
     return who + ": a light set is held and only pt_render_nee with PT_NEE_LIGHT or PT_NEE_MIS samples analytic lights (pt_clear_lights removes it)";
+}
+// pt_arealights.cpp: an area set with a pickable light is held: only pt_render_nee (every strategy) and the NEE path of pt_render_adaptive_ex
+// render; the effective P_area (no_other: nothing else is pickable); the view of the device copies; the text the other paths refuse with
+inline bool area_on(const pt_context* ctx) { return ctx->area_pickable; }
+float area_select(const pt_context* ctx, bool no_other);
+AreaLightsView area_view(const pt_context* ctx, bool no_other);
+inline std::string area_refusal(const std::string& who) {
+    return who + ": an area-light set is held and only pt_render_nee renders sphere lights and suns (pt_clear_area_lights removes it)";
 }
 // pt_medium.cpp: a medium with sigma_t > 0 is held: only pt_render_nee (every strategy) and the NEE path of pt_render_adaptive_ex render; the
 // view the kernels read; the text the other paths refuse with

@@ -1456,6 +1456,72 @@ PT_DEV f3 medium_direction(float g, f3 D, float u1, float u2, float* pb) {
     tangent_frame(D, &Z, &X);
     return madd(D, c, madd(Z, s * sinf(phi), X * (s * cosf(phi))));
 }
+// ---- area lights (pt_set_area_lights; pinned in include/pt_api.h): what the area-light instances of k_nee and
+// k_debug_area_light both call
+// the direction that (u1, u2) draw uniformly from the cone with 1 - cos(half angle) = q around the unit axis A, in medium_direction's frame
+PT_DEV f3 area_cone(f3 A, float q, float u1, float u2) {
+    const float c = 1.0f - u1 * q;
+    const float s = __builtin_sqrtf(max0(1.0f - c * c));
+    const float phi = 6.28318530717958647692f * u2;
+    f3 Z, X;
+    tangent_frame(A, &Z, &X);
+    return madd(A, c, madd(Z, s * sinf(phi), X * (s * cosf(phi))));
+}
+// the sphere q0 = {C, R} seen from o: q = 1 - cos(theta_m) without cancellation, or -1 when o is not outside it (or d^2 is not finite);
+// *c = C - o, *d2 = c.c, *R2 = R R
+PT_DEV float area_sphere_q(const float4 q0, f3 o, f3* c, float* d2, float* R2) {
+    *c = mk(q0.x, q0.y, q0.z) - o;
+    *d2 = dot3(*c, *c);
+    *R2 = q0.w * q0.w;
+    if (!(*d2 < __builtin_inff() && *d2 > *R2)) return -1.0f;
+    const float s2 = *R2 / *d2;
+    const float cm = __builtin_sqrtf(max0(1.0f - s2));
+    return s2 / (1.0f + cm);
+}
+// the sample of that sphere: false if rejected; else *w the direction, *pw its density 1 / (2 pi q), *ts the cut b - sqrt(max(0, b^2 - (d^2 - R^2)))
+PT_DEV bool area_sphere_sample(const float4 q0, f3 o, float u1, float u2, f3* w, float* pw, float* ts) {
+    f3 c;
+    float d2, R2;
+    const float q = area_sphere_q(q0, o, &c, &d2, &R2);
+    if (!(q > 0.0f)) return false;
+    *w = area_cone(normalize3(c), q, u1, u2);
+    *pw = 1.0f / (6.28318530717958647692f * q);
+    const float b = dot3(c, *w);
+    *ts = b - __builtin_sqrtf(max0(fmaf_(b, b, -(d2 - R2))));
+    return true;
+}
+// the nearest sphere of the set along (o, d) with 0 < t < tmax whose outside holds o, but for sphere `skip` (-1: none is skipped): its record
+// index and *t, or -1.  The trip count and the record addresses are wave-uniform (the view is a kernel argument): the records come through
+// scalar loads, and the lanes' arithmetic is plain FMA
+PT_DEV int area_sphere_hit(const AreaLightsView& v, f3 o, f3 d, float tmax, int skip, float* t) {
+    int best = -1;
+    float bt = tmax;
+    const float4* __restrict__ rec = v.rec;
+    for (int j = 0; j < v.n_sphere; ++j) {
+        const float4 q0 = rec[3 * j];
+        const f3 c = mk(q0.x, q0.y, q0.z) - o;
+        const float d2 = dot3(c, c), b = dot3(c, d);
+        const float R2 = q0.w * q0.w;
+        const float disc = fmaf_(b, b, -(d2 - R2));        // (the sample's cut, in the same operations)
+        const float tj = b - __builtin_sqrtf(max0(disc));
+        if (d2 > R2 && disc >= 0.0f && tj > 0.0f && tj < bt && j != skip) {
+            bt = tj;
+            best = j;
+        }
+    }
+    *t = bt;
+    return best;
+}
+// the suns of the set whose disc holds the unit direction d: bit j - n_sphere of the mask for record j
+PT_DEV unsigned long long area_sun_mask(const AreaLightsView& v, f3 d) {
+    unsigned long long mask = 0;
+    const float4* __restrict__ rec = v.rec;
+    for (int j = v.n_sphere; j < v.n; ++j) {
+        const float4 q0 = rec[3 * j];
+        if (dot3(d, mk(q0.x, q0.y, q0.z)) >= q0.w) mask |= 1ull << (j - v.n_sphere);
+    }
+    return mask;
+}
 // T of the ray (o, w) cut at `limit`: 1 exactly when no part of it lies in the box
 PT_DEV float medium_transmittance(const MediumView& mv, f3 o, f3 w, float limit) {
     float a;

@@ -1013,7 +1013,9 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
     if (interior_on(ctx) && (rc = interior_prepare(ctx, &nl->interior)) != PT_OK) return rc;
     const bool ltree = ctx->light_tree && !ctx->nee_tri.empty();      // (after nee_prepare, as above)
     if (ltree && (rc = light_tree_prepare(ctx, &nl->ltree)) != PT_OK) return rc;
-    nl->family = ltree                             ? kNeeLightTree
+    if (area_on(ctx)) nl->area = area_view(ctx, ctx->nee_tri.empty() && !(ctx->env_set && ctx->env_dist) && !lights_on(ctx));
+    nl->family = area_on(ctx)                      ? kNeeAreaLights
+                 : ltree                           ? kNeeLightTree
                  : interior_on(ctx)                ? kNeeInterior
                  : grid_on(ctx)                    ? kNeeGrid
                  : medium_on(ctx)                  ? kNeeMedium
@@ -1029,7 +1031,7 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
     // or a grid, kNeeLightTree frames with and without an interior binding)
     nl->flags = (ctx->glossy ? kNeeFlagGlossy : 0) | (ctx->coated ? kNeeFlagCoated : 0) | (lens_on(ctx) ? kNeeFlagLens : 0) | (frosted ? kNeeFlagFrosted : 0) |
                 (lights_on(ctx) ? kNeeFlagLights : 0) | (medium_on(ctx) ? kNeeFlagMedium : 0) | (grid_on(ctx) ? kNeeFlagGrid : 0) |
-                (interior_on(ctx) ? kNeeFlagInterior : 0);
+                (interior_on(ctx) ? kNeeFlagInterior : 0) | (ltree ? kNeeFlagLightTree : 0);
     return PT_OK;
 }
 hipError_t launch_nee_noted(pt_context* ctx, const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl) {

@@ -469,6 +469,18 @@ struct LightTreeView {
     const int32_t* slot;         // [packed triangles] tree-order light index, -1 for non-lights
     int32_t n_nodes, n_lights;   // 0, 0: no lights
 };
+// the area lights of pt_render_nee (pt_set_area_lights; pinned in include/pt_api.h; built by pt_arealights.cpp): spheres
+// first, then suns.  A record is three float4s:
+//   sphere  { centre.xyz, R }                          { radiance.rgb, P_light }  { 0, 0, 0, 0 }
+//   sun     { axis.xyz (unit, towards the sun), cos a } { radiance.rgb, P_light }  { q = 2 sin^2(a / 2), 0, 0, 0 }
+// A kernel argument by value: the pointers and the counts stay in scalar registers, and a loop over the records has wave-uniform addresses
+struct AreaLightsView {
+    const float4* rec;           // [n][3]
+    const float* cdf;            // [n], proportional to the selection weights; 1 from the last pickable light on
+    int32_t n_sphere, n;         // the spheres are records [0, n_sphere), the suns [n_sphere, n)
+    float p_area;                // the effective P_area of the launch (a multiple of 2^-24)
+};
+constexpr unsigned kAreaKey = 0x9e3779b9u;     // u_area's key is S ^ kAreaKey (PT_AREA_KEY, include/pt_api.h)
 constexpr int kLightTreeMaxDepth = 64;     // the loop bound of both walks; the builder keeps every leaf at or above it
 __host__ __device__ __forceinline__ int lt_bits(float f) { return __builtin_bit_cast(int, f); }
 // the importance of the child {q0 = (c, r), phi} from the origin o with the cull normal G (0: nothing is culled): 0 if its sphere lies
@@ -556,12 +568,14 @@ hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t 
                               const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream);
 // one launch of the NEE kernels (pt_nee.hip), as nee_launch_for (pt_context.hpp) fills it from the context.  Each family is the one before it
 // with one more feature compiled in; a launch takes the first family that covers what the frame needs
-enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium, kNeeGrid, kNeeInterior, kNeeLightTree };
+enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium, kNeeGrid, kNeeInterior, kNeeLightTree, kNeeAreaLights };
 // the families compiled in translation units of their own, as the preprocessor needs them (pt_nee.hip's PT_NEE_TU)
 #define PT_NEE_FAMILY_MEDIUM 8
 #define PT_NEE_FAMILY_GRID 9
 #define PT_NEE_FAMILY_INTERIOR 10
 #define PT_NEE_FAMILY_LIGHTTREE 11
+#define PT_NEE_FAMILY_AREALIGHTS 12
+static_assert(PT_NEE_FAMILY_AREALIGHTS == kNeeAreaLights, "the PT_NEE_FAMILY_* macros are the NeeFamily values");
 static_assert(PT_NEE_FAMILY_MEDIUM == kNeeMedium && PT_NEE_FAMILY_GRID == kNeeGrid && PT_NEE_FAMILY_INTERIOR == kNeeInterior && PT_NEE_FAMILY_LIGHTTREE == kNeeLightTree,
               "the PT_NEE_FAMILY_* macros are the NeeFamily values");
 // NeeLaunch::flags: what is live in the launch, for the families in which that is a run-time answer (a family below reads none of it: there the
@@ -575,6 +589,8 @@ enum NeeFlag : int {
     kNeeFlagMedium = 32,         // a medium with sigma_t > 0 is held (from kNeeInterior on, which serves frames without one)
     kNeeFlagGrid = 64,           // ... and its density grid is live (from kNeeInterior on)
     kNeeFlagInterior = 128,      // an interior binding is live (kNeeLightTree; else `interior` is never read)
+    kNeeFlagLightTree = 256,     // option light_tree with a non-empty light table: the tree is walked (kNeeAreaLights, which serves frames without
+                                 // one; else `ltree` is never read and the table's cdf picks)
 };
 struct NeeLaunch {
     const EnvView* env;          // null: the instances without an environment
@@ -586,7 +602,8 @@ struct NeeLaunch {
                                  // sigma_t > 0 (pt_set_medium) takes kNeeMedium whatever else is on, lights or not; a live density grid
                                  // (pt_set_medium_density with such a medium) takes kNeeGrid whatever else is on; a live interior binding
                                  // (pt_set_material_interior) takes kNeeInterior whatever else is on, medium and grid or not; option light_tree
-                                 // with a non-empty light table takes kNeeLightTree whatever else is on, an interior binding or not
+                                 // with a non-empty light table takes kNeeLightTree whatever else is on, an interior binding or not; an area
+                                 // set with a non-black light (pt_set_area_lights) takes kNeeAreaLights whatever else is on, a tree or not
     const float4* vn;            // the packed vertex normals (from kNeeSmooth on); null: option smooth_normals is off, which the families from
                                  // kNeeTex on read as "no triangle has vertex normals" (the pinned rule "no vertex normals: Ns = Ng, the same bits"
                                  // makes that exact)
@@ -597,7 +614,8 @@ struct NeeLaunch {
     MediumView medium;           // read from kNeeMedium on
     GridView grid;               // read from kNeeGrid on
     InteriorView interior;       // read from kNeeInterior on
-    LightTreeView ltree;         // read by kNeeLightTree
+    LightTreeView ltree;         // read from kNeeLightTree on
+    AreaLightsView area;         // read by kNeeAreaLights
     int* block;                  // out, may be null: the workgroup size the launch took, as launch_lanes / launch_lanes_wide chose it (0: nothing
                                  // was launched, an empty tile list)
 };
@@ -621,6 +639,10 @@ hipError_t launch_debug_interior(const float* in, int64_t n, float* out, hipStre
 // light hierarchy (pt_nee_lighttree.hip): pt_debug_light_tree_eval's kernel, per item {o, G, u0} (7 floats) and a tree-order target in,
 // {picked tree-order light, bits(P), bits(the weight walk's P of the target), 0} out
 hipError_t launch_debug_light_tree(const LightTreeView& v, const float* in, const int32_t* target, int64_t n, int32_t* out, hipStream_t stream);
+// area lights (pt_nee_arealights.hip): pt_debug_area_light_eval's kernel: n_s sample items {o, bits(light), u1, u2} (6 floats) -> {w, p_omega, t_s,
+// bits(accept)} (6 words) and n_h hit items {o, d, t_max} (7 floats) -> {sphere, bits(t), suns lo, suns hi} (4 words)
+hipError_t launch_debug_area_light(const AreaLightsView& v, const float* s_in, int64_t n_s, int32_t* s_out, const float* h_in, int64_t n_h, int32_t* h_out,
+                                   hipStream_t stream);
 // coated diffuse (pt_glossy.hip): pt_debug_coated's kernel, 12 floats in and 10 out per item
 hipError_t launch_debug_coated(const float* in, int64_t n, float* out, hipStream_t stream);
 // rough dielectric (pt_glossy.hip): pt_debug_frosted's kernel, 12 floats in and 10 out per item

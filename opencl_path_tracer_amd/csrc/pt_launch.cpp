@@ -365,6 +365,7 @@ static int refuse_nee_only_early(pt_context* ctx, const std::string& who) {
     if (medium_on(ctx)) return fail(ctx, PT_EINVAL, medium_refusal(who));
     if (interior_on(ctx)) return fail(ctx, PT_EINVAL, interior_refusal(who));
     if (lights_on(ctx)) return fail(ctx, PT_EINVAL, lights_refusal(who));
+    if (area_on(ctx)) return fail(ctx, PT_EINVAL, area_refusal(who));
     if (ctx->frosted) return fail(ctx, PT_EINVAL, who + ": option frosted is on and only pt_render_nee shades the rough dielectric of material type 6 (pt_set_option(ctx, \"frosted\", 0) turns it off)");
     if (lens_on(ctx)) return fail(ctx, PT_EINVAL, who + ": a lens with aperture > 0 is set and only pt_render_nee renders through it (pt_clear_lens removes it)");
     if (ctx->coated) return fail(ctx, PT_EINVAL, who + ": option coated is on and only pt_render_nee shades the coated diffuse of material type 5 (pt_set_option(ctx, \"coated\", 0) turns it off)");

@@ -34,7 +34,10 @@
 //   ltree   the triangle-light branch of a light sample picks its triangle by walking the light hierarchy (option light_tree, section 5.22), and
 //           an emitter hit's weight walks it towards the hit triangle from the previous lobe vertex, whose origin and cull normal the hook
 //           keeps; whether an interior binding is live is a run-time field (kNeeFlagInterior)
-// The kernels are k_nee<FAMILY, MODE, BLOCK, ENV, TILED> for the twelve families the host can ask for.  In a family whose option is off the data
+//   area    sphere lights and suns with an angular size (pt_set_area_lights, section 5.24): a lobe vertex samples the area set, or whatever it
+//           sampled before; a segment ends on the nearest sphere light in front of its hit, and a miss adds the suns whose disc holds it;
+//           every shadow ray is also blocked by the spheres; whether the light hierarchy is walked is a run-time field (kNeeFlagLightTree)
+// The kernels are k_nee<FAMILY, MODE, BLOCK, ENV, TILED> for the thirteen families the host can ask for.  In a family whose option is off the data
 // is null (vn, tv.uv) or the flag clear.
 #include "pt_device.hpp"
 #include <type_traits>
@@ -164,15 +167,25 @@ struct LightTreeSlot<true> {
     bool interior = true;          // an interior binding is live in this launch (else no table is read, as in the instances without one)
 };
 
+// what a hook carries for the area lights (pt_set_area_lights): nothing without them
+template <bool AREA>
+struct AreaLightsSlot {};
+template <>
+struct AreaLightsSlot<true> {
+    AreaLightsView v;              // records, cdf, counts and the launch's P_area: wave-uniform
+    bool tree = true;              // option light_tree with a non-empty table: the hierarchy is walked (else the table's cdf, as in the instances without it)
+};
+
 // shade_hit's light hook: what k_nee adds to a segment
 // and what a family compiles in: every feature up to its own (the names are what shade_hit asks a hook for, and what the comments here call them)
 template <int FAMILY, int MODE, bool ENV>
 struct NeeHook {
-    static_assert(FAMILY >= kNeePlain && FAMILY <= kNeeLightTree, "FAMILY is a NeeFamily");
+    static_assert(FAMILY >= kNeePlain && FAMILY <= kNeeAreaLights, "FAMILY is a NeeFamily");
     static constexpr bool active = true;
     static constexpr bool smooth = FAMILY >= kNeeSmooth, textured = FAMILY >= kNeeTex, glossy = FAMILY >= kNeeGlossy, coated = FAMILY >= kNeeCoated;
     static constexpr bool lens = FAMILY >= kNeeLens, frosted = FAMILY >= kNeeFrosted, lights = FAMILY >= kNeeLights, medium = FAMILY >= kNeeMedium;
     static constexpr bool grid = FAMILY >= kNeeGrid, interior = FAMILY >= kNeeInterior, ltree = FAMILY >= kNeeLightTree;
+    static constexpr bool area = FAMILY >= kNeeAreaLights;
     NeeTable lt;
     const SceneView& sv;
     LaneStack<typename StackOf<MODE>::type> stk;
@@ -195,6 +208,81 @@ struct NeeHook {
     GridSlot<grid> gr;
     InteriorSlot<interior> in;
     LightTreeSlot<ltree> lts;
+    AreaLightsSlot<area> ar;
+
+    // area: the light hierarchy is walked (a run-time answer in the area-light instances only: the light-tree ones run only when it is)
+    PT_DEV bool tree_live() const {
+        if constexpr (area) return ar.tree;
+        else return ltree;
+    }
+    // area: the nearest sphere light along (o, d) in front of t (its record index, t cut to its distance), or -1
+    PT_DEV int sphere_hit(f3 o, f3 d, float* t) const {
+        float ts;
+        const int j = area_sphere_hit(ar.v, o, d, *t, -1, &ts);
+        if (j >= 0) *t = ts;
+        return j;
+    }
+    // area: a path that ends on segment kk on a light of radiance L whose sample density from the segment's origin is pl: L itself on segment 0
+    // (the lamp seen by the camera, as the sky is), else the bracket of `miss` with the weight W_b
+    PT_DEV void area_emit(PathRegs& st, f3 L, float pl, int kk) const {
+        if (kk == 0) {
+            st.setC(st.C() + L);
+            return;
+        }
+        float wb = 1.0f;
+        if (nee && after_lobe && pl > 0.0f) {
+            if (mis) {
+                const float rr = pl / gs.pb;       // pb = 0: rr = inf, weight 0
+                wb = 1.0f / fmaf_(rr, rr, 1.0f);
+            } else {
+                wb = 0.0f;
+            }
+        }
+        st.setC(madd(((L * (st.L() + st.B())) * st.S()) * st.R(), wb, st.C()));
+    }
+    // area: the segment (o, d) ends on sphere j
+    PT_DEV void sphere_end(PathRegs& st, int j, f3 o, f3 d, int kk) const {
+        const float4 q0 = ar.v.rec[3 * j], q1 = ar.v.rec[3 * j + 1];
+        f3 c;
+        float d2, R2;
+        const float q = area_sphere_q(q0, o, &c, &d2, &R2);
+        area_emit(st, mk(q1.x, q1.y, q1.z), (ar.v.p_area * q1.w) * (1.0f / (6.28318530717958647692f * q)), kk);
+    }
+    // area: the segment along d misses everything: every sun whose disc holds d adds its radiance, each with its own weight
+    PT_DEV void sun_miss(PathRegs& st, f3 d, int kk) const {
+        for (int j = ar.v.n_sphere; j < ar.v.n; ++j) {
+            const float4 q0 = ar.v.rec[3 * j];
+            if (!(dot3(d, mk(q0.x, q0.y, q0.z)) >= q0.w)) continue;
+            const float4 q1 = ar.v.rec[3 * j + 1], q2 = ar.v.rec[3 * j + 2];
+            area_emit(st, mk(q1.x, q1.y, q1.z), (ar.v.p_area * q1.w) * (1.0f / (6.28318530717958647692f * q2.x)), kk);
+        }
+    }
+    // area: the light that u0 draws from the set's cdf, sampled from o with (u1, u2): false if rejected; else *w, *limit the search's cut (none
+    // for a sun), *e its radiance, *pl = P_area P_light p_omega and *j its record (-1 for a sun: no sphere is skipped by the shadow test)
+    PT_DEV bool area_direction(float u0, float u1, float u2, f3 o, f3* w, float* limit, f3* e, float* pl, int* j) const {
+        const AreaLightsView& av = ar.v;
+        int lo = 0, hi = av.n - 1;        // first light with cdf > u0
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (av.cdf[mid] > u0) hi = mid;
+            else lo = mid + 1;
+        }
+        const float4 q0 = av.rec[lo * 3], q1 = av.rec[lo * 3 + 1];
+        float pw;
+        if (lo < av.n_sphere) {
+            if (!area_sphere_sample(q0, o, u1, u2, w, &pw, limit)) return false;
+            *j = lo;
+        } else {
+            const float q = av.rec[lo * 3 + 2].x;
+            *w = area_cone(mk(q0.x, q0.y, q0.z), q, u1, u2);
+            pw = 1.0f / (6.28318530717958647692f * q);
+            *limit = __builtin_inff();
+            *j = -1;
+        }
+        *e = mk(q1.x, q1.y, q1.z);
+        *pl = (av.p_area * q1.w) * pw;
+        return true;
+    }
 
     // ltree: an interior binding is live (a run-time answer in the light-tree instances only: the interior ones run only when one is)
     PT_DEV bool interior_live() const {
@@ -485,14 +573,17 @@ struct NeeHook {
         float pa;
         if constexpr (ltree) {             // the weight walk from the previous lobe vertex: the P the pick there had for this triangle
             pa = 0.0f;
-            const int s = lts.v.slot[ti];
-            if (s >= 0 && inten > 0.0f) {
-                float P;
-                if (lt_walk<false>(lts.v, lts.o.x, lts.o.y, lts.o.z, lts.G.x, lts.G.y, lts.G.z, 0.0f, s, &P) >= 0) pa = P * lts.v.inv_area[s];
-            }
+            if (tree_live()) {
+                const int s = lts.v.slot[ti];
+                if (s >= 0 && inten > 0.0f) {
+                    float P;
+                    if (lt_walk<false>(lts.v, lts.o.x, lts.o.y, lts.o.z, lts.G.x, lts.G.y, lts.G.z, 0.0f, s, &P) >= 0) pa = P * lts.v.inv_area[s];
+                }
+            } else if constexpr (area) pa = lt.pdf_area[ti];
         } else pa = lt.pdf_area[ti];
         if constexpr (ENV) pa *= 1.0f - env.v.p_env;                 // the light table is chosen with probability 1 - P_env
         if constexpr (lights) pa *= 1.0f - lg.v.p_ana;               // ... and the sky or the table with probability 1 - P_ana
+        if constexpr (area) pa *= 1.0f - ar.v.p_area;                // ... and any of them with probability 1 - P_area
         if (!(pa > 0.0f && inten > 0.0f)) return 1.0f;
         if (!mis) return 0.0f;
         float pb;
@@ -671,10 +762,20 @@ struct NeeHook {
         float limit, pl, g;            // the search's cut, p_l, the emitter's cosine (1 for the sky and for an analytic light)
         int want;                      // what the shadow ray must return
         bool delta = false;            // lights: the sample is an analytic light's
-        if constexpr (lights) delta = nee_unit(nee_rand(~key, k, 2)) < lg.v.p_ana;
-        if (lights && delta) {
+        bool apick = false;            // area: the sample is an area light's, of sphere aj (-1: a sun)
+        int aj = -1;
+        if constexpr (area) apick = nee_unit(nee_rand(key ^ kAreaKey, k, 0)) < ar.v.p_area;
+        if constexpr (lights) delta = !apick && nee_unit(nee_rand(~key, k, 2)) < lg.v.p_ana;
+        if (area && apick) {
+            if constexpr (area) {
+                if (!area_direction(nee_unit(nee_rand(key, k, 0)), u1, u2, o, &w, &limit, &e, &pl, &aj)) return;
+                g = 1.0f;
+                want = -1;
+            }
+        } else if (lights && delta) {
             if constexpr (lights) {
                 if (!analytic_direction(nee_unit(nee_rand(key, k, 0)), o, &w, &limit, &e, &pl)) return;
+                if constexpr (area) pl *= 1.0f - ar.v.p_area;
                 g = 1.0f;
                 want = -1;
             }
@@ -710,6 +811,7 @@ struct NeeHook {
                 e = mk(tx.x, tx.y, tx.z) * ev.scale;
                 pl = ev.p_env * tx.w;
                 if constexpr (lights) pl *= 1.0f - lg.v.p_ana;
+                if constexpr (area) pl *= 1.0f - ar.v.p_area;
                 g = 1.0f;
                 limit = __builtin_inff();
                 want = -1;
@@ -718,9 +820,11 @@ struct NeeHook {
             if (lt.n <= 0) return;            // (P_env or P_ana is 1 then: not reached)
             f3 y, Ny;
             float r2, r, pa;
-            if constexpr (ltree) {
-                want = tree_light_point(p, o, nee_unit(nee_rand(key, k, 0)), u1, u2, &y, &Ny, &pa);
-                if (want < 0) return;         // (a tree that does not cover its table: not reached)
+            if (ltree && tree_live()) {
+                if constexpr (ltree) {
+                    want = tree_light_point(p, o, nee_unit(nee_rand(key, k, 0)), u1, u2, &y, &Ny, &pa);
+                    if (want < 0) return;     // (a tree that does not cover its table: not reached)
+                }
             } else {
                 want = light_point(p, nee_unit(nee_rand(key, k, 0)), u1, u2, &y, &Ny);
                 pa = lt.pdf_area[want];
@@ -729,6 +833,7 @@ struct NeeHook {
             if constexpr (ENV) pl = (pa * (1.0f - env.v.p_env)) * r2 / g;     // g = 0: inf or NaN, rejected below
             else pl = pa * r2 / g;
             if constexpr (lights) pl *= 1.0f - lg.v.p_ana;
+            if constexpr (area) pl *= 1.0f - ar.v.p_area;
             e = ldf3(p.mats[p.meta[want].mati].emission);
             limit = r * 1.0001f;
         }
@@ -750,7 +855,12 @@ struct NeeHook {
                 if (depth != 0.0f) md.T = expf(-depth);
             }
         } else if constexpr (medium) md.T = ins ? 1.0f : medium_transmittance(md.v, o, w, limit);
-        if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
+        if constexpr (area) {          // one traversal, then the spheres: the nearest thing along w must be what was sampled
+            const int got = shadow_hit<MODE>(sv, o, w, limit, stk, wc);
+            float tb;
+            if (area_sphere_hit(ar.v, o, w, limit, aj, &tb) >= 0) return;
+            if (got != want) return;
+        } else if (shadow_hit<MODE>(sv, o, w, limit, stk, wc) != want) return;
         if constexpr (lights) light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e, delta);
         else light_add(st, p, m, type, N, hp, rD, ins, w, cosx, pl, g, want, e);
     }
@@ -769,6 +879,7 @@ struct NeeHook {
         float wb = 1.0f;
         float pl = ev.p_env * tx.w;
         if constexpr (lights) pl *= 1.0f - lg.v.p_ana;
+        if constexpr (area) pl *= 1.0f - ar.v.p_area;
         if (nee && after_lobe && pl > 0.0f) {
             if (mis) {
                 float pb;
@@ -799,7 +910,7 @@ struct NeeHook {
 template <int FAMILY, int MODE, int BLOCK, bool ENV, bool TILED>
 PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<ENV>& env, long long npix, const float4* vn, const TexView* tv, int flags,
                       const LensView* lens, const LightsView* lights, const MediumView* medium, const GridView* grid, const InteriorView* interior,
-                      const LightTreeView* ltree) {
+                      const LightTreeView* ltree, const AreaLightsView* area) {
     using Hook = NeeHook<FAMILY, MODE, ENV>;
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
@@ -834,6 +945,11 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
     if constexpr (Hook::ltree) {
         hook.lts.v = *ltree;
         hook.lts.interior = (flags & kNeeFlagInterior) != 0;
+    }
+    if constexpr (Hook::area) {
+        hook.ar.v = *area;
+        hook.ar.tree = (flags & kNeeFlagLightTree) != 0;
+        if (area->p_area > 0.0f) hook.nee = lt.strategy != 0;      // the set is a light
     }
     const int camX = (int)p.cam.XM;
     unsigned rendered = 0;                     // TILED: pixels this lane rendered (statistic "samples", as k_render counts them)
@@ -888,12 +1004,19 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
                     // boundary it hits at ti, the surface the path will leave through, and the interior is the one bound to that material.
                     // Only lanes that are inside look the table up.  Its scatter vertex takes no light sample (a shadow ray from inside ends
                     // on the object's own boundary), so the lane skips shade_hit
+                    // area: a sphere light nearer than the hit ends the segment in its place (sj: which), before either free flight looks at
+                    // the segment's length; a segment that reaches it ends the path there
                     hook.k = k;
+                    int sj = -1;
+                    if constexpr (Hook::area) {
+                        if (ti < 0) t = __builtin_inff();
+                        sj = hook.sphere_hit(rP, rD, &t);
+                    }
                     float ts = -1.0f;              // the distance of this segment's scatter vertex; < 0: it reaches its hit or misses
                     float ig = 0.0f;               // the g of the interior it scatters in
                     bool isc = false, dead = false;
                     if (!inside) {
-                        if (hook.medium_live()) ts = hook.free_flight(rP, rD, ti < 0 ? __builtin_inff() : t);
+                        if (hook.medium_live()) ts = hook.free_flight(rP, rD, ti < 0 && sj < 0 ? __builtin_inff() : t);
                     } else if (ti >= 0 && hook.interior_live()) {
                         const float4* __restrict__ rec = hook.in.v.rec + 2 * (size_t)p.meta[ti].mati;
                         const float4 q1 = rec[1];
@@ -908,10 +1031,16 @@ PT_DEV void nee_frame(const RenderParams& p, const NeeTable& lt, const EnvSlot<E
                     if (dead) break;
                     const bool sc = ts >= 0.0f && !isc;
                     hook.md.sc = sc;
-                    if (ti < 0 && !sc) {
+                    if (ti < 0 && sj < 0 && !sc) {
+                        if constexpr (Hook::area) hook.sun_miss(st, rD, k);
                         if constexpr (ENV) hook.miss(st, rD, k);
                         break;
                     }
+                    if constexpr (Hook::area)
+                        if (sj >= 0 && !sc && !isc) {
+                            hook.sphere_end(st, sj, rP, rD, k);
+                            break;
+                        }
                     if (sc && !hook.scatter_albedo(st)) break;
                     if (!isc) shade_hit<false>(rP, rD, st, seed, inside, p, p.tris, p.meta, ti, sc ? ts : t, &hook);
                     if (sc) hook.scatter_direction(rP, rD, ts);
@@ -968,7 +1097,8 @@ template <int FAMILY, int MODE, int BLOCK, bool ENV, bool TILED, class F = NeeHo
 __global__ void __launch_bounds__(BLOCK)
     k_nee(RenderParams p, NeeTable lt, NeeArg<ENV, EnvView> env, NeeArg<F::smooth, const float4*> vn, NeeArg<F::textured, TexView> tv, NeeArg<F::coated, int> flags,
           NeeArg<F::lens, LensView> lv, NeeArg<F::lights, LightsView> lg, NeeArg<F::medium, MediumView> mv, NeeArg<F::grid, GridView> gv,
-          NeeArg<F::interior, InteriorView> iv, NeeArg<F::ltree, LightTreeView> tr, NeeArg<!TILED, long long> npix) {
+          NeeArg<F::interior, InteriorView> iv, NeeArg<F::ltree, LightTreeView> tr, NeeArg<F::area, AreaLightsView> av,
+          NeeArg<!TILED, long long> npix) {
     EnvSlot<ENV> slot;
     long long n = 0;
     const float4* vnp = nullptr;
@@ -980,6 +1110,7 @@ __global__ void __launch_bounds__(BLOCK)
     const GridView* gvp = nullptr;
     const InteriorView* ivp = nullptr;
     const LightTreeView* trp = nullptr;
+    const AreaLightsView* avp = nullptr;
     if constexpr (ENV) slot.v = env;
     if constexpr (!TILED) n = npix;
     if constexpr (F::smooth) vnp = vn;
@@ -991,7 +1122,8 @@ __global__ void __launch_bounds__(BLOCK)
     if constexpr (F::grid) gvp = &gv;
     if constexpr (F::interior) ivp = &iv;
     if constexpr (F::ltree) trp = &tr;
-    nee_frame<FAMILY, MODE, BLOCK, ENV, TILED>(p, lt, slot, n, vnp, tvp, fl, lvp, lgp, mvp, gvp, ivp, trp);
+    if constexpr (F::area) avp = &av;
+    nee_frame<FAMILY, MODE, BLOCK, ENV, TILED>(p, lt, slot, n, vnp, tvp, fl, lvp, lgp, mvp, gvp, ivp, trp, avp);
 }
 
 // launch_lanes with 512-thread workgroups for a treelet: in the mode's 1,024-thread shape the 128-VGPR cap of sixteen waves per workgroup makes
@@ -1012,8 +1144,8 @@ static hipError_t launch_lanes_wide(PICK pick, const RenderParams& p, int64_t n,
 // which forms of a family take launch_lanes_wide: bit f is form f = ENV + 2 TILED.  The smooth family's ENV TILED instance; the textured
 // family's ENV one too (3 VGPRs more than the smooth one's, which sits at the 128-VGPR cap); every instance from the glossy family on
 enum : int { kWidePlain = 1, kWideEnv = 2, kWideTiles = 4, kWideEnvTiles = 8, kWideAll = 15 };
-constexpr int kNeeWide[kNeeLightTree + 1] = {0,        kWideEnvTiles, kWideEnv | kWideEnvTiles, kWideAll, kWideAll, kWideAll,
-                                             kWideAll, kWideAll,      kWideAll,                 kWideAll, kWideAll, kWideAll};
+constexpr int kNeeWide[kNeeAreaLights + 1] = {0,        kWideEnvTiles, kWideEnv | kWideEnvTiles, kWideAll, kWideAll, kWideAll, kWideAll,
+                                              kWideAll, kWideAll,      kWideAll,                 kWideAll, kWideAll, kWideAll};
 
 // launch_lanes_t keys its static LdsMark on the type of `pick`, so every kernel arrives through a type of its own
 template <int FAMILY, bool ENV, bool TILED>
@@ -1037,7 +1169,7 @@ static hipError_t launch_nee_form(const RenderParams& p, const NeeTable& lt, con
     };
     return launch(nee_arg<ENV>(nl.env ? *nl.env : EnvView{}), nee_arg<F::smooth>(nl.vn), nee_arg<F::textured>(nl.tv), nee_arg<F::coated>(nl.flags),
                   nee_arg<F::lens>(nl.lens), nee_arg<F::lights>(nl.lights), nee_arg<F::medium>(nl.medium), nee_arg<F::grid>(nl.grid),
-                  nee_arg<F::interior>(nl.interior), nee_arg<F::ltree>(nl.ltree), nee_arg<!TILED>((long long)n));
+                  nee_arg<F::interior>(nl.interior), nee_arg<F::ltree>(nl.ltree), nee_arg<F::area>(nl.area), nee_arg<!TILED>((long long)n));
 }
 // the four kernels of one family: n is the pixels of the frame or, tiled, 64 work items per listed tile
 template <int FAMILY>
@@ -1048,7 +1180,7 @@ static hipError_t launch_nee_family(const RenderParams& p, const NeeTable& lt, c
 }
 
 // The families from kNeeMedium on are each compiled in a translation unit of their own: pt_nee_medium.hip, pt_nee_grid.hip, pt_nee_interior.hip
-// and pt_nee_lighttree.hip include this file with PT_NEE_TU set to their family (PT_NEE_FAMILY_*, pt_internal.hpp) and get launch_nee_tu<PT_NEE_TU> only.  Compiled next to the
+// pt_nee_lighttree.hip and pt_nee_arealights.hip include this file with PT_NEE_TU set to their family (PT_NEE_FAMILY_*, pt_internal.hpp) and get launch_nee_tu<PT_NEE_TU> only.  Compiled next to the
 // other families, the medium instances cost 48 of them two instructions in their uv fetch (the compiler no longer derives for a helper they
 // share that its triangle index is never negative; profiles/medium/README.md); each later family likewise, so that the ones before it compile
 // as they did before it existed
@@ -1077,6 +1209,7 @@ hipError_t launch_nee(const RenderParams& p, const NeeTable& lt, const NeeLaunch
     case kNeeGrid: e = launch_nee_tu<kNeeGrid>(p, lt, nl, npix, cu_count, stream); break;
     case kNeeInterior: e = launch_nee_tu<kNeeInterior>(p, lt, nl, npix, cu_count, stream); break;
     case kNeeLightTree: e = launch_nee_tu<kNeeLightTree>(p, lt, nl, npix, cu_count, stream); break;
+    case kNeeAreaLights: e = launch_nee_tu<kNeeAreaLights>(p, lt, nl, npix, cu_count, stream); break;
     }
     if (nl.block) *nl.block = t_lanes_block;      // (what launch_lanes_t launched with, in this translation unit or in the family's own)
     return e;
@@ -1103,6 +1236,59 @@ __global__ void __launch_bounds__(256) k_debug_light_tree(LightTreeView v, const
 hipError_t launch_debug_light_tree(const LightTreeView& v, const float* in, const int32_t* target, int64_t n, int32_t* out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_debug_light_tree, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, v, in, target, (long long)n, out);
+    return hipGetLastError();
+}
+#endif
+
+#if defined(PT_NEE_TU) && PT_NEE_TU == PT_NEE_FAMILY_AREALIGHTS     // (pt_debug_area_light_eval's kernel sits with the instances that call the same functions)
+// sample items: in 6 floats {o, bits(record), u1, u2}, out 6 words {w, p_omega, t_s (+inf for a sun), accept}; hit items: in 7 floats {o, d, t_max},
+// out 4 words {nearest sphere or -1, bits(t), the suns' mask low, high}.  Every record index is tested against the count before its loads
+__global__ void __launch_bounds__(256) k_debug_area_light(AreaLightsView v, const float* __restrict__ s_in, long long n_s, int32_t* __restrict__ s_out,
+                                                          const float* __restrict__ h_in, long long n_h, int32_t* __restrict__ h_out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_s) {
+        const float* q = s_in + i * 6;
+        const int j = __float_as_int(q[3]);
+        f3 w = mk(0.f, 0.f, 0.f);
+        float pw = 0.0f, ts = __builtin_inff();
+        bool ok = false;
+        if ((unsigned)j < (unsigned)v.n) {
+            const float4 q0 = v.rec[3 * j];
+            if (j < v.n_sphere) {
+                ok = area_sphere_sample(q0, mk(q[0], q[1], q[2]), q[4], q[5], &w, &pw, &ts);
+            } else {
+                const float qq = v.rec[3 * j + 2].x;
+                w = area_cone(mk(q0.x, q0.y, q0.z), qq, q[4], q[5]);
+                pw = 1.0f / (6.28318530717958647692f * qq);
+                ok = true;
+            }
+        }
+        int32_t* o = s_out + i * 6;
+        o[0] = __float_as_int(w.x);
+        o[1] = __float_as_int(w.y);
+        o[2] = __float_as_int(w.z);
+        o[3] = __float_as_int(pw);
+        o[4] = __float_as_int(ts);
+        o[5] = ok ? 1 : 0;
+    }
+    if (i < n_h) {
+        const float* q = h_in + i * 7;
+        float t;
+        const f3 d = mk(q[3], q[4], q[5]);
+        const int j = area_sphere_hit(v, mk(q[0], q[1], q[2]), d, q[6], -1, &t);
+        const unsigned long long m = area_sun_mask(v, d);
+        int32_t* o = h_out + i * 4;
+        o[0] = j;
+        o[1] = __float_as_int(t);
+        o[2] = (int32_t)(unsigned)(m & 0xffffffffull);
+        o[3] = (int32_t)(unsigned)(m >> 32);
+    }
+}
+hipError_t launch_debug_area_light(const AreaLightsView& v, const float* s_in, int64_t n_s, int32_t* s_out, const float* h_in, int64_t n_h, int32_t* h_out,
+                                   hipStream_t stream) {
+    const int64_t n = n_s > n_h ? n_s : n_h;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_debug_area_light, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, v, s_in, (long long)n_s, s_out, h_in, (long long)n_h, h_out);
     return hipGetLastError();
 }
 #endif

@@ -41,6 +41,9 @@ class SceneSpec:
     lights: list = field(default_factory=list)       # optional: analytic lights as api.light_from takes them, dict(kind="point" | "spot" |
                                                      # "directional", ...) (Scene.load applies them with Scene.set_lights)
     lights_select: float = 0.5                       # ... and set_lights' select
+    area_lights: list = field(default_factory=list)  # optional: sphere lights and suns as api.area_light_from takes them, dict(kind="sphere" |
+                                                     # "sun", ...) (Scene.load applies them with Scene.set_area_lights)
+    area_lights_select: float = 0.5                  # ... and set_area_lights' select
     medium: dict = field(default_factory=dict)       # optional: a homogeneous medium, Scene.set_medium's arguments: dict(sigma_t=, albedo=,
                                                      # g=, bounds=(lo, hi)) (Scene.load applies it)
     medium_density: object = None                    # optional: a voxel density for that medium, an array (nz, ny, nx) as
@@ -145,6 +148,7 @@ def checker_texture(n, a, b):
 
 LAMP_LIGHT_Y = 990.0           # cornell_box(lamp="point" / "spot"): the light hangs this high, under the ceiling at 1000
 LAMP_SPOT_DEGREES = (60.0, 90.0)      # ... and the spot's inner and outer half angles
+LAMP_SPHERE_RADIUS = 60.0      # cornell_box(lamp="sphere"): the sphere light's radius; it hangs 10 under the ceiling
 
 
 CORNELL_ROOM = ((-100.0, 0.0, -1000.0), (1100.0, 1000.0, 1000.0))      # cornell_box(fog=...): the fog's box, the room wall to wall
@@ -182,7 +186,9 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
     below its centre (Scene.set_lights through Scene.load; only render_nee renders the scene then).  The quad of area A and emission E
     radiates pi E A; a point light of intensity I radiates 4 pi I, so I = E A / 4; the spot points down, full inside 60 degrees of its
     axis and dark from 90 on, and the smoothstep between integrates to half its width: 2 pi I (1 - cos 60 + cos 60 / 2), so
-    I = E A / 1.5.
+    I = E A / 1.5.  "sphere" removes the quad too and hangs a sphere light (Scene.set_area_lights through Scene.load) of radius
+    LAMP_SPHERE_RADIUS and the same total power under its centre: a sphere of radiance L radiates 4 pi^2 R^2 L, so L = E A / (4 pi R^2).
+    It casts soft shadows and is seen by the camera and in the chromium sphere.
     fog: sigma_t > 0 fills the room (CORNELL_ROOM) with a white medium of that extinction per unit, albedo 0.9 and g = 0.6
     (Scene.set_medium through Scene.load; only render_nee renders the scene then).  1e-3 is a mean free path of the room's width.
     density: with fog, a voxel density (nz, ny, nx) over the room, such as smoke_plume(): the extinction is fog x density
@@ -195,8 +201,8 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
         raise ValueError("cornell_box: tint and wax fill the glass sphere, which coated replaces with an opaque plastic")
     if coated and frosted:
         raise ValueError("cornell_box: coated and frosted both replace the glass sphere's material")
-    if lamp not in ("quad", "point", "spot"):
-        raise ValueError("cornell_box: lamp must be \"quad\", \"point\" or \"spot\"")
+    if lamp not in ("quad", "point", "spot", "sphere"):
+        raise ValueError("cornell_box: lamp must be \"quad\", \"point\", \"spot\" or \"sphere\"")
     spec = SceneSpec(materials=list(BUILTIN_MATERIALS), name="cornell_box")
     walls, wall_mats = cornell_walls()
     if lamp != "quad":
@@ -205,7 +211,11 @@ def cornell_box(segments=32, rings=16, smooth=False, textured=False, glossy=Fals
         centre = quad.reshape(-1, 3).mean(axis=0)
         emission = np.asarray(BUILTIN_MATERIALS[LAMP][2], dtype=np.float64)
         position = (float(centre[0]), LAMP_LIGHT_Y, float(centre[2]))
-        if lamp == "point":
+        if lamp == "sphere":
+            R = LAMP_SPHERE_RADIUS
+            spec.area_lights = [dict(kind="sphere", center=(float(centre[0]), 1000.0 - 10.0 - R, float(centre[2])), radius=R,
+                                     radiance=tuple(emission * area / (4.0 * np.pi * R * R)))]
+        elif lamp == "point":
             spec.lights = [dict(kind="point", position=position, intensity=tuple(emission * area / 4.0))]
         else:
             spec.lights = [dict(kind="spot", position=position, direction=(0.0, -1.0, 0.0), intensity=tuple(emission * area / 1.5),
@@ -372,6 +382,17 @@ def sun_and_sky(width=64, height=32, sun_dir=(0.3, 0.8, 0.5), sun_radius_deg=5.0
     disc.flat[int(np.argmax(cosang))] = True
     img[disc] = np.asarray(sun_radiance)
     return img.astype(np.float32)
+
+
+def sun_and_sky_light(sun_dir=(0.3, 0.8, 0.5), sun_radius_deg=5.0, sun_radiance=(400.0, 360.0, 300.0), **kw):
+    """(map, sun): sun_and_sky's map with the same arguments, and the description of the sun light that matches its disc, as
+    api.area_light_from and SceneSpec.area_lights take it: the light travels along -sun_dir, with the disc's angular diameter and radiance.
+    The map still holds its disc: set either the map or the light as the scene's sun, since a frame lit by both counts it twice."""
+    img = sun_and_sky(sun_dir=sun_dir, sun_radius_deg=sun_radius_deg, sun_radiance=sun_radiance, **kw)
+    s = np.asarray(sun_dir, dtype=np.float64)
+    sun = dict(kind="sun", direction=tuple(float(-v) for v in s), angular_diameter_degrees=2.0 * float(sun_radius_deg),
+               radiance=tuple(float(v) for v in sun_radiance))
+    return img, sun
 
 
 def _lcg_floats(n, seed=1):
