@@ -380,7 +380,11 @@ int pt_debug_lights(pt_context* ctx, float* records, float* cdf, float* P_light,
  * PT_NEE_BSDF takes no light sample and has W_b = 1; it is allowed with an area set (and still refused while a delta set is held).
  * While a set with a pickable light is held, pt_render, pt_generate_rays, pt_trace_rays, pt_render_adaptive and pt_render_adaptive_ex with
  * PT_ADAPT_PATH_RENDER return PT_EINVAL naming pt_clear_area_lights, checked before the device.
- * Not done: the guides, the denoisers, temporal accumulation and the despeckle stage keep the view without the lights.
+ * Guides: with option "aov_lights" = 1 pt_render_aovs and pt_render_aovs_ex see the set -- a sphere light ends a chain of the guide pass
+ * exactly where it ends a segment here (the same device function, area_sphere_hit), a miss takes the suns whose disc holds the direction
+ * (area_sun_mask) -- so the denoisers and temporal accumulation, which read the guides, treat a visible lamp as a surface of its own (the
+ * lit guides are pinned with the guide buffers below).  pt_set_area_lights and pt_clear_area_lights make lit guides stale.  With the option
+ * off (the default) the guides keep the view without the lights.  The despeckle stage (pt_despeckle) reads no guides and is what it was.
  * The set lives in the context like the analytic set: uploads keep it, every rank of a tiled frame sets its own copy, a host-only context
  * validates and stores. */
 #define PT_AREA_LIGHT_SPHERE 0
@@ -953,7 +957,8 @@ void* pt_device_variance(pt_context* ctx);                           /* the same
  * adaptive frame is held.  Any context (tiled ranks: their local pixels, at global pixel ids).  Arguments are checked
  * before the device: out-of-range ones give PT_EINVAL, a host-only context PT_ENODEVICE. */
 int pt_render_aovs(pt_context* ctx, const pt_camera* cam, int32_t subpixels, int32_t specular_depth);
-/* albedo_rgbm: {r, g, b, material index of the first sub-pixel's terminal hit or -1}; normal_depth: {nx, ny, nz, depth};
+/* albedo_rgbm: {r, g, b, material index of the first sub-pixel's terminal hit or -1; lit guides: -2 - j where its chain ended on record
+ * j of the area set}; normal_depth: {nx, ny, nz, depth};
  * 16 B each per local pixel, either pointer may be NULL */
 int pt_read_aovs(pt_context* ctx, float* albedo_rgbm, float* normal_depth, int64_t npix);
 /* Shaded guides (new: the guides of what pt_render_nee shades with under options "smooth_normals" and "textures").
@@ -987,6 +992,28 @@ int pt_read_aovs(pt_context* ctx, float* albedo_rgbm, float* normal_depth, int64
  * them stale exactly as an upload does (the consumers return PT_EINVAL until guides are rendered again, and the first guides after that
  * drop the temporal history); geometric guides are not affected by those calls, and changing the two options invalidates neither. */
 enum { PT_AOV_GEOMETRIC = 0, PT_AOV_SHADED = 1 };
+/* Lit guides (new: opt-in with option "aov_lights" = 0 | 1, default 0; other values PT_EINVAL).  A guide call -- pt_render_aovs,
+ * pt_render_aovs_ex with either shading -- renders lit guides iff, at the call, the option is on and the context holds an area set with a
+ * non-black light (pt_set_area_lights; the condition that selects NEE family 12).  Otherwise it launches the kernel instances of before
+ * and writes the same bits.  Stat "aov_lights": 1 iff the last guide launch used a lit instance, else 0.  pt_aov_params::shading stays
+ * {0, 1}.  Everything not named here is pt_render_aovs / PT_AOV_SHADED as pinned above (sub-pixel rays, raster order, sums,
+ * normalisation, layout).  The records are the set's table (spheres before suns, each kind in the order given; pt_debug_area_lights).
+ * Sphere test, after EVERY closest-hit search of a chain (the primary ray and every ray after a specular step), with the ray (P, D) and
+ *   t_tri = the triangle's distance or +inf on a miss: j = area_sphere_hit(set, P, D, t_tri, -1, &t_s), the nearest sphere with
+ *   0 < t_s < t_tri whose outside holds P (an origin inside a sphere does not see it), in the operations of the area-light block.  If
+ *   j >= 0 the chain ends on that sphere, whatever the triangle's type and however much specular depth is left:
+ *   albedo = tint x L_j; normal = normalize3(madd(D, t_s, P) - C_j), the same in geometric and shaded guides; material = -2 - j (exact in
+ *   float, distinct from a miss's -1).
+ * Primary ray: a sphere that ends it makes it a hit -- t_s joins the depth sum and the hit count, also where no triangle was hit.
+ * Miss with no sphere, anywhere on a chain: mask = area_sun_mask(set, D) (the suns with dot3(D, axis) >= cos a).  If it is non-zero:
+ *   albedo = tint x the sum of L over the suns of the mask in ascending record order (from 0); normal 0; material = -2 - j of the lowest
+ *   such record.  A primary ray that ends so is still a miss: it is left out of the hit count, and the depth is -1 when no sub-pixel hit.
+ *   So the filters' hit / miss rule and step 1 of the temporal pass stay as pinned: a sun's disc gets no history and no depth edge.  With
+ *   an empty mask the miss is what it was.
+ * Consumers are unchanged and read whichever guides were rendered last.  Lit guides are a snapshot of the set: pt_set_area_lights and
+ * pt_clear_area_lights make them stale exactly as an upload does (the consumers return PT_EINVAL until guides are rendered again, and the
+ * first guides after that drop the temporal history); unlit guides are not affected by those two calls, and changing the option
+ * invalidates nothing.  The lens, the fog and the interiors stay out of the guides. */
 typedef struct { int32_t subpixels, specular_depth, shading; } pt_aov_params;
 void pt_aov_defaults(pt_aov_params* p);
 int pt_render_aovs_ex(pt_context* ctx, const pt_camera* cam, const pt_aov_params* params);

@@ -233,7 +233,7 @@ public:
         pt_denoise_variance_defaults(&d);
         ck(pt_denoise_variance(ctx, p ? p : &d));
     }
-    void set_option(const char* key, int64_t value) { ck(pt_set_option(ctx, key, value)); }   // pt_set_option, e.g. ("moments", 1)
+    void set_option(const char* key, int64_t value) { ck(pt_set_option(ctx, key, value)); }   // pt_set_option, e.g. ("moments", 1), ("aov_lights", 1)
     // temporal accumulation with reprojection (pt_temporal_accumulate; p = NULL: the defaults): after a frame rendered with option
     // "moments" = 1 and render_aovs() of its camera
     void temporal_accumulate(const pt_temporal_params* p = nullptr) {

@@ -1336,7 +1336,8 @@ class Scene:
     def render_aovs(self, subpixels=1, specular_depth=4, shading="geometric"):
         """Guide buffers of the current view: albedo, normal, depth per local pixel; touches no render state.  shading="geometric"
         (pt_render_aovs): the geometric normal and the material's kd; "shaded" (pt_render_aovs_ex, PT_AOV_SHADED): the shading normal and
-        the textured albedo of the NEE path under options "smooth_normals" / "textures" as they are now."""
+        the textured albedo of the NEE path under options "smooth_normals" / "textures" as they are now.  With set_option("aov_lights", 1)
+        and an area set with a non-black light held, either form also sees the sphere lights and the suns (stat "aov_lights")."""
         if shading not in AOV_SHADING:
             raise ValueError("shading must be 'geometric' or 'shaded', not %r" % (shading,))
         if AOV_SHADING[shading] == PT_AOV_GEOMETRIC:
@@ -1346,7 +1347,9 @@ class Scene:
         self._ck(LIB.pt_render_aovs_ex(self._h, _ptr(self.camera), C.byref(p)))
 
     def read_aovs(self):
-        """(albedo_rgbm, normal_depth), each (local_pixels, 4) float32: {r, g, b, material or -1}, {nx, ny, nz, depth or -1}."""
+        """(albedo_rgbm, normal_depth), each (local_pixels, 4) float32: {r, g, b, material or -1}, {nx, ny, nz, depth or -1}.  The material
+        is the index of the first sub-pixel's terminal hit, -1 for a miss, and in lit guides (option "aov_lights") -2 - j where that chain
+        ended on the sphere light or under the sun of record j of debug_area_lights()."""
         alb = np.empty((self.local_pixels, 4), dtype=np.float32)
         nd = np.empty((self.local_pixels, 4), dtype=np.float32)
         self._ck(LIB.pt_read_aovs(self._h, _ptr(alb), _ptr(nd), alb.shape[0]))

@@ -167,6 +167,9 @@ struct pt_context {
     bool aov_valid = false;            // pt_render_aovs ran and no pt_upload_triangles / pt_upload_materials has made its guides stale
     bool aov_shaded = false;           // the guides are shaded ones (pt_render_aovs_ex, PT_AOV_SHADED): the authoring calls for vertex normals,
                                        // uvs, textures and bindings make them stale too (shaded_guides_stale, pt_host.cpp)
+    int aov_lights = 0;                // option "aov_lights": guides rendered while an area set with a non-black light is held see its lights
+    bool aov_lit = false;              // the last guide launch used a lit instance (stat "aov_lights"): pt_set_area_lights and
+                                       // pt_clear_area_lights make such guides stale too
     // option "moments": render launches fold the second moment into colors[].w; moments_valid = every launch of the current frame did
     // (note_moments); the variance read-out (pt_read_variance, pt_denoise_variance) lives in d_variance, allocated on first use
     int moments = 0;

@@ -2,6 +2,7 @@
 //   k_aovs      one lane per local pixel, persistent blocks: n x n fixed sub-pixel camera rays through the render kernels'
 //               traversal (pt_device.hpp), a short deterministic specular chain, then albedo / normal / depth (include/pt_api.h)
 //               k_aovs<.., AovShade>: the same pass with the shading normal and the textured albedo of the NEE path (pt_render_aovs_ex)
+//               k_aovs<.., AovLights>, k_aovs<.., AovShade, AovLights>: either pass seeing the sphere lights and the suns (option aov_lights)
 //   k_atrous    one launch per iteration, 32x8 blocks, 5x5 taps at step 2^i; demodulation fused into the first launch and
 //               remodulation into the last
 // The specular step below restates what shade_hit does for types 1 and 2 without the random draw.
@@ -21,12 +22,52 @@ struct AovShade {
     int coated;                    // option coated: a terminal type-5 hit is a plastic (albedo tint x kd')
     int frosted;                   // option frosted: a terminal type-6 hit is a rough dielectric (albedo tint x 1)
 };
-PT_DEV const AovShade& only(const AovShade& s) { return s; }
+// The lit forms (option aov_lights with an area set that has a non-black light) take an AovLights last: after every closest_hit of a chain the
+// nearest sphere light in front of the triangle ends the chain, and a miss takes the suns whose disc holds the direction (pinned in
+// include/pt_api.h).  The view is a kernel argument by value, so the loops over the records have a wave-uniform trip count and wave-uniform
+// addresses, as in k_nee; they run once per chain hit, outside the traversal.  Every statement of the lit forms sits under if constexpr (LIT).
+struct AovLights {
+    AreaLightsView v;
+};
+template <class... SH>
+PT_DEV const AovShade& only(const AovShade& s, const SH&...) { return s; }
+PT_DEV const AreaLightsView& lights_of(const AovLights& l) { return l.v; }
+PT_DEV const AreaLightsView& lights_of(const AovShade&, const AovLights& l) { return l.v; }
+template <class T, class... SH>
+constexpr bool aov_has = (std::is_same<T, SH>::value || ...);
+
+// the lit guides' test after the closest_hit (ti, t) of the ray (P, D), with the chain's tint: 1 the chain ends on a sphere light at *ts, 2 it
+// ends on a miss (under the suns whose disc holds D, if any), 0 it goes on with triangle ti
+PT_DEV int aov_light_end(const AreaLightsView& v, f3 P, f3 D, int ti, float t, f3 tint, f3* alb, f3* nrm, float* mat, float* ts) {
+    const int j = area_sphere_hit(v, P, D, ti >= 0 ? t : __builtin_inff(), -1, ts);
+    if (j >= 0) {
+        const float4 q0 = v.rec[3 * j], q1 = v.rec[3 * j + 1];
+        *alb = tint * mk(q1.x, q1.y, q1.z);
+        *nrm = normalize3(madd(D, *ts, P) - mk(q0.x, q0.y, q0.z));
+        *mat = (float)(-2 - j);
+        return 1;
+    }
+    if (ti >= 0) return 0;
+    const unsigned long long mask = area_sun_mask(v, D);
+    if (mask) {
+        f3 L = mk(0.f, 0.f, 0.f);
+        int first = -1;
+        for (int k = v.n_sphere; k < v.n; ++k) {
+            if (!((mask >> (k - v.n_sphere)) & 1ull)) continue;
+            const float4 q1 = v.rec[3 * k + 1];
+            L = L + mk(q1.x, q1.y, q1.z);
+            if (first < 0) first = k;
+        }
+        *alb = tint * L;
+        *mat = (float)(-2 - first);
+    }
+    return 2;
+}
 
 template <int MODE, int BLOCK, class... SH>
 __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spec_depth, long long npix, float4* albedo_rgbm, float4* normal_depth,
                                                 SH... shade) {
-    constexpr bool SHADED = sizeof...(SH) != 0;
+    constexpr bool SHADED = aov_has<AovShade, SH...>, LIT = aov_has<AovLights, SH...>;
     LaneStack<typename StackOf<MODE>::type> stk;
     SceneView sv;
     setup_traversal<MODE, BLOCK>(p, &sv, &stk);
@@ -48,7 +89,17 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
                 int ti = closest_hit<MODE, false>(sv, P, D, stk, &t, &wc);
                 f3 alb = mk(0.f, 0.f, 0.f), nrm = alb;
                 float mat = -1.0f;
-                if (ti >= 0) {
+                bool chain = ti >= 0;
+                if constexpr (LIT) {
+                    float ts;
+                    const int e = aov_light_end(lights_of(shade...), P, D, ti, t, mk(1.f, 1.f, 1.f), &alb, &nrm, &mat, &ts);
+                    if (e == 1) {           // a sphere light ends the primary ray: a hit, also where no triangle was
+                        st += ts;
+                        ++hits;
+                    }
+                    chain = e == 0;
+                }
+                if (chain) {
                     st += t;
                     ++hits;
                     f3 tint = mk(1.f, 1.f, 1.f);
@@ -96,7 +147,10 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
                                 D = normalize3(dnew);
                                 P = madd(Ng, refr ? -0.001f : 0.001f, hp);
                                 ti = closest_hit<MODE, false>(sv, P, D, stk, &t, &wc);
-                                if (ti < 0) break;          // escaped: albedo 0, normal 0
+                                if constexpr (LIT) {
+                                    float ts;
+                                    if (aov_light_end(lights_of(shade...), P, D, ti, t, tint, &alb, &nrm, &mat, &ts)) break;
+                                } else if (ti < 0) break;   // escaped: albedo 0, normal 0
                                 continue;
                             }
                             const f3 a = type == 1 || (type == 4 && sh.glossy) ? ldf3(m->F0) : type == 2 || (type == 6 && sh.frosted) ? mk(1.f, 1.f, 1.f) : plastic ? kd : kd + ldf3(m->emission);
@@ -127,7 +181,10 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
                             D = normalize3(dnew);
                             P = madd(N, side, hp);
                             ti = closest_hit<MODE, false>(sv, P, D, stk, &t, &wc);
-                            if (ti < 0) break;          // escaped: albedo 0, normal 0
+                            if constexpr (LIT) {
+                                float ts;
+                                if (aov_light_end(lights_of(shade...), P, D, ti, t, tint, &alb, &nrm, &mat, &ts)) break;
+                            } else if (ti < 0) break;       // escaped: albedo 0, normal 0
                             continue;
                         }
                         const f3 a = type == 1 ? ldf3(m->F0) : type == 2 ? mk(1.f, 1.f, 1.f) : ldf3(m->kd) + ldf3(m->emission);
@@ -153,14 +210,23 @@ __global__ void __launch_bounds__(BLOCK) k_aovs(RenderParams p, int sub, int spe
     }
 }
 
+// lights == nullptr: the unlit instances, which are what they were before the lit ones existed
 hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
-                              const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream) {
+                              const float4* vn, const TexView& tv, int glossy, int coated, int frosted, const AreaLightsView* lights, int cu_count,
+                              hipStream_t stream) {
+    const AovShade sh{vn, tv, glossy, coated, frosted};
+    if (lights)
+        return launch_lanes([](auto s) { return k_aovs<s.mode, s.block, AovShade, AovLights>; }, p, npix, cu_count, stream, subpixels, specular_depth,
+                            (long long)npix, albedo_rgbm, normal_depth, sh, AovLights{*lights});
     return launch_lanes([](auto s) { return k_aovs<s.mode, s.block, AovShade>; }, p, npix, cu_count, stream, subpixels, specular_depth,
-                        (long long)npix, albedo_rgbm, normal_depth, AovShade{vn, tv, glossy, coated, frosted});
+                        (long long)npix, albedo_rgbm, normal_depth, sh);
 }
 
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
-                       int cu_count, hipStream_t stream) {
+                       const AreaLightsView* lights, int cu_count, hipStream_t stream) {
+    if (lights)
+        return launch_lanes([](auto s) { return k_aovs<s.mode, s.block, AovLights>; }, p, npix, cu_count, stream, subpixels, specular_depth,
+                            (long long)npix, albedo_rgbm, normal_depth, AovLights{*lights});
     return launch_lanes([](auto s) { return k_aovs<s.mode, s.block>; }, p, npix, cu_count, stream, subpixels, specular_depth, (long long)npix,
                         albedo_rgbm, normal_depth);
 }

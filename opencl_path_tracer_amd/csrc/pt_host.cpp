@@ -463,6 +463,8 @@ int pt_read_tile_state(pt_context* ctx, int32_t* spp, float* err, int64_t n_tile
     return PT_OK;
 }
 // ---- guide buffers + a-trous denoiser (kernels: pt_denoise.hip; the filter is pinned in include/pt_api.h)
+// the lit instances of k_aovs: option aov_lights, and an area set with a non-black light (what selects kNeeAreaLights)
+static bool aov_lit_now(const pt_context* ctx) { return ctx->aov_lights && area_on(ctx); }
 int pt_render_aovs(pt_context* ctx, const pt_camera* cam, int32_t subpixels, int32_t specular_depth) {
     if (!ctx) return PT_EINVAL;
     if (subpixels < 1 || subpixels > 8) return fail(ctx, PT_EINVAL, "pt_render_aovs: subpixels must be 1..8");
@@ -474,12 +476,15 @@ int pt_render_aovs(pt_context* ctx, const pt_camera* cam, int32_t subpixels, int
     PT_ALLOC(ctx, ctx->d_aov.reserve(2 * (size_t)std::max<int64_t>(ctx->npix, 1)));
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
-    PT_HIP(ctx, launch_aovs(p, subpixels, specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, ctx->cu_count, ctx->stream));
+    const bool lit = aov_lit_now(ctx);
+    const AreaLightsView lights = area_view(ctx, true);
+    PT_HIP(ctx, launch_aovs(p, subpixels, specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, lit ? &lights : nullptr, ctx->cu_count, ctx->stream));
     // the first guides after pt_upload_triangles / pt_upload_materials (which made the old ones stale): the temporal history describes
     // the old scene, and every accumulate needs guides, so this is where it is dropped
     if (!ctx->aov_valid) ctx->temporal_history = false;
     ctx->aov_valid = true;
     ctx->aov_shaded = false;
+    ctx->aov_lit = lit;
     ctx->aov_cam = *cam;
     ++ctx->aov_serial;
     return PT_OK;
@@ -509,11 +514,14 @@ int pt_render_aovs_ex(pt_context* ctx, const pt_camera* cam, const pt_aov_params
     PT_ALLOC(ctx, ctx->d_aov.reserve(2 * (size_t)std::max<int64_t>(ctx->npix, 1)));
     RenderParams p;
     fill_params(ctx, cam, &p);         // the render kernels' node placement
-    PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->glossy, ctx->coated, ctx->frosted, ctx->cu_count,
-                                   ctx->stream));
+    const bool lit = aov_lit_now(ctx);
+    const AreaLightsView lights = area_view(ctx, true);
+    PT_HIP(ctx, launch_aovs_shaded(p, ap->subpixels, ap->specular_depth, ctx->npix, ctx->d_aov, ctx->d_aov + ctx->npix, vn, tv, ctx->glossy, ctx->coated, ctx->frosted,
+                                   lit ? &lights : nullptr, ctx->cu_count, ctx->stream));
     if (!ctx->aov_valid) ctx->temporal_history = false;      // (as pt_render_aovs: the first guides after stale ones)
     ctx->aov_valid = true;
     ctx->aov_shaded = true;
+    ctx->aov_lit = lit;
     ctx->aov_cam = *cam;
     ++ctx->aov_serial;
     return PT_OK;
@@ -1667,6 +1675,9 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value) {
     } else if (k == "light_tree") {
         if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "light_tree must be 0 (a light sample picks its triangle from the table's cdf) or 1 (pt_render_nee picks it by walking the light hierarchy)");
         ctx->light_tree = (int)value;
+    } else if (k == "aov_lights") {
+        if (value != 0 && value != 1) return fail(ctx, PT_EINVAL, "aov_lights must be 0 (the guides see triangles only) or 1 (pt_render_aovs and pt_render_aovs_ex see the sphere lights and suns of the area set)");
+        ctx->aov_lights = (int)value;
     } else if (k == "timing") {
         ctx->timing = value ? 1 : 0;
     } else if (k == "count_work") {
@@ -1784,6 +1795,7 @@ int pt_get_stat(pt_context* ctx, const char* key, double* out) {
         return PT_OK;
     }
     if (k == "nee_family") { *out = (double)ctx->nee_family; return PT_OK; }
+    if (k == "aov_lights") { *out = ctx->aov_lit ? 1.0 : 0.0; return PT_OK; }
     if (k == "nee_form") { *out = (double)ctx->nee_form; return PT_OK; }
     if (k == "nee_block") { *out = (double)ctx->nee_block; return PT_OK; }
     if (k == "kernel_launches") { *out = (double)ctx->kernel_launches; return PT_OK; }

@@ -370,9 +370,11 @@ hipError_t launch_debug_spec(int fn, const uint32_t* in, int64_t n, uint32_t* ou
 // pt_debug_shade (pt_debug.hip): 32-bit words per item in and out (layout in pt_api.h); instance = PT_SHADE_SK | PT_SHADE_REC bits
 constexpr int kShadeWordsIn = PT_SHADE_WORDS_IN, kShadeWordsOut = PT_SHADE_WORDS_OUT;
 hipError_t launch_debug_shade(const RenderParams& p, int instance, const uint32_t* in, int64_t n, uint32_t* out, hipStream_t stream);
-// guide buffers and the a-trous filter (pt_denoise.hip; the filter is pinned in include/pt_api.h next to pt_denoise)
+// guide buffers and the a-trous filter (pt_denoise.hip; the filter is pinned in include/pt_api.h next to pt_denoise).  lights: the area set
+// of the lit guides (option aov_lights), or nullptr for the unlit instances
+struct AreaLightsView;
 hipError_t launch_aovs(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
-                       int cu_count, hipStream_t stream);
+                       const AreaLightsView* lights, int cu_count, hipStream_t stream);
 struct AtrousStep {
     int32_t step;            // 2^i
     int32_t demodulate;
@@ -563,9 +565,10 @@ inline LensView lens_view(const pt_camera& cam, float aperture, float focus) {
 }
 // the shaded guides (pt_render_aovs_ex with PT_AOV_SHADED; pt_denoise.hip): vn == nullptr: option smooth_normals is off, tv.uv == nullptr:
 // option textures is off, glossy: option glossy (a terminal type-4 hit gives tint x F0), coated: option coated (a terminal type-5 hit gives tint x kd'),
-// frosted: option frosted (a terminal type-6 hit gives tint x 1)
+// frosted: option frosted (a terminal type-6 hit gives tint x 1); lights as in launch_aovs
 hipError_t launch_aovs_shaded(const RenderParams& p, int32_t subpixels, int32_t specular_depth, int64_t npix, float4* albedo_rgbm, float4* normal_depth,
-                              const float4* vn, const TexView& tv, int glossy, int coated, int frosted, int cu_count, hipStream_t stream);
+                              const float4* vn, const TexView& tv, int glossy, int coated, int frosted, const AreaLightsView* lights, int cu_count,
+                              hipStream_t stream);
 // one launch of the NEE kernels (pt_nee.hip), as nee_launch_for (pt_context.hpp) fills it from the context.  Each family is the one before it
 // with one more feature compiled in; a launch takes the first family that covers what the frame needs
 enum NeeFamily { kNeePlain, kNeeSmooth, kNeeTex, kNeeGlossy, kNeeCoated, kNeeLens, kNeeFrosted, kNeeLights, kNeeMedium, kNeeGrid, kNeeInterior, kNeeLightTree, kNeeAreaLights };
