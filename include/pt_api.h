@@ -1153,6 +1153,74 @@ int pt_denoise_despeckled(pt_context* ctx, const pt_denoise_variance_params* p);
  * other parameters are checked as above (PT_EINVAL before PT_ENODEVICE) */
 int pt_debug_despeckle(pt_context* ctx, const float* rgbv_in, int32_t w, int32_t h, const pt_despeckle_params* p, float* rgbv_out, int32_t* flags);
 
+/* ---- display stage (new: a post-process from any of the four HDR results to an LDR image, on the device, no host round trip; the
+ * path-tracing kernels, the estimator, pt_resolve_ldr and pt_write_ppm are untouched) -----
+ * pt_display meters an exposure, adds bloom, applies a tone curve and an encoding, and writes {r, g, b, 1} per pixel plus three bytes per
+ * pixel in PPM row order.  Input: a W x H frame, colour c(p) = .xyz, index y W + x, row 0 the bottom of the view.  All arithmetic float32;
+ * products and sums are rounded one by one (no fused multiply-add) except where fmaf is written (kernels in pt_display.hip):
+ *   0. l(p) = fmaf(0.0722f, b, fmaf(0.7152f, g, 0.2126f * r)) (the l pinned for the moments).  p is live iff r, g, b and l are all finite.
+ *      A pixel that is not live takes no part in metering or bloom, is written as {0, 0, 0, 1} with bytes 0, and is counted in n_nonfinite.
+ *   1. Exposure E.  A 256-bin histogram of the live pixels is always taken: l < 2^-16 (zero, negatives) counts in n_dark and in no bin;
+ *      otherwise bin = min((bits(l) >> 20) - 888, 255): eight bins per stop from 2^-16 to 2^16, everything brighter in bin 255.  Counts
+ *      are uint32.  N = sum of the bins; lo = N low_permille / 1000, hi = N high_permille / 1000 (uint64, integer division); walking the
+ *      bins upward, k_b = the samples of bin b with rank in [lo, hi); K = sum k_b; S = fmaf((float)k_b, lambda_b, S) over b ascending
+ *      from S = 0, lambda_b = (float)((b >> 3) - 16) + T[b & 7], T = PT_DISPLAY_LOG2_TABLE; M = S / (float)K (0 when K = 0).
+ *      PT_METER_MANUAL: E = exp2f(ev).  PT_METER_AUTO: E* = key * exp2f(ev - M), clamped to [exp2f(min_ev), exp2f(max_ev)]; E* =
+ *      exp2f(ev) when K = 0.  The context remembers the E of its last pt_display; with a remembered E_prev and adapt < 1,
+ *      E = exp2f((1 - adapt) * log2f(E_prev) + adapt * log2f(E*)), else E = E*.  pt_display_reset, pt_upload_triangles and
+ *      pt_upload_materials forget E_prev.  The reduction runs on the device; the later kernels read E from device memory.
+ *   2. Bloom, skipped entirely (no launches, out = h bit for bit) when bloom_intensity = 0.  h(p) = E * c(p) for a live p, else 0;
+ *      lh = l(h); bright pass B(p) = (h * (lh - threshold)) / lh per channel if lh > threshold, else 0.  Level sizes W_0 = W,
+ *      W_k = (W_(k-1) + 1) / 2, the same for H.  Down, k = 1 .. levels, D_0 = B:
+ *      D_k(x, y) = sum_j a_j (sum_i a_i D_(k-1)(clamp(2x - 1 + i), clamp(2y - 1 + j))), i, j = 0..3 ascending, a = {1, 3, 3, 1} / 8,
+ *      coordinates clamped to the source level.  Up, separable: target x reads s = x >> 1 with weight 0.75 and s + (x odd ? 1 : -1),
+ *      clamped to the source level, with weight 0.25; rows first, then the two rows the same way.  U_levels = D_levels,
+ *      U_k = D_k + up(U_(k+1)) for k = levels - 1 .. 1; out(p) = h(p) + (bloom_intensity / (float)levels) * up(U_1)(p).
+ *      The result does not depend on how a kernel tiles a level.
+ *   3. Curve per channel on x = out > 0 ? out : 0.  PT_CURVE_LINEAR: x.  PT_CURVE_REINHARD: x * ((1 + L / (white * white)) / (1 + L)),
+ *      L = l(x) (no division by L: black stays black; white = +inf: 1 / (1 + L)).  PT_CURVE_ACES: (x (2.51 x + 0.03)) / (x (2.43 x + 0.59) + 0.14).
+ *      Then v = the curve clamped to [0, 1] (a NaN, which only an overflow of E c or of the curve's squares can give, becomes 0), then
+ *      PT_ENCODE_SRGB: 12.92 v below 0.0031308, else 1.055 powf(v, 1 / 2.4f) - 0.055; PT_ENCODE_LINEAR: v.
+ *      Written: {r, g, b, 1} per pixel in the frame's order, and bytes (uint8)floorf(255 v + 0.5) r, g, b per pixel, top row first. */
+typedef struct {
+    int32_t source, metering; float ev, key; int32_t low_permille, high_permille; float min_ev, max_ev, adapt;
+    int32_t bloom_levels; float bloom_threshold, bloom_intensity; int32_t curve; float white; int32_t encoding;
+} pt_display_params;   /* 60 bytes */
+enum { PT_DISPLAY_FRAME = 0, PT_DISPLAY_DENOISED = 1, PT_DISPLAY_TEMPORAL = 2, PT_DISPLAY_DESPECKLED = 3 };
+enum { PT_METER_MANUAL = 0, PT_METER_AUTO = 1 };
+enum { PT_CURVE_LINEAR = 0, PT_CURVE_REINHARD = 1, PT_CURVE_ACES = 2 };
+enum { PT_ENCODE_SRGB = 0, PT_ENCODE_LINEAR = 1 };
+/* T[j] = log2(1 + (j + 0.5) / 8) rounded to float32: the centre of the j-th eighth of a stop */
+#define PT_DISPLAY_LOG2_TABLE { 0.0874628425f, 0.247927517f, 0.392317414f, 0.523561954f, 0.643856168f, 0.754887521f, 0.857980967f, 0.954196334f }
+/* {E, M, K, n_dark, n_nonfinite, bloom levels actually run (0 when bloom_intensity = 0)} of the last pt_display */
+struct pt_display_info { float exposure, mean_log2; uint32_t n_metered, n_dark, n_nonfinite; int32_t levels; };   /* 24 bytes */
+/* source FRAME, metering AUTO, ev 0, key 0.18, permille 100 / 950, ev range -16 .. 16, adapt 1, 4 levels, threshold 1, intensity 0,
+ * curve ACES, white +inf, encoding sRGB: trial values, not yet replaced by a sweep over rendered scenes (profiles/display/README.md) */
+void pt_display_defaults(pt_display_params* p);
+/* Source PT_DISPLAY_FRAME reads colors (the bound framebuffer, if any), DENOISED what pt_read_denoised serves, TEMPORAL what
+ * pt_read_temporal serves, DESPECKLED what pt_read_despeckled serves (.xyz of each).  The stage writes only its own buffers (allocated on
+ * first use: 19 B/px for the result, 64 / 3 B/px for the pyramid once bloom runs); colors, rnds, the guides, the denoised buffer, the
+ * temporal sets and the despeckled result are never written.  It does not synchronise with the host.  World-1 contexts only.  Checked
+ * in this order: PT_EINVAL for params NULL; source, metering, curve or encoding out of range; a NaN in any float; key <= 0; permille
+ * outside 0 <= low < high <= 1000; min_ev > max_ev; adapt outside (0, 1]; bloom_levels outside 1..6; bloom_threshold < 0;
+ * bloom_intensity < 0; white <= 0; world != 1.  Then PT_ENODEVICE on a host-only context.  Then PT_EINVAL under the source's own rule:
+ * pt_denoise / pt_temporal_accumulate / pt_despeckle has not run (FRAME is always there). */
+int pt_display(pt_context* ctx, const pt_display_params* p);
+/* the last pt_display's result: rgba {r, g, b, 1} 16 B per pixel (row 0 = bottom), rgb8 3 B per pixel (top row first); either may be NULL */
+int pt_read_display(pt_context* ctx, float* rgba, uint8_t* rgb8, int64_t npix);
+void* pt_device_display(pt_context* ctx);       /* the float4 result on the device, the bytes right behind it; NULL before the first pt_display */
+/* the numbers of the last pt_display; this is where a host that wants them synchronises */
+int pt_display_info(pt_context* ctx, struct pt_display_info* out);
+int pt_debug_display_histogram(pt_context* ctx, uint32_t out[256]);     /* the last pt_display's 256 bins */
+int pt_display_reset(pt_context* ctx);          /* forgets the remembered exposure: the next pt_display adapts from nothing */
+/* the last pt_display's bytes as a binary P6 file with pt_write_ppm's conventions (maxval 255, top row first) */
+int pt_write_display_ppm(pt_context* ctx, const char* path);
+/* the same kernels on a caller's frame rgba_in ({r, g, b, .} per pixel, 1 <= w, h <= 4096); source is ignored, the other parameters are
+ * checked as above (PT_EINVAL before PT_ENODEVICE); prev_exposure > 0 stands in for the remembered exposure, <= 0: none; the context's
+ * own is neither read nor written.  Any of rgba_out, rgb8_out, hist (256 bins) and info may be NULL. */
+int pt_debug_display(pt_context* ctx, const float* rgba_in, int32_t w, int32_t h, const pt_display_params* p, float prev_exposure,
+                     float* rgba_out, uint8_t* rgb8_out, uint32_t* hist, struct pt_display_info* info);
+
 /* ---- multi-GPU frame assembly (SURVEY 8b "RCCL communicator per context", 8e) ----------
  * The reference is single-device (main.cpp:466-476); a host that tiles the frame over N contexts with
  * pt_create_tiled assembles it with these.  One process (or thread) per GPU:

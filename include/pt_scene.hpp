@@ -269,6 +269,16 @@ public:
         pt_denoise_variance_defaults(&d);
         ck(pt_denoise_despeckled(ctx, p ? p : &d));
     }
+    // the display stage (pt_display; p = NULL: the defaults): exposure, bloom, tone curve and encoding of p->source on the device, no
+    // read-back; the result: pt_read_display / pt_device_display / pt_write_display_ppm, the metered numbers: display_info()
+    void display(const pt_display_params* p = nullptr) {
+        pt_display_params d;
+        pt_display_defaults(&d);
+        ck(pt_display(ctx, p ? p : &d));
+    }
+    struct pt_display_info display_info() { struct pt_display_info i = {}; ck(::pt_display_info(ctx, &i)); return i; }
+    void display_reset() { ck(pt_display_reset(ctx)); }
+    void write_display_ppm(const std::string& path) { ck(pt_write_display_ppm(ctx, path.c_str())); }
     int current_sample() { int32_t s = 0; ck(pt_get_current_sample(ctx, &s)); return s; }
     void reset_samples() { ck(pt_set_current_sample(ctx, 0)); }                                // main.cpp:1046
     void finish() { ck(pt_sync(ctx)); }                                                        // queue.finish(), main.cpp:675

@@ -61,6 +61,8 @@ EXPORTS = [
     "pt_read_variance", "pt_device_variance", "pt_denoise_variance_defaults", "pt_denoise_variance",
     "pt_temporal_defaults", "pt_temporal_accumulate", "pt_read_temporal", "pt_device_temporal", "pt_denoise_temporal", "pt_debug_reproject",
     "pt_despeckle_defaults", "pt_despeckle", "pt_read_despeckled", "pt_device_despeckled", "pt_denoise_despeckled", "pt_debug_despeckle",
+    "pt_display_defaults", "pt_display", "pt_read_display", "pt_device_display", "pt_display_info", "pt_debug_display_histogram",
+    "pt_display_reset", "pt_write_display_ppm", "pt_debug_display",
     "pt_render_aovs", "pt_read_aovs", "pt_aov_defaults", "pt_render_aovs_ex", "pt_denoise_defaults", "pt_denoise", "pt_read_denoised", "pt_device_denoised",
     "pt_local_pixel_count", "pt_local_pixel_ids", "pt_read_colors", "pt_read_rnds", "pt_read_rays",
     "pt_resolve_ldr", "pt_bind_framebuffer", "pt_device_colors", "pt_device_rnds", "pt_set_stream",
@@ -191,6 +193,15 @@ def _load():
     sig("pt_device_despeckled", vp, vp)
     sig("pt_denoise_despeckled", C.c_int, vp, vp)
     sig("pt_debug_despeckle", C.c_int, vp, vp, i32, i32, vp, vp, vp)
+    sig("pt_display_defaults", None, vp)
+    sig("pt_display", C.c_int, vp, vp)
+    sig("pt_read_display", C.c_int, vp, vp, vp, i64)
+    sig("pt_device_display", vp, vp)
+    sig("pt_display_info", C.c_int, vp, vp)
+    sig("pt_debug_display_histogram", C.c_int, vp, vp)
+    sig("pt_display_reset", C.c_int, vp)
+    sig("pt_write_display_ppm", C.c_int, vp, C.c_char_p)
+    sig("pt_debug_display", C.c_int, vp, vp, i32, i32, vp, f32, vp, vp, vp, vp)
     sig("pt_debug_reproject", C.c_int, vp, vp, i32, i32, f32, fp)
     sig("pt_render_aovs", C.c_int, vp, vp, i32, i32)
     sig("pt_read_aovs", C.c_int, vp, vp, vp, i64)
@@ -665,6 +676,54 @@ def _despeckle_params(who, params):
         if k not in p.as_dict():
             raise TypeError("unknown %s parameter %r" % (who, k))
         setattr(p, k, DESPECKLE_SOURCE.get(v, v) if k == "source" and isinstance(v, str) else v)
+    return p
+
+
+PT_DISPLAY_FRAME, PT_DISPLAY_DENOISED, PT_DISPLAY_TEMPORAL, PT_DISPLAY_DESPECKLED = range(4)
+PT_METER_MANUAL, PT_METER_AUTO = 0, 1
+PT_CURVE_LINEAR, PT_CURVE_REINHARD, PT_CURVE_ACES = range(3)
+PT_ENCODE_SRGB, PT_ENCODE_LINEAR = 0, 1
+DISPLAY_NAMES = {
+    "source": {"frame": PT_DISPLAY_FRAME, "denoised": PT_DISPLAY_DENOISED, "temporal": PT_DISPLAY_TEMPORAL, "despeckled": PT_DISPLAY_DESPECKLED},
+    "metering": {"manual": PT_METER_MANUAL, "auto": PT_METER_AUTO},
+    "curve": {"linear": PT_CURVE_LINEAR, "reinhard": PT_CURVE_REINHARD, "aces": PT_CURVE_ACES},
+    "encoding": {"srgb": PT_ENCODE_SRGB, "linear": PT_ENCODE_LINEAR},
+}
+
+
+class DisplayParams(C.Structure):
+    """pt_display_params (include/pt_api.h)."""
+    _fields_ = [("source", C.c_int32), ("metering", C.c_int32), ("ev", C.c_float), ("key", C.c_float), ("low_permille", C.c_int32),
+                ("high_permille", C.c_int32), ("min_ev", C.c_float), ("max_ev", C.c_float), ("adapt", C.c_float), ("bloom_levels", C.c_int32),
+                ("bloom_threshold", C.c_float), ("bloom_intensity", C.c_float), ("curve", C.c_int32), ("white", C.c_float),
+                ("encoding", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class DisplayInfo(C.Structure):
+    """struct pt_display_info (include/pt_api.h)."""
+    _fields_ = [("exposure", C.c_float), ("mean_log2", C.c_float), ("n_metered", C.c_uint32), ("n_dark", C.c_uint32),
+                ("n_nonfinite", C.c_uint32), ("levels", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def display_defaults():
+    """pt_display_defaults as a dict (the fields of pt_display_params)."""
+    p = DisplayParams()
+    LIB.pt_display_defaults(C.byref(p))
+    return p.as_dict()
+
+
+def _display_params(who, params):
+    p = DisplayParams(**display_defaults())
+    for k, v in params.items():
+        if k not in p.as_dict():
+            raise TypeError("unknown %s parameter %r" % (who, k))
+        setattr(p, k, DISPLAY_NAMES[k][v] if isinstance(v, str) else v)
     return p
 
 
@@ -1452,6 +1511,60 @@ class Scene:
         flags = np.empty(a.shape[:2], dtype=np.int32)
         self._ck(LIB.pt_debug_despeckle(self._h, _ptr(a), a.shape[1], a.shape[0], C.byref(p), _ptr(out), _ptr(flags)))
         return out, flags
+
+    # -- display stage (include/pt_api.h pins it)
+    def display(self, **params):
+        """pt_display with pt_display_defaults overridden by params (source, metering, curve and encoding also by name: "frame" /
+        "denoised" / "temporal" / "despeckled", "manual" / "auto", "linear" / "reinhard" / "aces", "srgb" / "linear"): exposure, bloom,
+        tone curve and encoding of one of the HDR results, on the device.  Nothing is read back: read_display(), display_info()."""
+        p = _display_params("display", params)
+        self._ck(LIB.pt_display(self._h, C.byref(p)))
+
+    def read_display(self):
+        """(rgba (local_pixels, 4) float32 {r, g, b, 1}, row 0 the bottom; rgb8 (H, W, 3) uint8, top row first) of the last display."""
+        rgba = np.empty((self.local_pixels, 4), dtype=np.float32)
+        rgb8 = np.empty((rgba.shape[0] // self.width, self.width, 3), dtype=np.uint8)
+        self._ck(LIB.pt_read_display(self._h, _ptr(rgba), _ptr(rgb8), rgba.shape[0]))
+        return rgba, rgb8
+
+    def device_display(self):
+        """Device pointer of the last display's {r, g, b, 1} per local pixel, the bytes right behind (None before the first)."""
+        return LIB.pt_device_display(self._h)
+
+    def display_info(self):
+        """pt_display_info as a dict: exposure, mean_log2, n_metered, n_dark, n_nonfinite, levels.  Synchronises."""
+        info = DisplayInfo()
+        self._ck(LIB.pt_display_info(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def display_histogram(self):
+        """The 256 luminance bins of the last display (uint32)."""
+        out = np.empty(256, dtype=np.uint32)
+        self._ck(LIB.pt_debug_display_histogram(self._h, _ptr(out)))
+        return out
+
+    def display_reset(self):
+        """pt_display_reset: the next display adapts from nothing."""
+        self._ck(LIB.pt_display_reset(self._h))
+
+    def write_display_ppm(self, path):
+        """The last display's bytes as a binary P6 file."""
+        self._ck(LIB.pt_write_display_ppm(self._h, os.fsencode(path)))
+
+    def debug_display(self, frame, prev_exposure=None, **params):
+        """pt_debug_display: the display kernels on a caller's frame (h, w, 4) float32 {r, g, b, .}; source is ignored, prev_exposure
+        stands in for the remembered exposure.  Returns (rgba (h, w, 4), rgb8 (h, w, 3) top row first, hist (256,), info dict)."""
+        a = np.ascontiguousarray(frame, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("frame must have shape (h, w, 4)")
+        p = _display_params("debug_display", params)
+        out = np.empty_like(a)
+        rgb8 = np.empty(a.shape[:2] + (3,), dtype=np.uint8)
+        hist = np.empty(256, dtype=np.uint32)
+        info = DisplayInfo()
+        self._ck(LIB.pt_debug_display(self._h, _ptr(a), a.shape[1], a.shape[0], C.byref(p), 0.0 if prev_exposure is None else float(prev_exposure),
+                                      _ptr(out), _ptr(rgb8), _ptr(hist), C.byref(info)))
+        return out, rgb8, hist, info.as_dict()
 
     def read_denoised(self):
         out = np.empty((self.local_pixels, 4), dtype=np.float32)

@@ -201,6 +201,16 @@ struct pt_context {
     uint64_t despeckle_epoch = 0;            // render_epoch: no launch has written colors since
     uint64_t despeckle_frame = 0;            // frame_serial: no frame has started since
     uint64_t despeckle_temporal = 0;         // temporal_frame (source PT_DESPECKLE_TEMPORAL): no newer accumulate ran
+    // the display stage (pt_display), allocated on first use: {r, g, b, 1} per local pixel with the 3 B per pixel right behind it; the
+    // bloom pyramid (grown when a call asks for more levels); the histogram and the metering's numbers (DisplayStat), where the
+    // exposure of the last call also waits as the next call's E_prev while display_has_prev -- pt_display_reset, pt_upload_triangles
+    // and pt_upload_materials clear it
+    DeviceArray<float4> d_display;
+    DeviceArray<float4> d_display_pyr;
+    DeviceArray<DisplayStat> d_display_stat;
+    bool display_ran = false;
+    bool display_has_prev = false;
+    int32_t display_levels = 0;              // bloom levels the last call ran
     // next-event estimation (pt_render_nee): the light table, built on the host at first use after an upload (nee_valid).  Packed
     // triangle index and cdf per light; P_sel / area per packed triangle (0 for non-lights).  Device copies allocated with it.
     std::vector<int32_t> nee_tri;

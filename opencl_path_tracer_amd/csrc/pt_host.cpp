@@ -263,6 +263,7 @@ int pt_upload_materials(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
     ctx->aov_valid = false;
     ctx->despeckle_valid = false;    // (pt_despeckle's result is a frame of the old scene)
+    ctx->display_has_prev = false;   // (and pt_display's remembered exposure its brightness)
     ctx->nee_valid = false;          // the light table reads emission and type
     ctx->tex_dirty = true;           // and the bindings on the device the type
     ctx->interior_dirty = true;      // (the interiors' table too)
@@ -878,6 +879,207 @@ int pt_debug_despeckle(pt_context* ctx, const float* rgbv_in, int32_t w, int32_t
     if (rc != PT_OK) return rc;
     std::memcpy(rgbv_out, out.data(), sizeof(float4) * n);
     std::memcpy(flags, out.data() + n, sizeof(int32_t) * n);
+    return PT_OK;
+}
+
+// ---- display stage (kernels k_display_*, pt_display.hip; pinned in include/pt_api.h)
+void pt_display_defaults(pt_display_params* p) {
+    if (!p) return;
+    p->source = PT_DISPLAY_FRAME;
+    p->metering = PT_METER_AUTO;
+    p->ev = 0.0f;
+    p->key = 0.18f;
+    p->low_permille = 100;
+    p->high_permille = 950;
+    p->min_ev = -16.0f;
+    p->max_ev = 16.0f;
+    p->adapt = 1.0f;
+    p->bloom_levels = 4;
+    p->bloom_threshold = 1.0f;
+    p->bloom_intensity = 0.0f;
+    p->curve = PT_CURVE_ACES;
+    p->white = std::numeric_limits<float>::infinity();
+    p->encoding = PT_ENCODE_SRGB;
+}
+// the arguments of the display stage in the pinned order: "" or what is wrong (pt_display, pt_debug_display)
+static std::string display_params_error(const pt_display_params* dp) {
+    if (!dp) return "params is NULL";
+    if (dp->source < PT_DISPLAY_FRAME || dp->source > PT_DISPLAY_DESPECKLED) return "source must be PT_DISPLAY_FRAME .. PT_DISPLAY_DESPECKLED";
+    if (dp->metering != PT_METER_MANUAL && dp->metering != PT_METER_AUTO) return "metering must be PT_METER_MANUAL or PT_METER_AUTO";
+    if (dp->curve < PT_CURVE_LINEAR || dp->curve > PT_CURVE_ACES) return "curve must be PT_CURVE_LINEAR, PT_CURVE_REINHARD or PT_CURVE_ACES";
+    if (dp->encoding != PT_ENCODE_SRGB && dp->encoding != PT_ENCODE_LINEAR) return "encoding must be PT_ENCODE_SRGB or PT_ENCODE_LINEAR";
+    for (float f : {dp->ev, dp->key, dp->min_ev, dp->max_ev, dp->adapt, dp->bloom_threshold, dp->bloom_intensity, dp->white})
+        if (std::isnan(f)) return "a parameter is NaN";
+    if (!(dp->key > 0.0f)) return "key must be > 0";
+    if (dp->low_permille < 0 || dp->low_permille >= dp->high_permille || dp->high_permille > 1000) return "permille must be 0 <= low < high <= 1000";
+    if (dp->min_ev > dp->max_ev) return "min_ev must be <= max_ev";
+    if (!(dp->adapt > 0.0f && dp->adapt <= 1.0f)) return "adapt must be in (0, 1]";
+    if (dp->bloom_levels < 1 || dp->bloom_levels > kDisplayMaxLevels) return "bloom_levels must be 1..6";
+    if (dp->bloom_threshold < 0.0f) return "bloom_threshold must be >= 0";
+    if (dp->bloom_intensity < 0.0f) return "bloom_intensity must be >= 0";
+    if (!(dp->white > 0.0f)) return "white must be > 0";
+    return "";
+}
+static void display_args(const pt_display_params* dp, DisplayArgs* a) {
+    a->metering = dp->metering;
+    a->ev = dp->ev;
+    a->key = dp->key;
+    a->low_permille = dp->low_permille;
+    a->high_permille = dp->high_permille;
+    a->min_ev = dp->min_ev;
+    a->max_ev = dp->max_ev;
+    a->adapt = dp->adapt;
+    a->levels = dp->bloom_intensity > 0.0f ? dp->bloom_levels : 0;
+    a->threshold = dp->bloom_threshold;
+    a->intensity = dp->bloom_intensity;
+    a->curve = dp->curve;
+    a->white = dp->white;
+    a->encoding = dp->encoding;
+}
+// the bytes of d_display: right behind the float4 result
+static uint8_t* display_bytes(const pt_context* ctx) { return reinterpret_cast<uint8_t*>(ctx->d_display + (size_t)std::max<int64_t>(ctx->npix, 1)); }
+static void display_info_from(const DisplayStat& st, int32_t levels, struct pt_display_info* out) {
+    out->exposure = st.exposure;
+    out->mean_log2 = st.mean_log2;
+    out->n_metered = st.n_metered;
+    out->n_dark = st.n_dark;
+    out->n_nonfinite = st.n_nonfinite;
+    out->levels = levels;
+}
+int pt_display(pt_context* ctx, const pt_display_params* dp) {
+    if (!ctx) return PT_EINVAL;
+    const std::string why = display_params_error(dp);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_display: " + why);
+    if (ctx->world != 1) return fail(ctx, PT_EINVAL, "pt_display: contexts of one rank (world == 1) only");
+    PT_NEED_DEVICE(ctx);
+    DisplayArgs a;
+    switch (dp->source) {
+    case PT_DISPLAY_DENOISED:
+        if (!ctx->d_denoised) return fail(ctx, PT_EINVAL, "pt_display: source DENOISED, but pt_denoise has not run");
+        a.c = ctx->d_denoised;
+        break;
+    case PT_DISPLAY_TEMPORAL:
+        if (ctx->temporal_out < 0) return fail(ctx, PT_EINVAL, "pt_display: source TEMPORAL, but pt_temporal_accumulate has not run");
+        a.c = temporal_colour(ctx, ctx->temporal_out);
+        break;
+    case PT_DISPLAY_DESPECKLED:
+        if (!ctx->d_despeckle) return fail(ctx, PT_EINVAL, "pt_display: source DESPECKLED, but pt_despeckle has not run");
+        a.c = ctx->d_despeckle;
+        break;
+    default: a.c = ctx->d_colors; break;
+    }
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t np = (size_t)std::max<int64_t>(ctx->npix, 1);
+    display_args(dp, &a);
+    PT_ALLOC(ctx, ctx->d_display.reserve(np + (3 * np + sizeof(float4) - 1) / sizeof(float4)));
+    PT_ALLOC(ctx, ctx->d_display_stat.reserve(1));
+    if (a.levels > 0) PT_ALLOC(ctx, ctx->d_display_pyr.reserve(display_pyramid_elems(ctx->W, ctx->local_rows, a.levels)));
+    a.W = ctx->W;
+    a.H = ctx->local_rows;
+    a.stat = ctx->d_display_stat;
+    a.out = ctx->d_display;
+    a.rgb8 = display_bytes(ctx);
+    a.pyr = ctx->d_display_pyr;
+    a.prev_mode = ctx->display_has_prev ? 1 : 0;
+    a.prev_value = 0.0f;
+    ctx->display_ran = false;
+    ctx->display_has_prev = false;
+    PT_HIP(ctx, launch_display(a, ctx->stream));
+    ctx->display_ran = true;
+    ctx->display_has_prev = true;
+    ctx->display_levels = a.levels;
+    return PT_OK;
+}
+int pt_read_display(pt_context* ctx, float* rgba, uint8_t* rgb8, int64_t npix) {
+    PT_NEED_DEVICE(ctx);
+    if (npix != ctx->npix) return fail(ctx, PT_EINVAL, "npix must equal the local pixel count");
+    if (!ctx->display_ran) return fail(ctx, PT_EINVAL, "pt_read_display: pt_display has not run");
+    int rc = PT_OK;
+    if (rgba && (rc = read_back(ctx, rgba, ctx->d_display, sizeof(float4) * (size_t)npix)) != PT_OK) return rc;
+    if (rgb8 && (rc = read_back(ctx, rgb8, display_bytes(ctx), 3 * (size_t)npix)) != PT_OK) return rc;
+    return PT_OK;
+}
+void* pt_device_display(pt_context* ctx) { return ctx && ctx->display_ran ? (void*)ctx->d_display.get() : nullptr; }
+int pt_display_info(pt_context* ctx, struct pt_display_info* out) {
+    PT_NEED_DEVICE(ctx);
+    if (!out) return fail(ctx, PT_EINVAL, "pt_display_info: NULL argument");
+    if (!ctx->display_ran) return fail(ctx, PT_EINVAL, "pt_display_info: pt_display has not run");
+    DisplayStat st;
+    const int rc = read_back(ctx, &st, ctx->d_display_stat, sizeof(st));
+    if (rc != PT_OK) return rc;
+    display_info_from(st, ctx->display_levels, out);
+    return PT_OK;
+}
+int pt_debug_display_histogram(pt_context* ctx, uint32_t out[256]) {
+    PT_NEED_DEVICE(ctx);
+    if (!out) return fail(ctx, PT_EINVAL, "pt_debug_display_histogram: NULL argument");
+    if (!ctx->display_ran) return fail(ctx, PT_EINVAL, "pt_debug_display_histogram: pt_display has not run");
+    return read_back(ctx, out, ctx->d_display_stat, sizeof(uint32_t) * 256);
+}
+int pt_display_reset(pt_context* ctx) {
+    if (!ctx) return PT_EINVAL;
+    ctx->display_has_prev = false;
+    return PT_OK;
+}
+int pt_write_display_ppm(pt_context* ctx, const char* path) {
+    if (!ctx || !path) return PT_EINVAL;
+    PT_NEED_DEVICE(ctx);
+    if (!ctx->display_ran) return fail(ctx, PT_EINVAL, "pt_write_display_ppm: pt_display has not run");
+    std::vector<uint8_t> bytes(3 * (size_t)ctx->npix);
+    const int rc = read_back(ctx, bytes.data(), display_bytes(ctx), bytes.size());
+    if (rc != PT_OK) return rc;
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return fail(ctx, PT_EIO, std::string("cannot write ") + path);
+    std::fprintf(f, "P6\n%d %d\n255\n", ctx->W, ctx->local_rows);      // (the bytes are top row first already)
+    bool ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? PT_OK : fail(ctx, PT_EIO, std::string("cannot write ") + path);
+}
+int pt_debug_display(pt_context* ctx, const float* rgba_in, int32_t w, int32_t h, const pt_display_params* dp, float prev_exposure, float* rgba_out,
+                     uint8_t* rgb8_out, uint32_t* hist, struct pt_display_info* info) {
+    if (!ctx) return PT_EINVAL;
+    pt_display_params p = {};
+    if (dp) {
+        p = *dp;
+        p.source = PT_DISPLAY_FRAME;         // (ignored)
+    }
+    const std::string why = display_params_error(dp ? &p : nullptr);
+    if (!why.empty()) return fail(ctx, PT_EINVAL, "pt_debug_display: " + why);
+    if (w < 1 || w > 4096 || h < 1 || h > 4096) return fail(ctx, PT_EINVAL, "pt_debug_display: w and h must be 1..4096");
+    if (!rgba_in || std::isnan(prev_exposure)) return fail(ctx, PT_EINVAL, "pt_debug_display: rgba_in is NULL or prev_exposure is NaN");
+    PT_NEED_DEVICE(ctx);
+    DisplayArgs a;
+    display_args(&p, &a);
+    // the output allocation, in float4: the result, its bytes, the DisplayStat, the pyramid
+    const size_t n = (size_t)w * (size_t)h, nb = (3 * n + sizeof(float4) - 1) / sizeof(float4), ns = sizeof(DisplayStat) / sizeof(float4);
+    static_assert(sizeof(DisplayStat) % sizeof(float4) == 0, "the DisplayStat sits between float4 arrays");
+    const size_t back = n + nb + ns;          // what comes back to the host
+    std::vector<float4> out(back);
+    const int rc = debug_round_trip(ctx, rgba_in, sizeof(float4) * n, out.data(), sizeof(float4) * back, [&](void* d_in, void* d_out) {
+        DeviceBuf pyr;                       // (freed when the lambda returns, so the lambda waits for the kernels below)
+        if (a.levels > 0) {
+            const hipError_t e = pyr.alloc(sizeof(float4) * display_pyramid_elems(w, h, a.levels));
+            if (e != hipSuccess) return e;
+        }
+        a.c = static_cast<const float4*>(d_in);
+        a.W = w;
+        a.H = h;
+        a.out = static_cast<float4*>(d_out);
+        a.rgb8 = reinterpret_cast<uint8_t*>(a.out + n);
+        a.stat = reinterpret_cast<DisplayStat*>(a.out + n + nb);
+        a.pyr = static_cast<float4*>(pyr.p);
+        a.prev_mode = prev_exposure > 0.0f ? 2 : 0;
+        a.prev_value = prev_exposure;
+        hipError_t e = launch_display(a, ctx->stream);
+        if (e == hipSuccess && a.levels > 0) e = hipStreamSynchronize(ctx->stream);      // the pyramid must outlive the kernels
+        return e;
+    });
+    if (rc != PT_OK) return rc;
+    const DisplayStat* st = reinterpret_cast<const DisplayStat*>(out.data() + n + nb);
+    if (rgba_out) std::memcpy(rgba_out, out.data(), sizeof(float4) * n);
+    if (rgb8_out) std::memcpy(rgb8_out, out.data() + n, 3 * n);
+    if (hist) std::memcpy(hist, st->hist, sizeof(uint32_t) * 256);
+    if (info) display_info_from(*st, a.levels, info);
     return PT_OK;
 }
 int pt_debug_reproject(const pt_camera* cur, const pt_camera* prev, int32_t x, int32_t y, float depth, float out[3]) {

@@ -709,6 +709,45 @@ struct DespeckleArgs {
     float threshold, floor_, min_rel_sigma;
 };
 hipError_t launch_despeckle(const DespeckleArgs& a, int32_t radius, int32_t spread, hipStream_t stream);
+// the display stage (pt_display.hip; pinned in include/pt_api.h next to pt_display)
+struct DisplayStat {               // what one pt_display leaves on the device: the histogram and the metering's numbers
+    uint32_t hist[256];
+    uint32_t n_dark, n_nonfinite, n_metered;
+    float exposure, mean_log2;     // exposure is also the remembered E_prev of the next call
+    uint32_t pad[3];
+};
+constexpr size_t kDisplayStatCounters = 259;       // the words launch_display clears: hist, n_dark, n_nonfinite, n_metered
+constexpr int kDisplayMaxLevels = 6;
+struct DisplayArgs {
+    const float4* c;               // the input colour, .xyz
+    int32_t W, H;
+    DisplayStat* stat;
+    float4* out;                   // {r, g, b, 1}
+    uint8_t* rgb8;                 // 3 B per pixel, top row first; 4-byte aligned
+    float4* pyr;                   // display_pyramid_elems(W, H, levels) float4: the levels D_1 .. D_levels, U_k written over D_k
+    int32_t metering;
+    float ev, key;
+    int32_t low_permille, high_permille;
+    float min_ev, max_ev, adapt;
+    int32_t prev_mode;             // E_prev: 0 none, 1 stat->exposure as the last call left it, 2 prev_value
+    float prev_value;
+    int32_t levels;                // bloom levels to run, 0: no bloom
+    float threshold, intensity;
+    int32_t curve;
+    float white;
+    int32_t encoding;
+};
+inline size_t display_pyramid_elems(int32_t W, int32_t H, int32_t levels) {
+    size_t n = 0;
+    for (int k = 1; k <= levels; ++k) {
+        W = (W + 1) / 2;
+        H = (H + 1) / 2;
+        n += (size_t)W * (size_t)H;
+    }
+    return n;
+}
+// clears the counters, then histogram, metering and (levels > 0) the pyramid, then the final kernel, all on stream; no host synchronise
+hipError_t launch_display(const DisplayArgs& a, hipStream_t stream);
 // float32 dot / cross with the fma placement of pt_device.hpp's dot3 / cross3
 __host__ __device__ __forceinline__ float rp_dot(const float* a, const float* b) { return __builtin_fmaf(a[2], b[2], __builtin_fmaf(a[1], b[1], a[0] * b[0])); }
 __host__ __device__ __forceinline__ void rp_cross(const float* a, const float* b, float* r) {
