@@ -10,7 +10,7 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-s
 
 all: $(PKG)/libptamd.so oracle tests/cpp/dropin check-isa
 
-SRCS    := $(CSRC)/pt_host.cpp $(CSRC)/pt_builder.cpp $(CSRC)/pt_launch.cpp $(CSRC)/pt_obj.cpp $(CSRC)/pt_kernels.hip $(CSRC)/pt_wavefront.hip $(CSRC)/pt_debug.hip $(CSRC)/pt_lbvh.hip $(CSRC)/pt_sahdev.hip $(CSRC)/pt_widedev.hip $(CSRC)/pt_comm.hip $(CSRC)/pt_adaptive.hip $(CSRC)/pt_denoise.hip $(CSRC)/pt_nee.hip $(CSRC)/pt_temporal.hip $(CSRC)/pt_despeckle.hip $(CSRC)/pt_display.hip $(CSRC)/pt_shaderec.hip $(CSRC)/pt_smooth.hip $(CSRC)/pt_texture.hip $(CSRC)/pt_glossy.hip $(CSRC)/pt_lens.hip $(CSRC)/pt_image.cpp $(CSRC)/pt_wide.cpp $(CSRC)/pt_env.cpp $(CSRC)/pt_lights.cpp $(CSRC)/pt_medium.cpp $(CSRC)/pt_interior.cpp $(CSRC)/pt_lighttree.cpp $(CSRC)/pt_arealights.cpp $(CSRC)/pt_medium.hip $(CSRC)/pt_nee_medium.hip $(CSRC)/pt_nee_grid.hip $(CSRC)/pt_nee_interior.hip $(CSRC)/pt_nee_lighttree.hip $(CSRC)/pt_nee_arealights.hip
+SRCS    := $(CSRC)/pt_host.cpp $(CSRC)/pt_builder.cpp $(CSRC)/pt_launch.cpp $(CSRC)/pt_obj.cpp $(CSRC)/pt_kernels.hip $(CSRC)/pt_wavefront.hip $(CSRC)/pt_debug.hip $(CSRC)/pt_lbvh.hip $(CSRC)/pt_sahdev.hip $(CSRC)/pt_widedev.hip $(CSRC)/pt_comm.hip $(CSRC)/pt_adaptive.hip $(CSRC)/pt_denoise.hip $(CSRC)/pt_nee.hip $(CSRC)/pt_temporal.hip $(CSRC)/pt_despeckle.hip $(CSRC)/pt_display.hip $(CSRC)/pt_shaderec.hip $(CSRC)/pt_smooth.hip $(CSRC)/pt_texture.hip $(CSRC)/pt_glossy.hip $(CSRC)/pt_lens.hip $(CSRC)/pt_image.cpp $(CSRC)/pt_wide.cpp $(CSRC)/pt_env.cpp $(CSRC)/pt_lights.cpp $(CSRC)/pt_medium.cpp $(CSRC)/pt_interior.cpp $(CSRC)/pt_lighttree.cpp $(CSRC)/pt_arealights.cpp $(CSRC)/pt_post.cpp $(CSRC)/pt_smooth.cpp $(CSRC)/pt_texture.cpp $(CSRC)/pt_lens.cpp $(CSRC)/pt_medium.hip $(CSRC)/pt_nee_medium.hip $(CSRC)/pt_nee_grid.hip $(CSRC)/pt_nee_interior.hip $(CSRC)/pt_nee_lighttree.hip $(CSRC)/pt_nee_arealights.hip
 HDRS    := $(CSRC)/pt_internal.hpp $(CSRC)/pt_context.hpp $(CSRC)/pt_devbuf.hpp $(CSRC)/pt_device.hpp include/pt_api.h
 OBJS    := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 
@@ -57,8 +57,9 @@ check-isa: build/isa/pt_kernels.s build/isa/pt_wavefront.s tools/check_isa.py
 # top, splice, 4-wide collapse) under ThreadSanitizer and under AddressSanitizer + UBSan, on a generated 200k-triangle OBJ,
 # one context and then two at once.  CPU only (host-only contexts); the device objects are linked in unchanged.  First the
 # ownership type of the device arrays on its own, with a counting allocator (tests/cpp/devbuf_test.cpp).
-HOSTSRC := pt_host.cpp pt_builder.cpp pt_launch.cpp pt_obj.cpp pt_wide.cpp pt_image.cpp pt_env.cpp pt_lights.cpp pt_medium.cpp pt_interior.cpp pt_lighttree.cpp pt_arealights.cpp
-DEVOBJ  := build/pt_kernels.hip.o build/pt_wavefront.hip.o build/pt_debug.hip.o build/pt_lbvh.hip.o build/pt_sahdev.hip.o build/pt_widedev.hip.o build/pt_comm.hip.o build/pt_adaptive.hip.o build/pt_denoise.hip.o build/pt_nee.hip.o build/pt_temporal.hip.o build/pt_despeckle.hip.o build/pt_display.hip.o build/pt_shaderec.hip.o build/pt_smooth.hip.o build/pt_texture.hip.o build/pt_glossy.hip.o build/pt_lens.hip.o build/pt_medium.hip.o build/pt_nee_medium.hip.o build/pt_nee_grid.hip.o build/pt_nee_interior.hip.o build/pt_nee_lighttree.hip.o build/pt_nee_arealights.hip.o
+# (every source is named once, in SRCS: the host files are its .cpp, the device objects those of its .hip)
+HOSTSRC := $(notdir $(filter %.cpp,$(SRCS)))
+DEVOBJ  := $(patsubst $(CSRC)/%,build/%.o,$(filter %.hip,$(SRCS)))
 SANFLAGS := -O1 -g -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -Iinclude -I$(CSRC)
 sanitize-host: $(DEVOBJ)
 	@mkdir -p build/san_devbuf && g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o build/san_devbuf/devbuf_test tests/cpp/devbuf_test.cpp && build/san_devbuf/devbuf_test

@@ -54,7 +54,7 @@ void pt_area_lights_defaults(pt_area_lights_params* p) {
 
 int pt_clear_area_lights(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
-    if (ctx->aov_lit) ctx->aov_valid = false;      // lit guides (option aov_lights) show the set: stale, as after an upload
+    post_area_lights_changed(ctx);      // lit guides (option aov_lights) show the set: stale, as after an upload
     ctx->area_lights.clear();      // the device buffers stay until the next set or pt_destroy
     ctx->area_rec.clear();
     ctx->area_cdf.clear();

@@ -1236,9 +1236,7 @@ static void compute_cost_boxes(pt_context* ctx) { compute_cost_boxes_impl(ctx); 
 
 int pt_upload_triangles(pt_context* ctx) {
     if (!ctx) return PT_EINVAL;
-    ctx->aov_valid = false;          // the guides of pt_render_aovs describe the old scene
-    ctx->despeckle_valid = false;    // and pt_despeckle's result a frame of it
-    ctx->display_has_prev = false;   // and pt_display's remembered exposure its brightness
+    post_scene_uploaded(ctx);        // guides, the despeckled frame and the remembered exposure describe the old scene
     ctx->nee_valid = false;          // and the light table its packed order
     ctx->vnormals_dirty = true;      // and the packed vertex normals
     ctx->vuvs_dirty = true;          // and uvs

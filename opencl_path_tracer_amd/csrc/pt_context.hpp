@@ -1,10 +1,16 @@
 // pt_context.hpp -- what the host-side translation units of libptamd.so share: the context behind the opaque pt_context* of
 // include/pt_api.h, the error / HIP-call conventions, the host thread pool, and the functions that cross file boundaries.
-//   pt_host.cpp     the C ABI: constructors, context life cycle, authoring, read-back, options, statistics, debug entry points
+//   pt_host.cpp     the C ABI: constructors, context life cycle, authoring, read-back, options, statistics, debug entry points; the
+//                   NEE launch path (light table, the kernel family a launch takes, pt_render_nee)
 //   pt_builder.cpp  scene -> tree: encounter ranks of end_Obj, the binned-SAH builder (host) and its orchestration on the device,
 //                   big-triangle list, packets, cost boxes; pt_end_obj, pt_upload_triangles
 //   pt_launch.cpp   tree -> launches: node placement (LDS / treelet / 4-wide), stack sizing, kernel parameters, the launch policy
 //                   (instance, schedule, pass length), the wavefront chains; pt_generate_rays, pt_trace_rays, pt_render, pt_sync
+//   pt_post.cpp     the post-process chain: guides, a-trous, variance, variance-guided a-trous, temporal, despeckle, display, and
+//                   the one place that says what makes their results stale
+//   pt_smooth.cpp, pt_texture.cpp, pt_lens.cpp, pt_env.cpp, pt_lights.cpp, pt_arealights.cpp, pt_medium.cpp, pt_interior.cpp,
+//   pt_lighttree.cpp    one scene feature each: its authoring calls, its device copies (*_prepare), its debug entry points
+//   pt_obj.cpp, pt_image.cpp, pt_wide.cpp    the OBJ / MTL loader, the image files, the 4-wide collapse on the host
 // Internal: not part of the ABI.  (`using namespace ptamd` below is deliberate: these files ARE the library.)
 #pragma once
 
@@ -159,6 +165,9 @@ struct pt_context {
     DeviceArray<int32_t> d_adapt_list;   // n_tiles entries, then the count word
     int32_t* h_adapt_count = nullptr;  // pinned
     bool adaptive_frame = false;       // an adaptive frame is held: pt_render / pt_trace_rays / pt_render_adaptive refuse until pt_set_current_sample(0)
+    // ---- the post-process chain (pt_post.cpp).  What says whether a stage's result is current -- aov_valid / shaded / lit / serial / cam,
+    // temporal_history, despeckle_valid, display_ran / has_prev -- is written by pt_post.cpp alone: the other files report an upload or
+    // an authoring call through post_scene_uploaded, post_shading_inputs_changed and post_area_lights_changed below
     // guide buffers (pt_render_aovs) and the a-trous filter (pt_denoise), allocated on first use: per local pixel albedo_rgbm then
     // normal_depth (2 x npix float4); two ping-pong frames (2 x npix float4); d_denoised points at the one the last pt_denoise left
     DeviceArray<float4> d_aov;
@@ -166,7 +175,7 @@ struct pt_context {
     float4* d_denoised = nullptr;
     bool aov_valid = false;            // pt_render_aovs ran and no pt_upload_triangles / pt_upload_materials has made its guides stale
     bool aov_shaded = false;           // the guides are shaded ones (pt_render_aovs_ex, PT_AOV_SHADED): the authoring calls for vertex normals,
-                                       // uvs, textures and bindings make them stale too (shaded_guides_stale, pt_host.cpp)
+                                       // uvs, textures and bindings make them stale too (post_shading_inputs_changed)
     int aov_lights = 0;                // option "aov_lights": guides rendered while an area set with a non-black light is held see its lights
     bool aov_lit = false;              // the last guide launch used a lit instance (stat "aov_lights"): pt_set_area_lights and
                                        // pt_clear_area_lights make such guides stale too
@@ -255,7 +264,7 @@ struct pt_context {
     // albedo textures (option textures, pt_add_texture / pt_set_vertex_uvs / pt_set_material_texture; pinned in include/pt_api.h).
     // Host: every texture's texels back to back (8 B each: three halves r g b and 16 zero bits) with one descriptor per texture, the
     // binding per material (-1: none; shorter than mats: the rest has none) and 6 floats per add-order triangle (NaN where a triangle
-    // has no uvs; shorter than tris: the rest has none).  The device copies are made by texture_prepare (pt_host.cpp) at the first
+    // has no uvs; shorter than tris: the rest has none).  The device copies are made by texture_prepare (pt_texture.cpp) at the first
     // textured launch after any of them, the uploaded triangles or the uploaded materials changed; d_vuvs: 2 float4 per packed
     // triangle (k_pack_vertex_uvs, pt_texture.hip); d_mat_tex: per material on the device the binding, -1 where its type is not 0
     int textures = 0;
@@ -418,9 +427,9 @@ inline std::string medium_refusal(const std::string& who) {
 }
 // a lens with aperture > 0 is set: only pt_render_nee and the NEE path of pt_render_adaptive_ex render
 inline bool lens_on(const pt_context* ctx) { return ctx->lens_set && ctx->lens_aperture > 0.0f; }
-// pt_host.cpp: the packed vertex normals on the device for a smooth launch (repacked if stale); *vn = null when the option is off, unless force
+// pt_smooth.cpp: the packed vertex normals on the device for a smooth launch (repacked if stale); *vn = null when the option is off, unless force
 int smooth_prepare(pt_context* ctx, const float4** vn, bool force = false);
-// pt_host.cpp: the textures, bindings and packed uvs on the device for a textured launch (refreshed if stale); tv->uv = null when the
+// pt_texture.cpp: the textures, bindings and packed uvs on the device for a textured launch (refreshed if stale); tv->uv = null when the
 // option is off, unless force
 int texture_prepare(pt_context* ctx, TexView* tv, bool force = false);
 // pt_host.cpp: the NEE launch the context's options, materials and lens ask for (NeeLaunch, pt_internal.hpp), with the vertex normals and
@@ -430,6 +439,13 @@ int nee_launch_for(pt_context* ctx, const pt_camera* cam, bool nee_on, NeeLaunch
 // tiled) and the workgroup size the launcher chose -- is kept for pt_get_stat ("nee_family", "nee_form", "nee_block")
 hipError_t launch_nee_noted(pt_context* ctx, const RenderParams& p, const NeeTable& lt, const NeeLaunch& nl);
 int host_threads(const pt_context* ctx);                        // threads of the host-side scene path (option build_threads)
+int read_back(pt_context* ctx, void* dst, const void* src, size_t bytes);      // pt_host.cpp: sync_and_check, then device -> host
+// pt_post.cpp: what the rest of the library tells the post-process chain.  The scene was uploaded (guides, the despeckled frame and the
+// remembered exposure are stale); an input of shaded guides changed (vertex normals, uvs, textures, bindings: shaded guides are stale);
+// the area set changed (lit guides are stale)
+void post_scene_uploaded(pt_context* ctx);
+void post_shading_inputs_changed(pt_context* ctx);
+void post_area_lights_changed(pt_context* ctx);
 
 #define PT_HIP(ctx, call)                                                                   \
     do {                                                                                    \

@@ -188,6 +188,29 @@ def test_option_validation(api):
         with pytest.raises(api.PtError) as e:
             sc.set_option(key, bad)
         assert e.value.code == api.PT_EINVAL, key
+    # every option of pt_set_option's table: its lowest and highest accepted value are accepted, the values just outside are refused
+    # with a text that begins with the key; the values inside the range that are still refused are
+    ranges = {"variant": (0, 1), "lds_scene": (0, 2), "treelet": (-1, 2048), "lbvh_cluster": (0, 1 << 20), "build_threads": (0, 256),
+              "wide_nodes": (0, 2), "wide_lds_entries": (4, 20), "moments": (0, 1), "smooth_normals": (0, 1), "textures": (0, 1), "glossy": (0, 1),
+              "coated": (0, 1), "frosted": (0, 1), "light_tree": (0, 1), "aov_lights": (0, 1), "chunk_taper": (-1, 1 << 15), "chunk_spp": (-1, 1 << 20),
+              "sah_visit_cost": (0, 1000), "schedule": (-1, 2), "flat_list": (0, 32), "poll_timeout_ms": (1, 40000),
+              "debug_stall_tile": (-1, 0x7fffffff), "wf_streams": (-1, 8), "node_min_lanes": (-1, 63), "leaf_min_lanes": (-1, 63),
+              "migrate_lanes": (-1, 64), "suspend_lanes": (-1, 63), "waves_per_simd": (-1, 8), "bvh_device": (-1, 1), "wide_on_device": (0, 1),
+              "sah_grain": (8, 1 << 16), "lbvh_ploc": (0, 32), "lds_block": (-1, 768), "debug_repeat": (0, 1000), "bvh_policy": (0, 5)}
+    holes = {"lds_scene": (1,), "wide_lds_entries": (5, 19), "wf_streams": (0,), "migrate_lanes": (0,), "waves_per_simd": (0, 3), "lbvh_ploc": (1, 7, 24),
+             "lds_block": (0, 511, 513, 767)}
+    for key, (lo, hi) in ranges.items():
+        sc.set_option(key, lo)
+        sc.set_option(key, hi)
+        for bad in (lo - 1, hi + 1, -(1 << 40), 1 << 40) + holes.get(key, ()):
+            with pytest.raises(api.PtError) as e:
+                sc.set_option(key, bad)
+            assert e.value.code == api.PT_EINVAL, (key, bad)
+            assert api.LIB.pt_last_error(sc._h).decode().startswith(key), (key, bad)
+    for key in ("timing", "count_work", "persistent", "cost_binning"):      # flags: any value, kept as 0 / 1
+        for v in (0, 1, -5, 1 << 40):
+            sc.set_option(key, v)
+    sc.close()
 
 
 def test_bvh_never_culls_a_real_hit(api, oracle, cb_spec, cb_oracle_scene):
