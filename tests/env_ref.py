@@ -5,6 +5,7 @@ the tables themselves (tests/test_env_host.py)."""
 import numpy as np
 
 import nee_ref as R
+from path_ref import PathModel
 
 EDGE_MARGIN = 1e-4          # radians: a miss direction this close to a texel edge may read the neighbour in float32
 SELECT_MARGIN = 2.0 ** -20
@@ -69,159 +70,10 @@ def texel_pdf(row_cdf, col_cdf):
     return pr[:, None] * pc / solid_angles(w, h)[:, None]
 
 
-class EnvModel(R.Model):
-    """nee_ref.Model plus an environment: rgb (h, w, 3), scale, yaw_degrees, and Scene.debug_environment()'s tables."""
+class EnvModel(PathModel):
+    """nee_ref.Model plus an environment: rgb (h, w, 3), scale, yaw_degrees, and Scene.debug_environment()'s tables (no triangles at all:
+    only the camera and the sky)."""
 
     def __init__(self, verts, normals, mats, mat_of, cam, rgb, env_tables, scale=1.0, yaw_degrees=0.0, table=None, margin=1e-4):
-        if len(verts):
-            super().__init__(verts, normals, mats, mat_of, cam, table=table, margin=margin)
-        else:                                   # no triangles at all: only the camera and the sky
-            self.v = np.zeros((0, 3, 3))
-            self.cam, self.lights, self.mats = cam, np.zeros(0, dtype=np.int64), mats
-        self.rgb = np.asarray(rgb, dtype=np.float32).astype(np.float64)
-        self.h, self.w = self.rgb.shape[:2]
-        self.scale = float(np.float32(scale))
-        self.yaw_degrees = yaw_degrees
-        self.row_cdf = np.asarray(env_tables["row_cdf"], dtype=np.float32)
-        self.col_cdf = np.asarray(env_tables["col_cdf"], dtype=np.float32)
-        self.pdf = np.asarray(env_tables["pdf"], dtype=np.float64)
-        self.pe = float(env_tables["P_env"])
-        self.has_dist = bool((self.pdf > 0).any())
-
-    def intersect(self, P, D, limit=np.inf):
-        if not len(self.v):
-            return -1, np.inf, False
-        return super().intersect(P, D, limit)
-
-    def sky(self, d):
-        """(E(d), p_env(d), near a texel edge)"""
-        row, col, dist = lookup(self.w, self.h, self.yaw_degrees, d)
-        return self.rgb[row, col] * self.scale, float(self.pdf[row, col]), dist < EDGE_MARGIN
-
-    def sky_sample(self, u1, u2):
-        """(direction, E, p_env) of the texel u1, u2 pick"""
-        row = min(int(np.searchsorted(self.row_cdf, np.float32(u1), side="right")), self.h - 1)
-        rb = float(self.row_cdf[row - 1]) if row else 0.0
-        t1 = (u1 - rb) / (float(self.row_cdf[row]) - rb)
-        cc = self.col_cdf[row]
-        col = min(int(np.searchsorted(cc, np.float32(u2), side="right")), self.w - 1)
-        cb = float(cc[col - 1]) if col else 0.0
-        t2 = (u2 - cb) / (float(cc[col]) - cb)
-        c0, c1 = np.cos(np.pi * row / self.h), np.cos(np.pi * (row + 1) / self.h)
-        ct = c0 - t1 * (c0 - c1)
-        sn = np.sqrt(max(0.0, 1.0 - ct * ct))
-        phi = 2.0 * np.pi * ((col + t2) / self.w) + yaw_radians(self.yaw_degrees)
-        return np.array([sn * np.cos(phi), ct, sn * np.sin(phi)]), self.rgb[row, col] * self.scale, float(self.pdf[row, col])
-
-    def sample(self, gid, seed, iterations, strategy):
-        """one sample of pixel gid: (colour, new LCG state, near-tie seen)"""
-        key = int(seed) & 0xFFFFFFFF
-        tie = False
-        seed, r1 = R.lcg(seed)
-        seed, r2 = R.lcg(seed)
-        P, D = self.camera_ray(gid, r1, r2)
-        one = np.ones(3)
-        fL, fB, fS, fR, C = one.copy(), one.copy(), one.copy(), one.copy(), np.zeros(3)
-        after_lobe, Nprev = False, None
-        nee = strategy != 0 and (len(self.lights) > 0 or self.has_dist)
-        pe = self.pe
-        for k in range(iterations):
-            ti, t, tt = self.intersect(P, D)
-            tie |= tt
-            if ti < 0:
-                E, penv, edge = self.sky(D)
-                tie |= edge
-                if k == 0:
-                    C = C + E
-                else:
-                    wb = 1.0
-                    pl = pe * penv
-                    if nee and after_lobe and pl > 0:
-                        if strategy == 1:
-                            wb = 0.0
-                        else:
-                            pb = max(0.0, float(Nprev @ D)) / np.pi
-                            wb = pb * pb / (pb * pb + pl * pl)
-                    C = C + E * (fL + fB) * fS * fR * wb
-                break
-            m = self._mat(ti)
-            typ = int(m["type"])
-            N = self.n[ti].copy()
-            hp = P + D * t
-            E = m["emission"][:3].astype(np.float64)
-            if iterations == 1:
-                C = m["kd"][:3].astype(np.float64) + E
-            if D @ N > 0:
-                N = -N
-            if typ in (0, 3):
-                inten = max(0.0, float(-D @ N))
-                wb = 1.0
-                pa = self.pdf_area[ti] * (1.0 - pe)
-                if typ == 3 and nee and after_lobe and pa > 0 and inten > 0:
-                    if strategy == 1:
-                        wb = 0.0
-                    else:
-                        pb = max(0.0, float(Nprev @ D)) / np.pi
-                        pl = pa * t * t / inten
-                        wb = pb * pb / (pb * pb + pl * pl)
-                if nee and k + 1 < iterations:
-                    u0 = R.nee_unit(R.nee_rand(key, k, 0))
-                    u1 = R.nee_unit(R.nee_rand(key, k, 1))
-                    u2 = R.nee_unit(R.nee_rand(key, k, 2))
-                    us = R.nee_unit(R.nee_rand(~key & 0xFFFFFFFF, k, 0))
-                    tie |= abs(us - pe) < SELECT_MARGIN and 0.0 < pe < 1.0
-                    o = hp + N * 0.001
-                    add = None
-                    if us < pe:
-                        w, Ey, penv = self.sky_sample(u1, u2)
-                        cosx = float(N @ w)
-                        pl = pe * penv
-                        if cosx > 0 and pl > 0:
-                            hi, _, st = self.intersect(o, w)
-                            tie |= st
-                            if hi < 0:
-                                add = (Ey, pl, 1.0, cosx, w)
-                    elif len(self.lights):
-                        j = min(int(np.searchsorted(self.cdf, np.float32(u0), side="right")), len(self.cdf) - 1)
-                        li = int(self.lights[j])
-                        v = self.v[li]
-                        su = np.sqrt(u1)
-                        y = v[0] + (v[1] - v[0]) * (u2 * su) + (v[2] - v[0]) * (su * (1.0 - u2))
-                        d = y - o
-                        r = np.linalg.norm(d)
-                        w = d / r
-                        cosx = float(N @ w)
-                        cosy = abs(float(w @ self.n[li]))
-                        if cosx > 0 and cosy > 0:
-                            pl = self.pdf_area[li] * (1.0 - pe) * r * r / cosy
-                            if pl > 0:
-                                hi, _, st = self.intersect(o, w, r * R.SHADOW_CUT)
-                                tie |= st
-                                if hi == li:
-                                    add = (self._mat(li)["emission"][:3].astype(np.float64), pl, cosy, cosx, w)
-                    if add is not None:
-                        Ey, pl, g, cosx, w = add
-                        pb = cosx / np.pi
-                        wl = pb / pl if strategy == 1 else pb * pl / (pb * pb + pl * pl)
-                        fl, fb = (self._update(m, N, hp, w, fL, fB) if typ == 0 else (fL, fB))
-                        C = C + Ey * (fl + fb) * fS * fR * (g * wl)
-                seed, r1 = R.lcg(seed)
-                seed, r2 = R.lcg(seed)
-                nd = self.diffuse_dir(N, r1, r2)
-                if typ == 0:
-                    fL, fB = self._update(m, N, hp, nd, fL, fB)
-                else:
-                    C = C + E * (fL + fB) * fS * fR * (inten * wb)
-                P, D = hp + N * 0.001, nd
-                after_lobe, Nprev = True, N
-            elif typ == 1:
-                F0 = m["F0"][:3].astype(np.float64)
-                cosa = abs(float(N @ D))
-                F = F0 + (1.0 - F0) * (1.0 - cosa) ** 5
-                fS = fS * F
-                nd = D - N * (2.0 * float(N @ D))
-                P, D = hp + N * 0.001, nd / np.linalg.norm(nd)
-                after_lobe = False
-            else:
-                raise NotImplementedError("the model covers material types 0, 1 and 3")
-        return C, seed, tie
+        super().__init__(verts, normals, mats, mat_of, cam, table=table, margin=margin, side_margins=False,
+                         env=dict(rgb=rgb, tables=env_tables, scale=scale, yaw_degrees=yaw_degrees))

@@ -1,6 +1,6 @@
 """Float64 statement of the medium's density grid (Scene.set_medium_density; include/pt_api.h pins the walk): walk(), the regular
-tracking the grid instances of k_nee run in float32, step for step, and GridModel, tests/medium_ref.py's MediumModel with only the free
-flight and the transmittance replaced.  tests/test_grid_host.py checks walk() against brute-force integration of the density along
+tracking the grid instances of k_nee run in float32, step for step, and GridModel, tests/medium_ref.py's MediumModel with the free
+flight and the transmittance taken from walk() (the setting `density` of tests/path_ref.py's PathModel).  tests/test_grid_host.py checks walk() against brute-force integration of the density along
 random rays and GridModel against MediumModel on a 1 x 1 x 1 unit grid; tests/test_gpu_grid.py holds pt_debug_grid and the frames to them."""
 import numpy as np
 
@@ -91,58 +91,17 @@ def brute_depth(sigma_t, density, lo, hi, P, D, t0, t1, steps=200000):
     return float((sigma_t * rho[g[:, 2], g[:, 1], g[:, 0]] * inside).sum() * ((t1 - t0) / steps))
 
 
+EVENTS = M.EVENTS + ("grid_scatter_thin", "grid_scatter_dense", "grid_empty_crossed", "grid_light_partial")
+
+
 class GridModel(M.MediumModel):
-    """medium_ref.MediumModel with a density grid: density = Scene.medium_density() (None: the model is MediumModel's).  MediumModel.sample
-    reaches the medium through three functions of its module -- clip and flight for the free flight, transmittance for a light sample --
-    and sample() here runs it with flight and transmittance replaced by walk() for the duration of the call (clip stays, and leaves the
-    segment with flight): the rest of the estimator is MediumModel's own code, not a copy.  The free flight is handed back as the
-    distance past the clip's entry, (t_cur - a) + d, or +inf without a scatter, so MediumModel's `d < b - a` and `a + d` decide and place as
-    the walk did.  Near ties of the walk (SCATTER_MARGIN, PLANE_MARGIN) are added to the sample's."""
+    """medium_ref.MediumModel with a density grid: density = Scene.medium_density() (None: the model is MediumModel's).  The free flight
+    and the transmittance of a light sample come from walk() in place of flight() and transmittance() (clip stays, and leaves the
+    segment with the flight), and the walk's near ties (SCATTER_MARGIN, PLANE_MARGIN) are added to the sample's.  dense_from: a scatter
+    vertex counts as "dense" in a voxel of at least this density, else "thin"."""
 
-    EVENTS = M.MediumModel.EVENTS + ("grid_scatter_thin", "grid_scatter_dense", "grid_empty_crossed", "grid_light_partial")
+    EVENTS = EVENTS
 
-    def __init__(self, *args, density=None, dense_from=2.0, **kw):
-        super().__init__(*args, **kw)
-        self.density = None if density is None or self.medium is None else np.asarray(density, dtype=np.float64)
-        self.dense_from = dense_from           # a scatter vertex counts as "dense" in a voxel of at least this density, else "thin"
-
-    def _walk(self, P, D, t, tau):
-        med = self.medium
-        w = walk(med["sigma_t"], self.density, med["lo"], med["hi"], P, D, t, tau)
-        self._tie |= w["near"] or w["margin"] < SCATTER_MARGIN
-        return w
-
-    def _clip(self, lo, hi, P, D, t):
-        self._segment = (P, D, t)
-        return self._real_clip(lo, hi, P, D, t)
-
-    def _flight(self, sigma_t, u):
-        P, D, t = self._segment
-        w = self._walk(P, D, t, -np.log1p(-u))
-        rho = self.density.reshape(-1)
-        crossed = [v for v, t0, t1 in w["voxels"][:-1 if w["scatter"] else None] if t1 > t0]
-        self.last["grid_empty_crossed"] += int(any(rho[v] == 0.0 for v in crossed) and any(rho[v] > 0.0 for v in crossed))
-        if not w["scatter"]:
-            return np.inf
-        self.last["grid_scatter_dense" if rho[w["voxel"]] >= self.dense_from else "grid_scatter_thin"] += 1
-        return (w["t_cur"] - w["a"]) + w["d"]          # (on a 1 x 1 x 1 grid t_cur = a: d itself, MediumModel's own number)
-
-    def _transmittance(self, med, o, w, limit):
-        k = self._walk(o, w, limit, np.inf)
-        T = float(np.exp(-k["acc"]))
-        lit = {v for v, t0, t1 in k["voxels"] if t1 > t0 and self.density.reshape(-1)[v] > 0.0}
-        self.last["grid_light_partial"] += int(0.0 < T < 1.0 and len(lit) >= 2)
-        return T, False
-
-    def sample(self, gid, seed, iterations, strategy):
-        if self.density is None:
-            return super().sample(gid, seed, iterations, strategy)
-        self._tie = False
-        self._real_clip = M.clip
-        saved = M.clip, M.flight, M.transmittance
-        M.clip, M.flight, M.transmittance = self._clip, self._flight, self._transmittance
-        try:
-            C, seed, tie = super().sample(gid, seed, iterations, strategy)
-        finally:
-            M.clip, M.flight, M.transmittance = saved
-        return C, seed, bool(tie or self._tie)
+    def __init__(self, *args, density=None, dense_from=2.0, **settings):
+        settings.setdefault("events", M.S.BASE_EVENTS + EVENTS)
+        super().__init__(*args, density=density, dense_from=dense_from, **settings)

@@ -1,5 +1,5 @@
-"""Float64 numpy statement of the thin-lens ray of Scene.set_lens (include/pt_api.h pins it), as a mixin over tests/nee_ref.py's Model and
-its subclasses, and a float32 restatement of the pinned sequence that the tests measure their tolerance with.  It shares no code with the
+"""Float64 numpy statement of the thin-lens ray of Scene.set_lens (include/pt_api.h pins it), which tests/path_ref.py's PathModel takes as
+its camera ray after set_lens, and a float32 restatement of the pinned sequence that the tests measure their tolerance with.  It shares no code with the
 library."""
 import numpy as np
 
@@ -73,22 +73,5 @@ def distance_to_ray(Q, P, D):
 
 
 class LensMixin:
-    """class LensModel(LensMixin, SomeModel): the model's camera ray becomes the lens ray once set_lens(aperture > 0, focus) was called.
-    The key S is the seed sample() is called with: every Model computes its own key from it before the two draws of the camera ray, so
-    wrapping sample() keeps it without touching the estimator."""
-
-    lens = None
-
-    def set_lens(self, aperture, focus):
-        self.lens = (float(aperture), float(focus)) if aperture > 0 else None
-        return self
-
-    def sample(self, gid, seed, iterations, strategy):
-        self._lens_key = int(seed)
-        return super().sample(gid, seed, iterations, strategy)
-
-    def camera_ray(self, gid, rnd1, rnd2):
-        if self.lens is None:
-            return super().camera_ray(gid, rnd1, rnd2)
-        P, D, _ = lens_rays(self.cam, self.lens[0], self.lens[1], [gid], [self._lens_key], rnd=([rnd1], [rnd2]))
-        return P[0], D[0]
+    """class LensModel(LensMixin, SomeModel): kept for the tests that name it.  The lens is a setting of tests/path_ref.py's PathModel:
+    set_lens(aperture > 0, focus) turns every model's camera ray into lens_rays' of the seed sample() was called with."""

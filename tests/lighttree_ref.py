@@ -1,6 +1,6 @@
 """Float64 model of the light hierarchy of Scene.render_nee (option light_tree; include/pt_api.h pins the tree, the walk and the
 probabilities): the walk over the nodes Scene.debug_light_tree() returns, and tests/nee_ref.py's estimator with it (TreeModel: the
-existing model is imported, its sample() restated with the pick and the weight walk in place of the table's cdf and P_sel).  Also
+setting `tree` of tests/path_ref.py's PathModel puts the pick and the weight walk in place of the table's cdf and P_sel).  Also
 the invariants a tree must satisfy, as the host test states them."""
 import numpy as np
 
@@ -126,96 +126,13 @@ def check_invariants(nodes, orig_tri, verts, phi_of):
 
 
 class TreeModel(R.Model):
-    """nee_ref.Model with the light hierarchy: `tree` a Tree over the same lights.  sample() is nee_ref's with the pick in place of the
-    cdf search and P inv_area in place of P_sel / area, from the origin and the cull normal of the lobe vertex."""
+    """nee_ref.Model with the light hierarchy: `tree` a Tree over the same lights; the pick in place of the cdf search and P inv_area
+    in place of P_sel / area, from the origin and the cull normal of the lobe vertex."""
 
     def __init__(self, *args, tree=None, **kw):
         super().__init__(*args, **kw)
         self.tree = tree
         assert sorted(tree.tri.tolist()) == sorted(int(x) for x in self.lights)
-
-    def sample(self, gid, seed, iterations, strategy):
-        lcg, nee_unit, nee_rand = R.lcg, R.nee_unit, R.nee_rand
-        key = int(seed) & 0xFFFFFFFF
-        tie = False
-        seed, r1 = lcg(seed)
-        seed, r2 = lcg(seed)
-        P, D = self.camera_ray(gid, r1, r2)
-        one = np.ones(3)
-        fL, fB, fS, fR, C = one.copy(), one.copy(), one.copy(), one.copy(), np.zeros(3)
-        after_lobe, Nprev, oprev = False, None, None
-        nee = len(self.lights) > 0 and strategy != 0
-        for k in range(iterations):
-            ti, t, tt = self.intersect(P, D)
-            tie |= tt
-            if ti < 0:
-                break
-            m = self._mat(ti)
-            typ = int(m["type"])
-            N = self.n[ti].copy()
-            hp = P + D * t
-            E = m["emission"][:3].astype(np.float64)
-            if iterations == 1:
-                C = m["kd"][:3].astype(np.float64) + E
-            if D @ N > 0:
-                N = -N
-            if typ in (0, 3):
-                inten = max(0.0, float(-D @ N))
-                wb = 1.0
-                if typ == 3 and nee and after_lobe and inten > 0:
-                    pa = self.tree.weight(oprev, Nprev, self.tree.slot_of.get(int(ti), -1)) / self.area[ti]
-                    if pa > 0:
-                        if strategy == 1:
-                            wb = 0.0
-                        else:
-                            pb = max(0.0, float(Nprev @ D)) / np.pi
-                            pl = pa * t * t / inten
-                            wb = pb * pb / (pb * pb + pl * pl)
-                o = hp + N * 0.001
-                if nee and k + 1 < iterations:
-                    u0 = nee_unit(nee_rand(key, k, 0))
-                    u1 = nee_unit(nee_rand(key, k, 1))
-                    u2 = nee_unit(nee_rand(key, k, 2))
-                    slot, Psel, _ = self.tree.pick(o, N, u0)
-                    li = int(self.tree.tri[slot])
-                    v = self.v[li]
-                    su = np.sqrt(u1)
-                    y = v[0] + (v[1] - v[0]) * (u2 * su) + (v[2] - v[0]) * (su * (1.0 - u2))
-                    d = y - o
-                    r = np.linalg.norm(d)
-                    w = d / r
-                    cosx = float(N @ w)
-                    cosy = abs(float(w @ self.n[li]))
-                    if cosx > 0 and cosy > 0 and Psel > 0:
-                        hi, _, st = self.intersect(o, w, r * R.SHADOW_CUT)
-                        tie |= st
-                        if hi == li:
-                            pb = cosx / np.pi
-                            pl = Psel / self.area[li] * r * r / cosy
-                            wl = pb / pl if strategy == 1 else pb * pl / (pb * pb + pl * pl)
-                            fl, fb = (self._update(m, N, hp, w, fL, fB) if typ == 0 else (fL, fB))
-                            Ey = self._mat(li)["emission"][:3].astype(np.float64)
-                            C = C + Ey * (fl + fb) * fS * fR * (cosy * wl)
-                seed, r1 = lcg(seed)
-                seed, r2 = lcg(seed)
-                nd = self.diffuse_dir(N, r1, r2)
-                if typ == 0:
-                    fL, fB = self._update(m, N, hp, nd, fL, fB)
-                else:
-                    C = C + E * (fL + fB) * fS * fR * (inten * wb)
-                P, D = o, nd
-                after_lobe, Nprev, oprev = True, N, o
-            elif typ == 1:
-                F0 = m["F0"][:3].astype(np.float64)
-                cosa = abs(float(N @ D))
-                F = F0 + (1.0 - F0) * (1.0 - cosa) ** 5
-                fS = fS * F
-                nd = D - N * (2.0 * float(N @ D))
-                P, D = hp + N * 0.001, nd / np.linalg.norm(nd)
-                after_lobe = False
-            else:
-                raise NotImplementedError("the model covers material types 0, 1 and 3")
-        return C, seed, tie
 
 
 def variance_ratio_prediction(tree, table_phi, points, normals, verts, emission_sum):

@@ -281,8 +281,8 @@ def replay_spec():
     return spec
 
 
-def replay_scene(api, spec, sky, W, H, smooth=True):
-    sc, env = TG.replay_scene(api, spec, sky, W, H, smooth)      # (option glossy on)
+def replay_scene(api, spec, sky, W, H, smooth=True, device=0):
+    sc, env = TG.replay_scene(api, spec, sky, W, H, smooth, device)     # (option glossy on)
     sc.set_option("coated", 1)
     return sc, env
 

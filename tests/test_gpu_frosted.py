@@ -287,8 +287,8 @@ def replay_spec():
     return spec
 
 
-def replay_scene(api, spec, sky, W, H, smooth=True):
-    sc, env = TC.replay_scene(api, spec, sky, W, H, smooth)      # (options glossy and coated on)
+def replay_scene(api, spec, sky, W, H, smooth=True, device=0):
+    sc, env = TC.replay_scene(api, spec, sky, W, H, smooth, device)     # (options glossy and coated on)
     sc.set_option("frosted", 1)
     return sc, env
 

@@ -311,9 +311,9 @@ def replay_model(api, sc, spec, env=None, table=None, smooth=True):
     return G.GlossyModel(verts, recs["N"], mats, mo, sc.camera[0], vn, env=env, table=table)
 
 
-def replay_scene(api, spec, sky, W, H, smooth=True):
+def replay_scene(api, spec, sky, W, H, smooth=True, device=0):
     from opencl_path_tracer_amd import scenes
-    sc = api.Scene(W, H).load(spec)
+    sc = api.Scene(W, H, device=device).load(spec)
     env = None
     if sky:
         rgb = scenes.sun_and_sky()

@@ -230,6 +230,7 @@ def test_a_unit_grid_is_the_medium_model_exactly(api):
                         sc.debug_lights(), sc.medium(), env=env, table=sc.debug_light_table(), density=sc.medium_density())
     seeds = TL.replay_seeds()
     scattered = 0
+    module = M.clip, M.flight, M.transmittance
     for gid in range(5, TL.REPLAY["W"] * TL.REPLAY["H"], 37):
         for strategy in (1, 2):
             a = plain.sample(gid, int(seeds[gid]), 4, strategy)
@@ -238,7 +239,7 @@ def test_a_unit_grid_is_the_medium_model_exactly(api):
             assert np.array_equal(a[0], b[0]) and a[1] == b[1] and (a[2] or not b[2]), gid      # (the walk may add a tie, never lose one)
             assert all(grid.last[k] == v for k, v in events.items())
             scattered += events["scatter"]
-    assert scattered > 20 and M.clip is not grid._clip                # the module is as it was after the calls
+    assert scattered > 20 and (M.clip, M.flight, M.transmittance) == module          # the module is as it was after the calls
     none = GR.GridModel(verts, api.triangles_from_vertices(verts, mo)["N"], np.concatenate([api.Material(*m) for m in spec.materials]), mo, sc.camera[0],
                         sc.debug_lights(), sc.medium(), env=env, table=sc.debug_light_table(), density=None)
     assert np.array_equal(none.sample(5, int(seeds[5]), 4, 2)[0], plain.sample(5, int(seeds[5]), 4, 2)[0])

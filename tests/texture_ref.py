@@ -61,54 +61,9 @@ def albedo(kd, v, N, hp, uv, texels, filt):
     return np.asarray(kd, dtype=np.float64) * tex, near
 
 
-class _Vertex:
-    """a material record as the model reads it, with the triangle it was fetched for and, once known, the textured kd"""
-
-    def __init__(self, rec, ti, kd=None):
-        self.rec, self.ti, self.kd = rec, ti, kd
-
-    def __getitem__(self, key):
-        if key == "kd" and self.kd is not None:
-            return self.kd
-        return self.rec[key]
-
-
 class TextureModel(S.SmoothModel):
     """smooth_ref.SmoothModel with albedo textures: uvs (n,3,2) as recorded (add order; non-finite where a triangle has none),
     textures = [(texels (h,w,3) of Scene.debug_texture, filter)], mat_tex = {material index: texture index}."""
 
     def __init__(self, verts, normals, mats, mat_of, cam, vnormals, uvs, textures, mat_tex, env=None, table=None, margin=1e-4):
-        super().__init__(verts, normals, mats, mat_of, cam, vnormals, env=env, table=table, margin=margin)
-        self.uv = np.asarray(uvs, dtype=np.float32).reshape(-1, 3, 2)
-        self.has_uv = has_uvs(self.uv)
-        self.textures = [(np.asarray(t, dtype=np.float32), int(f)) for t, f in textures]
-        self.mat_tex = dict(mat_tex)
-        self.textured_vertices = 0
-        self._tie = False
-
-    def _mat(self, ti):
-        return _Vertex(self.mats[int(self.mat_of[ti])], int(ti))
-
-    def albedo_at(self, ti, hp):
-        """(kd', near a decision, textured) of a hit at hp on triangle ti"""
-        m = self.mats[int(self.mat_of[ti])]
-        kd = m["kd"][:3].astype(np.float64)
-        T = self.mat_tex.get(int(self.mat_of[ti]), -1)
-        if int(m["type"]) != 0 or T is None or T < 0 or not self.has_uv[ti]:
-            return kd, False, False
-        texels, filt = self.textures[T]
-        out, near = albedo(kd, self.v[ti], self.n[ti], hp, self.uv[ti], texels, filt)
-        return out, near, True
-
-    def _update(self, m, N, hp, w, fL, fB):
-        kd, near, textured = self.albedo_at(m.ti, hp)
-        self._tie |= near
-        self.textured_vertices += int(textured)
-        return super()._update(_Vertex(m.rec, m.ti, kd), N, hp, w, fL, fB)
-
-    def sample(self, gid, seed, iterations, strategy):
-        if iterations == 1:
-            raise NotImplementedError("the preview of iterations == 1 is not modelled")
-        self._tie = False
-        c, s, tie = super().sample(gid, seed, iterations, strategy)
-        return c, s, bool(tie or self._tie)
+        super().__init__(verts, normals, mats, mat_of, cam, vnormals, env=env, table=table, margin=margin, uvs=uvs, textures=textures, mat_tex=mat_tex)
