@@ -1334,7 +1334,8 @@ int pt_set_option(pt_context* ctx, const char* key, int64_t value);
  * pt_render_nee or of an NEE round of pt_render_adaptive_ex took: the kernel family 0..10 -- plain, smooth, tex, glossy,
  * coated, lens, frosted, lights, medium, grid (a medium with a live density grid), interior (a material holds an interior) --, the form -- bit 0 an environment is drawn, bit 1 tiled -- and the workgroup
  * size; -1 each before the first such launch), "treelet_nodes", "wide_nodes" (how many 4-wide nodes),
- * "wide_pending" (their worst-case stack), "flat_triangles", "flat_boxes" (their distinct bounding boxes), and with
+ * "wide_pending" (their worst-case stack), "flat_triangles", "flat_boxes" (their distinct bounding boxes), "obj_pieces" (into how
+ * many pieces the last pt_add_obj cut its file for the parallel parse; 0 before the first), and with
  * count_work: "node_visits", "tri_tests", "wave_node_steps", "wave_tri_steps", "tile_lane_steps", "wave_shade_steps",
  * "wave_trips", "wave_rounds" */
 int pt_get_stat(pt_context* ctx, const char* key, double* out);

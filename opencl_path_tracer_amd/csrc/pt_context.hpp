@@ -278,6 +278,7 @@ struct pt_context {
     DeviceArray<int32_t> d_mat_tex;
     DeviceArray<float4> d_vuvs;
     int obj_textures_loaded = 0, obj_textures_skipped = 0;      // map_Kd lines of the last pt_add_obj
+    int obj_pieces = 0;                                         // pieces its parse cut the file into
     // rough metal (option glossy; pinned in include/pt_api.h): material type 4 is a GGX lobe vertex in pt_render_nee.  The glossy k_nee
     // instances run only when the option is on AND the materials uploaded last hold a type-4 one; every other frame is today's launch
     int glossy = 0;

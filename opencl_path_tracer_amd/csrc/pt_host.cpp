@@ -837,6 +837,7 @@ int pt_get_stat(pt_context* ctx, const char* key, double* out) {
     if (k == "flat_triangles") { *out = (double)ctx->n_flat; return PT_OK; }
     if (k == "obj_textures_loaded") { *out = (double)ctx->obj_textures_loaded; return PT_OK; }
     if (k == "obj_textures_skipped") { *out = (double)ctx->obj_textures_skipped; return PT_OK; }
+    if (k == "obj_pieces") { *out = (double)ctx->obj_pieces; return PT_OK; }
     if (k == "flat_boxes") { *out = (double)ctx->n_fbox; return PT_OK; }
     if (k == "node_mode") {      // what the next launch will use: 0 whole tree in LDS, 1 L1/L2 only, 2 treelet
         pt_camera cam;

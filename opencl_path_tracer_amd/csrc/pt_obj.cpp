@@ -3,6 +3,9 @@
 // an own minimal reader that reproduces the parts of its behaviour add_Obj depends on:
 //   * v / f records; f accepts i, i/j, i//k, i/j/k; negative (relative) indices
 //     (tiny_obj_loader.h:410-414); polygons are fan-triangulated (tiny_obj_loader.h:893-916)
+//   * numbers: the token's shape is the reference's grammar (tiny_obj_loader.h:437-443: sign, digits, optional fraction,
+//     optional non-empty exponent; anything else is the default 0, so `.5`, `nan`, `inf`, `1e`, `0x10` read as 0), its value
+//     strtod's -- on the number forms exporters write the two give the same float (tests/golden/obj/numbers.obj)
 //   * shapes are split on g / o (tiny_obj_loader.h:1509-1567); usemtl switches the per-face
 //     material without starting a new shape (tiny_obj_loader.h:1452-1478)
 //   * MTL: newmtl, Kd, Ks, Ke, Ns; every other "key value" line is kept as a string, first
@@ -16,6 +19,7 @@
 // New as well (the reference throws vt and map_Kd away): a face whose corners all carry a vt index records those uvs for its fan
 // triangles (pt_set_vertex_uvs), and a material's map_Kd -- a .ppm or .pfm next to the MTL -- becomes a texture bound to the material
 // pt_add_obj creates (pt_add_texture / pt_set_material_texture; include/pt_api.h).  A map that cannot be used leaves the material as it was.
+// In a vt or vn position an index 0 (or nothing behind the slash) means "no index" here; the reference's fixIndex reads it as the first element.
 // Deviations, all turning undefined behaviour of the reference into errors: a missing
 // Kn/Kk/Tp, a face without usemtl (material id -1) and an empty shape return PT_EIO.
 #include "pt_context.hpp"
@@ -88,7 +92,7 @@ bool next_line(char** cur, char* end, char** line) {
 }
 
 // One number: the token runs to the next blank / tab (lines are NUL-terminated in the buffer); its value is what strtod
-// makes of the token's prefix, 0 if nothing converts.  strtod runs on the buffer itself -- it stops at the blank or NUL that
+// makes of the token's prefix where the reference's grammar accepts one, else 0.  strtod runs on the buffer itself -- it stops at the blank or NUL that
 // ends the token, so the copy into a std::string that used to precede it bought nothing.  (std::from_chars is no
 // alternative with this toolchain: libstdc++ 11 implements it as newlocale + strtod per call, slower and serialised on
 // the locale lock -- the parallel parse did not scale at all with it, profiles/r03/e_*.)
@@ -98,10 +102,23 @@ float parse_float(const char** tok) {
     const char* end = t + std::strcspn(t, " \t");
     *tok = end;
     if (t == end) return 0.0f;
-    char* e = nullptr;
-    const double d = std::strtod(t, &e);
-    if (e == t) return 0.0f;
-    return (float)d;
+    // the token's shape first, as the reference's grammar has it (tiny_obj_loader.h:437-443): [sign] digits [. [digits]]
+    // [e|E [sign] digits], read greedily; no digit after the sign, or an e / E without digits behind it, gives the default 0
+    // (`.5`, `nan`, `inf`, `1e`, `1e+`), and what follows a well-formed prefix is ignored (`1.5.3` is 1.5, `12abc` is 12).
+    // strtod agrees with that on every prefix but a hexadecimal one, which the grammar ends after its `0`.
+    const char* p = t;
+    if (*p == '+' || *p == '-') ++p;
+    const char* digits = p;
+    while (*p >= '0' && *p <= '9') ++p;
+    if (p == digits) return 0.0f;
+    if ((*p == 'x' || *p == 'X') && p == digits + 1 && *digits == '0') return *t == '-' ? -0.0f : 0.0f;
+    if (*p == '.') { ++p; while (*p >= '0' && *p <= '9') ++p; }
+    if (*p == 'e' || *p == 'E') {
+        ++p;
+        if (*p == '+' || *p == '-') ++p;
+        if (!(*p >= '0' && *p <= '9')) return 0.0f;
+    }
+    return (float)std::strtod(t, nullptr);
 }
 
 void parse_float3(float out[3], const char** tok) {
@@ -324,6 +341,7 @@ extern "C" int pt_add_obj(pt_context* ctx, const char* file, const float pos[3],
     const unsigned hw = std::thread::hardware_concurrency();
     const size_t n_pieces = std::max<size_t>(1, std::min<size_t>((size_t)std::min<unsigned>(hw ? hw : 1u, 16u) * 4, (size_t)(file_end - file_begin) >> 16));
     std::vector<Piece> pieces(n_pieces);
+    ctx->obj_pieces = (int)n_pieces;
     {
         char* start = file_begin;
         for (size_t k = 0; k < n_pieces; ++k) {

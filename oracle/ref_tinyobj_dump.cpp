@@ -1,7 +1,8 @@
 // ref_tinyobj_dump.cpp -- harness around the REFERENCE's own vendored parser
 // (/root/reference/tiny_obj_loader.h, compiled where it lies; nothing is copied).  It calls
 // tinyobj::LoadObj exactly like Scene::add_Obj does (main.cpp:553-558) and dumps what add_Obj
-// reads from the result (main.cpp:564-613) as JSON.  Used only by tests/golden/make_obj_golden.py
+// reads from the result (main.cpp:564-613) as JSON, and with it the normals, the texcoords and their per-corner
+// indices, which add_Obj drops and the product's reader keeps.  Used only by tests/golden/make_obj_golden.py
 // in the build container to produce fixtures for the product's own OBJ reader.
 #define TINYOBJLOADER_IMPLEMENTATION
 #include "tiny_obj_loader.h"
@@ -34,6 +35,10 @@ int main(int argc, char** argv) {
     jstr(err);
     std::printf(",\n \"vertices\": [");
     for (size_t i = 0; i < attrib.vertices.size(); ++i) std::printf("%s%.9g", i ? ", " : "", attrib.vertices[i]);
+    std::printf("],\n \"normals\": [");
+    for (size_t i = 0; i < attrib.normals.size(); ++i) std::printf("%s%.9g", i ? ", " : "", attrib.normals[i]);
+    std::printf("],\n \"texcoords\": [");
+    for (size_t i = 0; i < attrib.texcoords.size(); ++i) std::printf("%s%.9g", i ? ", " : "", attrib.texcoords[i]);
     std::printf("],\n \"materials\": [");
     for (size_t i = 0; i < materials.size(); ++i) {
         const tinyobj::material_t& m = materials[i];
@@ -62,6 +67,10 @@ int main(int argc, char** argv) {
         for (size_t f = 0; f < shapes[s].mesh.material_ids.size(); ++f) std::printf("%s%d", f ? ", " : "", shapes[s].mesh.material_ids[f]);
         std::printf("], \"vertex_index\": [");
         for (size_t k = 0; k < shapes[s].mesh.indices.size(); ++k) std::printf("%s%d", k ? ", " : "", shapes[s].mesh.indices[k].vertex_index);
+        std::printf("], \"normal_index\": [");
+        for (size_t k = 0; k < shapes[s].mesh.indices.size(); ++k) std::printf("%s%d", k ? ", " : "", shapes[s].mesh.indices[k].normal_index);
+        std::printf("], \"texcoord_index\": [");
+        for (size_t k = 0; k < shapes[s].mesh.indices.size(); ++k) std::printf("%s%d", k ? ", " : "", shapes[s].mesh.indices[k].texcoord_index);
         std::printf("]}");
     }
     std::printf("]}\n");
